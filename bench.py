@@ -24,7 +24,7 @@ timing  : W untimed warm-up steps, then EXACTLY K steps between (barrier +) torc
           stream events at the stage boundaries; the per-section HIP events behind `roofline` / `section_ms` are recorded in a
           THIRD run of the same K steps (primed; every 8th iteration), because a profiled iteration costs ~60 us of event
           records and pipeline bubbles.
-          `value_crop` (scene=survey runs only; --no-crop skips it) is ONE complete 1950-iteration fit, timed the same way, of the
+          `value_crop` (--full, scene=survey runs only; --no-crop skips it) is ONE complete 1950-iteration fit, timed the same way, of the
           crop-filling scene: the animal as large in the image as the reference's loaders deliver it (utils.py:5-36).  It does
           not scale with --steps: every fit starts from the reference's small initial mesh, so only a complete fit spends most
           of its iterations in that regime.
@@ -35,6 +35,12 @@ multi-GPU: `python bench.py --gpus N` launches N ranks itself (torch.distributed
           64-frame sequence is BASELINE.json's config 4), see smalify_amd/distributed.py.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the cold K-step fit behind `value` / `ms_per_step` and prints the line.  `--full` adds
+everything else the line can carry: `value_primed`, the profiled run behind `section_ms` / `roofline`, `value_crop` (scene=survey;
+--no-crop skips it), and with one rank `cpu_baseline` and `final_loss_vs_ref` (--no-cpu-baseline skips them).
+`--dump-outputs DIR` writes what the timed fit returns after its last step -- the fitted parameters and the loss terms -- as
+float32 DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 SMALFIT_BENCH_FORCE_DIST=1 (validation hook): run the sharded step with its all-gather even when the world is one
 rank, so that the RCCL path can be exercised on a single-GPU box.
@@ -244,6 +250,24 @@ def final_loss_parity(torch):
     return keep
 
 
+def dump_outputs(out_dir, base, losses, rank, world):
+    """--dump-outputs: what the timed fit hands its caller after its last step -- the fitted parameters (the per-frame ones over
+    all frames, gathered from the ranks) and the loss terms -- as float32 DIR/<name>.npy (about 30 KB; rank 0 writes)"""
+    import torch.distributed as dist
+    arrays = {k: v.detach().cpu().numpy() for k, v in base.p.items()}
+    if world > 1:
+        per_frame = [k for k, v in arrays.items() if v.ndim > 1]       # joint_rotations, global_rotation, trans (+ per-frame scales)
+        parts = [None] * world
+        dist.all_gather_object(parts, {k: arrays[k] for k in per_frame})
+        for k in per_frame:
+            arrays[k] = np.concatenate([p[k] for p in parts])
+    arrays["losses"] = losses.detach().cpu().numpy()
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -266,8 +290,13 @@ def main():
     ap.add_argument("--steps", type=int, default=390)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--scene", default="survey", choices=["survey", "crop"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-crop", action="store_true", help="skip the second timed scene (value_crop: one complete 1950-iteration fit, ~3 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: value_primed, the profiled run behind section_ms / "
+                         "roofline, value_crop (scene=survey), cpu_baseline and final_loss_vs_ref")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and final_loss_vs_ref")
+    ap.add_argument("--no-crop", action="store_true", help="with --full: skip the second timed scene (value_crop: one complete 1950-iteration fit, ~3 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed fit returns after its last step (fitted parameters, loss terms) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -305,7 +334,7 @@ def main():
     gt, tj, vis, tsil, shape_prior = build_problem(full_engine, torch, args.scene)
     # the second scene the line reports: the animal filling the crop, as the reference's loaders deliver it (utils.py:5-36
     # crop_to_silhouette, called at data_loader.py:48,117) -- `value_crop`; the headline stays BASELINE.md section 4's draw
-    crop_targets = build_problem(full_engine, torch, "crop")[1:4] if args.scene == "survey" and not args.no_crop else None
+    crop_targets = build_problem(full_engine, torch, "crop")[1:4] if args.full and args.scene == "survey" and not args.no_crop else None
     lo, hi = distributed.shard_range(NUM_FRAMES, rank, world, WINDOW)      # any contiguous split: the engine is told where it sits
     if world > 1:
         del full_engine
@@ -396,25 +425,28 @@ def main():
                     status=base.e.status(), fitter=fitter, base=base)
 
     cold = timed(primed=False)                       # -> value
-    primed = timed(primed=True)                      # -> value_primed
-    profiled = timed(primed=True, sections=True)     # -> section_ms / roofline (not a quoted rate)
-    # -> value_crop: one COMPLETE fit (the reference's 150/400/600/800 iterations) on the crop-filling scene, timed the same way.
-    # A K-step window cannot show this scene: every fit starts from the reference's initial state (translation 0: the animal a
-    # third of the image wide), and only as it converges on its targets does the mesh grow to fill the crop -- the regime most of
-    # a BADJA fit runs in.  K = 1950 is the shortest window that contains it as a real fit does.
-    crop_cold = crop_profiled = None
-    if crop_targets is not None:
-        crop_cold = timed(primed=False, targets=crop_targets, schedule=list(SCHEDULE_ITERS))
-        crop_profiled = timed(primed=False, sections=True, targets=crop_targets, schedule=list(SCHEDULE_ITERS))
+    primed = profiled = crop_cold = crop_profiled = None
+    if args.full:
+        primed = timed(primed=True)                      # -> value_primed
+        profiled = timed(primed=True, sections=True)     # -> section_ms / roofline (not a quoted rate)
+        # -> value_crop: one COMPLETE fit (the reference's 150/400/600/800 iterations) on the crop-filling scene, timed the same way.
+        # A K-step window cannot show this scene: every fit starts from the reference's initial state (translation 0: the animal a
+        # third of the image wide), and only as it converges on its targets does the mesh grow to fill the crop -- the regime most of
+        # a BADJA fit runs in.  K = 1950 is the shortest window that contains it as a real fit does.
+        if crop_targets is not None:
+            crop_cold = timed(primed=False, targets=crop_targets, schedule=list(SCHEDULE_ITERS))
+            crop_profiled = timed(primed=False, sections=True, targets=crop_targets, schedule=list(SCHEDULE_ITERS))
     elapsed, t_issued, stage_seconds, status = (cold[k] for k in ("elapsed", "t_issued", "stage_seconds", "status"))
-    sections = profiled["sections"]
-    status |= primed["status"] | profiled["status"]
-    if crop_cold is not None:
-        status |= crop_cold["status"] | crop_profiled["status"]
+    for r in (primed, profiled, crop_cold, crop_profiled):
+        if r is not None:
+            status |= r["status"]
     fitter, base = cold["fitter"], cold["base"]
-    final_losses = (fitter.global_losses() if use_dist else base.losses).cpu().numpy().tolist()
+    losses = fitter.global_losses() if use_dist else base.losses
+    final_losses = losses.cpu().numpy().tolist()
     import hashlib
     state_sha = hashlib.sha256(base.flat.cpu().numpy().tobytes() + base.losses.cpu().numpy().tobytes()).hexdigest()[:16]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, base, losses, rank, world)
 
     world_proof = None
     if use_dist:
@@ -424,20 +456,13 @@ def main():
     if rank == 0:
         V, F, S = md.num_verts, md.num_faces, IMAGE_SIZE
         nloc = hi - lo
-        sec_ms = {k: (v[0] / v[1] if v[1] else None) for k, v in sections.items()}
-        # dominant kernel: whichever rasteriser kernel has the largest average launch time in this run (HIP events
-        # around that kernel alone).  Algorithmic bytes per launch of the two face sweeps: the
+        # Algorithmic bytes per launch of the two face sweeps: the
         # frame's projected vertices (12 V per frame) and the faces (12 F) in, the per-pixel sums / per-face adjoints
         # are intermediates.  The target silhouette belongs to the resolve kernel, which reads it.
         algo = {"raster_sweep": nloc * 12 * V + 12 * F, "raster_bwd": nloc * 12 * V + 12 * F + nloc * 24 * F,
                 "raster_select": nloc * 12 * V + 12 * F, "raster_resolve": nloc * 4 * S * S}
         kernel_of = {"raster_sweep": "raster_sweep_kernel", "raster_select": "raster_select_kernel",
                      "raster_resolve": "raster_resolve_kernel", "raster_bwd": "raster_bwd_kernel"}
-        cand = {k: sec_ms[k] for k in kernel_of if sec_ms.get(k)}
-        dom_name = max(cand, key=cand.get) if cand else None
-        dom = cand.get(dom_name) if dom_name else None
-        algo_bytes = algo.get(dom_name)
-        achieved = algo_bytes / (dom * 1e-3) / 1e9 if dom else None
         def issue_and_traffic(kernel, launch_ms, algo, summary_path):
             """`roofline.issue`: how busy the vector ALUs were -- vector wave-instructions per launch (SQ_INSTS_VALU of the committed PMC
             summary) x the 2 cycles a full-rate wave64 instruction occupies a SIMD (/opt/skills/guides/MI355X_MICROARCH.md, "Per-instruction
@@ -468,14 +493,10 @@ def main():
             return out_i, traffic_, src
 
         ms_per_step = 1e3 * elapsed / args.steps
-        issue, traffic, traffic_source = issue_and_traffic(kernel_of.get(dom_name), dom, algo_bytes, PMC_SUMMARY_CROP if args.scene == "crop" else PMC_SUMMARY) if dom_name else (None, None, None)
-        iter_bytes = 2 * 16442644 + NUM_FRAMES * (4 * S * S + 3324)            # 49.88 MB / iteration
         out = {
             "metric": "fitter iterations/sec", "value": args.steps / elapsed, "unit": "iterations/s",
-            "value_primed": args.steps / primed["elapsed"], "ms_per_step_primed": 1e3 * primed["elapsed"] / args.steps,
             "value_definition": "value: cold rasteriser cache (a fit of a new sequence, first exact K-nearest selection and the host-side "
-                                "set-up of every stage's argument block inside the timed region); value_primed: same K steps timed again after one untimed silhouette evaluation of "
-                                "the initial state (a K-step window inside a long fit)",
+                                "set-up of every stage's argument block inside the timed region)",
             "n_gpus": world, "steps": args.steps, "warmup": n_warm, "warmup_requested": args.warmup,
             "ms_per_step": ms_per_step, "host_issue_ms_per_step": 1e3 * t_issued / args.steps,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
@@ -486,20 +507,36 @@ def main():
                        "frames": NUM_FRAMES, "image_size": S, "window": WINDOW, "parallelism": "frames/%d" % world},
             "per_stage_iterations_per_s": {"stage%d" % i: (sched[i] / stage_seconds[i] if stage_seconds[i] > 0 and sched[i] else None)
                                            for i in range(len(sched))},
-            "per_stage_iterations_per_s_primed": {"stage%d" % i: (sched[i] / primed["stage_seconds"][i] if primed["stage_seconds"][i] > 0 and sched[i] else None)
-                                                  for i in range(len(sched))},
-            "roofline": {"bound": "hbm", "bound_note": "HBM is the contract's yardstick; this kernel is bound by vector issue and waits: see `issue`", "kernel": kernel_of.get(dom_name), "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
-                         "traffic_source": traffic_source, "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_ms": dom,
-                         "issue": issue,
-                         # whole iteration, whole job: SURVEY.md section 8d's byte formula over the measured step, against N x peak
-                         "iteration": {"algorithmic_bytes": iter_bytes, "achieved": iter_bytes / (ms_per_step * 1e-3) / 1e9,
-                                       "frac": iter_bytes / (ms_per_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world)}},
-            "section_ms": sec_ms, "section_ms_source": "third run of the same steps (primed, HIP events on every %dth iteration): %.1f it/s with the events in"
-                                                     % (PROFILE_STRIDE, args.steps / profiled["elapsed"]),
             "final_losses": dict(zip(eng.LOSS_NAMES, final_losses)), "status_bits": status,
             "final_state_sha256": state_sha, "kernel_source_sha": kernel_source_sha(),
         }
+        if args.full:
+            sec_ms = {k: (v[0] / v[1] if v[1] else None) for k, v in profiled["sections"].items()}
+            # dominant kernel: whichever rasteriser kernel has the largest average launch time in this run (HIP events
+            # around that kernel alone)
+            cand = {k: sec_ms[k] for k in kernel_of if sec_ms.get(k)}
+            dom_name = max(cand, key=cand.get) if cand else None
+            dom = cand.get(dom_name) if dom_name else None
+            algo_bytes = algo.get(dom_name)
+            achieved = algo_bytes / (dom * 1e-3) / 1e9 if dom else None
+            issue, traffic, traffic_source = issue_and_traffic(kernel_of.get(dom_name), dom, algo_bytes, PMC_SUMMARY_CROP if args.scene == "crop" else PMC_SUMMARY) if dom_name else (None, None, None)
+            iter_bytes = 2 * 16442644 + NUM_FRAMES * (4 * S * S + 3324)            # 49.88 MB / iteration
+            out["value_definition"] += ("; value_primed: same K steps timed again after one untimed silhouette evaluation of "
+                                        "the initial state (a K-step window inside a long fit)")
+            out.update({
+                "value_primed": args.steps / primed["elapsed"], "ms_per_step_primed": 1e3 * primed["elapsed"] / args.steps,
+                "per_stage_iterations_per_s_primed": {"stage%d" % i: (sched[i] / primed["stage_seconds"][i] if primed["stage_seconds"][i] > 0 and sched[i] else None)
+                                                      for i in range(len(sched))},
+                "roofline": {"bound": "hbm", "bound_note": "HBM is the contract's yardstick; this kernel is bound by vector issue and waits: see `issue`", "kernel": kernel_of.get(dom_name), "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
+                             "traffic_source": traffic_source, "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_ms": dom,
+                             "issue": issue,
+                             # whole iteration, whole job: SURVEY.md section 8d's byte formula over the measured step, against N x peak
+                             "iteration": {"algorithmic_bytes": iter_bytes, "achieved": iter_bytes / (ms_per_step * 1e-3) / 1e9,
+                                           "frac": iter_bytes / (ms_per_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world)}},
+                "section_ms": sec_ms, "section_ms_source": "third run of the same steps (primed, HIP events on every %dth iteration): %.1f it/s with the events in"
+                                                         % (PROFILE_STRIDE, args.steps / profiled["elapsed"]),
+            })
         if use_dist:
             out["world_proof"] = world_proof        # rank stamps gathered through the loop's own collective; ncclCommCount / ncclCommUserRank
             if collective_fallback is not None:
@@ -523,7 +560,7 @@ def main():
                 ach = algo[dk] / (cc[dk] * 1e-3) / 1e9
                 out["roofline_crop"] = {"bound": "hbm", "kernel": kernel_of[dk], "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
                                         "traffic": ct, "traffic_source": cs, "algorithmic_bytes_per_launch": algo[dk], "avg_launch_ms": cc[dk], "issue": ci}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(md, pose_prior, shape_prior, tj.cpu().numpy(), vis.cpu().numpy(), tsil.cpu().numpy(), W)
             out["final_loss_vs_ref"] = final_loss_parity(torch)
         line = json.dumps(out)

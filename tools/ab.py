@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """developer helper (GPU box): A/B of library variants built with tools/build_variant.sh (or by hand into smalify_amd/_variants/).
 usage: python tools/ab.py [--steps K] [--reps R] [--scene survey|crop] NAME [NAME ...]      NAME = 'main' (smalify_amd/libsmalfit.so) or a variant name
-Runs bench.py per variant (SMALFIT_LIB) and prints value / value_primed / per-stage rates / the raster sections and the
+Runs bench.py --full per variant (SMALFIT_LIB) and prints value / value_primed / per-stage rates / the raster sections and the
 sha256 of the final parameters + losses -- equal hashes = bit-identical fits."""
 import json
 import os
@@ -25,7 +25,7 @@ for name in args:
     if name != "main":
         env["SMALFIT_LIB"] = os.path.join(ROOT, "smalify_amd", "_variants", name + ".so")
     for _ in range(reps):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--no-cpu-baseline", "--no-crop", "--scene", scene], env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--no-cpu-baseline", "--no-crop", "--scene", scene], env=env, capture_output=True, text=True)
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode != 0 or not lines:
             print("%-12s FAILED rc=%d %s" % (name, out.returncode, out.stderr[-400:]))

@@ -3,11 +3,12 @@
 # FETCH_SIZE / WRITE_SIZE are in KiB summed over the L2 memory-side requests; on gfx950 FETCH_SIZE reports half of a
 # wide coalesced read stream (MI355X_MICROARCH.md §HBM) -- the summary keeps raw values and states the correction.
 set -e
+repo=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_r1
 mkdir -p $OUT
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o pmc -- python $GRAFT_REPO_ROOT/bench.py --steps 39 --warmup 4 --no-cpu-baseline > $OUT/fetch.json 2> $OUT/fetch.err || true
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o pmc -- python $GRAFT_REPO_ROOT/bench.py --steps 39 --warmup 4 --no-cpu-baseline > $OUT/write.json 2> $OUT/write.err || true
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o pmc -- python $repo/bench.py --full --steps 39 --warmup 4 --no-cpu-baseline > $OUT/fetch.json 2> $OUT/fetch.err || true
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o pmc -- python $repo/bench.py --full --steps 39 --warmup 4 --no-cpu-baseline > $OUT/write.json 2> $OUT/write.err || true
 python - <<PY
 import csv, glob, collections, json
 out = {}
