@@ -2,30 +2,25 @@
 
 // ------------------------------------------------------------------------------------------------
 // K6: vertex adjoint: gather raster grads of incident faces, camera adjoint, joint-regressor adjoint,
-//     skinning adjoint wrt v_posed.   block = 256 vertices x FRB frames
+//     skinning adjoint wrt v_posed.   block = 256 vertices of one frame
 // ------------------------------------------------------------------------------------------------
-template <int FRB>
 __global__ void __launch_bounds__(256)
 vertex_bwd_kernel(ModelDev m, int M, const float* __restrict__ proj, const float* __restrict__ dface,
                   const float* __restrict__ dJ41 /*[M][41][3] or null*/,
                   const float* __restrict__ dverts_ext /*[M][3][Vp] extra world-space adjoint or null*/,
                   const float* __restrict__ Am, float* __restrict__ dvert /*[M][3][Vp]*/,
                   float* __restrict__ dvp /*[M][3][Vp]*/, float* __restrict__ dtr_part /*[VT][M][3]*/) {
-  __shared__ float As[FRB][420];
-  __shared__ float dJs[FRB][123];
+  __shared__ float As[420];
+  __shared__ float dJs[123];
   __shared__ float red[16];
   const int Vp = m.Vp;
   PHASE_MARK(pv0);
   // Frame -> XCD affinity (round 6, like the rasteriser kernels: workgroups are dealt to the 8 XCDs round-robin by linear id, every XCD
   // has its own L2): with one frame per workgroup and a 1-D grid, frame n runs on XCD n % 8 -- where raster_bwd_kernel left the
   // frame's face adjoints and where lbs_bwd_mid_kernel's dA blocks and chain_bwd_kernel's frame block will read what this kernel writes.
-  int vblock = blockIdx.x, n0 = blockIdx.y * FRB;
-#ifndef SMALFIT_NO_LBS_XCD
-  if (FRB == 1 && gridDim.y == 1) {
-    xcd_block(Vp / 256, n0, vblock);
-    if (n0 >= M) return;
-  }
-#endif
+  int n, vblock;
+  xcd_block(Vp / 256, n, vblock);
+  if (n >= M) return;
   const int v = vblock * 256 + threadIdx.x;
   // Round 6: everything whose address depends on the vertex alone -- the range of its incident (face, corner) list and the list's
   // first entries -- is requested BEFORE the transforms are staged and the workgroup meets at the barrier: behind it the chain
@@ -34,94 +29,84 @@ vertex_bwd_kernel(ModelDev m, int M, const float* __restrict__ proj, const float
   const int vc = min(v, m.V - 1);
   const int vf0 = m.vf_off[vc], vf1 = (v < m.V) ? m.vf_off[vc + 1] : vf0;
   int vfi[kPre];
+  // (clamped: unconditional loads, see tools/isa_loads.py; an empty list at the end reads the zero entry smalfit_model_create pads vf_idx with)
 #pragma unroll
-  for (int q = 0; q < kPre; ++q) vfi[q] = m.vf_idx[min(vf0 + q, max(vf1 - 1, vf0))];      // (clamped: unconditional loads, see tools/isa_loads.py)
-  for (int i = threadIdx.x; i < FRB * 420; i += 256) {
-    const int f = i / 420;
-    As[f][i % 420] = (n0 + f < M) ? Am[(size_t)(n0 + f) * 420 + (i % 420)] : 0.f;
-  }
-  for (int i = threadIdx.x; i < FRB * 123; i += 256) {
-    const int f = i / 123;
-    dJs[f][i % 123] = (dJ41 && n0 + f < M) ? dJ41[(size_t)(n0 + f) * 123 + (i % 123)] : 0.f;
-  }
+  for (int q = 0; q < kPre; ++q) vfi[q] = m.vf_idx[min(vf0 + q, max(vf1 - 1, vf0))];
+  for (int i = threadIdx.x; i < 420; i += 256) As[i] = Am[(size_t)n * 420 + i];
+  for (int i = threadIdx.x; i < 123; i += 256) dJs[i] = dJ41 ? dJ41[(size_t)n * 123 + i] : 0.f;
   __syncthreads();
   int lm = -1;
 #pragma unroll
   for (int i = 0; i < 6; ++i) if (v == m.landmarks[i]) lm = i;
   const bool live = v < m.V;
-  for (int f = 0; f < FRB; ++f) {
-    const int n = n0 + f;
-    if (n >= M) break;
-    float g[3] = {0.f, 0.f, 0.f};       // adjoint of translated world vertex (raster path)
-    if (live && dface) {
-      float gxn = 0.f, gyn = 0.f;
-      const float2* df = reinterpret_cast<const float2*>(dface + (size_t)n * m.F * 6);     // (x, y) adjoint of every face corner: one 8-byte gather each
-      float2 gq[kPre];
+  float g[3] = {0.f, 0.f, 0.f};         // adjoint of translated world vertex (raster path)
+  if (live && dface) {
+    float gxn = 0.f, gyn = 0.f;
+    const float2* df = reinterpret_cast<const float2*>(dface + (size_t)n * m.F * 6);     // (x, y) adjoint of every face corner: one 8-byte gather each
+    float2 gq[kPre];
 #pragma unroll
-      for (int q = 0; q < kPre; ++q) gq[q] = df[vfi[q]];                                   // (all in flight together; entries past the list repeat its last)
+    for (int q = 0; q < kPre; ++q) gq[q] = df[vfi[q]];                                   // (all in flight together; entries past the list repeat its last)
 #pragma unroll
-      for (int q = 0; q < kPre; ++q)
-        if (vf0 + q < vf1) { gxn += gq[q].x; gyn += gq[q].y; }                             // same order as the list: the same bits
-      for (int i = vf0 + kPre; i < vf1; ++i) {
-        const float2 g2 = df[m.vf_idx[i]];           // face*3 + corner
-        gxn += g2.x;
-        gyn += g2.y;
-      }
-      const float* pv = proj + (size_t)n * 3 * Vp;
-      world_to_ndc_bwd(pv[v], pv[Vp + v], pv[2 * Vp + v], gxn, gyn, g[0], g[1], g[2]);
+    for (int q = 0; q < kPre; ++q)
+      if (vf0 + q < vf1) { gxn += gq[q].x; gyn += gq[q].y; }                             // same order as the list: the same bits
+    for (int i = vf0 + kPre; i < vf1; ++i) {
+      const float2 g2 = df[m.vf_idx[i]];           // face*3 + corner
+      gxn += g2.x;
+      gyn += g2.y;
     }
-    if (live && dverts_ext) {
+    const float* pv = proj + (size_t)n * 3 * Vp;
+    world_to_ndc_bwd(pv[v], pv[Vp + v], pv[2 * Vp + v], gxn, gyn, g[0], g[1], g[2]);
+  }
+  if (live && dverts_ext) {
 #pragma unroll
-      for (int a = 0; a < 3; ++a) g[a] += dverts_ext[((size_t)n * 3 + a) * Vp + v];
-    }
-    // translation adjoint: sum over vertices of the translated-vertex adjoint
-    {
-      const float s0 = wave_sum(live ? g[0] : 0.f), s1 = wave_sum(live ? g[1] : 0.f), s2 = wave_sum(live ? g[2] : 0.f);
-      __syncthreads();                               // red[] of the previous frame has been consumed
-      if ((threadIdx.x & 63) == 0) { float* q = &red[(threadIdx.x >> 6) * 4]; q[0] = s0; q[1] = s1; q[2] = s2; }
-      __syncthreads();
-      if (threadIdx.x < 3)
-        dtr_part[((size_t)vblock * M + n) * 3 + threadIdx.x] =
-            ((red[threadIdx.x] + red[4 + threadIdx.x]) + red[8 + threadIdx.x]) + red[12 + threadIdx.x];
-    }
-    // joints = J_regressor^T verts  (+ landmark picks)
-    float dv[3] = {g[0], g[1], g[2]};
-    if (live) {
+    for (int a = 0; a < 3; ++a) g[a] += dverts_ext[((size_t)n * 3 + a) * Vp + v];
+  }
+  // translation adjoint: sum over vertices of the translated-vertex adjoint
+  {
+    const float s0 = wave_sum(live ? g[0] : 0.f), s1 = wave_sum(live ? g[1] : 0.f), s2 = wave_sum(live ? g[2] : 0.f);
+    if ((threadIdx.x & 63) == 0) { float* q = &red[(threadIdx.x >> 6) * 4]; q[0] = s0; q[1] = s1; q[2] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+      dtr_part[((size_t)vblock * M + n) * 3 + threadIdx.x] =
+          ((red[threadIdx.x] + red[4 + threadIdx.x]) + red[8 + threadIdx.x]) + red[12 + threadIdx.x];
+  }
+  // joints = J_regressor^T verts  (+ landmark picks)
+  float dv[3] = {g[0], g[1], g[2]};
+  if (live) {
 #pragma unroll 4
-      for (int e = 0; e < m.Kj; ++e) {
-        const int j = m.jrv_j[e * Vp + v];
-        const float c = m.jrv_val[e * Vp + v];
+    for (int e = 0; e < m.Kj; ++e) {
+      const int j = m.jrv_j[e * Vp + v];
+      const float c = m.jrv_val[e * Vp + v];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) dv[a] = fmaf(c, dJs[f][j * 3 + a], dv[a]);
-      }
-      if (lm >= 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) dv[a] += dJs[f][(35 + lm) * 3 + a];
-      }
+      for (int a = 0; a < 3; ++a) dv[a] = fmaf(c, dJs[j * 3 + a], dv[a]);
     }
-    // skinning: vert = T.R vp + T.t  ->  dvp = T.R^T dv
-    float T[9];
+    if (lm >= 0) {
 #pragma unroll
-    for (int e = 0; e < 9; ++e) T[e] = 0.f;
-    if (live) {
+      for (int a = 0; a < 3; ++a) dv[a] += dJs[(35 + lm) * 3 + a];
+    }
+  }
+  // skinning: vert = T.R vp + T.t  ->  dvp = T.R^T dv
+  float T[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) T[e] = 0.f;
+  if (live) {
 #pragma unroll 4
-      for (int e = 0; e < m.Kw; ++e) {
-        const int j = m.w_j[e * Vp + v];
-        const float wv = m.w_val[e * Vp + v];
-        const float* A = &As[f][j * 12];
+    for (int e = 0; e < m.Kw; ++e) {
+      const int j = m.w_j[e * Vp + v];
+      const float wv = m.w_val[e * Vp + v];
+      const float* A = &As[j * 12];
 #pragma unroll
-        for (int a = 0; a < 3; ++a)
+      for (int a = 0; a < 3; ++a)
 #pragma unroll
-          for (int b = 0; b < 3; ++b) T[a * 3 + b] = fmaf(wv, A[a * 4 + b], T[a * 3 + b]);
-      }
+        for (int b = 0; b < 3; ++b) T[a * 3 + b] = fmaf(wv, A[a * 4 + b], T[a * 3 + b]);
     }
+  }
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const float o = T[b] * dv[0] + T[3 + b] * dv[1] + T[6 + b] * dv[2];
-      if (v < Vp) {
-        dvp[((size_t)n * 3 + b) * Vp + v] = live ? o : 0.f;
-        dvert[((size_t)n * 3 + b) * Vp + v] = live ? dv[b] : 0.f;
-      }
+  for (int b = 0; b < 3; ++b) {
+    const float o = T[b] * dv[0] + T[3 + b] * dv[1] + T[6 + b] * dv[2];
+    if (v < Vp) {
+      dvp[((size_t)n * 3 + b) * Vp + v] = live ? o : 0.f;
+      dvert[((size_t)n * 3 + b) * Vp + v] = live ? dv[b] : 0.f;
     }
   }
   PHASE_MARK(pv1);
@@ -172,8 +157,8 @@ dbeta_block(const ModelDev& m, int M, int nb, int shared, int bx, int by, int bz
     if (shared) {       // frames are split over bz
       const int per = (M + gzn - 1) / gzn;
       const int n0 = bz * per, n1 = min(M, n0 + per);
-      // (summed in double, rounded once: the frames' adjoints of one column largely cancel in a fit that has settled, and the
-      // gradient the ranks exchange is what is left -- round 6, with the assembly's sums below)
+      // (summed in double, rounded once: the frames' adjoints of one column largely cancel in a fit that has settled -- round 6, with
+      // the assembly's sums below, which measured no different from float32 sums)
       double gd = 0.0;
 #pragma unroll 8
       for (int n = n0; n < n1; ++n) gd += (double)dvp[(size_t)n * ncol + c];
@@ -213,16 +198,7 @@ dbeta_block(const ModelDev& m, int M, int nb, int shared, int bx, int by, int bz
 // `posedirs` is read once per evaluation instead of once per tile (round 2: 119 MB counted for a 14.3 MB basis) -- and the
 // column range is a quarter as long instead (24 splits instead of 6: the same number of blocks, the same number of matrix
 // instructions per wave, a quarter of the B loads and half the dependent load batches).
-#ifndef SMALFIT_PBM_SPLITS
-#define SMALFIT_PBM_SPLITS 24
-#endif
-#ifndef SMALFIT_PBM_U
-#define SMALFIT_PBM_U 2
-#endif
-#ifndef SMALFIT_PBM_TILES
-#define SMALFIT_PBM_TILES 4
-#endif
-constexpr int PBM_SPLITS = SMALFIT_PBM_SPLITS, PBM_U = SMALFIT_PBM_U, PBM_TILES = SMALFIT_PBM_TILES;
+constexpr int PBM_SPLITS = 24, PBM_U = 2, PBM_TILES = 4;
 static_assert(PBM_SPLITS % 8 == 0, "the blocks of a column split are placed on one XCD (ids in chunks of 8 splits)");
 __device__ __forceinline__ void
 poseblend_bwd_mfma_block(const ModelDev& m, int M, int tchunk, int kpair, int split, const float* __restrict__ dvp,
@@ -294,24 +270,19 @@ poseblend_bwd_mfma_block(const ModelDev& m, int M, int tchunk, int kpair, int sp
 }
 
 // everything between the vertex adjoint and the chain adjoint in ONE launch (the parts are independent and each is
-// latency-bound on its own): the pose-blend adjoint (4 waves = 4 tiles per block), 35 x M blocks dA_j, then (optionally)
-// the shape-blend adjoint partials.
+// latency-bound on its own): the pose-blend adjoint (4 waves = 4 tiles per block), then 35 x M blocks dA_j.  (The shape-blend
+// adjoint partials ride on chain_bwd_kernel.)
 // Block -> XCD placement of the pose-blend part (round 3).  Workgroups are dealt to the 8 XCDs round-robin by linear id and
 // every XCD has its own L2.  The 10 feature-pair blocks of one column split read the same columns of dvp (A): their ids are
 // laid out as chunks of 8 splits x 10 feature pairs with the split in the low 3 bits, so they share an XCD and that slice of
 // dvp is fetched once; every element of `posedirs` (B) is fetched by exactly one block per chunk of PBM_TILES frame tiles.
 // Speed only: results never depend on the placement.
 __host__ __device__ inline int mid_pb_ids(int M) { return 10 * PBM_SPLITS * (((M + 15) / 16 + PBM_TILES - 1) / PBM_TILES); }
-#ifndef SMALFIT_NO_LBS_XCD
 __host__ __device__ inline int mid_da_ids(int M) { return xcd_grid(35, M); }       // dA blocks: frame n on XCD n % 8 (see vertex_bwd_kernel)
-#else
-__host__ __device__ inline int mid_da_ids(int M) { return 35 * M; }
-#endif
-__host__ __device__ inline int mid_grid(int M, int nPB, int n_db) { return (nPB ? mid_pb_ids(M) : 0) + mid_da_ids(M) + n_db; }
+__host__ __device__ inline int mid_grid(int M, int nPB) { return (nPB ? mid_pb_ids(M) : 0) + mid_da_ids(M); }
 __global__ void __launch_bounds__(256, 4)      // <= 128 registers (vector + accumulation): four workgroups per CU for the 35 M dA blocks
-lbs_bwd_mid_kernel(ModelDev m, int M, int CS, int nb, int betas_shared, int nPB, int nDB_x, int nDB_y, int nDB_z,
-                   const float* __restrict__ dvert, const float* __restrict__ vposed, const float* __restrict__ dvp,
-                   float* __restrict__ dA, float* __restrict__ dpf_part, float* __restrict__ dbeta_part) {
+lbs_bwd_mid_kernel(ModelDev m, int M, int nPB, const float* __restrict__ dvert, const float* __restrict__ vposed,
+                   const float* __restrict__ dvp, float* __restrict__ dA, float* __restrict__ dpf_part) {
   __shared__ float part[4][32];
   __shared__ float tile_red[4][8][64];
   int blk = blockIdx.x;
@@ -328,20 +299,12 @@ lbs_bwd_mid_kernel(ModelDev m, int M, int CS, int nb, int betas_shared, int nPB,
     }
     blk -= ids;
   }
-  if (blk < mid_da_ids(M)) {
-    PHASE_MARK(pd0);
-    int n = blk / 35, j = blk % 35;
-#ifndef SMALFIT_NO_LBS_XCD
-    xcd_block_of(blk, 35, n, j);          // (the pose-blend ids before these are a multiple of 8: blk % 8 is the workgroup's XCD)
-    if (n >= M) return;
-#endif
-    dA_block(m, j, n, dvert, vposed, dA, part);
-    PHASE_MARK(pd1); PHASE_END(PH_MID_DA, pd0, pd1);
-    return;
-  }
-  blk -= mid_da_ids(M);
-  if (blk < nDB_x * nDB_y * nDB_z)
-    dbeta_block(m, M, nb, betas_shared, blk % nDB_x, (blk / nDB_x) % nDB_y, blk / (nDB_x * nDB_y), nDB_x, nDB_z, dvp, dbeta_part, part);
+  PHASE_MARK(pd0);
+  int n, j;
+  xcd_block_of(blk, 35, n, j);            // (the pose-blend ids before these are a multiple of 8: blk % 8 is the workgroup's XCD)
+  if (n >= M) return;
+  dA_block(m, j, n, dvert, vposed, dA, part);
+  PHASE_MARK(pd1); PHASE_END(PH_MID_DA, pd0, pd1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -713,9 +676,9 @@ assemble_kernel(AssembleArgs a) {
       const int s = role;
       const int b = t % 20, slice = t / 20;
       // The shared-shape gradient is the sum of every frame's and every column block's partial, and in a fit that has settled those
-      // partials largely cancel: they are added in DOUBLE (round 6; fixed order as before) and rounded once -- the float32 partials
-      // themselves carry the information, a float32 running sum of a few dozen of them was losing it (config 3 after stage 1:
-      // d/d betas 9.8e-6, d/d log scales 3.6e-5 off the float64 oracle where a float32 torch evaluation is 3.0e-6 / 6.6e-6 off).
+      // partials largely cancel: they are added in DOUBLE (round 6; fixed order as before) and rounded once.  That is the principled
+      // sum, but it moved no printed digit: config 3 after stage 1 stays at d/d betas 9.86e-6, d/d log scales 3.64e-5 off the float64
+      // oracle, as with the float32 running sum (profiles/r6_gpu_tests.log, profiles/r6_eval_fixture_tables.txt).
       if (slice < 12 && b < a.nb) {
         double acc = 0.0;
         const int nlo = a.betas_shared ? 0 : s, nhi = a.betas_shared ? M : s + 1;

@@ -266,10 +266,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // wave w takes k-steps [20 w, 20 w + 20) -- ONE batch of operand loads, 60 matrix instructions -- the four partial tiles meet in LDS
 // and are added in wave order (fixed: deterministic), and wave w finishes frame 4 (lane >> 4) + w of its lanes' vertices: one
 // (vertex, frame) pair per lane for the skinning instead of four.  Four times the workgroups, a quarter of the chain each.
-#ifndef SMALFIT_SKIN_GROUPS
-#define SMALFIT_SKIN_GROUPS 2
-#endif
-constexpr int kSkinGroups = SMALFIT_SKIN_GROUPS;   // 16-vertex groups per workgroup (4 waves each): they share the staged transforms of the 16 frames
+constexpr int kSkinGroups = 2;                     // 16-vertex groups per workgroup (4 waves each): they share the staged transforms of the 16 frames
 constexpr int kSkinVerts = 16 * kSkinGroups;       // vertices per workgroup of skin_mfma_kernel
 constexpr int kSkinThreads = 256 * kSkinGroups;
 constexpr int kSkinStage = (16 * 105 + kSkinThreads - 1) / kSkinThreads;   // float4 words of the transforms a thread stages

@@ -77,55 +77,34 @@ __device__ __forceinline__ int wave_max_i(int v) {
 //   * kNoList: "evaluate the whole box" -- more than 1024 pixels, or the exact selection found one of the K nearest beyond the old
 //     far bound at a pixel of the box.
 constexpr int kListCap = 128;             // bytes per face in HBM: <= 128 indices, or 16 lanes x one 64-bit mask
-#ifndef SMALFIT_LIST_LDS
-#define SMALFIT_LIST_LDS 128              // with the 36 x 36 window the kernel's LDS is 19 984 bytes: eight workgroups per CU, like its 63 registers
-#endif
-constexpr int kListLds = SMALFIT_LIST_LDS;   // list entries per face staged in the sweep's LDS (longer lists go out as masks)
+// list entries per face staged in the sweep's LDS (longer lists go out as masks).  With the 36 x 36 window the kernel's LDS is
+// 19 984 bytes: eight workgroups per CU, like its 63 registers (checked in raster_sweep_kernel)
+constexpr int kListLds = 128;
 static_assert(kListLds <= kListCap && kListLds % 8 == 0, "lists are copied out in 8-byte pieces");
 constexpr int kMaskRounds = 64;           // rounds (of 16 pixels) a mask covers
 constexpr unsigned char kMaskList = 254;  // pcount: the face's 128 bytes hold the 16 masks
 constexpr unsigned char kNoList = 255;    // pcount: walk the whole box
 constexpr float kBoxSlack = 1.0f / 64.0f; // pixels added to each side of a face's pixel box (rounding guard)
 constexpr int kRectFaces = 8;             // faces per entry of the union-box index
-#ifndef SMALFIT_SEL_GROUPS
-#define SMALFIT_SEL_GROUPS 16
-#endif
-constexpr int kSelGroups = SMALFIT_SEL_GROUPS;   // ticket counters per XCD of the selection kernel (one per group of its workgroups)
+constexpr int kSelGroups = 16;            // ticket counters per XCD of the selection kernel (one per group of its workgroups)
 constexpr int kTicketBase = 64, kTicketStride = 16;   // in the queue-counter array: one counter per 64-byte line
 constexpr int kQCountInts = kTicketBase + 8 * kSelGroups * kTicketStride;
-#ifndef SMALFIT_SWEEP_FACES
-#define SMALFIT_SWEEP_FACES 32
-#endif
-#ifndef SMALFIT_ACC_WIN
-#define SMALFIT_ACC_WIN 36               // round 6 (was 32): see the zeroing loop of the sweep; 40 with 64-entry lists measured +4.1 % on the
-#endif                                   // crop-filling scene but -0.7 % on the headline one, 36 with full lists +3.1 % / -0.3 % (profiles/r6_ab_lists_window.txt)
-constexpr int kSweepFaces = SMALFIT_SWEEP_FACES;   // faces per sweep block
-constexpr int kAccWin = SMALFIT_ACC_WIN;  // LDS accumulator window edge (pixels); outside: global atomics
+constexpr int kSweepFaces = 32;           // faces per sweep block
+// LDS accumulator window edge (pixels); outside: global atomics.  Round 6 (was 32): see the zeroing loop of the sweep; 40 with 64-entry
+// lists measured +4.1 % on the crop-filling scene but -0.7 % on the headline one, 36 with full lists +3.1 % / -0.3 %
+// (profiles/r6_ab_lists_window.txt)
+constexpr int kAccWin = 36;
 constexpr int kCountShift = 50;
 constexpr float kLogFix = 16777216.0f;    // 2^24
 constexpr int kBandCap = 64;              // per-pixel list of candidates between the two cached depth bounds
 // (round 5: 24 / 40 / 12 instead of round 3's 30 / 50 / 16 -- with the sweep at its issue ceiling a band entry appended costs more than a
 // miss re-selected: +0.2 % / +0.6 % / +1.3 % on the 195-step run / the crop-filling fit / the 20-step window; 20 / 32 / 10 and 16 / 28 / 8
-// measured the same within noise, 36 / 60 / 20 worse: profiles/r5_ab_band_fill.txt)
-#ifndef SMALFIT_BAND_FILL
-#define SMALFIT_BAND_FILL 24
-#endif
-#ifndef SMALFIT_BAND_FILL_WIDE
-#define SMALFIT_BAND_FILL_WIDE 40      // round 3: 60 left 4 entries of headroom below kBandCap; 50 / half-width 4 measured best then (profiles/r3_ab_band_policy_*.txt)
-#endif
-#ifndef SMALFIT_BAND_FILL_NARROW
-#define SMALFIT_BAND_FILL_NARROW 12
-#endif
-constexpr int kBandFill = SMALFIT_BAND_FILL;   // the select kernel sizes the band to hold at most this many entries ...
-constexpr int kBandFillWide = SMALFIT_BAND_FILL_WIDE, kBandFillNarrow = SMALFIT_BAND_FILL_NARROW;   // ... or these, by miss rate
-#ifndef SMALFIT_BAND_STAGE
-#define SMALFIT_BAND_STAGE 64
-#endif
-constexpr int kBandStage = SMALFIT_BAND_STAGE;   // band entries staged per wave in the sweep before a batched append
-#ifndef SMALFIT_BAND_HALF
-#define SMALFIT_BAND_HALF 4.0f
-#endif
-constexpr float kBandHalf = SMALFIT_BAND_HALF;   // initial half-width of the band, in mean depth gaps of the K nearest
+// measured the same within noise, 36 / 60 / 20 worse: profiles/r5_ab_band_fill.txt.  Round 3: 60 left 4 entries of headroom below
+// kBandCap; 50 / half-width 4 measured best then, profiles/r3_ab_band_policy_*.txt)
+constexpr int kBandFill = 24;             // the select kernel sizes the band to hold at most this many entries ...
+constexpr int kBandFillWide = 40, kBandFillNarrow = 12;   // ... or these, by miss rate
+constexpr int kBandStage = 64;            // band entries staged per wave in the sweep before a batched append
+constexpr float kBandHalf = 4.0f;         // initial half-width of the band, in mean depth gaps of the K nearest
 
 // target silhouettes: float32 (M,S,S), or bytes b = 255 t (the masks the reference's loaders read are 8-bit images,
 // data_loader.py:43: a quarter of the target traffic).  b / 255 is a correctly rounded division: the value a float32
@@ -178,11 +157,7 @@ __device__ __forceinline__ unsigned long long pack_candidate(float d) {
   // pixel -- 2^(2^-25 c) - 1 ~ 2e-8 per candidate, 1-2e-6 with the 50-100 candidates of a pixel: a bias of one sign in every adjoint
   // seed and in the silhouette loss (the loss term was 7e-7 ... 3.6e-6 off the float64 oracle where a float32 torch evaluation is
   // 1e-7 ... 3e-7 off; the shared-shape gradient, which adds the frames' seeds up, 3-5 x a float32 evaluation's deviation)
-#ifdef SMALFIT_PACK_TRUNCATE
-  return (1ull << kCountShift) | (unsigned long long)(unsigned)(f * kLogFix);
-#else
   return (1ull << kCountShift) | (unsigned long long)(unsigned)fmaf(f, kLogFix, 0.5f);
-#endif
 }
 
 // p = sigmoid(-d / sigma) with the hardware exp2 / rcp (backward sweep)
@@ -281,9 +256,7 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
   int n, bxi;
   xcd_block_of((int)blockIdx.x - nfr, (m.F + 255) / 256, n, bxi);
   if (n >= M) return;
-#ifndef SMALFIT_BBOX_DIRECT_STORE
   __shared__ __attribute__((aligned(16))) float4 recs[256][kRecVecs];
-#endif
   const int f = bxi * 256 + threadIdx.x;
   const float* px = proj + (size_t)n * 3 * Vp;
   int2 box = make_int2(1, 1);     // c0=1 > c1=0 : empty
@@ -315,13 +288,8 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
       if (onscreen) box = make_int2((int)c0 | ((int)c1 << 16), (int)r0 | ((int)r1 << 16));
     }
     fbox[(size_t)n * m.F + f] = box;
-#ifdef SMALFIT_BBOX_DIRECT_STORE
-    store_face_rec(frec + ((size_t)n * m.F + f) * kRecVecs, r);
-#else
     store_face_rec(&recs[threadIdx.x][0], r);
-#endif
   }
-#ifndef SMALFIT_BBOX_DIRECT_STORE
   // The 256 records of the workgroup leave through LDS (round 6): written per face they are four 16-byte pieces at a 64-byte stride
   // per store instruction -- every 64-byte line is touched by four instructions -- while the workgroup's records are ONE contiguous
   // 16 KB run: four instructions of 256 x 16 consecutive bytes.
@@ -335,7 +303,6 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
       if (idx < nrec * kRecVecs) dst[idx] = recs[idx >> 2][idx & 3];
     }
   }
-#endif
   // union box of each group of kRectFaces consecutive faces (sub-wave shuffle reduction)
   const bool live = (box.x & 0xffff) <= (box.x >> 16);
   int x0 = live ? (box.x & 0xffff) : 0x7fff, x1 = live ? (box.x >> 16) : -1;
@@ -354,10 +321,7 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
 // integer (count << 50 | log sum); candidates in (lo, hi] are appended to the pixel's short band list; farther ones
 // are dropped.  raster_resolve_kernel proves from the counts that the K nearest are {<= lo} + the nearest few of the
 // band, or sends the pixel to the exact selection.
-#ifndef SMALFIT_SWEEP_MINWAVES
-#define SMALFIT_SWEEP_MINWAVES 1
-#endif
-__global__ void __launch_bounds__(256, SMALFIT_SWEEP_MINWAVES)
+__global__ void __launch_bounds__(256, 1)
 raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const int2* __restrict__ fbox, const int4* __restrict__ brect, const float* __restrict__ zc, const float2* __restrict__ zband,
                     unsigned long long* __restrict__ gacc /*[M][S*S]*/, unsigned* __restrict__ bcnt /*[M][S*S]*/,
                     float2* __restrict__ blist /*[M][S*S][kBandCap]*/, unsigned char* __restrict__ plist /*[M][F][kListCap]*/,
@@ -376,6 +340,8 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
   __shared__ int st_n[4];
   __shared__ __attribute__((aligned(8))) unsigned char lsts[kSweepFaces][kListLds];
   __shared__ int lcn[kSweepFaces];
+  static_assert(sizeof(raw) + sizeof(boxes) + sizeof(acc) + sizeof(st_e) + sizeof(st_p) + sizeof(st_n) + sizeof(lsts) + sizeof(lcn)
+                <= 160 * 1024 / 8, "eight sweep workgroups per CU (160 KB of LDS)");
   const int t = threadIdx.x;
   int n, bxi;
   xcd_block((F + kSweepFaces - 1) / kSweepFaces, n, bxi);
@@ -479,7 +445,6 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
     // crop-filling animal the bounds of eight resident windows no longer sit in the L1.  The index maths of the next round is formed
     // twice (here and at the top of that round: carrying it would take the kernel past 64 registers) -- eight more instructions per
     // round and still 3 % less time on both scenes (119.6 -> 115.6 us, 312.8 -> 305.0 us), bit-identical.
-#ifndef SMALFIT_NO_SWEEP_PREFETCH
     auto bounds_of = [&](float q) {
       const float ry = floorf(fmaf(q, ibw, hbw));
       const float rw = r0f + ry, cl = c0f + fmaf(-ry, bwf, q);
@@ -487,53 +452,32 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
     };
     float2 zb_next = make_float2(0.f, 0.f);
     if ((float)sub < npxf) zb_next = bounds_of((float)sub);
-#endif
-#ifdef SMALFIT_ABL_NOLOOP          // timing ablation (developer builds): no pixel loop at all
-    if (npx > 100000)
-#endif
     for (float qf = (float)sub; qf < npxf; qf += 16.0f, lbit <<= 1) {
       const float ryf = floorf(fmaf(qf, ibw, hbw));
       const float rowf = r0f + ryf, colf = c0f + fmaf(-ryf, bwf, qf);
       const unsigned boff = (unsigned)fmaf(rowf, s8, 8.0f * colf);      // byte offset of the pixel in an 8-byte-per-pixel plane (< 2^24)
-#ifdef SMALFIT_ABL_NOZB          // timing ablations (developer builds, results are wrong)
-      const float2 zb = make_float2(__int_as_float(0x7f800000), __int_as_float(0x7f800000));
-#elif !defined(SMALFIT_NO_SWEEP_PREFETCH)
       const float2 zb = zb_next;
       if (qf + 16.0f < npxf) zb_next = bounds_of(qf + 16.0f);
-#else
-      const float2 zb = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(zbp) + boff);
-#endif
       const float ppx = fmaf(colf, ndc_a, ndc_b), ppy = fmaf(rowf, ndc_a, ndc_b);
       const float rz = face_pixel_depth(rk, ppx, ppy) - zcn;   // depth relative to the frame reference
       SMALFIT_WORK(++ws_vis; ++ws_trips;)
-#ifdef SMALFIT_ABL_NOEVAL
-      if (rz > -1.0e30f) continue;
-#endif
       if (!(rz <= zb.y)) continue;                   // beyond the pixel's far bound: dropped whatever its distance
       SMALFIT_WORK(++ws_depth;)
       PixEval e;
       if (!face_pixel_candidate(rk, ppx, ppy, e.d)) continue;
       SMALFIT_WORK(++ws_eval;)
-#ifndef SMALFIT_ABL_NOBITS
-#ifndef SMALFIT_ABL_NOMASK
       lmask |= lbit;                                 // the face's candidates: as a mask ...
-#endif
       if (listed) {                                  // ... and as a list (the backward gather visits these pixels instead of the box)
         const int pos = atomicAdd(&lcn[k], 1);
         if (pos < kListLds) lsts[k][pos] = (unsigned char)(int)qf;
       }
-#endif
       if (rz <= zb.x) {
         SMALFIT_WORK(++ws_near;)
         const float lxf = colf - wx0f, lyf = rowf - wy0f;
-#ifdef SMALFIT_ABL_NOACC
-        if (e.d == 123.456f) acc[0] = pack_candidate(e.d);
-#else
         // (a block whose rectangle fits the window -- nearly all -- skips the per-pixel window test: `clip` is uniform)
         if (!clip || (fabsf(lxf - hwin) <= hwin && fabsf(lyf - hwin) <= hwin))
           atomicAdd(reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(acc) + (unsigned)fmaf(lyf, 8.0f * (float)kAccWin, 8.0f * lxf)), pack_candidate(e.d));
         else { atomicAdd(reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ga) + boff), pack_candidate(e.d)); SMALFIT_WORK(++ws_clipped;) }
-#endif
       } else {
         const int sl = atomicAdd(&st_n[wv], 1);
         if (sl < kBandStage) {
@@ -546,9 +490,6 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
         }
       }
     }
-#if defined(SMALFIT_ABL_NOBITS)
-    if (sub == 0) pcount[(size_t)n * F + f0 + k] = kNoList;
-#else
     {
       // (lane indices re-derived behind an opaque copy of the thread id: values that are only needed out here must not
       // occupy registers across the pixel loop -- the kernel sits at the 64-register occupancy step)
@@ -576,7 +517,6 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
       }
       if (sub2 == 0) pcount[fi] = flag;
     }
-#endif
   }
   SMALFIT_WORK(const unsigned long long ws_t3 = __builtin_amdgcn_s_memtime();)
   // the last band flush is split around the window flush: the list slots (returning global atomics, a full trip to the
@@ -600,12 +540,7 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
     const int lyw = i / kAccWin, lxw = i % kAccWin;
     if (lxw >= ww) continue;
     const unsigned long long v = acc[lyw * kAccWin + lxw];
-#ifdef SMALFIT_ABL_NOFLUSH
-    if (v == 0x123456789ull)
-#else
-    if (v)
-#endif
-    { atomicAdd(&ga[(wy0 + lyw) * S + wx0 + lxw], v); SMALFIT_WORK(++ws_flush;) }
+    if (v) { atomicAdd(&ga[(wy0 + lyw) * S + wx0 + lxw], v); SMALFIT_WORK(++ws_flush;) }
   }
   if (fslot < (unsigned)kBandCap) blist[fpi * kBandCap + fslot] = fe;
   SMALFIT_WORK(work_add(0, ws_vis); work_add(1, ws_depth); work_add(2, ws_eval); work_add(3, ws_near); work_add(7, ws_clipped); work_add(31, (lane == 0 && clip) ? 1 : 0);
@@ -640,10 +575,7 @@ __device__ __forceinline__ float alpha_from_log_sum(unsigned long long sum) {
 // depth tie at the cut -- raster_select_kernel redoes the pixel from scratch and refreshes its bounds.
 // raster_resolve_kernel is thread-per-pixel: it finishes the pixels that need no sorting and appends the others to
 // the band queue or the select queue (one global atomic per block and queue).
-#ifndef SMALFIT_RESOLVE_SUB
-#define SMALFIT_RESOLVE_SUB 2
-#endif
-constexpr int kResSub = SMALFIT_RESOLVE_SUB;     // a resolve workgroup takes (16 kResSub)^2 pixels, kResSub^2 per thread: the launch is
+constexpr int kResSub = 2;                       // a resolve workgroup takes (16 kResSub)^2 pixels, kResSub^2 per thread: the launch is
                                                   // bound by the number of workgroups, not by bytes
 constexpr int kResEdge = 16 * kResSub;
 __global__ void __launch_bounds__(256)
@@ -755,11 +687,7 @@ raster_resolve_kernel(int S, int M, WinMap win, float w_sil, unsigned long long*
       // 1.0f exactly whatever the remaining K - c factors are (1 - alpha rounds to 1), and where the target is 1 too the pixel's loss
       // and adjoint seed are exactly zero: nothing for the band ranking or the exact selection to decide.  These are the interior
       // pixels of the animal -- most of the pixels that hold depth bounds at all.  (Their bounds simply stay as they are.)
-#ifndef SMALFIT_NO_SATURATION_SHORTCUT
       const bool saturated = c > 0 && c <= K && (vb & kSumMask) >= (26ull << 24) && (!tsil || tss[s] == 1.0f);
-#else
-      const bool saturated = false;
-#endif
       if (saturated) act = 0;
       else if (!(zb.x < kInf)) act = (c <= K) ? 0 : 1;
       else if (need < 0 || b > kBandCap) act = 1;
@@ -806,9 +734,6 @@ raster_resolve_kernel(int S, int M, WinMap win, float w_sil, unsigned long long*
     for (int i = 0; i < 4; ++i) tot += red[i];
     blk_loss[(size_t)n * (TX * TX) + bxi] = tot;
   }
-#ifdef SMALFIT_ABL_RESOLVE_ATOMICS    // timing ablation: a second returning atomic per workgroup and queue on another pair of shared addresses
-  if (t < 2 && qn[t] > 0) { int v = atomicAdd(&qcount[40 + t], qn[t]); asm volatile("" :: "v"(v)); }
-#endif
   if (t == 2 && qn[0] > 0) atomicAdd(&qcount[2], qn[0]);   // [2] stays fixed while the band kernel appends its failures to [0]
   __syncthreads();
 #pragma unroll
@@ -819,22 +744,14 @@ raster_resolve_kernel(int S, int M, WinMap win, float w_sil, unsigned long long*
 }
 
 // Register budget of the band kernel: the narrow ranking loop is unrolled by four, the rare wide loop stays rolled
-#ifndef SMALFIT_BAND_NARROW_UNROLL
-#define SMALFIT_BAND_NARROW_UNROLL 4
-#endif
-#ifndef SMALFIT_BAND_WIDE_UNROLL
-#define SMALFIT_BAND_WIDE_UNROLL 1
-#endif
+constexpr int kBandNarrowUnroll = 4, kBandWideUnroll = 1;
 // 5c': band.  Persistent grid, one QUARTER-wave (16 lanes) per queued pixel: a lane holds band entries l and l + 16 (and
 // l + 32, l + 48 of the rare lists with more than 32 entries): rank by counting against an LDS broadcast of the depths,
 // include the K - c nearest, check for a tie at the cut, then re-centre (and, when the pose moves little, narrow) the
 // pixel's bounds.  (Round 3: a band holds 16-30 entries in the steady state, so a half-wave per pixel left half its lanes
 // idle; with 16 lanes per pixel twice as many pixels are in flight per wave -- the kernel is bound by the chain of
 // dependent loads per pixel, not by arithmetic.)
-#ifndef SMALFIT_BAND_BLOCKS
-#define SMALFIT_BAND_BLOCKS 1536
-#endif
-constexpr int kBandBlocks = SMALFIT_BAND_BLOCKS;
+constexpr int kBandBlocks = 1536;
 // the band work of 256-thread workgroup `bi` of `nblocks`.  zs: 16 x 64 floats of LDS.  A pixel whose band cannot decide (a
 // depth tie at the cut) is appended to the selection queue.  Returns the lane's loss partial.
 __device__ __forceinline__ long long
@@ -900,14 +817,14 @@ band_role(int bi, int nblocks, float (*zs)[64], int S, int M, WinMap win, float 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     int rank[4] = {0, 0, 0, 0};
-#pragma unroll SMALFIT_BAND_NARROW_UNROLL
+#pragma unroll kBandNarrowUnroll
     for (int k4 = 0; k4 < 8; ++k4) {
       const float4 q = *reinterpret_cast<const float4*>(&zs[qw][k4 * 4]);
       rank[0] += (q.x < e[0].x) + (q.y < e[0].x) + (q.z < e[0].x) + (q.w < e[0].x);
       rank[1] += (q.x < e[1].x) + (q.y < e[1].x) + (q.z < e[1].x) + (q.w < e[1].x);
     }
     if (wide) {
-#pragma unroll SMALFIT_BAND_WIDE_UNROLL
+#pragma unroll kBandWideUnroll
       for (int k4 = 0; k4 < 8; ++k4) {
         const float4 q = *reinterpret_cast<const float4*>(&zs[qw][k4 * 4]);
         const float4 p = *reinterpret_cast<const float4*>(&zs[qw][32 + k4 * 4]);
@@ -971,10 +888,8 @@ band_role(int bi, int nblocks, float (*zs)[64], int S, int M, WinMap win, float 
   return lacc;
 }
 
-#ifndef SMALFIT_BAND_MINWAVES
-#define SMALFIT_BAND_MINWAVES 6          // <= 80 registers: six instead of five workgroups per CU (resolve + band 43.5 -> 41.9 us; 8 spills)
-#endif
-__global__ void __launch_bounds__(256, SMALFIT_BAND_MINWAVES)
+// 6 waves per SIMD: <= 80 registers, six instead of five workgroups per CU (resolve + band 43.5 -> 41.9 us; 8 spills)
+__global__ void __launch_bounds__(256, 6)
 raster_band_kernel(int S, int M, WinMap win, float w_sil, unsigned long long* __restrict__ gacc,
                    unsigned* __restrict__ bcnt, const float2* __restrict__ blist,
                    SilTarget tsil, float* __restrict__ sil_out, float2* __restrict__ gz,
@@ -997,23 +912,14 @@ raster_band_kernel(int S, int M, WinMap win, float w_sil, unsigned long long* __
 // containing the pixel, evaluates those faces (lane per face, record loads software-prefetched), compacts
 // the candidates into LDS in face order, finds the K-th smallest depth exactly (histogram over a linear quantisation
 // of the depth range, narrowed to <= 64 entries, then exact ranks) and multiplies the K nearest (1 - p) in a fixed order.
-#ifndef SMALFIT_BAND_TRIES
-#define SMALFIT_BAND_TRIES 6
-#endif
-#ifndef SMALFIT_CAND_CAP
-#define SMALFIT_CAND_CAP 1024
-#endif
-#ifndef SMALFIT_COVER_CAP
-#define SMALFIT_COVER_CAP 1024         // round 3: 11 KB of LDS per wave -> 7 workgroups (14 waves) per CU at <= 128 registers; a pixel with more
-#endif                                 // covering faces walks every face instead, which costs about as many rounds as the three-stage scan of such a pixel
-constexpr int kCandCap = SMALFIT_CAND_CAP;   // candidates per pixel kept in LDS; beyond: multi-pass re-evaluation
-constexpr int kHitCap = 2 * SMALFIT_CAND_CAP < 1024 ? 2 * SMALFIT_CAND_CAP : 1024;   // union boxes containing a pixel kept in LDS (aliases the candidate buffer)
-constexpr int kCoverCap = SMALFIT_COVER_CAP;   // faces whose box covers the pixel, kept in LDS (u16 ids)
+constexpr int kCandCap = 1024;            // candidates per pixel kept in LDS; beyond: multi-pass re-evaluation
+constexpr int kHitCap = 1024;             // union boxes containing a pixel kept in LDS (aliases the candidate buffer)
+// faces whose box covers the pixel, kept in LDS (u16 ids).  Round 3: 11 KB of LDS per wave -> 7 workgroups (14 waves) per CU at
+// <= 128 registers; a pixel with more covering faces walks every face instead, which costs about as many rounds as the three-stage
+// scan of such a pixel
+constexpr int kCoverCap = 1024;
 
-#ifndef SMALFIT_SEL_SLOTS
-#define SMALFIT_SEL_SLOTS 2
-#endif
-constexpr int kSelSlots = SMALFIT_SEL_SLOTS;   // rounds of face records in flight per wave while a pixel's covering faces are evaluated (4 measured the same as 2, with 14 more VGPRs)
+constexpr int kSelSlots = 2;              // rounds of face records in flight per wave while a pixel's covering faces are evaluated (4 measured the same as 2, with 14 more VGPRs)
 constexpr int kSelWaves = 2;              // waves per select block: 11 KB of LDS per wave -> 7 blocks (14 waves) per CU
 
 // one queued pixel, by one wave (see the kernel below): the exact K nearest from scratch.  Returns (lane 0) the pixel's weighted
@@ -1280,7 +1186,7 @@ __device__ __forceinline__ long long select_pixel(const SelCtx& c, const SelLds&
   }
   // ---- one pass: product of the included factors, the nearest depth beyond the K-th, and the band population
   // for kBandTries candidate half-widths (delta, delta/2, delta/4, ...)
-  constexpr int kBandTries = SMALFIT_BAND_TRIES;
+  constexpr int kBandTries = 6;
   const float delta0 = (nc > K) ? kBandHalf * (zk - zmn) * (1.0f / (float)K) : 0.f;
   float a = 1.0f, znext = kInf;
   // The half-widths' bounds are wave-uniform: held in scalar registers, and each population is counted with a ballot (scalar
@@ -1364,10 +1270,8 @@ __device__ __forceinline__ long long select_pixel(const SelCtx& c, const SelLds&
   return loss_fp;
 }
 
-#ifndef SMALFIT_SEL_MINWAVES
-#define SMALFIT_SEL_MINWAVES 4         // <= 128 VGPRs (133 unconstrained; 12 bytes of scratch): 4 waves/SIMD allowed, LDS admits 14 waves per CU
-#endif
-__global__ void __launch_bounds__(64 * kSelWaves, SMALFIT_SEL_MINWAVES)
+// 4 waves per SIMD: <= 128 VGPRs (133 unconstrained; 12 bytes of scratch), LDS admits 14 waves per CU
+__global__ void __launch_bounds__(64 * kSelWaves, 4)
 raster_select_kernel(int F, int S, int M, WinMap win, float w_sil, const float4* __restrict__ frec, const float* __restrict__ zc,
                      const int4* __restrict__ brect, const int2* __restrict__ fbox, int* __restrict__ qcount,
                      const int* __restrict__ queue, SilTarget tsil,
@@ -1447,20 +1351,13 @@ __global__ void gpix_from_dsil_kernel(size_t total, const float* __restrict__ si
 
 // 5e: backward, face-parallel gather (deterministic, no atomics).  16 lanes per face walk the face's pixel box
 // row-major like the forward sweep; d(signed dist^2)/d(vertex) flows through the nearest edge only.
-#ifndef SMALFIT_BWD_FACES
-#define SMALFIT_BWD_FACES 4
-#endif
-#ifndef SMALFIT_BWD_LANES
-#define SMALFIT_BWD_LANES 16
-#endif
-#ifndef SMALFIT_BWD_DEPTH
-#define SMALFIT_BWD_DEPTH 1
-#endif
-constexpr int kBwdDepth = SMALFIT_BWD_DEPTH;      // pixels per lane whose adjoint seeds are requested together (see the kernel)
-constexpr int kBwdLanes = SMALFIT_BWD_LANES;      // lanes per face of the backward gather (16; 8 = developer A/B)
-constexpr int kBwdFaces = SMALFIT_BWD_FACES;      // faces per workgroup of the backward gather (16 lanes each).  One wave per
-                                                  // workgroup measured best (4 / 8 / 16 / 32 / 64 faces: 90 / 92 / 93 / 100 / 111 us): a
-                                                  // wave that is done frees its slot at once instead of waiting for its block mates
+constexpr int kBwdLanes = 16;             // lanes per face of the backward gather
+static_assert(kBwdLanes == 16, "mask lists are laid out for 16 lanes per face");
+// faces per workgroup of the backward gather (16 lanes each).  One wave per workgroup measured best (4 / 8 / 16 / 32 / 64 faces:
+// 90 / 92 / 93 / 100 / 111 us): a wave that is done frees its slot at once instead of waiting for its block mates
+constexpr int kBwdFaces = 4;
+static_assert(kSweepFaces % 16 == 0 && kBwdFaces * kBwdLanes == 64,
+              "a sweep round is 16 faces of 16 lanes, and the four faces of a sweep wave are the four faces of a backward wave");
 // kUnclampedT (smalfit_engine_set_option SMALFIT_OPT_UNCLAMPED_EDGE_T; SURVEY App. B, last row): the adjoint of the point-segment
 // distance with the edge parameter t NOT clamped to [0, 1] -- q = p - (a + t (b - a)) on the infinite line, weights (1 - t), t --
 // which is what some pytorch3d 0.2.x sources are recalled to compute in PointLineDistanceBackward.  It differs from the exact
@@ -1557,8 +1454,8 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
         gc[0] = fmaf(cc, gx, gc[0]); gc[1] = fmaf(cc, gy, gc[1]);
       };
       SMALFIT_WORK(if (sub == 0) { atomicAdd(&g_work[cnt <= kListCap ? 21 : (cnt == kMaskList ? 22 : 23)], 1ull); if (cnt == kNoList) atomicAdd(&g_work[24], (unsigned long long)npx); })
-      // (mask and box walks can request the seeds of kBwdDepth pixels per lane before the first pair is evaluated; measured on both
-      // scenes: 1 / 2 / 4 are the same within noise -- the gather is bound by its rounds' instructions, not by the seed loads)
+      // (one pixel per lane and round: requesting the seeds of 2 or 4 pixels per lane before the first pair is evaluated measured the
+      // same within noise on both scenes -- the gather is bound by its rounds' instructions, not by the seed loads)
       auto coords = [&](float qf, float& rowf, float& colf) {
         const float ryf = floorf(fmaf(qf, ibw, hbw));    // q / bw: (q + 1/2) / bw is >= 1/2048 from any integer, the reciprocal good to 1 ulp
         rowf = r0f + ryf; colf = c0f + fmaf(-ryf, bwf, qf);
@@ -1574,44 +1471,19 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
       } else if (cnt == kMaskList) {
         // the forward sweep's candidate masks: bit r of the lane's word = pixel 16 r + sub of the box
         while (lmask) {
-          float qs[kBwdDepth];
-          float2 gs[kBwdDepth];
-#pragma unroll
-          for (int j = 0; j < kBwdDepth; ++j) {
-            qs[j] = -1.0f; gs[j] = make_float2(0.f, 0.f);
-            if (lmask) {
-              qs[j] = (float)(((__ffsll((long long)lmask) - 1) * kBwdLanes) + sub);
-              lmask &= lmask - 1ull;
-              float rowf, colf;
-              coords(qs[j], rowf, colf);
-              gs[j] = load_seed(rowf, colf);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < kBwdDepth; ++j) {
-            if (qs[j] >= 0.0f) {
-              float rowf, colf;
-              coords(qs[j], rowf, colf);
-              pair(rowf, colf, gs[j]);
-            }
-          }
+          const float qf = (float)(((__ffsll((long long)lmask) - 1) * kBwdLanes) + sub);
+          lmask &= lmask - 1ull;
+          float rowf, colf;
+          coords(qf, rowf, colf);
+          pair(rowf, colf, load_seed(rowf, colf));
         }
       } else {
         // neither: the box's pixels in row-major order, 16 at a time, like the forward sweep
         const float npxf = (float)npx;
-        for (float qf = (float)sub; qf < npxf; qf += (float)(kBwdLanes * kBwdDepth)) {
-          float2 gs[kBwdDepth];
-#pragma unroll
-          for (int j = 0; j < kBwdDepth; ++j) {
-            gs[j] = make_float2(0.f, 0.f);
-            const float qj = qf + (float)(kBwdLanes * j);
-            if (qj < npxf) { float rowf, colf; coords(qj, rowf, colf); gs[j] = load_seed(rowf, colf); }
-          }
-#pragma unroll
-          for (int j = 0; j < kBwdDepth; ++j) {
-            const float qj = qf + (float)(kBwdLanes * j);
-            if (qj < npxf) { float rowf, colf; coords(qj, rowf, colf); pair(rowf, colf, gs[j]); }
-          }
+        for (float qf = (float)sub; qf < npxf; qf += (float)kBwdLanes) {
+          float rowf, colf;
+          coords(qf, rowf, colf);
+          pair(rowf, colf, load_seed(rowf, colf));
         }
       }
     }

@@ -12,10 +12,7 @@ namespace smalfit {
 
 static thread_local std::string g_err;
 static constexpr int kBetaGroups = 8;        // frame groups of the shape-blend adjoint (dbeta_block) when betas are shared
-#ifndef SMALFIT_SELECT_BLOCKS
-#define SMALFIT_SELECT_BLOCKS 1792
-#endif
-static constexpr int kSelectBlocks = SMALFIT_SELECT_BLOCKS;   // persistent grid of raster_select_kernel: 7 resident 2-wave blocks x 256 CUs
+static constexpr int kSelectBlocks = 1792;   // persistent grid of raster_select_kernel: 7 resident 2-wave blocks x 256 CUs
 static_assert(kSelectBlocks % (8 * kSelGroups) == 0, "every ticket group of every XCD needs the same number of selection workgroups (a group without one would leave its pixels undone)");
 #ifdef SMALFIT_DEV_PROBES
 static int g_dbg = 0;             // developer builds only (tools/build_variant.sh ... -DSMALFIT_DEV_PROBES): smalfit_debug_set
@@ -277,8 +274,9 @@ int smalfit_model_create(const smalfit_model_desc* d, smalfit_model** out) {
     for (int f = 0; f < F; ++f)
       for (int k = 0; k < 3; ++k) faces_int[(size_t)f * 3 + k] = d->faces[keyed[f].second * 3 + k];
   }
-  // vertex -> (face, corner) adjacency (internal face ids)
-  std::vector<int> vf_off(V + 1, 0), vf_idx((size_t)F * 3);
+  // vertex -> (face, corner) adjacency (internal face ids).  vf_idx ends with one zero entry past the 3 F corners: vertex_bwd_kernel's
+  // clamped unconditional loads read vf_idx[vf_off[V]] when the last vertices have no incident face
+  std::vector<int> vf_off(V + 1, 0), vf_idx((size_t)F * 3 + 1, 0);
   for (int i = 0; i < F * 3; ++i) vf_off[faces_int[i] + 1]++;
   for (int v = 0; v < V; ++v) vf_off[v + 1] += vf_off[v];
   {
@@ -669,28 +667,15 @@ static int run_lbs_backward(smalfit_engine* e, hipStream_t st, int M, int nb, in
                             const float* dface, const float* dJ41, const float* dext, bool need_pose,
                             bool need_beta, bool need_ls, const float* dth_direct, int j_stride, float* dRs_out = nullptr) {
   const ModelDev& m = e->model->dev;
-#ifndef SMALFIT_VB_FRAMES
-#define SMALFIT_VB_FRAMES 1
-#endif
-#ifndef SMALFIT_NO_LBS_XCD
-  const dim3 vb_grid = (SMALFIT_VB_FRAMES == 1) ? dim3(xcd_grid(m.Vp / 256, M), 1) : dim3(m.Vp / 256, (M + SMALFIT_VB_FRAMES - 1) / SMALFIT_VB_FRAMES);
-#else
-  const dim3 vb_grid(m.Vp / 256, (M + SMALFIT_VB_FRAMES - 1) / SMALFIT_VB_FRAMES);
-#endif
-  vertex_bwd_kernel<SMALFIT_VB_FRAMES><<<vb_grid, 256, 0, st>>>(
-      m, M, e->proj, dface, dJ41, dext, e->Am, e->dvert, e->dvp, e->dtr_part);
+  vertex_bwd_kernel<<<xcd_grid(m.Vp / 256, M), 256, 0, st>>>(m, M, e->proj, dface, dJ41, dext, e->Am, e->dvert, e->dvp, e->dtr_part);
   LAUNCH_OK("vertex_bwd_kernel");
   {
     const int nPB = need_pose ? mid_pb_ids(M) : 0;   // (up to PBM_TILES x 16 frames) x 32 pose features x column split
     const int dbx = need_beta ? e->nblk_beta : 0, dby = betas_shared ? 1 : M, dbz = betas_shared ? kBetaGroups : 1;
-#ifndef SMALFIT_DBETA_RIDER
-#define SMALFIT_DBETA_RIDER 1
-#endif
-    const int ndb_mid = SMALFIT_DBETA_RIDER ? 0 : dbx * dby * dbz, ndb_chain = SMALFIT_DBETA_RIDER ? dbx * dby * dbz : 0;
-    lbs_bwd_mid_kernel<<<mid_grid(M, nPB, ndb_mid), 256, 0, st>>>(m, M, e->CS, nb, betas_shared, nPB, ndb_mid ? dbx : 0, dby, dbz, e->dvert,
-                                                               e->vposed, e->dvp, e->dA, e->dpf_part, e->dbeta_part);
+    lbs_bwd_mid_kernel<<<mid_grid(M, nPB), 256, 0, st>>>(m, M, nPB, e->dvert, e->vposed, e->dvp, e->dA, e->dpf_part);
     LAUNCH_OK("lbs_bwd_mid_kernel");
-    chain_bwd_kernel<<<M + ndb_chain, 256, 0, st>>>(m, M, e->theta, e->Rm, e->Gm, e->scm, e->Jrest, j_stride, e->dA,
+    // the shape-blend adjoint partials ride on the chain launch: dbx * dby * dbz workgroups after its M frame blocks
+    chain_bwd_kernel<<<M + dbx * dby * dbz, 256, 0, st>>>(m, M, e->theta, e->Rm, e->Gm, e->scm, e->Jrest, j_stride, e->dA,
                                                    need_pose ? e->dpf_part : nullptr, e->CS, dth_direct, e->dtheta,
                                                    need_ls ? e->dls : nullptr, e->dJrest, need_beta ? e->dbetaJ : nullptr, dRs_out,
                                                    nb, betas_shared, dbx, dby, dbz, e->dvp, e->dbeta_part);

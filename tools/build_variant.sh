@@ -1,5 +1,7 @@
 #!/bin/bash
-# developer helper: build a variant of libsmalfit.so with extra -D flags.  usage: tools/build_variant.sh NAME -DX=1 ...
+# developer helper: build a variant of libsmalfit.so from the current sources with extra compiler flags -- the instrumentation builds
+# (-DSMALFIT_DEV_PROBES, -DSMALFIT_WORK_STATS, -DSMALFIT_PHASES), or no flags for a constant edited in a scratch branch.
+# usage: tools/build_variant.sh NAME [FLAGS ...]
 # run a tool against it with SMALFIT_LIB=smalify_amd/_variants/NAME.so
 set -e
 cd "$(dirname "$0")/.."
