@@ -674,26 +674,35 @@ assemble_kernel(AssembleArgs a) {
   if (role < nbs) {
     if (a.g_betas) {
       const int s = role;
-      const int b = t % 20, slice = t / 20;
+      const int bl = t % 20, slice = t / 20;
       // The shared-shape gradient is the sum of every frame's and every column block's partial, and in a fit that has settled those
       // partials largely cancel: they are added in DOUBLE (round 6; fixed order as before) and rounded once.  That is the principled
       // sum, but it moved no printed digit: config 3 after stage 1 stays at d/d betas 9.86e-6, d/d log scales 3.64e-5 off the float64
       // oracle, as with the float32 running sum (profiles/r6_gpu_tests.log, profiles/r6_eval_fixture_tables.txt).
-      if (slice < 12 && b < a.nb) {
-        double acc = 0.0;
-        const int nlo = a.betas_shared ? 0 : s, nhi = a.betas_shared ? M : s + 1;
-        for (int n = nlo + slice; n < nhi; n += 12) acc += (double)a.dbetaJ[(size_t)n * a.NBall + b];
-        const int nparts = a.nblk_beta * a.ngrp_beta;
+      // One pass sums shape directions [b0, b0 + 20) in 12 slices each.
+      auto beta_pass = [&](int b0) {
+        const int b = b0 + bl;
+        if (slice < 12 && b < a.nb) {
+          double acc = 0.0;
+          const int nlo = a.betas_shared ? 0 : s, nhi = a.betas_shared ? M : s + 1;
+          for (int n = nlo + slice; n < nhi; n += 12) acc += (double)a.dbetaJ[(size_t)n * a.NBall + b];
+          const int nparts = a.nblk_beta * a.ngrp_beta;
 #pragma unroll 8
-        for (int blk = slice; blk < nparts; blk += 12) acc += (double)a.dbeta_part[((size_t)s * nparts + blk) * a.nb + b];
-        bsum[slice][b] = acc;
-      }
-      __syncthreads();
-      if (t < a.nb) {
-        double tot = 0.0;
-        for (int sl = 0; sl < 12; ++sl) tot += bsum[sl][t];
-        if (a.gb_prior && s == 0) tot += (double)a.gb_prior[t];
-        a.g_betas[s * a.nb + t] = (float)tot;
+          for (int blk = slice; blk < nparts; blk += 12) acc += (double)a.dbeta_part[((size_t)s * nparts + blk) * a.nb + b];
+          bsum[slice][bl] = acc;
+        }
+        __syncthreads();
+        if (t < 20 && b0 + t < a.nb) {
+          double tot = 0.0;
+          for (int sl = 0; sl < 12; ++sl) tot += bsum[sl][t];
+          if (a.gb_prior && s == 0) tot += (double)a.gb_prior[b0 + t];
+          a.g_betas[s * a.nb + b0 + t] = (float)tot;
+        }
+      };
+      beta_pass(0);
+      for (int b0 = 20; b0 < a.nb; b0 += 20) {    // more than 20 directions (up to NBall): further passes (a.nb is block-uniform)
+        __syncthreads();                          // the previous pass has read bsum
+        beta_pass(b0);
       }
     }
   } else if ((role -= nbs) == 0) {

@@ -59,3 +59,30 @@ def target_meshes_from_smal(md, N, seed):
 
 def synthetic_smal_data(seed=0):
     return synthetic.synthetic_smal_dicts(seed=seed)[1]
+
+
+def fitter_problem(N, seed=0):
+    """SMAL3DFitter of N meshes (stand-in model, 20 betas) + N target meshes from the oracle's LBS -> (md, fitter, targets)"""
+    from smalify_amd.fitter_3d import SMAL3DFitter, TargetMeshes
+    md = synthetic.synthetic_model(seed=0, shape_family_id=-1)
+    tv, tf = target_meshes_from_smal(md, N, seed=seed + 1)
+    fit = SMAL3DFitter(batch_size=N, shape_family=-1, model_data=md, smal_data=synthetic_smal_data())
+    return md, fit, TargetMeshes(tv, [tf] * N)
+
+
+def fused_and_component_runs(N, seed=6, iters=6):
+    """`iters` Stage iterations of N meshes as one smalfit_fit3d_step each (Stage.step) and as the component calls
+    (Stage.step_unfused), each from a fresh fitter -> [(losses (iters,), {parameter: values}, last sampled points)] x 2"""
+    from smalify_amd.fitter_3d import Stage
+    results = []
+    for fused in (True, False):
+        md, fit, targets = fitter_problem(N, seed=seed)
+        stage = Stage(iters, "default", fit, targets, lr=0.02, custom_lrs={"joint_rot": 0.004, "betas": 0.03}, seed=11)
+        losses = []
+        for it in range(iters):
+            losses.append((stage.step(it) if fused else stage.step_unfused(it)).clone())
+        torch.cuda.synchronize()
+        results.append((torch.stack(losses).cpu().numpy(), {k: getattr(fit, k).detach().cpu().numpy().copy() for k in
+                                                           ("betas", "global_rot", "joint_rot", "trans", "deform_verts")},
+                        stage.last_points.cpu().numpy().copy()))
+    return results

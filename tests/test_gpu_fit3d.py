@@ -116,11 +116,7 @@ def test_sampler_matches_host_emulation_and_is_deterministic():
 
 
 def _fitter(N, seed=0):
-    from smalify_amd.fitter_3d import SMAL3DFitter, TargetMeshes
-    md = mc.synthetic.synthetic_model(seed=0, shape_family_id=-1)
-    tv, tf = mc.target_meshes_from_smal(md, N, seed=seed + 1)
-    fit = SMAL3DFitter(batch_size=N, shape_family=-1, model_data=md, smal_data=mc.synthetic_smal_data())
-    return md, fit, TargetMeshes(tv, [tf] * N)
+    return mc.fitter_problem(N, seed)
 
 
 @pytest.mark.parametrize("scheme,lr,custom_lrs,iters", [("default", 0.01, {"joint_rot": 0.005}, 12), ("deform", 2e-4, None, 8)])
@@ -184,20 +180,7 @@ def test_fused_step_equals_the_component_calls():
     """smalfit_fit3d_step against the same iteration composed from smalfit_lbs_forward / mesh_targets_sample /
     mesh_objective_eval / lbs_backward / adam_step: same kernels on the same inputs -> same bits, except that the fused
     path builds theta inside the LBS head kernel (no difference) and runs the LBS forward once"""
-    from smalify_amd.fitter_3d import Stage
-    N = 3
-    results = []
-    for fused in (True, False):
-        md, fit, targets = _fitter(N, seed=6)
-        stage = Stage(6, "default", fit, targets, lr=0.02, custom_lrs={"joint_rot": 0.004, "betas": 0.03}, seed=11)
-        losses = []
-        for it in range(6):
-            losses.append((stage.step(it) if fused else stage.step_unfused(it)).clone())
-        torch.cuda.synchronize()
-        results.append((torch.stack(losses).cpu().numpy(), {k: getattr(fit, k).detach().cpu().numpy().copy() for k in
-                                                           ("betas", "global_rot", "joint_rot", "trans", "deform_verts")},
-                        stage.last_points.cpu().numpy().copy()))
-    (la, pa, xa), (lb, pb, xb) = results
+    (la, pa, xa), (lb, pb, xb) = mc.fused_and_component_runs(3)
     assert np.array_equal(xa, xb)
     assert np.abs(la - lb).max() <= 1e-6 * np.abs(lb).max()
     for k in pa:

@@ -34,7 +34,9 @@ def test_adam():
 
 @pytest.mark.parametrize("M,dense,with_scale", [(3, False, True), (3, True, False), (8, False, True), (8, True, False), (21, False, True)])
 def test_lbs_forward_backward(M, dense, with_scale):
-    """M = 8 and 21 take the matrix-core pose-blend kernel (frames in tiles of 16: a half-empty tile, a ragged second tile);
+    """M = 3 skins with skin_kernel<8>, M = 8 and 21 with skin_mfma_split_kernel (frames in tiles of 16: a half-empty tile,
+    a ragged second tile); the pose-blend adjoint runs on the matrix cores at every M, here in one chunk of up to 64 frames.
+    The wide skinning kernel (M >= 49) and the further pose-blend chunks (M > 64) are covered by test_gpu_frame_counts.py.
     dense = the reference's dense (V,35) weight matrices, i.e. 35 skinning weights per vertex"""
     m = pc.case_lbs(M, dense, with_scale)
     for k in ("lbs_verts_rel", "lbs_joints_rel", "lbs_Rs_rel", "lbs_vshaped_rel"):

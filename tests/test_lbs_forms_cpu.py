@@ -1,0 +1,61 @@
+"""The frame counts of tests/test_gpu_frame_counts.py reach every kernel form the host can pick, and tests/lbs_forms.py
+still restates the host's selection rules (no GPU needed)."""
+import os
+import re
+
+from tests import lbs_forms as lf
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "smalify_amd", "csrc")
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def test_the_rules_are_the_hosts():
+    launch = _src("smalfit_launch.inc")
+    # run_lbs_forward: the wide kernel's condition, then the split kernel for M > 4, then skin_kernel<8>
+    m = re.search(r"if \(M > 4 && \(m\.Vp / 64\) \* \(\(M \+ 15\) / 16\) >= 256\)\s*skin_mfma_kernel<<<.*?"
+                  r"else if \(M > 4\)[^\n]*\n\s*skin_mfma_split_kernel<<<.*?else\s*skin_kernel<8><<<", launch, re.S)
+    assert m, "run_lbs_forward's choice of skinning kernel changed: update tests/lbs_forms.py"
+    assert "const int Vp = (int)align_up((size_t)V, 256);" in launch
+    bwd = _src("kernels_lbs_backward.inc")
+    tiles = re.search(r"constexpr int PBM_SPLITS = \d+, PBM_U = \d+, PBM_TILES = (\d+);", bwd)
+    assert tiles and int(tiles.group(1)) == lf.PBM_TILES
+    assert ("mid_pb_ids(int M) { return 10 * PBM_SPLITS * (((M + 15) / 16 + PBM_TILES - 1) / PBM_TILES); }" in bwd)
+    assert "const int nft = (M + 15) / 16, t0 = tchunk * PBM_TILES, nt = min(PBM_TILES, nft - t0);" in bwd
+
+
+def test_rule_boundaries():
+    assert lf.padded_verts() == 4096
+    assert [lf.skin_form(M) for M in (1, 4, 5, 48, 49, 64, 65)] == ["plain", "plain", "split", "split", "wide", "wide", "wide"]
+    assert [lf.pose_blend_chunks(M) for M in (1, 64, 65, 128, 129)] == [1, 1, 2, 2, 3]
+
+
+def test_frame_lists_reach_every_form():
+    forms = {lf.skin_form(M) for M in lf.LBS_FRAMES}
+    assert forms == {"plain", "split", "wide"}
+    assert {lf.pose_blend_chunks(M) for M in lf.LBS_FRAMES} == {1, 2, 3}
+    for form in ("split", "wide"):             # the matrix-core forms with full and with ragged 16-frame tiles
+        ms = [M for M in lf.LBS_FRAMES if lf.skin_form(M) == form]
+        assert any(lf.ragged_tile(M) for M in ms) and any(not lf.ragged_tile(M) for M in ms), form
+    assert any(lf.skin_form(M) == "wide" and lf.ragged_tile(M) and lf.pose_blend_chunks(M) == 1 for M in lf.LBS_FRAMES)
+    assert any(M % 8 for M in lf.LBS_FRAMES if M > 8)
+    assert [lf.skin_form(M) for M in lf.ONE_PER_FORM] == ["plain", "split", "wide"]
+    assert {lf.skin_form(M) for M in lf.FIT_FRAMES} == {"split", "wide"}
+    assert {lf.pose_blend_chunks(M) for M in lf.FIT_FRAMES} == {1, 2, 3}
+
+
+def test_prefix_pairs_share_their_forms():
+    for M1, M2 in lf.PREFIX_PAIRS:
+        assert M1 < M2 and lf.same_forms(M1, M2), (M1, M2)
+    assert {lf.skin_form(M1) for M1, _ in lf.PREFIX_PAIRS} == {"plain", "split", "wide"}
+    assert not lf.same_forms(48, 49) and not lf.same_forms(64, 65)
+
+
+def test_beta_counts_reach_both_groups_and_the_limit():
+    nb = lf.BETA_COUNTS
+    assert min(nb) == 1 and max(nb) == 41                        # 41 = every direction of the model (NBall)
+    assert 20 in nb and 21 in nb                                 # the shipped count and the first past it
+    assert any(20 < b <= 32 for b in nb) and any(b > 32 for b in nb)   # dbeta_block's first and second group of 32
