@@ -70,14 +70,17 @@ def fitter_problem(N, seed=0):
     return md, fit, TargetMeshes(tv, [tf] * N)
 
 
-def fused_and_component_runs(N, seed=6, iters=6):
+DEFAULT_CUSTOM_LRS = {"joint_rot": 0.004, "betas": 0.03}
+
+
+def fused_and_component_runs(N, seed=6, iters=6, scheme="default", lr=0.02, custom_lrs=DEFAULT_CUSTOM_LRS):
     """`iters` Stage iterations of N meshes as one smalfit_fit3d_step each (Stage.step) and as the component calls
     (Stage.step_unfused), each from a fresh fitter -> [(losses (iters,), {parameter: values}, last sampled points)] x 2"""
     from smalify_amd.fitter_3d import Stage
     results = []
     for fused in (True, False):
         md, fit, targets = fitter_problem(N, seed=seed)
-        stage = Stage(iters, "default", fit, targets, lr=0.02, custom_lrs={"joint_rot": 0.004, "betas": 0.03}, seed=11)
+        stage = Stage(iters, scheme, fit, targets, lr=lr, custom_lrs=custom_lrs, seed=11)
         losses = []
         for it in range(iters):
             losses.append((stage.step(it) if fused else stage.step_unfused(it)).clone())
@@ -86,3 +89,29 @@ def fused_and_component_runs(N, seed=6, iters=6):
                                                            ("betas", "global_rot", "joint_rot", "trans", "deform_verts")},
                         stage.last_points.cpu().numpy().copy()))
     return results
+
+
+def stage_loop_against_oracle(scheme, lr, custom_lrs, iters, N=2, seed=0):
+    """Stage.step x iters against the oracle: same sampled points, loss + autograd through the LBS oracle, torch-style
+    Adam with betas (0.9, 0.999) and per-parameter learning rates -> (per-iteration relative loss errors, fitter,
+    oracle parameters after the loop, names of the trained parameters)"""
+    from smalify_amd.fitter_3d import SMALParamGroup, Stage
+    md, fit, targets = fitter_problem(N, seed)
+    weights = dict(w_chamfer=1.0, w_edge=0.8, w_normal=0.02, w_laplacian=0.01)
+    stage = Stage(iters, scheme, fit, targets, loss_weights=weights, lr=lr, custom_lrs=custom_lrs, seed=5)
+    om = so.OracleModel(md)
+    edges, pairs = mo.unique_edges(md.faces), mo.face_pairs(md.faces)
+    names = [n for n in SMALParamGroup.param_map[scheme] if n != "log_beta_scales"]      # frozen in the reference
+    params = {k: getattr(fit, k).detach().cpu().double() for k in
+              ("betas", "log_beta_scales", "global_rot", "joint_rot", "trans", "deform_verts")}
+    adam = mo.Adam({n: (custom_lrs or {}).get(n, lr) for n in names})
+    trace = []
+    for it in range(iters):
+        loss = stage.step(it)
+        pts = stage.last_points.cpu().double()
+        leaf = {k: v.clone().requires_grad_(k in names) for k, v in params.items()}
+        total, _ = mo.objective(mo.fitter_verts(om, leaf), pts, edges, pairs, weights)
+        grads = dict(zip(names, torch.autograd.grad(total, [leaf[n] for n in names])))
+        adam.step(params, grads)
+        trace.append(abs(float(loss) - float(total.detach())) / abs(float(total.detach())))
+    return trace, fit, params, names

@@ -126,27 +126,8 @@ def test_stage_loop_follows_the_oracle(scheme, lr, custom_lrs, iters):
     mean edge length (0.02): Adam moves every coordinate by ~lr per iteration whatever the gradient's size, and at
     lr = 0.01 the mesh crumples within a few steps (flipped and degenerate faces), where float32 and float64 part ways
     at the clamp of the normal term."""
-    from smalify_amd.fitter_3d import SMALParamGroup, Stage
-    N = 2
-    md, fit, targets = _fitter(N)
-    weights = dict(w_chamfer=1.0, w_edge=0.8, w_normal=0.02, w_laplacian=0.01)
-    stage = Stage(iters, scheme, fit, targets, loss_weights=weights, lr=lr, custom_lrs=custom_lrs, seed=5)
-    om = so.OracleModel(md)
-    edges, pairs = mo.unique_edges(md.faces), mo.face_pairs(md.faces)
-    names = [n for n in SMALParamGroup.param_map[scheme] if n != "log_beta_scales"]      # frozen in the reference
-    params = {k: getattr(fit, k).detach().cpu().double() for k in
-              ("betas", "log_beta_scales", "global_rot", "joint_rot", "trans", "deform_verts")}
-    adam = mo.Adam({n: (custom_lrs or {}).get(n, lr) for n in names})
-    worst, trace = 0.0, []
-    for it in range(iters):
-        loss = stage.step(it)
-        pts = stage.last_points.cpu().double()
-        leaf = {k: v.clone().requires_grad_(k in names) for k, v in params.items()}
-        total, _ = mo.objective(mo.fitter_verts(om, leaf), pts, edges, pairs, weights)
-        grads = dict(zip(names, torch.autograd.grad(total, [leaf[n] for n in names])))
-        adam.step(params, grads)
-        trace.append(abs(float(loss) - float(total.detach())) / abs(float(total.detach())))
-        worst = max(worst, trace[-1])
+    trace, fit, params, names = mc.stage_loop_against_oracle(scheme, lr, custom_lrs, iters, N=2)
+    worst = max(trace)
     assert worst < 1e-4, trace
     # free vertices: Adam turns every coordinate's gradient into a step of ~lr whatever its size, so a coordinate whose
     # gradient passes through zero during the run takes a different path in float32 (measured 1.4e-3 rel-L2 after 8
