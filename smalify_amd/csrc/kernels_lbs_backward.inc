@@ -821,23 +821,6 @@ assemble_kernel(AssembleArgs a) {
   PHASE_END(PH_ASM_LAST, pa1, pa2);
 }
 
-// ------------------------------------------------------------------------------------------------
-// K12: Adam (torch.optim.Adam semantics: eps outside the bias-corrected sqrt)
-// ------------------------------------------------------------------------------------------------
-__global__ void adam_kernel(int count, float* __restrict__ p, const float* __restrict__ g,
-                            float* __restrict__ mm, float* __restrict__ vv,
-                            float step_size, float b1, float b2, float eps, float bc2_sqrt) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const float gi = g[i];
-  const float mi = b1 * mm[i] + (1.0f - b1) * gi;
-  const float vi = b2 * vv[i] + (1.0f - b2) * gi * gi;
-  mm[i] = mi;
-  vv[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] - step_size * (mi / denom);
-}
-
 // adjoint of a per-frame template offset (SMAL.__call__'s del_v / v_template): d v_shaped = d v_posed + J_regressor d(rest joints)
 __global__ void offset_grad_kernel(ModelDev m, int M, const float* __restrict__ dvp /*[M][3][Vp]*/,
                                    const float* __restrict__ dJrest /*[M][105]*/, float* __restrict__ doff /*[M][V][3]*/) {
@@ -856,40 +839,40 @@ __global__ void offset_grad_kernel(ModelDev m, int M, const float* __restrict__ 
   o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
 }
 
-// Adam over up to four [begin, end) ranges of one flat parameter buffer in a single launch (the trainable set of a
-// stage).  fresh != 0: first step of a stage -- the moments are taken as zero instead of being read, so a stage needs
-// no fill of the optimiser state (b * 0 + x == x exactly: the same bits as stepping from zero-filled moments).
+// ------------------------------------------------------------------------------------------------
+// K12: Adam over up to four [begin, end) ranges of one flat parameter buffer in a single launch (the trainable set of a
+// stage; the update itself is adam_update).  fresh != 0: first step of a stage -- the moments are taken as zero instead
+// of being read, so a stage needs no fill of the optimiser state.
+// ------------------------------------------------------------------------------------------------
 struct AdamSegments {
   int nseg;
   int beg[4];
   int off[5];        // prefix sums of the range lengths; off[nseg] = total
 };
+// element j (< off[nseg]) of the packed ranges
+__device__ __forceinline__ void adam_segments_element(const AdamSegments& sg, int j, float* p, const float* g, float* mm,
+                                                      float* vv, float step_size, float b1, float b2, float eps,
+                                                      float bc2_sqrt, bool fresh) {
+  int sgi = 0;
+#pragma unroll
+  for (int k = 1; k < 4; ++k) sgi += (k < sg.nseg && j >= sg.off[k]) ? 1 : 0;
+  const int i = sg.beg[sgi] + (j - sg.off[sgi]);
+  const float gi = g[i];
+  adam_update(gi, fresh ? 0.f : mm[i], fresh ? 0.f : vv[i], b1, b2, eps, step_size, bc2_sqrt, mm[i], vv[i], p[i]);
+}
 __global__ void adam_segments_kernel(AdamSegments sg, float* __restrict__ p, const float* __restrict__ g,
                                      float* __restrict__ mm, float* __restrict__ vv,
                                      float step_size, float b1, float b2, float eps, float bc2_sqrt, int fresh) {
   PHASE_MARK(pz0);
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= sg.off[sg.nseg]) return;
-  int sgi = 0;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) sgi += (k < sg.nseg && j >= sg.off[k]) ? 1 : 0;
-  const int i = sg.beg[sgi] + (j - sg.off[sgi]);
-  const float gi = g[i];
-  const float m0 = fresh ? 0.f : mm[i], v0 = fresh ? 0.f : vv[i];
-  const float mi = b1 * m0 + (1.0f - b1) * gi;
-  const float vi = b2 * v0 + (1.0f - b2) * gi * gi;
-  mm[i] = mi;
-  vv[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] - step_size * (mi / denom);
+  adam_segments_element(sg, j, p, g, mm, vv, step_size, b1, b2, eps, bc2_sqrt, fresh != 0);
   PHASE_MARK(pz1);
   PHASE_END(PH_ADAM, pz0, pz1);
 }
 
 // The same step for a captured HIP graph: the launch parameters of a graph node are frozen, so the step count comes from a
-// device counter (advanced by tick_kernel at the head of every replay) and the bias corrections are formed here, in
-// double like torch's python-side scalars (1 - beta^t; beta1 = 0.5 is exact, pow is accurate to the last bit or two of
-// the double, far below the float32 the result is rounded to).
+// device counter (advanced by tick_kernel at the head of every replay) and the bias terms are formed here.
 __global__ void tick_kernel(int* counter) { *counter += 1; }
 __global__ void set_counter_kernel(int* counter, int value) { *counter = value; }
 __global__ void adam_segments_graph_kernel(AdamSegments sg, float* __restrict__ p, const float* __restrict__ g,
@@ -898,21 +881,9 @@ __global__ void adam_segments_graph_kernel(AdamSegments sg, float* __restrict__ 
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= sg.off[sg.nseg]) return;
   const int t = *step_counter;
-  const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-  const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  const bool fresh = t == 1;
-  int sgi = 0;
-#pragma unroll
-  for (int k = 1; k < 4; ++k) sgi += (k < sg.nseg && j >= sg.off[k]) ? 1 : 0;
-  const int i = sg.beg[sgi] + (j - sg.off[sgi]);
-  const float gi = g[i];
-  const float m0 = fresh ? 0.f : mm[i], v0 = fresh ? 0.f : vv[i];
-  const float mi = b1 * m0 + (1.0f - b1) * gi;
-  const float vi = b2 * v0 + (1.0f - b2) * gi * gi;
-  mm[i] = mi;
-  vv[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] - step_size * (mi / denom);
+  float step_size, bc2_sqrt;
+  adam_bias_terms(lr, b1, b2, t, step_size, bc2_sqrt);
+  adam_segments_element(sg, j, p, g, mm, vv, step_size, b1, b2, eps, bc2_sqrt, t == 1);
 }
 
 // Frame-sharded fitting, per-rank record of one iteration (smalify_amd/distributed.py): the rank's partial gradient of
@@ -946,13 +917,7 @@ __global__ void shard_reduce_adam_kernel(int world, int stride, const float* __r
   for (int r = 0; r < world; ++r) gi += gathered[(size_t)r * stride + i];
   g[i] = gi;
   if (i >= ns_train) return;
-  const float m0 = fresh ? 0.f : mm[i], v0 = fresh ? 0.f : vv[i];
-  const float mi = b1 * m0 + (1.0f - b1) * gi;
-  const float vi = b2 * v0 + (1.0f - b2) * gi * gi;
-  mm[i] = mi;
-  vv[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] - step_size * (mi / denom);
+  adam_update(gi, fresh ? 0.f : mm[i], fresh ? 0.f : vv[i], b1, b2, eps, step_size, bc2_sqrt, mm[i], vv[i], p[i]);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -297,8 +297,8 @@ __global__ __launch_bounds__(256) void mesh3d_sample_kernel(MeshTargetsDev t, in
 }
 
 // ---- Adam on all trained parameters of a Stage.step in one launch ----------------------------------------------------
-// same arithmetic as adam_kernel (torch.optim.Adam, eps outside the bias-corrected sqrt); a segment's gradient may be a
-// column block of a wider row-major buffer (global_rot / joint_rot are columns 0..2 / 3..104 of d theta [N][105])
+// torch.optim.Adam (adam_update) over the trained parameters, one launch; a segment's gradient may be a column block of a
+// wider row-major buffer (global_rot / joint_rot are columns 0..2 / 3..104 of d theta [N][105])
 struct Fit3dAdamSeg {
   float* p;
   const float* g;
@@ -325,10 +325,9 @@ __global__ __launch_bounds__(256) void fit3d_adam_kernel(Fit3dAdamArgs a) {
   if (i >= sg.count) return;
   const int row = i / sg.row_len, col = i - row * sg.row_len;
   const float gi = sg.g[(size_t)row * sg.g_stride + sg.g_offset + col];
-  const float mi = a.b1 * sg.m[i] + (1.0f - a.b1) * gi;
-  const float vi = a.b2 * sg.v[i] + (1.0f - a.b2) * gi * gi;
-  sg.m[i] = mi;
-  sg.v[i] = vi;
-  const float denom = sqrtf(vi) / a.bc2_sqrt + a.eps;
-  sg.p[i] = sg.p[i] - sg.step_size * (mi / denom);
+  // read in this order (gradient, b1, m, b2, v): the order of the loads decides which product of each moment update the
+  // compiler fuses into a multiply-add, and with it the rounding of m and v (b1 = 0.9 in the 3D fitter: neither product
+  // is exact); this order keeps the bits this kernel has always produced
+  const float b1 = a.b1, m0 = sg.m[i], b2 = a.b2, v0 = sg.v[i];
+  adam_update(gi, m0, v0, b1, b2, a.eps, sg.step_size, a.bc2_sqrt, sg.m[i], sg.v[i], sg.p[i]);
 }

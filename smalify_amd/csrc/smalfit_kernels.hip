@@ -22,7 +22,7 @@
 //   face_bbox / raster_sweep / raster_resolve / raster_band / raster_select / raster_bwd
 //                       p3d_renderer.py:26-39,65-66 (pytorch3d rasterize_meshes + sigmoid_alpha_blend)
 //   vertex_bwd, lbs_bwd_mid, chain_bwd, assemble    autograd of the above (optimize_to_joints.py:136)
-//   adam_kernel         optimize_to_joints.py:96,137 (torch.optim.Adam, betas=(0.5,0.999))
+//   adam_segments_kernel  optimize_to_joints.py:96,137 (torch.optim.Adam, betas=(0.5,0.999))
 //   mesh3d_*            fitter_3d/trainer.py:205-227 (pytorch3d sample_points_from_meshes, chamfer_distance, mesh_edge_loss,
 //                       mesh_normal_consistency, mesh_laplacian_smoothing) and their adjoints
 #include <hip/hip_runtime.h>

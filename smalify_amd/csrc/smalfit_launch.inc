@@ -1126,10 +1126,10 @@ int smalfit_temporal(smalfit_engine* e, void* stream, int N, float w_temp, const
 }
 
 namespace smalfit {
-static int launch_adam_segments(hipStream_t st, const smalfit_adam_args* o, int t) {
+// the ranges of `o` packed for the segment kernels, checked: every launch of them (eager, graph node) goes through here
+static int pack_adam_segments(const smalfit_adam_args* o, AdamSegments& sg) {
   if (!o->param || !o->grad || !o->exp_avg || !o->exp_avg_sq) return fail("smalfit adam: null buffer");
   if (o->num_segments < 0 || o->num_segments > 4) return fail("smalfit adam: at most 4 segments");
-  AdamSegments sg;
   std::memset(&sg, 0, sizeof(sg));
   sg.nseg = o->num_segments;
   int total = 0;
@@ -1140,22 +1140,34 @@ static int launch_adam_segments(hipStream_t st, const smalfit_adam_args* o, int 
     total += o->seg_end[k] - o->seg_begin[k];
   }
   for (int k = sg.nseg; k <= 4; ++k) sg.off[k] = total;
+  return 0;
+}
+
+// optimizer.step() with the hyperparameters of `o` on the packed ranges at the 1-based step t; fresh: the moments are
+// taken as zero instead of being read
+static int launch_adam_segments(hipStream_t st, const AdamSegments& sg, const smalfit_adam_args* o, int t, bool fresh) {
+  const int total = sg.off[sg.nseg];
   if (total == 0) return 0;
-  // scalars in double like torch's python-side bias corrections
-  const double bc1 = 1.0 - pow((double)o->beta1, (double)t);
-  const double bc2 = 1.0 - pow((double)o->beta2, (double)t);
-  adam_segments_kernel<<<(total + 255) / 256, 256, 0, st>>>(sg, o->param, o->grad, o->exp_avg, o->exp_avg_sq,
-                                                           (float)((double)o->lr / bc1), o->beta1, o->beta2, o->eps,
-                                                           (float)sqrt(bc2), t == 1 ? 1 : 0);
+  float step_size, bc2_sqrt;
+  adam_bias_terms(o->lr, o->beta1, o->beta2, t, step_size, bc2_sqrt);
+  adam_segments_kernel<<<(total + 255) / 256, 256, 0, st>>>(sg, o->param, o->grad, o->exp_avg, o->exp_avg_sq, step_size,
+                                                           o->beta1, o->beta2, o->eps, bc2_sqrt, fresh ? 1 : 0);
   LAUNCH_OK("adam_segments_kernel");
   return 0;
+}
+
+// the next step of the optimiser `o` describes: t = o->step + 1, and the first step of a stage does not read the moments
+static int launch_adam_next_step(hipStream_t st, const smalfit_adam_args* o) {
+  AdamSegments sg;
+  if (pack_adam_segments(o, sg)) return 1;
+  return launch_adam_segments(st, sg, o, o->step + 1, o->step == 0);
 }
 }  // namespace smalfit
 
 int smalfit_adam_segments(void* stream, const smalfit_adam_args* o) {
   if (!o) return fail("smalfit_adam_segments: null argument");
   if (o->step < 0) return fail("smalfit_adam_segments: step must be >= 0");
-  return launch_adam_segments((hipStream_t)stream, o, o->step + 1);
+  return launch_adam_next_step((hipStream_t)stream, o);
 }
 
 int smalfit_engine_set_graph(smalfit_engine* e, int enable) {
@@ -1166,13 +1178,8 @@ int smalfit_engine_set_graph(smalfit_engine* e, int enable) {
 }
 
 namespace smalfit {
-static int launch_adam_graph_node(smalfit_engine* e, hipStream_t st, const smalfit_adam_args* o) {
-  AdamSegments sg;
-  std::memset(&sg, 0, sizeof(sg));
-  sg.nseg = o->num_segments;
-  int total = 0;
-  for (int k = 0; k < sg.nseg; ++k) { sg.beg[k] = o->seg_begin[k]; sg.off[k] = total; total += o->seg_end[k] - o->seg_begin[k]; }
-  for (int k = sg.nseg; k <= 4; ++k) sg.off[k] = total;
+static int launch_adam_graph_node(smalfit_engine* e, hipStream_t st, const AdamSegments& sg, const smalfit_adam_args* o) {
+  const int total = sg.off[sg.nseg];
   if (total == 0) return 0;
   adam_segments_graph_kernel<<<(total + 255) / 256, 256, 0, st>>>(sg, o->param, o->grad, o->exp_avg, o->exp_avg_sq, e->step_counter,
                                                                  o->lr, o->beta1, o->beta2, o->eps);
@@ -1185,7 +1192,8 @@ int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, 
   if (!e || !a || !o) return fail("smalfit_fit_run: null argument");
   if (iterations <= 0) return fail("smalfit_fit_run: iterations must be positive");
   if (o->step < 0) return fail("smalfit_fit_run: step must be >= 0");
-  if (o->num_segments < 0 || o->num_segments > 4) return fail("smalfit_fit_run: at most 4 segments");
+  AdamSegments sg;
+  if (pack_adam_segments(o, sg)) return 1;
   hipStream_t st = (hipStream_t)stream;
   if (e->use_graph && !e->prof_on && iterations >= 2 && st != nullptr) {
     // one iteration (tick, the evaluation's kernels, Adam) captured once per (arguments, stream) and replayed
@@ -1204,7 +1212,7 @@ int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, 
       HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
       tick_kernel<<<1, 1, 0, st>>>(e->step_counter);
       int rc = smalfit_fit_eval(e, stream, a);
-      if (!rc) rc = launch_adam_graph_node(e, st, o);
+      if (!rc) rc = launch_adam_graph_node(e, st, sg, o);
       const hipError_t ce = hipStreamEndCapture(st, &graph);
       if (rc) { if (graph) (void)hipGraphDestroy(graph); return 1; }
       if (ce != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
@@ -1219,8 +1227,9 @@ int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, 
     return 0;
   }
   for (int it = 0; it < iterations; ++it) {
+    const int t = o->step + it + 1;
     if (smalfit_fit_eval(e, stream, a)) return 1;
-    if (launch_adam_segments(st, o, o->step + it + 1)) return 1;
+    if (launch_adam_segments(st, sg, o, t, t == 1)) return 1;
   }
   return 0;
 }
@@ -1241,7 +1250,7 @@ int smalfit_shard_local_step(smalfit_engine* e, void* stream, const smalfit_fit_
   if (!e || !a || !o || !record || !shared_grad) return fail("smalfit_shard_local_step: null argument");
   if (o->step < 0) return fail("smalfit_shard_local_step: step must be >= 0");
   if (smalfit_fit_eval(e, stream, a)) return 1;
-  if (launch_adam_segments((hipStream_t)stream, o, o->step + 1)) return 1;
+  if (launch_adam_next_step((hipStream_t)stream, o)) return 1;
   return smalfit_shard_record(stream, num_shared, shared_grad, a->num_frames, a->global_rotation, a->joint_rotations, a->trans,
                               a->global_mask ? a->global_mask : e->ones, a->rotation_mask ? a->rotation_mask : e->ones, record);
 }
@@ -1251,13 +1260,11 @@ int smalfit_shard_reduce_step(void* stream, int world_size, int record_stride, c
   if (world_size <= 0 || record_stride < num_shared || !gathered || num_shared <= 0 || num_trainable < 0 || num_trainable > num_shared || !o)
     return fail("smalfit_shard_reduce_step: bad argument");
   if (!o->param || !o->grad || !o->exp_avg || !o->exp_avg_sq || o->step < 0) return fail("smalfit_shard_reduce_step: bad optimiser state");
-  const int t = o->step + 1;
-  const double bc1 = 1.0 - pow((double)o->beta1, (double)t);
-  const double bc2 = 1.0 - pow((double)o->beta2, (double)t);
+  float step_size, bc2_sqrt;
+  adam_bias_terms(o->lr, o->beta1, o->beta2, o->step + 1, step_size, bc2_sqrt);
   shard_reduce_adam_kernel<<<(num_shared + 255) / 256, 256, 0, (hipStream_t)stream>>>(world_size, record_stride, gathered, num_shared, num_trainable,
-                                                                                   o->param, o->grad, o->exp_avg, o->exp_avg_sq,
-                                                                                   (float)((double)o->lr / bc1), o->beta1, o->beta2, o->eps,
-                                                                                   (float)sqrt(bc2), t == 1 ? 1 : 0);
+                                                                                   o->param, o->grad, o->exp_avg, o->exp_avg_sq, step_size,
+                                                                                   o->beta1, o->beta2, o->eps, bc2_sqrt, o->step == 0 ? 1 : 0);
   LAUNCH_OK("shard_reduce_adam_kernel");
   return 0;
 }
@@ -1299,14 +1306,14 @@ int smalfit_shard_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a
 int smalfit_adam_step(void* stream, int count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                       float lr, float beta1, float beta2, float eps, int t) {
   if (count <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || t <= 0) return fail("smalfit_adam_step: bad argument");
-  // scalars in double like torch's python-side bias corrections
-  const double bc1 = 1.0 - pow((double)beta1, (double)t);
-  const double bc2 = 1.0 - pow((double)beta2, (double)t);
-  adam_kernel<<<(count + 255) / 256, 256, 0, (hipStream_t)stream>>>(count, param, grad, exp_avg, exp_avg_sq,
-                                                                    (float)((double)lr / bc1), beta1, beta2, eps,
-                                                                    (float)sqrt(bc2));
-  LAUNCH_OK("adam_kernel");
-  return 0;
+  // one range [0, count); the moments are always read, also at t = 1
+  smalfit_adam_args o{};
+  o.param = param; o.grad = const_cast<float*>(grad); o.exp_avg = exp_avg; o.exp_avg_sq = exp_avg_sq;
+  o.num_segments = 1; o.seg_begin[0] = 0; o.seg_end[0] = count;
+  o.lr = lr; o.beta1 = beta1; o.beta2 = beta2; o.eps = eps;
+  AdamSegments sg;
+  if (pack_adam_segments(&o, sg)) return 1;
+  return launch_adam_segments((hipStream_t)stream, sg, &o, t, false);
 }
 
 }  // extern "C"

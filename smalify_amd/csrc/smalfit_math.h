@@ -398,4 +398,30 @@ SMALFIT_HD float log2_one_minus_prob(float d) {
 // one definition, so pixel centres agree bitwise between them)
 SMALFIT_HD float pix_to_ndc(int i, float inv_s) { return fmaf((float)i, -2.0f * inv_s, 1.0f - inv_s); }
 
+// ------------------------------------------------------------------------------------------------
+// Adam (torch.optim.Adam semantics: eps outside the bias-corrected sqrt): the one definition every optimiser kernel uses
+// ------------------------------------------------------------------------------------------------
+// bias terms of the 1-based step t, in double like torch's python-side scalars and rounded to float once:
+// step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)  (beta1 = 0.5 makes 1 - beta1^t exact; pow is accurate to
+// the last bit or two of the double, far below the float32 the results are rounded to)
+SMALFIT_HD void adam_bias_terms(float lr, float beta1, float beta2, int t, float& step_size, float& bc2_sqrt) {
+  const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+  step_size = (float)((double)lr / bc1);
+  bc2_sqrt = (float)sqrt(bc2);
+}
+
+// one element: the incoming moments m0 / v0 (the caller passes 0 on the first step of a stage instead of reading them:
+// b * 0 + x == x exactly, the same bits as stepping from zero-filled moments), the new moments out, the parameter p updated
+// in place -- stored in that order, with the operand order of every expression fixed (the multiply-adds contract alike in
+// every kernel)
+SMALFIT_HD void adam_update(float g, float m0, float v0, float b1, float b2, float eps, float step_size, float bc2_sqrt,
+                            float& m, float& v, float& p) {
+  const float mi = b1 * m0 + (1.0f - b1) * g;
+  const float vi = b2 * v0 + (1.0f - b2) * g * g;
+  m = mi;
+  v = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p = p - step_size * (mi / denom);
+}
+
 }  // namespace smalfit

@@ -280,10 +280,8 @@ int smalfit_fit3d_step(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mes
   }
 
   // torch.optim.Adam over the parameters of the scheme, one launch
-  const double bc1 = 1.0 - pow((double)a->beta1, (double)a->adam_t);
-  const double bc2 = 1.0 - pow((double)a->beta2, (double)a->adam_t);
   Fit3dAdamArgs ad{};
-  ad.b1 = a->beta1; ad.b2 = a->beta2; ad.eps = a->eps; ad.bc2_sqrt = (float)sqrt(bc2);
+  ad.b1 = a->beta1; ad.b2 = a->beta2; ad.eps = a->eps;
   const float* grads[kFit3dParams] = {m->gbetas, e->dtheta, e->dtheta, m->dtrans, m->dverts};
   const int counts[kFit3dParams] = {N * nb, N * 3, N * 102, N * 3, N * md.V * 3};
   const int row_len[kFit3dParams] = {nb, 3, 102, 3, md.V * 3};
@@ -295,7 +293,7 @@ int smalfit_fit3d_step(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mes
     Fit3dAdamSeg& sg = ad.seg[ad.nseg++];
     sg.p = tr[k].p; sg.g = grads[k]; sg.m = tr[k].mm; sg.v = tr[k].vv;
     sg.count = counts[k]; sg.row_len = row_len[k]; sg.g_stride = g_stride[k]; sg.g_offset = g_offset[k];
-    sg.step_size = (float)((double)tr[k].lr / bc1);
+    adam_bias_terms(tr[k].lr, a->beta1, a->beta2, a->adam_t, sg.step_size, ad.bc2_sqrt);   // (bc2_sqrt: the same for every lr)
     sg.block0 = blocks;
     blocks += (counts[k] + 255) / 256;
   }

@@ -232,20 +232,26 @@ class FusedFitter:
         return tuple(None if t is None else t.data_ptr() for t in
                      (self.global_mask, self.rotation_mask, self.target_joints, vis, self.target_sil, self.halo_prev, self.halo_next))
 
-    def _stage_plan(self, weights, w_temp, lr, stage_id, names):
-        """argument blocks of the stage's iterations, rebuilt only when something they depend on changes.  The halo buffers
-        (like the masks, targets and visibility tensors: _pointer_key) enter the key by ADDRESS (the block holds raw device pointers): ShardedFitter hands out views of one persistent
-        gather buffer, so the key is stable across iterations; a caller that allocates fresh halo tensors every step gets a
-        fresh block every step -- correct, but it pays the ~100 us of marshalling each time (reuse the buffers instead)."""
-        key = (tuple(float(w) for w in weights), float(w_temp), float(lr), stage_id, tuple(names), self.use_joint_limits) + self._pointer_key(stage_id)
-        plans = self._plan if isinstance(getattr(self, "_plan", None), dict) else {}
+    def _cached_blocks(self, kind, weights, w_temp, lr, stage_id, names, build, extra=(), keep=()):
+        """argument blocks of one kind of call in one stage, (fit args,) + build(), built once per key.  A block holds raw
+        device pointers, so the key holds the address of every tensor it points at: _pointer_key for the fit args, `extra`
+        for whatever build()'s blocks point at (`keep`: those tensors, held with the blocks).  ShardedFitter's halos are views
+        of one persistent gather buffer, so the key is stable across iterations; a caller that allocates fresh halo tensors
+        every step gets a fresh block every step -- correct, but it pays the ~100 us of marshalling each time."""
+        key = (kind, tuple(float(w) for w in weights), float(w_temp), float(lr), stage_id, tuple(names), self.use_joint_limits) \
+            + tuple(extra) + self._pointer_key(stage_id)
+        plans = self._plan or {}
         if key not in plans:
             if len(plans) > 8:
                 plans.clear()
-            fa, _, _, keep = self._fit_args(weights, w_temp, stage_id, names)
-            plans[key] = (fa, self._adam_args(names, lr), keep)
+            fa, _, _, held = self._fit_args(weights, w_temp, stage_id, names)
+            plans[key] = ((fa,) + build(), held + list(keep))
         self._plan = plans
-        fa, aa, _ = plans[key]
+        return plans[key][0]
+
+    def _stage_plan(self, weights, w_temp, lr, stage_id, names):
+        """argument blocks of the stage's iterations (smalfit_fit_run)"""
+        fa, aa = self._cached_blocks("fit_run", weights, w_temp, lr, stage_id, names, lambda: (self._adam_args(names, lr),))
         aa.step = self.step_count
         return fa, aa
 
@@ -273,21 +279,22 @@ class FusedFitter:
     def num_shared(self):
         return 20 + (6 if self.ls_shared else 0)
 
+    def _split_trainable(self, names):
+        """a stage's trainable set -> (the names each rank steps on its own: the per-frame tensors, and the limb scales when
+        they are per frame; the number of trained shared floats: betas, and the limb scales when they are shared)"""
+        local = tuple(k for k in names if k not in ("betas", "log_beta_scales") or (k == "log_beta_scales" and not self.ls_shared))
+        ntrain = 0
+        if "betas" in names:
+            ntrain = 20 + (6 if (self.ls_shared and "log_beta_scales" in names) else 0)
+        return local, ntrain
+
     def local_step(self, weights, w_temp, lr, stage_id, record):
         """evaluation + Adam on the per-frame parameters + this rank's record (partial shared gradient | boundary
         frames after the step) written into `record` (num_shared() + 216 floats)"""
         self.assert_joint_limits()
         names = self.trainable(stage_id)
-        local = tuple(k for k in names if k not in ("betas", "log_beta_scales") or (k == "log_beta_scales" and not self.ls_shared))
-        key = (tuple(float(w) for w in weights), float(w_temp), float(lr), stage_id, tuple(names), "sharded", self.use_joint_limits) + self._pointer_key(stage_id)
-        plans = self._plan if isinstance(getattr(self, "_plan", None), dict) else {}
-        if key not in plans:
-            if len(plans) > 8:
-                plans.clear()
-            fa, _, _, keep = self._fit_args(weights, w_temp, stage_id, names)
-            plans[key] = (fa, self._adam_args(local, lr), keep)
-        self._plan = plans
-        fa, aa, _ = plans[key]
+        local, _ = self._split_trainable(names)
+        fa, aa = self._cached_blocks("sharded", weights, w_temp, lr, stage_id, names, lambda: (self._adam_args(local, lr),))
         aa.step = self.step_count
         eng.shard_local_step(self.e, fa, aa, self.num_shared(), self.grad, record)
 
@@ -297,25 +304,18 @@ class FusedFitter:
         rank-ordered reduction + shared Adam, all enqueued from C.  halo_prev / halo_next must be views of `gathered`."""
         self.assert_joint_limits()
         names = self.trainable(stage_id)
-        local = tuple(k for k in names if k not in ("betas", "log_beta_scales") or (k == "log_beta_scales" and not self.ls_shared))
-        ntrain = 0
-        if "betas" in names:
-            ntrain = 20 + (6 if (self.ls_shared and "log_beta_scales" in names) else 0)
-        key = (tuple(float(w) for w in weights), float(w_temp), float(lr), stage_id, tuple(names), "shard_run", self.use_joint_limits,
-               rank, world_size, record.data_ptr(), gathered.data_ptr(), int(allgather), int(allgather_ctx or 0)) + self._pointer_key(stage_id)
-        plans = self._plan if isinstance(getattr(self, "_plan", None), dict) else {}
-        if key not in plans:
-            if len(plans) > 8:
-                plans.clear()
-            fa, _, _, keep = self._fit_args(weights, w_temp, stage_id, names)
+        local, ntrain = self._split_trainable(names)
+
+        def build():
             sa = eng.ShardArgs()
             sa.world_size, sa.rank, sa.num_shared, sa.num_trainable_shared = int(world_size), int(rank), self.num_shared(), ntrain
             sa.shared_grad, sa.record, sa.gathered = eng._ptr(self.grad), eng._ptr(record), eng._ptr(gathered)
             sa.allgather, sa.allgather_ctx = int(allgather), allgather_ctx
-            plans[key] = (fa, self._adam_args(local, lr), eng.make_adam_args(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, [], lr), sa,
-                          keep + [record, gathered])
-        self._plan = plans
-        fa, al, ash, sa, _ = plans[key]
+            return self._adam_args(local, lr), eng.make_adam_args(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, [], lr), sa
+
+        fa, al, ash, sa = self._cached_blocks(
+            "shard_run", weights, w_temp, lr, stage_id, names, build, keep=(record, gathered),
+            extra=(rank, world_size, record.data_ptr(), gathered.data_ptr(), int(allgather), int(allgather_ctx or 0)))
         al.step = ash.step = self.step_count
         eng.shard_run(self.e, fa, al, ash, sa, iterations)
         self.step_count = al.step
@@ -324,10 +324,7 @@ class FusedFitter:
     def shared_step(self, gathered, world_size, lr, stage_id):
         """sum of the ranks' partial shared gradients + Adam on the shared parameters the stage trains; closes the
         iteration (advances the step count)"""
-        names = self.trainable(stage_id)
-        ntrain = 0
-        if "betas" in names:
-            ntrain = 20 + (6 if (self.ls_shared and "log_beta_scales" in names) else 0)
+        _, ntrain = self._split_trainable(self.trainable(stage_id))
         aa = eng.make_adam_args(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, [], lr, step=self.step_count)
         eng.shard_reduce_step(world_size, gathered.shape[-1], gathered, self.num_shared(), ntrain, aa)
         self.step_count += 1

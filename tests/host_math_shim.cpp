@@ -118,6 +118,15 @@ void hm_global_rigid_bwd(int n, const float* Rs, const float* Js, const int* par
                            dRs + (size_t)i * 315, dJs + (size_t)i * 105, logscale ? dls + (size_t)i * 6 : nullptr);
 }
 
+// the optimiser kernels' Adam on the host: the bias terms of the 1-based step t into bias[0] (step_size), bias[1] (bc2_sqrt),
+// then the update of n elements (fresh: the moments are taken as zero instead of being read, as on a stage's first step)
+void hm_adam(int n, float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps, int t, int fresh,
+             float* bias) {
+  adam_bias_terms(lr, b1, b2, t, bias[0], bias[1]);
+  for (int i = 0; i < n; ++i)
+    adam_update(g[i], fresh ? 0.f : m[i], fresh ? 0.f : v[i], b1, b2, eps, bias[0], bias[1], m[i], v[i], p[i]);
+}
+
 void hm_camera(int n, const float* p, const float* g2, float* ndc, float* g3) {
   for (int i = 0; i < n; ++i) {
     world_to_ndc(p[3 * i], p[3 * i + 1], p[3 * i + 2], ndc[3 * i], ndc[3 * i + 1], ndc[3 * i + 2]);

@@ -1,7 +1,8 @@
 """CPU check of the per-element device maths (smalify_amd/csrc/smalfit_math.h compiled for the host by
-g++, test-only shim) against the oracle: Rodrigues fwd/bwd, camera fwd/bwd, and the per (pixel, face)
-silhouette evaluation incl. the K-nearest depth threshold, on the full-size synthetic mesh."""
+g++, test-only shim) against the oracle: Rodrigues fwd/bwd, camera fwd/bwd, the per (pixel, face)
+silhouette evaluation incl. the K-nearest depth threshold, on the full-size synthetic mesh, and Adam."""
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -48,6 +49,45 @@ def test_rodrigues_host(shim):
     err = np.linalg.norm(dth - t.grad.numpy()) / np.linalg.norm(t.grad.numpy())
     assert err < 2e-5, err
     assert np.abs(dth[0] - t.grad.numpy()[0]).max() < 1e-5       # theta = 0: generators, finite
+
+
+def test_adam_host(shim):
+    """adam_bias_terms / adam_update (the arithmetic of every optimiser kernel): the bias terms bit-equal to torch's
+    python-side scalars rounded to float32, 20 steps against a float64 replica of torch.optim.Adam's update, and a stage's
+    first step (moments taken as zero, not read) the same bits as a step from zero-filled moments"""
+    f = C.c_float
+    shim.hm_adam.argtypes = [C.c_int] + [C.c_void_p] * 4 + [f] * 4 + [C.c_int, C.c_int, C.c_void_p]
+    lr, b1, b2, eps = (float(np.float32(x)) for x in (0.02, 0.5, 0.999, 1e-8))
+    bias = np.zeros(2, np.float32)
+    none = np.zeros(1, np.float32)
+    for t in range(1, 51):
+        shim.hm_adam(0, _p(none), _p(none), _p(none), _p(none), lr, b1, b2, eps, t, 0, _p(bias))
+        assert bias[0] == np.float32(lr / (1 - b1 ** t)) and bias[1] == np.float32(math.sqrt(1 - b2 ** t)), (t, bias)
+
+    rs = np.random.RandomState(3)
+    n = 1000
+    p = rs.randn(n).astype(np.float32)
+    m, v = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    p64, m64, v64 = p.astype(np.float64), np.zeros(n), np.zeros(n)
+    for t in range(1, 21):
+        g = (rs.randn(n) * 10.0 ** rs.uniform(-3, 1, n)).astype(np.float32)
+        shim.hm_adam(n, _p(p), _p(g), _p(m), _p(v), lr, b1, b2, eps, t, int(t == 1), _p(bias))
+        g64 = g.astype(np.float64)
+        m64 = b1 * m64 + (1 - b1) * g64
+        v64 = b2 * v64 + (1 - b2) * g64 * g64
+        p64 = p64 - lr / (1 - b1 ** t) * m64 / (np.sqrt(v64) / math.sqrt(1 - b2 ** t) + eps)
+        for got, want in ((m, m64), (v, v64), (p, p64)):
+            assert np.linalg.norm(got - want) / np.linalg.norm(want) < 1e-6, t
+
+    g = rs.randn(n).astype(np.float32)
+    p0 = rs.randn(n).astype(np.float32)
+    stale = rs.randn(2, n).astype(np.float32)
+    fresh = [p0.copy(), stale[0].copy(), stale[1].copy()]
+    zeros = [p0.copy(), np.zeros(n, np.float32), np.zeros(n, np.float32)]
+    shim.hm_adam(n, _p(fresh[0]), _p(g), _p(fresh[1]), _p(fresh[2]), lr, b1, b2, eps, 1, 1, _p(bias))
+    shim.hm_adam(n, _p(zeros[0]), _p(g), _p(zeros[1]), _p(zeros[2]), lr, b1, b2, eps, 1, 0, _p(bias))
+    for a, b in zip(fresh, zeros):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def test_camera_host(shim):
