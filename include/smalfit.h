@@ -242,7 +242,10 @@ int smalfit_fit_eval(smalfit_engine* engine, void* stream, const smalfit_fit_arg
  * with optimizer = torch.optim.Adam(model.parameters(), lr, betas=(0.5, 0.999)) created per stage (:96).
  * The fit parameters, their gradient and the two Adam moments are four flat device buffers of one layout (the caller
  * chooses it; the pointers inside smalfit_fit_args point into `param` / `grad`); the trainable tensors of the stage are
- * up to four [begin, end) ranges of that layout and are updated by ONE kernel launch per iteration.
+ * up to four [begin, end) ranges of that layout and are updated by ONE kernel launch per iteration -- or by none: when the
+ * ranges are exactly whole parameter tensors of `args` with their gradients at the same offsets of `grad`, the step of every
+ * iteration but the last is taken by the next iteration's first launch (same results, bit for bit; on return parameters,
+ * moments, gradients and losses are those of the last iteration either way).
  * step = optimiser steps already taken in this stage; when it is 0 the moments are taken as zero and not read, so a new
  * stage needs no fill.  Everything is enqueued on `stream`; nothing synchronises. */
 typedef struct smalfit_adam_args {

@@ -673,53 +673,27 @@ assemble_kernel(AssembleArgs a) {
   const int ph_role = (role < nbs) ? PH_ASM_BETA : PH_ASM_ELEM;
   if (role < nbs) {
     if (a.g_betas) {
+      // (the sums themselves: asm_beta_fetch / _slices / _total, kernels_lbs_forward.inc)
       const int s = role;
-      const int bl = t % 20, slice = t / 20;
-      // The shared-shape gradient is the sum of every frame's and every column block's partial, and in a fit that has settled those
-      // partials largely cancel: they are added in DOUBLE (round 6; fixed order as before) and rounded once.  That is the principled
-      // sum, but it moved no printed digit: config 3 after stage 1 stays at d/d betas 9.86e-6, d/d log scales 3.64e-5 off the float64
-      // oracle, as with the float32 running sum (profiles/r6_gpu_tests.log, profiles/r6_eval_fixture_tables.txt).
-      // One pass sums shape directions [b0, b0 + 20) in 12 slices each.
-      auto beta_pass = [&](int b0) {
-        const int b = b0 + bl;
-        if (slice < 12 && b < a.nb) {
-          double acc = 0.0;
-          const int nlo = a.betas_shared ? 0 : s, nhi = a.betas_shared ? M : s + 1;
-          for (int n = nlo + slice; n < nhi; n += 12) acc += (double)a.dbetaJ[(size_t)n * a.NBall + b];
-          const int nparts = a.nblk_beta * a.ngrp_beta;
-#pragma unroll 8
-          for (int blk = slice; blk < nparts; blk += 12) acc += (double)a.dbeta_part[((size_t)s * nparts + blk) * a.nb + b];
-          bsum[slice][bl] = acc;
-        }
+      for (int b0 = 0; b0 < a.nb; b0 += 20) {     // more than 20 directions (up to NBall): further passes (a.nb is block-uniform)
+        if (b0) __syncthreads();                  // the previous pass has read bsum
+        BetaOperands bo;
+        asm_beta_fetch(a, s, b0, bo);
+        asm_beta_slices(a, s, b0, bo, bsum);
         __syncthreads();
-        if (t < 20 && b0 + t < a.nb) {
-          double tot = 0.0;
-          for (int sl = 0; sl < 12; ++sl) tot += bsum[sl][t];
-          if (a.gb_prior && s == 0) tot += (double)a.gb_prior[b0 + t];
-          a.g_betas[s * a.nb + b0 + t] = (float)tot;
-        }
-      };
-      beta_pass(0);
-      for (int b0 = 20; b0 < a.nb; b0 += 20) {    // more than 20 directions (up to NBall): further passes (a.nb is block-uniform)
-        __syncthreads();                          // the previous pass has read bsum
-        beta_pass(b0);
+        const float tot = asm_beta_total(a, s, b0, bo, bsum);
+        if (t < 20 && b0 + t < a.nb) a.g_betas[s * a.nb + b0 + t] = tot;
       }
     }
   } else if ((role -= nbs) == 0) {
     if (a.g_ls) {
       if (a.ls_shared) {
-        // 6 scales x 32 frame slices
-        const int e = t & 7, sl = t >> 3;
-        double acc = 0.0;                  // (in double, like the shape gradient above)
-        if (e < 6) for (int n = sl; n < M; n += 32) acc += (double)a.dls[(size_t)n * 6 + e];
-        dpart[sl][e] = acc;                // then the 32 slices of each scale in a fixed order
+        LsOperands lo;
+        asm_ls_fetch(a, lo);
+        asm_ls_slices(a, lo, dpart);
         __syncthreads();
-        if (t < 6) {
-          double tot = 0.0;
-          for (int i = 0; i < 32; ++i) tot += dpart[i][t];
-          if (a.gls_prior) tot += (double)a.gls_prior[t];
-          a.g_ls[t] = (float)tot;
-        }
+        const float tot = asm_ls_total(a, lo, dpart);
+        if (t < 6) a.g_ls[t] = tot;
       } else {
         for (int i = t; i < M * 6; i += 256) a.g_ls[i] = a.dls[i];
       }
@@ -728,13 +702,8 @@ assemble_kernel(AssembleArgs a) {
     const int gt = role * 256 + t, gs = kAsmElem * 256;
     for (int i = gt; i < M * 3; i += gs) {
       const int n = i / 3, e = i % 3;
-      if (a.g_grot) a.g_grot[i] = a.dtheta[(size_t)n * 105 + e] * a.gmask[e];
-      if (a.g_trans) {
-        double acc = a.dtr_direct ? (double)a.dtr_direct[i] : 0.0;     // (the vertex blocks' partials cancel too: in double)
-#pragma unroll 16
-        for (int vt = 0; vt < a.nvt; ++vt) acc += (double)a.dtr_part[((size_t)vt * M + n) * 3 + e];
-        a.g_trans[i] = (float)acc;
-      }
+      if (a.g_grot) a.g_grot[i] = asm_grot_elem(a, n, e);
+      if (a.g_trans) a.g_trans[i] = asm_trans_elem(a, n, e);
     }
     if (a.g_jrot) {
       // eight elements per trip: loads first (clamped index), stores after -- as a loop of load-load-store the compiler kept
@@ -745,7 +714,7 @@ assemble_kernel(AssembleArgs a) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int i = min(i0 + u * gs, total - 1), n = i / 102, e = i % 102;
-          v[u] = a.dtheta[(size_t)n * 105 + 3 + e] * a.rmask[e];
+          v[u] = asm_jrot_elem(a, n, e);
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u)
@@ -884,6 +853,17 @@ __global__ void adam_segments_graph_kernel(AdamSegments sg, float* __restrict__ 
   float step_size, bc2_sqrt;
   adam_bias_terms(lr, b1, b2, t, step_size, bc2_sqrt);
   adam_segments_element(sg, j, p, g, mm, vv, step_size, b1, b2, eps, bc2_sqrt, t == 1);
+}
+
+// betas / shared limb scales from a slot of the engine's shared-parameter staging (smalfit_engine::shstate) back to the caller's flat buffers (one launch per smalfit_fit_run)
+__global__ void shared_state_restore_kernel(const float* __restrict__ slot, float* __restrict__ p, float* __restrict__ mm, float* __restrict__ vv,
+                                            int nbeta, int off_beta, int nls, int off_ls) {
+  const int t = threadIdx.x;
+  int i = -1, j = t;
+  if (t < nbeta) i = off_beta + t;
+  else if (t >= 20 && t < 20 + nls) i = off_ls + (t - 20);
+  if (i < 0) return;
+  p[i] = slot[j]; mm[i] = slot[32 + j]; vv[i] = slot[64 + j];
 }
 
 // Frame-sharded fitting, per-rank record of one iteration (smalify_amd/distributed.py): the rank's partial gradient of

@@ -1,6 +1,119 @@
 // LBS forward and per-frame losses (K0-K4) -- part of smalfit_kernels.hip (included inside namespace smalfit; not a translation unit of its own)
 
 // ------------------------------------------------------------------------------------------------
+// Gradient assembly roles: ONE definition for assemble_kernel and for the pending step of lbs_head_step_kernel (the same
+// operations in the same order: the same bits wherever they run).  Written for 256-thread blocks.  Each sum comes as a FETCH --
+// its first batch of operands requested unconditionally from clamped indices, so that a caller can have everything it reads in
+// flight at once -- and the additions, in the order of a plain loop over the operands.
+// ------------------------------------------------------------------------------------------------
+// d loss / d betas of shape set s, directions [b0, b0 + 20), in two halves around a block barrier: 12 slices of the frames' joint
+// paths and the column-block partials per direction, then the slices in order (+ the prior's share).
+// The shared-shape gradient is the sum of every frame's and every column block's partial, and in a fit that has settled those
+// partials largely cancel: they are added in DOUBLE (round 6; fixed order as before) and rounded once.  That is the principled
+// sum, but it moved no printed digit: config 3 after stage 1 stays at d/d betas 9.86e-6, d/d log scales 3.64e-5 off the float64
+// oracle, as with the float32 running sum (profiles/r6_gpu_tests.log, profiles/r6_eval_fixture_tables.txt).
+// Batches of 8 frames and 32 column-block partials per thread: one batch each at 64 frames of the SMAL mesh (as a plain loop,
+// every few additions waited for their own trip to memory: ten trips in a role that is one chain of latencies).
+constexpr int kAsmFr = 8, kAsmPa = 32, kAsmLs = 4;
+struct BetaOperands { float fv[kAsmFr], pv[kAsmPa], prior; };
+__device__ __forceinline__ void asm_beta_fetch(const AssembleArgs& a, int s, int b0, BetaOperands& o) {
+  const int t = threadIdx.x, slice = min(t / 20, 11), b = min(b0 + t % 20, a.nb - 1);
+  const int nlo = a.betas_shared ? 0 : s, nhi = a.betas_shared ? a.M : s + 1, nparts = a.nblk_beta * a.ngrp_beta;
+  const float* pj = a.dbetaJ + b;
+  const float* pp = a.dbeta_part + (size_t)s * nparts * a.nb + b;
+#pragma unroll
+  for (int u = 0; u < kAsmFr; ++u) o.fv[u] = pj[(size_t)min(nlo + slice + 12 * u, nhi - 1) * a.NBall];
+#pragma unroll
+  for (int u = 0; u < kAsmPa; ++u) o.pv[u] = pp[(size_t)min(slice + 12 * u, nparts - 1) * a.nb];
+  o.prior = (a.gb_prior && s == 0) ? a.gb_prior[min(b0 + min(t, 19), a.nb - 1)] : 0.f;     // thread t < 20: the prior's share of direction b0 + t
+}
+__device__ __forceinline__ void asm_beta_slices(const AssembleArgs& a, int s, int b0, BetaOperands& o, double (*bsum)[32]) {
+  const int t = threadIdx.x, bl = t % 20, slice = t / 20, b = b0 + bl;
+  if (slice < 12 && b < a.nb) {
+    const int nlo = a.betas_shared ? 0 : s, nhi = a.betas_shared ? a.M : s + 1, nparts = a.nblk_beta * a.ngrp_beta;
+    const float* pj = a.dbetaJ + b;
+    const float* pp = a.dbeta_part + (size_t)s * nparts * a.nb + b;
+    double acc = 0.0;
+    for (int n0 = nlo + slice; n0 < nhi; n0 += 12 * kAsmFr) {
+#pragma unroll
+      for (int u = 0; u < kAsmFr; ++u)
+        if (n0 + 12 * u < nhi) acc += (double)o.fv[u];
+      if (n0 + 12 * kAsmFr < nhi) {
+#pragma unroll
+        for (int u = 0; u < kAsmFr; ++u) o.fv[u] = pj[(size_t)min(n0 + 12 * (kAsmFr + u), nhi - 1) * a.NBall];
+      }
+    }
+    for (int k0 = slice; k0 < nparts; k0 += 12 * kAsmPa) {
+#pragma unroll
+      for (int u = 0; u < kAsmPa; ++u)
+        if (k0 + 12 * u < nparts) acc += (double)o.pv[u];
+      if (k0 + 12 * kAsmPa < nparts) {
+#pragma unroll
+        for (int u = 0; u < kAsmPa; ++u) o.pv[u] = pp[(size_t)min(k0 + 12 * (kAsmPa + u), nparts - 1) * a.nb];
+      }
+    }
+    bsum[slice][bl] = acc;
+  }
+}
+// ... behind the barrier: thread t < 20 returns direction b0 + t (valid where b0 + t < a.nb)
+__device__ __forceinline__ float asm_beta_total(const AssembleArgs& a, int s, int b0, const BetaOperands& o, double (*bsum)[32]) {
+  const int t = threadIdx.x;
+  double tot = 0.0;
+  if (t < 20 && b0 + t < a.nb) {
+    for (int sl = 0; sl < 12; ++sl) tot += bsum[sl][t];
+    if (a.gb_prior && s == 0) tot += (double)o.prior;
+  }
+  return (float)tot;
+}
+// d loss / d shared limb scales, likewise: 6 scales x 32 frame slices (in double, like the shape gradient), then thread t < 6
+// adds the 32 slices of scale t in a fixed order
+struct LsOperands { float lv[kAsmLs], prior; };
+__device__ __forceinline__ void asm_ls_fetch(const AssembleArgs& a, LsOperands& o) {
+  const int t = threadIdx.x, e = min(t & 7, 5), sl = t >> 3;
+#pragma unroll
+  for (int u = 0; u < kAsmLs; ++u) o.lv[u] = a.dls[(size_t)min(sl + 32 * u, a.M - 1) * 6 + e];
+  o.prior = a.gls_prior ? a.gls_prior[min(t, 5)] : 0.f;
+}
+__device__ __forceinline__ void asm_ls_slices(const AssembleArgs& a, LsOperands& o, double (*dpart)[8]) {
+  const int t = threadIdx.x, e = t & 7, sl = t >> 3;
+  double acc = 0.0;
+  if (e < 6)
+    for (int n0 = sl; n0 < a.M; n0 += 32 * kAsmLs) {
+#pragma unroll
+      for (int u = 0; u < kAsmLs; ++u)
+        if (n0 + 32 * u < a.M) acc += (double)o.lv[u];
+      if (n0 + 32 * kAsmLs < a.M) {
+#pragma unroll
+        for (int u = 0; u < kAsmLs; ++u) o.lv[u] = a.dls[(size_t)min(n0 + 32 * (kAsmLs + u), a.M - 1) * 6 + e];
+      }
+    }
+  dpart[sl][e] = acc;
+}
+__device__ __forceinline__ float asm_ls_total(const AssembleArgs& a, const LsOperands& o, double (*dpart)[8]) {
+  const int t = threadIdx.x;
+  double tot = 0.0;
+  if (t < 6) {
+    for (int i = 0; i < 32; ++i) tot += dpart[i][t];
+    if (a.gls_prior) tot += (double)o.prior;
+  }
+  return (float)tot;
+}
+// per-frame elements: masks on the axis-angle adjoint (component l of the frame's 105: the global rotation, then the joints);
+// the translation's direct part + the vertex blocks' partials
+__device__ __forceinline__ float asm_theta_elem(const AssembleArgs& a, int n, int l) {
+  const float* mk = (l < 3) ? a.gmask + l : a.rmask + max(l - 3, 0);
+  return a.dtheta[(size_t)n * 105 + l] * *mk;
+}
+__device__ __forceinline__ float asm_grot_elem(const AssembleArgs& a, int n, int e) { return asm_theta_elem(a, n, e); }
+__device__ __forceinline__ float asm_jrot_elem(const AssembleArgs& a, int n, int e) { return asm_theta_elem(a, n, 3 + e); }
+__device__ __forceinline__ float asm_trans_elem(const AssembleArgs& a, int n, int e) {
+  double acc = a.dtr_direct ? (double)a.dtr_direct[n * 3 + e] : 0.0;     // (the vertex blocks' partials cancel too: in double)
+#pragma unroll 16
+  for (int vt = 0; vt < a.nvt; ++vt) acc += (double)a.dtr_part[((size_t)vt * a.M + n) * 3 + e];
+  return (float)acc;
+}
+
+// ------------------------------------------------------------------------------------------------
 // K0: shape blend + rest joints
 // ------------------------------------------------------------------------------------------------
 
@@ -35,8 +148,99 @@ struct HeadArgs {
   const float* voff;         // [M][3][Vp] per-frame template offset (del_v + v_template override), or null
 };
 
+// The pending optimiser step (PendingStep, smalfit_fit_run): what assemble_kernel + adam_segments_kernel would have done behind the
+// previous evaluation, done here by the first -- and, for the per-frame tensors, the only -- reader of the stepped values.
+// A block requests everything the step reads in one go (pending_shared_fetch, pending_jrot_fetch, the caller's own operands),
+// computes, and meets at two barriers: slices of the shared gradients | their totals and Adam | the stepped values in LDS.
+constexpr int kPendingNb = 20;    // shape directions of the fitter (smalfit_fit_eval); the pending path holds a thread's operands in registers
+// LDS the stepped / staged shared parameters are handed over in: betas, then the (shared or this frame's) limb scales
+struct HeadShared {
+  float beta[kPendingNb], ls[8], grot[4];
+  double bsum[12][32], dpart[32][8];
+};
+struct AdamOperands { float p, m, v; };     // element i of a tensor as the step finds it
+__device__ __forceinline__ AdamOperands pending_load(const PendingStep& p, const PendingTensor& T, int i) {
+  return AdamOperands{T.p_in[i], p.fresh ? 0.f : T.m_in[i], p.fresh ? 0.f : T.v_in[i]};
+}
+__device__ __forceinline__ float pending_adam(const PendingStep& p, const PendingTensor& T, int i, const AdamOperands& o, float gi, bool store) {
+  float mi, vi, pv = o.p;
+  adam_update(gi, o.m, o.v, p.b1, p.b2, p.eps, p.step_size, p.bc2_sqrt, mi, vi, pv);
+  if (store) { T.m[i] = mi; T.v[i] = vi; T.p[i] = pv; T.g[i] = gi; }
+  return pv;
+}
+// the shared tensors (every block of the launch, redundantly): operands of the gradients' slices and, in the threads that will
+// step them, the parameters as they are
+struct SharedOperands { AdamOperands beta, ls; BetaOperands bo; LsOperands lo; };
+// (an untrained tensor's PendingTensor names the tensor itself as p_in / m_in / v_in: the same loads fetch it as it is.  n: the
+// frame whose limb scales are staged when they are per frame -- their step, if any, is pending_frame_extras')
+__device__ __forceinline__ void pending_shared_fetch(const PendingStep& p, const HeadArgs& a, int n, SharedOperands& o) {
+  const int t = threadIdx.x;
+  o.beta = pending_load(p, p.betas, min(t, 19));
+  if (p.betas.train) asm_beta_fetch(p.g, 0, 0, o.bo);
+  if (a.logscale) {
+    if (p.g.ls_shared) o.ls = pending_load(p, p.ls, min(t, 5));
+    else if (!p.ls.train) o.ls.p = a.logscale[(size_t)n * a.ls_stride + min(t, 5)];
+    if (p.ls.train && p.g.ls_shared) asm_ls_fetch(p.g, o.lo);
+  }
+}
+__device__ __forceinline__ void pending_shared_slices(const PendingStep& p, SharedOperands& o, HeadShared& sh) {
+  if (p.betas.train) asm_beta_slices(p.g, 0, 0, o.bo, sh.bsum);
+  if (p.ls.train && p.g.ls_shared) asm_ls_slices(p.g, o.lo, sh.dpart);
+}
+// behind the first barrier: totals, Adam, and the values every thread of the block reads from LDS after one more barrier; block
+// 0 stores
+__device__ __forceinline__ void pending_shared_step(const PendingStep& p, const HeadArgs& a, const SharedOperands& o, HeadShared& sh) {
+  const int t = threadIdx.x;
+  const bool store = blockIdx.x == 0;
+  if (p.betas.train) {
+    const float gi = asm_beta_total(p.g, 0, 0, o.bo, sh.bsum);
+    if (t < 20) sh.beta[t] = pending_adam(p, p.betas, t, o.beta, gi, store);
+  } else if (t < 20) {
+    sh.beta[t] = o.beta.p;
+  }
+  if (a.logscale && (p.g.ls_shared || !p.ls.train)) {
+    if (p.ls.train) {
+      const float gi = asm_ls_total(p.g, o.lo, sh.dpart);
+      if (t < 6) sh.ls[t] = pending_adam(p, p.ls, t, o.ls, gi, store);
+    } else if (t < 6) {
+      sh.ls[t] = o.ls.p;
+    }
+  }
+}
+// frame n's own parameters.  Thread 3 <= l < 105 owns joint-rotation component l - 3: its operands, requested unconditionally
+// (an untrained tensor's PendingTensor names the tensor itself as p_in / m_in / v_in: readable) ...
+struct ThetaOperands { AdamOperands ao; float gi; };
+__device__ __forceinline__ void pending_jrot_fetch(const PendingStep& p, int n, ThetaOperands& o) {
+  const int l = max(min((int)threadIdx.x, 104), 3);
+  o.ao = pending_load(p, p.jrot, n * 102 + (l - 3));
+  o.gi = asm_theta_elem(p.g, n, l);
+}
+// ... and its step: returns the component (unmasked) as the pose block goes on with it
+__device__ __forceinline__ float pending_jrot_step(const PendingStep& p, int n, const ThetaOperands& o) {
+  const int l = threadIdx.x;
+  if (l >= 3 && l < 105 && p.jrot.train) return pending_adam(p, p.jrot, n * 102 + (l - 3), o.ao, o.gi, true);
+  return o.ao.p;
+}
+// the frame's small tensors, three or six threads each in the waves that own no joint rotation: the translation in the third, the
+// global rotation (handed to threads l < 3 through LDS: they meet two barriers before they need it) and the frame's limb scales,
+// when those are per frame, in the fourth
+__device__ __forceinline__ void pending_frame_extras(const PendingStep& p, int n, HeadShared& sh) {
+  const int l = threadIdx.x;
+  if (l >= 128 && l < 131) {
+    const int i = n * 3 + (l - 128);
+    if (p.trans.train) pending_adam(p, p.trans, i, pending_load(p, p.trans, i), asm_trans_elem(p.g, n, l - 128), true);
+  } else if (l >= 224 && l < 227) {
+    const int i = n * 3 + (l - 224);
+    const AdamOperands ao = pending_load(p, p.grot, i);
+    sh.grot[l - 224] = p.grot.train ? pending_adam(p, p.grot, i, ao, asm_theta_elem(p.g, n, l - 224), true) : ao.p;
+  } else if (l >= 192 && l < 198) {
+    if (p.ls.train && !p.g.ls_shared) { const int i = n * 6 + (l - 192); sh.ls[l - 192] = pending_adam(p, p.ls, i, pending_load(p, p.ls, i), p.g.dls[i], true); }
+  }
+}
+
+template <bool kPending>
 __device__ __forceinline__ void
-pose_block(const ModelDev& m, const HeadArgs& a, int n) {
+pose_block(const ModelDev& m, const HeadArgs& a, int n, const PendingStep* pend, HeadShared* sh) {
   __shared__ float th[105];
   __shared__ float R[35][9];
   __shared__ float sc[35][3], isc[35][3];
@@ -53,23 +257,63 @@ pose_block(const ModelDev& m, const HeadArgs& a, int n) {
   }
   if (l >= 128 && l < 128 + kTreeMaxPass * 8) { const int q = l - 128; t_pj[q >> 3][q & 7] = tl.pass_joint[q >> 3][q & 7]; t_pp[q >> 3][q & 7] = tl.pass_parent[q >> 3][q & 7]; }
   const int nlev = tl.nlev;
+  float tv_pend = 0.f, js_pre[kPendingNb], jt_pre = 0.f, mv_pre = 0.f;
+  int idx_pre = 0;
+  if constexpr (kPending) {
+    // the pending step (fitter path: parameters given as grot / jrot, shared betas of kPendingNb directions).  What the thread
+    // reads of the model and the masks is requested first: behind the step's barriers it would be a second trip to memory.
+    // Then the slices of the shared gradients and this frame's own elements before the barrier, the shared totals behind it,
+    // and one more barrier before anyone reads the stepped values
+    const int lc = min(l, 104);
+    idx_pre = m.scale_idx[lc]; jt_pre = m.Jt[lc];
+    mv_pre = (lc < 3) ? a.gmask[lc] : a.rmask[max(lc - 3, 0)];
+#pragma unroll
+    for (int b = 0; b < kPendingNb; ++b) js_pre[b] = m.JS[lc * m.NBall + b];
+    SharedOperands so;
+    ThetaOperands to;
+    pending_shared_fetch(*pend, a, n, so);
+    pending_jrot_fetch(*pend, n, to);
+    pending_frame_extras(*pend, n, *sh);
+    tv_pend = pending_jrot_step(*pend, n, to);
+    pending_shared_slices(*pend, so, *sh);
+    PHASE_MARK(pp1);                    // everything fetched, the frame's own step taken, slices of the shared gradients in LDS
+    __syncthreads();
+    pending_shared_step(*pend, a, so, *sh);
+    PHASE_MARK(pp2);                    // shared totals and their step
+    __syncthreads();
+    if (l < 3) tv_pend = sh->grot[l];
+    PHASE_MARK(pp3);
+    PHASE_ADD(PH_HEAD_POSE, 4, ph0, pp1); PHASE_ADD(PH_HEAD_POSE, 5, pp1, pp2); PHASE_ADD(PH_HEAD_POSE, 6, pp2, pp3);   // (parts of phase 0)
+  }
   if (l < 105) {
     // operands whose address depends on nothing loaded are requested together, through pointers selected without a branch
     // (a load inside a per-lane condition is a branch plus a wait for everything in flight: tools/isa_loads.py)
     const int lj = max(l - 3, 0);
     const float* tsrc = a.theta_in ? a.theta_in + (size_t)n * 105 + l : ((l < 3) ? a.grot + n * 3 + l : a.jrot + (size_t)n * 102 + lj);
     const float* msrc = a.theta_in ? tsrc : ((l < 3) ? a.gmask + l : a.rmask + lj);
-    const int idx = m.scale_idx[l];
-    const float tv0 = *tsrc, mv = *msrc;
-    float acc = m.Jt[l];
-    const float lsv = a.logscale ? a.logscale[(size_t)n * a.ls_stride + max(idx, 0)] : 0.f;   // (its address needs idx: second trip)
+    int idx;
+    float tv0, mv, lsv, acc;
+    if constexpr (kPending) {
+      idx = idx_pre; tv0 = tv_pend; mv = mv_pre; acc = jt_pre;
+      lsv = a.logscale ? sh->ls[max(idx, 0)] : 0.f;
+    } else {
+      idx = m.scale_idx[l];
+      tv0 = *tsrc; mv = *msrc;
+      acc = m.Jt[l];
+      lsv = a.logscale ? a.logscale[(size_t)n * a.ls_stride + max(idx, 0)] : 0.f;   // (its address needs idx: second trip)
+    }
     const float tv = a.theta_in ? tv0 : tv0 * mv;
     th[l] = tv;
     a.theta[(size_t)n * 105 + l] = tv;
     // rest joint coordinate l of this frame's shape
-    const float* beta = a.betas + (size_t)(a.betas_stride ? n : 0) * a.betas_stride;
+    if constexpr (kPending) {
+#pragma unroll
+      for (int b = 0; b < kPendingNb; ++b) acc = fmaf(js_pre[b], sh->beta[b], acc);
+    } else {
+      const float* beta = a.betas + (size_t)(a.betas_stride ? n : 0) * a.betas_stride;
 #pragma unroll 10
-    for (int b = 0; b < a.nb; ++b) acc = fmaf(m.JS[l * m.NBall + b], beta[b], acc);
+      for (int b = 0; b < a.nb; ++b) acc = fmaf(m.JS[l * m.NBall + b], beta[b], acc);
+    }
     if (a.joff) acc += a.joff[(size_t)n * a.joff_stride + l];
     J[l / 3][l % 3] = acc;
     if (a.betas_stride || n == 0) a.Jrest[(size_t)(a.betas_stride ? n : 0) * 105 + l] = acc;
@@ -187,11 +431,76 @@ pose_block(const ModelDev& m, const HeadArgs& a, int n) {
   PHASE_END(PH_HEAD_POSE, ph0, ph4);
 }
 
-__global__ void __launch_bounds__(256)
-lbs_head_kernel(ModelDev m, HeadArgs a) {
+template <bool kPending>
+__device__ __forceinline__ void
+head_block(const ModelDev& m, const HeadArgs& a, const PendingStep* pend, HeadShared* sh) {
   int blk = blockIdx.x;
-  if (blk < a.M) { pose_block(m, a, blk); return; }
+  if (blk < a.M) { pose_block<kPending>(m, a, blk, pend, sh); return; }
   blk -= a.M;
+  if constexpr (kPending) {
+    // shape and prior blocks read the shared parameters: they take the shared part of the pending step too (bit-equal copies),
+    // with their own operands requested before its barriers (shared betas: one shape set, a.nshape == a.nshape_x)
+    const int Vp = m.Vp, v = min(blk, a.nshape_x - 1) * 256 + threadIdx.x, t = threadIdx.x, D = a.prior_D;
+    const bool shape = blk < a.nshape;
+    float vt_pre[3], sd_pre[3][kPendingNb], pcol[26], prow[26];
+    if (shape) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        vt_pre[c] = m.vt[c * Vp + v];
+#pragma unroll
+        for (int b = 0; b < kPendingNb; ++b) sd_pre[c][b] = m.sd[((size_t)b * 3 + c) * Vp + v];
+      }
+    } else if (a.prior_prec) {
+      const int tc = min(t, D - 1);
+#pragma unroll
+      for (int r = 0; r < 26; ++r) { const int rc = min(r, D - 1); pcol[r] = a.prior_prec[rc * D + tc]; prow[r] = a.prior_prec[tc * D + rc]; }
+    }
+    const float pmean = (!shape && a.prior_prec) ? a.prior_mean[min(t, D - 1)] : 0.f;
+    SharedOperands so;
+    pending_shared_fetch(*pend, a, 0, so);
+    pending_shared_slices(*pend, so, *sh);
+    __syncthreads();
+    pending_shared_step(*pend, a, so, *sh);
+    __syncthreads();
+    if (shape) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float acc = vt_pre[c];
+#pragma unroll
+        for (int b = 0; b < kPendingNb; ++b) acc = fmaf(sh->beta[b], sd_pre[c][b], acc);
+        if (a.voff) acc += a.voff[(size_t)c * Vp + v];
+        a.v_shaped[(size_t)c * Vp + v] = acc;
+      }
+      return;
+    }
+    // shape prior, as below with the operands held
+    if (a.prior_prec && t < 64) {
+      __shared__ float x[32], res[32];
+      if (t < D) x[t] = ((t < 20) ? sh->beta[t] : sh->ls[t - 20]) - pmean;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      float lv = 0.f;
+      if (t < D) {
+        float acc = 0.f;
+#pragma unroll
+        for (int r = 0; r < 26; ++r) if (r < D) acc = fmaf(x[r], pcol[r], acc);
+        res[t] = acc;
+        lv = acc * acc;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      lv = wave_sum(lv);
+      if (t == 0) *a.prior_loss = a.prior_w * lv / (float)D;
+      if (t < D) {
+        float acc = 0.f;
+#pragma unroll
+        for (int c = 0; c < 26; ++c) if (c < D) acc = fmaf(res[c], prow[c], acc);
+        acc *= 2.0f * a.prior_w / (float)D;
+        if (t < 20) a.prior_gb[t] = acc; else if (a.prior_use_ls) a.prior_gls[t - 20] = acc;
+      }
+    }
+    return;
+  }
   if (blk < a.nshape) {
     PHASE_MARK(ps0);
     const int s = blk / a.nshape_x;
@@ -237,6 +546,16 @@ lbs_head_kernel(ModelDev m, HeadArgs a) {
       if (t < 20) a.prior_gb[t] = acc; else if (a.prior_use_ls) a.prior_gls[t - 20] = acc;
     }
   }
+}
+
+__global__ void __launch_bounds__(256)
+lbs_head_kernel(ModelDev m, HeadArgs a) { head_block<false>(m, a, nullptr, nullptr); }
+
+// ... carrying the optimiser step the previous evaluation left pending (smalfit_fit_run)
+__global__ void __launch_bounds__(256)
+lbs_head_step_kernel(ModelDev m, HeadArgs a, PendingStep p) {
+  __shared__ HeadShared sh;
+  head_block<true>(m, a, &p, &sh);
 }
 
 // theta[n][0] = global_rotation[n] * gmask ; theta[n][1+j] = joint_rotations[n][j] * rmask[j]

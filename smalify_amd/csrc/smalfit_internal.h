@@ -129,4 +129,22 @@ struct AssembleArgs {
   float* losses;
 };
 
+// One optimiser step that has not been taken yet, carried by the NEXT evaluation's lbs_head_kernel (smalfit_fit_run): the raw
+// partials of the previous evaluation's backward pass as assemble_kernel would read them, and per parameter tensor where its
+// value / moments are read and where value / moments / gradient go.  Per-frame tensors are stepped in place by their frame's
+// block.  The shared ones (betas, shared limb scales) are stepped by EVERY block from the same operands in the same order, so
+// all copies agree bitwise, and stored by one block only -- to other addresses than they are read from, because the other
+// blocks of the launch are still reading.
+struct PendingTensor {
+  int train;                       // stepped by this launch (else the tensor is read through HeadArgs as ever)
+  const float *p_in, *m_in, *v_in;
+  float *p, *m, *v, *g;
+};
+struct PendingStep {
+  AssembleArgs g;                  // partials, masks, shape of the previous evaluation (output pointers unused)
+  PendingTensor betas, ls, grot, jrot, trans;
+  float step_size, b1, b2, eps, bc2_sqrt;   // adam_bias_terms of the pending step
+  int fresh;                       // first step of a stage: moments taken as zero
+};
+
 }  // namespace smalfit

@@ -16,6 +16,7 @@
 //   lbs_head_kernel     pose blocks: batch_lbs.py:33-52 (Rodrigues), :105-129 (limb scales), :131-168 (chain, A);
 //                       shape blocks: smal_torch.py:115 (+ :125-128 through the precomputed J0 + JS beta);
 //                       prior block: smal_fitter.py:162-171
+//   lbs_head_step_kernel  the same, taking the previous iteration's optimizer.step() with it (optimize_to_joints.py:136-137)
 //   skin_mfma_kernel / skin_kernel   smal_torch.py:138-163 (pose blend, W*A, skinning) + renderer camera transform
 //   joints_kernel       smal_torch.py:171-184
 //   loss_kernel         smal_fitter.py:129-132,140-160,177-190 ; pose_prior_35.py:117-124

@@ -92,6 +92,7 @@ struct smalfit_engine {
   float* lpart;
   long long* qpart;
   int* asm_counter;
+  float* shstate;     // shared parameters between the iterations of smalfit_fit_run: [2 slots][value, exp_avg, exp_avg_sq][32: betas 20 | limb scales 6]
   float *silbuf, *tile_loss, *dface;
   // adjoints
   float *dJ41, *dvert, *dvp, *dext, *dA, *dpf_part, *dbeta_part, *dtheta, *dls, *dJrest;
@@ -453,6 +454,7 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   CARVE(qpart, 64, long long);
   CARVE(zc, M, float);
   CARVE(asm_counter, 4, int);
+  CARVE(shstate, 2 * 3 * 32, float);
   CARVE(step_counter, 4, int);
   CARVE(gb_prior, 64, float);
   CARVE(gls_prior, 16, float);
@@ -574,7 +576,10 @@ struct HeadExtras {
   float prior_w = 0.f;
   const float *Rs_in = nullptr, *joff = nullptr, *voff = nullptr;   // SMAL.__call__ options (component API)
   int joff_stride = 0;
+  const PendingStep* pending = nullptr;   // smalfit_fit_run: the optimiser step the previous evaluation left to this launch
+  int prior_slot = 0;                     // which half of gb_prior / gls_prior the prior block writes (a pending step reads the other)
 };
+static constexpr int kPriorSlotB = 32, kPriorSlotLs = 8;   // floats per slot of smalfit_engine::gb_prior / gls_prior
 
 static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float* betas, int betas_stride,
                            int nb, const float* logscale, int ls_stride, const float* trans,
@@ -594,9 +599,11 @@ static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float
   const bool prior = ex && ex->prior_prec;
   if (prior) {
     h.prior_prec = ex->prior_prec; h.prior_mean = ex->prior_mean; h.prior_D = ex->prior_D; h.prior_use_ls = ex->prior_use_ls;
-    h.prior_w = ex->prior_w; h.prior_loss = e->loss_betas; h.prior_gb = e->gb_prior; h.prior_gls = e->gls_prior;
+    h.prior_w = ex->prior_w; h.prior_loss = e->loss_betas;
+    h.prior_gb = e->gb_prior + ex->prior_slot * kPriorSlotB; h.prior_gls = e->gls_prior + ex->prior_slot * kPriorSlotLs;
   }
-  lbs_head_kernel<<<M + h.nshape + (prior ? 1 : 0), 256, 0, st>>>(m, h);
+  if (ex && ex->pending) lbs_head_step_kernel<<<M + h.nshape + (prior ? 1 : 0), 256, 0, st>>>(m, h, *ex->pending);
+  else lbs_head_kernel<<<M + h.nshape + (prior ? 1 : 0), 256, 0, st>>>(m, h);
   LAUNCH_OK("lbs_head_kernel");
   const int vs_stride = betas_stride ? 3 * m.Vp : 0;
   // M-adaptive launch shape (round 6): the wide matrix-core kernel (64 vertices x 16 frames per workgroup) fills the chip from 64
@@ -686,12 +693,20 @@ static int run_lbs_backward(smalfit_engine* e, hipStream_t st, int M, int nb, in
 
 }  // namespace smalfit
 
-extern "C" {
-
 // ------------------------------------------------------------------------------------------------
 // SMALFitter fused evaluation
 // ------------------------------------------------------------------------------------------------
-int smalfit_fit_eval(smalfit_engine* e, void* stream, const smalfit_fit_args* a) {
+namespace smalfit {
+// How smalfit_fit_run strings evaluations together: an evaluation may take over the optimiser step its predecessor left pending
+// (lbs_head_step_kernel), and may itself stop after the backward pass, leaving gradient assembly + Adam to its successor.
+struct EvalFold {
+  const PendingStep* pending = nullptr;   // taken by this evaluation's head launch
+  int prior_slot = 0;                     // half of the shape prior's gradient buffers this evaluation writes
+  bool assemble = true;                   // run assemble_kernel (gradients to the caller's buffers, the nine loss terms)
+  AssembleArgs* args_out = nullptr;       // the assembly's arguments, for the successor's pending step
+};
+
+static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const EvalFold& fold) {
   if (!e || !a) return fail("smalfit_fit_eval: null argument");
   // struct_size first: with a block laid out by another version of smalfit.h no other field can be trusted
   if (a->struct_size != (unsigned)sizeof(smalfit_fit_args))
@@ -729,6 +744,7 @@ int smalfit_fit_eval(smalfit_engine* e, void* stream, const smalfit_fit_args* a)
     Section sec(e, st, SMALFIT_SEC_LBS_FWD);
     HeadExtras ex;
     ex.grot = a->global_rotation; ex.jrot = a->joint_rotations; ex.gmask = gmask; ex.rmask = rmask;
+    ex.pending = fold.pending; ex.prior_slot = fold.prior_slot;
     if (shape_prior) {
       ex.prior_prec = e->shape_prec; ex.prior_mean = e->shape_mean; ex.prior_D = D; ex.prior_use_ls = prior_uses_ls ? 1 : 0;
       // the shape prior is evaluated once per window (smal_fitter.py:162-171 inside forward()): this evaluation owns the
@@ -786,8 +802,8 @@ int smalfit_fit_eval(smalfit_engine* e, void* stream, const smalfit_fit_args* a)
   g.nblk_beta = e->nblk_beta; g.nvt = e->nvt; g.betas_shared = 1; g.ls_shared = a->logscale_mode == 1;
   g.w_sil = a->w_sil;
   g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = kBetaGroups;
-  g.gb_prior = shape_prior ? e->gb_prior : nullptr;
-  g.gls_prior = prior_uses_ls ? e->gls_prior : nullptr;
+  g.gb_prior = shape_prior ? e->gb_prior + fold.prior_slot * kPriorSlotB : nullptr;
+  g.gls_prior = prior_uses_ls ? e->gls_prior + fold.prior_slot * kPriorSlotLs : nullptr;
   g.dls = e->dls; g.dtheta = e->dtheta; g.gmask = gmask; g.rmask = rmask;
   g.dtr_direct = e->dtr_direct; g.dtr_part = e->dtr_part; g.loss_part = e->loss_part;
   g.loss_betas = shape_prior ? e->loss_betas : nullptr;
@@ -799,14 +815,22 @@ int smalfit_fit_eval(smalfit_engine* e, void* stream, const smalfit_fit_args* a)
   g.g_grot = a->g_global_rotation; g.g_jrot = a->g_joint_rotations; g.g_trans = a->g_trans;
   g.losses = a->losses;
   g.lpart = e->lpart; g.qpart = e->qpart; g.counter = e->asm_counter;
-  assemble_kernel<<<1 + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g);
-  LAUNCH_OK("assemble_kernel");
+  if (fold.args_out) *fold.args_out = g;
+  if (fold.assemble) {
+    assemble_kernel<<<1 + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g);
+    LAUNCH_OK("assemble_kernel");
+  }
   if (e->prof_on) {
     if (e->prof_iter < e->prof_cap && (e->prof_tick % e->prof_stride) == 0) e->prof_iter++;
     e->prof_tick++;
   }
   return 0;
 }
+}  // namespace smalfit
+
+extern "C" {
+
+int smalfit_fit_eval(smalfit_engine* e, void* stream, const smalfit_fit_args* a) { return fit_eval_impl(e, stream, a, EvalFold{}); }
 
 // ------------------------------------------------------------------------------------------------
 // per-section timing with HIP events on the caller's stream
@@ -1178,6 +1202,43 @@ int smalfit_engine_set_graph(smalfit_engine* e, int enable) {
 }
 
 namespace smalfit {
+// Can the optimiser step of `o` be folded into the next evaluation's head launch?  Only when the trainable ranges are exactly a
+// set of whole parameter tensors of `a` (the ranges of adjacent tensors may be merged) whose gradients the evaluation writes to
+// the matching ranges of o->grad: then every trainable float has one known reader (PendingStep).  -> which tensors, and where.
+struct FoldPlan {
+  bool train[5];      // betas, log_beta_scales, global_rotation, joint_rotations, trans
+  int off[5];         // their offsets in the flat buffers
+};
+static bool plan_fold(const smalfit_fit_args* a, const smalfit_adam_args* o, const AdamSegments& sg, FoldPlan& plan) {
+  const int M = a->num_frames;
+  if (M <= 0 || !a->betas || !a->global_rotation || !a->joint_rotations || !a->trans) return false;
+  const float* ptr[5] = {a->betas, a->logscale_mode ? a->log_beta_scales : nullptr, a->global_rotation, a->joint_rotations, a->trans};
+  const float* gptr[5] = {a->g_betas, a->g_log_beta_scales, a->g_global_rotation, a->g_joint_rotations, a->g_trans};
+  const long long cnt[5] = {20, a->logscale_mode == 1 ? 6 : (long long)M * 6, (long long)M * 3, (long long)M * 102, (long long)M * 3};
+  long long lo[5], covered = 0;
+  for (int k = 0; k < 5; ++k) {
+    plan.train[k] = false; plan.off[k] = 0; lo[k] = 0;
+    if (!ptr[k]) continue;
+    const long long bytes = (long long)((const char*)ptr[k] - (const char*)o->param);
+    if (bytes % 4) return false;
+    lo[k] = bytes / 4;
+    bool inside = false, touches = false;
+    for (int q = 0; q < sg.nseg; ++q) {
+      const long long b = sg.beg[q], en = b + (sg.off[q + 1] - sg.off[q]);
+      if (b <= lo[k] && lo[k] + cnt[k] <= en) inside = true;
+      else if (lo[k] < en && b < lo[k] + cnt[k]) touches = true;
+    }
+    if (touches) return false;                                     // a range cuts through the tensor
+    if (!inside) continue;
+    if (gptr[k] != o->grad + lo[k]) return false;                  // its gradient is not written where Adam reads it
+    for (int j = 0; j < k; ++j)
+      if (plan.train[j] && lo[j] < lo[k] + cnt[k] && lo[k] < lo[j] + cnt[j]) return false;   // two tensors share floats
+    plan.train[k] = true; plan.off[k] = (int)lo[k];
+    covered += cnt[k];
+  }
+  return covered > 0 && covered == sg.off[sg.nseg];               // nothing else in the ranges
+}
+
 static int launch_adam_graph_node(smalfit_engine* e, hipStream_t st, const AdamSegments& sg, const smalfit_adam_args* o) {
   const int total = sg.off[sg.nseg];
   if (total == 0) return 0;
@@ -1225,6 +1286,54 @@ int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, 
     LAUNCH_OK("set_counter_kernel");
     for (int it = 0; it < iterations; ++it) HIP_OK(hipGraphLaunch(e->graph_exec, st));
     return 0;
+  }
+  // Gradient assembly and Adam of every iteration but the last ride in the NEXT iteration's head launch -- its frame blocks are
+  // the first and only readers of the stepped per-frame parameters, so no fence, counter or tail is needed -- and the loss
+  // terms of those iterations, which no caller can see, are not summed at all.  The last iteration closes with the two
+  // kernels as ever, so the caller finds parameters, moments, gradients and losses exactly as from the plain chain below.
+  FoldPlan plan;
+  if (iterations >= 2 && !e->prof_on && plan_fold(a, o, sg, plan)) {
+    const bool ls_shared = a->logscale_mode == 1, shared_trained = plan.train[0] || (plan.train[1] && ls_shared);
+    PendingStep ps;
+    for (int it = 0; it < iterations; ++it) {
+      const bool last = it == iterations - 1;
+      EvalFold fold;
+      AssembleArgs g;
+      fold.pending = it ? &ps : nullptr; fold.prior_slot = it & 1; fold.assemble = last; fold.args_out = &g;
+      if (fit_eval_impl(e, stream, a, fold)) return 1;
+      if (last) break;
+      // the step this evaluation leaves pending.  Per-frame tensors are stepped in place; the shared ones travel through the
+      // two slots of e->shstate (read from one, stored to the other: the launch's other blocks are still reading), starting
+      // from the caller's buffers and, from the third iteration on, ending there: the last pending step reads a slot
+      std::memset(&ps, 0, sizeof(ps));
+      ps.g = g;
+      const int t = o->step + it + 1;
+      adam_bias_terms(o->lr, o->beta1, o->beta2, t, ps.step_size, ps.bc2_sqrt);
+      ps.b1 = o->beta1; ps.b2 = o->beta2; ps.eps = o->eps; ps.fresh = t == 1 ? 1 : 0;
+      PendingTensor* pt[5] = {&ps.betas, &ps.ls, &ps.grot, &ps.jrot, &ps.trans};
+      const float* tensor[5] = {a->betas, a->logscale_mode ? a->log_beta_scales : nullptr, a->global_rotation, a->joint_rotations, a->trans};
+      for (int k = 0; k < 5; ++k) {
+        PendingTensor& T = *pt[k];
+        if (!plan.train[k]) { T.p_in = T.m_in = T.v_in = tensor[k]; continue; }   // read as it is (unconditional loads: any readable words as moments)
+        const int off = plan.off[k];
+        T.train = 1;
+        T.p_in = T.p = o->param + off; T.m_in = T.m = o->exp_avg + off; T.v_in = T.v = o->exp_avg_sq + off; T.g = o->grad + off;
+        if (k == 0 || (k == 1 && ls_shared)) {
+          const int at = k == 0 ? 0 : 20;
+          float* dst = e->shstate + ((it + 1) & 1) * 96 + at;
+          const float* src = e->shstate + (it & 1) * 96 + at;
+          if (it) { T.p_in = src; T.m_in = src + 32; T.v_in = src + 64; }
+          if (!(it && it + 2 == iterations)) { T.p = dst; T.m = dst + 32; T.v = dst + 64; }
+        }
+      }
+    }
+    if (shared_trained && iterations == 2) {   // the only pending step read the caller's buffers, so it could not store there
+      shared_state_restore_kernel<<<1, 64, 0, st>>>(e->shstate + ((iterations - 1) & 1) * 96, o->param, o->exp_avg, o->exp_avg_sq,
+                                                   plan.train[0] ? 20 : 0, plan.off[0], (plan.train[1] && ls_shared) ? 6 : 0, plan.off[1]);
+      LAUNCH_OK("shared_state_restore_kernel");
+    }
+    const int t = o->step + iterations;
+    return launch_adam_segments(st, sg, o, t, t == 1);
   }
   for (int it = 0; it < iterations; ++it) {
     const int t = o->step + it + 1;

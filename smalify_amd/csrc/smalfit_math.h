@@ -412,16 +412,18 @@ SMALFIT_HD void adam_bias_terms(float lr, float beta1, float beta2, int t, float
 
 // one element: the incoming moments m0 / v0 (the caller passes 0 on the first step of a stage instead of reading them:
 // b * 0 + x == x exactly, the same bits as stepping from zero-filled moments), the new moments out, the parameter p updated
-// in place -- stored in that order, with the operand order of every expression fixed (the multiply-adds contract alike in
-// every kernel)
+// in place -- stored in that order.  Which product of a sum of two products is fused into the addition is written out (fmaf, and
+// no contraction besides): left to the compiler, a * b + c * d came out as fma(a, b, c * d) in one kernel and fma(c, d, a * b) in
+// another, one unit in the last place apart.  The forms are those the optimiser kernels of smalfit_fit_run have always had.
 SMALFIT_HD void adam_update(float g, float m0, float v0, float b1, float b2, float eps, float step_size, float bc2_sqrt,
                             float& m, float& v, float& p) {
-  const float mi = b1 * m0 + (1.0f - b1) * g;
-  const float vi = b2 * v0 + (1.0f - b2) * g * g;
+#pragma clang fp contract(off)
+  const float mi = fmaf(1.0f - b1, g, b1 * m0);
+  const float vi = fmaf((1.0f - b2) * g, g, b2 * v0);
   m = mi;
   v = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p = p - step_size * (mi / denom);
+  p = fmaf(-step_size, mi / denom, p);
 }
 
 }  // namespace smalfit

@@ -9,7 +9,8 @@ import numpy as np, torch
 import bench
 from smalify_amd import _lib, engine as eng, synthetic, fitter as fit, config
 
-KERNELS = [("lbs_head: pose block (per frame)", ["operands -> LDS", "Rodrigues", "tree walk", "A / G out"]),
+KERNELS = [("lbs_head: pose block (per frame)", ["operands -> LDS", "Rodrigues", "tree walk", "A / G out",
+                                                 "  of the first, with a pending step: fetch, own step, slices", "  ... barrier, shared totals + Adam", "  ... barrier"]),
            ("lbs_head: shape-blend block", []),
            ("skin_mfma (64 vertices x 16 frames)", ["side operands", "pose-blend GEMM", "skinning + camera"]),
            ("vertex_bwd (256 vertices x 1 frame)", []),
