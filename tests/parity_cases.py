@@ -324,37 +324,69 @@ def case_cache_consistency(M=4, S=64, window=3, stage=2, z=1.45, steps=6, seed=2
     return {"loss_rel_max": loss_rel, "grad_rel_max": grad_rel, "status": e_a.status() | e_b.status()}
 
 
-def case_sil_trajectory(M=4, S=64, window=2, iters=8, seed=21):
+def _oracle_trajectory(prob, cur, M, S, window, iters, seed, names, masks):
+    """the oracle's loop of case_sil_trajectory: loss histories and end parameters (kept: the same trajectory serves every
+    way of cutting the device's iterations into library calls)"""
+    key = ("oracle_trajectory", M, S, window, iters, seed, tuple(names), None if masks is None else tuple(np.concatenate([m.reshape(-1) for m in masks])))
+    if key not in _CACHE:
+        W = np.array(cfg.OPT_WEIGHTS).T
+        weights, w_temp, lr = W[2][:6].copy(), float(W[2][6]), float(W[2][8])
+        params = {k: torch.from_numpy(v).double() for k, v in cur.items()}
+        mk = {} if masks is None else {"global_rotation": torch.from_numpy(masks[0]).double(), "joint_rotations": torch.from_numpy(masks[1]).double()}
+        opt = so.Adam(names, lr=lr)
+        hist_o = []
+        for _ in range(iters):
+            # a masked parameter enters the objective as param * mask, so its gradient is the masked value's times the mask
+            seen = {k: v * mk[k] if k in mk else v for k, v in params.items()}
+            total, sums, grads = so.loss_and_grads(prob, seen, weights, w_temp, names)
+            grads = {k: g * mk[k] if k in mk else g for k, g in grads.items()}
+            opt.step(params, grads)
+            hist_o.append(float(total))
+        _CACHE[key] = (hist_o, {k: v.numpy() for k, v in params.items()})
+    return _CACHE[key]
+
+
+def case_sil_trajectory(M=4, S=64, window=2, iters=8, seed=21, chunk=1, trainable=None, allow_limb_scaling=True, masks=None):
     """The full loop with the silhouette on (stage-2 weights, lr 5e-4): FusedFitter on the GPU vs the oracle's loss +
     autograd + Adam on the CPU, same start, same targets.  Returns the per-tensor relative differences after `iters`
-    iterations and the loss histories."""
+    iterations and the loss histories.
+    chunk: iterations per library call (1: one smalfit_fit_run per iteration, nothing folded; `iters`: the whole trajectory
+    in one folded call -- then only the last iteration's loss is seen and compared).
+    trainable: the tensors both sides train (default: the stage's, without the limb scales if allow_limb_scaling is False:
+    frozen by stage 0, optimize_to_joints.py:101, and thawed by nothing).  masks: (global_mask (3,), rotation_mask (34,3))."""
     from smalify_amd import fitter as fit
     W = np.array(cfg.OPT_WEIGHTS).T
     stage = 2
     weights, w_temp, lr = W[stage][:6].copy(), float(W[stage][6]), float(W[stage][8])
     e, prob, cur, tg = make_problem(M, S, window, seed)
-    names = so.trainable_names(stage)
-    # oracle loop
-    params = {k: torch.from_numpy(v).double() for k, v in cur.items()}
-    opt = so.Adam(so.PARAM_ORDER, lr=lr)
-    hist_o = []
-    for _ in range(iters):
-        total, sums, grads = so.loss_and_grads(prob, params, weights, w_temp, names)
-        opt.step(params, grads)
-        hist_o.append(float(total))
+    names = so.trainable_names(stage, allow_limb_scaling, scales_trainable_default=False) if trainable is None else tuple(trainable)
+    hist_o, params = _oracle_trajectory(prob, cur, M, S, window, iters, seed, names, masks)
+
+    class Fitter(fit.FusedFitter):
+        def trainable(self, stage_id):
+            return names if trainable is not None else super().trainable(stage_id)
+
     # device loop (betas / limb scales start from the perturbed values, as in the oracle)
-    f = fit.FusedFitter(e, tg["tj"], tg["vis"], tg["tsil"], window, True, cur["betas"], cur["log_beta_scales"])
+    f = Fitter(e, tg["tj"], tg["vis"], tg["tsil"], window, True, cur["betas"], cur["log_beta_scales"], allow_limb_scaling=allow_limb_scaling)
+    assert set(f.trainable(stage)) == set(names)
     for k in ("global_rotation", "joint_rotations", "trans"):
         f.p[k].copy_(dev(cur[k]))
+    if masks is not None:
+        f.global_mask.copy_(dev(masks[0]))
+        f.rotation_mask.copy_(dev(masks[1]))
     f.begin_stage(stage)
-    hist = []
-    for _ in range(iters):
-        f.step(weights, w_temp, lr, stage)
+    hist, seen = [], []
+    done = 0
+    while done < iters:
+        n = min(chunk, iters - done)
+        f.run_iterations(weights, w_temp, lr, stage, n)
+        done += n
         hist.append(float(f.losses.double().sum().item()))
-    out = {"traj_loss_rel_max": float(np.max(np.abs(np.array(hist) - np.array(hist_o)) / np.abs(np.array(hist_o)))),
+        seen.append(hist_o[done - 1])
+    out = {"traj_loss_rel_max": float(np.max(np.abs(np.array(hist) - np.array(seen)) / np.abs(np.array(seen)))),
            "traj_status": e.status()}
     for k in ("betas", "log_beta_scales", "global_rotation", "joint_rotations", "trans"):
-        out["traj_%s_rel" % k] = rel(f.p[k].cpu().numpy().reshape(params[k].shape), params[k].numpy())
+        out["traj_%s_rel" % k] = rel(f.p[k].cpu().numpy().reshape(params[k].shape), params[k])
     return out
 
 

@@ -100,16 +100,51 @@ def test_raster_cache_never_changes_results():
         assert m["status"] == 0
 
 
-@pytest.mark.parametrize("M,S,window,iters", [(4, 64, 2, 8), (8, 128, 4, 5)])
-def test_fit_loop_with_silhouette_follows_the_oracle(M, S, window, iters):
-    """8 iterations of the whole loop with the silhouette term on (cached depth bounds included): losses and parameters
-    against the oracle's loss + autograd + Adam.  north_star's bar for parameters is 1e-4 relative L2."""
-    m = pc.case_sil_trajectory(M, S, window, iters)
+def _assert_trajectory(m):
+    print(m)
     assert m["traj_status"] == 0
     assert m["traj_loss_rel_max"] < 1e-4, m
     for k, v in m.items():
         if k.endswith("_rel") and k != "traj_loss_rel_max":
             assert v < 1e-4, (k, v, m)
+
+
+@pytest.mark.parametrize("M,S,window,iters", [(4, 64, 2, 8), (8, 128, 4, 5)])
+def test_fit_loop_with_silhouette_follows_the_oracle(M, S, window, iters):
+    """8 iterations of the whole loop with the silhouette term on (cached depth bounds included): losses and parameters
+    against the oracle's loss + autograd + Adam.  north_star's bar for parameters is 1e-4 relative L2.
+    Once with one library call per iteration (nothing folded: assemble_kernel + adam_segments_kernel behind every evaluation)
+    and once with the whole trajectory in one call (every optimiser step but the last inside lbs_head_step_kernel)."""
+    _assert_trajectory(pc.case_sil_trajectory(M, S, window, iters))
+    _assert_trajectory(pc.case_sil_trajectory(M, S, window, iters, chunk=iters))
+
+
+def _trajectory_masks():
+    import numpy as np
+    gm = np.array([1.0, 0.0, 0.5], np.float32)
+    rm = np.ones((34, 3), np.float32)
+    rm[::3] = 0.0
+    rm[1::3, 1] = 0.25
+    return gm, rm
+
+
+# the kinds of trainable set no other oracle check runs: kwargs of case_sil_trajectory
+TRAJECTORY_SETS = {
+    "no_limb_scaling": dict(allow_limb_scaling=False),
+    "betas_and_scales": dict(trainable=("betas", "log_beta_scales")),
+    "joint_rotations": dict(trainable=("joint_rotations",)),
+    "rotation_and_trans": dict(trainable=("global_rotation", "trans")),
+    "masked": dict(masks=_trajectory_masks()),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(TRAJECTORY_SETS))
+def test_folded_fit_loop_follows_the_oracle_for_other_trainable_sets(kind):
+    """as test_fit_loop_with_silhouette_follows_the_oracle, the 8 iterations in ONE folded call, with what the fitter can train
+    besides "everything": no limb scales (allow_limb_scaling=False), strict subsets (so.Adam over the same names), and masked
+    rotations (the oracle is handed param * mask and its gradient is multiplied by the mask).  The same bars.  For these sets
+    the device functions shared by assemble_kernel and the step kernel meet the float64 oracle only here."""
+    _assert_trajectory(pc.case_sil_trajectory(4, 64, 2, 8, chunk=8, **TRAJECTORY_SETS[kind]))
 
 
 @pytest.mark.parametrize("scaled", [False, True])
