@@ -36,8 +36,9 @@ typedef struct smalfit_engine smalfit_engine;
  * smalfit_fit_args gained target_sil_u8 / w_limit; 3 = smalfit_fit_args.struct_size (first field), frame_offset,
  * total_frames; smalfit_engine_clear_joint_limits, smalfit_shard_local_step; 4 = smalfit_shard_run (the sharded loop of a
  * whole stage in one call, the collective supplied by the host as a function pointer), smalfit_rccl_allgather;
- * 5 = smalfit_engine_set_option. */
-#define SMALFIT_ABI_VERSION 5
+ * 5 = smalfit_engine_set_option; 6 = smalfit_fit_args.subject_frames / losses_per_frame (a batch of independent images,
+ * each with its own shape; one row of loss terms per frame). */
+#define SMALFIT_ABI_VERSION 6
 int smalfit_version(void);
 const char* smalfit_last_error(void);
 
@@ -232,6 +233,22 @@ typedef struct smalfit_fit_args {
    * Zeros = the M frames are the whole sequence. */
   int frame_offset;               /* index of local frame 0 in the sequence                     */
   int total_frames;               /* frames in the whole sequence; 0 = frame_offset + num_frames */
+  /* Whose frames these are.  0 (default): the M frames are ONE subject -- one shape, everything above as documented.
+   * 1: every frame is its own subject, an unrelated image (the reference fits those one image per SMALFitter,
+   * optimize_to_joints.py with BASELINE config 1): betas (M,20), g_betas (M,20); logscale_mode 0 or 2 (1 is refused:
+   * nothing is shared); window must be 1, frame_offset / total_frames / temporal 0 and halo_* NULL (refused otherwise);
+   * the shape prior (20-dim, or 26-dim over [betas_n | log_beta_scales_n] with logscale_mode 2) is evaluated once per
+   * frame with weight w_betas, its gradient going to row n of g_betas / g_log_beta_scales; losses[3] is the sum over
+   * frames.  smalfit_fit_eval and smalfit_fit_run accept it (the run keeps the plain chain: nothing is folded);
+   * smalfit_shard_* and the graph replay refuse it.  Any other value is refused: clips of K > 1 frames per subject in one
+   * batch are not implemented. */
+  int subject_frames;
+  /* (M, SMALFIT_NUM_LOSS_TERMS) or NULL, either mode: row n = frame n's contribution to each term of `losses`, same
+   * weights and normalisers, so that every column sums to `losses` (up to float32 re-ordering).  The temporal columns of
+   * row n are the terms of the pair (n, n+1), zero for the last frame without a halo and for independent images.  The
+   * betas column: frame n's own prior term for independent images; for one subject the window's term in the row of the
+   * window's first frame when this evaluation owns that window, zero elsewhere.  Asking for it changes no other output. */
+  float* losses_per_frame;
 } smalfit_fit_args;
 
 int smalfit_fit_eval(smalfit_engine* engine, void* stream, const smalfit_fit_args* args);

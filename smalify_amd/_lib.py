@@ -11,7 +11,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 5                    # SMALFIT_ABI_VERSION of include/smalfit.h this binding mirrors
+ABI_VERSION = 6                    # SMALFIT_ABI_VERSION of include/smalfit.h this binding mirrors
 LIB_PATH = os.environ.get("SMALFIT_LIB") or os.path.join(_HERE, "libsmalfit.so")   # override: development builds
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -42,7 +42,8 @@ class FitArgs(C.Structure):
                 ("g_global_rotation", C.c_void_p), ("g_joint_rotations", C.c_void_p),
                 ("g_trans", C.c_void_p), ("sil_out", C.c_void_p), ("proj_out", C.c_void_p),
                 ("verts_out", C.c_void_p), ("target_sil_u8", C.c_void_p), ("w_limit", C.c_float),
-                ("frame_offset", C.c_int), ("total_frames", C.c_int)]
+                ("frame_offset", C.c_int), ("total_frames", C.c_int),
+                ("subject_frames", C.c_int), ("losses_per_frame", C.c_void_p)]
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)

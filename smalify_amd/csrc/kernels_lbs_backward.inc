@@ -144,6 +144,7 @@ dA_block(const ModelDev& m, int j, int n, const float* __restrict__ dvert, const
 }
 
 constexpr int kAsmElem = 4, kAsmLoss = 16;   // assemble_kernel: blocks for element-wise gradients / loss partial sums
+constexpr int kAsmRows = 4;                  // blocks of frame_loss_rows_kernel
 
 // K9: shape-blend adjoint.  shared betas: dbeta_part[block][b] = sum_col sd[b][col] * sum_n dvp[n][col]
 //     per-frame betas (blockIdx.y = frame): no sum over frames.
@@ -652,8 +653,11 @@ chain_bwd_kernel(ModelDev m, int M, const float* __restrict__ theta, const float
 // ------------------------------------------------------------------------------------------------
 // K11: gradient assembly (single block): shared-parameter reductions, masks, loss totals
 // ------------------------------------------------------------------------------------------------
+// kPerImage: independent images -- every shape set and every frame's limb scales carry a prior term of their own (AssembleExt).
+// <false> is the kernel as it always was.
+template <bool kPerImage>
 __global__ void __launch_bounds__(256)
-assemble_kernel(AssembleArgs a) {
+assemble_kernel(AssembleArgs a, AssembleExt x) {
   // Blocks take roles (kAsmElem / kAsmLoss are compile-time):
   //   [0, nbs)            d loss / d betas of shape set s: column-block partials + joint path + prior
   //   nbs                 limb scales
@@ -682,6 +686,10 @@ assemble_kernel(AssembleArgs a) {
         asm_beta_slices(a, s, b0, bo, bsum);
         __syncthreads();
         const float tot = asm_beta_total(a, s, b0, bo, bsum);
+        // (independent images: shape set s has a prior term of its own, its gradient is row s)
+        if constexpr (kPerImage) {
+          if (t < 20 && b0 + t < a.nb) a.g_betas[s * a.nb + b0 + t] = x.gb_prior_pf ? tot + x.gb_prior_pf[(size_t)s * x.gb_stride + b0 + t] : tot;
+        } else
         if (t < 20 && b0 + t < a.nb) a.g_betas[s * a.nb + b0 + t] = tot;
       }
     }
@@ -695,7 +703,10 @@ assemble_kernel(AssembleArgs a) {
         const float tot = asm_ls_total(a, lo, dpart);
         if (t < 6) a.g_ls[t] = tot;
       } else {
-        for (int i = t; i < M * 6; i += 256) a.g_ls[i] = a.dls[i];
+        if (kPerImage && x.gls_prior_pf)     // independent images: frame n's own prior row
+          for (int i = t; i < M * 6; i += 256) a.g_ls[i] = a.dls[i] + x.gls_prior_pf[(size_t)(i / 6) * x.gls_stride + i % 6];
+        else
+          for (int i = t; i < M * 6; i += 256) a.g_ls[i] = a.dls[i];
       }
     }
   } else if ((role -= 1) < kAsmElem) {
@@ -770,12 +781,17 @@ assemble_kernel(AssembleArgs a) {
     const int k = t & 7, sl = t >> 3;
     float acc = 0.f;
     if (a.loss_part) for (int n = sl; n < M; n += 32) acc += a.loss_part[n * 8 + k];
+    // (column 4 of the per-frame partials is unused -- the silhouette comes from the tiles: with one prior term per frame it adds those)
+    if (kPerImage && x.prior_loss_pf && k == 4) { acc = 0.f; for (int n = sl; n < M; n += 32) acc += x.prior_loss_pf[n]; }
     part[sl][k] = acc;
   }
   __syncthreads();
   if (t < 8) {
     float acc = 0.f;
-    if (t == 3) acc = a.loss_betas ? *a.loss_betas : 0.f;
+    if (t == 3) {
+      acc = a.loss_betas ? *a.loss_betas : 0.f;
+      if (kPerImage && x.prior_loss_pf) for (int i = 0; i < 32; ++i) acc += part[i][4];
+    }
     else if (t == 4) acc = lsil;
     else for (int i = 0; i < 32; ++i) acc += part[i][t];
     a.losses[t] = acc;
@@ -788,6 +804,37 @@ assemble_kernel(AssembleArgs a) {
   if (t == 0) *a.counter = 0;
   PHASE_MARK(pa2);
   PHASE_END(PH_ASM_LAST, pa1, pa2);
+}
+
+// One row of the nine loss terms per frame (smalfit_fit_args.losses_per_frame), launched only when a caller asks for it -- a kernel of
+// its own so that assemble_kernel, the tail of every iteration, stays what it is.  One wave per frame; everything it reads was
+// written by earlier launches.  The tile partials of a frame are added lane-strided and then in the butterfly's order (fixed), the
+// queue kernels' share is an integer: two runs give the same bits.
+__global__ void __launch_bounds__(256)
+frame_loss_rows_kernel(AssembleArgs a, AssembleExt x) {
+  const int t = threadIdx.x, lane = t & 63, M = a.M;
+  for (int n = (int)blockIdx.x * 4 + (t >> 6); n < M; n += kAsmRows * 4) {
+    const int Bn = frame_window_size(n, a.win);
+    float lsil = 0.f;
+    if (a.tile_loss) {
+      const float wn = a.w_sil / ((float)Bn * (float)a.S * (float)a.S);
+      for (int k = lane; k < a.T; k += 64) lsil += a.tile_loss[(size_t)n * a.T + k] * wn;
+    }
+    lsil = wave_sum(lsil);
+    if (lane == 0) {
+      if (a.tile_loss) {
+        unsigned long long* fq = x.frame_qloss + (size_t)n * kFrameLossStride;
+        lsil += (float)((double)*fq * (1.0 / (double)kLossFix));
+        *fq = 0ull;                  // zero for the next evaluation that feeds it
+      }
+      float prior = 0.f;
+      if (x.prior_loss_pf) prior = x.prior_loss_pf[n];
+      else if (a.loss_betas && x.prior_windows > 0 && (n + a.win.offset) % a.win.window == 0) prior = *a.loss_betas / (float)x.prior_windows;
+      const float* lp = a.loss_part + n * 8;
+      float* o = x.losses_pf + (size_t)n * 9;
+      o[0] = lp[0]; o[1] = lp[1]; o[2] = lp[2]; o[3] = prior; o[4] = lsil; o[5] = lp[5]; o[6] = lp[6]; o[7] = lp[7]; o[8] = lp[3];
+    }
+  }
 }
 
 // adjoint of a per-frame template offset (SMAL.__call__'s del_v / v_template): d v_shaped = d v_posed + J_regressor d(rest joints)

@@ -431,9 +431,56 @@ pose_block(const ModelDev& m, const HeadArgs& a, int n, const PendingStep* pend,
   PHASE_END(PH_HEAD_POSE, ph0, ph4);
 }
 
+// Shape prior of independent images: w mean_c(((x_n - mean) prec)_c ^2) with x_n = [betas_n | log scales_n], one term per frame.
+// A block takes kPriorFrames frames, one wave every fourth of them; prec and mean are staged in LDS once per block (2.7 KB; the
+// shared-shape block below reads them from memory once, here that would be once per frame).  Per frame the operations and their
+// order are those of the shared block, so one image gives the bits a one-frame shared fit gives.  Each frame's loss is a plain
+// store; who adds them up (assemble_kernel) does so in a fixed order.
+// Its arguments travel beside HeadArgs (lbs_head_kernel only): the step kernel's argument block stays what it is.
+constexpr int kPriorFrames = 16;
+struct PriorFrames {
+  int on, gb_stride, gls_stride;   // on: ceil(M / kPriorFrames) blocks behind the shape blocks evaluate one prior term per frame
+  float* loss;                     // [M]: frame n's term
+  float *gb, *gls;                 // rows of gb_stride / gls_stride floats: its gradient wrt betas_n / log scales_n
+};
+__device__ __forceinline__ void prior_frames_block(const HeadArgs& a, const PriorFrames& pf, int pb) {
+  __shared__ float prec[26 * 26], mean[32], xs[4][32], rs[4][32];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, D = a.prior_D;
+  for (int i = t; i < D * D; i += 256) prec[i] = a.prior_prec[i];
+  if (t < D) mean[t] = a.prior_mean[t];
+  __syncthreads();
+  const int n_end = min((pb + 1) * kPriorFrames, a.M);
+  for (int n = pb * kPriorFrames + w; n < n_end; n += 4) {       // (n is uniform over the wave)
+    if (lane < D)
+      xs[w][lane] = ((lane < 20) ? a.betas[(size_t)n * a.betas_stride + lane] : a.logscale[(size_t)n * a.ls_stride + lane - 20]) - mean[lane];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    float lv = 0.f;
+    if (lane < D) {
+      float acc = 0.f;
+      for (int r = 0; r < D; ++r) acc = fmaf(xs[w][r], prec[r * D + lane], acc);
+      rs[w][lane] = acc;
+      lv = acc * acc;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    lv = wave_sum(lv);
+    if (lane == 0) pf.loss[n] = a.prior_w * lv / (float)D;
+    if (lane < D) {
+      float acc = 0.f;
+      for (int c = 0; c < D; ++c) acc = fmaf(rs[w][c], prec[lane * D + c], acc);
+      acc *= 2.0f * a.prior_w / (float)D;
+      if (lane < 20) pf.gb[(size_t)n * pf.gb_stride + lane] = acc;
+      else if (a.prior_use_ls) pf.gls[(size_t)n * pf.gls_stride + lane - 20] = acc;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // the next frame of this wave overwrites xs / rs
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 template <bool kPending>
 __device__ __forceinline__ void
-head_block(const ModelDev& m, const HeadArgs& a, const PendingStep* pend, HeadShared* sh) {
+head_block(const ModelDev& m, const HeadArgs& a, const PendingStep* pend, HeadShared* sh, const PriorFrames* pf = nullptr) {
   int blk = blockIdx.x;
   if (blk < a.M) { pose_block<kPending>(m, a, blk, pend, sh); return; }
   blk -= a.M;
@@ -521,6 +568,7 @@ head_block(const ModelDev& m, const HeadArgs& a, const PendingStep* pend, HeadSh
     PHASE_END(PH_HEAD_SHAPE, ps0, ps1);
     return;
   }
+  if (pf && pf->on) { prior_frames_block(a, *pf, blk - a.nshape); return; }
   // shape prior: w_eff * mean_c( ((x - mean) prec)_c ^2 ), x = [betas | log scales]
   if (a.prior_prec && threadIdx.x < 64) {
     __shared__ float x[32], res[32];
@@ -550,6 +598,10 @@ head_block(const ModelDev& m, const HeadArgs& a, const PendingStep* pend, HeadSh
 
 __global__ void __launch_bounds__(256)
 lbs_head_kernel(ModelDev m, HeadArgs a) { head_block<false>(m, a, nullptr, nullptr); }
+
+// ... for independent images: the prior blocks evaluate one term per frame (prior_frames_block)
+__global__ void __launch_bounds__(256)
+lbs_head_images_kernel(ModelDev m, HeadArgs a, PriorFrames pf) { head_block<false>(m, a, nullptr, nullptr, &pf); }
 
 // ... carrying the optimiser step the previous evaluation left pending (smalfit_fit_run)
 __global__ void __launch_bounds__(256)

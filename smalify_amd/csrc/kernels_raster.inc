@@ -560,6 +560,23 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
   return v;
 }
 
+// One row of loss terms per frame (smalfit_fit_args.losses_per_frame) needs the queue kernels' loss per FRAME, and their persistent
+// workgroups draw pixels of any frame: the <true> instantiations of the band / select kernels also add every settled pixel's
+// fixed-point loss to its frame's 64-bit counter -- integer adds again, so order-free and bit-reproducible.  A lane keeps a running
+// sum while its pixels stay in one frame (the queues are roughly frame-ordered) and sends one atomic per change of frame.
+// Counters sit 256 bytes apart (different memory channels); frame_loss_rows_kernel reads and clears them.  The <false>
+// instantiations are the kernels as they were: without per-frame rows nothing here costs a register or an instruction.
+constexpr int kFrameLossStride = 32;             // unsigned long longs between two frames' counters
+struct FrameLoss { long long acc; int n; };
+__device__ __forceinline__ void frame_loss_flush(unsigned long long* floss, FrameLoss& f) {
+  if (f.acc) atomicAdd(floss + (size_t)f.n * kFrameLossStride, (unsigned long long)f.acc);
+  f.acc = 0;
+}
+__device__ __forceinline__ void frame_loss_add(unsigned long long* floss, FrameLoss& f, int n, long long v) {
+  if (n != f.n) { frame_loss_flush(floss, f); f.n = n; }
+  f.acc += v;
+}
+
 // alpha = 2^-(sum / 2^24) for the fixed-point log sum of a pixel: integer part by exponent arithmetic, the 24-bit
 // fraction through the hardware exp2 (1 ulp) -- no double precision needed; resolve and band kernels share it
 __device__ __forceinline__ float alpha_from_log_sum(unsigned long long sum) {
@@ -754,11 +771,13 @@ constexpr int kBandNarrowUnroll = 4, kBandWideUnroll = 1;
 constexpr int kBandBlocks = 1536;
 // the band work of 256-thread workgroup `bi` of `nblocks`.  zs: 16 x 64 floats of LDS.  A pixel whose band cannot decide (a
 // depth tie at the cut) is appended to the selection queue.  Returns the lane's loss partial.
+template <bool kFrameLoss>
 __device__ __forceinline__ long long
 band_role(int bi, int nblocks, float (*zs)[64], int S, int M, WinMap win, float w_sil, unsigned long long* __restrict__ gacc,
           unsigned* __restrict__ bcnt, const float2* __restrict__ blist,
           SilTarget tsil, float* __restrict__ sil_out, float2* __restrict__ gz,
-          float2* __restrict__ zband, int* __restrict__ qcount, int* __restrict__ queue, const int* __restrict__ bqueue) {
+          float2* __restrict__ zband, int* __restrict__ qcount, int* __restrict__ queue, const int* __restrict__ bqueue,
+          unsigned long long* __restrict__ floss /*kFrameLoss: the per-frame counters*/) {
   static_assert(kBandCap == 64, "four band entries per lane of a quarter-wave");
   (void)M;
   constexpr int K = kFacesPerPixel;
@@ -769,6 +788,7 @@ band_role(int bi, int nblocks, float (*zs)[64], int S, int M, WinMap win, float 
   const int nb = qcount[1];
   const int npix = S * S;
   long long lacc = 0;
+  FrameLoss fl{0, 0};
   // band population this evaluation's miss rate calls for (same rule as the selection kernel; qcount[2] does not
   // change while this kernel runs, so the decision is the same in every run)
   const float miss = (float)qcount[2] / (float)max(qcount[2] + nb, 1);
@@ -866,7 +886,9 @@ band_role(int bi, int nblocks, float (*zs)[64], int S, int M, WinMap win, float 
           const int n = gp / npix;
           const float wn = w_sil / ((float)frame_window_size(n, win) * (float)S * (float)S);
           const float diff = sil - ts;
-          lacc += (long long)(fabsf(diff) * wn * kLossFix);
+          const long long lp = (long long)(fabsf(diff) * wn * kLossFix);
+          lacc += lp;
+          if constexpr (kFrameLoss) frame_loss_add(floss, fl, n, lp);
           const float sgn = (diff > 0.f) ? 1.0f : ((diff < 0.f) ? -1.0f : 0.0f);
           gx = -wn * sgn * alpha * (1.0f / kSigma);
         }
@@ -885,20 +907,23 @@ band_role(int bi, int nblocks, float (*zs)[64], int S, int M, WinMap win, float 
     }
     __builtin_amdgcn_wave_barrier();
   }
+  if constexpr (kFrameLoss) frame_loss_flush(floss, fl);
   return lacc;
 }
 
 // 6 waves per SIMD: <= 80 registers, six instead of five workgroups per CU (resolve + band 43.5 -> 41.9 us; 8 spills)
+template <bool kFrameLoss>
 __global__ void __launch_bounds__(256, 6)
 raster_band_kernel(int S, int M, WinMap win, float w_sil, unsigned long long* __restrict__ gacc,
                    unsigned* __restrict__ bcnt, const float2* __restrict__ blist,
                    SilTarget tsil, float* __restrict__ sil_out, float2* __restrict__ gz,
                    float2* __restrict__ zband, int* __restrict__ qcount, int* __restrict__ queue,
-                   const int* __restrict__ bqueue, long long* __restrict__ bloss /*[gridDim.x]: weighted |sil - target| per block in 2^-40 fixed point, or null*/) {
+                   const int* __restrict__ bqueue, long long* __restrict__ bloss /*[gridDim.x]: weighted |sil - target| per block in 2^-40 fixed point, or null*/,
+                   unsigned long long* __restrict__ floss /*kFrameLoss: [M][kFrameLossStride], the same loss per frame*/) {
   __shared__ __attribute__((aligned(16))) float zs[16][64];
   const int t = threadIdx.x;
-  const long long lacc = band_role(blockIdx.x, gridDim.x, zs, S, M, win, w_sil, gacc, bcnt, blist, tsil, sil_out, gz, zband,
-                                   qcount, queue, bqueue);
+  const long long lacc = band_role<kFrameLoss>(blockIdx.x, gridDim.x, zs, S, M, win, w_sil, gacc, bcnt, blist, tsil, sil_out, gz, zband,
+                                               qcount, queue, bqueue, floss);
   if (bloss) {
     __shared__ long long lred[4];
     const long long ws = wave_sum_i64(lacc);
@@ -1271,16 +1296,19 @@ __device__ __forceinline__ long long select_pixel(const SelCtx& c, const SelLds&
 }
 
 // 4 waves per SIMD: <= 128 VGPRs (133 unconstrained; 12 bytes of scratch), LDS admits 14 waves per CU
+template <bool kFrameLoss>
 __global__ void __launch_bounds__(64 * kSelWaves, 4)
 raster_select_kernel(int F, int S, int M, WinMap win, float w_sil, const float4* __restrict__ frec, const float* __restrict__ zc,
                      const int4* __restrict__ brect, const int2* __restrict__ fbox, int* __restrict__ qcount,
                      const int* __restrict__ queue, SilTarget tsil,
                      float* __restrict__ sil_out, float2* __restrict__ gz, float2* __restrict__ zband,
                      unsigned char* __restrict__ pcount /*[M][F]: set to kNoList for faces the forward sweep's lists may miss*/,
-                     long long* __restrict__ qloss /*[gridDim.x]: weighted |sil - target| per block in 2^-40 fixed point, or null*/, int dbg) {
+                     long long* __restrict__ qloss /*[gridDim.x]: weighted |sil - target| per block in 2^-40 fixed point, or null*/, int dbg,
+                     unsigned long long* __restrict__ floss /*kFrameLoss: [M][kFrameLossStride], the same loss per frame*/) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kSelWaves][kSelLdsBytes];
   __shared__ long long wloss[kSelWaves];
   long long lacc = 0;
+  FrameLoss fl{0, 0};
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int nq = *qcount;                                   // resolve's pixels + the band kernel's failures
   // how many candidates the new bands may hold: wide bands survive large parameter steps (stage 1) but cost list
@@ -1323,13 +1351,16 @@ raster_select_kernel(int F, int S, int M, WinMap win, float w_sil, const float4*
 #pragma unroll 1
     for (int i = 0; i < B; ++i) {
       const int gp_next = (i + 1 < B) ? entry(tk + i + 1) : -1;     // in flight while this pixel is selected
-      lacc += select_pixel(c, L, gp);
+      const long long lp = select_pixel(c, L, gp);
+      lacc += lp;
+      if constexpr (kFrameLoss) { if (lane == 0) frame_loss_add(floss, fl, gp / (S * S), lp); }
       __builtin_amdgcn_wave_barrier();
       gp = gp_next;
       if (gp < 0) { more = (i + 1 == B); break; }            // end of the batch, or the batch ran past the end of the share
     }
     if (!more) break;
   }
+  if constexpr (kFrameLoss) { if (lane == 0) frame_loss_flush(floss, fl); }
   if (qloss) {
     if (lane == 0) wloss[w] = lacc;
     __syncthreads();

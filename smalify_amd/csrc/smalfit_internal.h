@@ -129,6 +129,20 @@ struct AssembleArgs {
   float* losses;
 };
 
+// What assemble_kernel and frame_loss_rows_kernel take beside AssembleArgs (which the pending step carries into lbs_head_step_kernel
+// and therefore stays what it is): independent images and one row of loss terms per frame.  All zero: neither.
+struct AssembleExt {
+  // independent images (one shape set per frame): the prior's gradient as one row per shape set, its loss as one term per frame
+  const float* gb_prior_pf;                // rows of gb_stride floats, or null
+  const float* gls_prior_pf;               // rows of gls_stride floats, or null
+  int gb_stride, gls_stride;
+  const float* prior_loss_pf;              // [M] or null
+  // one row of loss terms per frame (smalfit_fit_args.losses_per_frame), written by frame_loss_rows_kernel
+  float* losses_pf;                        // [M][9] or null
+  unsigned long long* frame_qloss;         // [M][kFrameLossStride]: the queue kernels' 2^-40 fixed-point loss per frame; cleared by its reader
+  int prior_windows;                       // one subject: windows whose prior term this evaluation owns (their sum is *loss_betas)
+};
+
 // One optimiser step that has not been taken yet, carried by the NEXT evaluation's lbs_head_kernel (smalfit_fit_run): the raw
 // partials of the previous evaluation's backward pass as assemble_kernel would read them, and per parameter tensor where its
 // value / moments are read and where value / moments / gradient go.  Per-frame tensors are stepped in place by their frame's

@@ -98,6 +98,8 @@ struct smalfit_engine {
   float *dJ41, *dvert, *dvp, *dext, *dA, *dpf_part, *dbeta_part, *dtheta, *dls, *dJrest;
   float* dbetaJ;
   float *dth_direct, *dtr_direct, *dtr_part, *loss_part, *loss_betas, *gb_prior, *gls_prior;
+  float *loss_betas_pf, *gb_prior_pf, *gls_prior_pf;   // independent images: the prior per frame, [maxM], [maxM][kPriorSlotB], [maxM][kPriorSlotLs]
+  unsigned long long* frame_qloss;                     // the queue kernels' loss per frame: [maxM][kFrameLossStride], zero between evaluations
   float *ones, *zeros;
   int* canon;
   // priors
@@ -458,6 +460,10 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   CARVE(step_counter, 4, int);
   CARVE(gb_prior, 64, float);
   CARVE(gls_prior, 16, float);
+  CARVE(loss_betas_pf, M, float);
+  CARVE(gb_prior_pf, M * 32, float);
+  CARVE(gls_prior_pf, M * 8, float);
+  CARVE(frame_qloss, M * kFrameLossStride, unsigned long long);
   CARVE(ones, 128, float);
   CARVE(zeros, M * 128, float);
   CARVE(canon, 32, int);
@@ -578,8 +584,9 @@ struct HeadExtras {
   int joff_stride = 0;
   const PendingStep* pending = nullptr;   // smalfit_fit_run: the optimiser step the previous evaluation left to this launch
   int prior_slot = 0;                     // which half of gb_prior / gls_prior the prior block writes (a pending step reads the other)
+  bool prior_per_frame = false;           // independent images: one prior term per frame (rows of gb_prior_pf / gls_prior_pf, loss_betas_pf)
 };
-static constexpr int kPriorSlotB = 32, kPriorSlotLs = 8;   // floats per slot of smalfit_engine::gb_prior / gls_prior
+static constexpr int kPriorSlotB = 32, kPriorSlotLs = 8;   // floats per slot of smalfit_engine::gb_prior / gls_prior, per row of gb_prior_pf / gls_prior_pf
 
 static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float* betas, int betas_stride,
                            int nb, const float* logscale, int ls_stride, const float* trans,
@@ -602,8 +609,16 @@ static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float
     h.prior_w = ex->prior_w; h.prior_loss = e->loss_betas;
     h.prior_gb = e->gb_prior + ex->prior_slot * kPriorSlotB; h.prior_gls = e->gls_prior + ex->prior_slot * kPriorSlotLs;
   }
+  PriorFrames pf;
+  std::memset(&pf, 0, sizeof(pf));
+  if (prior && ex->prior_per_frame) {
+    pf.on = 1; pf.loss = e->loss_betas_pf; pf.gb = e->gb_prior_pf; pf.gb_stride = kPriorSlotB; pf.gls = e->gls_prior_pf; pf.gls_stride = kPriorSlotLs;
+  }
+  // blocks behind the shape blocks: one for the shared shape's prior, one per kPriorFrames frames for independent images
+  const int nprior = !prior ? 0 : (ex->prior_per_frame ? (M + kPriorFrames - 1) / kPriorFrames : 1);
   if (ex && ex->pending) lbs_head_step_kernel<<<M + h.nshape + (prior ? 1 : 0), 256, 0, st>>>(m, h, *ex->pending);
-  else lbs_head_kernel<<<M + h.nshape + (prior ? 1 : 0), 256, 0, st>>>(m, h);
+  else if (pf.on) lbs_head_images_kernel<<<M + h.nshape + nprior, 256, 0, st>>>(m, h, pf);
+  else lbs_head_kernel<<<M + h.nshape + nprior, 256, 0, st>>>(m, h);
   LAUNCH_OK("lbs_head_kernel");
   const int vs_stride = betas_stride ? 3 * m.Vp : 0;
   // M-adaptive launch shape (round 6): the wide matrix-core kernel (64 vertices x 16 frames per workgroup) fills the chip from 64
@@ -631,7 +646,7 @@ static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float
 // resolve launches (they depend on the skinned vertices only and are needed by the backward pass only)
 static int run_raster_forward(smalfit_engine* e, hipStream_t st, int M, WinMap win, float w_sil,
                               SilTarget tsil, float* sil_out, float2* gz_unused, float* blk_loss,
-                              float* joints_out = nullptr, const LossArgs* la = nullptr) {
+                              float* joints_out = nullptr, const LossArgs* la = nullptr, unsigned long long* floss = nullptr) {
   (void)gz_unused;
   // e->gz is persistent state: .y carries each pixel's depth threshold into the next evaluation (verified there)
   float2* gz = e->gz;
@@ -658,13 +673,22 @@ static int run_raster_forward(smalfit_engine* e, hipStream_t st, int M, WinMap w
                                                                          la ? *la : no_loss, la ? M : 0);
     LAUNCH_OK("raster_resolve_kernel");
     // the band kernel's loss partials follow the select kernel's in qloss
-    raster_band_kernel<<<kBandBlocks, 256, 0, st>>>(e->S, M, win, w_sil, e->gacc, e->bcnt, e->blist, tsil, sil_out, gz, e->zband,
-                                                    e->qcount, e->queue, e->bqueue, tsil ? e->qloss + kSelectBlocks : nullptr);
+    // (floss: the caller wants the loss per frame too -- the instantiations that feed the per-frame counters)
+    if (floss && tsil)
+      raster_band_kernel<true><<<kBandBlocks, 256, 0, st>>>(e->S, M, win, w_sil, e->gacc, e->bcnt, e->blist, tsil, sil_out, gz, e->zband,
+                                                            e->qcount, e->queue, e->bqueue, e->qloss + kSelectBlocks, floss);
+    else
+      raster_band_kernel<false><<<kBandBlocks, 256, 0, st>>>(e->S, M, win, w_sil, e->gacc, e->bcnt, e->blist, tsil, sil_out, gz, e->zband,
+                                                             e->qcount, e->queue, e->bqueue, tsil ? e->qloss + kSelectBlocks : nullptr, nullptr);
     LAUNCH_OK("raster_band_kernel");
   }
   Section sec(e, st, SMALFIT_SEC_RASTER_SELECT);
-  raster_select_kernel<<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(m.F, e->S, M, win, w_sil, e->frec, e->zc, e->brect, e->fbox, e->qcount, e->queue,
-                                                      tsil, sil_out, gz, e->zband, e->pcount, tsil ? e->qloss : nullptr, g_dbg);
+  if (floss && tsil)
+    raster_select_kernel<true><<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(m.F, e->S, M, win, w_sil, e->frec, e->zc, e->brect, e->fbox, e->qcount, e->queue,
+                                                        tsil, sil_out, gz, e->zband, e->pcount, e->qloss, g_dbg, floss);
+  else
+    raster_select_kernel<false><<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(m.F, e->S, M, win, w_sil, e->frec, e->zc, e->brect, e->fbox, e->qcount, e->queue,
+                                                        tsil, sil_out, gz, e->zband, e->pcount, tsil ? e->qloss : nullptr, g_dbg, nullptr);
   LAUNCH_OK("raster_select_kernel");
   return 0;
 }
@@ -725,6 +749,17 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   if (a->w_pose > 0.f && !e->has_pose_prior) return fail("smalfit_fit_eval: pose prior not set");
   if (a->w_betas > 0.f && e->shape_dim <= 0) return fail("smalfit_fit_eval: shape prior not set");
   if (a->logscale_mode != 0 && !a->log_beta_scales) return fail("smalfit_fit_eval: log_beta_scales missing");
+  // independent images: every frame its own subject.  Everything that couples frames is refused, not ignored
+  if (a->subject_frames != 0 && a->subject_frames != 1)
+    return fail("smalfit_fit_eval: subject_frames must be 0 (one subject) or 1 (independent images); clips of K > 1 frames per subject in one batch are not implemented");
+  const bool indep = a->subject_frames == 1;
+  if (indep) {
+    if (a->window != 1) return fail("smalfit_fit_eval: subject_frames = 1 needs window = 1 (an image is its own window)");
+    if (a->temporal) return fail("smalfit_fit_eval: subject_frames = 1 needs temporal = 0 (unrelated images have no neighbours)");
+    if (a->logscale_mode == 1) return fail("smalfit_fit_eval: subject_frames = 1 takes logscale_mode 0 or 2 (nothing is shared between images)");
+    if (a->halo_prev || a->halo_next) return fail("smalfit_fit_eval: subject_frames = 1 needs halo_prev = halo_next = NULL");
+    if (a->frame_offset != 0 || a->total_frames != 0) return fail("smalfit_fit_eval: subject_frames = 1 needs frame_offset = total_frames = 0");
+  }
   hipStream_t st = (hipStream_t)stream;
   const ModelDev& m = e->model->dev;
   const float* gmask = a->global_mask ? a->global_mask : e->ones;
@@ -738,8 +773,13 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   const bool shape_prior = a->w_betas > 0.f;
   const int D = a->shape_prior_dim > 0 ? a->shape_prior_dim : e->shape_dim;
   const bool prior_uses_ls = shape_prior && D > 20;
-  if (shape_prior && prior_uses_ls && a->logscale_mode != 1)
+  if (indep && shape_prior && prior_uses_ls && a->logscale_mode != 2)
+    return fail("smalfit_fit_eval: a 26-dim shape prior of independent images needs per-frame log_beta_scales (logscale_mode 2)");
+  if (!indep && shape_prior && prior_uses_ls && a->logscale_mode != 1)
     return fail("smalfit_fit_eval: a 26-dim shape prior needs shared log_beta_scales");
+  // one row of loss terms per frame: only an evaluation that assembles writes (and clears the counters behind) them
+  const bool rows = a->losses_per_frame != nullptr && fold.assemble;
+  int prior_windows = 0;
   {
     Section sec(e, st, SMALFIT_SEC_LBS_FWD);
     HeadExtras ex;
@@ -751,9 +791,12 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
       // windows that START among its frames (a shard in the middle of a window owns none of it)
       const int w0 = (win.offset + win.window - 1) / win.window, w1 = (win.offset + M + win.window - 1) / win.window;
       ex.prior_w = a->w_betas * (float)(w1 - w0);
+      prior_windows = w1 - w0;
+      if (indep) { ex.prior_w = a->w_betas; ex.prior_per_frame = true; }    // once per image
     }
     // with the rasteriser running, the joint regression and the loss terms ride in its launches (run_raster_forward)
-    if (run_lbs_forward(e, st, M, a->betas, 0, nb, ls, ls_stride, a->trans, fused_loss ? nullptr : e->joints, &ex)) return 1;
+    // (betas_stride nb: one shape set per frame)
+    if (run_lbs_forward(e, st, M, a->betas, indep ? nb : 0, nb, ls, ls_stride, a->trans, fused_loss ? nullptr : e->joints, &ex)) return 1;
   }
 
   LossArgs la;
@@ -776,7 +819,8 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
     SilTarget tsil{nullptr, nullptr};
     if (sil_on) { if (a->target_sil_u8) tsil.b = a->target_sil_u8; else tsil.f = a->target_sil; }
     if (run_raster_forward(e, st, M, win, a->w_sil, tsil, a->sil_out,
-                           sil_on ? e->gz : nullptr, sil_on ? e->tile_loss : nullptr, e->joints, &la)) return 1;
+                           sil_on ? e->gz : nullptr, sil_on ? e->tile_loss : nullptr, e->joints, &la,
+                           (rows && sil_on) ? e->frame_qloss : nullptr)) return 1;
   }
   if (sil_on) {
     Section sec(e, st, SMALFIT_SEC_RASTER_BWD);
@@ -793,8 +837,9 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   const bool need_ls = a->g_log_beta_scales != nullptr && a->logscale_mode != 0;
   {
     Section sec(e, st, SMALFIT_SEC_LBS_BWD);
-    if (run_lbs_backward(e, st, M, nb, 1, sil_on ? e->dface : nullptr, e->dJ41, nullptr, need_pose, need_beta, need_ls,
-                         e->dth_direct, 0)) return 1;
+    // (independent images: per-frame partials of the shape-blend adjoint, per-frame rest joints)
+    if (run_lbs_backward(e, st, M, nb, indep ? 0 : 1, sil_on ? e->dface : nullptr, e->dJ41, nullptr, need_pose, need_beta, need_ls,
+                         e->dth_direct, indep ? 105 : 0)) return 1;
   }
 
   AssembleArgs g;
@@ -815,10 +860,27 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   g.g_grot = a->g_global_rotation; g.g_jrot = a->g_joint_rotations; g.g_trans = a->g_trans;
   g.losses = a->losses;
   g.lpart = e->lpart; g.qpart = e->qpart; g.counter = e->asm_counter;
+  AssembleExt gx;
+  std::memset(&gx, 0, sizeof(gx));
+  gx.losses_pf = rows ? a->losses_per_frame : nullptr; gx.frame_qloss = e->frame_qloss; gx.prior_windows = prior_windows;
+  if (indep) {
+    g.betas_shared = 0; g.ls_shared = 0; g.ngrp_beta = 1;
+    g.gb_prior = nullptr; g.gls_prior = nullptr; g.loss_betas = nullptr;      // the shared-shape slots stay unused: one row per image instead
+    if (shape_prior) {
+      gx.gb_prior_pf = e->gb_prior_pf; gx.gb_stride = kPriorSlotB; gx.prior_loss_pf = e->loss_betas_pf;
+      if (prior_uses_ls) { gx.gls_prior_pf = e->gls_prior_pf; gx.gls_stride = kPriorSlotLs; }
+    }
+  }
   if (fold.args_out) *fold.args_out = g;
   if (fold.assemble) {
-    assemble_kernel<<<1 + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g);
+    // roles: one block per shape set | limb scales | elements | loss partials
+    if (indep) assemble_kernel<true><<<M + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g, gx);
+    else assemble_kernel<false><<<1 + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g, gx);
     LAUNCH_OK("assemble_kernel");
+    if (rows) {
+      frame_loss_rows_kernel<<<kAsmRows, 256, 0, st>>>(g, gx);
+      LAUNCH_OK("frame_loss_rows_kernel");
+    }
   }
   if (e->prof_on) {
     if (e->prof_iter < e->prof_cap && (e->prof_tick % e->prof_stride) == 0) e->prof_iter++;
@@ -950,7 +1012,7 @@ int smalfit_lbs_backward_ex(smalfit_engine* e, void* stream, const smalfit_lbs_a
     g.M = M; g.nb = nb; g.NBall = m.NBall; g.nblk_beta = e->nblk_beta; g.betas_shared = 0;
     g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = 1; g.g_betas = a->dbeta;
     g.win = WinMap{1, 0, M};
-    assemble_kernel<<<M, 256, 0, st>>>(g);   // only the per-frame betas roles
+    assemble_kernel<false><<<M, 256, 0, st>>>(g, AssembleExt{});   // only the per-frame betas roles
     LAUNCH_OK("assemble_kernel");
   }
   if (a->dv_offset) {
@@ -1212,6 +1274,7 @@ struct FoldPlan {
 static bool plan_fold(const smalfit_fit_args* a, const smalfit_adam_args* o, const AdamSegments& sg, FoldPlan& plan) {
   const int M = a->num_frames;
   if (M <= 0 || !a->betas || !a->global_rotation || !a->joint_rotations || !a->trans) return false;
+  if (a->subject_frames != 0) return false;      // independent images keep the plain chain (per-image betas are not folded yet)
   const float* ptr[5] = {a->betas, a->logscale_mode ? a->log_beta_scales : nullptr, a->global_rotation, a->joint_rotations, a->trans};
   const float* gptr[5] = {a->g_betas, a->g_log_beta_scales, a->g_global_rotation, a->g_joint_rotations, a->g_trans};
   const long long cnt[5] = {20, a->logscale_mode == 1 ? 6 : (long long)M * 6, (long long)M * 3, (long long)M * 102, (long long)M * 3};
@@ -1253,9 +1316,14 @@ int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, 
   if (!e || !a || !o) return fail("smalfit_fit_run: null argument");
   if (iterations <= 0) return fail("smalfit_fit_run: iterations must be positive");
   if (o->step < 0) return fail("smalfit_fit_run: step must be >= 0");
+  // struct_size before any other field of the block is read (subject_frames sits at its tail: a block of an older header ends before it)
+  if (a->struct_size != (unsigned)sizeof(smalfit_fit_args))
+    return fail("smalfit_fit_run: smalfit_fit_args.struct_size does not match this library (built against another smalfit.h?)");
   AdamSegments sg;
   if (pack_adam_segments(o, sg)) return 1;
   hipStream_t st = (hipStream_t)stream;
+  if (e->use_graph && a->subject_frames != 0)
+    return fail("smalfit_fit_run: subject_frames != 0 is not supported by the graph replay (smalfit_engine_set_graph)");
   if (e->use_graph && !e->prof_on && iterations >= 2 && st != nullptr) {
     // one iteration (tick, the evaluation's kernels, Adam) captured once per (arguments, stream) and replayed
     smalfit_adam_args okey = *o;
@@ -1358,6 +1426,8 @@ int smalfit_shard_local_step(smalfit_engine* e, void* stream, const smalfit_fit_
                              const float* shared_grad, float* record) {
   if (!e || !a || !o || !record || !shared_grad) return fail("smalfit_shard_local_step: null argument");
   if (o->step < 0) return fail("smalfit_shard_local_step: step must be >= 0");
+  if (a->struct_size == (unsigned)sizeof(smalfit_fit_args) && a->subject_frames != 0)
+    return fail("smalfit_shard_local_step: subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)");
   if (smalfit_fit_eval(e, stream, a)) return 1;
   if (launch_adam_next_step((hipStream_t)stream, o)) return 1;
   return smalfit_shard_record(stream, num_shared, shared_grad, a->num_frames, a->global_rotation, a->joint_rotations, a->trans,
@@ -1398,6 +1468,8 @@ int smalfit_shard_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a
   if (sh->num_shared <= 0 || sh->num_trainable_shared < 0 || sh->num_trainable_shared > sh->num_shared) return fail("smalfit_shard_run: bad num_shared / num_trainable_shared");
   if (!sh->shared_grad || !sh->record || !sh->gathered || !sh->allgather) return fail("smalfit_shard_run: missing buffer / collective");
   if (ol->step < 0 || os->step != ol->step) return fail("smalfit_shard_run: adam_local and adam_shared must carry the same step >= 0");
+  if (a->struct_size == (unsigned)sizeof(smalfit_fit_args) && a->subject_frames != 0)
+    return fail("smalfit_shard_run: subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)");
   const int stride = sh->num_shared + 216;
   for (int it = 0; it < iterations; ++it) {
     smalfit_adam_args l = *ol, s = *os;

@@ -274,7 +274,7 @@ int smalfit_fit3d_step(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mes
       g.M = N; g.nb = nb; g.NBall = md.NBall; g.nblk_beta = e->nblk_beta; g.betas_shared = 0;
       g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = md.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = 1; g.g_betas = m->gbetas;
       g.win = WinMap{1, 0, N};
-      assemble_kernel<<<N, 256, 0, st>>>(g);
+      assemble_kernel<false><<<N, 256, 0, st>>>(g, AssembleExt{});
       LAUNCH_OK("assemble_kernel");
     }
   }

@@ -166,7 +166,8 @@ class Engine:
                  temporal=True, global_mask=None, rotation_mask=None, halo_prev=None, halo_next=None,
                  losses=None, grads=None, want=("betas", "log_beta_scales", "global_rotation",
                                                 "joint_rotations", "trans"),
-                 sil_out=None, proj_out=None, verts_out=None, frame_offset=0, total_frames=0):
+                 sil_out=None, proj_out=None, verts_out=None, frame_offset=0, total_frames=0,
+                 subject_frames=0, losses_per_frame=None):
         """One evaluation of sum_windows SMALFitter.forward + get_temporal and its gradient.
 
         weights = (w_j2d, w_sil, w_betas, w_pose, w_limit, w_splay) as in the reference's OPT_WEIGHTS columns
@@ -178,7 +179,8 @@ class Engine:
             target_visibility=target_visibility, target_sil=target_sil, weights=weights, w_temp=w_temp, window=window,
             temporal=temporal, global_mask=global_mask, rotation_mask=rotation_mask, halo_prev=halo_prev,
             halo_next=halo_next, losses=losses, grads=grads, want=want, sil_out=sil_out, proj_out=proj_out,
-            verts_out=verts_out, frame_offset=frame_offset, total_frames=total_frames)
+            verts_out=verts_out, frame_offset=frame_offset, total_frames=total_frames,
+            subject_frames=subject_frames, losses_per_frame=losses_per_frame)
         check(self.lib.smalfit_fit_eval(self.handle, _stream(), C.byref(a)), "smalfit_fit_eval")
         return losses, grads
 
@@ -187,9 +189,12 @@ class Engine:
                        temporal=True, global_mask=None, rotation_mask=None, halo_prev=None, halo_next=None,
                        losses=None, grads=None, want=("betas", "log_beta_scales", "global_rotation",
                                                       "joint_rotations", "trans"),
-                       sil_out=None, proj_out=None, verts_out=None, frame_offset=0, total_frames=0):
+                       sil_out=None, proj_out=None, verts_out=None, frame_offset=0, total_frames=0,
+                       subject_frames=0, losses_per_frame=None):
         """-> (smalfit_fit_args, losses, grads, keep-alive list): the argument block of smalfit_fit_eval / smalfit_fit_run.
-        The block holds raw device pointers: the caller keeps the tensors alive for as long as it uses it."""
+        The block holds raw device pointers: the caller keeps the tensors alive for as long as it uses it.
+        subject_frames=1: every frame is an unrelated image with its own betas (M,20) (and limb scales (M,6));
+        losses_per_frame: an (M, 9) float32 tensor that receives each frame's share of the loss terms."""
         M = int(global_rotation.shape[0])
         w_j2d, w_sil, w_betas, w_pose, w_limit, w_splay = [float(w) for w in weights]
         dev = global_rotation.device
@@ -215,6 +220,20 @@ class Engine:
         a.shape_prior_dim = 0
         # where these M frames sit in their sequence (shards; zeros = they are the whole sequence)
         a.frame_offset, a.total_frames = int(frame_offset), int(total_frames)
+        a.subject_frames = int(subject_frames)
+        if a.subject_frames == 1:
+            # the library cannot know the extent of a device pointer: the usual (20,) betas here would be read M * 20 floats far
+            if betas is None or betas.numel() != M * 20:
+                raise SmalfitError("subject_frames=1 takes betas of (num_frames, 20): one shape per image")
+            if log_beta_scales is not None and log_beta_scales.dim() != 1 and log_beta_scales.numel() != M * 6:
+                raise SmalfitError("subject_frames=1 takes log_beta_scales of (num_frames, 6), or None")   # ((6,) = shared: the library refuses it)
+            for k in ("betas", "log_beta_scales"):
+                if k in want and grads.get(k) is not None and params[k] is not None and grads[k].numel() != params[k].numel():
+                    raise SmalfitError("subject_frames=1: the gradient buffer of %s must have its shape" % k)
+        if losses_per_frame is not None and (losses_per_frame.dtype != torch.float32 or not losses_per_frame.is_contiguous()
+                                             or losses_per_frame.numel() < M * NUM_LOSS_TERMS):
+            raise SmalfitError("losses_per_frame must be a contiguous float32 tensor of (num_frames, %d)" % NUM_LOSS_TERMS)
+        a.losses_per_frame = _ptr(losses_per_frame)
         a.w_j2d, a.w_sil, a.w_betas, a.w_pose, a.w_splay, a.w_temp = w_j2d, w_sil, w_betas, w_pose, w_splay, float(w_temp)
         a.betas, a.log_beta_scales = _ptr(betas), _ptr(log_beta_scales)
         a.global_rotation, a.joint_rotations, a.trans = _ptr(global_rotation), _ptr(joint_rotations), _ptr(trans)
@@ -234,7 +253,8 @@ class Engine:
         a.g_trans = _ptr(grads.get("trans")) if "trans" in want else None
         a.sil_out, a.proj_out, a.verts_out = _ptr(sil_out), _ptr(proj_out), _ptr(verts_out)
         keep = [betas, log_beta_scales, global_rotation, joint_rotations, trans, target_joints, target_visibility,
-                target_sil, global_mask, rotation_mask, halo_prev, halo_next, losses, grads, sil_out, proj_out, verts_out]
+                target_sil, global_mask, rotation_mask, halo_prev, halo_next, losses, grads, sil_out, proj_out, verts_out,
+                losses_per_frame]
         return a, losses, grads, keep
 
     def fit_run(self, fit_args, adam_args, iterations):

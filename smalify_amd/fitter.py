@@ -82,26 +82,15 @@ class FusedFitter:
         self.visibility_stage0 = vis0.contiguous()
 
         N = self.N
-        self.ls_shared = self.unity            # smal_fitter.py:61 vs :71-72
-        n_ls = 6 if self.ls_shared else N * 6
-        self.offsets = {}
-        off = 0
-        for name, count in (("betas", 20), ("log_beta_scales", n_ls), ("joint_rotations", N * 102),
-                            ("global_rotation", N * 3), ("trans", N * 3)):
-            self.offsets[name] = (off, count)
-            off += count
+        self.ls_shared = self._limb_scales_shared()
+        self.offsets, shapes, off = self._parameter_layout(N)
         self.flat = torch.zeros(off, **f32)
         self.grad = torch.zeros(off, **f32)
         self.exp_avg = torch.zeros(off, **f32)
         self.exp_avg_sq = torch.zeros(off, **f32)
-        shapes = dict(betas=(20,), log_beta_scales=(6,) if self.ls_shared else (N, 6),
-                      joint_rotations=(N, 34, 3), global_rotation=(N, 3), trans=(N, 3))
         self.p = {k: self.flat[o:o + c].view(shapes[k]) for k, (o, c) in self.offsets.items()}
         self.g = {k: self.grad[o:o + c].view(shapes[k]) for k, (o, c) in self.offsets.items()}
-        if mean_betas is not None:
-            self.p["betas"].copy_(torch.as_tensor(np.asarray(mean_betas)[:20], **f32))
-        if mean_log_scales is not None and self.ls_shared:
-            self.p["log_beta_scales"].copy_(torch.as_tensor(np.asarray(mean_log_scales), **f32))
+        self._initial_shape(mean_betas, mean_log_scales, f32)
         self.p["global_rotation"].copy_(torch.as_tensor(model_io.initial_global_rotation(), **f32)[None].expand(N, 3))
         self.global_mask = torch.ones(3, **f32)
         self.rotation_mask = torch.ones(34, 3, **f32)
@@ -114,6 +103,33 @@ class FusedFitter:
         # rest of the construction, not in front of the first launch of the first stage
         for stage_id in (0, 1):
             self._fit_args((0, 0, 0, 0, 0, 0), 0.0, stage_id, PARAM_NAMES)
+
+    # ---- what a subclass with another notion of "shared" replaces (smalify_amd/image_batch.py) ---------------
+    def _limb_scales_shared(self):
+        return self.unity                      # smal_fitter.py:61 vs :71-72
+
+    def _parameter_layout(self, N):
+        """-> ({name: (offset, count)} in the flat buffers, {name: shape}, total floats)"""
+        n_ls = 6 if self.ls_shared else N * 6
+        offsets, off = {}, 0
+        for name, count in (("betas", 20), ("log_beta_scales", n_ls), ("joint_rotations", N * 102),
+                            ("global_rotation", N * 3), ("trans", N * 3)):
+            offsets[name] = (off, count)
+            off += count
+        shapes = dict(betas=(20,), log_beta_scales=(6,) if self.ls_shared else (N, 6),
+                      joint_rotations=(N, 34, 3), global_rotation=(N, 3), trans=(N, 3))
+        return offsets, shapes, off
+
+    def _initial_shape(self, mean_betas, mean_log_scales, f32):
+        if mean_betas is not None:
+            self.p["betas"].copy_(torch.as_tensor(np.asarray(mean_betas)[:20], **f32))
+        if mean_log_scales is not None and self.ls_shared:
+            self.p["log_beta_scales"].copy_(torch.as_tensor(np.asarray(mean_log_scales), **f32))
+
+    def _sequence_kwargs(self):
+        """how the frames relate to each other, as build_fit_args takes it"""
+        return dict(window=self.window, temporal=True, halo_prev=self.halo_prev, halo_next=self.halo_next,
+                    frame_offset=self.frame_offset, total_frames=self.total_frames)
 
     def enable_joint_limits(self, min_values=None, max_values=None):
         """switch on the joint-limit hinge the reference has commented out (smal_fitter.py:76-79,146-151): from then on
@@ -175,10 +191,9 @@ class FusedFitter:
                 betas=self.p["betas"], log_beta_scales=self.p["log_beta_scales"],
                 global_rotation=self.p["global_rotation"], joint_rotations=self.p["joint_rotations"],
                 trans=self.p["trans"], target_joints=self.target_joints, target_visibility=vis,
-                target_sil=self.target_sil, weights=weights, w_temp=w_temp, window=self.window,
-                temporal=True, global_mask=self.global_mask, rotation_mask=self.rotation_mask,
-                halo_prev=self.halo_prev, halo_next=self.halo_next,
-                losses=self.losses, grads=self.g, want=want, frame_offset=self.frame_offset, total_frames=self.total_frames, **outs)
+                target_sil=self.target_sil, weights=weights, w_temp=w_temp,
+                global_mask=self.global_mask, rotation_mask=self.rotation_mask,
+                losses=self.losses, grads=self.g, want=want, **self._sequence_kwargs(), **outs)
         # Every pointer of the block is known once the fitter exists: it is marshalled ONCE per set of tensors (~100 us of ctypes work:
         # 35 checked pointers) and a stage's block is a copy of that template with the handful of per-stage fields set -- a stage
         # change costs the host ~10 us instead of ~100 (it sits in front of the first launch of every stage).
@@ -192,10 +207,9 @@ class FusedFitter:
                 betas=self.p["betas"], log_beta_scales=self.p["log_beta_scales"],
                 global_rotation=self.p["global_rotation"], joint_rotations=self.p["joint_rotations"],
                 trans=self.p["trans"], target_joints=self.target_joints, target_visibility=vis,
-                target_sil=self.target_sil, weights=(0, 0, 0, 0, 0, 0), w_temp=0.0, window=self.window,
-                temporal=True, global_mask=self.global_mask, rotation_mask=self.rotation_mask,
-                halo_prev=self.halo_prev, halo_next=self.halo_next,
-                losses=self.losses, grads=self.g, want=PARAM_NAMES, frame_offset=self.frame_offset, total_frames=self.total_frames)
+                target_sil=self.target_sil, weights=(0, 0, 0, 0, 0, 0), w_temp=0.0,
+                global_mask=self.global_mask, rotation_mask=self.rotation_mask,
+                losses=self.losses, grads=self.g, want=PARAM_NAMES, **self._sequence_kwargs())
             base = bases[pk] = (bytes(a), keep)
         a = eng.FitArgs.from_buffer_copy(base[0])
         a.w_j2d, a.w_sil, a.w_betas, a.w_pose, a.w_limit, a.w_splay = weights

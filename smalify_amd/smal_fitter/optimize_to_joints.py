@@ -2,7 +2,9 @@
 
 `main()` loads the configured sequence (data_loader.py), runs the fused on-device loop (smalify_amd.fitter.FusedFitter)
 with the reference's schedule and writes the same per-frame checkpoint files (st{stage}_ep{epoch}.pkl / .ply, final
-st10_ep0).  `fit_sequence` takes the loader's output tuple `(rgb, sil, joints, visibility), filenames` directly."""
+st10_ep0).  `fit_sequence` takes the loader's output tuple `(rgb, sil, joints, visibility), filenames` directly.
+`fit_images` (opt-in: `main(independent=True)`, `--independent`) takes the same tuple as UNRELATED images -- a dataset
+of single images, each with its own shape -- and fits them in batches (smalify_amd.image_batch.ImageBatchFitter)."""
 from __future__ import annotations
 
 import os
@@ -120,7 +122,42 @@ def fit_sequence(data, filenames, model_data, pose_prior, shape_prior, use_unity
     return f
 
 
-def main():
+def fit_images(data, filenames, model_data, pose_prior, shape_prior, use_unity_prior=True, output_dir=None,
+               opt_weights=None, iters_scale=1.0, max_batch=64):
+    """The loader's images as unrelated subjects: every image gets the complete schedule of a one-image fit (its own
+    betas, limb scales and prior term, no temporal term), `max_batch` images per ImageBatchFitter.  Per image the final
+    checkpoint of the sequence path is written (st10_ep0.pkl / .ply under <output_dir>/<image name>/).
+    Returns the per-image parameter dicts in the loader's order."""
+    from .. import image_batch
+    rgb, sil, joints, vis = data
+    N, S = int(np.asarray(joints).shape[0]), int(sil.shape[-1])
+    dm = eng.DeviceModel(model_data)
+    engine = eng.Engine(dm, min(N, int(max_batch)), S)
+    engine.set_pose_prior(*pose_prior)
+    engine.set_shape_prior(*shape_prior)
+    exporter = ImageExporter(output_dir, filenames) if output_dir else None
+    out = []
+    for lo in range(0, N, int(max_batch)):
+        hi = min(N, lo + int(max_batch))
+        engine.reset_raster_cache()                    # the depth bounds of the previous batch's pixels say nothing about these
+        f = image_batch.ImageBatchFitter(engine, joints[lo:hi], vis[lo:hi], sil[lo:hi], use_unity_prior,
+                                         mean_betas=shape_prior[1][:20],
+                                         mean_log_scales=shape_prior[1][20:26] if use_unity_prior else None,
+                                         allow_limb_scaling=config.ALLOW_LIMB_SCALING)
+        f.run_schedule(opt_weights, iters_scale)
+        params = f.frame_parameters()
+        if exporter is not None:
+            v_np = f.snapshot()[0].cpu().numpy()
+            for i, prm in enumerate(params):
+                stem = os.path.join(exporter.output_dirs[lo + i], "st10_ep0")
+                with open(stem + ".pkl", "wb") as fh:
+                    pkl.dump(prm, fh)
+                write_ply(stem + ".ply", v_np[i], model_data.faces)
+        out += params
+    return out
+
+
+def main(independent=False):
     """reference optimize_to_joints.py:55-144: dataset from config.SEQUENCE_OR_IMAGE_NAME, model / priors from the config
     paths (data root: $SMALIFY_DATA), the full schedule, checkpoints under config.OUTPUT_DIR."""
     from .data_loader import load_badja_sequence, load_stanford_sequence
@@ -137,9 +174,13 @@ def main():
     pose_prior = model_io.load_pose_prior(config.WALKING_PRIOR_FILE)
     shape_prior = (model_io.unity_shape_prior(config.UNITY_SHAPE_PRIOR) if use_unity_prior
                    else model_io.family_shape_prior(model_io.load_pickle(config.SMAL_DATA_FILE), config.SHAPE_FAMILY))
+    if independent:                                    # the loader's images are unrelated: one shape per image
+        return fit_images(data, filenames, model_data, pose_prior, shape_prior, use_unity_prior=use_unity_prior,
+                          output_dir=config.OUTPUT_DIR)
     return fit_sequence(data, filenames, model_data, pose_prior, shape_prior, use_unity_prior=use_unity_prior,
                         output_dir=config.OUTPUT_DIR)
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+    main(independent="--independent" in sys.argv[1:])
