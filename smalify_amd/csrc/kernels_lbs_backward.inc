@@ -860,11 +860,7 @@ __global__ void offset_grad_kernel(ModelDev m, int M, const float* __restrict__ 
 // stage; the update itself is adam_update).  fresh != 0: first step of a stage -- the moments are taken as zero instead
 // of being read, so a stage needs no fill of the optimiser state.
 // ------------------------------------------------------------------------------------------------
-struct AdamSegments {
-  int nseg;
-  int beg[4];
-  int off[5];        // prefix sums of the range lengths; off[nseg] = total
-};
+// (the packed ranges: AdamSegments of smalfit_plan.h)
 // element j (< off[nseg]) of the packed ranges
 __device__ __forceinline__ void adam_segments_element(const AdamSegments& sg, int j, float* p, const float* g, float* mm,
                                                       float* vv, float step_size, float b1, float b2, float eps,

@@ -760,7 +760,7 @@ skin_mfma_split_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_sh
 
 // The wide form (rounds 2-5): a workgroup owns 64 vertices x 16 frames, a wave 16 vertices and the whole contraction.  One workgroup
 // per CU at 64 frames, where it beats the split form by 2 us (the split form's four-fold workgroups fetch the frames' pose features
-// and transforms four times as often); the host picks by the number of workgroups (smalfit_launch.inc).
+// and transforms four times as often); the host picks by the number of workgroups (skin_form of smalfit_plan.h).
 __global__ void __launch_bounds__(256)
 skin_mfma_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_shaped, int vs_stride /*0 | 3*Vp*/,
                  const float* __restrict__ pfT, const float* __restrict__ Am, const float* __restrict__ trans,

@@ -1544,3 +1544,20 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
                    atomicAdd(&g_work[28], 1ull); } })
 }
 
+// smalfit_render_backward only.  d(sil)/d(world verts): gather incident-face adjoints, camera adjoint, write interleaved (M,V,3)
+__global__ void raster_vertex_grad_kernel(ModelDev m, const float* __restrict__ proj, const float* __restrict__ dface,
+                                          float* __restrict__ dverts) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
+  if (v >= m.V) return;
+  float gxn = 0.f, gyn = 0.f;
+  const float* df = dface + (size_t)n * m.F * 6;
+  for (int i = m.vf_off[v]; i < m.vf_off[v + 1]; ++i) {
+    gxn += df[m.vf_idx[i] * 2];
+    gyn += df[m.vf_idx[i] * 2 + 1];
+  }
+  const float* pv = proj + (size_t)n * 3 * m.Vp;
+  float g[3];
+  world_to_ndc_bwd(pv[v], pv[m.Vp + v], pv[2 * m.Vp + v], gxn, gyn, g[0], g[1], g[2]);
+  float* o = dverts + ((size_t)n * m.V + v) * 3;
+  o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
+}

@@ -1,5 +1,7 @@
 // Host side of libsmalfit.so: model upload, workspace carving, kernel sequencing, C-ABI.
-// Included at the end of smalfit_kernels.hip (same translation unit as the kernels).
+// Included at the end of smalfit_kernels.hip (same translation unit as the kernels).  Every choice between launches, every grid
+// that depends on the problem's size and every refusal of an argument block is a function of smalfit_plan.h; here are the
+// pointers and the launches.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -7,11 +9,12 @@
 #include <vector>
 
 #include "../../include/smalfit.h"
+#include "smalfit_plan.h"
 
 namespace smalfit {
 
 static thread_local std::string g_err;
-static constexpr int kBetaGroups = 8;        // frame groups of the shape-blend adjoint (dbeta_block) when betas are shared
+static_assert(kHeadPriorFrames == kPriorFrames, "smalfit_plan.h counts the prior blocks of lbs_head_images_kernel");
 static constexpr int kSelectBlocks = 1792;   // persistent grid of raster_select_kernel: 7 resident 2-wave blocks x 256 CUs
 static_assert(kSelectBlocks % (8 * kSelGroups) == 0, "every ticket group of every XCD needs the same number of selection workgroups (a group without one would leave its pixels undone)");
 #ifdef SMALFIT_DEV_PROBES
@@ -24,6 +27,8 @@ static int fail(const std::string& msg) {
   g_err = msg;
   return 1;
 }
+// a refusal of smalfit_plan.h (nullptr: none) under the name of the entry point that met it
+static int refused(const char* who, const char* why) { return why ? fail(std::string(who) + ": " + why) : 0; }
 
 #define HIP_OK(expr)                                                                         \
   do {                                                                                       \
@@ -186,14 +191,13 @@ int smalfit_model_create(const smalfit_model_desc* d, smalfit_model** out) {
   if (!d || !out) return fail("smalfit_model_create: null argument");
   const int V = d->num_verts, F = d->num_faces, NB = d->num_betas;
   if (V <= 0 || F <= 0 || NB <= 0) return fail("smalfit_model_create: bad dimensions");
-  for (int i = 1; i < 35; ++i)
-    if (!(d->parents[i] >= 0 && d->parents[i] < i)) return fail("smalfit_model_create: parents must satisfy 0 <= parents[i] < i");
+  if (!parents_ordered(d->parents, 35)) return fail("smalfit_model_create: parents must satisfy 0 <= parents[i] < i");
   for (int i = 0; i < F * 3; ++i)
     if (d->faces[i] < 0 || d->faces[i] >= V) return fail("smalfit_model_create: face index out of range");
   const int* lms = kDefaultLandmarks;
   for (int i = 0; i < 6; ++i)
     if (lms[i] >= V) return fail("smalfit_model_create: model has fewer vertices than the SMAL landmark ids");
-  const int Vp = (int)align_up((size_t)V, 256);
+  const int Vp = padded_verts(V);
   Blob b;
   // planar bases
   std::vector<float> vt((size_t)3 * Vp, 0.f), sd((size_t)NB * 3 * Vp, 0.f), pd((size_t)306 * 3 * Vp, 0.f);
@@ -386,10 +390,8 @@ void smalfit_model_destroy(smalfit_model* m) {
 // ------------------------------------------------------------------------------------------------
 int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, smalfit_engine** out) {
   if (!model || !out || max_frames <= 0 || image_size <= 0) return fail("smalfit_engine_create: bad argument");
-  // The sweep / backward pixel walk runs in float32 (kernels_raster.inc): row = floor((q + 1/2) / bw) keeps a margin of 1 / (2 bw) >= 1/2048
-  // against an error of ~rows * 2^-22, and byte offsets row * 8 S + 8 col stay below 2^24, for S <= 1024 -- twice the largest size
-  // the reference uses (config 5: 512).  Larger images are rejected rather than walked inexactly.
-  if (image_size > 1024) return fail("smalfit_engine_create: image_size above 1024 is not supported (float32 pixel walk, see kernels_raster.inc)");
+  static_assert(kMaxImageSize == 1024, "the message below names the limit");
+  if (image_size > kMaxImageSize) return fail("smalfit_engine_create: image_size above 1024 is not supported (float32 pixel walk, see kernels_raster.inc)");
   smalfit_engine* e = new smalfit_engine();
   e->model = model;
   e->maxM = max_frames;
@@ -399,7 +401,7 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   e->T = e->Tx * e->Tx;
   e->nrb = ((image_size + kResEdge - 1) / kResEdge) * ((image_size + kResEdge - 1) / kResEdge);   // resolve tiles per frame
   e->nvt = model->Vp / 256;
-  e->nblk_beta = (3 * model->Vp + 255) / 256;
+  e->nblk_beta = nblk_beta(model->Vp);
   const size_t M = max_frames, Vp = model->Vp, F = model->F, S = image_size, T = e->T;
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
@@ -442,7 +444,7 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   CARVE(dext, M * 3 * Vp, float);
   CARVE(dA, M * 420, float);
   CARVE(dpf_part, (size_t)e->CS * M * 308, float);
-  CARVE(dbeta_part, (M + kBetaGroups) * (size_t)e->nblk_beta * model->NBall, float);
+  CARVE(dbeta_part, dbeta_rows(max_frames) * e->nblk_beta * model->NBall, float);
   CARVE(dtheta, M * 105, float);
   CARVE(dls, M * 6, float);
   CARVE(dJrest, M * 105, float);
@@ -456,7 +458,7 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   CARVE(qpart, 64, long long);
   CARVE(zc, M, float);
   CARVE(asm_counter, 4, int);
-  CARVE(shstate, 2 * 3 * 32, float);
+  CARVE(shstate, 2 * kSharedSlotFloats, float);
   CARVE(step_counter, 4, int);
   CARVE(gb_prior, 64, float);
   CARVE(gls_prior, 16, float);
@@ -592,11 +594,10 @@ static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float
                            int nb, const float* logscale, int ls_stride, const float* trans,
                            float* joints_out, const HeadExtras* ex = nullptr) {
   const ModelDev& m = e->model->dev;
-  const int nbs = betas_stride ? M : 1;
   HeadArgs h;
   std::memset(&h, 0, sizeof(h));
   h.M = M; h.Mp = e->Mp; h.nb = nb; h.betas_stride = betas_stride; h.ls_stride = ls_stride;
-  h.nshape_x = m.Vp / 256; h.nshape = h.nshape_x * nbs;
+  h.nshape_x = m.Vp / 256; h.nshape = head_shape_blocks(M, m.Vp, betas_stride != 0);
   h.betas = betas; h.logscale = logscale;
   h.theta_in = (ex && ex->grot) ? nullptr : e->theta;       // component API: theta was copied in by the caller
   if (ex) { h.grot = ex->grot; h.jrot = ex->jrot; h.gmask = ex->gmask; h.rmask = ex->rmask;
@@ -614,25 +615,26 @@ static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float
   if (prior && ex->prior_per_frame) {
     pf.on = 1; pf.loss = e->loss_betas_pf; pf.gb = e->gb_prior_pf; pf.gb_stride = kPriorSlotB; pf.gls = e->gls_prior_pf; pf.gls_stride = kPriorSlotLs;
   }
-  // blocks behind the shape blocks: one for the shared shape's prior, one per kPriorFrames frames for independent images
-  const int nprior = !prior ? 0 : (ex->prior_per_frame ? (M + kPriorFrames - 1) / kPriorFrames : 1);
-  if (ex && ex->pending) lbs_head_step_kernel<<<M + h.nshape + (prior ? 1 : 0), 256, 0, st>>>(m, h, *ex->pending);
-  else if (pf.on) lbs_head_images_kernel<<<M + h.nshape + nprior, 256, 0, st>>>(m, h, pf);
-  else lbs_head_kernel<<<M + h.nshape + nprior, 256, 0, st>>>(m, h);
+  const int nhead = head_blocks(M, m.Vp, betas_stride != 0, !prior ? HeadPrior::None : (pf.on ? HeadPrior::PerFrame : HeadPrior::Shared));
+  if (ex && ex->pending) lbs_head_step_kernel<<<nhead, 256, 0, st>>>(m, h, *ex->pending);   // (one subject: plan_fold refuses independent images)
+  else if (pf.on) lbs_head_images_kernel<<<nhead, 256, 0, st>>>(m, h, pf);
+  else lbs_head_kernel<<<nhead, 256, 0, st>>>(m, h);
   LAUNCH_OK("lbs_head_kernel");
   const int vs_stride = betas_stride ? 3 * m.Vp : 0;
-  // M-adaptive launch shape (round 6): the wide matrix-core kernel (64 vertices x 16 frames per workgroup) fills the chip from 64
-  // frames on; below that its workgroups are too few and too long, and the split form (contraction over four waves, four times the
-  // workgroups, a third of the chain each) is 5 us faster at 8 frames, 3 us at 16 (profiles/r6_ab_skin_split.txt)
-  if (M > 4 && (m.Vp / 64) * ((M + 15) / 16) >= 256)
-    skin_mfma_kernel<<<dim3(m.Vp / 64, (M + 15) / 16), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am, trans,
-                                                                    e->vposed, e->verts, e->proj);
-  else if (M > 4)   // the matrix-core kernels work on tiles of 16 frames; below 5 frames the plain kernel wastes less
-    skin_mfma_split_kernel<<<dim3(m.Vp / kSkinVerts, (M + 15) / 16), kSkinThreads, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am, trans,
-                                                                    e->vposed, e->verts, e->proj);
-  else
-    skin_kernel<8><<<dim3(m.Vp / 64, (M + 7) / 8), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am,
-                                                                 trans, e->vposed, e->verts, e->proj);
+  switch (skin_form(M, m.Vp)) {
+    case SkinForm::Wide:
+      skin_mfma_kernel<<<dim3(m.Vp / 64, (M + 15) / 16), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am, trans,
+                                                                      e->vposed, e->verts, e->proj);
+      break;
+    case SkinForm::Split:
+      skin_mfma_split_kernel<<<dim3(m.Vp / kSkinVerts, (M + 15) / 16), kSkinThreads, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT,
+                                                                                             e->Am, trans, e->vposed, e->verts, e->proj);
+      break;
+    case SkinForm::Plain:
+      skin_kernel<8><<<dim3(m.Vp / 64, (M + 7) / 8), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am,
+                                                                   trans, e->vposed, e->verts, e->proj);
+      break;
+  }
   LAUNCH_OK("skin_kernel");
   if (joints_out) {   // callers that only need the vertices (smalfit_fit3d_step) skip the joint regression
     joints_kernel<<<dim3(41, M), 128, 0, st>>>(m, e->verts, joints_out);
@@ -645,9 +647,8 @@ static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float
 // `joints_out` / `la`: the joint regression and the per-frame loss terms ride along as extra workgroups of the box and
 // resolve launches (they depend on the skinned vertices only and are needed by the backward pass only)
 static int run_raster_forward(smalfit_engine* e, hipStream_t st, int M, WinMap win, float w_sil,
-                              SilTarget tsil, float* sil_out, float2* gz_unused, float* blk_loss,
+                              SilTarget tsil, float* sil_out, float* blk_loss,
                               float* joints_out = nullptr, const LossArgs* la = nullptr, unsigned long long* floss = nullptr) {
-  (void)gz_unused;
   // e->gz is persistent state: .y carries each pixel's depth threshold into the next evaluation (verified there)
   float2* gz = e->gz;
   const ModelDev& m = e->model->dev;
@@ -702,14 +703,14 @@ static int run_lbs_backward(smalfit_engine* e, hipStream_t st, int M, int nb, in
   LAUNCH_OK("vertex_bwd_kernel");
   {
     const int nPB = need_pose ? mid_pb_ids(M) : 0;   // (up to PBM_TILES x 16 frames) x 32 pose features x column split
-    const int dbx = need_beta ? e->nblk_beta : 0, dby = betas_shared ? 1 : M, dbz = betas_shared ? kBetaGroups : 1;
+    const DbetaGrid db = dbeta_grid(need_beta, m.Vp, betas_shared != 0, M);
     lbs_bwd_mid_kernel<<<mid_grid(M, nPB), 256, 0, st>>>(m, M, nPB, e->dvert, e->vposed, e->dvp, e->dA, e->dpf_part);
     LAUNCH_OK("lbs_bwd_mid_kernel");
-    // the shape-blend adjoint partials ride on the chain launch: dbx * dby * dbz workgroups after its M frame blocks
-    chain_bwd_kernel<<<M + dbx * dby * dbz, 256, 0, st>>>(m, M, e->theta, e->Rm, e->Gm, e->scm, e->Jrest, j_stride, e->dA,
+    // the shape-blend adjoint partials ride on the chain launch: db.blocks() workgroups after its M frame blocks
+    chain_bwd_kernel<<<M + db.blocks(), 256, 0, st>>>(m, M, e->theta, e->Rm, e->Gm, e->scm, e->Jrest, j_stride, e->dA,
                                                    need_pose ? e->dpf_part : nullptr, e->CS, dth_direct, e->dtheta,
                                                    need_ls ? e->dls : nullptr, e->dJrest, need_beta ? e->dbetaJ : nullptr, dRs_out,
-                                                   nb, betas_shared, dbx, dby, dbz, e->dvp, e->dbeta_part);
+                                                   nb, betas_shared, db.bx, db.by, db.bz, e->dvp, e->dbeta_part);
   }
   LAUNCH_OK("chain_bwd_kernel");
   return 0;
@@ -732,34 +733,11 @@ struct EvalFold {
 
 static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const EvalFold& fold) {
   if (!e || !a) return fail("smalfit_fit_eval: null argument");
-  // struct_size first: with a block laid out by another version of smalfit.h no other field can be trusted
-  if (a->struct_size != (unsigned)sizeof(smalfit_fit_args))
-    return fail("smalfit_fit_eval: smalfit_fit_args.struct_size does not match this library (built against another smalfit.h?)");
+  if (refused("smalfit_fit_eval", fit_args_refusal(a, EngineFacts{e->maxM, e->has_pose_prior, e->shape_dim}))) return 1;
   const int M = a->num_frames;
-  if (M <= 0 || M > e->maxM) return fail("smalfit_fit_eval: num_frames exceeds the engine's max_frames");
-  if (a->window <= 0) return fail("smalfit_fit_eval: window must be positive");
-  if (a->frame_offset < 0) return fail("smalfit_fit_eval: frame_offset must be >= 0");
-  if (a->total_frames != 0 && a->total_frames < a->frame_offset + M) return fail("smalfit_fit_eval: total_frames is smaller than frame_offset + num_frames");
   // where these M frames sit in their sequence: per-window normalisers follow the sequence's windows
-  const WinMap win{a->window, a->frame_offset, a->total_frames > 0 ? a->total_frames : a->frame_offset + M};
-  if (!a->betas || !a->global_rotation || !a->joint_rotations || !a->trans || !a->losses)
-    return fail("smalfit_fit_eval: missing parameter / losses pointer");
-  if (a->w_j2d > 0.f && (!a->target_joints || !a->target_visibility)) return fail("smalfit_fit_eval: keypoint targets missing");
-  if (a->w_sil > 0.f && !a->target_sil && !a->target_sil_u8) return fail("smalfit_fit_eval: target_sil missing with w_sil > 0");
-  if (a->w_pose > 0.f && !e->has_pose_prior) return fail("smalfit_fit_eval: pose prior not set");
-  if (a->w_betas > 0.f && e->shape_dim <= 0) return fail("smalfit_fit_eval: shape prior not set");
-  if (a->logscale_mode != 0 && !a->log_beta_scales) return fail("smalfit_fit_eval: log_beta_scales missing");
-  // independent images: every frame its own subject.  Everything that couples frames is refused, not ignored
-  if (a->subject_frames != 0 && a->subject_frames != 1)
-    return fail("smalfit_fit_eval: subject_frames must be 0 (one subject) or 1 (independent images); clips of K > 1 frames per subject in one batch are not implemented");
-  const bool indep = a->subject_frames == 1;
-  if (indep) {
-    if (a->window != 1) return fail("smalfit_fit_eval: subject_frames = 1 needs window = 1 (an image is its own window)");
-    if (a->temporal) return fail("smalfit_fit_eval: subject_frames = 1 needs temporal = 0 (unrelated images have no neighbours)");
-    if (a->logscale_mode == 1) return fail("smalfit_fit_eval: subject_frames = 1 takes logscale_mode 0 or 2 (nothing is shared between images)");
-    if (a->halo_prev || a->halo_next) return fail("smalfit_fit_eval: subject_frames = 1 needs halo_prev = halo_next = NULL");
-    if (a->frame_offset != 0 || a->total_frames != 0) return fail("smalfit_fit_eval: subject_frames = 1 needs frame_offset = total_frames = 0");
-  }
+  const WinMap win{a->window, a->frame_offset, sequence_frames(a)};
+  const bool indep = independent_images(a);
   hipStream_t st = (hipStream_t)stream;
   const ModelDev& m = e->model->dev;
   const float* gmask = a->global_mask ? a->global_mask : e->ones;
@@ -771,27 +749,19 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   const bool sil_on = a->w_sil > 0.f;
   const bool fused_loss = sil_on || a->sil_out;     // the rasteriser runs in this evaluation
   const bool shape_prior = a->w_betas > 0.f;
-  const int D = a->shape_prior_dim > 0 ? a->shape_prior_dim : e->shape_dim;
-  const bool prior_uses_ls = shape_prior && D > 20;
-  if (indep && shape_prior && prior_uses_ls && a->logscale_mode != 2)
-    return fail("smalfit_fit_eval: a 26-dim shape prior of independent images needs per-frame log_beta_scales (logscale_mode 2)");
-  if (!indep && shape_prior && prior_uses_ls && a->logscale_mode != 1)
-    return fail("smalfit_fit_eval: a 26-dim shape prior needs shared log_beta_scales");
+  const bool prior_uses_ls = prior_uses_limb_scales(a, e->shape_dim);
   // one row of loss terms per frame: only an evaluation that assembles writes (and clears the counters behind) them
   const bool rows = a->losses_per_frame != nullptr && fold.assemble;
-  int prior_windows = 0;
+  int nwin = 0;   // windows whose shape-prior term this evaluation owns
   {
     Section sec(e, st, SMALFIT_SEC_LBS_FWD);
     HeadExtras ex;
     ex.grot = a->global_rotation; ex.jrot = a->joint_rotations; ex.gmask = gmask; ex.rmask = rmask;
     ex.pending = fold.pending; ex.prior_slot = fold.prior_slot;
     if (shape_prior) {
-      ex.prior_prec = e->shape_prec; ex.prior_mean = e->shape_mean; ex.prior_D = D; ex.prior_use_ls = prior_uses_ls ? 1 : 0;
-      // the shape prior is evaluated once per window (smal_fitter.py:162-171 inside forward()): this evaluation owns the
-      // windows that START among its frames (a shard in the middle of a window owns none of it)
-      const int w0 = (win.offset + win.window - 1) / win.window, w1 = (win.offset + M + win.window - 1) / win.window;
-      ex.prior_w = a->w_betas * (float)(w1 - w0);
-      prior_windows = w1 - w0;
+      ex.prior_prec = e->shape_prec; ex.prior_mean = e->shape_mean; ex.prior_D = shape_prior_dim(a, e->shape_dim); ex.prior_use_ls = prior_uses_ls ? 1 : 0;
+      nwin = prior_windows(win.window, win.offset, M);
+      ex.prior_w = a->w_betas * (float)nwin;
       if (indep) { ex.prior_w = a->w_betas; ex.prior_per_frame = true; }    // once per image
     }
     // with the rasteriser running, the joint regression and the loss terms ride in its launches (run_raster_forward)
@@ -818,8 +788,7 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   } else {
     SilTarget tsil{nullptr, nullptr};
     if (sil_on) { if (a->target_sil_u8) tsil.b = a->target_sil_u8; else tsil.f = a->target_sil; }
-    if (run_raster_forward(e, st, M, win, a->w_sil, tsil, a->sil_out,
-                           sil_on ? e->gz : nullptr, sil_on ? e->tile_loss : nullptr, e->joints, &la,
+    if (run_raster_forward(e, st, M, win, a->w_sil, tsil, a->sil_out, sil_on ? e->tile_loss : nullptr, e->joints, &la,
                            (rows && sil_on) ? e->frame_qloss : nullptr)) return 1;
   }
   if (sil_on) {
@@ -846,7 +815,7 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   g.M = M; g.S = e->S; g.T = e->nrb; g.win = win; g.nb = nb; g.NBall = m.NBall;
   g.nblk_beta = e->nblk_beta; g.nvt = e->nvt; g.betas_shared = 1; g.ls_shared = a->logscale_mode == 1;
   g.w_sil = a->w_sil;
-  g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = kBetaGroups;
+  g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = beta_groups(!indep);
   g.gb_prior = shape_prior ? e->gb_prior + fold.prior_slot * kPriorSlotB : nullptr;
   g.gls_prior = prior_uses_ls ? e->gls_prior + fold.prior_slot * kPriorSlotLs : nullptr;
   g.dls = e->dls; g.dtheta = e->dtheta; g.gmask = gmask; g.rmask = rmask;
@@ -862,9 +831,9 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   g.lpart = e->lpart; g.qpart = e->qpart; g.counter = e->asm_counter;
   AssembleExt gx;
   std::memset(&gx, 0, sizeof(gx));
-  gx.losses_pf = rows ? a->losses_per_frame : nullptr; gx.frame_qloss = e->frame_qloss; gx.prior_windows = prior_windows;
+  gx.losses_pf = rows ? a->losses_per_frame : nullptr; gx.frame_qloss = e->frame_qloss; gx.prior_windows = nwin;
   if (indep) {
-    g.betas_shared = 0; g.ls_shared = 0; g.ngrp_beta = 1;
+    g.betas_shared = 0; g.ls_shared = 0;
     g.gb_prior = nullptr; g.gls_prior = nullptr; g.loss_betas = nullptr;      // the shared-shape slots stay unused: one row per image instead
     if (shape_prior) {
       gx.gb_prior_pf = e->gb_prior_pf; gx.gb_stride = kPriorSlotB; gx.prior_loss_pf = e->loss_betas_pf;
@@ -1050,15 +1019,21 @@ int smalfit_rodrigues(void* stream, int count, const float* theta, float* R) {
   return 0;
 }
 
+namespace smalfit {
+// the caller's parent table as a kernel argument, checked
+static int pack_parents(const int* parents, Parents35& par, const char* who) {
+  if (!parents_ordered(parents, 35)) return refused(who, "parents must satisfy 0 <= parents[i] < i");
+  par.p[0] = -1;
+  for (int i = 1; i < 35; ++i) par.p[i] = parents[i];
+  return 0;
+}
+}  // namespace smalfit
+
 int smalfit_global_rigid_transformation(void* stream, int count, const float* Rs, const float* Js, const int* parents,
                                         const float* logscale, float* new_J, float* A) {
   if (count <= 0 || !Rs || !Js || !parents || !new_J || !A) return fail("smalfit_global_rigid_transformation: bad argument");
   Parents35 par;
-  par.p[0] = -1;
-  for (int i = 1; i < 35; ++i) {
-    if (!(parents[i] >= 0 && parents[i] < i)) return fail("smalfit_global_rigid_transformation: parents must satisfy 0 <= parents[i] < i");
-    par.p[i] = parents[i];
-  }
+  if (pack_parents(parents, par, "smalfit_global_rigid_transformation")) return 1;
   global_rigid_kernel<<<(count + 63) / 64, 64, 0, (hipStream_t)stream>>>(count, Rs, Js, par, logscale, new_J, A);
   LAUNCH_OK("global_rigid_kernel");
   return 0;
@@ -1070,11 +1045,7 @@ int smalfit_global_rigid_transformation_backward(void* stream, int count, const 
   if (count <= 0 || !Rs || !Js || !parents || !d_new_J || !d_A || !scratch || !dRs || !dJs)
     return fail("smalfit_global_rigid_transformation_backward: bad argument");
   Parents35 par;
-  par.p[0] = -1;
-  for (int i = 1; i < 35; ++i) {
-    if (!(parents[i] >= 0 && parents[i] < i)) return fail("smalfit_global_rigid_transformation_backward: parents must satisfy 0 <= parents[i] < i");
-    par.p[i] = parents[i];
-  }
+  if (pack_parents(parents, par, "smalfit_global_rigid_transformation_backward")) return 1;
   global_rigid_bwd_kernel<<<(count + 63) / 64, 64, 0, (hipStream_t)stream>>>(count, Rs, Js, par, logscale, d_new_J, d_A, scratch, dRs, dJs,
                                                                             logscale ? dlogscale : nullptr);
   LAUNCH_OK("global_rigid_bwd_kernel");
@@ -1100,7 +1071,7 @@ int smalfit_render_forward(smalfit_engine* e, void* stream, int M, const float* 
   if (sil) {
     project_verts_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
     LAUNCH_OK("project_verts_kernel");
-    if (run_raster_forward(e, st, M, WinMap{1, 0, M}, 0.f, SilTarget{nullptr, nullptr}, sil, nullptr, nullptr)) return 1;
+    if (run_raster_forward(e, st, M, WinMap{1, 0, M}, 0.f, SilTarget{nullptr, nullptr}, sil, nullptr)) return 1;
   }
   if (points && proj_points && P > 0) {
     project_points_kernel<<<(M * P + 255) / 256, 256, 0, st>>>(M * P, e->S, points, proj_points);
@@ -1108,30 +1079,6 @@ int smalfit_render_forward(smalfit_engine* e, void* stream, int M, const float* 
   }
   return 0;
 }
-
-}  // extern "C"
-
-namespace smalfit {
-// d(sil)/d(world verts): gather incident-face adjoints, camera adjoint, write interleaved (M,V,3)
-__global__ void raster_vertex_grad_kernel(ModelDev m, const float* __restrict__ proj, const float* __restrict__ dface,
-                                          float* __restrict__ dverts) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
-  if (v >= m.V) return;
-  float gxn = 0.f, gyn = 0.f;
-  const float* df = dface + (size_t)n * m.F * 6;
-  for (int i = m.vf_off[v]; i < m.vf_off[v + 1]; ++i) {
-    gxn += df[m.vf_idx[i] * 2];
-    gyn += df[m.vf_idx[i] * 2 + 1];
-  }
-  const float* pv = proj + (size_t)n * 3 * m.Vp;
-  float g[3];
-  world_to_ndc_bwd(pv[v], pv[m.Vp + v], pv[2 * m.Vp + v], gxn, gyn, g[0], g[1], g[2]);
-  float* o = dverts + ((size_t)n * m.V + v) * 3;
-  o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
-}
-}  // namespace smalfit
-
-extern "C" {
 
 int smalfit_render_color(smalfit_engine* e, void* stream, int M, const float* verts, const float* rgb, float* image) {
   if (!e || !verts || !rgb || !image) return fail("smalfit_render_color: null argument");
@@ -1162,7 +1109,7 @@ int smalfit_render_backward(smalfit_engine* e, void* stream, int M, const float*
   const ModelDev& m = e->model->dev;
   project_verts_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
   // recompute the forward (stateless adjoint): depth thresholds land in gz.y, then seed gz.x from dsil
-  if (run_raster_forward(e, st, M, WinMap{1, 0, M}, 0.f, SilTarget{nullptr, nullptr}, e->silbuf, e->gz, nullptr)) return 1;
+  if (run_raster_forward(e, st, M, WinMap{1, 0, M}, 0.f, SilTarget{nullptr, nullptr}, e->silbuf, nullptr)) return 1;
   const size_t total = (size_t)M * e->S * e->S;
   gpix_from_dsil_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(total, sil, dsil, e->gz);
   launch_raster_bwd(e, st, M);
@@ -1213,20 +1160,9 @@ int smalfit_temporal(smalfit_engine* e, void* stream, int N, float w_temp, const
 
 namespace smalfit {
 // the ranges of `o` packed for the segment kernels, checked: every launch of them (eager, graph node) goes through here
-static int pack_adam_segments(const smalfit_adam_args* o, AdamSegments& sg) {
-  if (!o->param || !o->grad || !o->exp_avg || !o->exp_avg_sq) return fail("smalfit adam: null buffer");
-  if (o->num_segments < 0 || o->num_segments > 4) return fail("smalfit adam: at most 4 segments");
-  std::memset(&sg, 0, sizeof(sg));
-  sg.nseg = o->num_segments;
-  int total = 0;
-  for (int k = 0; k < sg.nseg; ++k) {
-    if (o->seg_begin[k] < 0 || o->seg_end[k] < o->seg_begin[k]) return fail("smalfit adam: bad segment");
-    sg.beg[k] = o->seg_begin[k];
-    sg.off[k] = total;
-    total += o->seg_end[k] - o->seg_begin[k];
-  }
-  for (int k = sg.nseg; k <= 4; ++k) sg.off[k] = total;
-  return 0;
+static int packed_adam_segments(const smalfit_adam_args* o, AdamSegments& sg) {
+  const char* why = pack_adam_segments(o, sg);
+  return why ? fail(why) : 0;
 }
 
 // optimizer.step() with the hyperparameters of `o` on the packed ranges at the 1-based step t; fresh: the moments are
@@ -1245,7 +1181,7 @@ static int launch_adam_segments(hipStream_t st, const AdamSegments& sg, const sm
 // the next step of the optimiser `o` describes: t = o->step + 1, and the first step of a stage does not read the moments
 static int launch_adam_next_step(hipStream_t st, const smalfit_adam_args* o) {
   AdamSegments sg;
-  if (pack_adam_segments(o, sg)) return 1;
+  if (packed_adam_segments(o, sg)) return 1;
   return launch_adam_segments(st, sg, o, o->step + 1, o->step == 0);
 }
 }  // namespace smalfit
@@ -1264,44 +1200,6 @@ int smalfit_engine_set_graph(smalfit_engine* e, int enable) {
 }
 
 namespace smalfit {
-// Can the optimiser step of `o` be folded into the next evaluation's head launch?  Only when the trainable ranges are exactly a
-// set of whole parameter tensors of `a` (the ranges of adjacent tensors may be merged) whose gradients the evaluation writes to
-// the matching ranges of o->grad: then every trainable float has one known reader (PendingStep).  -> which tensors, and where.
-struct FoldPlan {
-  bool train[5];      // betas, log_beta_scales, global_rotation, joint_rotations, trans
-  int off[5];         // their offsets in the flat buffers
-};
-static bool plan_fold(const smalfit_fit_args* a, const smalfit_adam_args* o, const AdamSegments& sg, FoldPlan& plan) {
-  const int M = a->num_frames;
-  if (M <= 0 || !a->betas || !a->global_rotation || !a->joint_rotations || !a->trans) return false;
-  if (a->subject_frames != 0) return false;      // independent images keep the plain chain (per-image betas are not folded yet)
-  const float* ptr[5] = {a->betas, a->logscale_mode ? a->log_beta_scales : nullptr, a->global_rotation, a->joint_rotations, a->trans};
-  const float* gptr[5] = {a->g_betas, a->g_log_beta_scales, a->g_global_rotation, a->g_joint_rotations, a->g_trans};
-  const long long cnt[5] = {20, a->logscale_mode == 1 ? 6 : (long long)M * 6, (long long)M * 3, (long long)M * 102, (long long)M * 3};
-  long long lo[5], covered = 0;
-  for (int k = 0; k < 5; ++k) {
-    plan.train[k] = false; plan.off[k] = 0; lo[k] = 0;
-    if (!ptr[k]) continue;
-    const long long bytes = (long long)((const char*)ptr[k] - (const char*)o->param);
-    if (bytes % 4) return false;
-    lo[k] = bytes / 4;
-    bool inside = false, touches = false;
-    for (int q = 0; q < sg.nseg; ++q) {
-      const long long b = sg.beg[q], en = b + (sg.off[q + 1] - sg.off[q]);
-      if (b <= lo[k] && lo[k] + cnt[k] <= en) inside = true;
-      else if (lo[k] < en && b < lo[k] + cnt[k]) touches = true;
-    }
-    if (touches) return false;                                     // a range cuts through the tensor
-    if (!inside) continue;
-    if (gptr[k] != o->grad + lo[k]) return false;                  // its gradient is not written where Adam reads it
-    for (int j = 0; j < k; ++j)
-      if (plan.train[j] && lo[j] < lo[k] + cnt[k] && lo[k] < lo[j] + cnt[j]) return false;   // two tensors share floats
-    plan.train[k] = true; plan.off[k] = (int)lo[k];
-    covered += cnt[k];
-  }
-  return covered > 0 && covered == sg.off[sg.nseg];               // nothing else in the ranges
-}
-
 static int launch_adam_graph_node(smalfit_engine* e, hipStream_t st, const AdamSegments& sg, const smalfit_adam_args* o) {
   const int total = sg.off[sg.nseg];
   if (total == 0) return 0;
@@ -1310,105 +1208,126 @@ static int launch_adam_graph_node(smalfit_engine* e, hipStream_t st, const AdamS
   LAUNCH_OK("adam_segments_graph_kernel");
   return 0;
 }
+
+// RunLoop::Graph: one iteration (tick, the evaluation's kernels, Adam) captured once per (arguments, stream) and replayed
+static int run_graph_replay(smalfit_engine* e, hipStream_t st, const smalfit_fit_args* a, const smalfit_adam_args* o,
+                            const AdamSegments& sg, int iterations) {
+  smalfit_adam_args okey = *o;
+  okey.step = 0;
+  // (the engine's configuration is baked into the captured launches too: prior dimensions, limit switch, probes)
+  const unsigned cfg[2] = {e->config_epoch, (unsigned)g_dbg};
+  std::vector<unsigned char> key(sizeof(*a) + sizeof(okey) + sizeof(st) + sizeof(cfg));
+  std::memcpy(key.data(), a, sizeof(*a));
+  std::memcpy(key.data() + sizeof(*a), &okey, sizeof(okey));
+  std::memcpy(key.data() + sizeof(*a) + sizeof(okey), &st, sizeof(st));
+  std::memcpy(key.data() + sizeof(*a) + sizeof(okey) + sizeof(st), cfg, sizeof(cfg));
+  if (!e->graph_exec || key != e->graph_key) {
+    if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }
+    hipGraph_t graph = nullptr;
+    HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    tick_kernel<<<1, 1, 0, st>>>(e->step_counter);
+    int rc = smalfit_fit_eval(e, st, a);
+    if (!rc) rc = launch_adam_graph_node(e, st, sg, o);
+    const hipError_t ce = hipStreamEndCapture(st, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return 1; }
+    if (ce != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+    const hipError_t ie = hipGraphInstantiate(&e->graph_exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ie != hipSuccess) { e->graph_exec = nullptr; return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
+    e->graph_key = key;
+  }
+  set_counter_kernel<<<1, 1, 0, st>>>(e->step_counter, o->step);
+  LAUNCH_OK("set_counter_kernel");
+  for (int it = 0; it < iterations; ++it) HIP_OK(hipGraphLaunch(e->graph_exec, st));
+  return 0;
+}
+
+// the optimiser step iteration `it` leaves to the head launch of iteration it + 1: the assembly `g` of its gradients, Adam at
+// step o->step + it + 1.  Per-frame tensors are stepped in place; the shared ones follow shared_route(it, iterations)
+static void pend_step(smalfit_engine* e, const smalfit_fit_args* a, const smalfit_adam_args* o, const FoldPlan& plan,
+                      const AssembleArgs& g, int it, int iterations, PendingStep& ps) {
+  std::memset(&ps, 0, sizeof(ps));
+  ps.g = g;
+  const int t = o->step + it + 1;
+  adam_bias_terms(o->lr, o->beta1, o->beta2, t, ps.step_size, ps.bc2_sqrt);
+  ps.b1 = o->beta1; ps.b2 = o->beta2; ps.eps = o->eps; ps.fresh = t == 1 ? 1 : 0;
+  PendingTensor* pt[5] = {&ps.betas, &ps.ls, &ps.grot, &ps.jrot, &ps.trans};
+  const float* tensor[5] = {a->betas, a->logscale_mode ? a->log_beta_scales : nullptr, a->global_rotation, a->joint_rotations, a->trans};
+  const SharedRoute route = shared_route(it, iterations);
+  for (int k = 0; k < 5; ++k) {
+    PendingTensor& T = *pt[k];
+    if (!plan.train[k]) { T.p_in = T.m_in = T.v_in = tensor[k]; continue; }   // read as it is (unconditional loads: any readable words as moments)
+    const int off = plan.off[k];
+    T.train = 1;
+    T.p_in = T.p = o->param + off; T.m_in = T.m = o->exp_avg + off; T.v_in = T.v = o->exp_avg_sq + off; T.g = o->grad + off;
+    if (!tensor_is_shared(k, a->logscale_mode)) continue;
+    const int at = k == 0 ? kSharedSlotBetas : kSharedSlotScales;
+    if (route.read != kCaller) {
+      const float* src = e->shstate + route.read * kSharedSlotFloats + at;
+      T.p_in = src; T.m_in = src + 32; T.v_in = src + 64;
+    }
+    if (route.write != kCaller) {
+      float* dst = e->shstate + route.write * kSharedSlotFloats + at;
+      T.p = dst; T.m = dst + 32; T.v = dst + 64;
+    }
+  }
+}
+
+// RunLoop::Folded.  Gradient assembly and Adam of every iteration but the last ride in the NEXT iteration's head launch -- its
+// frame blocks are the first and only readers of the stepped per-frame parameters, so no fence, counter or tail is needed --
+// and the loss terms of those iterations, which no caller can see, are not summed at all.  The last iteration closes with the
+// two kernels as ever, so the caller finds parameters, moments, gradients and losses exactly as from the plain chain.
+static int run_folded_loop(smalfit_engine* e, hipStream_t st, const smalfit_fit_args* a, const smalfit_adam_args* o,
+                           const AdamSegments& sg, const FoldPlan& plan, int iterations) {
+  PendingStep ps;
+  for (int it = 0; it < iterations; ++it) {
+    const bool last = it == iterations - 1;
+    EvalFold fold;
+    AssembleArgs g;
+    fold.pending = it ? &ps : nullptr; fold.prior_slot = prior_slot(it); fold.assemble = last; fold.args_out = &g;
+    if (fit_eval_impl(e, st, a, fold)) return 1;
+    if (!last) pend_step(e, a, o, plan, g, it, iterations, ps);
+  }
+  const bool betas_home = plan.train[0], scales_home = plan.train[1] && tensor_is_shared(1, a->logscale_mode);
+  const int slot = restore_slot(iterations, betas_home || scales_home);
+  if (slot != kCaller) {
+    shared_state_restore_kernel<<<1, 64, 0, st>>>(e->shstate + slot * kSharedSlotFloats, o->param, o->exp_avg, o->exp_avg_sq,
+                                                 betas_home ? 20 : 0, plan.off[0], scales_home ? 6 : 0, plan.off[1]);
+    LAUNCH_OK("shared_state_restore_kernel");
+  }
+  const int t = o->step + iterations;
+  return launch_adam_segments(st, sg, o, t, t == 1);
+}
+
+// RunLoop::Plain
+static int run_plain_chain(smalfit_engine* e, hipStream_t st, const smalfit_fit_args* a, const smalfit_adam_args* o,
+                           const AdamSegments& sg, int iterations) {
+  for (int it = 0; it < iterations; ++it) {
+    const int t = o->step + it + 1;
+    if (smalfit_fit_eval(e, st, a)) return 1;
+    if (launch_adam_segments(st, sg, o, t, t == 1)) return 1;
+  }
+  return 0;
+}
 }  // namespace smalfit
 
 int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const smalfit_adam_args* o, int iterations) {
   if (!e || !a || !o) return fail("smalfit_fit_run: null argument");
   if (iterations <= 0) return fail("smalfit_fit_run: iterations must be positive");
   if (o->step < 0) return fail("smalfit_fit_run: step must be >= 0");
-  // struct_size before any other field of the block is read (subject_frames sits at its tail: a block of an older header ends before it)
-  if (a->struct_size != (unsigned)sizeof(smalfit_fit_args))
-    return fail("smalfit_fit_run: smalfit_fit_args.struct_size does not match this library (built against another smalfit.h?)");
+  if (refused("smalfit_fit_run", fit_args_size_refusal(a))) return 1;
   AdamSegments sg;
-  if (pack_adam_segments(o, sg)) return 1;
+  if (packed_adam_segments(o, sg)) return 1;
   hipStream_t st = (hipStream_t)stream;
   if (e->use_graph && a->subject_frames != 0)
     return fail("smalfit_fit_run: subject_frames != 0 is not supported by the graph replay (smalfit_engine_set_graph)");
-  if (e->use_graph && !e->prof_on && iterations >= 2 && st != nullptr) {
-    // one iteration (tick, the evaluation's kernels, Adam) captured once per (arguments, stream) and replayed
-    smalfit_adam_args okey = *o;
-    okey.step = 0;
-    // (the engine's configuration is baked into the captured launches too: prior dimensions, limit switch, probes)
-    const unsigned cfg[2] = {e->config_epoch, (unsigned)g_dbg};
-    std::vector<unsigned char> key(sizeof(*a) + sizeof(okey) + sizeof(st) + sizeof(cfg));
-    std::memcpy(key.data(), a, sizeof(*a));
-    std::memcpy(key.data() + sizeof(*a), &okey, sizeof(okey));
-    std::memcpy(key.data() + sizeof(*a) + sizeof(okey), &st, sizeof(st));
-    std::memcpy(key.data() + sizeof(*a) + sizeof(okey) + sizeof(st), cfg, sizeof(cfg));
-    if (!e->graph_exec || key != e->graph_key) {
-      if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }
-      hipGraph_t graph = nullptr;
-      HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      tick_kernel<<<1, 1, 0, st>>>(e->step_counter);
-      int rc = smalfit_fit_eval(e, stream, a);
-      if (!rc) rc = launch_adam_graph_node(e, st, sg, o);
-      const hipError_t ce = hipStreamEndCapture(st, &graph);
-      if (rc) { if (graph) (void)hipGraphDestroy(graph); return 1; }
-      if (ce != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-      const hipError_t ie = hipGraphInstantiate(&e->graph_exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (ie != hipSuccess) { e->graph_exec = nullptr; return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
-      e->graph_key = key;
-    }
-    set_counter_kernel<<<1, 1, 0, st>>>(e->step_counter, o->step);
-    LAUNCH_OK("set_counter_kernel");
-    for (int it = 0; it < iterations; ++it) HIP_OK(hipGraphLaunch(e->graph_exec, st));
-    return 0;
+  const FoldPlan plan = plan_fold(a, o, sg);
+  switch (run_loop(e->use_graph, e->prof_on, iterations, st != nullptr, plan.accepted())) {
+    case RunLoop::Graph: return run_graph_replay(e, st, a, o, sg, iterations);
+    case RunLoop::Folded: return run_folded_loop(e, st, a, o, sg, plan, iterations);
+    case RunLoop::Plain: break;
   }
-  // Gradient assembly and Adam of every iteration but the last ride in the NEXT iteration's head launch -- its frame blocks are
-  // the first and only readers of the stepped per-frame parameters, so no fence, counter or tail is needed -- and the loss
-  // terms of those iterations, which no caller can see, are not summed at all.  The last iteration closes with the two
-  // kernels as ever, so the caller finds parameters, moments, gradients and losses exactly as from the plain chain below.
-  FoldPlan plan;
-  if (iterations >= 2 && !e->prof_on && plan_fold(a, o, sg, plan)) {
-    const bool ls_shared = a->logscale_mode == 1, shared_trained = plan.train[0] || (plan.train[1] && ls_shared);
-    PendingStep ps;
-    for (int it = 0; it < iterations; ++it) {
-      const bool last = it == iterations - 1;
-      EvalFold fold;
-      AssembleArgs g;
-      fold.pending = it ? &ps : nullptr; fold.prior_slot = it & 1; fold.assemble = last; fold.args_out = &g;
-      if (fit_eval_impl(e, stream, a, fold)) return 1;
-      if (last) break;
-      // the step this evaluation leaves pending.  Per-frame tensors are stepped in place; the shared ones travel through the
-      // two slots of e->shstate (read from one, stored to the other: the launch's other blocks are still reading), starting
-      // from the caller's buffers and, from the third iteration on, ending there: the last pending step reads a slot
-      std::memset(&ps, 0, sizeof(ps));
-      ps.g = g;
-      const int t = o->step + it + 1;
-      adam_bias_terms(o->lr, o->beta1, o->beta2, t, ps.step_size, ps.bc2_sqrt);
-      ps.b1 = o->beta1; ps.b2 = o->beta2; ps.eps = o->eps; ps.fresh = t == 1 ? 1 : 0;
-      PendingTensor* pt[5] = {&ps.betas, &ps.ls, &ps.grot, &ps.jrot, &ps.trans};
-      const float* tensor[5] = {a->betas, a->logscale_mode ? a->log_beta_scales : nullptr, a->global_rotation, a->joint_rotations, a->trans};
-      for (int k = 0; k < 5; ++k) {
-        PendingTensor& T = *pt[k];
-        if (!plan.train[k]) { T.p_in = T.m_in = T.v_in = tensor[k]; continue; }   // read as it is (unconditional loads: any readable words as moments)
-        const int off = plan.off[k];
-        T.train = 1;
-        T.p_in = T.p = o->param + off; T.m_in = T.m = o->exp_avg + off; T.v_in = T.v = o->exp_avg_sq + off; T.g = o->grad + off;
-        if (k == 0 || (k == 1 && ls_shared)) {
-          const int at = k == 0 ? 0 : 20;
-          float* dst = e->shstate + ((it + 1) & 1) * 96 + at;
-          const float* src = e->shstate + (it & 1) * 96 + at;
-          if (it) { T.p_in = src; T.m_in = src + 32; T.v_in = src + 64; }
-          if (!(it && it + 2 == iterations)) { T.p = dst; T.m = dst + 32; T.v = dst + 64; }
-        }
-      }
-    }
-    if (shared_trained && iterations == 2) {   // the only pending step read the caller's buffers, so it could not store there
-      shared_state_restore_kernel<<<1, 64, 0, st>>>(e->shstate + ((iterations - 1) & 1) * 96, o->param, o->exp_avg, o->exp_avg_sq,
-                                                   plan.train[0] ? 20 : 0, plan.off[0], (plan.train[1] && ls_shared) ? 6 : 0, plan.off[1]);
-      LAUNCH_OK("shared_state_restore_kernel");
-    }
-    const int t = o->step + iterations;
-    return launch_adam_segments(st, sg, o, t, t == 1);
-  }
-  for (int it = 0; it < iterations; ++it) {
-    const int t = o->step + it + 1;
-    if (smalfit_fit_eval(e, stream, a)) return 1;
-    if (launch_adam_segments(st, sg, o, t, t == 1)) return 1;
-  }
-  return 0;
+  return run_plain_chain(e, st, a, o, sg, iterations);
 }
 
 int smalfit_shard_record(void* stream, int num_shared, const float* shared_grad, int num_frames, const float* global_rotation,
@@ -1426,7 +1345,7 @@ int smalfit_shard_local_step(smalfit_engine* e, void* stream, const smalfit_fit_
                              const float* shared_grad, float* record) {
   if (!e || !a || !o || !record || !shared_grad) return fail("smalfit_shard_local_step: null argument");
   if (o->step < 0) return fail("smalfit_shard_local_step: step must be >= 0");
-  if (a->struct_size == (unsigned)sizeof(smalfit_fit_args) && a->subject_frames != 0)
+  if (!fit_args_size_refusal(a) && a->subject_frames != 0)   // (a block of another header is refused by the evaluation below)
     return fail("smalfit_shard_local_step: subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)");
   if (smalfit_fit_eval(e, stream, a)) return 1;
   if (launch_adam_next_step((hipStream_t)stream, o)) return 1;
@@ -1468,7 +1387,7 @@ int smalfit_shard_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a
   if (sh->num_shared <= 0 || sh->num_trainable_shared < 0 || sh->num_trainable_shared > sh->num_shared) return fail("smalfit_shard_run: bad num_shared / num_trainable_shared");
   if (!sh->shared_grad || !sh->record || !sh->gathered || !sh->allgather) return fail("smalfit_shard_run: missing buffer / collective");
   if (ol->step < 0 || os->step != ol->step) return fail("smalfit_shard_run: adam_local and adam_shared must carry the same step >= 0");
-  if (a->struct_size == (unsigned)sizeof(smalfit_fit_args) && a->subject_frames != 0)
+  if (!fit_args_size_refusal(a) && a->subject_frames != 0)
     return fail("smalfit_shard_run: subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)");
   const int stride = sh->num_shared + 216;
   for (int it = 0; it < iterations; ++it) {
@@ -1493,7 +1412,7 @@ int smalfit_adam_step(void* stream, int count, float* param, const float* grad, 
   o.num_segments = 1; o.seg_begin[0] = 0; o.seg_end[0] = count;
   o.lr = lr; o.beta1 = beta1; o.beta2 = beta2; o.eps = eps;
   AdamSegments sg;
-  if (pack_adam_segments(&o, sg)) return 1;
+  if (packed_adam_segments(&o, sg)) return 1;
   return launch_adam_segments((hipStream_t)stream, sg, &o, t, false);
 }
 

@@ -2,6 +2,8 @@
 // kernel sequencing, C-ABI.  Included at the end of smalfit_kernels.hip after smalfit_launch.inc.
 #include "mesh3d_topology.h"
 
+static_assert(kMeshQueries == kChamQueries && kMeshThreads == kMeshBlock, "smalfit_plan.h sizes the grids of the mesh3d kernels");
+
 struct smalfit_mesh_objective {
   Mesh3dTables t{};
   void* tables = nullptr;     // one allocation behind t.*
@@ -27,9 +29,9 @@ static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num
                               const float* trans, const float* deform_verts, const float* points, int num_points,
                               const float* weights, float* verts_out, float* losses, float* dverts, float* dtrans,
                               const float* lbs_planar = nullptr, int Vp = 0, float* dverts_planar = nullptr) {
-  const float wc = std::max(weights[0], 0.f);
+  const float wc = mesh_weight(weights[0]);
   Mesh3dArgs a{};
-  a.N = num_meshes; a.V = m->t.V; a.S = wc > 0.f ? num_points : 1;
+  a.N = num_meshes; a.V = m->t.V; a.S = mesh_points(wc, num_points);
   a.t = m->t;
   a.lbs_verts = lbs_verts; a.lbs_planar = lbs_planar; a.Vp = Vp; a.dverts_planar = dverts_planar;
   a.trans = trans; a.deform = deform_verts;
@@ -37,11 +39,11 @@ static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num
   a.points = points; a.nn_idx = m->nn_idx;
   a.gcham = m->gcham; a.gedge = m->gedge; a.lap_unit = m->lap_unit; a.gpair = m->gpair;
   a.dverts = dverts; a.dtrans = dtrans; a.losses = losses;
-  a.w_chamfer = wc; a.w_edge = std::max(weights[1], 0.f); a.w_normal = std::max(weights[2], 0.f);
-  a.w_laplacian = std::max(weights[3], 0.f);
+  a.w_chamfer = wc; a.w_edge = mesh_weight(weights[1]); a.w_normal = mesh_weight(weights[2]);
+  a.w_laplacian = mesh_weight(weights[3]);
   a.part_cx = m->part_cx; a.part_cy = m->part_cy; a.part_edge = m->part_edge; a.part_lap = m->part_lap;
   a.part_normal = m->part_normal; a.part_dtr = m->part_dtr;
-  a.bx = (a.S + kChamQueries - 1) / kChamQueries; a.by = m->by; a.bv = m->bv; a.bp = m->bp;
+  a.bx = mesh_query_blocks(a.S); a.by = m->by; a.bv = m->bv; a.bp = m->bp;
   const size_t total = (size_t)a.N * a.V * 3;
   mesh3d_compose_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(a);
   LAUNCH_OK("mesh3d_compose_kernel");
@@ -98,10 +100,8 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   m->t.inc_off = (const int*)(base + o_io); m->t.inc = (const int*)(base + o_in);
   m->max_meshes = max_meshes; m->max_points = max_points;
   const int N = max_meshes, V = h.V, P = std::max(h.P, 1);
-  m->bx = (max_points + kChamQueries - 1) / kChamQueries;
-  m->by = (V + kChamQueries - 1) / kChamQueries;
-  m->bv = (V + kMeshBlock - 1) / kMeshBlock;
-  m->bp = (h.P + kMeshBlock - 1) / kMeshBlock;
+  const MeshGrids grids = mesh_grids(max_points, V, h.P);   // (bx: the capacity; an evaluation's own follows its num_points)
+  m->bx = grids.bx; m->by = grids.by; m->bv = grids.bv; m->bp = grids.bp;
   size_t bytes = 0;
   auto carve = [&](size_t n) { const size_t o = align_up(bytes, 256); bytes = o + n; return o; };
   const size_t nv3 = (size_t)N * V * 3 * sizeof(float);

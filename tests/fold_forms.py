@@ -1,16 +1,18 @@
 """What smalfit_fit_run decides on the host before it launches anything -- a restatement, so that the GPU tests of the folded
-optimiser step (tests/test_gpu_fold_step.py) can name the cases that reach each branch and say which path a case must take,
-and tests/test_fold_forms_cpu.py can check both that the case lists reach every branch and that the restatement still matches
-the host code.  Nothing here needs a GPU.
+optimiser step (tests/test_gpu_fold_step.py) can name the cases that reach each branch and say which path a case must take
+at collection time, without a compiler, and tests/test_fold_forms_cpu.py can check both that the case lists reach every branch
+and that the restatement answers like the host's own functions (smalify_amd/csrc/smalfit_plan.h, compiled for the host by g++:
+tests/host_plan_shim.cpp, tests/host_plan.py).  Nothing here needs a GPU.
 
-  smalfit_launch.inc: smalfit_fit_run
+  smalfit_plan.h: run_loop (smalfit_fit_run dispatches on it)
       graph switch on, not profiled, iterations >= 2, a stream of the caller's   -> one captured iteration, replayed ("graph")
       iterations >= 2, not profiled, plan_fold accepts                           -> the folded loop ("folded"): iteration it's
                                                                                     gradient assembly + Adam ride in the head launch
                                                                                     of iteration it + 1 (lbs_head_step_kernel)
       otherwise                                                                  -> evaluation, Adam, evaluation, Adam ("plain")
-  smalfit_launch.inc: plan_fold -- the trainable ranges must be exactly a set of whole parameter tensors whose gradients the
-      evaluation writes to the matching ranges of adam.grad
+  smalfit_plan.h: plan_fold -- the trainable ranges must be exactly a set of whole parameter tensors whose gradients the
+      evaluation writes to the matching ranges of adam.grad; FoldRefusal names the reasons below in the same order
+  smalfit_plan.h: shared_route, restore_slot, prior_slot, prior_windows -- where the shared parameters travel
   kernels_lbs_forward.inc: asm_beta_* / asm_ls_* -- the sums over frames behind the shared gradients, in slices and batches
 """
 from __future__ import annotations

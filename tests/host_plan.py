@@ -1,0 +1,152 @@
+"""The host's launch decisions (smalify_amd/csrc/smalfit_plan.h) as Python calls: tests/host_plan_shim.cpp built by g++ the way
+tests/test_host_math.py builds its shim, loaded through ctypes, each function returning what the restatements of
+tests/fold_forms.py, lbs_forms.py and mesh3d_forms.py return, so that a test compares the two with `==`.  The CPU tests call
+load() from a module fixture; nothing here needs a GPU, and nothing the GPU tests import needs this file."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+
+from smalify_amd import _lib
+from tests import fold_forms as ff
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "host_plan_shim.cpp")
+SO = os.path.join(HERE, "_build", "libhost_plan_shim.so")
+DEPS = (SRC, os.path.join(HERE, "..", "smalify_amd", "csrc", "smalfit_plan.h"), os.path.join(HERE, "..", "include", "smalfit.h"))
+
+LOOPS = ("graph", "folded", "plain")                                  # RunLoop
+SKIN_FORMS = ("plain", "split", "wide")                               # SkinForm
+REASONS = (None, "cut", "gradient", "alias", "nothing", "extra")      # FoldRefusal
+HEAD_PRIORS = {"none": 0, "shared": 1, "per_frame": 2}                # HeadPrior
+
+
+class Plan:
+    def __init__(self, lib):
+        self.lib = lib
+        for name in ("hp_fit_args_refusal", "hp_fit_args_size_refusal", "hp_pack_adam_segments"):
+            getattr(lib, name).restype = C.c_char_p
+        lib.hp_mesh_weight.restype = C.c_float
+        lib.hp_mesh_weight.argtypes = [C.c_float]
+        lib.hp_mesh_points.argtypes = [C.c_float, C.c_int]
+        out = (C.c_int * 8)()
+        lib.hp_constants(out)
+        (self.BETA_GROUPS, self.MAX_IMAGE_SIZE, self.MESH_QUERIES, self.MESH_THREADS, self.HEAD_PRIOR_FRAMES, self.CALLER,
+         self.SHARED_SLOT_FLOATS, self.SIZEOF_FIT_ARGS) = list(out)
+
+    # ---- smalfit_fit_run ----
+    def path(self, iterations, graph, profiled, default_stream, accepted):
+        return LOOPS[self.lib.hp_run_loop(int(graph), int(profiled), iterations, int(not default_stream), int(accepted))]
+
+    def plan_fold(self, M, logscale_mode, offsets, ranges, grad_at_offset, subject_frames=0):
+        """fold_forms.plan_fold's arguments and result; a tensor missing from `offsets` is a null pointer"""
+        off = (C.c_longlong * 5)(*[offsets.get(k, 0) for k in ff.TENSORS])
+        present = (C.c_int * 5)(*[int(k in offsets) for k in ff.TENSORS])
+        gao = (C.c_int * 5)(*[int(bool(grad_at_offset.get(k, False))) for k in ff.TENSORS])
+        beg = (C.c_int * 4)(*[b for b, _ in ranges])
+        end = (C.c_int * 4)(*[e for _, e in ranges])
+        train, at = (C.c_int * 5)(), (C.c_int * 5)()
+        why = self.lib.hp_plan_fold(M, logscale_mode, subject_frames, off, present, gao, len(ranges), beg, end, train, at)
+        assert why >= 0, "the ranges themselves were refused"
+        trained = {k: bool(train[i]) for i, k in enumerate(ff.TENSORS)}
+        assert all(at[i] == offsets[k] for i, k in enumerate(ff.TENSORS) if trained[k])
+        return why == 0, trained, REASONS[why]
+
+    def _place(self, slot):
+        return "caller" if slot == self.CALLER else slot
+
+    def shared_travel(self, iterations):
+        out, rw = [], (C.c_int * 2)()
+        for it in range(iterations - 1):
+            self.lib.hp_shared_route(it, iterations, rw)
+            out.append((self._place(rw[0]), self._place(rw[1])))
+        return out
+
+    def restore_slot(self, iterations, shared_trained=True):
+        slot = self.lib.hp_restore_slot(iterations, int(shared_trained))
+        return None if slot == self.CALLER else slot
+
+    def prior_slot(self, it):
+        return self.lib.hp_prior_slot(it)
+
+    def prior_windows(self, window, frame_offset, M):
+        return self.lib.hp_prior_windows(window, frame_offset, M)
+
+    def tensor_is_shared(self, k, logscale_mode):
+        return bool(self.lib.hp_tensor_is_shared(k, logscale_mode))
+
+    def pack_adam_segments(self, adam):
+        """-> (refusal text or None, (nseg, beg[4], off[5]))"""
+        sg = (C.c_int * 10)()
+        why = self.lib.hp_pack_adam_segments(C.byref(adam), sg)
+        return (why.decode() if why else None), (sg[0], list(sg[1:5]), list(sg[5:10]))
+
+    # ---- geometry ----
+    def padded_verts(self, V):
+        return self.lib.hp_padded_verts(V)
+
+    def nblk_beta(self, Vp):
+        return self.lib.hp_nblk_beta(Vp)
+
+    def skin_form(self, M, V):
+        return SKIN_FORMS[self.lib.hp_skin_form(M, self.padded_verts(V))]
+
+    def head_blocks(self, M, Vp, shape_per_frame, prior):
+        return self.lib.hp_head_blocks(M, Vp, int(shape_per_frame), HEAD_PRIORS[prior])
+
+    def dbeta_grid(self, need_beta, Vp, betas_shared, M):
+        out = (C.c_int * 3)()
+        self.lib.hp_dbeta_grid(int(need_beta), Vp, int(betas_shared), M, out)
+        return tuple(out)
+
+    def parents_ordered(self, parents):
+        return bool(self.lib.hp_parents_ordered((C.c_int * len(parents))(*parents), len(parents)))
+
+    def mesh_grids(self, V, S, P):
+        """mesh3d_forms.grids's arguments and result"""
+        out = (C.c_int * 4)()
+        self.lib.hp_mesh_grids(S, V, P, out)
+        return dict(zip(("bx", "by", "bv", "bp"), out))
+
+    def mesh_query_blocks(self, queries):
+        return self.lib.hp_mesh_query_blocks(queries)
+
+    def mesh_weight(self, w):
+        return self.lib.hp_mesh_weight(w)
+
+    def mesh_points(self, w_chamfer, num_points):
+        return self.lib.hp_mesh_points(w_chamfer, num_points)
+
+    # ---- smalfit_fit_args ----
+    def fit_args_refusal(self, args, max_frames, has_pose_prior, shape_dim):
+        why = self.lib.hp_fit_args_refusal(C.byref(args), max_frames, int(has_pose_prior), shape_dim)
+        return why.decode() if why else None
+
+    def fit_args_size_refusal(self, args):
+        why = self.lib.hp_fit_args_size_refusal(C.byref(args))
+        return why.decode() if why else None
+
+    def sequence_frames(self, args):
+        return self.lib.hp_sequence_frames(C.byref(args))
+
+
+def load():
+    os.makedirs(os.path.dirname(SO), exist_ok=True)
+    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in DEPS):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", SRC, "-o", SO], check=True)
+    return Plan(C.CDLL(SO))
+
+
+def valid_fit_args(**fields):
+    """a block smalfit_fit_eval accepts on an engine with both priors set (dummy non-null pointers: nothing dereferences them),
+    with `fields` changed"""
+    a = _lib.FitArgs()
+    a.num_frames, a.window, a.logscale_mode, a.temporal = 4, 2, 1, 1
+    a.w_j2d = a.w_sil = a.w_betas = a.w_pose = 1.0
+    for i, name in enumerate(("betas", "log_beta_scales", "global_rotation", "joint_rotations", "trans", "target_joints",
+                              "target_visibility", "target_sil", "losses")):
+        setattr(a, name, 0x1000 * (i + 1))
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a

@@ -14,24 +14,15 @@ import torch
 from oracle import smal_oracle as so
 from smalify_amd import config as cfg
 from smalify_amd import model_io, synthetic
-from tests import lbs_forms as lf
+from tests.lbs_forms import skin_form      # noqa: F401  (the cases' launch forms: ic.skin_form(N))
 from tests import parity_cases as pc
 
 TERMS = ("joint", "pose", "splay", "betas", "sil_reproj", "temp_joint", "temp_global", "temp_trans", "limit")
 PARAMS = ("betas", "log_beta_scales", "global_rotation", "joint_rotations", "trans")
 
-# test 1: batch size -> the skinning launch run_lbs_forward takes for it (restated in skin_form below, asserted on the CPU)
+# test 1: batch size -> the skinning launch run_lbs_forward takes for it (tests/lbs_forms.skin_form, asserted on the CPU)
 EVAL_CASES = ((1, "plain"), (3, "plain"), (6, "split"), (20, "split"), (64, "wide"))
 S_EVAL = 64
-
-
-def skin_form(M, padded_verts=None):
-    """run_lbs_forward's three-way choice, restated: M <= 4 the plain kernel; otherwise the wide matrix-core kernel when its
-    grid (Vp / 64 vertex tiles x ceil(M / 16) frame tiles) has at least 256 workgroups, else the split form"""
-    vp = lf.padded_verts() if padded_verts is None else padded_verts
-    if M > 4 and (vp // 64) * ((M + 15) // 16) >= 256:
-        return "wide"
-    return "split" if M > 4 else "plain"
 
 
 def stage_weights(stage):

@@ -1,8 +1,9 @@
 """Which kernel forms the host picks for an LBS evaluation of M frames -- a restatement of the launch rules, so that the
-GPU tests can name the frame counts that reach each form and tests/test_lbs_forms_cpu.py can check both that the chosen
-lists cover every form and that the restatement still matches the host code.  Nothing here needs a GPU.
+GPU tests can name the frame counts that reach each form without a compiler, and tests/test_lbs_forms_cpu.py can check both
+that the chosen lists cover every form and that the restatement answers like the host's own functions.  Nothing here needs a
+GPU.
 
-  skinning forward   smalfit_launch.inc:605 (run_lbs_forward)
+  skinning forward   smalfit_plan.h: skin_form(M, Vp), padded_verts(V) (run_lbs_forward launches what it returns)
       M > 4 and (Vp / 64) * ceil(M / 16) >= 256  -> skin_mfma_kernel        (64 vertices x 16 frames per workgroup)
       M > 4 otherwise                            -> skin_mfma_split_kernel  (tiles of 16 frames, contraction over 4 waves)
       M <= 4                                     -> skin_kernel<8>

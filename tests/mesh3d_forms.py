@@ -1,5 +1,5 @@
 """Which branches of the 3D mesh objective a case reaches -- a restatement of the launch geometry of
-smalify_amd/csrc/kernels_mesh3d.inc and smalfit_mesh3d.inc, the cases of tests/test_gpu_mesh3d_forms.py, and a float64
+smalify_amd/csrc/kernels_mesh3d.inc and of the host's grids (smalfit_plan.h: mesh_grids), the cases of tests/test_gpu_mesh3d_forms.py, and a float64
 numpy reference of the objective whose nearest-neighbour rule is explicit.  tests/test_mesh3d_forms_cpu.py checks that the
 restatement still matches the source, that the cases reach every form and that the reference agrees with the oracle and
 the host shim.  Nothing here asserts or needs a GPU.

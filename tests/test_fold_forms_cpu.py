@@ -1,9 +1,16 @@
-"""tests/fold_forms.py still restates what smalfit_fit_run decides on the host, and the case lists of
-tests/test_gpu_fold_step.py reach every branch of the folded optimiser step (no GPU needed)."""
+"""tests/fold_forms.py answers like the functions smalfit_fit_run decides with (smalify_amd/csrc/smalfit_plan.h, called through
+tests/host_plan_shim.cpp), and the case lists of tests/test_gpu_fold_step.py reach every branch of the folded optimiser step
+(no GPU needed)."""
+import itertools
 import os
+import random
 import re
 
+import pytest
+
+from smalify_amd import _lib
 from tests import fold_forms as ff
+from tests import host_plan
 from tests import lbs_forms as lf
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "smalify_amd", "csrc")
@@ -14,47 +21,152 @@ def _src(name):
         return f.read()
 
 
-def test_the_rules_are_the_hosts():
-    launch = _src("smalfit_launch.inc")
-    # the two conditions at the top of smalfit_fit_run, in this order, and the plain chain behind them
-    m = re.search(r"if \(e->use_graph && !e->prof_on && iterations >= 2 && st != nullptr\) \{.*?"
-                  r"if \(iterations >= 2 && !e->prof_on && plan_fold\(a, o, sg, plan\)\) \{.*?"
-                  r"for \(int it = 0; it < iterations; \+\+it\) \{\s*const int t = o->step \+ it \+ 1;\s*"
-                  r"if \(smalfit_fit_eval\(e, stream, a\)\) return 1;\s*if \(launch_adam_segments\(st, sg, o, t, t == 1\)\) return 1;",
-                  launch, re.S)
-    assert m, "smalfit_fit_run's choice of loop changed: update tests/fold_forms.py"
-    # plan_fold, line by line
-    for line in (
-            "const float* ptr[5] = {a->betas, a->logscale_mode ? a->log_beta_scales : nullptr, a->global_rotation, a->joint_rotations, a->trans};",
-            "const float* gptr[5] = {a->g_betas, a->g_log_beta_scales, a->g_global_rotation, a->g_joint_rotations, a->g_trans};",
-            "const long long cnt[5] = {20, a->logscale_mode == 1 ? 6 : (long long)M * 6, (long long)M * 3, (long long)M * 102, (long long)M * 3};",
-            "if (!ptr[k]) continue;",
-            "if (b <= lo[k] && lo[k] + cnt[k] <= en) inside = true;",
-            "else if (lo[k] < en && b < lo[k] + cnt[k]) touches = true;",
-            "if (touches) return false;",
-            "if (!inside) continue;",
-            "if (gptr[k] != o->grad + lo[k]) return false;",
-            "if (plan.train[j] && lo[j] < lo[k] + cnt[k] && lo[k] < lo[j] + cnt[j]) return false;",
-            "return covered > 0 && covered == sg.off[sg.nseg];"):
-        assert line in launch, "plan_fold changed (%s): update tests/fold_forms.py" % line
-    # where the shared parameters travel, the restore launch, the prior's slot, the number of head-step launches
-    for line in (
-            "fold.pending = it ? &ps : nullptr; fold.prior_slot = it & 1; fold.assemble = last; fold.args_out = &g;",
-            "if (k == 0 || (k == 1 && ls_shared)) {",
-            "float* dst = e->shstate + ((it + 1) & 1) * 96 + at;",
-            "const float* src = e->shstate + (it & 1) * 96 + at;",
-            "if (it) { T.p_in = src; T.m_in = src + 32; T.v_in = src + 64; }",
-            "if (!(it && it + 2 == iterations)) { T.p = dst; T.m = dst + 32; T.v = dst + 64; }",
-            "const bool ls_shared = a->logscale_mode == 1, shared_trained = plan.train[0] || (plan.train[1] && ls_shared);",
-            "if (shared_trained && iterations == 2) {",
-            "shared_state_restore_kernel<<<1, 64, 0, st>>>(e->shstate + ((iterations - 1) & 1) * 96, o->param, o->exp_avg, o->exp_avg_sq,",
-            "if (ex && ex->pending) lbs_head_step_kernel<<<M + h.nshape + (prior ? 1 : 0), 256, 0, st>>>(m, h, *ex->pending);",
-            "const int w0 = (win.offset + win.window - 1) / win.window, w1 = (win.offset + M + win.window - 1) / win.window;",
-            "ex.prior_w = a->w_betas * (float)(w1 - w0);",
-            "static constexpr int kBetaGroups = %d;" % ff.BETA_GROUPS,
-            "e->nblk_beta = (3 * model->Vp + 255) / 256;",
-            "g.ngrp_beta = kBetaGroups;"):
-        assert line in launch, "smalfit_fit_run changed (%s): update tests/fold_forms.py" % line
+@pytest.fixture(scope="module")
+def plan():
+    return host_plan.load()
+
+
+def test_the_rules_are_the_hosts(plan):
+    """run_loop for every combination of the flags, 1 to 8 iterations"""
+    for K in range(1, 9):
+        for graph, profiled, default_stream, accepted in itertools.product((False, True), repeat=4):
+            want = ff.path(K, graph, profiled, default_stream, accepted)
+            assert plan.path(K, graph, profiled, default_stream, accepted) == want, (K, graph, profiled, default_stream, accepted)
+
+
+def _same_plan(plan, M, mode, offsets, ranges, gao):
+    want = ff.plan_fold(M, mode, offsets, ranges, gao)
+    got = plan.plan_fold(M, mode, offsets, ranges, gao)
+    assert got == want, (M, mode, offsets, ranges, gao, got, want)
+    return got
+
+
+def test_plan_fold_is_the_hosts_on_the_case_lists(plan):
+    seen = set()
+    for name, why in ff.REFUSED:
+        for mode in (1, 2):
+            for M in ff.FRAMES:
+                r = ff.refused_layout(name, M, mode)
+                got = _same_plan(plan, M, mode, r["offsets"], r["ranges"], r["grad_at_offset"])[2]
+                assert got == why or (M == 1 and name == "half_of_joint_rotations" and got is None)    # (half of one frame's rows: all of them)
+                seen.add(why)
+    for mode in (0, 1, 2):
+        for M in ff.FRAMES:
+            for order in (None, ff.TENSORS[::-1]):
+                offs, _ = ff.layout(M, mode, order=order)
+                for names, want in ff.trainable_sets(mode).values():
+                    ok, train, _ = _same_plan(plan, M, mode, {k: o for k, (o, _) in offs.items()}, ff.merged_ranges(offs, names),
+                                              {k: k in want for k in offs})
+                    assert ok and {k for k in train if train[k]} == set(names)
+    al = ff.ALIASED_LAYOUT
+    seen.add(_same_plan(plan, al["M"], al["logscale_mode"], al["offsets"], al["ranges"], al["grad_at_offset"])[2])
+    assert seen == {"cut", "gradient", "extra"}
+    # what the restatement leaves out: independent images and a missing tensor are not folded
+    offs, _ = ff.layout(4, 2)
+    o = {k: v[0] for k, v in offs.items()}
+    every = dict.fromkeys(offs, True)
+    assert plan.plan_fold(4, 2, o, ff.merged_ranges(offs, ff.TENSORS), every)[0]
+    assert plan.plan_fold(4, 2, o, ff.merged_ranges(offs, ff.TENSORS), every, subject_frames=1) == (False, dict.fromkeys(ff.TENSORS, False), "nothing")
+    assert not plan.plan_fold(4, 2, {k: v for k, v in o.items() if k != "trans"}, [(0, 20)], every)[0]
+    assert plan.plan_fold(0, 1, o, [(0, 20)], every) == ff.plan_fold(0, 1, o, [(0, 20)], every)
+
+
+def test_plan_fold_is_the_hosts_on_random_layouts(plan):
+    """tensors overlapping, padded and outside the buffer, 0 to 4 ranges drawn around the tensors' ends: every reason and the
+    acceptance are met, and the restatement answers like the host each time"""
+    rs = random.Random(20260)
+    seen = {}
+    for _ in range(6000):
+        M, mode = rs.choice((1, 2, 3, 5)), rs.choice((0, 1, 2))
+        cnt = ff.counts(M, mode)
+        kind = rs.random()
+        if kind < 0.5:                                     # a tidy buffer in a random order, sometimes padded
+            offs, size = ff.layout(M, mode, order=rs.sample(ff.TENSORS, 5), pad=rs.choice((0, 0, 0, 3)))
+            offsets = {k: o for k, (o, _) in offs.items()}
+        else:                                              # anywhere: overlaps, gaps, negative offsets
+            size = sum(cnt.values())
+            offsets = {k: rs.randrange(-30, size) for k in ff.TENSORS if not (k == "log_beta_scales" and mode == 0)}
+        if rs.random() < 0.15:
+            offsets[rs.choice(list(offsets))] = -(1 << 20) + rs.randrange(64)         # a tensor in a buffer of its own
+        if rs.random() < 0.15 and "trans" in offsets:
+            offsets["trans"] = offsets["global_rotation"] + rs.choice((0, 1, -1))      # two tensors on the same floats
+        names = [k for k in offsets if offsets[k] >= 0 and rs.random() < 0.6]          # (a range begins inside the buffer)
+        if rs.random() < 0.6:
+            ranges = ff.merged_ranges({k: (offsets[k], cnt[k]) for k in names}, names)[:4]
+        else:
+            ends = sorted({max(offsets[k] + d, 0) for k in offsets for d in (0, cnt[k], cnt[k] // 2, 1)} | {0, size})
+            ranges = []
+            for _ in range(rs.randrange(0, 5)):
+                b, e = sorted((rs.choice(ends), rs.choice(ends)))
+                ranges.append((b, e))
+        if ranges and rs.random() < 0.1:
+            b, e = ranges[-1]
+            ranges[-1] = (b, e + rs.choice((1, 5)))
+        gao = {k: rs.random() < 0.9 for k in offsets}
+        ok, train, why = _same_plan(plan, M, mode, offsets, ranges, gao)
+        seen[why] = seen.get(why, 0) + 1
+    assert set(seen) == {None, "cut", "gradient", "alias", "nothing", "extra"} and min(seen.values()) >= 20, seen
+
+
+def test_the_routes_are_the_hosts(plan):
+    for K in range(1, 13):
+        assert plan.shared_travel(K) == ff.shared_travel(K), K
+        for trained in (True, False):
+            assert plan.restore_slot(K, trained) == ff.restore_slot(K, trained), (K, trained)
+        assert plan.prior_slot(K - 1) == ff.prior_slot(K - 1)
+    for window in (1, 2, 3, 4, 8):
+        for offset in range(0, 20):
+            for M in range(1, 20):
+                assert plan.prior_windows(window, offset, M) == ff.prior_windows(window, offset, M), (window, offset, M)
+    # which tensors travel: the betas, and the limb scales when one set serves every frame
+    assert [[plan.tensor_is_shared(k, mode) for k in range(5)] for mode in (0, 1, 2)] == \
+        [[True, False, False, False, False], [True, True, False, False, False], [True, False, False, False, False]]
+    assert plan.SHARED_SLOT_FLOATS == 3 * 32 and ff.NUM_BETAS + 6 <= 32
+
+
+def test_the_sizes_are_the_hosts(plan):
+    assert plan.BETA_GROUPS == ff.BETA_GROUPS
+    for V in (1, 255, 256, 257, lf.NUM_VERTS, 4096, 4097):
+        Vp = plan.padded_verts(V)
+        assert Vp == lf.padded_verts(V)
+        assert plan.nblk_beta(Vp) * plan.BETA_GROUPS == ff.column_partials(V)
+        for M in (1, 5, 64):
+            # shared betas: column blocks x one shape set x kBetaGroups frame groups; per frame: x M sets x one group
+            assert plan.dbeta_grid(True, Vp, True, M) == (plan.nblk_beta(Vp), 1, ff.BETA_GROUPS)
+            assert plan.dbeta_grid(True, Vp, False, M) == (plan.nblk_beta(Vp), M, 1)
+            assert plan.dbeta_grid(False, Vp, True, M)[0] == 0
+            # the head launch: M pose blocks, Vp / 256 shape blocks per shape set, the prior's block(s); the step kernel's launch
+            # is the shared-shape one
+            assert plan.head_blocks(M, Vp, False, "none") == M + Vp // 256
+            assert plan.head_blocks(M, Vp, False, "shared") == M + Vp // 256 + 1
+            assert plan.head_blocks(M, Vp, True, "none") == M + Vp // 256 * M
+            assert plan.head_blocks(M, Vp, True, "per_frame") == M + Vp // 256 * M + (M + plan.HEAD_PRIOR_FRAMES - 1) // plan.HEAD_PRIOR_FRAMES
+    fwd = _src("kernels_lbs_forward.inc")
+    assert "constexpr int kPriorFrames = %d;" % plan.HEAD_PRIOR_FRAMES in fwd
+
+
+def test_adam_ranges_are_packed_or_refused(plan):
+    def adam(ranges, **kw):
+        a = _lib.AdamArgs()
+        a.param, a.grad, a.exp_avg, a.exp_avg_sq = 0x1000, 0x2000, 0x3000, 0x4000
+        a.num_segments = len(ranges)
+        for q, (b, e) in enumerate(ranges[:4]):
+            a.seg_begin[q], a.seg_end[q] = b, e
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+    assert plan.pack_adam_segments(adam([(0, 20), (26, 242)])) == (None, (2, [0, 26, 0, 0], [0, 20, 236, 236, 236]))
+    assert plan.pack_adam_segments(adam([])) == (None, (0, [0, 0, 0, 0], [0, 0, 0, 0, 0]))
+    assert plan.pack_adam_segments(adam([(5, 5), (1, 2), (3, 4), (0, 9)]))[1] == (4, [5, 1, 3, 0], [0, 0, 1, 2, 11])
+    for field in ("param", "grad", "exp_avg", "exp_avg_sq"):
+        assert plan.pack_adam_segments(adam([(0, 1)], **{field: None}))[0] == "smalfit adam: null buffer"
+    assert plan.pack_adam_segments(adam([(0, 1)], num_segments=5))[0] == "smalfit adam: at most 4 segments"
+    assert plan.pack_adam_segments(adam([(0, 1)], num_segments=-1))[0] == "smalfit adam: at most 4 segments"
+    assert plan.pack_adam_segments(adam([(-1, 1)]))[0] == "smalfit adam: bad segment"
+    assert plan.pack_adam_segments(adam([(0, 4), (3, 2)]))[0] == "smalfit adam: bad segment"
+
+
+def test_the_step_kernels_sums_are_the_kernels():
     fwd = _src("kernels_lbs_forward.inc")
     assert "constexpr int kAsmFr = %d, kAsmPa = %d, kAsmLs = %d;" % (ff.ASM_FR, ff.ASM_PA, ff.ASM_LS) in fwd
     assert "constexpr int kPendingNb = %d;" % ff.NUM_BETAS in fwd

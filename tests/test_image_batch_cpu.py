@@ -3,12 +3,14 @@ the launch form every case of tests/test_gpu_image_batch.py takes, the argument 
 values' plumbing (an independent image is a one-frame problem of the unchanged oracle)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
+import pytest
 import torch
 
 from smalify_amd import _lib, image_batch as ib
+from tests import fold_forms as ff
+from tests import host_plan
 from tests import image_batch_cases as ic
 from tests import lbs_forms as lf
 
@@ -63,18 +65,31 @@ def test_the_fitters_ranges_are_the_layouts():
     assert Probe(3)._sequence_kwargs() == dict(window=1, temporal=False, subject_frames=1)
 
 
-def test_eval_cases_take_every_skinning_launch():
-    launch = open(os.path.join(ROOT, "smalify_amd", "csrc", "smalfit_launch.inc")).read()
-    # the condition skin_form restates
-    assert re.search(r"if \(M > 4 && \(m\.Vp / 64\) \* \(\(M \+ 15\) / 16\) >= 256\)\s*skin_mfma_kernel<<<.*?else if \(M > 4\)[^\n]*\n\s*"
-                     r"skin_mfma_split_kernel<<<.*?else\s*skin_kernel<8><<<", launch, re.S)
+@pytest.fixture(scope="module")
+def plan():
+    return host_plan.load()
+
+
+def test_eval_cases_take_every_skinning_launch(plan):
     assert {form for _, form in ic.EVAL_CASES} == {"plain", "split", "wide"}
     for N, form in ic.EVAL_CASES:
-        assert ic.skin_form(N) == form == lf.skin_form(N), N
+        assert ic.skin_form(N) == form == plan.skin_form(N, lf.NUM_VERTS), N
     assert [ic.skin_form(M) for M in (4, 5, 48, 49)] == ["plain", "split", "split", "wide"]
-    # independent mode reaches that launch with one shape set per frame and keeps the plain chain
-    assert "indep ? nb : 0" in launch and "indep ? 0 : 1" in launch
-    assert "if (a->subject_frames != 0) return false;" in launch
+    # independent mode reaches that launch with one shape set per frame: M times the shape blocks, M sets of dbeta partials in
+    # one frame group each, a prior block per 16 frames
+    Vp = lf.padded_verts()
+    for N, _ in ic.EVAL_CASES:
+        assert plan.head_blocks(N, Vp, True, "per_frame") - plan.head_blocks(N, Vp, False, "shared") == (N - 1) * (Vp // 256) + (N + 15) // 16 - 1
+        assert plan.dbeta_grid(True, Vp, False, N)[1:] == (N, 1) and plan.dbeta_grid(True, Vp, True, N)[1:] == (1, ff.BETA_GROUPS)
+    # ... and keeps the plain chain: plan_fold refuses the mode whatever the ranges, so smalfit_fit_run never folds it
+    for N in (1, 6):
+        offs, shapes, size = ib.flat_layout(N)
+        o = {k: v[0] for k, v in offs.items()}
+        for stage in (0, 1):
+            ranges = ib.adam_ranges(offs, ib.trainable_names(stage))
+            ok, train, why = plan.plan_fold(N, 2, o, ranges, dict.fromkeys(offs, True), subject_frames=1)
+            assert not ok and not any(train.values())
+            assert all(plan.path(K, False, False, ds, ok) == "plain" for K in (1, 2, 7) for ds in (True, False))
 
 
 def test_argument_block_fields():

@@ -1,8 +1,12 @@
 """The frame counts of tests/test_gpu_frame_counts.py reach every kernel form the host can pick, and tests/lbs_forms.py
-still restates the host's selection rules (no GPU needed)."""
+answers like the host's selection rules (smalify_amd/csrc/smalfit_plan.h, called through tests/host_plan_shim.cpp; no GPU
+needed)."""
 import os
 import re
 
+import pytest
+
+from tests import host_plan
 from tests import lbs_forms as lf
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "smalify_amd", "csrc")
@@ -13,13 +17,21 @@ def _src(name):
         return f.read()
 
 
-def test_the_rules_are_the_hosts():
-    launch = _src("smalfit_launch.inc")
-    # run_lbs_forward: the wide kernel's condition, then the split kernel for M > 4, then skin_kernel<8>
-    m = re.search(r"if \(M > 4 && \(m\.Vp / 64\) \* \(\(M \+ 15\) / 16\) >= 256\)\s*skin_mfma_kernel<<<.*?"
-                  r"else if \(M > 4\)[^\n]*\n\s*skin_mfma_split_kernel<<<.*?else\s*skin_kernel<8><<<", launch, re.S)
-    assert m, "run_lbs_forward's choice of skinning kernel changed: update tests/lbs_forms.py"
-    assert "const int Vp = (int)align_up((size_t)V, 256);" in launch
+@pytest.fixture(scope="module")
+def plan():
+    return host_plan.load()
+
+
+def test_the_rules_are_the_hosts(plan):
+    # skin_form and padded_verts: every frame count up to 300, vertex counts around the block size and the models'
+    for V in (1, 64, 255, 256, 257, 1000, 2048, 3072, 3073, lf.NUM_VERTS, 4096, 4097, 8192, 20000):
+        assert plan.padded_verts(V) == lf.padded_verts(V), V
+        for M in range(1, 301):
+            assert plan.skin_form(M, V) == lf.skin_form(M, V), (M, V)
+    assert {plan.skin_form(M, V) for M in (4, 5, 300) for V in (64, 20000)} == {"plain", "split", "wide"}
+
+
+def test_the_chunks_are_the_kernels():
     bwd = _src("kernels_lbs_backward.inc")
     tiles = re.search(r"constexpr int PBM_SPLITS = \d+, PBM_U = \d+, PBM_TILES = (\d+);", bwd)
     assert tiles and int(tiles.group(1)) == lf.PBM_TILES

@@ -1,7 +1,9 @@
 """The cases of tests/test_gpu_mesh3d_forms.py reach every branch of the 3D mesh objective, tests/mesh3d_forms.py still
-restates the kernels' launch geometry and tie rule, and its float64 reference agrees with the oracle (no ties) and with
-the host shim of the kernels' maths (designed ties, lowest index wins).  No GPU needed."""
+restates the kernels' tie rule and answers like the host's launch geometry (smalify_amd/csrc/smalfit_plan.h, called through
+tests/host_plan_shim.cpp), and its float64 reference agrees with the oracle (no ties) and with the host shim of the kernels'
+maths (designed ties, lowest index wins).  No GPU needed."""
 import ctypes as C
+import itertools
 import os
 import re
 import subprocess
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import mesh3d_oracle as mo
+from tests import host_plan
 from tests import mesh3d_cases as mc
 from tests import mesh3d_forms as mf
 
@@ -71,20 +74,21 @@ def test_the_rules_are_the_kernels():
 
 
 def test_the_grids_are_the_hosts():
-    h = _src("smalfit_mesh3d.inc")
-    for line in ("a.N = num_meshes; a.V = m->t.V; a.S = wc > 0.f ? num_points : 1;",
-                 "a.bx = (a.S + kChamQueries - 1) / kChamQueries; a.by = m->by; a.bv = m->bv; a.bp = m->bp;",
-                 "m->by = (V + kChamQueries - 1) / kChamQueries;", "m->bv = (V + kMeshBlock - 1) / kMeshBlock;",
-                 "m->bp = (h.P + kMeshBlock - 1) / kMeshBlock;",
-                 "mesh3d_chamfer_kernel<0><<<dim3(a.bx, a.N), 256, 0, st>>>(a);",
-                 "mesh3d_chamfer_kernel<1><<<dim3(a.by, a.N), 256, 0, st>>>(a);",
-                 "mesh3d_ring_kernel<<<dim3(a.bv + a.bp, a.N), kMeshBlock, 0, st>>>(a);",
-                 "mesh3d_gather_kernel<<<dim3(a.bv, a.N), kMeshBlock, 0, st>>>(a);",
-                 "HIP_OK(hipMemsetAsync(m->gcham, 0, total * sizeof(float), st));"):
-        assert line in h, line
-    # negative weights are clamped to 0 on the host
-    for i in range(4):
-        assert "std::max(weights[%d], 0.f)" % i in h
+    plan = host_plan.load()
+    # the block sizes the host divides by are the kernels' (pinned to kernels_mesh3d.inc above)
+    assert (plan.MESH_QUERIES, plan.MESH_THREADS) == (mf.CHAM_QUERIES, mf.MESH_BLOCK)
+    # the sizes test_rule_boundaries names and every case's, each with a grid around it
+    sizes = {(3889, 3000, 11529), (64, 64, 0), (65, 65, 257)} | {(r["V"], r["S"], r["P"]) for r in mf.coverage_table()}
+    for V, S, P in sizes:
+        for dv, ds, dp in itertools.product((-1, 0, 1, 63, 64, 255, 256), repeat=3):
+            v, s, p = V + dv, max(S + ds, 1), max(P + dp, 0)
+            assert plan.mesh_grids(v, s, p) == mf.grids(v, s, p), (v, s, p)
+            assert plan.mesh_query_blocks(s) == mf.grids(v, s, p)["bx"]          # an evaluation's own bx follows its num_points
+    # the chamfer-off call stands as one query (S = 1, see mf.grids), whatever num_points says
+    assert [plan.mesh_points(w, 3000) for w in (1.0, 1e-30, 0.0, -1.0)] == [3000, 3000, 1, 1]
+    # negative weights are clamped to 0 on the host, like mf.reference does
+    for w in (-2.5, -0.0, 0.0, 1e-30, 0.25, 7.0):
+        assert plan.mesh_weight(w) == np.float32(max(w, 0.0))
 
 
 def test_rule_boundaries():

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from tests import host_plan
 from tests import raster_forms as rf
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "smalify_amd", "csrc")
@@ -34,7 +35,7 @@ def test_the_constants_are_the_kernels():
         assert _const(r, name) == val, name
     assert "constexpr int kBandFillWide = %d, kBandFillNarrow = %d;" % (rf.BAND_FILL_WIDE, rf.BAND_FILL_NARROW) in r
     assert "constexpr float kBoxSlack = 1.0f / 64.0f;" in r
-    assert "if (image_size > %d) return fail(" % rf.MAX_S in _src("smalfit_launch.inc")
+    assert host_plan.load().MAX_IMAGE_SIZE == rf.MAX_S          # smalfit_engine_create refuses larger images
 
 
 def test_the_decisions_are_the_kernels():
