@@ -253,6 +253,32 @@ typedef struct smalfit_fit_args {
 
 int smalfit_fit_eval(smalfit_engine* engine, void* stream, const smalfit_fit_args* args);
 
+/* ---- the same evaluation, with every window's loss terms and its share of the shared gradients ------------------------
+ * replaces: the per-window calls of SMALFitter.forward inside one epoch and the backward of their (weighted) sum
+ *           reference smal_fitter/smal_fitter.py:107-175, smal_fitter/optimize_to_joints.py:119-122
+ * The reference's driver calls forward() once per window and backward() once per epoch on the sum.  One evaluation of the
+ * whole sequence serves that loop exactly when each window's loss and each window's gradient can be handed out on their own:
+ * the gradients of global_rotation, joint_rotations, trans and per-frame limb scales are per frame already; the rows below
+ * are the missing part, the shared parameters.
+ *   row w of losses            the nine terms restricted to the frames of window w (same weights and normalisers); the shape
+ *                              prior's term in the rows of the windows this evaluation owns; the temporal columns of the pair
+ *                              (n, n+1) in the row of frame n's window
+ *   row w of g_betas /         gradient of row w's total: the shape-blend adjoint of the window's frames, their rest-joint
+ *     g_log_beta_scales        path, and the prior's gradient once per owned window
+ * args->losses, the per-frame gradients and args->losses_per_frame are what smalfit_fit_eval writes for the same block, bit
+ * for bit; args->g_betas / args->g_log_beta_scales (shared, logscale_mode 1), when not NULL, are the rows added in window
+ * order in double and rounded once.  One subject only (args->subject_frames 0: independent images already have one row per
+ * image). */
+typedef struct smalfit_window_rows {
+  unsigned struct_size;          /* sizeof(smalfit_window_rows) of the caller's header; checked before any other field */
+  int num_windows;               /* W = windows of the SEQUENCE holding at least one of the M frames:
+                                    (frame_offset + M - 1) / window - frame_offset / window + 1; any other value is refused */
+  float* losses;                 /* (W, 9), required */
+  float* g_betas;                /* (W, 20) or NULL */
+  float* g_log_beta_scales;      /* (W, 6) or NULL; logscale_mode 1 only, refused when non-NULL in modes 0 / 2 */
+} smalfit_window_rows;
+int smalfit_fit_eval_windows(smalfit_engine* engine, void* stream, const smalfit_fit_args* args, const smalfit_window_rows* rows);
+
 /* ---- the epoch loop: loss + backward + optimizer.step(), `iterations` times in one call ---------------------------
  * replaces: the body of the epoch loop                        reference smal_fitter/optimize_to_joints.py:113-137
  *   optimizer.zero_grad(); acc_loss = sum over windows of model(...) + temporal; acc_loss.backward(); optimizer.step()

@@ -50,6 +50,16 @@ class FitArgs(C.Structure):
         self.struct_size = C.sizeof(FitArgs)
 
 
+class WindowRows(C.Structure):
+    """smalfit_window_rows: one row per window of the sequence (smalfit_fit_eval_windows)"""
+    _fields_ = [("struct_size", C.c_uint), ("num_windows", C.c_int), ("losses", C.c_void_p), ("g_betas", C.c_void_p),
+                ("g_log_beta_scales", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(WindowRows)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -127,6 +137,7 @@ SIGNATURES = {
     "smalfit_render_backward": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP]),
     "smalfit_project_points_backward": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
     "smalfit_fit_eval": (_I, [_VP, _VP, C.POINTER(FitArgs)]),
+    "smalfit_fit_eval_windows": (_I, [_VP, _VP, C.POINTER(FitArgs), C.POINTER(WindowRows)]),
     "smalfit_fit_run": (_I, [_VP, _VP, C.POINTER(FitArgs), C.POINTER(AdamArgs), _I]),
     "smalfit_engine_set_graph": (_I, [_VP, _I]),
     "smalfit_adam_segments": (_I, [_VP, C.POINTER(AdamArgs)]),
@@ -148,6 +159,10 @@ SIGNATURES = {
     "smalfit_mesh_targets_sample": (_I, [_VP, _VP, _I, C.c_ulonglong, C.c_uint, _VP]),
     "smalfit_fit3d_step": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs)]),
 }
+
+# Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
+# built before them loads, and resolve() names the symbol when one is asked for
+LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows"])
 
 
 class SmalfitError(RuntimeError):
@@ -204,12 +219,25 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:
+            if name in LAZY_SYMBOLS:
+                continue
             raise SmalfitError("%s does not export %s although it reports ABI version %d: header / library mismatch, rebuild the library"
                                % (LIB_PATH, name, version)) from exc
         fn.restype = res
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def resolve(lib, name):
+    """an entry point of LAZY_SYMBOLS with its signature attached, or a SmalfitError that names it"""
+    try:
+        fn = getattr(lib, name)
+    except AttributeError as exc:
+        raise SmalfitError("%s does not export %s: the library was built from an older source tree of ABI version %d, rebuild it"
+                           % (getattr(lib, "_name", LIB_PATH), name, ABI_VERSION)) from exc
+    fn.restype, fn.argtypes = SIGNATURES[name]
+    return fn
 
 
 def check(rc, what=""):

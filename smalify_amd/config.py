@@ -25,6 +25,12 @@ SEQUENCE_OR_IMAGE_NAME = "badja:rs_dog"
 IMAGE_RANGE = range(0, 1)
 WINDOW_SIZE = 10
 
+# No counterpart in the reference.  True: the caller states that its epoch loop asks SMALFitter.forward for EVERY window of the
+# sequence between two optimiser steps (optimize_to_joints.py:119-122 does); the fitter then evaluates the whole sequence once
+# per epoch and hands each window its own loss and gradients (SMALFitter(..., epoch_evaluation=None) reads this).  A caller that
+# asks for single windows is slower with it: the fitter cannot see at the first call which windows will follow.
+EPOCH_EVALUATION = False
+
 CHECKPOINT_NAME = "20201001-125009"
 EPOCH_NAME = "st10_ep0"
 

@@ -837,6 +837,113 @@ frame_loss_rows_kernel(AssembleArgs a, AssembleExt x) {
   }
 }
 
+// One row per WINDOW of the sequence (smalfit_fit_eval_windows): the nine loss terms of the window's frames and the window's share
+// of the shared parameters' gradient, so that a caller can weight or backpropagate every window of ONE evaluation on its own
+// (smal_fitter.py:107-175 is called per window, optimize_to_joints.py:119-122).  Launched only by that entry point, behind
+// everything it reads, like frame_loss_rows_kernel: the backward pass ran in the per-frame partial layout of independent images
+// (dbeta_part[n][column block][nb], chain_bwd_kernel's riders with betas_shared 0) and assemble_kernel left the shared gradients
+// alone.  One block per window: 8 slices of its frames' column-block partials per shape direction, then the slices, the frames'
+// rest-joint paths and the prior's share in a fixed order, in double, rounded once; wave 1 the shared limb scales, wave 2 the loss
+// row (the queue kernels' integer share is added as integers and converted once).  The block that arrives last adds the rows in
+// window order, in double: that is smalfit_fit_args.g_betas / g_log_beta_scales.  Two runs give the same bits.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__global__ void __launch_bounds__(256)
+window_rows_kernel(AssembleArgs a, AssembleExt x, WindowRowsDev r) {
+  __shared__ double bsum[8][kWindowRowBetas];
+  __shared__ int is_last;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, w = blockIdx.x, M = a.M;
+  // local frames [n0, n1) of the w-th window that holds any of these frames; a shard may start inside a window it does not own
+  const int start = (a.win.offset / a.win.window + w) * a.win.window;
+  const int n0 = max(start - a.win.offset, 0), n1 = min(start + a.win.window - a.win.offset, M);
+  const bool owned = start >= a.win.offset && x.prior_windows > 0;
+  if (r.row_betas) {
+    const int bl = t & 31, slice = t >> 5;
+    double acc = 0.0;
+    if (bl < a.nb) {
+      const int items = (n1 - n0) * a.nblk_beta;                                   // frame-major, column blocks inside: contiguous rows of nb
+      const float* pp = a.dbeta_part + (size_t)n0 * a.nblk_beta * a.nb + bl;
+#pragma unroll 8
+      for (int i = slice; i < items; i += 8) acc += (double)pp[(size_t)i * a.nb];
+    }
+    bsum[slice][bl] = acc;
+  }
+  __syncthreads();
+  if (r.row_betas && t < a.nb) {
+    double tot = 0.0;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) tot += bsum[s][t];
+    for (int n = n0; n < n1; ++n) tot += (double)a.dbetaJ[(size_t)n * a.NBall + t];
+    if (a.gb_prior && owned) tot += (double)a.gb_prior[t] / (double)x.prior_windows;
+    const float row = (float)tot;
+    r.row_betas[w * kWindowRowBetas + t] = row;
+    if (r.g_betas) r.g_betas[w * a.nb + t] = row;
+  } else if (r.row_ls && wave == 1 && lane < 6) {
+    double tot = 0.0;
+    for (int n = n0; n < n1; ++n) tot += (double)a.dls[(size_t)n * 6 + lane];
+    if (a.gls_prior && owned) tot += (double)a.gls_prior[lane] / (double)x.prior_windows;
+    const float row = (float)tot;
+    r.row_ls[w * kWindowRowScales + lane] = row;
+    if (r.g_ls) r.g_ls[w * 6 + lane] = row;
+  } else if (wave == 2) {
+    double lsil = 0.0;
+    if (a.tile_loss) {
+      // (every frame of a window has the window's normaliser)
+      const float wn = a.w_sil / ((float)frame_window_size(n0, a.win) * (float)a.S * (float)a.S);
+      const int cnt = (n1 - n0) * a.T;
+      const float* tl = a.tile_loss + (size_t)n0 * a.T;
+      for (int k = lane; k < cnt; k += 64) lsil += (double)(tl[k] * wn);
+    }
+    lsil = wave_sum_f64(lsil);
+    if (lane == 4 && a.tile_loss) {
+      unsigned long long q = 0ull;
+      for (int n = n0; n < n1; ++n) {
+        unsigned long long* fq = x.frame_qloss + (size_t)n * kFrameLossStride;
+        q += *fq;
+        if (r.clear_qloss) *fq = 0ull;           // zero for the next evaluation that feeds it
+      }
+      lsil += (double)q * (1.0 / (double)kLossFix);
+    }
+    if (lane < 9) {
+      // columns: joint, pose, splay, betas, sil_reproj, temp_joint, temp_global, temp_trans, limit <- loss_part[n][0, 1, 2, -, -, 5, 6, 7, 3]
+      float v;
+      if (lane == 3) v = (a.loss_betas && owned) ? *a.loss_betas / (float)x.prior_windows : 0.f;
+      else if (lane == 4) v = (float)lsil;
+      else {
+        const int src = lane == 8 ? 3 : lane;
+        double acc = 0.0;
+        for (int n = n0; n < n1; ++n) acc += (double)a.loss_part[n * 8 + src];
+        v = (float)acc;
+      }
+      r.losses[w * 9 + lane] = v;
+    }
+  }
+  if (!r.tot_betas && !r.tot_ls) return;
+  // ---- the last block to arrive adds the rows in window order
+  __threadfence();
+  __syncthreads();
+  if (t == 0) is_last = (atomicAdd(r.counter, 1) == (int)gridDim.x - 1);
+  __syncthreads();
+  if (!is_last) return;
+  __threadfence();
+  if (r.tot_betas && t < a.nb) {
+    const volatile float* rows = r.row_betas;
+    double tot = 0.0;
+    for (int i = 0; i < r.W; ++i) tot += (double)rows[i * kWindowRowBetas + t];
+    r.tot_betas[t] = (float)tot;
+  }
+  if (r.tot_ls && wave == 1 && lane < 6) {
+    const volatile float* rows = r.row_ls;
+    double tot = 0.0;
+    for (int i = 0; i < r.W; ++i) tot += (double)rows[i * kWindowRowScales + lane];
+    r.tot_ls[lane] = (float)tot;
+  }
+  if (t == 0) *r.counter = 0;
+}
+
 // adjoint of a per-frame template offset (SMAL.__call__'s del_v / v_template): d v_shaped = d v_posed + J_regressor d(rest joints)
 __global__ void offset_grad_kernel(ModelDev m, int M, const float* __restrict__ dvp /*[M][3][Vp]*/,
                                    const float* __restrict__ dJrest /*[M][105]*/, float* __restrict__ doff /*[M][V][3]*/) {

@@ -143,6 +143,20 @@ struct AssembleExt {
   int prior_windows;                       // one subject: windows whose prior term this evaluation owns (their sum is *loss_betas)
 };
 
+// What window_rows_kernel takes beside AssembleArgs / AssembleExt (smalfit_fit_eval_windows): one row per window of the sequence.
+struct WindowRowsDev {
+  int W;                    // rows
+  int clear_qloss;          // this kernel is the last reader of frame_qloss (no frame_loss_rows_kernel behind it): clear it
+  float* losses;            // [W][9]
+  float* g_betas;           // [W][nb] or null
+  float* g_ls;              // [W][6] or null
+  float* row_betas;         // workspace [W][kWindowRowBetas]: the rows as the block that arrives last adds them up; null: no shape gradient
+  float* row_ls;            // workspace [W][kWindowRowScales]; null: no shared limb-scale gradient
+  float* tot_betas;         // [nb] the rows added in window order (smalfit_fit_args.g_betas) or null
+  float* tot_ls;            // [6] likewise or null
+  int* counter;             // arrival counter of the kernel's blocks (zero between launches)
+};
+
 // One optimiser step that has not been taken yet, carried by the NEXT evaluation's lbs_head_kernel (smalfit_fit_run): the raw
 // partials of the previous evaluation's backward pass as assemble_kernel would read them, and per parameter tensor where its
 // value / moments are read and where value / moments / gradient go.  Per-frame tensors are stepped in place by their frame's

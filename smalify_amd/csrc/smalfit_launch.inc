@@ -103,6 +103,7 @@ struct smalfit_engine {
   float *dJ41, *dvert, *dvp, *dext, *dA, *dpf_part, *dbeta_part, *dtheta, *dls, *dJrest;
   float* dbetaJ;
   float *dth_direct, *dtr_direct, *dtr_part, *loss_part, *loss_betas, *gb_prior, *gls_prior;
+  float *win_gb, *win_gls;                             // smalfit_fit_eval_windows: the rows before they are added up, [maxM][kWindowRowBetas], [maxM][kWindowRowScales]
   float *loss_betas_pf, *gb_prior_pf, *gls_prior_pf;   // independent images: the prior per frame, [maxM], [maxM][kPriorSlotB], [maxM][kPriorSlotLs]
   unsigned long long* frame_qloss;                     // the queue kernels' loss per frame: [maxM][kFrameLossStride], zero between evaluations
   float *ones, *zeros;
@@ -466,6 +467,8 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   CARVE(gb_prior_pf, M * 32, float);
   CARVE(gls_prior_pf, M * 8, float);
   CARVE(frame_qloss, M * kFrameLossStride, unsigned long long);
+  CARVE(win_gb, M * kWindowRowBetas, float);      // (a window holds at least one frame: at most M rows)
+  CARVE(win_gls, M * kWindowRowScales, float);
   CARVE(ones, 128, float);
   CARVE(zeros, M * 128, float);
   CARVE(canon, 32, int);
@@ -729,6 +732,7 @@ struct EvalFold {
   int prior_slot = 0;                     // half of the shape prior's gradient buffers this evaluation writes
   bool assemble = true;                   // run assemble_kernel (gradients to the caller's buffers, the nine loss terms)
   AssembleArgs* args_out = nullptr;       // the assembly's arguments, for the successor's pending step
+  const smalfit_window_rows* window_rows = nullptr;   // smalfit_fit_eval_windows: one row per window (checked by the caller)
 };
 
 static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const EvalFold& fold) {
@@ -752,6 +756,8 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   const bool prior_uses_ls = prior_uses_limb_scales(a, e->shape_dim);
   // one row of loss terms per frame: only an evaluation that assembles writes (and clears the counters behind) them
   const bool rows = a->losses_per_frame != nullptr && fold.assemble;
+  // one row per window: the shared parameters' gradients are formed per window from per-frame partials (window_rows_kernel)
+  const smalfit_window_rows* wr = fold.window_rows;
   int nwin = 0;   // windows whose shape-prior term this evaluation owns
   {
     Section sec(e, st, SMALFIT_SEC_LBS_FWD);
@@ -789,7 +795,7 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
     SilTarget tsil{nullptr, nullptr};
     if (sil_on) { if (a->target_sil_u8) tsil.b = a->target_sil_u8; else tsil.f = a->target_sil; }
     if (run_raster_forward(e, st, M, win, a->w_sil, tsil, a->sil_out, sil_on ? e->tile_loss : nullptr, e->joints, &la,
-                           (rows && sil_on) ? e->frame_qloss : nullptr)) return 1;
+                           ((rows || wr) && sil_on) ? e->frame_qloss : nullptr)) return 1;
   }
   if (sil_on) {
     Section sec(e, st, SMALFIT_SEC_RASTER_BWD);
@@ -802,12 +808,13 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
   }
 
   const bool need_pose = a->g_joint_rotations != nullptr;
-  const bool need_beta = a->g_betas != nullptr;
-  const bool need_ls = a->g_log_beta_scales != nullptr && a->logscale_mode != 0;
+  const bool need_beta = a->g_betas != nullptr || (wr && wr->g_betas);
+  const bool need_ls = (a->g_log_beta_scales != nullptr || (wr && wr->g_log_beta_scales)) && a->logscale_mode != 0;
   {
     Section sec(e, st, SMALFIT_SEC_LBS_BWD);
-    // (independent images: per-frame partials of the shape-blend adjoint, per-frame rest joints)
-    if (run_lbs_backward(e, st, M, nb, indep ? 0 : 1, sil_on ? e->dface : nullptr, e->dJ41, nullptr, need_pose, need_beta, need_ls,
+    // (independent images: per-frame partials of the shape-blend adjoint, per-frame rest joints; window rows: the same partial
+    // layout -- M rows of nblk_beta * nb floats, dbeta_rows() holds them -- over the one shared shape)
+    if (run_lbs_backward(e, st, M, nb, (indep || wr) ? 0 : 1, sil_on ? e->dface : nullptr, e->dJ41, nullptr, need_pose, need_beta, need_ls,
                          e->dth_direct, indep ? 105 : 0)) return 1;
   }
 
@@ -840,12 +847,30 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
       if (prior_uses_ls) { gx.gls_prior_pf = e->gls_prior_pf; gx.gls_stride = kPriorSlotLs; }
     }
   }
+  WindowRowsDev wd;
+  std::memset(&wd, 0, sizeof(wd));
+  if (wr) {
+    static_assert(kWindowRowBetas >= 20 && kWindowRowScales >= 6, "a row of the workspace holds a row of the gradient");
+    const bool ls_rows = need_ls && a->logscale_mode == 1;
+    wd.W = wr->num_windows; wd.clear_qloss = rows ? 0 : 1;
+    wd.losses = wr->losses; wd.g_betas = wr->g_betas; wd.g_ls = wr->g_log_beta_scales;
+    wd.row_betas = need_beta ? e->win_gb : nullptr; wd.row_ls = ls_rows ? e->win_gls : nullptr;
+    wd.tot_betas = a->g_betas; wd.tot_ls = ls_rows ? a->g_log_beta_scales : nullptr;
+    wd.counter = e->asm_counter + 1;          // (assemble_kernel's is slot 0)
+    // the assembly leaves the shared gradients to window_rows_kernel (per-frame limb scales stay its own)
+    g.g_betas = nullptr;
+    if (a->logscale_mode == 1) g.g_ls = nullptr;
+  }
   if (fold.args_out) *fold.args_out = g;
   if (fold.assemble) {
     // roles: one block per shape set | limb scales | elements | loss partials
     if (indep) assemble_kernel<true><<<M + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g, gx);
     else assemble_kernel<false><<<1 + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g, gx);
     LAUNCH_OK("assemble_kernel");
+    if (wr) {     // (before frame_loss_rows_kernel, which clears the per-frame counters both read)
+      window_rows_kernel<<<wd.W, 256, 0, st>>>(g, gx, wd);
+      LAUNCH_OK("window_rows_kernel");
+    }
     if (rows) {
       frame_loss_rows_kernel<<<kAsmRows, 256, 0, st>>>(g, gx);
       LAUNCH_OK("frame_loss_rows_kernel");
@@ -862,6 +887,17 @@ static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args
 extern "C" {
 
 int smalfit_fit_eval(smalfit_engine* e, void* stream, const smalfit_fit_args* a) { return fit_eval_impl(e, stream, a, EvalFold{}); }
+
+int smalfit_fit_eval_windows(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const smalfit_window_rows* rows) {
+  if (!e || !a || !rows) return fail("smalfit_fit_eval_windows: null argument");
+  // the sizes of both blocks before any other field of either
+  if (refused("smalfit_fit_eval_windows", window_rows_size_refusal(rows))) return 1;
+  if (refused("smalfit_fit_eval_windows", fit_args_refusal(a, EngineFacts{e->maxM, e->has_pose_prior, e->shape_dim}))) return 1;
+  if (refused("smalfit_fit_eval_windows", window_rows_refusal(a, rows))) return 1;
+  EvalFold fold;
+  fold.window_rows = rows;
+  return fit_eval_impl(e, stream, a, fold);
+}
 
 // ------------------------------------------------------------------------------------------------
 // per-section timing with HIP events on the caller's stream

@@ -136,6 +136,33 @@ inline int prior_windows(int window, int frame_offset, int M) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// smalfit_window_rows: one row per window of the sequence (smalfit_fit_eval_windows)
+// ------------------------------------------------------------------------------------------------
+// windows of the SEQUENCE that hold at least one of the M frames [frame_offset, frame_offset + M); the first may be one this
+// evaluation does not own (prior_windows counts the owned ones)
+inline int window_rows_count(int window, int frame_offset, int M) {
+  return (frame_offset + M - 1) / window - frame_offset / window + 1;
+}
+// the engine keeps the rows of an evaluation in its workspace before they are added up: floats per row
+constexpr int kWindowRowBetas = 32, kWindowRowScales = 8;
+inline const char* window_rows_size_refusal(const smalfit_window_rows* r) {
+  return r->struct_size == (unsigned)sizeof(smalfit_window_rows)
+             ? nullptr : "smalfit_window_rows.struct_size does not match this library (built against another smalfit.h?)";
+}
+// -> why smalfit_fit_eval_windows refuses the rows for a block that fit_args_refusal accepts, or nullptr
+inline const char* window_rows_refusal(const smalfit_fit_args* a, const smalfit_window_rows* r) {
+  if (const char* msg = window_rows_size_refusal(r)) return msg;
+  if (!r->losses) return "smalfit_window_rows.losses missing";
+  if (a->subject_frames != 0) return "window rows need subject_frames = 0 (independent images already have one row per image)";
+  if (a->window <= 0 || a->num_frames <= 0 || a->frame_offset < 0 ||
+      r->num_windows != window_rows_count(a->window, a->frame_offset, a->num_frames))
+    return "smalfit_window_rows.num_windows is not the number of windows these frames belong to";
+  if (r->g_log_beta_scales && a->logscale_mode != 1)
+    return "smalfit_window_rows.g_log_beta_scales needs shared log_beta_scales (logscale_mode 1)";
+  return nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------
 // smalfit_adam_args: the trainable ranges, packed for the segment kernels
 // ------------------------------------------------------------------------------------------------
 struct AdamSegments {

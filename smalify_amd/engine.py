@@ -184,6 +184,52 @@ class Engine:
         check(self.lib.smalfit_fit_eval(self.handle, _stream(), C.byref(a)), "smalfit_fit_eval")
         return losses, grads
 
+    @staticmethod
+    def num_windows(num_frames, window, frame_offset=0):
+        """windows of the sequence that hold at least one of the frames [frame_offset, frame_offset + num_frames)"""
+        return (frame_offset + num_frames - 1) // window - frame_offset // window + 1
+
+    def fit_eval_windows(self, *, window_losses=None, window_grads=None, **fit):
+        """fit_eval (same arguments) that also hands out every window's share (smalfit_fit_eval_windows; reference
+        smal_fitter.py:107-175 called per window, optimize_to_joints.py:119-122): row w of window_losses (W, 9) holds the nine
+        terms of window w's frames, row w of window_grads["betas"] (W, 20) / ["log_beta_scales"] (W, 6) the gradient of that
+        row's total with respect to the shared parameter.  Rows are formed for the shared tensors named in `want`
+        (log_beta_scales only when it is shared, (6,)); the caller may pass the buffers.
+        Returns (losses (9,), grads, window_losses, window_grads)."""
+        fn = _lib.resolve(self.lib, "smalfit_fit_eval_windows")
+        a, losses, grads, _keep = self.build_fit_args(**fit)
+        if a.window <= 0 or a.frame_offset < 0:
+            raise SmalfitError("window must be positive and frame_offset >= 0")
+        W = self.num_windows(a.num_frames, a.window, a.frame_offset)
+        dev = fit["global_rotation"].device
+
+        def rows(t, cols, what):
+            # the library cannot know the extent of a device pointer
+            if t is None:
+                return torch.empty(W, cols, device=dev, dtype=torch.float32)
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (W, cols)):
+                raise SmalfitError("%s must be a contiguous float32 tensor of (%d, %d): one row per window" % (what, W, cols))
+            return t
+
+        window_losses = rows(window_losses, NUM_LOSS_TERMS, "window_losses")
+        given = dict(window_grads) if window_grads is not None else {}
+        unknown = set(given) - {"betas", "log_beta_scales"}
+        if unknown:
+            raise SmalfitError("window_grads takes 'betas' and 'log_beta_scales', not %s" % sorted(unknown))
+        want = fit.get("want", ("betas", "log_beta_scales"))
+        out = {}
+        if "betas" in want or "betas" in given:
+            out["betas"] = rows(given.get("betas"), 20, "window_grads['betas']")
+        if a.logscale_mode == 1 and ("log_beta_scales" in want or "log_beta_scales" in given):
+            out["log_beta_scales"] = rows(given.get("log_beta_scales"), 6, "window_grads['log_beta_scales']")
+        elif "log_beta_scales" in given:
+            raise SmalfitError("window_grads['log_beta_scales'] needs shared log_beta_scales of (6,)")
+        r = _lib.WindowRows()
+        r.num_windows = W
+        r.losses, r.g_betas, r.g_log_beta_scales = _ptr(window_losses), _ptr(out.get("betas")), _ptr(out.get("log_beta_scales"))
+        check(fn(self.handle, _stream(), C.byref(a), C.byref(r)), "smalfit_fit_eval_windows")
+        return losses, grads, window_losses, out
+
     def build_fit_args(self, *, betas, log_beta_scales, global_rotation, joint_rotations, trans,
                        target_joints, target_visibility, target_sil, weights, w_temp, window,
                        temporal=True, global_mask=None, rotation_mask=None, halo_prev=None, halo_next=None,

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from .. import config, engine as eng, model_io, runtime
 from ..smal_model.smal_torch import SMAL
+from .epoch import StateKey, WindowPartition
 from .p3d_renderer import Renderer
 from .priors.pose_prior_35 import Prior
 
@@ -67,6 +68,55 @@ class _WindowLoss(torch.autograd.Function):
                 scatter(grads["joint_rotations"], s_j), scatter(grads["trans"], s_t))
 
 
+class _EpochEvaluation:
+    """one smalfit_fit_eval_windows call over the whole sequence; owns its output tensors"""
+
+    def __init__(self, fitter, weights):
+        N = fitter.num_images
+        dev = fitter.device
+        e = fitter._engine(N)
+        ls = fitter.log_beta_scales.detach().contiguous()
+        self.per_frame_ls = ls.dim() == 2
+        # the reference driver swaps in a CPU float tensor after stage 0: one upload per evaluation
+        vis = fitter.target_visibility.to(dev).float().contiguous()
+        self.losses, self.grads, self.rows, self.row_grads = e.fit_eval_windows(
+            betas=fitter.betas.detach().contiguous(), log_beta_scales=ls,
+            global_rotation=fitter.global_rotation.detach().contiguous(), joint_rotations=fitter.joint_rotations.detach().contiguous(),
+            trans=fitter.trans.detach().contiguous(), target_joints=fitter.target_joints.contiguous(), target_visibility=vis,
+            target_sil=fitter.sil_imgs.reshape(N, fitter.image_size, fitter.image_size).contiguous(), weights=weights, w_temp=0.0,
+            window=fitter.batch_size, temporal=False, global_mask=fitter.global_mask.reshape(3).contiguous(),
+            rotation_mask=fitter.rotation_mask.contiguous())
+        self.frame_windows = fitter._frame_windows
+        self.graph = None         # (grad mode and requires_grad flags it was built for, the (W,) totals with their autograd node)
+
+
+class _EpochLoss(torch.autograd.Function):
+    """the (W,) window totals of one epoch evaluation; backward hands every window's gradients out weighted by its upstream
+    gradient: the shared parameters from the per-window rows, the per-frame ones scaled by their frame's window"""
+
+    @staticmethod
+    def forward(ctx, ev, betas, log_beta_scales, global_rotation, joint_rotations, trans):
+        ctx.ev = ev               # a loss returned earlier keeps ITS evaluation, whatever the fitter evaluates later
+        return ev.rows[:, :5].sum(dim=1) + ev.rows[:, 8]      # per window: the terms of forward() (temporal is separate); [8] = joint limits
+
+    @staticmethod
+    def backward(ctx, g):
+        ev, need = ctx.ev, ctx.needs_input_grad
+        gf = g.index_select(0, ev.frame_windows)          # upstream weight of every frame's window
+        out = [None] * 6
+        if need[1]:
+            out[1] = g @ ev.row_grads["betas"]
+        if need[2]:
+            out[2] = ev.grads["log_beta_scales"] * gf[:, None] if ev.per_frame_ls else g @ ev.row_grads["log_beta_scales"]
+        if need[3]:
+            out[3] = ev.grads["global_rotation"] * gf[:, None]
+        if need[4]:
+            out[4] = ev.grads["joint_rotations"] * gf[:, None, None]
+        if need[5]:
+            out[5] = ev.grads["trans"] * gf[:, None]
+        return tuple(out)
+
+
 class _Temporal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fitter, w_temp, global_rotation, joint_rotations, trans):
@@ -86,11 +136,17 @@ class _Temporal(torch.autograd.Function):
 
 class SMALFitter(nn.Module):
     def __init__(self, device, data_batch, batch_size, shape_family, use_unity_prior, model_data=None,
-                 pose_prior_data=None, shape_prior_data=None, enable_joint_limits=False):
+                 pose_prior_data=None, shape_prior_data=None, enable_joint_limits=False, epoch_evaluation=None):
         """model_data / pose_prior_data / shape_prior_data let tests inject the synthetic stand-ins; by default
         everything is read from the paths in smalify_amd.config exactly like the reference (smal_fitter.py:40-74).
-        enable_joint_limits: switch on the w_limit term the reference has commented out (smal_fitter.py:76-79,146-151)."""
+        enable_joint_limits: switch on the w_limit term the reference has commented out (smal_fitter.py:76-79,146-151).
+        epoch_evaluation (None: config.EPOCH_EVALUATION): the caller's epoch loop asks forward() for every window of the sequence
+        between two optimiser steps, as the reference's does -- the sequence is then evaluated ONCE per epoch
+        (smalfit_fit_eval_windows) and every window call is served from it; see forward()."""
         super().__init__()
+        self.epoch_evaluation = bool(config.EPOCH_EVALUATION if epoch_evaluation is None else epoch_evaluation)
+        self.engine_evaluations = 0       # smalfit_fit_eval* calls made by forward()
+        self._epoch = None                # (StateKey, _EpochEvaluation) of the last epoch evaluation
         self.enable_joint_limits = bool(enable_joint_limits)
         self.rgb_imgs, self.sil_imgs, self.target_joints, self.target_visibility = data_batch
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -131,6 +187,8 @@ class SMALFitter(nn.Module):
         self.smal_model = SMAL(dev, shape_family_id=shape_family, model_data=model_data,
                                engine_image_size=self.image_size)
         self.renderer = Renderer(self.image_size, dev, model=self.smal_model.device_model)
+        self._partition = WindowPartition(self.num_images, self.batch_size)
+        self._frame_windows = torch.tensor(self._partition.frame_windows(), device=dev, dtype=torch.long)
 
     def _engine(self, frames):
         e = runtime.get_engine(self.smal_model.device_model, max(frames, self.batch_size), self.image_size)
@@ -148,8 +206,13 @@ class SMALFitter(nn.Module):
         weights = [float(w) for w in weights]
         if not self.enable_joint_limits:        # like the reference: the weight table says 100, the term does not exist
             weights[4] = 0.0
-        total, losses = _WindowLoss.apply(self, list(batch_range), weights, self.betas,
-                                          self.log_beta_scales, self.global_rotation, self.joint_rotations, self.trans)
+        w = self._partition.window_of(batch_range) if self.epoch_evaluation else None
+        if w is not None:
+            total, losses = self._epoch_window(w, weights)
+        else:
+            self.engine_evaluations += 1
+            total, losses = _WindowLoss.apply(self, list(batch_range), weights, self.betas,
+                                              self.log_beta_scales, self.global_rotation, self.joint_rotations, self.trans)
         w_j2d, w_reproj, w_betas, w_pose, w_limit, w_splay = [float(w) for w in weights]
         active = dict(joint=w_j2d > 0, pose=w_pose > 0, splay=w_splay > 0, betas=w_betas > 0, sil_reproj=w_reproj > 0)
         objs = {}
@@ -159,6 +222,23 @@ class SMALFitter(nn.Module):
             if k == "joint" and w_limit > 0 and self.enable_joint_limits:   # the reference's (disabled) term order: joint, limit, pose, ...
                 objs["limit"] = losses[8]
         return total, objs
+
+    def _epoch_window(self, w, weights):
+        """window w's (total, nine terms) from the evaluation of the whole sequence, evaluated again only when something it
+        depended on has changed since: a parameter or a target (replaced, or written in place), a weight"""
+        params = (self.betas, self.log_beta_scales, self.global_rotation, self.joint_rotations, self.trans)
+        tensors = params + (self.target_joints, self.target_visibility, self.sil_imgs, self.global_mask, self.rotation_mask)
+        scalars = tuple(weights) + (self.enable_joint_limits,)
+        if self._epoch is None or not self._epoch[0].matches(tensors, scalars):
+            key = StateKey(tensors, scalars)
+            self.engine_evaluations += 1
+            self._epoch = (key, _EpochEvaluation(self, weights))
+        ev = self._epoch[1]
+        # one autograd node per evaluation -- built again only when what needs a gradient has changed (that changes no value)
+        built_for = (torch.is_grad_enabled(),) + tuple(p.requires_grad for p in params)
+        if ev.graph is None or ev.graph[0] != built_for:
+            ev.graph = (built_for, _EpochLoss.apply(ev, *params))
+        return ev.graph[1][w], ev.rows[w]
 
     def get_temporal(self, w_temp):
         return _Temporal.apply(self, float(w_temp), self.global_rotation, self.joint_rotations, self.trans)
