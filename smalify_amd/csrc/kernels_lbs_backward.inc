@@ -457,7 +457,9 @@ chain_bwd_kernel(ModelDev m, int M, const float* __restrict__ theta, const float
     // requested a pass ahead -- inside a pass the level offsets -> joint -> parent -> child list chase cost more than the
     // arithmetic (19 k cycles of the block's 42 k for 12 passes, profiles/r6_lbs_phase_breakdown.txt).  Passes run deepest level
     // first; the loop stays rolled (straight-line code run once by one wave pays an instruction-cache miss per line: the unrolled
-    // form was slower than the table-driven loop).  The operations and their order are those of the loop below: the same bits.
+    // form was slower than the table-driven loop).  The operations and their order are meant to be those of the loop below; no test
+    // compares the two walks' bits (a tree takes one or the other) -- each is held to the float64 oracle on trees that reach it, this one
+    // with kTreeMaxChildren children per joint and kTreeMaxPass passes too (tests/test_gpu_model_forms.py).
     const int npass = tl.npass;
     const int slot_c = min(slot, 7);
     uint2 sch_n = t_sch[max(npass - 1, 0)][slot_c];
@@ -629,7 +631,7 @@ chain_bwd_kernel(ModelDev m, int M, const float* __restrict__ theta, const float
     }
   }
   for (int i = l; i < 105; i += 256) dJrest[(size_t)n * 105 + i] = dJ[i / 3][i % 3];
-  // rest joints are affine
+  // rest joints are affine.  One lane of a wave per shape direction: NBall <= kMaxModelBetas = 64 (smalfit_plan.h: model_dims_refusal)
   if (dbetaJ) {
     const int w = l >> 6, b = l & 63;
     if (b < m.NBall) {

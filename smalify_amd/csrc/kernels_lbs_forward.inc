@@ -353,7 +353,9 @@ pose_block(const ModelDev& m, const HeadArgs& a, int n, const PendingStep* pend,
     // 16-byte read of the parent's row, three multiply-adds and one write (until then: level offsets -> joint -> parent ->
     // operands, five dependent trips per pass; 8.2 k cycles of the block's 14.5 k, profiles/r6_lbs_phase_breakdown.txt).  The loop
     // stays rolled: one wave running straight-line code once pays an instruction-cache miss per line (the unrolled form of this
-    // walk was slower than the table-driven one).  The same operations in the same order: the same bits.
+    // walk was slower than the table-driven one).  The operations and their order are meant to be those of the table-driven loop below;
+    // no test compares the two walks' bits (a tree takes one or the other, smalfit_plan.h: tree_levels) -- each is held to the float64
+    // oracle on trees that reach it, this one at exactly kTreeMaxPass passes too (tests/test_gpu_model_forms.py).
     const int slot_c = min(l / 12, 7), e = l % 12, r = e >> 2, c = e & 3, cc = min(c, 2);
     const int npass = tl.npass;
     auto fetch = [&](int k, int& ijp, float (&kc)[3]) {

@@ -191,7 +191,7 @@ const char* smalfit_last_error(void) { return g_err.c_str(); }
 int smalfit_model_create(const smalfit_model_desc* d, smalfit_model** out) {
   if (!d || !out) return fail("smalfit_model_create: null argument");
   const int V = d->num_verts, F = d->num_faces, NB = d->num_betas;
-  if (V <= 0 || F <= 0 || NB <= 0) return fail("smalfit_model_create: bad dimensions");
+  if (refused("smalfit_model_create", model_dims_refusal(V, F, NB))) return 1;
   if (!parents_ordered(d->parents, 35)) return fail("smalfit_model_create: parents must satisfy 0 <= parents[i] < i");
   for (int i = 0; i < F * 3; ++i)
     if (d->faces[i] < 0 || d->faces[i] >= V) return fail("smalfit_model_create: face index out of range");
@@ -332,49 +332,7 @@ int smalfit_model_create(const smalfit_model_desc* d, smalfit_model** out) {
   g.vf_off = (const int*)(base + o_vfo); g.vf_idx = (const int*)(base + o_vfi);
   g.scale_idx = (const int*)(base + o_si);
   for (int i = 0; i < 6; ++i) g.landmarks[i] = lms[i];
-  {
-    TreeLevels& tl = g.tree;
-    int depth[35] = {0}, maxd = 0;
-    for (int i = 1; i < 35; ++i) { depth[i] = depth[d->parents[i]] + 1; maxd = std::max(maxd, depth[i]); }
-    tl.nlev = (unsigned char)(maxd + 1);
-    int pos = 0;
-    for (int L = 0; L <= maxd; ++L) {
-      tl.lvl_off[L] = (unsigned char)pos;
-      for (int i = 0; i < 35; ++i) if (depth[i] == L) tl.lvl_joint[pos++] = (unsigned char)i;
-    }
-    for (int L = maxd + 1; L < 36; ++L) tl.lvl_off[L] = (unsigned char)pos;
-    pos = 0;
-    for (int j = 0; j < 35; ++j) {
-      tl.child_off[j] = (unsigned char)pos;
-      for (int c = 34; c >= 1; --c) if (d->parents[c] == j) tl.child_idx[pos++] = (unsigned char)c;
-    }
-    tl.child_off[35] = (unsigned char)pos;
-    // the flat schedule of the walks (see TreeLevels)
-    memset(tl.pass_joint, 255, sizeof(tl.pass_joint));
-    memset(tl.pass_parent, 0, sizeof(tl.pass_parent));
-    memset(tl.pass_nchild, 0, sizeof(tl.pass_nchild));
-    memset(tl.pass_child, 0, sizeof(tl.pass_child));
-    int np = 0;
-    bool fits = true;
-    for (int L = 1; L <= maxd; ++L) {
-      const int j0 = tl.lvl_off[L], nj = tl.lvl_off[L + 1] - j0;
-      for (int base = 0; base < nj; base += 5, ++np) {
-        if (np >= kTreeMaxPass) { fits = false; continue; }
-        for (int s = 0; s < 5 && base + s < nj; ++s) {
-          const int i = tl.lvl_joint[j0 + base + s];
-          tl.pass_joint[np][s] = (unsigned char)i;
-          tl.pass_parent[np][s] = (unsigned char)d->parents[i];
-          const int nc = tl.child_off[i + 1] - tl.child_off[i];
-          if (nc > kTreeMaxChildren) fits = false;
-          tl.pass_nchild[np][s] = (unsigned char)std::min(nc, kTreeMaxChildren);
-          for (int q = 0; q < std::min(nc, kTreeMaxChildren); ++q) tl.pass_child[np][s][q] = tl.child_idx[tl.child_off[i] + q];
-        }
-      }
-    }
-    if (tl.child_off[1] - tl.child_off[0] > 35) fits = false;
-    tl.npass = (unsigned char)std::min(np, kTreeMaxPass);
-    tl.fast = fits ? 1 : 0;
-  }
+  g.tree = tree_levels(d->parents);
   m->V = V; m->Vp = Vp; m->F = F; m->NBall = NB;
   *out = m;
   return 0;
@@ -738,6 +696,7 @@ struct EvalFold {
 static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const EvalFold& fold) {
   if (!e || !a) return fail("smalfit_fit_eval: null argument");
   if (refused("smalfit_fit_eval", fit_args_refusal(a, EngineFacts{e->maxM, e->has_pose_prior, e->shape_dim}))) return 1;
+  if (refused("smalfit_fit_eval", fit_model_refusal(e->model->NBall))) return 1;
   const int M = a->num_frames;
   // where these M frames sit in their sequence: per-window normalisers follow the sequence's windows
   const WinMap win{a->window, a->frame_offset, sequence_frames(a)};
@@ -1352,6 +1311,7 @@ int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, 
   if (iterations <= 0) return fail("smalfit_fit_run: iterations must be positive");
   if (o->step < 0) return fail("smalfit_fit_run: step must be >= 0");
   if (refused("smalfit_fit_run", fit_args_size_refusal(a))) return 1;
+  if (refused("smalfit_fit_run", fit_model_refusal(e->model->NBall))) return 1;   // (before a capture could begin)
   AdamSegments sg;
   if (packed_adam_segments(o, sg)) return 1;
   hipStream_t st = (hipStream_t)stream;

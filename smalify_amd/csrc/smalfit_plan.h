@@ -68,6 +68,100 @@ inline bool parents_ordered(const int* parents, int num_joints) {
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the kinematic tree's schedule
+// ------------------------------------------------------------------------------------------------
+// kinematic tree by depth: joints of one level are independent, so the chain and its adjoint take `nlev` steps
+// (10 for SMAL) instead of 34.  children lists are in DESCENDING joint order: accumulating a parent's adjoint from its
+// children in that order reproduces the summation order of a plain reverse loop over the joints.
+constexpr int kTreeMaxPass = 16, kTreeMaxChildren = 4;
+struct TreeLevels {
+  unsigned char nlev;
+  unsigned char lvl_off[36];     // level L owns lvl_joint[lvl_off[L] .. lvl_off[L+1])
+  unsigned char lvl_joint[35];
+  unsigned char child_off[36];   // joint j owns child_idx[child_off[j] .. child_off[j+1])
+  unsigned char child_idx[35];
+  // The walks as a flat schedule (round 6): pass k handles up to five joints of one level (a wave = 5 joints x 12 lanes), levels in
+  // ascending order.  With it a lane reads its joint / parent / children of EVERY pass before the walk starts (independent loads, one
+  // latency) instead of chasing level offset -> joint -> parent -> child list through LDS inside every pass.  `fast` = the tree fits
+  // (at most kTreeMaxPass passes, kTreeMaxChildren children per joint: SMAL's needs 12 and 4); deeper / bushier trees take the
+  // table-driven loops as before.
+  unsigned char fast, npass;
+  unsigned char pass_joint[kTreeMaxPass][8];    // [pass][slot 0..4] joint, 255 = idle slot
+  unsigned char pass_parent[kTreeMaxPass][8];
+  unsigned char pass_nchild[kTreeMaxPass][8];
+  unsigned char pass_child[kTreeMaxPass][8][kTreeMaxChildren];   // in the order of child_idx (descending joint index)
+};
+// -> the schedule of a tree of 35 joints with 0 <= parents[i] < i (parents_ordered; parents[0] is not read)
+inline TreeLevels tree_levels(const int* parents) {
+  TreeLevels tl;
+  std::memset(&tl, 0, sizeof(tl));
+  int depth[35] = {0}, maxd = 0;
+  for (int i = 1; i < 35; ++i) { depth[i] = depth[parents[i]] + 1; maxd = std::max(maxd, depth[i]); }
+  tl.nlev = (unsigned char)(maxd + 1);
+  int pos = 0;
+  for (int L = 0; L <= maxd; ++L) {
+    tl.lvl_off[L] = (unsigned char)pos;
+    for (int i = 0; i < 35; ++i) if (depth[i] == L) tl.lvl_joint[pos++] = (unsigned char)i;
+  }
+  for (int L = maxd + 1; L < 36; ++L) tl.lvl_off[L] = (unsigned char)pos;
+  pos = 0;
+  for (int j = 0; j < 35; ++j) {
+    tl.child_off[j] = (unsigned char)pos;
+    for (int c = 34; c >= 1; --c) if (parents[c] == j) tl.child_idx[pos++] = (unsigned char)c;
+  }
+  tl.child_off[35] = (unsigned char)pos;
+  // the flat schedule of the walks (see TreeLevels)
+  std::memset(tl.pass_joint, 255, sizeof(tl.pass_joint));
+  int np = 0;
+  bool fits = true;
+  for (int L = 1; L <= maxd; ++L) {
+    const int j0 = tl.lvl_off[L], nj = tl.lvl_off[L + 1] - j0;
+    for (int base = 0; base < nj; base += 5, ++np) {
+      if (np >= kTreeMaxPass) { fits = false; continue; }
+      for (int s = 0; s < 5 && base + s < nj; ++s) {
+        const int i = tl.lvl_joint[j0 + base + s];
+        tl.pass_joint[np][s] = (unsigned char)i;
+        tl.pass_parent[np][s] = (unsigned char)parents[i];
+        const int nc = tl.child_off[i + 1] - tl.child_off[i];
+        if (nc > kTreeMaxChildren) fits = false;
+        tl.pass_nchild[np][s] = (unsigned char)std::min(nc, kTreeMaxChildren);
+        for (int q = 0; q < std::min(nc, kTreeMaxChildren); ++q) tl.pass_child[np][s][q] = tl.child_idx[tl.child_off[i] + q];
+      }
+    }
+  }
+  if (tl.child_off[1] - tl.child_off[0] > 35) fits = false;
+  tl.npass = (unsigned char)std::min(np, kTreeMaxPass);
+  tl.fast = fits ? 1 : 0;
+  return tl;
+}
+// passes the table-driven walks make (five joints of one level each): what npass would be without its cap
+inline int tree_walk_passes(const TreeLevels& tl) {
+  int np = 0;
+  for (int L = 1; L < tl.nlev; ++L) np += (tl.lvl_off[L + 1] - tl.lvl_off[L] + 4) / 5;
+  return np;
+}
+
+// ------------------------------------------------------------------------------------------------
+// smalfit_model_desc: which models are refused, and which the fitter refuses
+// ------------------------------------------------------------------------------------------------
+// chain_bwd_kernel reduces d/d betas through the rest joints with one lane per shape direction of one wave: 64 of them
+constexpr int kMaxModelBetas = 64;
+// the fitter (smalfit_fit_eval and everything built on it) optimises the first 20 shape directions (kPendingNb of kernels_lbs_forward.inc)
+constexpr int kFitBetas = 20;
+// -> why smalfit_model_create refuses a model of these dimensions (the text behind "smalfit_model_create: "), or nullptr
+inline const char* model_dims_refusal(int num_verts, int num_faces, int num_betas) {
+  if (num_verts <= 0 || num_faces <= 0 || num_betas <= 0) return "bad dimensions";
+  static_assert(kMaxModelBetas == 64, "the message below names the limit");
+  if (num_betas > kMaxModelBetas) return "num_betas above 64 is not supported (the rest-joint path of d/d betas reduces 64 shape directions)";
+  return nullptr;
+}
+// -> why the fitter refuses a model of `model_betas` shape directions (the text behind "smalfit_fit_eval: "), or nullptr
+inline const char* fit_model_refusal(int model_betas) {
+  static_assert(kFitBetas == 20, "the message below names the count");
+  return model_betas >= kFitBetas ? nullptr : "the model has fewer than the 20 shape directions the fitter optimises";
+}
+
 // the 3D mesh objective: grids over S target points, V vertices, P face pairs
 struct MeshGrids { int bx, by, bv, bp; };   // chamfer over the points | over the vertices | ring / gather over vertices | face pairs
 inline int mesh_query_blocks(int queries) { return (queries + kMeshQueries - 1) / kMeshQueries; }

@@ -25,7 +25,8 @@ HEAD_PRIORS = {"none": 0, "shared": 1, "per_frame": 2}                # HeadPrio
 class Plan:
     def __init__(self, lib):
         self.lib = lib
-        for name in ("hp_fit_args_refusal", "hp_fit_args_size_refusal", "hp_pack_adam_segments"):
+        for name in ("hp_fit_args_refusal", "hp_fit_args_size_refusal", "hp_pack_adam_segments", "hp_model_dims_refusal",
+                     "hp_fit_model_refusal"):
             getattr(lib, name).restype = C.c_char_p
         lib.hp_mesh_weight.restype = C.c_float
         lib.hp_mesh_weight.argtypes = [C.c_float]
@@ -102,6 +103,35 @@ class Plan:
 
     def parents_ordered(self, parents):
         return bool(self.lib.hp_parents_ordered((C.c_int * len(parents))(*parents), len(parents)))
+
+    def tree_levels(self, parents, tables=False):
+        """the walks' schedule of a tree of 35 joints (smalfit_plan.h: tree_levels): fast, npass, nlev, walk_passes (passes of
+        the table-driven walk: npass without its cap), most_children (of a non-root joint), root_children, max_pass,
+        max_children; with tables=True also the flat schedule, pass_joint / pass_parent / pass_nchild [max_pass][8] and
+        pass_child [max_pass][8][max_children]"""
+        assert len(parents) == 35
+        facts, limits = (C.c_int * 6)(), (C.c_int * 2)()
+        tab = (C.c_int * (16 * 8 * 8))() if tables else None
+        self.lib.hp_tree_levels((C.c_int * 35)(*[int(p) for p in parents]), facts, limits, tab)
+        out = dict(zip(("fast", "npass", "nlev", "walk_passes", "most_children", "root_children"), facts))
+        out["fast"] = bool(out["fast"])
+        out["max_pass"], out["max_children"] = limits
+        if tables:
+            P, K = out["max_pass"], out["max_children"]
+            assert P * 8 * (3 + K) <= len(tab)
+            flat = list(tab)
+            grid = lambda o: [flat[o + k * 8:o + k * 8 + 8] for k in range(P)]  # noqa: E731
+            out["pass_joint"], out["pass_parent"], out["pass_nchild"] = grid(0), grid(P * 8), grid(2 * P * 8)
+            out["pass_child"] = [[flat[3 * P * 8 + (k * 8 + s) * K:3 * P * 8 + (k * 8 + s + 1) * K] for s in range(8)] for k in range(P)]
+        return out
+
+    def model_dims_refusal(self, V, F, NB):
+        why = self.lib.hp_model_dims_refusal(V, F, NB)
+        return why.decode() if why else None
+
+    def fit_model_refusal(self, model_betas):
+        why = self.lib.hp_fit_model_refusal(model_betas)
+        return why.decode() if why else None
 
     def mesh_grids(self, V, S, P):
         """mesh3d_forms.grids's arguments and result"""

@@ -77,6 +77,28 @@ void hp_dbeta_grid(int need_beta, int Vp, int betas_shared, int M, int* out3) {
 }
 int hp_parents_ordered(const int* parents, int n) { return parents_ordered(parents, n); }
 
+// tree_levels of 35 parents -> facts6: fast, npass, nlev, passes of the table-driven walk, most children of a non-root joint,
+// children of the root; [kTreeMaxPass, kTreeMaxChildren] in limits2.  tables (may be null): pass_joint, pass_parent, pass_nchild
+// as [kTreeMaxPass][8] ints each, then pass_child as [kTreeMaxPass][8][kTreeMaxChildren]
+void hp_tree_levels(const int* parents35, int* facts6, int* limits2, int* tables) {
+  const TreeLevels tl = tree_levels(parents35);
+  int most = 0;
+  for (int j = 1; j < 35; ++j) most = std::max(most, tl.child_off[j + 1] - tl.child_off[j]);
+  const int f[6] = {tl.fast, tl.npass, tl.nlev, tree_walk_passes(tl), most, tl.child_off[1] - tl.child_off[0]};
+  for (int i = 0; i < 6; ++i) facts6[i] = f[i];
+  limits2[0] = kTreeMaxPass; limits2[1] = kTreeMaxChildren;
+  if (!tables) return;
+  for (int k = 0; k < kTreeMaxPass; ++k)
+    for (int s = 0; s < 8; ++s) {
+      tables[k * 8 + s] = tl.pass_joint[k][s];
+      tables[(kTreeMaxPass + k) * 8 + s] = tl.pass_parent[k][s];
+      tables[(2 * kTreeMaxPass + k) * 8 + s] = tl.pass_nchild[k][s];
+      for (int q = 0; q < kTreeMaxChildren; ++q) tables[3 * kTreeMaxPass * 8 + (k * 8 + s) * kTreeMaxChildren + q] = tl.pass_child[k][s][q];
+    }
+}
+const char* hp_model_dims_refusal(int V, int F, int NB) { return model_dims_refusal(V, F, NB); }
+const char* hp_fit_model_refusal(int model_betas) { return fit_model_refusal(model_betas); }
+
 void hp_mesh_grids(int S, int V, int P, int* out4) {
   const MeshGrids g = mesh_grids(S, V, P);
   out4[0] = g.bx; out4[1] = g.by; out4[2] = g.bv; out4[3] = g.bp;

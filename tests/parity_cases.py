@@ -153,9 +153,10 @@ def case_render(M=2, S=64, z=1.45, seed=11, shrink=1.0):
     return out
 
 
-def make_problem_cpu(M, S, window, seed=21, z=1.45, with_sil=True):
-    """Synthetic fitting problem: targets from a ground-truth pose, evaluation at a perturbed pose (oracle side only)."""
-    md, om = get_oracle_model()
+def make_problem_cpu(M, S, window, seed=21, z=1.45, with_sil=True, model=None):
+    """Synthetic fitting problem: targets from a ground-truth pose, evaluation at a perturbed pose (oracle side only).
+    model: (model description, oracle model) of another model than the stand-in (tests/model_forms.py)"""
+    md, om = get_oracle_model() if model is None else model
     pp = synthetic.synthetic_pose_prior()
     sp = synthetic.synthetic_shape_prior()
     gt = random_pose(M, seed, z=z)

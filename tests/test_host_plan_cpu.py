@@ -113,3 +113,19 @@ def test_sequence_frames_and_parents(plan):
     assert plan.parents_ordered(ok) and plan.parents_ordered([7] + ok[1:])        # (the root's entry is not read)
     for i, bad in ((1, 1), (5, 5), (34, 40), (12, -1)):
         assert not plan.parents_ordered(ok[:i] + [bad] + ok[i + 1:])
+
+
+def test_model_refusals(plan):
+    """smalfit_model_create refuses what chain_bwd_kernel cannot reduce (more than 64 shape directions: one lane of one wave
+    each), the fitter a model with fewer than the 20 directions it optimises; the texts name the limits"""
+    assert plan.model_dims_refusal(3889, 7774, 41) is None and plan.model_dims_refusal(3056, 1, 1) is None
+    assert plan.model_dims_refusal(3889, 7774, 64) is None
+    for dims in ((0, 7774, 41), (3889, 0, 41), (3889, 7774, 0), (-1, 7774, 41)):
+        assert plan.model_dims_refusal(*dims) == "bad dimensions"
+    for nb in (65, 66, 128, 300):
+        assert plan.model_dims_refusal(3889, 7774, nb) == "num_betas above 64 is not supported (the rest-joint path of d/d betas reduces 64 shape directions)"
+    assert plan.model_dims_refusal(0, 0, 65) == "bad dimensions"                       # the first fault is reported
+    for nb in (20, 21, 41, 64):
+        assert plan.fit_model_refusal(nb) is None
+    for nb in (1, 12, 19):
+        assert plan.fit_model_refusal(nb) == "the model has fewer than the 20 shape directions the fitter optimises"
