@@ -19,7 +19,7 @@ vertex_bwd_kernel(ModelDev m, int M, const float* __restrict__ proj, const float
   // has its own L2): with one frame per workgroup and a 1-D grid, frame n runs on XCD n % 8 -- where raster_bwd_kernel left the
   // frame's face adjoints and where lbs_bwd_mid_kernel's dA blocks and chain_bwd_kernel's frame block will read what this kernel writes.
   int n, vblock;
-  xcd_block(Vp / 256, n, vblock);
+  xcd_block(vertex_blocks(Vp), n, vblock);
   if (n >= M) return;
   const int v = vblock * 256 + threadIdx.x;
   // Round 6: everything whose address depends on the vertex alone -- the range of its incident (face, corner) list and the list's
@@ -143,8 +143,7 @@ dA_block(const ModelDev& m, int j, int n, const float* __restrict__ dvert, const
     dA[((size_t)n * 35 + j) * 12 + threadIdx.x] = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
 }
 
-constexpr int kAsmElem = 4, kAsmLoss = 16;   // assemble_kernel: blocks for element-wise gradients / loss partial sums
-constexpr int kAsmRows = 4;                  // blocks of frame_loss_rows_kernel
+// (kAsmElem, kAsmLoss, kAsmRows: the block roles of assemble_kernel and frame_loss_rows_kernel, smalfit_plan.h)
 
 // K9: shape-blend adjoint.  shared betas: dbeta_part[block][b] = sum_col sd[b][col] * sum_n dvp[n][col]
 //     per-frame betas (blockIdx.y = frame): no sum over frames.
@@ -199,8 +198,7 @@ dbeta_block(const ModelDev& m, int M, int nb, int shared, int bx, int by, int bz
 // `posedirs` is read once per evaluation instead of once per tile (round 2: 119 MB counted for a 14.3 MB basis) -- and the
 // column range is a quarter as long instead (24 splits instead of 6: the same number of blocks, the same number of matrix
 // instructions per wave, a quarter of the B loads and half the dependent load batches).
-constexpr int PBM_SPLITS = 24, PBM_U = 2, PBM_TILES = 4;
-static_assert(PBM_SPLITS % 8 == 0, "the blocks of a column split are placed on one XCD (ids in chunks of 8 splits)");
+constexpr int PBM_U = 2;   // (PBM_SPLITS, PBM_TILES: smalfit_plan.h)
 __device__ __forceinline__ void
 poseblend_bwd_mfma_block(const ModelDev& m, int M, int tchunk, int kpair, int split, const float* __restrict__ dvp,
                          float* __restrict__ dpf_part /*[PBM_SPLITS][M][308]*/, float (*red)[8][64]) {
@@ -278,9 +276,7 @@ poseblend_bwd_mfma_block(const ModelDev& m, int M, int tchunk, int kpair, int sp
 // laid out as chunks of 8 splits x 10 feature pairs with the split in the low 3 bits, so they share an XCD and that slice of
 // dvp is fetched once; every element of `posedirs` (B) is fetched by exactly one block per chunk of PBM_TILES frame tiles.
 // Speed only: results never depend on the placement.
-__host__ __device__ inline int mid_pb_ids(int M) { return 10 * PBM_SPLITS * (((M + 15) / 16 + PBM_TILES - 1) / PBM_TILES); }
-__host__ __device__ inline int mid_da_ids(int M) { return xcd_grid(35, M); }       // dA blocks: frame n on XCD n % 8 (see vertex_bwd_kernel)
-__host__ __device__ inline int mid_grid(int M, int nPB) { return (nPB ? mid_pb_ids(M) : 0) + mid_da_ids(M); }
+// (mid_pb_ids, mid_da_ids, mid_grid: smalfit_plan.h)
 __global__ void __launch_bounds__(256, 4)      // <= 128 registers (vector + accumulation): four workgroups per CU for the 35 M dA blocks
 lbs_bwd_mid_kernel(ModelDev m, int M, int nPB, const float* __restrict__ dvert, const float* __restrict__ vposed,
                    const float* __restrict__ dvp, float* __restrict__ dA, float* __restrict__ dpf_part) {
@@ -674,7 +670,7 @@ assemble_kernel(AssembleArgs a, AssembleExt x) {
   const int t = threadIdx.x;
   PHASE_MARK(pa0);
   const int M = a.M;
-  const int nbs = a.betas_shared ? 1 : M;
+  const int nbs = asm_shape_sets(a.betas_shared, M);
   int role = blockIdx.x;
   const int ph_role = (role < nbs) ? PH_ASM_BETA : PH_ASM_ELEM;
   if (role < nbs) {

@@ -639,9 +639,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // wave w takes k-steps [20 w, 20 w + 20) -- ONE batch of operand loads, 60 matrix instructions -- the four partial tiles meet in LDS
 // and are added in wave order (fixed: deterministic), and wave w finishes frame 4 (lane >> 4) + w of its lanes' vertices: one
 // (vertex, frame) pair per lane for the skinning instead of four.  Four times the workgroups, a quarter of the chain each.
-constexpr int kSkinGroups = 2;                     // 16-vertex groups per workgroup (4 waves each): they share the staged transforms of the 16 frames
-constexpr int kSkinVerts = 16 * kSkinGroups;       // vertices per workgroup of skin_mfma_kernel
-constexpr int kSkinThreads = 256 * kSkinGroups;
+// (kSkinGroups, kSkinVerts, kSkinThreads: smalfit_plan.h, which sizes the launch by them)
 constexpr int kSkinStage = (16 * 105 + kSkinThreads - 1) / kSkinThreads;   // float4 words of the transforms a thread stages
 __global__ void __launch_bounds__(kSkinThreads)
 skin_mfma_split_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_shaped, int vs_stride /*0 | 3*Vp*/,

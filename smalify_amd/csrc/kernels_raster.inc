@@ -85,11 +85,9 @@ constexpr int kMaskRounds = 64;           // rounds (of 16 pixels) a mask covers
 constexpr unsigned char kMaskList = 254;  // pcount: the face's 128 bytes hold the 16 masks
 constexpr unsigned char kNoList = 255;    // pcount: walk the whole box
 constexpr float kBoxSlack = 1.0f / 64.0f; // pixels added to each side of a face's pixel box (rounding guard)
-constexpr int kRectFaces = 8;             // faces per entry of the union-box index
-constexpr int kSelGroups = 16;            // ticket counters per XCD of the selection kernel (one per group of its workgroups)
+// (kRectFaces, kSelGroups, kSweepFaces and the other constants the launches are sized by: smalfit_plan.h)
 constexpr int kTicketBase = 64, kTicketStride = 16;   // in the queue-counter array: one counter per 64-byte line
 constexpr int kQCountInts = kTicketBase + 8 * kSelGroups * kTicketStride;
-constexpr int kSweepFaces = 32;           // faces per sweep block
 // LDS accumulator window edge (pixels); outside: global atomics.  Round 6 (was 32): see the zeroing loop of the sweep; 40 with 64-entry
 // lists measured +4.1 % on the crop-filling scene but -0.7 % on the headline one, 36 with full lists +3.1 % / -0.3 %
 // (profiles/r6_ab_lists_window.txt)
@@ -121,8 +119,7 @@ struct SilTarget {
 // face records one kernel writes are read back through HBM by the next (a 2-3 us dependent load at the head of every
 // block).  These kernels use a 1-D grid instead and give frame n to XCD n % 8 in all of them: producer and consumer
 // share an L2.  Only speed depends on the placement (HIP promises none); results never do.
-//   grid.x = xcd_grid(blocks_per_frame, M);   xcd_block(blocks_per_frame, n, bx) -> frame n (may be >= M: exit), block bx
-__host__ __device__ inline int xcd_grid(int blocks_per_frame, int M) { return blocks_per_frame * ((M + 7) / 8) * 8; }
+//   grid.x = xcd_grid(blocks_per_frame, M) of smalfit_plan.h;   xcd_block(blocks_per_frame, n, bx) -> frame n (may be >= M: exit), block bx
 __device__ __forceinline__ void xcd_block_of(int b /*linear workgroup id; b % 8 must be the workgroup's blockIdx.x % 8*/, int blocks_per_frame, int& n, int& bx) {
   const int xcd = b & 7, slot = b >> 3;
   n = (slot / blocks_per_frame) * 8 + xcd;
@@ -199,7 +196,7 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
                  posed joints (joints_block) -- independent of the boxes, latency-bound, and otherwise a launch of its own*/) {
   // grid: [frame riders, a multiple of 8] [face workgroups, frame n on XCD n % 8] [joint riders]  (the joint riders are short:
   // moving them in front of the face workgroups, as the resolve kernel's loss riders were, measured 0.4 % slower)
-  const int nfr = ((M + 7) / 8) * 8;
+  const int nfr = box_frame_blocks(M);
   const int Vp = m.Vp;
   if ((int)blockIdx.x < nfr) {
     // One workgroup per frame, first in the grid: the frame's reference depth and active pixel region.  (Until round 3 this was
@@ -246,15 +243,15 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
     }
     return;
   }
-  const int nbb = xcd_grid((m.F + 255) / 256, M);
+  const int nbb = box_face_blocks(m.F, M);
   if ((int)blockIdx.x >= nfr + nbb) {           // only launched with joints_out
     __shared__ float jred[16];
     const int k = (int)blockIdx.x - nfr - nbb;
-    joints_block(m, jverts, joints_out, k % 41, k / 41, jred);
+    joints_block(m, jverts, joints_out, k % kJointBlocks, k / kJointBlocks, jred);
     return;
   }
   int n, bxi;
-  xcd_block_of((int)blockIdx.x - nfr, (m.F + 255) / 256, n, bxi);
+  xcd_block_of((int)blockIdx.x - nfr, box_blocks_per_frame(m.F), n, bxi);
   if (n >= M) return;
   __shared__ __attribute__((aligned(16))) float4 recs[256][kRecVecs];
   const int f = bxi * 256 + threadIdx.x;
@@ -313,7 +310,7 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
     y0 = min(y0, __shfl_xor(y0, o, kRectFaces)); y1 = max(y1, __shfl_xor(y1, o, kRectFaces));
   }
   if ((threadIdx.x & (kRectFaces - 1)) == 0 && f < m.F)
-    brect[(size_t)n * ((m.F + kRectFaces - 1) / kRectFaces) + f / kRectFaces] = make_int4(x0, x1, y0, y1);
+    brect[(size_t)n * rect_count(m.F) + f / kRectFaces] = make_int4(x0, x1, y0, y1);
 }
 
 // 5b: sweep.  Each pixel carries two cached depth bounds lo <= hi from the last exact selection (zband; +inf
@@ -344,13 +341,13 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
                 <= 160 * 1024 / 8, "eight sweep workgroups per CU (160 KB of LDS)");
   const int t = threadIdx.x;
   int n, bxi;
-  xcd_block((F + kSweepFaces - 1) / kSweepFaces, n, bxi);
+  xcd_block(sweep_blocks_per_frame(F), n, bxi);
   if (n >= M) return;
   const int f0 = bxi * kSweepFaces;
   SMALFIT_WORK(const unsigned long long ws_t0 = __builtin_amdgcn_s_memtime();)
   int rect[4] = {0x7fff, -1, 0x7fff, -1};                 // x0, x1, y0, y1 (uniform)
   {
-    const int nrect = (F + kRectFaces - 1) / kRectFaces;
+    const int nrect = rect_count(F);
     const int4* br = brect + (size_t)n * nrect + (size_t)bxi * (kSweepFaces / kRectFaces);
 #pragma unroll
     for (int u = 0; u < kSweepFaces / kRectFaces; ++u) {
@@ -501,7 +498,7 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
       const int2 bx = boxes[k2];
       const int npx2 = ((bx.x >> 16) - (bx.x & 0xffff) + 1) * ((bx.y >> 16) - (bx.y & 0xffff) + 1);
       int n2, bx2;
-      xcd_block((F + kSweepFaces - 1) / kSweepFaces, n2, bx2);
+      xcd_block(sweep_blocks_per_frame(F), n2, bx2);
       const size_t fi = (size_t)n2 * F + bx2 * kSweepFaces + k2;
       // one format for the wave's four faces (= the four faces of one backward wave): lists when every one of them has one
       const bool has_list = npx2 <= 256 && cnt <= kListLds;
@@ -566,7 +563,7 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
 // sum while its pixels stay in one frame (the queues are roughly frame-ordered) and sends one atomic per change of frame.
 // Counters sit 256 bytes apart (different memory channels); frame_loss_rows_kernel reads and clears them.  The <false>
 // instantiations are the kernels as they were: without per-frame rows nothing here costs a register or an instruction.
-constexpr int kFrameLossStride = 32;             // unsigned long longs between two frames' counters
+// (kFrameLossStride, unsigned long longs between two frames' counters: smalfit_plan.h)
 struct FrameLoss { long long acc; int n; };
 __device__ __forceinline__ void frame_loss_flush(unsigned long long* floss, FrameLoss& f) {
   if (f.acc) atomicAdd(floss + (size_t)f.n * kFrameLossStride, (unsigned long long)f.acc);
@@ -592,9 +589,7 @@ __device__ __forceinline__ float alpha_from_log_sum(unsigned long long sum) {
 // depth tie at the cut -- raster_select_kernel redoes the pixel from scratch and refreshes its bounds.
 // raster_resolve_kernel is thread-per-pixel: it finishes the pixels that need no sorting and appends the others to
 // the band queue or the select queue (one global atomic per block and queue).
-constexpr int kResSub = 2;                       // a resolve workgroup takes (16 kResSub)^2 pixels, kResSub^2 per thread: the launch is
-                                                  // bound by the number of workgroups, not by bytes
-constexpr int kResEdge = 16 * kResSub;
+// (kResSub, kResEdge -- a resolve workgroup takes (16 kResSub)^2 pixels, kResSub^2 per thread -- and the grid's layout: smalfit_plan.h)
 __global__ void __launch_bounds__(256)
 raster_resolve_kernel(int S, int M, WinMap win, float w_sil, unsigned long long* __restrict__ gacc,
                       unsigned* __restrict__ bcnt, const int* __restrict__ frect, const float2* __restrict__ zband,
@@ -606,7 +601,7 @@ raster_resolve_kernel(int S, int M, WinMap win, float w_sil, unsigned long long*
   // the riders come FIRST in the grid (round 4: at its end they were dispatched after the last pixel workgroup, and their chain of
   // dependent latencies -- ~10 us -- was the tail of the launch); their count is padded to a multiple of 8 so that the pixel
   // workgroups keep their frame -> XCD placement
-  const int nlf = loss_frames > 0 ? ((loss_frames + 7) / 8) * 8 : 0;
+  const int nlf = resolve_loss_blocks(loss_frames);
   if ((int)blockIdx.x < nlf) {
     if ((int)blockIdx.x < loss_frames) loss_block(la, (int)blockIdx.x);
     return;
@@ -617,7 +612,7 @@ raster_resolve_kernel(int S, int M, WinMap win, float w_sil, unsigned long long*
   constexpr int R2 = kResSub * kResSub;
   constexpr unsigned long long kSumMask = (1ull << kCountShift) - 1ull;
   const float kInf = __int_as_float(0x7f800000);
-  const int TX = (S + kResEdge - 1) / kResEdge;
+  const int TX = resolve_tiles_x(S);
   int n, bxi;
   xcd_block_of((int)blockIdx.x - nlf, TX * TX, n, bxi);
   if (n >= M) return;
@@ -768,7 +763,6 @@ constexpr int kBandNarrowUnroll = 4, kBandWideUnroll = 1;
 // pixel's bounds.  (Round 3: a band holds 16-30 entries in the steady state, so a half-wave per pixel left half its lanes
 // idle; with 16 lanes per pixel twice as many pixels are in flight per wave -- the kernel is bound by the chain of
 // dependent loads per pixel, not by arithmetic.)
-constexpr int kBandBlocks = 1536;
 // the band work of 256-thread workgroup `bi` of `nblocks`.  zs: 16 x 64 floats of LDS.  A pixel whose band cannot decide (a
 // depth tie at the cut) is appended to the selection queue.  Returns the lane's loss partial.
 template <bool kFrameLoss>
@@ -945,7 +939,6 @@ constexpr int kHitCap = 1024;             // union boxes containing a pixel kept
 constexpr int kCoverCap = 1024;
 
 constexpr int kSelSlots = 2;              // rounds of face records in flight per wave while a pixel's covering faces are evaluated (4 measured the same as 2, with 14 more VGPRs)
-constexpr int kSelWaves = 2;              // waves per select block: 11 KB of LDS per wave -> 7 blocks (14 waves) per CU
 
 // one queued pixel, by one wave (see the kernel below): the exact K nearest from scratch.  Returns (lane 0) the pixel's weighted
 // |sil - target| in 2^-40 fixed point.  L: this wave's LDS (histogram, candidates, cover list).
@@ -974,7 +967,7 @@ __device__ __forceinline__ long long select_pixel(const SelCtx& c, const SelLds&
   const int lane = threadIdx.x & 63;
   const int F = c.F, S = c.S, M = c.M;
   (void)M;
-  const int nrect = (F + kRectFaces - 1) / kRectFaces;
+  const int nrect = rect_count(F);
   const float inv_s = 1.0f / (float)S;
   const int npix = S * S;
   long long loss_fp = 0;
@@ -1382,11 +1375,9 @@ __global__ void gpix_from_dsil_kernel(size_t total, const float* __restrict__ si
 
 // 5e: backward, face-parallel gather (deterministic, no atomics).  16 lanes per face walk the face's pixel box
 // row-major like the forward sweep; d(signed dist^2)/d(vertex) flows through the nearest edge only.
-constexpr int kBwdLanes = 16;             // lanes per face of the backward gather
 static_assert(kBwdLanes == 16, "mask lists are laid out for 16 lanes per face");
 // faces per workgroup of the backward gather (16 lanes each).  One wave per workgroup measured best (4 / 8 / 16 / 32 / 64 faces:
 // 90 / 92 / 93 / 100 / 111 us): a wave that is done frees its slot at once instead of waiting for its block mates
-constexpr int kBwdFaces = 4;
 static_assert(kSweepFaces % 16 == 0 && kBwdFaces * kBwdLanes == 64,
               "a sweep round is 16 faces of 16 lanes, and the four faces of a sweep wave are the four faces of a backward wave");
 // kUnclampedT (smalfit_engine_set_option SMALFIT_OPT_UNCLAMPED_EDGE_T; SURVEY App. B, last row): the adjoint of the point-segment
@@ -1400,7 +1391,7 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
                   const unsigned char* __restrict__ plist /*[M][F][kListCap]*/, const unsigned char* __restrict__ pcount /*[M][F]*/,
                   float* __restrict__ dface /*[M][F][6]*/) {
   int n, bxi;
-  xcd_block((F + kBwdFaces - 1) / kBwdFaces, n, bxi);
+  xcd_block(raster_bwd_blocks_per_frame(F), n, bxi);
   const bool frame_ok = n < M;
   if (!frame_ok) n = 0;
   const int f = frame_ok ? bxi * kBwdFaces + ((int)threadIdx.x / kBwdLanes) : F;

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "smalfit_math.h"
-#include "smalfit_plan.h"   // TreeLevels
+#include "smalfit_plan.h"   // TreeLevels, WinMap, the constants the launches are sized by
 
 #define SMALFIT_STATUS_BIN_OVERFLOW 1   // a frame's candidate-list pool overflowed
 
@@ -36,17 +36,6 @@ struct ModelDev {
   const int* scale_idx;   // [105] log-scale index per (joint, axis) or -1
   int landmarks[6];
   TreeLevels tree;
-};
-
-// Where the M frames of an evaluation sit in their sequence: frames are grouped into consecutive windows of `window`
-// frames counted from the START OF THE SEQUENCE (optimize_to_joints.py:119-120, the last window may be ragged), and the
-// reference's per-window normalisers 1/(B 50), 1/(B 105), 1/(B S^2) (smal_fitter.py:144,157,173) use the size B of the
-// window a frame belongs to.  An evaluation may hold any contiguous part of the sequence -- a whole sequence
-// (offset 0, total M), a shard of it, or a single frame of an 8-frame window (one frame per GPU).
-struct WinMap {
-  int window;   // WINDOW_SIZE
-  int offset;   // index of local frame 0 in the sequence
-  int total;    // frames in the whole sequence
 };
 
 struct LossArgs {

@@ -1,7 +1,7 @@
 // Host side of libsmalfit.so: model upload, workspace carving, kernel sequencing, C-ABI.
-// Included at the end of smalfit_kernels.hip (same translation unit as the kernels).  Every choice between launches, every grid
-// that depends on the problem's size and every refusal of an argument block is a function of smalfit_plan.h; here are the
-// pointers and the launches.
+// Included at the end of smalfit_kernels.hip (same translation unit as the kernels).  Every choice between launches (plan_eval
+// for an evaluation), every grid that depends on the problem's size and every refusal of an argument is a function of
+// smalfit_plan.h; here are the pointers and the launches.  (Errors of the runtime -- allocations, copies, launches -- are worded here.)
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -15,8 +15,6 @@ namespace smalfit {
 
 static thread_local std::string g_err;
 static_assert(kHeadPriorFrames == kPriorFrames, "smalfit_plan.h counts the prior blocks of lbs_head_images_kernel");
-static constexpr int kSelectBlocks = 1792;   // persistent grid of raster_select_kernel: 7 resident 2-wave blocks x 256 CUs
-static_assert(kSelectBlocks % (8 * kSelGroups) == 0, "every ticket group of every XCD needs the same number of selection workgroups (a group without one would leave its pixels undone)");
 #ifdef SMALFIT_DEV_PROBES
 static int g_dbg = 0;             // developer builds only (tools/build_variant.sh ... -DSMALFIT_DEV_PROBES): smalfit_debug_set
 #else
@@ -145,7 +143,7 @@ namespace smalfit {
 // the backward gather in the variant the engine's options select
 static void launch_raster_bwd(smalfit_engine* e, hipStream_t st, int M) {
   const ModelDev& m = e->model->dev;
-  const unsigned grid = (unsigned)xcd_grid((m.F + kBwdFaces - 1) / kBwdFaces, M), block = kBwdLanes * kBwdFaces;
+  const unsigned grid = (unsigned)raster_bwd_grid(m.F, M), block = kBwdLanes * kBwdFaces;
   if (e->unclamped_edge_t)
     raster_bwd_kernel<true><<<grid, block, 0, st>>>(m.F, M, e->S, e->frec, e->fbox, e->zc, e->gz, e->plist, e->pcount, e->dface);
   else
@@ -189,15 +187,15 @@ const char* smalfit_last_error(void) { return g_err.c_str(); }
 // model
 // ------------------------------------------------------------------------------------------------
 int smalfit_model_create(const smalfit_model_desc* d, smalfit_model** out) {
-  if (!d || !out) return fail("smalfit_model_create: null argument");
+  if (refused("smalfit_model_create", null_argument_refusal(d && out))) return 1;
   const int V = d->num_verts, F = d->num_faces, NB = d->num_betas;
   if (refused("smalfit_model_create", model_dims_refusal(V, F, NB))) return 1;
-  if (!parents_ordered(d->parents, 35)) return fail("smalfit_model_create: parents must satisfy 0 <= parents[i] < i");
+  if (!parents_ordered(d->parents, 35)) return refused("smalfit_model_create", "parents must satisfy 0 <= parents[i] < i");
   for (int i = 0; i < F * 3; ++i)
-    if (d->faces[i] < 0 || d->faces[i] >= V) return fail("smalfit_model_create: face index out of range");
+    if (d->faces[i] < 0 || d->faces[i] >= V) return refused("smalfit_model_create", "face index out of range");
   const int* lms = kDefaultLandmarks;
   for (int i = 0; i < 6; ++i)
-    if (lms[i] >= V) return fail("smalfit_model_create: model has fewer vertices than the SMAL landmark ids");
+    if (lms[i] >= V) return refused("smalfit_model_create", "model has fewer vertices than the SMAL landmark ids");
   const int Vp = padded_verts(V);
   Blob b;
   // planar bases
@@ -348,9 +346,7 @@ void smalfit_model_destroy(smalfit_model* m) {
 // engine
 // ------------------------------------------------------------------------------------------------
 int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, smalfit_engine** out) {
-  if (!model || !out || max_frames <= 0 || image_size <= 0) return fail("smalfit_engine_create: bad argument");
-  static_assert(kMaxImageSize == 1024, "the message below names the limit");
-  if (image_size > kMaxImageSize) return fail("smalfit_engine_create: image_size above 1024 is not supported (float32 pixel walk, see kernels_raster.inc)");
+  if (refused("smalfit_engine_create", engine_create_refusal(model && out, max_frames, image_size))) return 1;
   smalfit_engine* e = new smalfit_engine();
   e->model = model;
   e->maxM = max_frames;
@@ -358,8 +354,8 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   e->S = image_size;
   e->Tx = (image_size + 15) / 16;
   e->T = e->Tx * e->Tx;
-  e->nrb = ((image_size + kResEdge - 1) / kResEdge) * ((image_size + kResEdge - 1) / kResEdge);   // resolve tiles per frame
-  e->nvt = model->Vp / 256;
+  e->nrb = resolve_tiles(image_size);   // per frame
+  e->nvt = vertex_blocks(model->Vp);
   e->nblk_beta = nblk_beta(model->Vp);
   const size_t M = max_frames, Vp = model->Vp, F = model->F, S = image_size, T = e->T;
   size_t off = 0;
@@ -381,7 +377,7 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   CARVE(joints, M * 123, float);
   CARVE(fbox, M * F, int2);
   CARVE(frec, M * F * kRecVecs, float4);
-  CARVE(brect, M * ((F + kRectFaces - 1) / kRectFaces), int4);
+  CARVE(brect, M * rect_count(model->F), int4);
   CARVE(plist, M * F * kListCap, unsigned char);
   CARVE(pcount, M * F, unsigned char);
   CARVE(gacc, M * S * S, unsigned long long);
@@ -391,7 +387,7 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   CARVE(frect, M * 4, int);
   CARVE(queue, M * S * S, int);
   CARVE(bqueue, M * S * S, int);
-  CARVE(qloss, kSelectBlocks + kBandBlocks, long long);
+  CARVE(qloss, kQueueLossBlocks, long long);
   CARVE(status, 8, int);
   CARVE(gz, M * S * S, float2);
   CARVE(silbuf, M * S * S, float);
@@ -464,7 +460,7 @@ void smalfit_engine_destroy(smalfit_engine* e) {
 }
 
 int smalfit_engine_status(smalfit_engine* e, void* stream, int* bits) {
-  if (!e || !bits) return fail("smalfit_engine_status: null argument");
+  if (refused("smalfit_engine_status", null_argument_refusal(e && bits))) return 1;
   hipStream_t st = (hipStream_t)stream;
   HIP_OK(hipStreamSynchronize(st));
   HIP_OK(hipMemcpy(bits, e->status, sizeof(int), hipMemcpyDeviceToHost));
@@ -473,13 +469,13 @@ int smalfit_engine_status(smalfit_engine* e, void* stream, int* bits) {
 }
 
 int smalfit_engine_reset_raster_cache(smalfit_engine* e, void* stream) {
-  if (!e) return fail("smalfit_engine_reset_raster_cache: null argument");
+  if (refused("smalfit_engine_reset_raster_cache", null_argument_refusal(e != nullptr))) return 1;
   HIP_OK(hipMemsetD32Async((hipDeviceptr_t)e->zband, 0x7f800000, (size_t)e->maxM * e->S * e->S * 2, (hipStream_t)stream));
   return 0;
 }
 
 int smalfit_engine_set_pose_prior(smalfit_engine* e, const float* prec, const float* mean, const float* mask) {
-  if (!e || !prec || !mean || !mask) return fail("smalfit_engine_set_pose_prior: null argument");
+  if (refused("smalfit_engine_set_pose_prior", null_argument_refusal(e && prec && mean && mask))) return 1;
   HIP_OK(hipMemcpy(e->pose_prec, prec, 105 * 105 * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(e->pose_mean, mean, 105 * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(e->pose_mask, mask, 105 * 4, hipMemcpyHostToDevice));
@@ -489,9 +485,8 @@ int smalfit_engine_set_pose_prior(smalfit_engine* e, const float* prec, const fl
 }
 
 int smalfit_engine_set_joint_limits(smalfit_engine* e, const float* min_values, const float* max_values) {
-  if (!e || !min_values || !max_values) return fail("smalfit_engine_set_joint_limits: null argument");
-  for (int i = 0; i < 102; ++i)
-    if (!(min_values[i] <= max_values[i])) return fail("smalfit_engine_set_joint_limits: min must not exceed max");
+  if (refused("smalfit_engine_set_joint_limits", null_argument_refusal(e && min_values && max_values))) return 1;
+  if (refused("smalfit_engine_set_joint_limits", joint_limits_refusal(min_values, max_values))) return 1;
   HIP_OK(hipMemcpy(e->lim_min, min_values, 102 * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(e->lim_max, max_values, 102 * 4, hipMemcpyHostToDevice));
   e->has_joint_limits = true;
@@ -500,28 +495,22 @@ int smalfit_engine_set_joint_limits(smalfit_engine* e, const float* min_values, 
 }
 
 int smalfit_engine_clear_joint_limits(smalfit_engine* e) {
-  if (!e) return fail("smalfit_engine_clear_joint_limits: null argument");
+  if (refused("smalfit_engine_clear_joint_limits", null_argument_refusal(e != nullptr))) return 1;
   e->has_joint_limits = false;
   e->config_epoch++;
   return 0;
 }
 
 int smalfit_engine_set_option(smalfit_engine* e, int option, int value) {
-  if (!e) return fail("smalfit_engine_set_option: null argument");
-  switch (option) {
-    case SMALFIT_OPT_UNCLAMPED_EDGE_T:
-      if (value != 0 && value != 1) return fail("smalfit_engine_set_option: SMALFIT_OPT_UNCLAMPED_EDGE_T takes 0 or 1");
-      e->unclamped_edge_t = value != 0;
-      break;
-    default:
-      return fail("smalfit_engine_set_option: unknown option");
-  }
+  if (refused("smalfit_engine_set_option", null_argument_refusal(e != nullptr))) return 1;
+  if (refused("smalfit_engine_set_option", option_refusal(option, value))) return 1;
+  if (option == SMALFIT_OPT_UNCLAMPED_EDGE_T) e->unclamped_edge_t = value != 0;
   e->config_epoch++;
   return 0;
 }
 
 int smalfit_engine_set_shape_prior(smalfit_engine* e, const float* prec, const float* mean, int dim) {
-  if (!e || !prec || !mean || dim <= 0 || dim > 26) return fail("smalfit_engine_set_shape_prior: bad argument (dim must be 1..26)");
+  if (refused("smalfit_engine_set_shape_prior", shape_prior_refusal(e && prec && mean, dim))) return 1;
   HIP_OK(hipMemcpy(e->shape_prec, prec, (size_t)dim * dim * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(e->shape_mean, mean, (size_t)dim * 4, hipMemcpyHostToDevice));
   e->shape_dim = dim;
@@ -537,17 +526,17 @@ int smalfit_engine_set_shape_prior(smalfit_engine* e, const float* prec, const f
 namespace smalfit {
 
 // shape -> pose -> skin (+ joints).  theta must already be in e->theta.
-// optional extras of the head launch: build theta from the fitter's parameters, evaluate the shape prior
+// optional extras of the head launch: build theta from the fitter's parameters, evaluate the shape prior (as EvalPlan says)
 struct HeadExtras {
   const float *grot = nullptr, *jrot = nullptr, *gmask = nullptr, *rmask = nullptr;
-  const float *prior_prec = nullptr, *prior_mean = nullptr;
+  HeadKernel head = HeadKernel::Plain;    // EvalPlan::head
+  HeadPrior prior = HeadPrior::None;      // EvalPlan::head_prior, with prior_dim, prior_uses_ls, prior_weight
   int prior_D = 0, prior_use_ls = 0;
   float prior_w = 0.f;
   const float *Rs_in = nullptr, *joff = nullptr, *voff = nullptr;   // SMAL.__call__ options (component API)
   int joff_stride = 0;
-  const PendingStep* pending = nullptr;   // smalfit_fit_run: the optimiser step the previous evaluation left to this launch
+  const PendingStep* pending = nullptr;   // HeadKernel::Step: the optimiser step the previous evaluation left to this launch
   int prior_slot = 0;                     // which half of gb_prior / gls_prior the prior block writes (a pending step reads the other)
-  bool prior_per_frame = false;           // independent images: one prior term per frame (rows of gb_prior_pf / gls_prior_pf, loss_betas_pf)
 };
 static constexpr int kPriorSlotB = 32, kPriorSlotLs = 8;   // floats per slot of smalfit_engine::gb_prior / gls_prior, per row of gb_prior_pf / gls_prior_pf
 
@@ -555,61 +544,78 @@ static int run_lbs_forward(smalfit_engine* e, hipStream_t st, int M, const float
                            int nb, const float* logscale, int ls_stride, const float* trans,
                            float* joints_out, const HeadExtras* ex = nullptr) {
   const ModelDev& m = e->model->dev;
+  const HeadExtras none{};
+  const HeadExtras& x = ex ? *ex : none;
   HeadArgs h;
   std::memset(&h, 0, sizeof(h));
   h.M = M; h.Mp = e->Mp; h.nb = nb; h.betas_stride = betas_stride; h.ls_stride = ls_stride;
-  h.nshape_x = m.Vp / 256; h.nshape = head_shape_blocks(M, m.Vp, betas_stride != 0);
+  h.nshape_x = vertex_blocks(m.Vp); h.nshape = head_shape_blocks(M, m.Vp, betas_stride != 0);
   h.betas = betas; h.logscale = logscale;
-  h.theta_in = (ex && ex->grot) ? nullptr : e->theta;       // component API: theta was copied in by the caller
-  if (ex) { h.grot = ex->grot; h.jrot = ex->jrot; h.gmask = ex->gmask; h.rmask = ex->rmask;
-            h.Rs_in = ex->Rs_in; h.joff = ex->joff; h.joff_stride = ex->joff_stride; h.voff = ex->voff; }
+  h.theta_in = x.grot ? nullptr : e->theta;       // component API: theta was copied in by the caller
+  h.grot = x.grot; h.jrot = x.jrot; h.gmask = x.gmask; h.rmask = x.rmask;
+  h.Rs_in = x.Rs_in; h.joff = x.joff; h.joff_stride = x.joff_stride; h.voff = x.voff;
   h.theta = e->theta; h.Jrest = e->Jrest; h.v_shaped = e->v_shaped;
   h.Rm = e->Rm; h.Gm = e->Gm; h.scm = e->scm; h.Am = e->Am; h.pfT = e->pfT;
-  const bool prior = ex && ex->prior_prec;
-  if (prior) {
-    h.prior_prec = ex->prior_prec; h.prior_mean = ex->prior_mean; h.prior_D = ex->prior_D; h.prior_use_ls = ex->prior_use_ls;
-    h.prior_w = ex->prior_w; h.prior_loss = e->loss_betas;
-    h.prior_gb = e->gb_prior + ex->prior_slot * kPriorSlotB; h.prior_gls = e->gls_prior + ex->prior_slot * kPriorSlotLs;
+  if (x.prior != HeadPrior::None) {
+    h.prior_prec = e->shape_prec; h.prior_mean = e->shape_mean; h.prior_D = x.prior_D; h.prior_use_ls = x.prior_use_ls;
+    h.prior_w = x.prior_w; h.prior_loss = e->loss_betas;
+    h.prior_gb = e->gb_prior + x.prior_slot * kPriorSlotB; h.prior_gls = e->gls_prior + x.prior_slot * kPriorSlotLs;
   }
   PriorFrames pf;
   std::memset(&pf, 0, sizeof(pf));
-  if (prior && ex->prior_per_frame) {
+  if (x.prior == HeadPrior::PerFrame) {
     pf.on = 1; pf.loss = e->loss_betas_pf; pf.gb = e->gb_prior_pf; pf.gb_stride = kPriorSlotB; pf.gls = e->gls_prior_pf; pf.gls_stride = kPriorSlotLs;
   }
-  const int nhead = head_blocks(M, m.Vp, betas_stride != 0, !prior ? HeadPrior::None : (pf.on ? HeadPrior::PerFrame : HeadPrior::Shared));
-  if (ex && ex->pending) lbs_head_step_kernel<<<nhead, 256, 0, st>>>(m, h, *ex->pending);   // (one subject: plan_fold refuses independent images)
-  else if (pf.on) lbs_head_images_kernel<<<nhead, 256, 0, st>>>(m, h, pf);
-  else lbs_head_kernel<<<nhead, 256, 0, st>>>(m, h);
+  const int nhead = head_blocks(M, m.Vp, betas_stride != 0, x.prior);
+  switch (x.head) {
+    case HeadKernel::Step: lbs_head_step_kernel<<<nhead, 256, 0, st>>>(m, h, *x.pending); break;
+    case HeadKernel::Images: lbs_head_images_kernel<<<nhead, 256, 0, st>>>(m, h, pf); break;
+    case HeadKernel::Plain: lbs_head_kernel<<<nhead, 256, 0, st>>>(m, h); break;
+  }
   LAUNCH_OK("lbs_head_kernel");
   const int vs_stride = betas_stride ? 3 * m.Vp : 0;
-  switch (skin_form(M, m.Vp)) {
+  const SkinForm form = skin_form(M, m.Vp);
+  const Grid2 sg = skin_grid(form, M, m.Vp);
+  switch (form) {
     case SkinForm::Wide:
-      skin_mfma_kernel<<<dim3(m.Vp / 64, (M + 15) / 16), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am, trans,
-                                                                      e->vposed, e->verts, e->proj);
+      skin_mfma_kernel<<<dim3(sg.x, sg.y), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am, trans, e->vposed, e->verts, e->proj);
       break;
     case SkinForm::Split:
-      skin_mfma_split_kernel<<<dim3(m.Vp / kSkinVerts, (M + 15) / 16), kSkinThreads, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT,
-                                                                                             e->Am, trans, e->vposed, e->verts, e->proj);
+      skin_mfma_split_kernel<<<dim3(sg.x, sg.y), kSkinThreads, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am, trans, e->vposed,
+                                                                     e->verts, e->proj);
       break;
     case SkinForm::Plain:
-      skin_kernel<8><<<dim3(m.Vp / 64, (M + 7) / 8), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am,
-                                                                   trans, e->vposed, e->verts, e->proj);
+      skin_kernel<8><<<dim3(sg.x, sg.y), 256, 0, st>>>(m, M, e->Mp, e->v_shaped, vs_stride, e->pfT, e->Am, trans, e->vposed, e->verts, e->proj);
       break;
   }
   LAUNCH_OK("skin_kernel");
   if (joints_out) {   // callers that only need the vertices (smalfit_fit3d_step) skip the joint regression
-    joints_kernel<<<dim3(41, M), 128, 0, st>>>(m, e->verts, joints_out);
+    joints_kernel<<<dim3(kJointBlocks, M), 128, 0, st>>>(m, e->verts, joints_out);
     LAUNCH_OK("joints_kernel");
   }
   return 0;
 }
 
+// the queue kernels in the instantiation EvalPlan::frame_loss selects (floss: the per-frame counters it then feeds)
+template <typename... Args>
+static void launch_raster_band(hipStream_t st, bool frame_loss, Args... args) {
+  if (frame_loss) raster_band_kernel<true><<<kBandBlocks, 256, 0, st>>>(args...);
+  else raster_band_kernel<false><<<kBandBlocks, 256, 0, st>>>(args...);
+}
+template <typename... Args>
+static void launch_raster_select(hipStream_t st, bool frame_loss, Args... args) {
+  if (frame_loss) raster_select_kernel<true><<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(args...);
+  else raster_select_kernel<false><<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(args...);
+}
+
 // face boxes / records, sweep (per-pixel count + log-alpha), resolve (K-nearest).  e->proj holds camera-space vertices.
 // `joints_out` / `la`: the joint regression and the per-frame loss terms ride along as extra workgroups of the box and
-// resolve launches (they depend on the skinned vertices only and are needed by the backward pass only)
+// resolve launches (they depend on the skinned vertices only and are needed by the backward pass only).
+// `queue_loss` / `floss`: the queue kernels write their loss partials / count them per frame too (EvalPlan)
 static int run_raster_forward(smalfit_engine* e, hipStream_t st, int M, WinMap win, float w_sil,
                               SilTarget tsil, float* sil_out, float* blk_loss,
-                              float* joints_out = nullptr, const LossArgs* la = nullptr, unsigned long long* floss = nullptr) {
+                              float* joints_out = nullptr, const LossArgs* la = nullptr, bool queue_loss = false,
+                              unsigned long long* floss = nullptr) {
   // e->gz is persistent state: .y carries each pixel's depth threshold into the next evaluation (verified there)
   float2* gz = e->gz;
   const ModelDev& m = e->model->dev;
@@ -617,40 +623,32 @@ static int run_raster_forward(smalfit_engine* e, hipStream_t st, int M, WinMap w
     Section sec(e, st, SMALFIT_SEC_RASTER_BBOX);
     // the per-pixel accumulators are zero here: whoever reads them last (resolve / band kernel) clears them; the two
     // queue counters are reset by face_bbox_kernel
-    face_bbox_kernel<<<((M + 7) / 8) * 8 + xcd_grid((m.F + 255) / 256, M) + (joints_out ? 41 * M : 0), 256, 0, st>>>(m, M, e->S, e->proj, e->fbox, e->frec, e->brect, e->zc, e->frect,
-                                                                                                 e->qcount, e->verts, joints_out);
+    face_bbox_kernel<<<box_grid(m.F, M, joints_out != nullptr), 256, 0, st>>>(m, M, e->S, e->proj, e->fbox, e->frec, e->brect, e->zc, e->frect,
+                                                                           e->qcount, e->verts, joints_out);
     LAUNCH_OK("face_bbox_kernel");
   }
   {
     Section sec(e, st, SMALFIT_SEC_RASTER_SWEEP);
-    raster_sweep_kernel<<<xcd_grid((m.F + kSweepFaces - 1) / kSweepFaces, M), 256, 0, st>>>(m.F, M, e->S, e->frec, e->fbox, e->brect, e->zc, e->zband, e->gacc, e->bcnt, e->blist, e->plist, e->pcount);
+    raster_sweep_kernel<<<sweep_grid(m.F, M), 256, 0, st>>>(m.F, M, e->S, e->frec, e->fbox, e->brect, e->zc, e->zband, e->gacc, e->bcnt, e->blist, e->plist, e->pcount);
     LAUNCH_OK("raster_sweep_kernel");
   }
   {
     Section sec(e, st, SMALFIT_SEC_RASTER_RESOLVE);
     LossArgs no_loss;
     std::memset(&no_loss, 0, sizeof(no_loss));
-    raster_resolve_kernel<<<xcd_grid(e->nrb, M) + (la ? ((M + 7) / 8) * 8 : 0), 256, 0, st>>>(e->S, M, win, w_sil, e->gacc, e->bcnt, e->frect, e->zband, tsil, sil_out, gz,
-                                                                         blk_loss, e->qcount, e->queue, e->bqueue, g_dbg ? e->status : nullptr,
-                                                                         la ? *la : no_loss, la ? M : 0);
+    const int loss_frames = la ? M : 0;
+    raster_resolve_kernel<<<resolve_grid(e->nrb, M, loss_frames), 256, 0, st>>>(e->S, M, win, w_sil, e->gacc, e->bcnt, e->frect, e->zband, tsil, sil_out, gz,
+                                                                             blk_loss, e->qcount, e->queue, e->bqueue, g_dbg ? e->status : nullptr,
+                                                                             la ? *la : no_loss, loss_frames);
     LAUNCH_OK("raster_resolve_kernel");
     // the band kernel's loss partials follow the select kernel's in qloss
-    // (floss: the caller wants the loss per frame too -- the instantiations that feed the per-frame counters)
-    if (floss && tsil)
-      raster_band_kernel<true><<<kBandBlocks, 256, 0, st>>>(e->S, M, win, w_sil, e->gacc, e->bcnt, e->blist, tsil, sil_out, gz, e->zband,
-                                                            e->qcount, e->queue, e->bqueue, e->qloss + kSelectBlocks, floss);
-    else
-      raster_band_kernel<false><<<kBandBlocks, 256, 0, st>>>(e->S, M, win, w_sil, e->gacc, e->bcnt, e->blist, tsil, sil_out, gz, e->zband,
-                                                             e->qcount, e->queue, e->bqueue, tsil ? e->qloss + kSelectBlocks : nullptr, nullptr);
+    launch_raster_band(st, floss != nullptr, e->S, M, win, w_sil, e->gacc, e->bcnt, e->blist, tsil, sil_out, gz, e->zband,
+                       e->qcount, e->queue, e->bqueue, queue_loss ? e->qloss + kSelectBlocks : nullptr, floss);
     LAUNCH_OK("raster_band_kernel");
   }
   Section sec(e, st, SMALFIT_SEC_RASTER_SELECT);
-  if (floss && tsil)
-    raster_select_kernel<true><<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(m.F, e->S, M, win, w_sil, e->frec, e->zc, e->brect, e->fbox, e->qcount, e->queue,
-                                                        tsil, sil_out, gz, e->zband, e->pcount, e->qloss, g_dbg, floss);
-  else
-    raster_select_kernel<false><<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(m.F, e->S, M, win, w_sil, e->frec, e->zc, e->brect, e->fbox, e->qcount, e->queue,
-                                                        tsil, sil_out, gz, e->zband, e->pcount, tsil ? e->qloss : nullptr, g_dbg, nullptr);
+  launch_raster_select(st, floss != nullptr, m.F, e->S, M, win, w_sil, e->frec, e->zc, e->brect, e->fbox, e->qcount, e->queue,
+                       tsil, sil_out, gz, e->zband, e->pcount, queue_loss ? e->qloss : nullptr, g_dbg, floss);
   LAUNCH_OK("raster_select_kernel");
   return 0;
 }
@@ -660,19 +658,17 @@ static int run_lbs_backward(smalfit_engine* e, hipStream_t st, int M, int nb, in
                             const float* dface, const float* dJ41, const float* dext, bool need_pose,
                             bool need_beta, bool need_ls, const float* dth_direct, int j_stride, float* dRs_out = nullptr) {
   const ModelDev& m = e->model->dev;
-  vertex_bwd_kernel<<<xcd_grid(m.Vp / 256, M), 256, 0, st>>>(m, M, e->proj, dface, dJ41, dext, e->Am, e->dvert, e->dvp, e->dtr_part);
+  vertex_bwd_kernel<<<vertex_bwd_grid(m.Vp, M), 256, 0, st>>>(m, M, e->proj, dface, dJ41, dext, e->Am, e->dvert, e->dvp, e->dtr_part);
   LAUNCH_OK("vertex_bwd_kernel");
-  {
-    const int nPB = need_pose ? mid_pb_ids(M) : 0;   // (up to PBM_TILES x 16 frames) x 32 pose features x column split
-    const DbetaGrid db = dbeta_grid(need_beta, m.Vp, betas_shared != 0, M);
-    lbs_bwd_mid_kernel<<<mid_grid(M, nPB), 256, 0, st>>>(m, M, nPB, e->dvert, e->vposed, e->dvp, e->dA, e->dpf_part);
-    LAUNCH_OK("lbs_bwd_mid_kernel");
-    // the shape-blend adjoint partials ride on the chain launch: db.blocks() workgroups after its M frame blocks
-    chain_bwd_kernel<<<M + db.blocks(), 256, 0, st>>>(m, M, e->theta, e->Rm, e->Gm, e->scm, e->Jrest, j_stride, e->dA,
-                                                   need_pose ? e->dpf_part : nullptr, e->CS, dth_direct, e->dtheta,
-                                                   need_ls ? e->dls : nullptr, e->dJrest, need_beta ? e->dbetaJ : nullptr, dRs_out,
-                                                   nb, betas_shared, db.bx, db.by, db.bz, e->dvp, e->dbeta_part);
-  }
+  const int nPB = need_pose ? mid_pb_ids(M) : 0;   // (up to PBM_TILES x 16 frames) x 32 pose features x column split
+  const DbetaGrid db = dbeta_grid(need_beta, m.Vp, betas_shared != 0, M);
+  lbs_bwd_mid_kernel<<<mid_grid(M, nPB), 256, 0, st>>>(m, M, nPB, e->dvert, e->vposed, e->dvp, e->dA, e->dpf_part);
+  LAUNCH_OK("lbs_bwd_mid_kernel");
+  // the shape-blend adjoint partials ride on the chain launch: db.blocks() workgroups after its M frame blocks
+  chain_bwd_kernel<<<chain_grid(M, db), 256, 0, st>>>(m, M, e->theta, e->Rm, e->Gm, e->scm, e->Jrest, j_stride, e->dA,
+                                                    need_pose ? e->dpf_part : nullptr, e->CS, dth_direct, e->dtheta,
+                                                    need_ls ? e->dls : nullptr, e->dJrest, need_beta ? e->dbetaJ : nullptr, dRs_out,
+                                                    nb, betas_shared, db.bx, db.by, db.bz, e->dvp, e->dbeta_part);
   LAUNCH_OK("chain_bwd_kernel");
   return 0;
 }
@@ -692,146 +688,115 @@ struct EvalFold {
   AssembleArgs* args_out = nullptr;       // the assembly's arguments, for the successor's pending step
   const smalfit_window_rows* window_rows = nullptr;   // smalfit_fit_eval_windows: one row per window (checked by the caller)
 };
+static EngineFacts engine_facts(const smalfit_engine* e) { return EngineFacts{e->maxM, e->has_pose_prior, e->shape_dim, e->has_joint_limits}; }
 
+// plan_eval decides; here the plan's fields and the pointers of the block, the rows and the engine meet in the kernels' arguments
 static int fit_eval_impl(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const EvalFold& fold) {
-  if (!e || !a) return fail("smalfit_fit_eval: null argument");
-  if (refused("smalfit_fit_eval", fit_args_refusal(a, EngineFacts{e->maxM, e->has_pose_prior, e->shape_dim}))) return 1;
+  if (refused("smalfit_fit_eval", null_argument_refusal(e && a))) return 1;
+  if (refused("smalfit_fit_eval", fit_args_refusal(a, engine_facts(e)))) return 1;
   if (refused("smalfit_fit_eval", fit_model_refusal(e->model->NBall))) return 1;
-  const int M = a->num_frames;
-  // where these M frames sit in their sequence: per-window normalisers follow the sequence's windows
-  const WinMap win{a->window, a->frame_offset, sequence_frames(a)};
-  const bool indep = independent_images(a);
+  const smalfit_window_rows* wr = fold.window_rows;
+  EvalMode mode;
+  mode.pending = fold.pending != nullptr; mode.assemble = fold.assemble;
+  mode.window_rows = wr != nullptr; mode.want_betas = wr && wr->g_betas; mode.want_scales = wr && wr->g_log_beta_scales;
+  const EvalPlan p = plan_eval(a, engine_facts(e), mode);
+  const int M = p.M;
   hipStream_t st = (hipStream_t)stream;
   const ModelDev& m = e->model->dev;
   const float* gmask = a->global_mask ? a->global_mask : e->ones;
   const float* rmask = a->rotation_mask ? a->rotation_mask : e->ones;
-  const float* ls = a->logscale_mode ? a->log_beta_scales : nullptr;
-  const int ls_stride = a->logscale_mode == 2 ? 6 : 0;
-  const int nb = 20;
-
-  const bool sil_on = a->w_sil > 0.f;
-  const bool fused_loss = sil_on || a->sil_out;     // the rasteriser runs in this evaluation
-  const bool shape_prior = a->w_betas > 0.f;
-  const bool prior_uses_ls = prior_uses_limb_scales(a, e->shape_dim);
-  // one row of loss terms per frame: only an evaluation that assembles writes (and clears the counters behind) them
-  const bool rows = a->losses_per_frame != nullptr && fold.assemble;
-  // one row per window: the shared parameters' gradients are formed per window from per-frame partials (window_rows_kernel)
-  const smalfit_window_rows* wr = fold.window_rows;
-  int nwin = 0;   // windows whose shape-prior term this evaluation owns
   {
     Section sec(e, st, SMALFIT_SEC_LBS_FWD);
     HeadExtras ex;
     ex.grot = a->global_rotation; ex.jrot = a->joint_rotations; ex.gmask = gmask; ex.rmask = rmask;
-    ex.pending = fold.pending; ex.prior_slot = fold.prior_slot;
-    if (shape_prior) {
-      ex.prior_prec = e->shape_prec; ex.prior_mean = e->shape_mean; ex.prior_D = shape_prior_dim(a, e->shape_dim); ex.prior_use_ls = prior_uses_ls ? 1 : 0;
-      nwin = prior_windows(win.window, win.offset, M);
-      ex.prior_w = a->w_betas * (float)nwin;
-      if (indep) { ex.prior_w = a->w_betas; ex.prior_per_frame = true; }    // once per image
-    }
-    // with the rasteriser running, the joint regression and the loss terms ride in its launches (run_raster_forward)
-    // (betas_stride nb: one shape set per frame)
-    if (run_lbs_forward(e, st, M, a->betas, indep ? nb : 0, nb, ls, ls_stride, a->trans, fused_loss ? nullptr : e->joints, &ex)) return 1;
+    ex.head = p.head; ex.pending = fold.pending; ex.prior_slot = fold.prior_slot;
+    ex.prior = p.head_prior; ex.prior_D = p.prior_dim; ex.prior_use_ls = p.prior_uses_ls ? 1 : 0; ex.prior_w = p.prior_weight;
+    if (run_lbs_forward(e, st, M, a->betas, p.betas_stride, p.nb, p.limb_scales ? a->log_beta_scales : nullptr, p.ls_stride, a->trans,
+                        p.joints_in_head ? e->joints : nullptr, &ex)) return 1;
   }
 
   LossArgs la;
-  la.M = M; la.S = e->S; la.win = win;
+  la.M = M; la.S = e->S; la.win = p.win;
   la.theta = e->theta; la.trans = a->trans; la.joints = e->joints; la.canon = e->canon;
   la.tj = a->target_joints; la.vis = a->target_visibility;
-  la.w_j2d = a->w_j2d; la.w_pose = a->w_pose; la.w_splay = a->w_splay; la.w_temp = a->temporal ? a->w_temp : 0.f;
-  // the reference's weight table carries w_limit = 100 in stages 1-3 while the term itself is commented out
-  // (smal_fitter.py:146-151): it only exists here once a limit table has been given to the engine
-  la.w_limit = e->has_joint_limits ? a->w_limit : 0.f; la.lim_min = e->lim_min; la.lim_max = e->lim_max;
+  la.w_j2d = a->w_j2d; la.w_pose = a->w_pose; la.w_splay = a->w_splay; la.w_temp = p.w_temp;
+  la.w_limit = p.w_limit; la.lim_min = e->lim_min; la.lim_max = e->lim_max;
   la.pose_prec = e->pose_prec; la.pose_mean = e->pose_mean; la.pose_mask = e->pose_mask;
-  la.halo_prev = a->temporal ? a->halo_prev : nullptr;
-  la.halo_next = a->temporal ? a->halo_next : nullptr;
+  la.halo_prev = p.halos ? a->halo_prev : nullptr;
+  la.halo_next = p.halos ? a->halo_next : nullptr;
   la.proj_out = a->proj_out;
   la.dth_direct = e->dth_direct; la.dJ41 = e->dJ41; la.dtr_direct = e->dtr_direct; la.loss_part = e->loss_part;
-  if (!fused_loss) {
+  if (p.loss_launch == LossLaunch::OwnKernel) {
     loss_kernel<<<M, 128, 0, st>>>(la);
     LAUNCH_OK("loss_kernel");
   } else {
-    SilTarget tsil{nullptr, nullptr};
-    if (sil_on) { if (a->target_sil_u8) tsil.b = a->target_sil_u8; else tsil.f = a->target_sil; }
-    if (run_raster_forward(e, st, M, win, a->w_sil, tsil, a->sil_out, sil_on ? e->tile_loss : nullptr, e->joints, &la,
-                           ((rows || wr) && sil_on) ? e->frame_qloss : nullptr)) return 1;
+    const SilTarget tsil{p.sil_target == SilTargetKind::F32 ? a->target_sil : nullptr, p.sil_target == SilTargetKind::U8 ? a->target_sil_u8 : nullptr};
+    if (run_raster_forward(e, st, M, p.win, a->w_sil, tsil, a->sil_out, p.sil_on ? e->tile_loss : nullptr, e->joints, &la,
+                           p.queue_loss, p.frame_loss ? e->frame_qloss : nullptr)) return 1;
   }
-  if (sil_on) {
+  if (p.raster_backward) {
     Section sec(e, st, SMALFIT_SEC_RASTER_BWD);
     launch_raster_bwd(e, st, M);
     LAUNCH_OK("raster_bwd_kernel");
   }
-  if (a->verts_out) {
-    planar_to_interleaved_kernel<<<dim3((m.V * 3 + 255) / 256, M), 256, 0, st>>>(M, m.V, m.Vp, e->verts, 3 * m.Vp, a->trans, a->verts_out);
+  if (p.verts_out) {
+    planar_to_interleaved_kernel<<<dim3(elem_blocks(m.V * 3), M), 256, 0, st>>>(M, m.V, m.Vp, e->verts, 3 * m.Vp, a->trans, a->verts_out);
     LAUNCH_OK("planar_to_interleaved_kernel");
   }
-
-  const bool need_pose = a->g_joint_rotations != nullptr;
-  const bool need_beta = a->g_betas != nullptr || (wr && wr->g_betas);
-  const bool need_ls = (a->g_log_beta_scales != nullptr || (wr && wr->g_log_beta_scales)) && a->logscale_mode != 0;
   {
     Section sec(e, st, SMALFIT_SEC_LBS_BWD);
-    // (independent images: per-frame partials of the shape-blend adjoint, per-frame rest joints; window rows: the same partial
-    // layout -- M rows of nblk_beta * nb floats, dbeta_rows() holds them -- over the one shared shape)
-    if (run_lbs_backward(e, st, M, nb, (indep || wr) ? 0 : 1, sil_on ? e->dface : nullptr, e->dJ41, nullptr, need_pose, need_beta, need_ls,
-                         e->dth_direct, indep ? 105 : 0)) return 1;
+    if (run_lbs_backward(e, st, M, p.nb, p.bwd_betas_shared, p.raster_backward ? e->dface : nullptr, e->dJ41, nullptr, p.need_pose, p.need_beta,
+                         p.need_ls, e->dth_direct, p.j_stride)) return 1;
   }
 
+  const bool prior_shared = p.head_prior == HeadPrior::Shared, prior_rows = p.head_prior == HeadPrior::PerFrame;
   AssembleArgs g;
-  g.M = M; g.S = e->S; g.T = e->nrb; g.win = win; g.nb = nb; g.NBall = m.NBall;
-  g.nblk_beta = e->nblk_beta; g.nvt = e->nvt; g.betas_shared = 1; g.ls_shared = a->logscale_mode == 1;
+  g.M = M; g.S = e->S; g.T = e->nrb; g.win = p.win; g.nb = p.nb; g.NBall = m.NBall;
+  g.nblk_beta = e->nblk_beta; g.nvt = e->nvt; g.betas_shared = p.asm_betas_shared; g.ls_shared = p.asm_ls_shared;
   g.w_sil = a->w_sil;
-  g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = beta_groups(!indep);
-  g.gb_prior = shape_prior ? e->gb_prior + fold.prior_slot * kPriorSlotB : nullptr;
-  g.gls_prior = prior_uses_ls ? e->gls_prior + fold.prior_slot * kPriorSlotLs : nullptr;
+  g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = p.ngrp_beta;
+  // (independent images leave the shared-shape slots unused: one row per image instead, AssembleExt)
+  g.gb_prior = prior_shared ? e->gb_prior + fold.prior_slot * kPriorSlotB : nullptr;
+  g.gls_prior = prior_shared && p.prior_uses_ls ? e->gls_prior + fold.prior_slot * kPriorSlotLs : nullptr;
   g.dls = e->dls; g.dtheta = e->dtheta; g.gmask = gmask; g.rmask = rmask;
   g.dtr_direct = e->dtr_direct; g.dtr_part = e->dtr_part; g.loss_part = e->loss_part;
-  g.loss_betas = shape_prior ? e->loss_betas : nullptr;
-  g.tile_loss = sil_on ? e->tile_loss : nullptr;
-  g.qloss = sil_on ? e->qloss : nullptr;
-  g.nqblk = kSelectBlocks + kBandBlocks;
-  g.g_betas = need_beta ? a->g_betas : nullptr;
-  g.g_ls = need_ls ? a->g_log_beta_scales : nullptr;
+  g.loss_betas = prior_shared ? e->loss_betas : nullptr;
+  g.tile_loss = p.sil_on ? e->tile_loss : nullptr;
+  g.qloss = p.queue_loss ? e->qloss : nullptr;
+  g.nqblk = kQueueLossBlocks;
+  g.g_betas = p.assembly_leaves_betas ? nullptr : a->g_betas;
+  g.g_ls = p.need_ls && !p.assembly_leaves_scales ? a->g_log_beta_scales : nullptr;
   g.g_grot = a->g_global_rotation; g.g_jrot = a->g_joint_rotations; g.g_trans = a->g_trans;
   g.losses = a->losses;
   g.lpart = e->lpart; g.qpart = e->qpart; g.counter = e->asm_counter;
   AssembleExt gx;
   std::memset(&gx, 0, sizeof(gx));
-  gx.losses_pf = rows ? a->losses_per_frame : nullptr; gx.frame_qloss = e->frame_qloss; gx.prior_windows = nwin;
-  if (indep) {
-    g.betas_shared = 0; g.ls_shared = 0;
-    g.gb_prior = nullptr; g.gls_prior = nullptr; g.loss_betas = nullptr;      // the shared-shape slots stay unused: one row per image instead
-    if (shape_prior) {
-      gx.gb_prior_pf = e->gb_prior_pf; gx.gb_stride = kPriorSlotB; gx.prior_loss_pf = e->loss_betas_pf;
-      if (prior_uses_ls) { gx.gls_prior_pf = e->gls_prior_pf; gx.gls_stride = kPriorSlotLs; }
-    }
+  gx.losses_pf = p.rows ? a->losses_per_frame : nullptr; gx.frame_qloss = e->frame_qloss; gx.prior_windows = p.prior_windows;
+  if (prior_rows) {
+    gx.gb_prior_pf = e->gb_prior_pf; gx.gb_stride = kPriorSlotB; gx.prior_loss_pf = e->loss_betas_pf;
+    if (p.prior_uses_ls) { gx.gls_prior_pf = e->gls_prior_pf; gx.gls_stride = kPriorSlotLs; }
   }
   WindowRowsDev wd;
   std::memset(&wd, 0, sizeof(wd));
   if (wr) {
     static_assert(kWindowRowBetas >= 20 && kWindowRowScales >= 6, "a row of the workspace holds a row of the gradient");
-    const bool ls_rows = need_ls && a->logscale_mode == 1;
-    wd.W = wr->num_windows; wd.clear_qloss = rows ? 0 : 1;
+    wd.W = p.W; wd.clear_qloss = p.clear_qloss;
     wd.losses = wr->losses; wd.g_betas = wr->g_betas; wd.g_ls = wr->g_log_beta_scales;
-    wd.row_betas = need_beta ? e->win_gb : nullptr; wd.row_ls = ls_rows ? e->win_gls : nullptr;
-    wd.tot_betas = a->g_betas; wd.tot_ls = ls_rows ? a->g_log_beta_scales : nullptr;
+    wd.row_betas = p.need_beta ? e->win_gb : nullptr; wd.row_ls = p.ls_rows ? e->win_gls : nullptr;
+    wd.tot_betas = a->g_betas; wd.tot_ls = p.ls_rows ? a->g_log_beta_scales : nullptr;
     wd.counter = e->asm_counter + 1;          // (assemble_kernel's is slot 0)
-    // the assembly leaves the shared gradients to window_rows_kernel (per-frame limb scales stay its own)
-    g.g_betas = nullptr;
-    if (a->logscale_mode == 1) g.g_ls = nullptr;
   }
   if (fold.args_out) *fold.args_out = g;
   if (fold.assemble) {
-    // roles: one block per shape set | limb scales | elements | loss partials
-    if (indep) assemble_kernel<true><<<M + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g, gx);
-    else assemble_kernel<false><<<1 + 1 + kAsmElem + kAsmLoss, 256, 0, st>>>(g, gx);
+    if (p.independent) assemble_kernel<true><<<assemble_grid(p.asm_shape_sets), 256, 0, st>>>(g, gx);
+    else assemble_kernel<false><<<assemble_grid(p.asm_shape_sets), 256, 0, st>>>(g, gx);
     LAUNCH_OK("assemble_kernel");
     if (wr) {     // (before frame_loss_rows_kernel, which clears the per-frame counters both read)
-      window_rows_kernel<<<wd.W, 256, 0, st>>>(g, gx, wd);
+      window_rows_kernel<<<window_rows_grid(wd.W), 256, 0, st>>>(g, gx, wd);
       LAUNCH_OK("window_rows_kernel");
     }
-    if (rows) {
-      frame_loss_rows_kernel<<<kAsmRows, 256, 0, st>>>(g, gx);
+    if (p.rows) {
+      frame_loss_rows_kernel<<<frame_loss_rows_grid(), 256, 0, st>>>(g, gx);
       LAUNCH_OK("frame_loss_rows_kernel");
     }
   }
@@ -848,10 +813,10 @@ extern "C" {
 int smalfit_fit_eval(smalfit_engine* e, void* stream, const smalfit_fit_args* a) { return fit_eval_impl(e, stream, a, EvalFold{}); }
 
 int smalfit_fit_eval_windows(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const smalfit_window_rows* rows) {
-  if (!e || !a || !rows) return fail("smalfit_fit_eval_windows: null argument");
+  if (refused("smalfit_fit_eval_windows", null_argument_refusal(e && a && rows))) return 1;
   // the sizes of both blocks before any other field of either
   if (refused("smalfit_fit_eval_windows", window_rows_size_refusal(rows))) return 1;
-  if (refused("smalfit_fit_eval_windows", fit_args_refusal(a, EngineFacts{e->maxM, e->has_pose_prior, e->shape_dim}))) return 1;
+  if (refused("smalfit_fit_eval_windows", fit_args_refusal(a, engine_facts(e)))) return 1;
   if (refused("smalfit_fit_eval_windows", window_rows_refusal(a, rows))) return 1;
   EvalFold fold;
   fold.window_rows = rows;
@@ -862,7 +827,7 @@ int smalfit_fit_eval_windows(smalfit_engine* e, void* stream, const smalfit_fit_
 // per-section timing with HIP events on the caller's stream
 // ------------------------------------------------------------------------------------------------
 int smalfit_engine_profile_begin(smalfit_engine* e, int max_evals, int stride) {
-  if (!e || max_evals <= 0 || stride <= 0) return fail("smalfit_engine_profile_begin: bad argument");
+  if (refused("smalfit_engine_profile_begin", profile_begin_refusal(e != nullptr, max_evals, stride))) return 1;
   for (auto ev : e->prof_ev) (void)hipEventDestroy(ev);
   e->prof_ev.assign((size_t)max_evals * SMALFIT_NUM_SECTIONS * 2, nullptr);
   for (auto& ev : e->prof_ev) HIP_OK(hipEventCreate(&ev));
@@ -875,7 +840,7 @@ int smalfit_engine_profile_begin(smalfit_engine* e, int max_evals, int stride) {
 }
 
 int smalfit_engine_profile_end(smalfit_engine* e, void* stream, float* ms_total, int* counts) {
-  if (!e || !ms_total || !counts) return fail("smalfit_engine_profile_end: null argument");
+  if (refused("smalfit_engine_profile_end", null_argument_refusal(e && ms_total && counts))) return 1;
   HIP_OK(hipStreamSynchronize((hipStream_t)stream));
   e->prof_on = false;
   for (int sct = 0; sct < SMALFIT_NUM_SECTIONS; ++sct) { ms_total[sct] = 0.f; counts[sct] = 0; }
@@ -900,20 +865,16 @@ namespace smalfit {
 // stages a per-frame template offset: planar copy in e->dext, its joint regression (rows of 123 floats) in e->dJ41
 static int stage_vertex_offset(smalfit_engine* e, hipStream_t st, int M, const float* v_offset, HeadExtras& ex) {
   const ModelDev& m = e->model->dev;
-  interleaved_to_planar_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, v_offset, e->dext);
+  interleaved_to_planar_kernel<<<dim3(vertex_blocks(m.Vp), M), 256, 0, st>>>(M, m.V, m.Vp, v_offset, e->dext);
   LAUNCH_OK("interleaved_to_planar_kernel");
-  joints_kernel<<<dim3(41, M), 128, 0, st>>>(m, e->dext, e->dJ41);
+  joints_kernel<<<dim3(kJointBlocks, M), 128, 0, st>>>(m, e->dext, e->dJ41);
   LAUNCH_OK("joints_kernel");
   ex.voff = e->dext; ex.joff = e->dJ41; ex.joff_stride = 123;
   return 0;
 }
 static int check_lbs_args(smalfit_engine* e, const smalfit_lbs_args* a, const char* who) {
-  if (!e || !a) return fail(std::string(who) + ": null argument");
-  if (a->num_frames <= 0 || a->num_frames > e->maxM) return fail(std::string(who) + ": num_frames exceeds the engine's max_frames");
-  if (a->num_betas <= 0 || a->num_betas > e->model->dev.NBall) return fail(std::string(who) + ": num_betas out of range");
-  if (!a->beta) return fail(std::string(who) + ": beta missing");
-  if ((a->theta == nullptr) == (a->Rs == nullptr)) return fail(std::string(who) + ": give exactly one of theta (axis-angle) and Rs (rotation matrices)");
-  return 0;
+  if (refused(who, null_argument_refusal(e && a))) return 1;
+  return refused(who, lbs_args_refusal(a, e->maxM, e->model->dev.NBall));
 }
 static int lbs_forward_common(smalfit_engine* e, hipStream_t st, const smalfit_lbs_args* a, float* joints_out) {
   const int M = a->num_frames, nb = a->num_betas;
@@ -928,12 +889,12 @@ static int lbs_forward_common(smalfit_engine* e, hipStream_t st, const smalfit_l
 
 int smalfit_lbs_forward_ex(smalfit_engine* e, void* stream, const smalfit_lbs_args* a) {
   if (check_lbs_args(e, a, "smalfit_lbs_forward_ex")) return 1;
-  if (!a->verts || !a->joints) return fail("smalfit_lbs_forward_ex: verts / joints outputs missing");
+  if (refused("smalfit_lbs_forward_ex", lbs_outputs_refusal(a))) return 1;
   const ModelDev& m = e->model->dev;
   const int M = a->num_frames;
   hipStream_t st = (hipStream_t)stream;
   if (lbs_forward_common(e, st, a, a->joints)) return 1;
-  const dim3 grid((m.V * 3 + 255) / 256, M);
+  const dim3 grid(elem_blocks(m.V * 3), M);
   planar_to_interleaved_kernel<<<grid, 256, 0, st>>>(M, m.V, m.Vp, e->verts, 3 * m.Vp, nullptr, a->verts);
   if (a->v_shaped) planar_to_interleaved_kernel<<<grid, 256, 0, st>>>(M, m.V, m.Vp, e->v_shaped, 3 * m.Vp, nullptr, a->v_shaped);
   LAUNCH_OK("planar_to_interleaved_kernel");
@@ -951,7 +912,7 @@ int smalfit_lbs_backward_ex(smalfit_engine* e, void* stream, const smalfit_lbs_a
   const float* dext = nullptr;
   if (a->dverts) {
     // (e->dext held the planar offset during the forward; the head kernel has consumed it)
-    interleaved_to_planar_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, a->dverts, e->dext);
+    interleaved_to_planar_kernel<<<dim3(vertex_blocks(m.Vp), M), 256, 0, st>>>(M, m.V, m.Vp, a->dverts, e->dext);
     LAUNCH_OK("interleaved_to_planar_kernel");
     dext = e->dext;
   }
@@ -980,7 +941,7 @@ int smalfit_lbs_backward_ex(smalfit_engine* e, void* stream, const smalfit_lbs_a
     LAUNCH_OK("assemble_kernel");
   }
   if (a->dv_offset) {
-    offset_grad_kernel<<<dim3((m.V + 255) / 256, M), 256, 0, st>>>(m, M, e->dvp, e->dJrest, a->dv_offset);
+    offset_grad_kernel<<<dim3(elem_blocks(m.V), M), 256, 0, st>>>(m, M, e->dvp, e->dJrest, a->dv_offset);
     LAUNCH_OK("offset_grad_kernel");
   }
   return 0;
@@ -988,7 +949,7 @@ int smalfit_lbs_backward_ex(smalfit_engine* e, void* stream, const smalfit_lbs_a
 
 int smalfit_lbs_forward(smalfit_engine* e, void* stream, int M, int nb, const float* beta, const float* theta,
                         const float* logscale, float* verts, float* joints, float* Rs, float* v_shaped) {
-  if (!theta) return fail("smalfit_lbs_forward: null argument");
+  if (refused("smalfit_lbs_forward", null_argument_refusal(theta != nullptr))) return 1;
   smalfit_lbs_args a;
   std::memset(&a, 0, sizeof(a));
   a.num_frames = M; a.num_betas = nb; a.beta = beta; a.theta = theta; a.logscale = logscale;
@@ -999,7 +960,7 @@ int smalfit_lbs_forward(smalfit_engine* e, void* stream, int M, int nb, const fl
 int smalfit_lbs_backward(smalfit_engine* e, void* stream, int M, int nb, const float* beta, const float* theta,
                          const float* logscale, const float* dverts, const float* djoints, float* dbeta,
                          float* dtheta, float* dlogscale) {
-  if (!theta) return fail("smalfit_lbs_backward: null argument");
+  if (refused("smalfit_lbs_backward", null_argument_refusal(theta != nullptr))) return 1;
   smalfit_lbs_args a;
   std::memset(&a, 0, sizeof(a));
   a.num_frames = M; a.num_betas = nb; a.beta = beta; a.theta = theta; a.logscale = logscale;
@@ -1008,8 +969,8 @@ int smalfit_lbs_backward(smalfit_engine* e, void* stream, int M, int nb, const f
 }
 
 int smalfit_rodrigues(void* stream, int count, const float* theta, float* R) {
-  if (count <= 0 || !theta || !R) return fail("smalfit_rodrigues: bad argument");
-  rodrigues_kernel<<<(count + 255) / 256, 256, 0, (hipStream_t)stream>>>(count, theta, R);
+  if (refused("smalfit_rodrigues", operator_args_refusal(count, theta && R))) return 1;
+  rodrigues_kernel<<<elem_blocks(count), 256, 0, (hipStream_t)stream>>>(count, theta, R);
   LAUNCH_OK("rodrigues_kernel");
   return 0;
 }
@@ -1026,10 +987,10 @@ static int pack_parents(const int* parents, Parents35& par, const char* who) {
 
 int smalfit_global_rigid_transformation(void* stream, int count, const float* Rs, const float* Js, const int* parents,
                                         const float* logscale, float* new_J, float* A) {
-  if (count <= 0 || !Rs || !Js || !parents || !new_J || !A) return fail("smalfit_global_rigid_transformation: bad argument");
+  if (refused("smalfit_global_rigid_transformation", operator_args_refusal(count, Rs && Js && parents && new_J && A))) return 1;
   Parents35 par;
   if (pack_parents(parents, par, "smalfit_global_rigid_transformation")) return 1;
-  global_rigid_kernel<<<(count + 63) / 64, 64, 0, (hipStream_t)stream>>>(count, Rs, Js, par, logscale, new_J, A);
+  global_rigid_kernel<<<rigid_blocks(count), 64, 0, (hipStream_t)stream>>>(count, Rs, Js, par, logscale, new_J, A);
   LAUNCH_OK("global_rigid_kernel");
   return 0;
 }
@@ -1037,19 +998,18 @@ int smalfit_global_rigid_transformation(void* stream, int count, const float* Rs
 int smalfit_global_rigid_transformation_backward(void* stream, int count, const float* Rs, const float* Js, const int* parents,
                                                  const float* logscale, const float* d_new_J, const float* d_A,
                                                  float* scratch, float* dRs, float* dJs, float* dlogscale) {
-  if (count <= 0 || !Rs || !Js || !parents || !d_new_J || !d_A || !scratch || !dRs || !dJs)
-    return fail("smalfit_global_rigid_transformation_backward: bad argument");
+  if (refused("smalfit_global_rigid_transformation_backward", operator_args_refusal(count, Rs && Js && parents && d_new_J && d_A && scratch && dRs && dJs))) return 1;
   Parents35 par;
   if (pack_parents(parents, par, "smalfit_global_rigid_transformation_backward")) return 1;
-  global_rigid_bwd_kernel<<<(count + 63) / 64, 64, 0, (hipStream_t)stream>>>(count, Rs, Js, par, logscale, d_new_J, d_A, scratch, dRs, dJs,
+  global_rigid_bwd_kernel<<<rigid_blocks(count), 64, 0, (hipStream_t)stream>>>(count, Rs, Js, par, logscale, d_new_J, d_A, scratch, dRs, dJs,
                                                                             logscale ? dlogscale : nullptr);
   LAUNCH_OK("global_rigid_bwd_kernel");
   return 0;
 }
 
 int smalfit_rodrigues_backward(void* stream, int count, const float* theta, const float* dR, float* dtheta) {
-  if (count <= 0 || !theta || !dR || !dtheta) return fail("smalfit_rodrigues_backward: bad argument");
-  rodrigues_bwd_kernel<<<(count + 255) / 256, 256, 0, (hipStream_t)stream>>>(count, theta, dR, dtheta);
+  if (refused("smalfit_rodrigues_backward", operator_args_refusal(count, theta && dR && dtheta))) return 1;
+  rodrigues_bwd_kernel<<<elem_blocks(count), 256, 0, (hipStream_t)stream>>>(count, theta, dR, dtheta);
   LAUNCH_OK("rodrigues_bwd_kernel");
   return 0;
 }
@@ -1059,25 +1019,25 @@ int smalfit_rodrigues_backward(void* stream, int count, const float* theta, cons
 // ------------------------------------------------------------------------------------------------
 int smalfit_render_forward(smalfit_engine* e, void* stream, int M, const float* verts, const float* points, int P,
                            float* sil, float* proj_points) {
-  if (!e || !verts) return fail("smalfit_render_forward: null argument");
-  if (M <= 0 || M > e->maxM) return fail("smalfit_render_forward: M exceeds the engine's max_frames");
+  if (refused("smalfit_render_forward", null_argument_refusal(e && verts))) return 1;
+  if (refused("smalfit_render_forward", render_frames_refusal(M, e->maxM))) return 1;
   hipStream_t st = (hipStream_t)stream;
   const ModelDev& m = e->model->dev;
   if (sil) {
-    project_verts_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
+    project_verts_kernel<<<dim3(vertex_blocks(m.Vp), M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
     LAUNCH_OK("project_verts_kernel");
     if (run_raster_forward(e, st, M, WinMap{1, 0, M}, 0.f, SilTarget{nullptr, nullptr}, sil, nullptr)) return 1;
   }
   if (points && proj_points && P > 0) {
-    project_points_kernel<<<(M * P + 255) / 256, 256, 0, st>>>(M * P, e->S, points, proj_points);
+    project_points_kernel<<<elem_blocks((long long)M * P), 256, 0, st>>>(M * P, e->S, points, proj_points);
     LAUNCH_OK("project_points_kernel");
   }
   return 0;
 }
 
 int smalfit_render_color(smalfit_engine* e, void* stream, int M, const float* verts, const float* rgb, float* image) {
-  if (!e || !verts || !rgb || !image) return fail("smalfit_render_color: null argument");
-  if (M <= 0 || M > e->maxM) return fail("smalfit_render_color: M exceeds the engine's max_frames");
+  if (refused("smalfit_render_color", null_argument_refusal(e && verts && rgb && image))) return 1;
+  if (refused("smalfit_render_color", render_frames_refusal(M, e->maxM))) return 1;
   hipStream_t st = (hipStream_t)stream;
   const ModelDev& m = e->model->dev;
   const size_t npx = (size_t)e->S * e->S;
@@ -1085,12 +1045,13 @@ int smalfit_render_color(smalfit_engine* e, void* stream, int M, const float* ve
     return fail("smalfit_render_color: hipMalloc of the z-buffer failed");
   if (!e->vnorm && hipMalloc(&e->vnorm, (size_t)e->maxM * 3 * m.Vp * sizeof(float)) != hipSuccess)
     return fail("smalfit_render_color: hipMalloc of the vertex normals failed");
-  interleaved_to_planar_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->verts);
-  project_verts_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
-  vnormal_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(m, M, e->verts, e->vnorm);
+  const dim3 vgrid(vertex_blocks(m.Vp), M);
+  interleaved_to_planar_kernel<<<vgrid, 256, 0, st>>>(M, m.V, m.Vp, verts, e->verts);
+  project_verts_kernel<<<vgrid, 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
+  vnormal_kernel<<<vgrid, 256, 0, st>>>(m, M, e->verts, e->vnorm);
   HIP_OK(hipMemsetAsync(e->zbuf, 0xff, (size_t)M * npx * sizeof(unsigned long long), st));
-  color_zbuf_kernel<<<dim3((m.F + 15) / 16, M), 256, 0, st>>>(m, e->S, e->proj, e->zbuf);
-  color_shade_kernel<<<dim3((unsigned)((npx + 255) / 256), M), 256, 0, st>>>(m, e->S, e->proj, e->verts, e->vnorm, e->zbuf, rgb[0], rgb[1],
+  color_zbuf_kernel<<<dim3(color_face_blocks(m.F), M), 256, 0, st>>>(m, e->S, e->proj, e->zbuf);
+  color_shade_kernel<<<dim3((unsigned)elem_blocks((long long)npx), M), 256, 0, st>>>(m, e->S, e->proj, e->verts, e->vnorm, e->zbuf, rgb[0], rgb[1],
                                                                             rgb[2], image);
   LAUNCH_OK("colour render kernels");
   return 0;
@@ -1098,40 +1059,38 @@ int smalfit_render_color(smalfit_engine* e, void* stream, int M, const float* ve
 
 int smalfit_render_backward(smalfit_engine* e, void* stream, int M, const float* verts, const float* sil,
                             const float* dsil, float* dverts) {
-  if (!e || !verts || !sil || !dsil || !dverts) return fail("smalfit_render_backward: null argument");
-  if (M <= 0 || M > e->maxM) return fail("smalfit_render_backward: M exceeds the engine's max_frames");
+  if (refused("smalfit_render_backward", null_argument_refusal(e && verts && sil && dsil && dverts))) return 1;
+  if (refused("smalfit_render_backward", render_frames_refusal(M, e->maxM))) return 1;
   hipStream_t st = (hipStream_t)stream;
   const ModelDev& m = e->model->dev;
-  project_verts_kernel<<<dim3(m.Vp / 256, M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
+  project_verts_kernel<<<dim3(vertex_blocks(m.Vp), M), 256, 0, st>>>(M, m.V, m.Vp, verts, e->proj);
   // recompute the forward (stateless adjoint): depth thresholds land in gz.y, then seed gz.x from dsil
   if (run_raster_forward(e, st, M, WinMap{1, 0, M}, 0.f, SilTarget{nullptr, nullptr}, e->silbuf, nullptr)) return 1;
   const size_t total = (size_t)M * e->S * e->S;
-  gpix_from_dsil_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(total, sil, dsil, e->gz);
+  gpix_from_dsil_kernel<<<(unsigned)elem_blocks((long long)total), 256, 0, st>>>(total, sil, dsil, e->gz);
   launch_raster_bwd(e, st, M);
-  raster_vertex_grad_kernel<<<dim3((m.V + 255) / 256, M), 256, 0, st>>>(m, e->proj, e->dface, dverts);
+  raster_vertex_grad_kernel<<<dim3(elem_blocks(m.V), M), 256, 0, st>>>(m, e->proj, e->dface, dverts);
   LAUNCH_OK("render_backward kernels");
   return 0;
 }
 
 int smalfit_project_points_backward(void* stream, int count, int image_size, const float* points, const float* dproj,
                                     float* dpoints) {
-  if (count <= 0 || !points || !dproj || !dpoints) return fail("smalfit_project_points_backward: bad argument");
-  project_points_bwd_kernel<<<(count + 255) / 256, 256, 0, (hipStream_t)stream>>>(count, image_size, points, dproj, dpoints);
+  if (refused("smalfit_project_points_backward", operator_args_refusal(count, points && dproj && dpoints))) return 1;
+  project_points_bwd_kernel<<<elem_blocks(count), 256, 0, (hipStream_t)stream>>>(count, image_size, points, dproj, dpoints);
   LAUNCH_OK("project_points_bwd_kernel");
   return 0;
 }
 
 int smalfit_pose_prior(smalfit_engine* e, void* stream, int N, const float* x, float* out) {
-  if (!e || !x || !out || N <= 0) return fail("smalfit_pose_prior: bad argument");
-  if (!e->has_pose_prior) return fail("smalfit_pose_prior: pose prior not set");
+  if (refused("smalfit_pose_prior", pose_prior_refusal(e && x && out, N, e && e->has_pose_prior))) return 1;
   pose_prior_kernel<<<N, 128, 0, (hipStream_t)stream>>>(x, e->pose_prec, e->pose_mean, e->pose_mask, out);
   LAUNCH_OK("pose_prior_kernel");
   return 0;
 }
 
 int smalfit_pose_prior_backward(smalfit_engine* e, void* stream, int N, const float* x, const float* dout, float* dx) {
-  if (!e || !x || !dout || !dx || N <= 0) return fail("smalfit_pose_prior_backward: bad argument");
-  if (!e->has_pose_prior) return fail("smalfit_pose_prior_backward: pose prior not set");
+  if (refused("smalfit_pose_prior_backward", pose_prior_refusal(e && x && dout && dx, N, e && e->has_pose_prior))) return 1;
   pose_prior_bwd_kernel<<<N, 128, 0, (hipStream_t)stream>>>(x, e->pose_prec, e->pose_mean, e->pose_mask, dout, dx);
   LAUNCH_OK("pose_prior_bwd_kernel");
   return 0;
@@ -1141,14 +1100,14 @@ int smalfit_temporal(smalfit_engine* e, void* stream, int N, float w_temp, const
                      const float* joint_rotations, const float* trans, const float* global_mask,
                      const float* rotation_mask, float* losses, float* g_global_rotation, float* g_joint_rotations,
                      float* g_trans) {
-  if (!e || !global_rotation || !joint_rotations || !trans || !losses) return fail("smalfit_temporal: null argument");
-  if (N <= 0 || N > e->maxM) return fail("smalfit_temporal: N exceeds the engine's max_frames");
+  if (refused("smalfit_temporal", null_argument_refusal(e && global_rotation && joint_rotations && trans && losses))) return 1;
+  if (refused("smalfit_temporal", temporal_frames_refusal(N, e->maxM))) return 1;
   hipStream_t st = (hipStream_t)stream;
   const float* gmask = global_mask ? global_mask : e->ones;
   const float* rmask = rotation_mask ? rotation_mask : e->ones;
-  build_theta_kernel<<<(N * 105 + 255) / 256, 256, 0, st>>>(N, global_rotation, joint_rotations, gmask, rmask, e->theta);
+  build_theta_kernel<<<elem_blocks(N * 105), 256, 0, st>>>(N, global_rotation, joint_rotations, gmask, rmask, e->theta);
   temporal_kernel<<<1, 128, 0, st>>>(N, w_temp, e->theta, trans, losses, e->dtheta, g_trans ? g_trans : e->dtr_direct);
-  split_theta_grad_kernel<<<(N * 105 + 255) / 256, 256, 0, st>>>(N, e->dtheta, gmask, rmask, g_global_rotation, g_joint_rotations);
+  split_theta_grad_kernel<<<elem_blocks(N * 105), 256, 0, st>>>(N, e->dtheta, gmask, rmask, g_global_rotation, g_joint_rotations);
   LAUNCH_OK("temporal kernels");
   return 0;
 }
@@ -1167,7 +1126,7 @@ static int launch_adam_segments(hipStream_t st, const AdamSegments& sg, const sm
   if (total == 0) return 0;
   float step_size, bc2_sqrt;
   adam_bias_terms(o->lr, o->beta1, o->beta2, t, step_size, bc2_sqrt);
-  adam_segments_kernel<<<(total + 255) / 256, 256, 0, st>>>(sg, o->param, o->grad, o->exp_avg, o->exp_avg_sq, step_size,
+  adam_segments_kernel<<<elem_blocks(total), 256, 0, st>>>(sg, o->param, o->grad, o->exp_avg, o->exp_avg_sq, step_size,
                                                            o->beta1, o->beta2, o->eps, bc2_sqrt, fresh ? 1 : 0);
   LAUNCH_OK("adam_segments_kernel");
   return 0;
@@ -1182,13 +1141,13 @@ static int launch_adam_next_step(hipStream_t st, const smalfit_adam_args* o) {
 }  // namespace smalfit
 
 int smalfit_adam_segments(void* stream, const smalfit_adam_args* o) {
-  if (!o) return fail("smalfit_adam_segments: null argument");
-  if (o->step < 0) return fail("smalfit_adam_segments: step must be >= 0");
+  if (refused("smalfit_adam_segments", null_argument_refusal(o != nullptr))) return 1;
+  if (refused("smalfit_adam_segments", step_refusal(o->step))) return 1;
   return launch_adam_next_step((hipStream_t)stream, o);
 }
 
 int smalfit_engine_set_graph(smalfit_engine* e, int enable) {
-  if (!e) return fail("smalfit_engine_set_graph: null argument");
+  if (refused("smalfit_engine_set_graph", null_argument_refusal(e != nullptr))) return 1;
   e->use_graph = enable != 0;
   if (!e->use_graph && e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; e->graph_key.clear(); }
   return 0;
@@ -1198,7 +1157,7 @@ namespace smalfit {
 static int launch_adam_graph_node(smalfit_engine* e, hipStream_t st, const AdamSegments& sg, const smalfit_adam_args* o) {
   const int total = sg.off[sg.nseg];
   if (total == 0) return 0;
-  adam_segments_graph_kernel<<<(total + 255) / 256, 256, 0, st>>>(sg, o->param, o->grad, o->exp_avg, o->exp_avg_sq, e->step_counter,
+  adam_segments_graph_kernel<<<elem_blocks(total), 256, 0, st>>>(sg, o->param, o->grad, o->exp_avg, o->exp_avg_sq, e->step_counter,
                                                                  o->lr, o->beta1, o->beta2, o->eps);
   LAUNCH_OK("adam_segments_graph_kernel");
   return 0;
@@ -1307,16 +1266,15 @@ static int run_plain_chain(smalfit_engine* e, hipStream_t st, const smalfit_fit_
 }  // namespace smalfit
 
 int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const smalfit_adam_args* o, int iterations) {
-  if (!e || !a || !o) return fail("smalfit_fit_run: null argument");
-  if (iterations <= 0) return fail("smalfit_fit_run: iterations must be positive");
-  if (o->step < 0) return fail("smalfit_fit_run: step must be >= 0");
+  if (refused("smalfit_fit_run", null_argument_refusal(e && a && o))) return 1;
+  if (refused("smalfit_fit_run", iterations_refusal(iterations))) return 1;
+  if (refused("smalfit_fit_run", step_refusal(o->step))) return 1;
   if (refused("smalfit_fit_run", fit_args_size_refusal(a))) return 1;
   if (refused("smalfit_fit_run", fit_model_refusal(e->model->NBall))) return 1;   // (before a capture could begin)
   AdamSegments sg;
   if (packed_adam_segments(o, sg)) return 1;
   hipStream_t st = (hipStream_t)stream;
-  if (e->use_graph && a->subject_frames != 0)
-    return fail("smalfit_fit_run: subject_frames != 0 is not supported by the graph replay (smalfit_engine_set_graph)");
+  if (refused("smalfit_fit_run", graph_subject_refusal(e->use_graph, a))) return 1;
   const FoldPlan plan = plan_fold(a, o, sg);
   switch (run_loop(e->use_graph, e->prof_on, iterations, st != nullptr, plan.accepted())) {
     case RunLoop::Graph: return run_graph_replay(e, st, a, o, sg, iterations);
@@ -1329,9 +1287,9 @@ int smalfit_fit_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, 
 int smalfit_shard_record(void* stream, int num_shared, const float* shared_grad, int num_frames, const float* global_rotation,
                          const float* joint_rotations, const float* trans, const float* global_mask,
                          const float* rotation_mask, float* record) {
-  if (num_shared < 0 || !shared_grad || num_frames <= 0 || !global_rotation || !joint_rotations || !trans || !global_mask ||
-      !rotation_mask || !record) return fail("smalfit_shard_record: bad argument");
-  shard_record_kernel<<<(num_shared + 216 + 255) / 256, 256, 0, (hipStream_t)stream>>>(num_shared, shared_grad, num_frames, global_rotation,
+  if (refused("smalfit_shard_record", shard_record_refusal(num_shared, num_frames, shared_grad && global_rotation && joint_rotations && trans &&
+                                                                                         global_mask && rotation_mask && record))) return 1;
+  shard_record_kernel<<<elem_blocks(num_shared + 216), 256, 0, (hipStream_t)stream>>>(num_shared, shared_grad, num_frames, global_rotation,
                                                                                     joint_rotations, trans, global_mask, rotation_mask, record);
   LAUNCH_OK("shard_record_kernel");
   return 0;
@@ -1339,10 +1297,9 @@ int smalfit_shard_record(void* stream, int num_shared, const float* shared_grad,
 
 int smalfit_shard_local_step(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const smalfit_adam_args* o, int num_shared,
                              const float* shared_grad, float* record) {
-  if (!e || !a || !o || !record || !shared_grad) return fail("smalfit_shard_local_step: null argument");
-  if (o->step < 0) return fail("smalfit_shard_local_step: step must be >= 0");
-  if (!fit_args_size_refusal(a) && a->subject_frames != 0)   // (a block of another header is refused by the evaluation below)
-    return fail("smalfit_shard_local_step: subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)");
+  if (refused("smalfit_shard_local_step", null_argument_refusal(e && a && o && record && shared_grad))) return 1;
+  if (refused("smalfit_shard_local_step", step_refusal(o->step))) return 1;
+  if (refused("smalfit_shard_local_step", shard_subject_refusal(a))) return 1;
   if (smalfit_fit_eval(e, stream, a)) return 1;
   if (launch_adam_next_step((hipStream_t)stream, o)) return 1;
   return smalfit_shard_record(stream, num_shared, shared_grad, a->num_frames, a->global_rotation, a->joint_rotations, a->trans,
@@ -1351,12 +1308,10 @@ int smalfit_shard_local_step(smalfit_engine* e, void* stream, const smalfit_fit_
 
 int smalfit_shard_reduce_step(void* stream, int world_size, int record_stride, const float* gathered, int num_shared,
                               int num_trainable, const smalfit_adam_args* o) {
-  if (world_size <= 0 || record_stride < num_shared || !gathered || num_shared <= 0 || num_trainable < 0 || num_trainable > num_shared || !o)
-    return fail("smalfit_shard_reduce_step: bad argument");
-  if (!o->param || !o->grad || !o->exp_avg || !o->exp_avg_sq || o->step < 0) return fail("smalfit_shard_reduce_step: bad optimiser state");
+  if (refused("smalfit_shard_reduce_step", shard_reduce_refusal(world_size, record_stride, gathered != nullptr, num_shared, num_trainable, o))) return 1;
   float step_size, bc2_sqrt;
   adam_bias_terms(o->lr, o->beta1, o->beta2, o->step + 1, step_size, bc2_sqrt);
-  shard_reduce_adam_kernel<<<(num_shared + 255) / 256, 256, 0, (hipStream_t)stream>>>(world_size, record_stride, gathered, num_shared, num_trainable,
+  shard_reduce_adam_kernel<<<elem_blocks(num_shared), 256, 0, (hipStream_t)stream>>>(world_size, record_stride, gathered, num_shared, num_trainable,
                                                                                    o->param, o->grad, o->exp_avg, o->exp_avg_sq, step_size,
                                                                                    o->beta1, o->beta2, o->eps, bc2_sqrt, o->step == 0 ? 1 : 0);
   LAUNCH_OK("shard_reduce_adam_kernel");
@@ -1365,7 +1320,7 @@ int smalfit_shard_reduce_step(void* stream, int world_size, int record_stride, c
 
 int smalfit_rccl_allgather(void* ctx, const float* send, float* recv, int count, void* stream) {
   const smalfit_rccl_ctx* c = (const smalfit_rccl_ctx*)ctx;
-  if (!c || !c->comm || !c->nccl_all_gather) return fail("smalfit_rccl_allgather: no communicator / ncclAllGather address");
+  if (!c || !c->comm || !c->nccl_all_gather) return refused("smalfit_rccl_allgather", "no communicator / ncclAllGather address");
   typedef int (*all_gather_t)(const void*, void*, size_t, int, void*, hipStream_t);
   const int kNcclFloat32 = 7;                                   // ncclDataType_t: ncclFloat32
   const int rc = ((all_gather_t)c->nccl_all_gather)(send, recv, (size_t)count, kNcclFloat32, c->comm, (hipStream_t)stream);
@@ -1375,16 +1330,8 @@ int smalfit_rccl_allgather(void* ctx, const float* send, float* recv, int count,
 
 int smalfit_shard_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a, const smalfit_adam_args* ol,
                       const smalfit_adam_args* os, const smalfit_shard_args* sh, int iterations) {
-  if (!e || !a || !ol || !os || !sh) return fail("smalfit_shard_run: null argument");
-  if (sh->struct_size != (unsigned)sizeof(smalfit_shard_args))
-    return fail("smalfit_shard_run: smalfit_shard_args.struct_size does not match this library (built against another smalfit.h?)");
-  if (iterations <= 0) return fail("smalfit_shard_run: iterations must be positive");
-  if (sh->world_size <= 0 || sh->rank < 0 || sh->rank >= sh->world_size) return fail("smalfit_shard_run: bad rank / world_size");
-  if (sh->num_shared <= 0 || sh->num_trainable_shared < 0 || sh->num_trainable_shared > sh->num_shared) return fail("smalfit_shard_run: bad num_shared / num_trainable_shared");
-  if (!sh->shared_grad || !sh->record || !sh->gathered || !sh->allgather) return fail("smalfit_shard_run: missing buffer / collective");
-  if (ol->step < 0 || os->step != ol->step) return fail("smalfit_shard_run: adam_local and adam_shared must carry the same step >= 0");
-  if (!fit_args_size_refusal(a) && a->subject_frames != 0)
-    return fail("smalfit_shard_run: subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)");
+  if (refused("smalfit_shard_run", null_argument_refusal(e && a && ol && os && sh))) return 1;
+  if (refused("smalfit_shard_run", shard_run_refusal(a, ol, os, sh, iterations))) return 1;
   const int stride = sh->num_shared + 216;
   for (int it = 0; it < iterations; ++it) {
     smalfit_adam_args l = *ol, s = *os;
@@ -1401,7 +1348,7 @@ int smalfit_shard_run(smalfit_engine* e, void* stream, const smalfit_fit_args* a
 
 int smalfit_adam_step(void* stream, int count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                       float lr, float beta1, float beta2, float eps, int t) {
-  if (count <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || t <= 0) return fail("smalfit_adam_step: bad argument");
+  if (refused("smalfit_adam_step", adam_step_refusal(count, param && grad && exp_avg && exp_avg_sq, t))) return 1;
   // one range [0, count); the moments are always read, also at t = 1
   smalfit_adam_args o{};
   o.param = param; o.grad = const_cast<float*>(grad); o.exp_avg = exp_avg; o.exp_avg_sq = exp_avg_sq;

@@ -1,7 +1,8 @@
 // What the host decides before it launches anything, each rule once, as a pure function or a constant: which loop
 // smalfit_fit_run runs, whether an optimiser step can ride in the next head launch and where the shared parameters then
-// travel, which skinning kernel runs, the geometry of the launches that depends on the problem's size, and which argument
-// blocks are refused.  Plain C++17 over include/smalfit.h and the standard library -- no HIP -- so that the library
+// travel, which skinning kernel runs, what an evaluation launches and with which switches (plan_eval), the geometry of the
+// launches that depends on the problem's size -- with the constants the kernels decode their block roles by, defined here once --
+// and which arguments are refused.  Plain C++17 over include/smalfit.h and the standard library -- no HIP -- so that the library
 // (smalfit_launch.inc, smalfit_mesh3d.inc) and the CPU tests (tests/host_plan_shim.cpp, compiled by g++) call the same code.
 #pragma once
 #include <algorithm>
@@ -19,6 +20,9 @@ constexpr int kBetaGroups = 8;         // frame groups of the shape-blend adjoin
 // against an error of ~rows * 2^-22, and byte offsets row * 8 S + 8 col stay below 2^24, for S <= 1024 -- twice the largest size
 // the reference uses (config 5: 512).  Larger images are rejected rather than walked inexactly.
 constexpr int kMaxImageSize = 1024;
+// (the next three still mirror a constant that a kernel file defines under another name, tied by a static_assert where both are
+// visible: tests/test_fold_forms_cpu.py pins kPriorFrames's definition in kernels_lbs_forward.inc, and smalfit_mesh3d.inc names
+// both halves of the other two pairs.  Every other constant a launch is sized by is defined below, once)
 constexpr int kHeadPriorFrames = 16;   // frames per prior block of lbs_head_images_kernel (kPriorFrames of kernels_lbs_forward.inc)
 constexpr int kMeshQueries = 64;       // queries per chamfer block (kChamQueries of kernels_mesh3d.inc)
 constexpr int kMeshThreads = 256;      // vertices / face pairs per block of the ring and gather kernels (kMeshBlock)
@@ -60,6 +64,91 @@ inline int head_prior_blocks(int M, HeadPrior prior) {
 inline int head_blocks(int M, int Vp, bool shape_per_frame, HeadPrior prior) {
   return M + head_shape_blocks(M, Vp, shape_per_frame) + head_prior_blocks(M, prior);
 }
+
+// ------------------------------------------------------------------------------------------------
+// grids of the fit path with their riders: the host launches what these return, the kernels decode their roles through the same
+// functions and constants (constexpr: callable from device code)
+// ------------------------------------------------------------------------------------------------
+// Frame-to-XCD affinity of the per-frame kernels (kernels_raster.inc: xcd_block): a 1-D grid in which frame n's workgroups land on
+// XCD n % 8, so frames are dealt in rounds of eight
+constexpr int xcd_frames(int M) { return ((M + 7) / 8) * 8; }
+constexpr int xcd_grid(int blocks_per_frame, int M) { return blocks_per_frame * ((M + 7) / 8) * 8; }
+// threads per workgroup of every kernel below unless it says otherwise; elementwise launches: one thread per element
+constexpr int elem_blocks(long long elements) { return (int)((elements + 255) / 256); }
+constexpr int vertex_blocks(int Vp) { return Vp / 256; }
+constexpr int rigid_blocks(int count) { return (count + 63) / 64; }           // global_rigid_kernel and its adjoint: one wave per workgroup, a lane per chain
+constexpr int color_face_blocks(int F) { return (F + 15) / 16; }             // color_zbuf_kernel: 16 faces per workgroup
+
+// skinning: (vertex blocks, frame tiles) of the form skin_form chose
+constexpr int kSkinGroups = 2;               // skin_mfma_split_kernel: 16-vertex groups per workgroup (4 waves each): they share the staged transforms of the 16 frames
+constexpr int kSkinVerts = 16 * kSkinGroups;       // its vertices per workgroup
+constexpr int kSkinThreads = 256 * kSkinGroups;    // and its threads
+struct Grid2 { int x, y; };
+constexpr Grid2 skin_grid(SkinForm form, int M, int Vp) {
+  return form == SkinForm::Wide ? Grid2{Vp / 64, (M + 15) / 16} : form == SkinForm::Split ? Grid2{Vp / kSkinVerts, (M + 15) / 16} : Grid2{Vp / 64, (M + 7) / 8};
+}
+constexpr int kJointBlocks = 41;             // joints_kernel / the box kernel's joint riders: one workgroup per regressed joint and frame
+
+// face_bbox_kernel: [frame blocks, a multiple of 8] [face blocks of 256 faces, frame n on XCD n % 8] [joint riders, 41 per frame]
+constexpr int box_frame_blocks(int M) { return xcd_frames(M); }
+constexpr int box_blocks_per_frame(int F) { return (F + 255) / 256; }
+constexpr int box_face_blocks(int F, int M) { return xcd_grid(box_blocks_per_frame(F), M); }
+constexpr int box_joint_blocks(int M, bool joints) { return joints ? kJointBlocks * M : 0; }
+constexpr int box_grid(int F, int M, bool joints) { return box_frame_blocks(M) + box_face_blocks(F, M) + box_joint_blocks(M, joints); }
+
+// raster_sweep_kernel
+constexpr int kRectFaces = 8;                // faces per entry of the union-box index
+constexpr int kSweepFaces = 32;              // faces per sweep block
+constexpr int rect_count(int F) { return (F + kRectFaces - 1) / kRectFaces; }
+constexpr int sweep_blocks_per_frame(int F) { return (F + kSweepFaces - 1) / kSweepFaces; }
+constexpr int sweep_grid(int F, int M) { return xcd_grid(sweep_blocks_per_frame(F), M); }
+
+// raster_resolve_kernel: [loss riders, one per frame, padded to a multiple of 8] [tiles of kResEdge^2 pixels, frame n on XCD n % 8]
+constexpr int kResSub = 2;                   // a resolve workgroup takes (16 kResSub)^2 pixels, kResSub^2 per thread: the launch is
+                                             // bound by the number of workgroups, not by bytes
+constexpr int kResEdge = 16 * kResSub;
+constexpr int resolve_tiles_x(int S) { return (S + kResEdge - 1) / kResEdge; }
+constexpr int resolve_tiles(int S) { return resolve_tiles_x(S) * resolve_tiles_x(S); }
+constexpr int resolve_loss_blocks(int loss_frames) { return loss_frames > 0 ? ((loss_frames + 7) / 8) * 8 : 0; }
+constexpr int resolve_grid(int tiles, int M, int loss_frames) { return xcd_grid(tiles, M) + resolve_loss_blocks(loss_frames); }
+
+// raster_band_kernel / raster_select_kernel: persistent grids
+constexpr int kBandBlocks = 1536;
+constexpr int kSelWaves = 2;                 // waves per select block: 11 KB of LDS per wave -> 7 blocks (14 waves) per CU
+constexpr int kSelGroups = 16;               // ticket counters per XCD of the selection kernel (one per group of its workgroups)
+constexpr int kSelectBlocks = 1792;          // 7 resident 2-wave blocks x 256 CUs
+static_assert(kSelectBlocks % (8 * kSelGroups) == 0, "every ticket group of every XCD needs the same number of selection workgroups (a group without one would leave its pixels undone)");
+constexpr int kQueueLossBlocks = kSelectBlocks + kBandBlocks;   // partials of the queue kernels' loss: the select kernel's, then the band kernel's
+constexpr int kFrameLossStride = 32;         // unsigned long longs between two frames' counters of the queue kernels' loss
+
+// raster_bwd_kernel
+constexpr int kBwdLanes = 16;                // lanes per face of the backward gather
+constexpr int kBwdFaces = 4;                 // faces per workgroup
+constexpr int raster_bwd_blocks_per_frame(int F) { return (F + kBwdFaces - 1) / kBwdFaces; }
+constexpr int raster_bwd_grid(int F, int M) { return xcd_grid(raster_bwd_blocks_per_frame(F), M); }
+
+// vertex_bwd_kernel
+constexpr int vertex_bwd_grid(int Vp, int M) { return xcd_grid(vertex_blocks(Vp), M); }
+
+// lbs_bwd_mid_kernel: [pose-blend ids] [dA blocks].  Block -> XCD placement of the pose-blend part: the 10 feature-pair blocks of one
+// column split read the same columns of dvp: their ids are laid out as chunks of 8 splits x 10 feature pairs with the split in
+// the low 3 bits, per chunk of PBM_TILES tiles of 16 frames
+constexpr int PBM_SPLITS = 24, PBM_TILES = 4;
+static_assert(PBM_SPLITS % 8 == 0, "the blocks of a column split are placed on one XCD (ids in chunks of 8 splits)");
+constexpr int mid_pb_ids(int M) { return 10 * PBM_SPLITS * (((M + 15) / 16 + PBM_TILES - 1) / PBM_TILES); }
+constexpr int mid_da_ids(int M) { return xcd_grid(35, M); }       // dA blocks: frame n on XCD n % 8 (see vertex_bwd_kernel)
+constexpr int mid_grid(int M, int nPB) { return (nPB ? mid_pb_ids(M) : 0) + mid_da_ids(M); }
+
+// chain_bwd_kernel: [M frame blocks] [the dbeta partials' riders]
+inline int chain_grid(int M, const DbetaGrid& db) { return M + db.blocks(); }
+
+// assemble_kernel: [one block per shape set] [limb scales] [kAsmElem element blocks] [kAsmLoss loss partials]
+constexpr int kAsmElem = 4, kAsmLoss = 16;   // blocks for element-wise gradients / loss partial sums
+constexpr int kAsmRows = 4;                  // blocks of frame_loss_rows_kernel
+constexpr int asm_shape_sets(int betas_shared, int M) { return betas_shared ? 1 : M; }
+constexpr int assemble_grid(int shape_sets) { return shape_sets + 1 + kAsmElem + kAsmLoss; }
+constexpr int window_rows_grid(int W) { return W; }                // one block per row
+constexpr int frame_loss_rows_grid() { return kAsmRows; }
 
 // the kinematic tree is walked root first: every joint's parent precedes it
 inline bool parents_ordered(const int* parents, int num_joints) {
@@ -189,6 +278,7 @@ struct EngineFacts {
   int max_frames;        // the engine's capacity
   bool has_pose_prior;   // smalfit_engine_set_pose_prior was called
   int shape_dim;         // dimension given to smalfit_engine_set_shape_prior, 0: none
+  bool has_joint_limits = false;   // smalfit_engine_set_joint_limits was called (and not cleared since)
 };
 // -> why smalfit_fit_eval refuses the block (the text behind "smalfit_fit_eval: "), or nullptr
 inline const char* fit_args_refusal(const smalfit_fit_args* a, const EngineFacts& e) {
@@ -229,6 +319,17 @@ inline int prior_windows(int window, int frame_offset, int M) {
   return (frame_offset + M + window - 1) / window - (frame_offset + window - 1) / window;
 }
 
+// Where the M frames of an evaluation sit in their sequence: frames are grouped into consecutive windows of `window`
+// frames counted from the START OF THE SEQUENCE (optimize_to_joints.py:119-120, the last window may be ragged), and the
+// reference's per-window normalisers 1/(B 50), 1/(B 105), 1/(B S^2) (smal_fitter.py:144,157,173) use the size B of the
+// window a frame belongs to.  An evaluation may hold any contiguous part of the sequence -- a whole sequence
+// (offset 0, total M), a shard of it, or a single frame of an 8-frame window (one frame per GPU).
+struct WinMap {
+  int window;   // WINDOW_SIZE
+  int offset;   // index of local frame 0 in the sequence
+  int total;    // frames in the whole sequence
+};
+
 // ------------------------------------------------------------------------------------------------
 // smalfit_window_rows: one row per window of the sequence (smalfit_fit_eval_windows)
 // ------------------------------------------------------------------------------------------------
@@ -255,6 +356,224 @@ inline const char* window_rows_refusal(const smalfit_fit_args* a, const smalfit_
     return "smalfit_window_rows.g_log_beta_scales needs shared log_beta_scales (logscale_mode 1)";
   return nullptr;
 }
+
+// ------------------------------------------------------------------------------------------------
+// one evaluation (smalfit_fit_eval, smalfit_fit_eval_windows, the evaluations of smalfit_fit_run): what it launches, with
+// which switches.  fit_eval_impl fills its argument structs from these fields and the pointers of the block; it decides nothing
+// ------------------------------------------------------------------------------------------------
+// How the caller strings evaluations together and which rows it wants beside the totals
+struct EvalMode {
+  bool pending = false;      // the head launch takes over the optimiser step the previous evaluation left (smalfit_fit_run)
+  bool assemble = true;      // run assemble_kernel (gradients to the caller's buffers, the nine loss terms)
+  // smalfit_fit_eval_windows: one row per window (window_rows_refusal has accepted the rows)
+  bool window_rows = false;
+  bool want_betas = false;   // smalfit_window_rows.g_betas given
+  bool want_scales = false;  // smalfit_window_rows.g_log_beta_scales given
+};
+enum class HeadKernel { Plain = 0, Images = 1, Step = 2 };   // lbs_head_kernel | lbs_head_images_kernel | lbs_head_step_kernel
+enum class SilTargetKind { None = 0, F32 = 1, U8 = 2 };
+enum class LossLaunch { OwnKernel = 0, InResolve = 1 };     // loss_kernel | riders of raster_resolve_kernel
+struct EvalPlan {
+  // frames and strides
+  int M;
+  WinMap win;                // where the M frames sit in their sequence
+  bool independent;          // every frame its own subject
+  int nb;                    // shape directions the fitter optimises
+  int betas_stride;          // floats between two frames' betas; 0: one shape for all
+  int ls_stride;             // floats between two frames' limb scales; 0: one set for all
+  bool limb_scales;          // log_beta_scales is read at all
+  // shape prior
+  bool shape_prior;
+  int prior_dim;             // 0 without the prior
+  bool prior_uses_ls;        // the prior spans the limb scales too (dimension above 20)
+  int prior_windows;         // windows whose prior term this evaluation owns (independent images: window = 1, so one per image)
+  float prior_weight;        // w_betas x the owned windows; independent images: w_betas, once per image
+  bool prior_per_frame;
+  HeadPrior head_prior;
+  // head kernel
+  HeadKernel head;
+  // silhouette and rasteriser
+  bool sil_on;               // the silhouette term is in the loss
+  bool rasterise;            // the rasteriser runs: for the term or for sil_out alone
+  SilTargetKind sil_target;
+  bool frame_loss;           // the queue kernels also count their loss per frame (the kFrameLoss instantiations)
+  bool queue_loss;           // the queue kernels write their loss partials at all
+  bool raster_backward;
+  // loss launch
+  LossLaunch loss_launch;
+  bool joints_in_head;       // joints_kernel runs behind the skinning (else its blocks ride in the box kernel)
+  // effective weights
+  float w_temp;              // 0 unless `temporal`
+  float w_limit;             // 0 unless the engine has a limit table: the reference's weight table carries w_limit = 100 in stages
+                             // 1-3 while the term itself is commented out (smal_fitter.py:146-151)
+  bool halos;                // halo_prev / halo_next are read (where given)
+  // outputs and adjoints
+  bool verts_out;
+  bool need_pose, need_beta, need_ls;
+  // backward
+  int bwd_betas_shared;      // the dbeta partials are summed over the frames (0: one row of partials per frame)
+  int j_stride;              // floats between two frames' rest joints; 0: one set
+  // assembly
+  int asm_betas_shared, asm_ls_shared;
+  int ngrp_beta;             // frame groups of the dbeta partials the assembly would add up
+  int asm_shape_sets;        // blocks of assemble_kernel's first role
+  // per-frame rows
+  bool rows;                 // frame_loss_rows_kernel writes losses_per_frame
+  // window rows
+  int W;                     // rows; 0 without them
+  bool ls_rows;              // the shared limb scales' gradient is formed per window too
+  int clear_qloss;           // window_rows_kernel is the last reader of the per-frame loss counters and clears them
+  bool assembly_leaves_betas, assembly_leaves_scales;   // ... to window_rows_kernel
+};
+// -> the plan of a block that fit_args_refusal and fit_model_refusal accept (and, with window rows, window_rows_refusal)
+inline EvalPlan plan_eval(const smalfit_fit_args* a, const EngineFacts& e, const EvalMode& mode) {
+  EvalPlan p{};
+  const int M = p.M = a->num_frames;
+  p.win = WinMap{a->window, a->frame_offset, sequence_frames(a)};
+  const bool indep = p.independent = independent_images(a);
+  const bool wr = mode.window_rows;
+  p.nb = kFitBetas;
+  p.betas_stride = indep ? p.nb : 0;
+  p.ls_stride = a->logscale_mode == 2 ? 6 : 0;
+  p.limb_scales = a->logscale_mode != 0;
+
+  p.shape_prior = a->w_betas > 0.f;
+  p.prior_dim = p.shape_prior ? shape_prior_dim(a, e.shape_dim) : 0;
+  p.prior_uses_ls = prior_uses_limb_scales(a, e.shape_dim);
+  p.prior_windows = p.shape_prior ? prior_windows(p.win.window, p.win.offset, M) : 0;
+  p.prior_weight = !p.shape_prior ? 0.f : (indep ? a->w_betas : a->w_betas * (float)p.prior_windows);
+  p.prior_per_frame = p.shape_prior && indep;
+  p.head_prior = !p.shape_prior ? HeadPrior::None : (indep ? HeadPrior::PerFrame : HeadPrior::Shared);
+  // (one subject under a pending step: plan_fold refuses independent images.  Independent images without the prior take the plain kernel)
+  p.head = mode.pending ? HeadKernel::Step : (p.prior_per_frame ? HeadKernel::Images : HeadKernel::Plain);
+
+  p.sil_on = a->w_sil > 0.f;
+  p.rasterise = p.sil_on || a->sil_out != nullptr;
+  p.sil_target = !p.sil_on ? SilTargetKind::None : (a->target_sil_u8 ? SilTargetKind::U8 : SilTargetKind::F32);
+  // one row of loss terms per frame: only an evaluation that assembles writes (and clears the counters behind) them
+  p.rows = a->losses_per_frame != nullptr && mode.assemble;
+  p.frame_loss = (p.rows || wr) && p.sil_on;
+  p.queue_loss = p.sil_on;
+  p.raster_backward = p.sil_on;
+  // with the rasteriser running, the joint regression and the loss terms ride in its launches
+  p.loss_launch = p.rasterise ? LossLaunch::InResolve : LossLaunch::OwnKernel;
+  p.joints_in_head = !p.rasterise;
+
+  p.w_temp = a->temporal ? a->w_temp : 0.f;
+  p.w_limit = e.has_joint_limits ? a->w_limit : 0.f;
+  p.halos = a->temporal != 0;
+
+  p.verts_out = a->verts_out != nullptr;
+  p.need_pose = a->g_joint_rotations != nullptr;
+  p.need_beta = a->g_betas != nullptr || (wr && mode.want_betas);
+  p.need_ls = (a->g_log_beta_scales != nullptr || (wr && mode.want_scales)) && a->logscale_mode != 0;
+
+  // independent images: per-frame partials of the shape-blend adjoint, per-frame rest joints; window rows: the same partial
+  // layout -- M rows of nblk_beta * nb floats, dbeta_rows() holds them -- over the one shared shape
+  p.bwd_betas_shared = (indep || wr) ? 0 : 1;
+  p.j_stride = indep ? 105 : 0;
+
+  p.asm_betas_shared = indep ? 0 : 1;
+  p.asm_ls_shared = indep ? 0 : (a->logscale_mode == 1 ? 1 : 0);
+  // (odd, and kept: under window rows the backward pass wrote ONE group of per-frame partials, yet this stays the shared
+  // shape's group count.  Nothing reads it then: the assembly leaves the betas to window_rows_kernel, which walks the rows itself)
+  p.ngrp_beta = beta_groups(!indep);
+  p.asm_shape_sets = asm_shape_sets(p.asm_betas_shared, M);
+
+  // (window_rows_refusal has checked the caller's num_windows against this count)
+  p.W = wr ? window_rows_count(a->window, a->frame_offset, M) : 0;
+  p.ls_rows = wr && p.need_ls && a->logscale_mode == 1;
+  p.clear_qloss = wr && !p.rows ? 1 : 0;
+  // the assembly leaves the shared gradients to window_rows_kernel (per-frame limb scales stay its own)
+  p.assembly_leaves_betas = wr;
+  p.assembly_leaves_scales = wr && a->logscale_mode == 1;
+  return p;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the other entry points: which arguments are refused.  Each returns the text behind "<entry point>: " or nullptr; the first
+// fault is reported.  Pointers are asked for as `given` (all of them present), nothing is dereferenced unless it says so
+// ------------------------------------------------------------------------------------------------
+inline const char* null_argument_refusal(bool given) { return given ? nullptr : "null argument"; }
+inline const char* bad_argument_refusal(bool good) { return good ? nullptr : "bad argument"; }
+// the stateless operators (rodrigues, rigid transformation, point projection and their adjoints): a count and pointers
+inline const char* operator_args_refusal(int count, bool given) { return bad_argument_refusal(count > 0 && given); }
+inline const char* step_refusal(int step) { return step >= 0 ? nullptr : "step must be >= 0"; }
+inline const char* iterations_refusal(int iterations) { return iterations > 0 ? nullptr : "iterations must be positive"; }
+
+// smalfit_engine_create
+inline const char* engine_create_refusal(bool given, int max_frames, int image_size) {
+  if (!given || max_frames <= 0 || image_size <= 0) return "bad argument";
+  static_assert(kMaxImageSize == 1024, "the message below names the limit");
+  if (image_size > kMaxImageSize) return "image_size above 1024 is not supported (float32 pixel walk, see kernels_raster.inc)";
+  return nullptr;
+}
+constexpr int kMaxShapePriorDim = 26;        // 20 betas | 6 limb scales
+inline const char* shape_prior_refusal(bool given, int dim) {
+  static_assert(kMaxShapePriorDim == 26, "the message below names the limit");
+  return given && dim > 0 && dim <= kMaxShapePriorDim ? nullptr : "bad argument (dim must be 1..26)";
+}
+// (reads the 102 limits of both tables)
+inline const char* joint_limits_refusal(const float* min_values, const float* max_values) {
+  if (!min_values || !max_values) return "null argument";
+  for (int i = 0; i < 102; ++i)
+    if (!(min_values[i] <= max_values[i])) return "min must not exceed max";
+  return nullptr;
+}
+inline const char* option_refusal(int option, int value) {
+  switch (option) {
+    case SMALFIT_OPT_UNCLAMPED_EDGE_T: return value == 0 || value == 1 ? nullptr : "SMALFIT_OPT_UNCLAMPED_EDGE_T takes 0 or 1";
+    default: return "unknown option";
+  }
+}
+inline const char* profile_begin_refusal(bool given, int max_evals, int stride) { return bad_argument_refusal(given && max_evals > 0 && stride > 0); }
+
+// smalfit_lbs_forward_ex / smalfit_lbs_backward_ex (SMAL.__call__ and its adjoint)
+inline const char* lbs_args_refusal(const smalfit_lbs_args* a, int max_frames, int model_betas) {
+  if (a->num_frames <= 0 || a->num_frames > max_frames) return "num_frames exceeds the engine's max_frames";
+  if (a->num_betas <= 0 || a->num_betas > model_betas) return "num_betas out of range";
+  if (!a->beta) return "beta missing";
+  if ((a->theta == nullptr) == (a->Rs == nullptr)) return "give exactly one of theta (axis-angle) and Rs (rotation matrices)";
+  return nullptr;
+}
+inline const char* lbs_outputs_refusal(const smalfit_lbs_args* a) { return a->verts && a->joints ? nullptr : "verts / joints outputs missing"; }
+
+// smalfit_render_forward / _color / _backward, smalfit_temporal: a frame count against the engine's capacity
+inline const char* render_frames_refusal(int M, int max_frames) { return M > 0 && M <= max_frames ? nullptr : "M exceeds the engine's max_frames"; }
+inline const char* temporal_frames_refusal(int N, int max_frames) { return N > 0 && N <= max_frames ? nullptr : "N exceeds the engine's max_frames"; }
+// smalfit_pose_prior / _backward
+inline const char* pose_prior_refusal(bool given, int N, bool has_pose_prior) {
+  if (!given || N <= 0) return "bad argument";
+  return has_pose_prior ? nullptr : "pose prior not set";
+}
+
+// smalfit_fit_run under smalfit_engine_set_graph; the shard entry points.  (`a` has passed fit_args_size_refusal or is not read:
+// subject_frames sits at the block's tail.)
+inline const char* graph_subject_refusal(bool graph_on, const smalfit_fit_args* a) {
+  return graph_on && a->subject_frames != 0 ? "subject_frames != 0 is not supported by the graph replay (smalfit_engine_set_graph)" : nullptr;
+}
+inline const char* shard_subject_refusal(const smalfit_fit_args* a) {
+  // (a block of another header is refused by the evaluation itself)
+  return !fit_args_size_refusal(a) && a->subject_frames != 0
+             ? "subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)" : nullptr;
+}
+inline const char* shard_record_refusal(int num_shared, int num_frames, bool given) { return bad_argument_refusal(num_shared >= 0 && num_frames > 0 && given); }
+inline const char* shard_reduce_refusal(int world_size, int record_stride, bool gathered, int num_shared, int num_trainable, const smalfit_adam_args* o) {
+  if (world_size <= 0 || record_stride < num_shared || !gathered || num_shared <= 0 || num_trainable < 0 || num_trainable > num_shared || !o) return "bad argument";
+  if (!o->param || !o->grad || !o->exp_avg || !o->exp_avg_sq || o->step < 0) return "bad optimiser state";
+  return nullptr;
+}
+inline const char* shard_run_refusal(const smalfit_fit_args* a, const smalfit_adam_args* ol, const smalfit_adam_args* os, const smalfit_shard_args* sh, int iterations) {
+  if (sh->struct_size != (unsigned)sizeof(smalfit_shard_args)) return "smalfit_shard_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (iterations <= 0) return "iterations must be positive";
+  if (sh->world_size <= 0 || sh->rank < 0 || sh->rank >= sh->world_size) return "bad rank / world_size";
+  if (sh->num_shared <= 0 || sh->num_trainable_shared < 0 || sh->num_trainable_shared > sh->num_shared) return "bad num_shared / num_trainable_shared";
+  if (!sh->shared_grad || !sh->record || !sh->gathered || !sh->allgather) return "missing buffer / collective";
+  if (ol->step < 0 || os->step != ol->step) return "adam_local and adam_shared must carry the same step >= 0";
+  return shard_subject_refusal(a);
+}
+// smalfit_adam_step: one range [0, count) at the 1-based step t
+inline const char* adam_step_refusal(int count, bool given, int t) { return bad_argument_refusal(count > 0 && given && t > 0); }
 
 // ------------------------------------------------------------------------------------------------
 // smalfit_adam_args: the trainable ranges, packed for the segment kernels

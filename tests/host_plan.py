@@ -20,14 +20,40 @@ LOOPS = ("graph", "folded", "plain")                                  # RunLoop
 SKIN_FORMS = ("plain", "split", "wide")                               # SkinForm
 REASONS = (None, "cut", "gradient", "alias", "nothing", "extra")      # FoldRefusal
 HEAD_PRIORS = {"none": 0, "shared": 1, "per_frame": 2}                # HeadPrior
+HEAD_KERNELS = ("plain", "images", "step")                            # HeadKernel
+SIL_TARGETS = ("none", "f32", "u8")                                   # SilTargetKind
+LOSS_LAUNCHES = ("own_kernel", "in_resolve")                          # LossLaunch
+# EvalPlan as hp_plan_eval lays it out
+EVAL_INTS = ("M", "window", "frame_offset", "sequence_frames", "independent", "nb", "betas_stride", "ls_stride", "limb_scales",
+             "shape_prior", "prior_dim", "prior_uses_ls", "prior_windows", "prior_per_frame", "head_prior", "head",
+             "sil_on", "rasterise", "sil_target", "frame_loss", "queue_loss", "raster_backward", "loss_launch",
+             "joints_in_head", "halos", "verts_out", "need_pose", "need_beta", "need_ls", "bwd_betas_shared", "j_stride",
+             "asm_betas_shared", "asm_ls_shared", "ngrp_beta", "asm_shape_sets", "rows", "W", "ls_rows", "clear_qloss",
+             "assembly_leaves_betas", "assembly_leaves_scales")
+EVAL_FLOATS = ("prior_weight", "w_temp", "w_limit")
+EVAL_NAMED = {"head_prior": ("none", "shared", "per_frame"), "head": HEAD_KERNELS, "sil_target": SIL_TARGETS, "loss_launch": LOSS_LAUNCHES}
+GRID_CONSTANTS = ("SWEEP_FACES", "BWD_FACES", "BWD_LANES", "RES_EDGE", "RECT_FACES", "ASM_ELEM", "ASM_LOSS", "ASM_ROWS", "BAND_BLOCKS",
+                  "SELECT_BLOCKS", "SEL_WAVES", "SEL_GROUPS", "PBM_SPLITS", "PBM_TILES", "FRAME_LOSS_STRIDE", "JOINT_BLOCKS", "SKIN_VERTS",
+                  "SKIN_THREADS", "QUEUE_LOSS_BLOCKS")
 
 
 class Plan:
     def __init__(self, lib):
         self.lib = lib
         for name in ("hp_fit_args_refusal", "hp_fit_args_size_refusal", "hp_pack_adam_segments", "hp_model_dims_refusal",
-                     "hp_fit_model_refusal"):
+                     "hp_fit_model_refusal", "hp_null_argument_refusal", "hp_operator_args_refusal", "hp_step_refusal",
+                     "hp_iterations_refusal", "hp_engine_create_refusal", "hp_shape_prior_refusal", "hp_joint_limits_refusal",
+                     "hp_option_refusal", "hp_profile_begin_refusal", "hp_lbs_args_refusal", "hp_lbs_outputs_refusal",
+                     "hp_render_frames_refusal", "hp_temporal_frames_refusal", "hp_pose_prior_refusal", "hp_graph_subject_refusal",
+                     "hp_shard_subject_refusal", "hp_shard_record_refusal", "hp_shard_reduce_refusal", "hp_shard_run_refusal",
+                     "hp_adam_step_refusal", "hp_window_rows_refusal"):
             getattr(lib, name).restype = C.c_char_p
+        lib.hp_elem_blocks.argtypes = [C.c_longlong]
+        lib.hp_joint_limits_refusal.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_int * len(GRID_CONSTANTS))()
+        lib.hp_grid_constants(out)
+        for name, value in zip(GRID_CONSTANTS, out):
+            setattr(self, name, value)
         lib.hp_mesh_weight.restype = C.c_float
         lib.hp_mesh_weight.argtypes = [C.c_float]
         lib.hp_mesh_points.argtypes = [C.c_float, C.c_int]
@@ -159,6 +185,80 @@ class Plan:
 
     def sequence_frames(self, args):
         return self.lib.hp_sequence_frames(C.byref(args))
+
+
+    # ---- one evaluation ----
+    def plan_eval(self, args, max_frames=8, has_pose_prior=True, shape_dim=26, has_joint_limits=False, pending=False, assemble=True,
+                  window_rows=False, want_betas=False, want_scales=False):
+        """EvalPlan of a block the refusals accept, as a dict over EVAL_INTS + EVAL_FLOATS; enumerations by name"""
+        ints, floats = (C.c_int * 42)(), (C.c_float * 3)()
+        self.lib.hp_plan_eval(C.byref(args), max_frames, int(has_pose_prior), shape_dim, int(has_joint_limits), int(pending),
+                              int(assemble), int(window_rows), int(want_betas), int(want_scales), ints, floats)
+        out = dict(zip(EVAL_INTS, ints))
+        out.update(zip(EVAL_FLOATS, floats))
+        for k, names in EVAL_NAMED.items():
+            out[k] = names[out[k]]
+        return out
+
+    def window_rows_count(self, window, frame_offset, M):
+        return self.lib.hp_window_rows_count(window, frame_offset, M)
+
+    # ---- grids of the fit path ----
+    def _ints(self, fn, n, *args):
+        out = (C.c_int * n)()
+        fn(*args, out)
+        return tuple(out)
+
+    def xcd_grid(self, blocks_per_frame, M):
+        return self.lib.hp_xcd_grid(blocks_per_frame, M)
+
+    def box_grid(self, F, M, joints):
+        """(frame blocks, face blocks, joint riders, the launch)"""
+        return self._ints(self.lib.hp_box_grid, 4, F, M, int(joints))
+
+    def sweep_grid(self, F, M):
+        return self.lib.hp_sweep_grid(F, M)
+
+    def rect_count(self, F):
+        return self.lib.hp_rect_count(F)
+
+    def resolve_grid(self, S, M, loss_frames):
+        """(tiles per frame, loss riders, the launch)"""
+        return self._ints(self.lib.hp_resolve_grid, 3, S, M, loss_frames)
+
+    def raster_bwd_grid(self, F, M):
+        return self.lib.hp_raster_bwd_grid(F, M)
+
+    def vertex_bwd_grid(self, Vp, M):
+        return self.lib.hp_vertex_bwd_grid(Vp, M)
+
+    def mid_grid(self, M, need_pose):
+        """(pose-blend ids, dA ids, the launch)"""
+        return self._ints(self.lib.hp_mid_grid, 3, M, int(need_pose))
+
+    def chain_grid(self, M, need_beta, Vp, betas_shared):
+        return self.lib.hp_chain_grid(M, int(need_beta), Vp, int(betas_shared))
+
+    def assemble_grid(self, betas_shared, M):
+        return self.lib.hp_assemble_grid(int(betas_shared), M)
+
+    def window_rows_grid(self, W):
+        return self.lib.hp_window_rows_grid(W)
+
+    def frame_loss_rows_grid(self):
+        return self.lib.hp_frame_loss_rows_grid()
+
+    def skin_grid(self, M, Vp):
+        return self._ints(self.lib.hp_skin_grid, 2, M, Vp)
+
+    def elem_blocks(self, elements):
+        return self.lib.hp_elem_blocks(elements)
+
+    # ---- the other entry points' refusals: the text or None ----
+    def refusal(self, name, *args):
+        """hp_<name>_refusal(*args); ctypes structures go by reference"""
+        why = getattr(self.lib, "hp_%s_refusal" % name)(*[C.byref(a) if isinstance(a, C.Structure) else a for a in args])
+        return why.decode() if why else None
 
 
 def load():

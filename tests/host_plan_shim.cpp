@@ -113,4 +113,80 @@ const char* hp_fit_args_refusal(const smalfit_fit_args* a, int max_frames, int h
 const char* hp_fit_args_size_refusal(const smalfit_fit_args* a) { return fit_args_size_refusal(a); }
 int hp_sequence_frames(const smalfit_fit_args* a) { return sequence_frames(a); }
 
+// plan_eval of a block the refusals accept -> ints42 / floats3 in the order of tests/host_plan.py: EVAL_INTS, EVAL_FLOATS
+void hp_plan_eval(const smalfit_fit_args* a, int max_frames, int has_pose_prior, int shape_dim, int has_joint_limits, int pending,
+                  int assemble, int window_rows, int want_betas, int want_scales, int* ints42, float* floats3) {
+  EvalMode mode;
+  mode.pending = pending != 0; mode.assemble = assemble != 0;
+  mode.window_rows = window_rows != 0; mode.want_betas = want_betas != 0; mode.want_scales = want_scales != 0;
+  const EvalPlan p = plan_eval(a, EngineFacts{max_frames, has_pose_prior != 0, shape_dim, has_joint_limits != 0}, mode);
+  const int v[42] = {p.M, p.win.window, p.win.offset, p.win.total, p.independent, p.nb, p.betas_stride, p.ls_stride, p.limb_scales,
+                     p.shape_prior, p.prior_dim, p.prior_uses_ls, p.prior_windows, p.prior_per_frame, (int)p.head_prior, (int)p.head,
+                     p.sil_on, p.rasterise, (int)p.sil_target, p.frame_loss, p.queue_loss, p.raster_backward, (int)p.loss_launch,
+                     p.joints_in_head, p.halos, p.verts_out, p.need_pose, p.need_beta, p.need_ls, p.bwd_betas_shared, p.j_stride,
+                     p.asm_betas_shared, p.asm_ls_shared, p.ngrp_beta, p.asm_shape_sets, p.rows, p.W, p.ls_rows, p.clear_qloss,
+                     p.assembly_leaves_betas, p.assembly_leaves_scales, 0};
+  for (int i = 0; i < 42; ++i) ints42[i] = v[i];
+  floats3[0] = p.prior_weight; floats3[1] = p.w_temp; floats3[2] = p.w_limit;
+}
+int hp_window_rows_count(int window, int frame_offset, int M) { return window_rows_count(window, frame_offset, M); }
+
+// the fit path's grids.  [kSweepFaces, kBwdFaces, kBwdLanes, kResEdge, kRectFaces, kAsmElem, kAsmLoss, kAsmRows, kBandBlocks,
+// kSelectBlocks, kSelWaves, kSelGroups, PBM_SPLITS, PBM_TILES, kFrameLossStride, kJointBlocks, kSkinVerts, kSkinThreads, kQueueLossBlocks]
+void hp_grid_constants(int* out19) {
+  const int c[19] = {kSweepFaces, kBwdFaces, kBwdLanes, kResEdge, kRectFaces, kAsmElem, kAsmLoss, kAsmRows, kBandBlocks, kSelectBlocks,
+                     kSelWaves, kSelGroups, PBM_SPLITS, PBM_TILES, kFrameLossStride, kJointBlocks, kSkinVerts, kSkinThreads, kQueueLossBlocks};
+  for (int i = 0; i < 19; ++i) out19[i] = c[i];
+}
+int hp_xcd_grid(int blocks_per_frame, int M) { return xcd_grid(blocks_per_frame, M); }
+// [frame blocks, face blocks, joint riders, the launch]
+void hp_box_grid(int F, int M, int joints, int* out4) {
+  out4[0] = box_frame_blocks(M); out4[1] = box_face_blocks(F, M); out4[2] = box_joint_blocks(M, joints != 0); out4[3] = box_grid(F, M, joints != 0);
+}
+int hp_sweep_grid(int F, int M) { return sweep_grid(F, M); }
+int hp_rect_count(int F) { return rect_count(F); }
+// [tiles per frame, loss riders, the launch]
+void hp_resolve_grid(int S, int M, int loss_frames, int* out3) {
+  out3[0] = resolve_tiles(S); out3[1] = resolve_loss_blocks(loss_frames); out3[2] = resolve_grid(resolve_tiles(S), M, loss_frames);
+}
+int hp_raster_bwd_grid(int F, int M) { return raster_bwd_grid(F, M); }
+int hp_vertex_bwd_grid(int Vp, int M) { return vertex_bwd_grid(Vp, M); }
+// [pose-blend ids, dA ids, the launch]
+void hp_mid_grid(int M, int need_pose, int* out3) {
+  out3[0] = mid_pb_ids(M); out3[1] = mid_da_ids(M); out3[2] = mid_grid(M, need_pose ? mid_pb_ids(M) : 0);
+}
+int hp_chain_grid(int M, int need_beta, int Vp, int betas_shared) { return chain_grid(M, dbeta_grid(need_beta != 0, Vp, betas_shared != 0, M)); }
+int hp_assemble_grid(int betas_shared, int M) { return assemble_grid(asm_shape_sets(betas_shared, M)); }
+int hp_window_rows_grid(int W) { return window_rows_grid(W); }
+int hp_frame_loss_rows_grid(void) { return frame_loss_rows_grid(); }
+void hp_skin_grid(int M, int Vp, int* out2) { const Grid2 g = skin_grid(skin_form(M, Vp), M, Vp); out2[0] = g.x; out2[1] = g.y; }
+int hp_elem_blocks(long long elements) { return elem_blocks(elements); }
+
+// the other entry points' refusals: the text or NULL
+const char* hp_null_argument_refusal(int given) { return null_argument_refusal(given != 0); }
+const char* hp_operator_args_refusal(int count, int given) { return operator_args_refusal(count, given != 0); }
+const char* hp_step_refusal(int step) { return step_refusal(step); }
+const char* hp_iterations_refusal(int iterations) { return iterations_refusal(iterations); }
+const char* hp_engine_create_refusal(int given, int max_frames, int image_size) { return engine_create_refusal(given != 0, max_frames, image_size); }
+const char* hp_shape_prior_refusal(int given, int dim) { return shape_prior_refusal(given != 0, dim); }
+const char* hp_joint_limits_refusal(const float* lo, const float* hi) { return joint_limits_refusal(lo, hi); }
+const char* hp_option_refusal(int option, int value) { return option_refusal(option, value); }
+const char* hp_profile_begin_refusal(int given, int max_evals, int stride) { return profile_begin_refusal(given != 0, max_evals, stride); }
+const char* hp_lbs_args_refusal(const smalfit_lbs_args* a, int max_frames, int model_betas) { return lbs_args_refusal(a, max_frames, model_betas); }
+const char* hp_lbs_outputs_refusal(const smalfit_lbs_args* a) { return lbs_outputs_refusal(a); }
+const char* hp_render_frames_refusal(int M, int max_frames) { return render_frames_refusal(M, max_frames); }
+const char* hp_temporal_frames_refusal(int N, int max_frames) { return temporal_frames_refusal(N, max_frames); }
+const char* hp_pose_prior_refusal(int given, int N, int has_pose_prior) { return pose_prior_refusal(given != 0, N, has_pose_prior != 0); }
+const char* hp_graph_subject_refusal(int graph_on, const smalfit_fit_args* a) { return graph_subject_refusal(graph_on != 0, a); }
+const char* hp_shard_subject_refusal(const smalfit_fit_args* a) { return shard_subject_refusal(a); }
+const char* hp_shard_record_refusal(int num_shared, int num_frames, int given) { return shard_record_refusal(num_shared, num_frames, given != 0); }
+const char* hp_shard_reduce_refusal(int world_size, int record_stride, int gathered, int num_shared, int num_trainable, const smalfit_adam_args* o) {
+  return shard_reduce_refusal(world_size, record_stride, gathered != 0, num_shared, num_trainable, o);
+}
+const char* hp_shard_run_refusal(const smalfit_fit_args* a, const smalfit_adam_args* ol, const smalfit_adam_args* os, const smalfit_shard_args* sh, int iterations) {
+  return shard_run_refusal(a, ol, os, sh, iterations);
+}
+const char* hp_adam_step_refusal(int count, int given, int t) { return adam_step_refusal(count, given != 0, t); }
+const char* hp_window_rows_refusal(const smalfit_fit_args* a, const smalfit_window_rows* r) { return window_rows_refusal(a, r); }
+
 }  // extern "C"

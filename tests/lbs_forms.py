@@ -13,7 +13,7 @@ GPU.
 from __future__ import annotations
 
 NUM_VERTS = 3889                      # the synthetic stand-in's vertex count (and SMAL's)
-PBM_TILES = 4                         # kernels_lbs_backward.inc: constexpr int PBM_SPLITS = 24, PBM_U = 2, PBM_TILES = 4
+PBM_TILES = 4                         # smalfit_plan.h: constexpr int PBM_SPLITS = 24, PBM_TILES = 4
 
 
 def padded_verts(V=NUM_VERTS):

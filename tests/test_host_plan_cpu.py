@@ -129,3 +129,332 @@ def test_model_refusals(plan):
         assert plan.fit_model_refusal(nb) is None
     for nb in (1, 12, 19):
         assert plan.fit_model_refusal(nb) == "the model has fewer than the 20 shape directions the fitter optimises"
+
+
+# ------------------------------------------------------------------------------------------------
+# plan_eval: what one evaluation launches, with which switches
+# ------------------------------------------------------------------------------------------------
+P = 0x9000                                            # a dummy pointer
+# the plan of valid_fit_args() -- 4 frames, windows of 2, shared limb scales, every term on, no gradient wanted -- on an engine
+# with both priors (26-dim shape prior) and no joint limits; written from fit_eval_impl as it was before plan_eval existed
+DEFAULT_PLAN = dict(
+    M=4, window=2, frame_offset=0, sequence_frames=4, independent=0, nb=20, betas_stride=0, ls_stride=0, limb_scales=1,
+    shape_prior=1, prior_dim=26, prior_uses_ls=1, prior_windows=2, prior_weight=2.0, prior_per_frame=0, head_prior="shared", head="plain",
+    sil_on=1, rasterise=1, sil_target="f32", frame_loss=0, queue_loss=1, raster_backward=1, loss_launch="in_resolve", joints_in_head=0,
+    w_temp=0.0, w_limit=0.0, halos=1, verts_out=0, need_pose=0, need_beta=0, need_ls=0, bwd_betas_shared=1, j_stride=0,
+    asm_betas_shared=1, asm_ls_shared=1, ngrp_beta=8, asm_shape_sets=1, rows=0, W=0, ls_rows=0, clear_qloss=0,
+    assembly_leaves_betas=0, assembly_leaves_scales=0)
+NO_SIL = dict(sil_on=0, sil_target="none", queue_loss=0, raster_backward=0)
+NO_PRIOR = dict(shape_prior=0, prior_dim=0, prior_uses_ls=0, prior_windows=0, prior_weight=0.0, head_prior="none")
+ALL_GRADS = dict(g_betas=P, g_log_beta_scales=P, g_global_rotation=P, g_joint_rotations=P, g_trans=P)
+IMAGES = dict(INDEP, num_frames=3)
+# the plan of three independent images with the 26-dim prior, as differences from DEFAULT_PLAN
+IMAGES_PLAN = dict(M=3, window=1, sequence_frames=3, independent=1, betas_stride=20, ls_stride=6, prior_windows=3, prior_weight=1.0,
+                   prior_per_frame=1, head_prior="per_frame", head="images", halos=0, bwd_betas_shared=0, j_stride=105,
+                   asm_betas_shared=0, asm_ls_shared=0, ngrp_beta=1, asm_shape_sets=3)
+# window rows over the default block (smalfit_fit_eval_windows): two windows; the shared gradients are left to window_rows_kernel.
+# ngrp_beta stays 8 although the backward pass then writes one group of per-frame partials: kept as the host always had it
+WINDOWS_PLAN = dict(W=2, need_beta=1, bwd_betas_shared=0, frame_loss=1, clear_qloss=1, assembly_leaves_betas=1, assembly_leaves_scales=1,
+                    ngrp_beta=8)
+WR = dict(window_rows=True, want_betas=True)
+
+# name: (fields bent on valid_fit_args, engine facts / mode bent, the fields of the plan that differ from DEFAULT_PLAN)
+EVAL_PLANS = {
+    "default": ({}, {}, {}),
+    "w_sil 0": (dict(w_sil=0.0), {}, dict(NO_SIL, rasterise=0, loss_launch="own_kernel", joints_in_head=1)),
+    "w_sil 0, sil_out": (dict(w_sil=0.0, sil_out=P), {}, dict(NO_SIL, rasterise=1, loss_launch="in_resolve", joints_in_head=0)),
+    "u8 target": (dict(target_sil=None, target_sil_u8=P), {}, dict(sil_target="u8")),
+    "both targets: bytes win": (dict(target_sil_u8=P), {}, dict(sil_target="u8")),
+    "w_betas 0": (dict(w_betas=0.0), {}, NO_PRIOR),
+    "shape_prior_dim 20": (dict(shape_prior_dim=20), {}, dict(prior_dim=20, prior_uses_ls=0)),
+    "engine's prior of 20": ({}, dict(shape_dim=20), dict(prior_dim=20, prior_uses_ls=0)),
+    "logscale_mode 0": (dict(logscale_mode=0, shape_prior_dim=20, log_beta_scales=None, g_log_beta_scales=P), {},
+                        dict(limb_scales=0, asm_ls_shared=0, prior_dim=20, prior_uses_ls=0, need_ls=0)),
+    "logscale_mode 2": (dict(logscale_mode=2, shape_prior_dim=20, g_log_beta_scales=P), {},
+                        dict(ls_stride=6, asm_ls_shared=0, prior_dim=20, prior_uses_ls=0, need_ls=1)),
+    "shard": (dict(frame_offset=3, total_frames=16), {}, dict(frame_offset=3, sequence_frames=16, prior_windows=2, prior_weight=2.0)),
+    "shard inside one window": (dict(num_frames=1, window=8, frame_offset=3, total_frames=16), {},
+                                dict(M=1, window=8, frame_offset=3, sequence_frames=16, prior_windows=0, prior_weight=0.0)),
+    "temporal": (dict(w_temp=0.5, halo_prev=P, halo_next=P), {}, dict(w_temp=0.5)),
+    "temporal 0, halos given": (dict(temporal=0, w_temp=0.5, halo_prev=P, halo_next=P), {}, dict(w_temp=0.0, halos=0)),
+    "joint limits on": (dict(w_limit=100.0), dict(has_joint_limits=True), dict(w_limit=100.0)),
+    "joint limits off": (dict(w_limit=100.0), {}, dict(w_limit=0.0)),
+    "every gradient": (ALL_GRADS, {}, dict(need_pose=1, need_beta=1, need_ls=1)),
+    "g_joint_rotations alone missing": (dict(ALL_GRADS, g_joint_rotations=None), {}, dict(need_pose=0, need_beta=1, need_ls=1)),
+    "verts_out": (dict(verts_out=P), {}, dict(verts_out=1)),
+    "pending step": (ALL_GRADS, dict(pending=True), dict(head="step", need_pose=1, need_beta=1, need_ls=1)),
+    "losses_per_frame": (dict(losses_per_frame=P), {}, dict(rows=1, frame_loss=1)),
+    "assemble off, losses_per_frame": (dict(losses_per_frame=P), dict(assemble=False), dict(rows=0, frame_loss=0)),
+    "images": (IMAGES, {}, IMAGES_PLAN),
+    "images, prior off": (dict(IMAGES, w_betas=0.0), {}, dict(IMAGES_PLAN, **dict(NO_PRIOR, prior_per_frame=0, head="plain"))),
+    "images, rows": (dict(IMAGES, losses_per_frame=P), {}, dict(IMAGES_PLAN, rows=1, frame_loss=1)),
+    "images, every gradient": (dict(IMAGES, **ALL_GRADS), {}, dict(IMAGES_PLAN, need_pose=1, need_beta=1, need_ls=1)),
+    "windows: g_betas": ({}, WR, WINDOWS_PLAN),
+    "windows: both gradients": ({}, dict(WR, want_scales=True), dict(WINDOWS_PLAN, need_ls=1, ls_rows=1)),
+    "windows: totals too": (dict(g_betas=P, g_log_beta_scales=P), dict(WR, want_scales=True), dict(WINDOWS_PLAN, need_ls=1, ls_rows=1)),
+    "windows: losses only": ({}, dict(window_rows=True), dict(WINDOWS_PLAN, need_beta=0)),
+    "windows, rows": (dict(losses_per_frame=P), WR, dict(WINDOWS_PLAN, rows=1, clear_qloss=0)),
+    "windows, logscale_mode 2": (dict(logscale_mode=2, shape_prior_dim=20, g_log_beta_scales=P), WR,
+                                 dict(WINDOWS_PLAN, ls_stride=6, asm_ls_shared=0, prior_dim=20, prior_uses_ls=0, need_ls=1, ls_rows=0,
+                                      assembly_leaves_scales=0)),
+    "windows, w_sil 0": (dict(w_sil=0.0), WR, dict(WINDOWS_PLAN, **dict(NO_SIL, rasterise=0, loss_launch="own_kernel", joints_in_head=1,
+                                                                         frame_loss=0))),
+    "windows of a shard": (dict(frame_offset=3, total_frames=16), WR, dict(WINDOWS_PLAN, frame_offset=3, sequence_frames=16, W=3)),
+}
+FACTS = ("max_frames", "has_pose_prior", "shape_dim", "has_joint_limits")
+
+
+def _plan_of(plan, fields, bent):
+    args = valid_fit_args(**fields)
+    facts = {k: v for k, v in bent.items() if k in FACTS}
+    assert plan.fit_args_refusal(args, facts.get("max_frames", MAX_FRAMES), facts.get("has_pose_prior", True), facts.get("shape_dim", 26)) is None
+    if bent.get("window_rows"):
+        rows = _lib.WindowRows()
+        rows.num_windows, rows.losses = plan.window_rows_count(args.window, args.frame_offset, args.num_frames), P
+        rows.g_betas = P if bent.get("want_betas") else None
+        rows.g_log_beta_scales = P if bent.get("want_scales") else None
+        assert plan.refusal("window_rows", args, rows) is None
+    return plan.plan_eval(args, **bent)
+
+
+@pytest.mark.parametrize("name", list(EVAL_PLANS))
+def test_eval_plan(plan, name):
+    fields, bent, differs = EVAL_PLANS[name]
+    want = dict(DEFAULT_PLAN, **differs)
+    assert set(want) == set(host_plan.EVAL_INTS) | set(host_plan.EVAL_FLOATS)
+    got = _plan_of(plan, fields, bent)
+    assert got == want, {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+
+
+def test_eval_plan_crossings(plan):
+    # per-frame rows x window rows x silhouette term -> who counts the queue kernels' loss per frame, who clears the counters
+    #   (rows, windows, w_sil): (frame_loss, rows, clear_qloss, W)
+    table = {(0, 0, 1.0): (0, 0, 0, 0), (1, 0, 1.0): (1, 1, 0, 0), (0, 1, 1.0): (1, 0, 1, 2), (1, 1, 1.0): (1, 1, 0, 2),
+             (0, 0, 0.0): (0, 0, 0, 0), (1, 0, 0.0): (0, 1, 0, 0), (0, 1, 0.0): (0, 0, 1, 2), (1, 1, 0.0): (0, 1, 0, 2)}
+    for (rows, windows, w_sil), want in table.items():
+        got = _plan_of(plan, dict(w_sil=w_sil, losses_per_frame=P if rows else None), dict(WR) if windows else {})
+        assert (got["frame_loss"], got["rows"], got["clear_qloss"], got["W"]) == want, (rows, windows, w_sil)
+        assert got["queue_loss"] == got["raster_backward"] == got["sil_on"] == int(w_sil > 0)
+    # independent images x the prior's dimension x the scale mode (26 dimensions need the per-frame scales: refused otherwise)
+    #   (dim, mode): (prior_uses_ls, limb_scales, ls_stride, head, asm_ls_shared, asm_shape_sets)
+    table = {(26, 2): (1, 1, 6, "images", 0, 3), (20, 2): (0, 1, 6, "images", 0, 3), (20, 0): (0, 0, 0, "images", 0, 3)}
+    for (dim, mode), want in table.items():
+        got = _plan_of(plan, dict(IMAGES, shape_prior_dim=dim, logscale_mode=mode), {})
+        assert tuple(got[k] for k in ("prior_uses_ls", "limb_scales", "ls_stride", "head", "asm_ls_shared", "asm_shape_sets")) == want, (dim, mode)
+        assert got["prior_dim"] == dim and got["prior_weight"] == 1.0 and got["prior_windows"] == 3
+    # one subject x the same: the shared scales are the only mode 26 dimensions take
+    table = {(26, 1): (1, 1, 0, 1), (20, 1): (0, 1, 0, 1), (20, 2): (0, 1, 6, 0), (20, 0): (0, 0, 0, 0)}
+    for (dim, mode), want in table.items():
+        got = _plan_of(plan, dict(shape_prior_dim=dim, logscale_mode=mode), {})
+        assert tuple(got[k] for k in ("prior_uses_ls", "limb_scales", "ls_stride", "asm_ls_shared")) == want, (dim, mode)
+
+
+# ------------------------------------------------------------------------------------------------
+# grids of the fit path
+# ------------------------------------------------------------------------------------------------
+def test_grid_constants(plan):
+    assert (plan.SWEEP_FACES, plan.BWD_FACES, plan.BWD_LANES, plan.RES_EDGE, plan.RECT_FACES) == (32, 4, 16, 32, 8)
+    assert (plan.ASM_ELEM, plan.ASM_LOSS, plan.ASM_ROWS, plan.BAND_BLOCKS, plan.SELECT_BLOCKS, plan.SEL_WAVES, plan.SEL_GROUPS) == (4, 16, 4, 1536, 1792, 2, 16)
+    assert (plan.PBM_SPLITS, plan.PBM_TILES, plan.FRAME_LOSS_STRIDE, plan.JOINT_BLOCKS, plan.SKIN_VERTS, plan.SKIN_THREADS) == (24, 4, 32, 41, 32, 512)
+    assert plan.QUEUE_LOSS_BLOCKS == 3328
+
+
+def test_grids_by_frames(plan):
+    """M = 1, 8, 9: one frame, a full round of eight frames (one per XCD), the first overflow into a second round"""
+    assert [plan.xcd_grid(1, M) for M in (1, 8, 9, 16, 17)] == [8, 8, 16, 16, 24]
+    assert [plan.xcd_grid(31, M) for M in (1, 8, 9)] == [248, 248, 496]
+    # box kernel: frame blocks | face blocks | joint riders | launch
+    assert plan.box_grid(7774, 1, True) == (8, 248, 41, 297) and plan.box_grid(7774, 1, False) == (8, 248, 0, 256)
+    assert plan.box_grid(7774, 8, True) == (8, 248, 328, 584) and plan.box_grid(7774, 9, True) == (16, 496, 369, 881)
+    assert plan.box_grid(7774, 9, False) == (16, 496, 0, 512)
+    assert [plan.sweep_grid(7774, M) for M in (1, 8, 9)] == [1944, 1944, 3888]
+    assert [plan.raster_bwd_grid(7774, M) for M in (1, 8, 9)] == [15552, 15552, 31104]
+    assert [plan.vertex_bwd_grid(4096, M) for M in (1, 8, 9)] == [128, 128, 256]
+    assert [plan.vertex_bwd_grid(256, M) for M in (1, 8, 9)] == [8, 8, 16]
+    # resolve: tiles per frame | loss riders | launch
+    assert plan.resolve_grid(64, 1, 1) == (4, 8, 40) and plan.resolve_grid(64, 8, 8) == (4, 8, 40) and plan.resolve_grid(64, 9, 9) == (4, 16, 80)
+    assert plan.resolve_grid(64, 9, 0) == (4, 0, 64)
+    # mid kernel: pose-blend ids (chunks of four tiles of 16 frames) | dA ids | launch
+    assert plan.mid_grid(1, True) == (240, 280, 520) and plan.mid_grid(8, True) == (240, 280, 520) and plan.mid_grid(9, True) == (240, 560, 800)
+    assert plan.mid_grid(9, False) == (240, 560, 560)
+    assert plan.mid_grid(64, True)[0] == 240 and plan.mid_grid(65, True)[0] == 480
+    # chain: M frame blocks + the dbeta riders (48 column blocks at 4096 vertices, 3 at 256)
+    assert [plan.chain_grid(M, True, 4096, True) for M in (1, 8, 9)] == [385, 392, 393]
+    assert [plan.chain_grid(M, True, 4096, False) for M in (1, 8, 9)] == [49, 392, 441]
+    assert [plan.chain_grid(M, False, 4096, True) for M in (1, 8, 9)] == [1, 8, 9]
+    assert plan.chain_grid(4, True, 256, True) == 28 and plan.chain_grid(4, True, 256, False) == 16
+    # assembly: shape sets | limb scales | 4 element blocks | 16 loss partials
+    assert [plan.assemble_grid(True, M) for M in (1, 8, 9)] == [22, 22, 22]
+    assert [plan.assemble_grid(False, M) for M in (1, 8, 9)] == [22, 29, 30]
+    assert [plan.window_rows_grid(W) for W in (1, 2, 9)] == [1, 2, 9] and plan.frame_loss_rows_grid() == 4
+    # skinning: (vertex blocks, frame tiles) of the form skin_form chose -- plain to 4 frames, wide from 49 at 4096 vertices
+    assert plan.skin_grid(1, 4096) == (64, 1) and plan.skin_grid(4, 4096) == (64, 1)
+    assert plan.skin_grid(8, 4096) == (128, 1) and plan.skin_grid(9, 4096) == (128, 1) and plan.skin_grid(17, 4096) == (128, 2)
+    assert plan.skin_grid(48, 4096) == (128, 3) and plan.skin_grid(49, 4096) == (64, 4)
+
+
+def test_grids_by_faces_vertices_and_image_size(plan):
+    faces = (1, 255, 256, 257, 7774)
+    assert [plan.box_grid(F, 1, False)[1] for F in faces] == [8, 8, 8, 16, 248]               # 256 faces per block
+    assert [plan.sweep_grid(F, 1) for F in faces] == [8, 64, 64, 72, 1944]                    # 32
+    assert [plan.raster_bwd_grid(F, 1) for F in faces] == [8, 512, 512, 520, 15552]           # 4
+    assert [plan.rect_count(F) for F in faces] == [1, 32, 32, 33, 972]                        # 8 faces per union box
+    # image sizes whose tile count is / is not a multiple of the resolve edge (32)
+    assert [plan.resolve_grid(S, 1, 0)[0] for S in (1, 32, 33, 64, 100, 512, 1000, 1024)] == [1, 1, 4, 4, 16, 256, 1024, 1024]
+    assert plan.resolve_grid(100, 9, 9) == (16, 16, 272)
+    assert [plan.elem_blocks(n) for n in (0, 1, 256, 257, 3889 * 3, 2 ** 31 + 1)] == [0, 1, 1, 2, 46, 8388609]
+
+
+# ------------------------------------------------------------------------------------------------
+# the other entry points: every refusal, its order, the accepted edge next to the refused one
+# ------------------------------------------------------------------------------------------------
+def _lbs(**fields):
+    a = _lib.LbsArgs()
+    a.num_frames, a.num_betas, a.beta, a.theta, a.verts, a.joints = 2, 20, P, P, P, P
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def _adam(**fields):
+    o = _lib.AdamArgs()
+    o.param = o.grad = o.exp_avg = o.exp_avg_sq = P
+    for k, v in fields.items():
+        setattr(o, k, v)
+    return o
+
+
+def _shard(**fields):
+    sh = _lib.ShardArgs()
+    sh.world_size, sh.rank, sh.num_shared, sh.num_trainable_shared = 2, 1, 26, 20
+    sh.shared_grad = sh.record = sh.gathered = sh.allgather = P
+    for k, v in fields.items():
+        setattr(sh, k, v)
+    return sh
+
+
+def _table(plan, name, good, table):
+    """`good` is accepted; each row of `table` bends it and names the refusal; two faults at once: the first in the table's order"""
+    assert plan.refusal(name, *good) is None
+    for bent, msg in table:
+        assert plan.refusal(name, *bent) == msg, (name, msg)
+
+
+def test_null_count_step_refusals(plan):
+    assert plan.refusal("null_argument", 1) is None and plan.refusal("null_argument", 0) == "null argument"
+    _table(plan, "operator_args", (1, 1), (((0, 1), "bad argument"), ((-1, 1), "bad argument"), ((1, 0), "bad argument")))
+    assert plan.refusal("step", 0) is None and plan.refusal("step", -1) == "step must be >= 0"
+    assert plan.refusal("iterations", 1) is None and plan.refusal("iterations", 0) == "iterations must be positive"
+    _table(plan, "adam_step", (1, 1, 1), (((0, 1, 1), "bad argument"), ((1, 0, 1), "bad argument"), ((1, 1, 0), "bad argument")))
+    _table(plan, "profile_begin", (1, 1, 1), (((0, 1, 1), "bad argument"), ((1, 0, 1), "bad argument"), ((1, 1, 0), "bad argument")))
+
+
+def test_engine_refusals(plan):
+    big = "image_size above 1024 is not supported (float32 pixel walk, see kernels_raster.inc)"
+    _table(plan, "engine_create", (1, 1, 1024), (((0, 1, 64), "bad argument"), ((1, 0, 64), "bad argument"), ((1, 1, 0), "bad argument"),
+                                                 ((1, 1, 1025), big), ((0, 1, 1025), "bad argument"), ((1, 0, 4096), "bad argument")))
+    assert plan.refusal("engine_create", 1, 1, 1) is None and plan.MAX_IMAGE_SIZE == 1024
+    dims = "bad argument (dim must be 1..26)"
+    _table(plan, "shape_prior", (1, 26), (((1, 27), dims), ((1, 0), dims), ((1, -1), dims), ((0, 20), dims)))
+    assert plan.refusal("shape_prior", 1, 1) is None
+    lo, hi = (C.c_float * 102)(*([-1.0] * 102)), (C.c_float * 102)(*([1.0] * 102))
+    assert plan.refusal("joint_limits", lo, hi) is None and plan.refusal("joint_limits", lo, lo) is None       # min == max
+    assert plan.refusal("joint_limits", None, hi) == "null argument" == plan.refusal("joint_limits", lo, None)
+    assert plan.refusal("joint_limits", hi, lo) == "min must not exceed max"
+    for i in (0, 57, 101):
+        bad = (C.c_float * 102)(*([-1.0] * 102))
+        bad[i] = 1.5
+        assert plan.refusal("joint_limits", bad, hi) == "min must not exceed max"
+        bad[i] = float("nan")
+        assert plan.refusal("joint_limits", bad, hi) == "min must not exceed max"
+        bad[i] = 1.0
+        assert plan.refusal("joint_limits", bad, hi) is None
+    edge = "SMALFIT_OPT_UNCLAMPED_EDGE_T takes 0 or 1"
+    _table(plan, "option", (1, 1), (((1, 2), edge), ((1, -1), edge), ((0, 0), "unknown option"), ((2, 1), "unknown option")))
+    assert plan.refusal("option", 1, 0) is None
+
+
+def test_lbs_refusals(plan):
+    frames, one = "num_frames exceeds the engine's max_frames", "give exactly one of theta (axis-angle) and Rs (rotation matrices)"
+    table = ((dict(num_frames=0), frames), (dict(num_frames=MAX_FRAMES + 1), frames), (dict(num_betas=0), "num_betas out of range"),
+             (dict(num_betas=42), "num_betas out of range"), (dict(beta=None), "beta missing"), (dict(Rs=P), one), (dict(theta=None), one))
+    assert plan.refusal("lbs_args", _lbs(), MAX_FRAMES, 41) is None
+    assert plan.refusal("lbs_args", _lbs(num_frames=MAX_FRAMES, num_betas=41), MAX_FRAMES, 41) is None
+    assert plan.refusal("lbs_args", _lbs(theta=None, Rs=P), MAX_FRAMES, 41) is None
+    for i, (bent, msg) in enumerate(table):
+        assert plan.refusal("lbs_args", _lbs(**bent), MAX_FRAMES, 41) == msg
+        for later, other in table[i + 1:]:                                                    # the first fault is reported
+            if not set(later) & set(bent) and other != msg:
+                assert plan.refusal("lbs_args", _lbs(**dict(later, **bent)), MAX_FRAMES, 41) == msg
+    assert plan.refusal("lbs_outputs", _lbs()) is None
+    assert plan.refusal("lbs_outputs", _lbs(verts=None)) == "verts / joints outputs missing" == plan.refusal("lbs_outputs", _lbs(joints=None))
+
+
+def test_render_temporal_pose_prior_refusals(plan):
+    m, n = "M exceeds the engine's max_frames", "N exceeds the engine's max_frames"
+    _table(plan, "render_frames", (MAX_FRAMES, MAX_FRAMES), (((MAX_FRAMES + 1, MAX_FRAMES), m), ((0, MAX_FRAMES), m), ((-1, MAX_FRAMES), m)))
+    _table(plan, "temporal_frames", (MAX_FRAMES, MAX_FRAMES), (((MAX_FRAMES + 1, MAX_FRAMES), n), ((0, MAX_FRAMES), n)))
+    assert plan.refusal("render_frames", 1, MAX_FRAMES) is None and plan.refusal("temporal_frames", 1, MAX_FRAMES) is None
+    _table(plan, "pose_prior", (1, 1, 1), (((0, 1, 1), "bad argument"), ((1, 0, 1), "bad argument"), ((1, 1, 0), "pose prior not set"),
+                                           ((0, 1, 0), "bad argument"), ((1, 0, 0), "bad argument")))
+
+
+def test_fit_run_and_shard_refusals(plan):
+    graph = "subject_frames != 0 is not supported by the graph replay (smalfit_engine_set_graph)"
+    shard = "subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)"
+    assert plan.refusal("graph_subject", 1, valid_fit_args()) is None and plan.refusal("graph_subject", 0, valid_fit_args(**INDEP)) is None
+    assert plan.refusal("graph_subject", 1, valid_fit_args(**INDEP)) == graph
+    assert plan.refusal("shard_subject", valid_fit_args()) is None and plan.refusal("shard_subject", valid_fit_args(**INDEP)) == shard
+    # a block of another header: its tail is not read here, the evaluation refuses it
+    assert plan.refusal("shard_subject", valid_fit_args(struct_size=C.sizeof(_lib.FitArgs) - 8, **INDEP)) is None
+    _table(plan, "shard_record", (0, 1, 1), (((-1, 1, 1), "bad argument"), ((0, 0, 1), "bad argument"), ((0, 1, 0), "bad argument")))
+    good = (2, 26, 1, 26, 26, _adam())
+    state = "bad optimiser state"
+    _table(plan, "shard_reduce", good, (((0, 26, 1, 26, 26, _adam()), "bad argument"), ((2, 25, 1, 26, 26, _adam()), "bad argument"),
+                                        ((2, 26, 0, 26, 26, _adam()), "bad argument"), ((2, 26, 1, 0, 0, _adam()), "bad argument"),
+                                        ((2, 26, 1, 26, -1, _adam()), "bad argument"), ((2, 26, 1, 26, 27, _adam()), "bad argument"),
+                                        ((2, 26, 1, 26, 26, None), "bad argument"), ((2, 26, 1, 26, 26, _adam(param=None)), state),
+                                        ((2, 26, 1, 26, 26, _adam(exp_avg_sq=None)), state), ((2, 26, 1, 26, 26, _adam(step=-1)), state),
+                                        ((0, 26, 1, 26, 26, _adam(step=-1)), "bad argument")))
+    assert plan.refusal("shard_reduce", 1, 26, 1, 26, 0, _adam()) is None
+    # smalfit_shard_run, in the order it checks
+    a, o = valid_fit_args(), _adam(step=3)
+    table = ((dict(sh=_shard(struct_size=8)), "smalfit_shard_args.struct_size does not match this library (built against another smalfit.h?)"),
+             (dict(iterations=0), "iterations must be positive"),
+             (dict(sh=_shard(world_size=0)), "bad rank / world_size"), (dict(sh=_shard(rank=-1)), "bad rank / world_size"),
+             (dict(sh=_shard(rank=2)), "bad rank / world_size"),
+             (dict(sh=_shard(num_shared=0)), "bad num_shared / num_trainable_shared"), (dict(sh=_shard(num_trainable_shared=27)), "bad num_shared / num_trainable_shared"),
+             (dict(sh=_shard(num_trainable_shared=-1)), "bad num_shared / num_trainable_shared"),
+             (dict(sh=_shard(shared_grad=None)), "missing buffer / collective"), (dict(sh=_shard(allgather=None)), "missing buffer / collective"),
+             (dict(ol=_adam(step=-1), os=_adam(step=-1)), "adam_local and adam_shared must carry the same step >= 0"),
+             (dict(os=_adam(step=4)), "adam_local and adam_shared must carry the same step >= 0"),
+             (dict(a=valid_fit_args(**INDEP)), shard))
+
+    def run(**bent):
+        k = dict(dict(a=a, ol=o, os=_adam(step=3), sh=_shard(), iterations=1), **bent)
+        return plan.refusal("shard_run", k["a"], k["ol"], k["os"], k["sh"], k["iterations"])
+    assert run() is None and run(sh=_shard(rank=0, world_size=1, num_trainable_shared=26)) is None and run(sh=_shard(num_trainable_shared=0)) is None
+    for i, (bent, msg) in enumerate(table):
+        assert run(**bent) == msg, msg
+        for later, _ in table[i + 1:]:
+            if not set(later) & set(bent):
+                assert run(**dict(later, **bent)) == msg, (msg, list(later))
+
+
+def test_window_rows_refusals(plan):
+    def rows(**fields):
+        r = _lib.WindowRows()
+        r.num_windows, r.losses, r.g_betas, r.g_log_beta_scales = 2, P, P, P
+        for k, v in fields.items():
+            setattr(r, k, v)
+        return r
+    count = "smalfit_window_rows.num_windows is not the number of windows these frames belong to"
+    assert plan.refusal("window_rows", valid_fit_args(), rows()) is None
+    assert plan.refusal("window_rows", valid_fit_args(frame_offset=3), rows(num_windows=3)) is None
+    assert plan.refusal("window_rows", valid_fit_args(), rows(struct_size=8)) == "smalfit_window_rows.struct_size does not match this library (built against another smalfit.h?)"
+    assert plan.refusal("window_rows", valid_fit_args(), rows(losses=None)) == "smalfit_window_rows.losses missing"
+    assert plan.refusal("window_rows", valid_fit_args(**INDEP), rows(num_windows=4)) == "window rows need subject_frames = 0 (independent images already have one row per image)"
+    assert plan.refusal("window_rows", valid_fit_args(), rows(num_windows=3)) == count == plan.refusal("window_rows", valid_fit_args(frame_offset=3), rows())
+    assert plan.refusal("window_rows", valid_fit_args(logscale_mode=2), rows()) == "smalfit_window_rows.g_log_beta_scales needs shared log_beta_scales (logscale_mode 1)"
+    assert plan.refusal("window_rows", valid_fit_args(logscale_mode=2), rows(g_log_beta_scales=None)) is None
+    assert [plan.window_rows_count(2, off, 4) for off in (0, 1, 2, 3)] == [2, 3, 2, 3] and plan.window_rows_count(8, 3, 1) == 1

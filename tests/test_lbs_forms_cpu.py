@@ -32,10 +32,10 @@ def test_the_rules_are_the_hosts(plan):
 
 
 def test_the_chunks_are_the_kernels():
-    bwd = _src("kernels_lbs_backward.inc")
-    tiles = re.search(r"constexpr int PBM_SPLITS = \d+, PBM_U = \d+, PBM_TILES = (\d+);", bwd)
+    bwd, plan_h = _src("kernels_lbs_backward.inc"), _src("smalfit_plan.h")     # (the launch's constants and grid: the plan header)
+    tiles = re.search(r"constexpr int PBM_SPLITS = \d+, PBM_TILES = (\d+);", plan_h)
     assert tiles and int(tiles.group(1)) == lf.PBM_TILES
-    assert ("mid_pb_ids(int M) { return 10 * PBM_SPLITS * (((M + 15) / 16 + PBM_TILES - 1) / PBM_TILES); }" in bwd)
+    assert ("mid_pb_ids(int M) { return 10 * PBM_SPLITS * (((M + 15) / 16 + PBM_TILES - 1) / PBM_TILES); }" in plan_h)
     assert "const int nft = (M + 15) / 16, t0 = tchunk * PBM_TILES, nt = min(PBM_TILES, nft - t0);" in bwd
 
 

@@ -28,11 +28,13 @@ def test_the_constants_are_the_kernels():
     r = _src("kernels_raster.inc")
     assert _const(_src("smalfit_math.h"), "kFacesPerPixel") == rf.K
     for name, val in (("kListCap", rf.LIST_CAP), ("kListLds", rf.LIST_LDS), ("kMaskRounds", rf.MASK_ROUNDS),
-                      ("kAccWin", rf.ACC_WIN), ("kSweepFaces", rf.SWEEP_FACES), ("kRectFaces", rf.RECT_FACES),
+                      ("kAccWin", rf.ACC_WIN),
                       ("kBandCap", rf.BAND_CAP), ("kBandFill", rf.BAND_FILL), ("kBandHalf", rf.BAND_HALF),
                       ("kBandTries", rf.BAND_TRIES), ("kCandCap", rf.CAND_CAP), ("kHitCap", rf.HIT_CAP),
                       ("kCoverCap", rf.COVER_CAP)):
         assert _const(r, name) == val, name
+    for name, val in (("kSweepFaces", rf.SWEEP_FACES), ("kRectFaces", rf.RECT_FACES)):      # the constants a launch is sized by
+        assert _const(_src("smalfit_plan.h"), name) == val, name
     assert "constexpr int kBandFillWide = %d, kBandFillNarrow = %d;" % (rf.BAND_FILL_WIDE, rf.BAND_FILL_NARROW) in r
     assert "constexpr float kBoxSlack = 1.0f / 64.0f;" in r
     assert host_plan.load().MAX_IMAGE_SIZE == rf.MAX_S          # smalfit_engine_create refuses larger images
