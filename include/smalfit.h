@@ -181,6 +181,10 @@ int smalfit_render_color(smalfit_engine* engine, void* stream, int num_frames, c
 /* adjoint wrt verts given the saved silhouette and dL/dsil (M,S,S) */
 int smalfit_render_backward(smalfit_engine* engine, void* stream, int M, const float* verts,
                             const float* sil, const float* dsil, float* dverts);
+/* diagnostics: the hand-off of the last silhouette forward (smalfit_render_forward / _backward, an evaluation) to the backward
+ * gather, one byte per face: the length of the face's candidate list (0..128), 254 = candidate masks, 255 = the whole pixel box is
+ * walked.  lengths: device, (M,F) bytes.  Results never depend on which form a face takes; the tests of the gather do */
+int smalfit_engine_face_list_lengths(smalfit_engine* engine, void* stream, int M, unsigned char* lengths);
 int smalfit_project_points_backward(void* stream, int count, int image_size, const float* points,
                                     const float* dproj, float* dpoints);
 

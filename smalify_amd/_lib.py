@@ -135,6 +135,7 @@ SIGNATURES = {
     "smalfit_render_forward": (_I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _VP]),
     "smalfit_render_color": (_I, [_VP, _VP, _I, _VP, _VP, _VP]),
     "smalfit_render_backward": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "smalfit_engine_face_list_lengths": (_I, [_VP, _VP, _I, _VP]),
     "smalfit_project_points_backward": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
     "smalfit_fit_eval": (_I, [_VP, _VP, C.POINTER(FitArgs)]),
     "smalfit_fit_eval_windows": (_I, [_VP, _VP, C.POINTER(FitArgs), C.POINTER(WindowRows)]),

@@ -1387,7 +1387,8 @@ static_assert(kSweepFaces % 16 == 0 && kBwdFaces * kBwdLanes == 64,
 // it which edge is the nearest, is the same either way.
 template <bool kUnclampedT>
 __global__ void __launch_bounds__(kBwdLanes * kBwdFaces)
-raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const int2* __restrict__ fbox, const float* __restrict__ zc, const float2* __restrict__ gz,
+raster_bwd_kernel(int F, int M, int S, float inv_s /*1 / S, divided on the host: the same bits, and no division sequence in every wave*/,
+                  const float4* __restrict__ frec, const int2* __restrict__ fbox, const float* __restrict__ zc, const float2* __restrict__ gz,
                   const unsigned char* __restrict__ plist /*[M][F][kListCap]*/, const unsigned char* __restrict__ pcount /*[M][F]*/,
                   float* __restrict__ dface /*[M][F][6]*/) {
   int n, bxi;
@@ -1397,6 +1398,19 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
   const int f = frame_ok ? bxi * kBwdFaces + ((int)threadIdx.x / kBwdLanes) : F;
   const int sub = threadIdx.x & (kBwdLanes - 1);
   float ga[2] = {0.f, 0.f}, gb[2] = {0.f, 0.f}, gc[2] = {0.f, 0.f};
+  // (pin: knowing the sums are zero in the two peeled rounds, the compiler multiplies into fresh registers there and moves six
+  // zeros at each of pair's three exits; opaque, every round accumulates in place like the rolled loop)
+  asm volatile("" : "+v"(ga[0]), "+v"(ga[1]), "+v"(gb[0]), "+v"(gb[1]), "+v"(gc[0]), "+v"(gc[1]));
+  // Everything keyed by the face is addressed as (the frame's base, uniform over the workgroup: scalar registers) + (an unsigned
+  // 32-bit byte offset of the face in its frame: one vector register), the form the loads take without any 64-bit lane arithmetic.
+  // The largest offset is the list's, f kListCap + 127 < 2^32: kMaxModelFaces (smalfit_plan.h)
+  static_assert((unsigned long long)kMaxModelFaces * kListCap <= (1ull << 32), "a face's byte offset in its frame's lists fits 32 bits");
+  const size_t nF = (size_t)n * F;
+  const unsigned char* lst_n = plist + nF * kListCap;
+  const unsigned char* cnt_n = pcount + nF;
+  const char* rec_n = reinterpret_cast<const char*>(frec + nF * kRecVecs);
+  const char* box_n = reinterpret_cast<const char*>(fbox + nF);
+  char* out_n = reinterpret_cast<char*>(dface + nF * 6);
   SMALFIT_WORK(int wb_vis = 0; int wb_live = 0; int wb_eval = 0; int wb_in = 0; int wb_trips = 0; int wb_deadr = 0; int wb_r = 0;
                const unsigned long long wb_t0 = __builtin_amdgcn_s_memtime(); unsigned long long wb_t1 = wb_t0;
                int wb_a12 = 0; int wb_a24 = 0; int wb_a40 = 0; float wb_amax = 0.f;)
@@ -1406,14 +1420,13 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
     // everything whose address depends on the face id alone is requested in one go: the record, the list's flag / length, its
     // first two rounds of entries (most lists are shorter) and the lane's candidate mask (the same 128 bytes read the other way) --
     // one trip to memory, not three
-    const size_t fi = (size_t)n * F + f;
-    const unsigned char* lst = plist + fi * kListCap;
-    int cnt = pcount[fi];
-    int q_first = lst[sub], q_second = lst[sub + kBwdLanes];
-    unsigned long long lmask = reinterpret_cast<const unsigned long long*>(lst)[sub];
-    const float4* fr = frec + fi * kRecVecs;
+    const unsigned uf = (unsigned)f, lst_off = uf * (unsigned)kListCap;
+    int cnt = cnt_n[uf];
+    int q_first = lst_n[lst_off + (unsigned)sub], q_second = lst_n[lst_off + (unsigned)(sub + kBwdLanes)];
+    unsigned long long lmask = *reinterpret_cast<const unsigned long long*>(lst_n + (lst_off + (unsigned)sub * 8u));
+    const float4* fr = reinterpret_cast<const float4*>(rec_n + uf * (unsigned)(kRecVecs * sizeof(float4)));
     float4 ra = fr[0], rb = fr[1], rc = fr[2], rd = fr[3];
-    int2 box = fbox[fi];
+    int2 box = *reinterpret_cast<const int2*>(box_n + uf * (unsigned)sizeof(int2));
     // (pin: the compiler would otherwise sink each load to its first use, behind the branches, and serialise the trips)
     {
       unsigned mlo = (unsigned)lmask, mhi = (unsigned)(lmask >> 32);
@@ -1426,7 +1439,6 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
     const int c0 = box.x & 0xffff, c1 = box.x >> 16, r0 = box.y & 0xffff, r1 = box.y >> 16;
     SMALFIT_WORK(if (c0 <= c1 + 70000) wb_t1 = __builtin_amdgcn_s_memtime();)
     if (c0 <= c1) {
-      const float inv_s = 1.0f / (float)S;
       const float2* gp = gz + (size_t)n * S * S;
       const int bw = c1 - c0 + 1, npx = bw * (r1 - r0 + 1);
       // one (face, pixel) pair: adjoint seed, depth against the pixel's K-th nearest, distance maths, accumulate
@@ -1485,7 +1497,7 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
       if (cnt <= kListCap) {
         // the forward sweep's compacted candidate list: box-relative pixel indices, 16 at a time
         for (int i = sub; i < cnt; i += kBwdLanes) {
-          const float qf = (float)((i < kBwdLanes) ? q_first : ((i < 2 * kBwdLanes) ? q_second : (int)lst[i]));
+          const float qf = (float)((i < kBwdLanes) ? q_first : ((i < 2 * kBwdLanes) ? q_second : (int)lst_n[lst_off + (unsigned)i]));
           float rowf, colf;
           coords(qf, rowf, colf);
           pair(rowf, colf, load_seed(rowf, colf));
@@ -1511,15 +1523,28 @@ raster_bwd_kernel(int F, int M, int S, const float4* __restrict__ frec, const in
     }
   }
   SMALFIT_WORK(const unsigned long long wb_t2 = __builtin_amdgcn_s_memtime();)
-#pragma unroll
-  for (int o = kBwdLanes / 2; o > 0; o >>= 1) {
-    ga[0] += __shfl_xor(ga[0], o, 64); ga[1] += __shfl_xor(ga[1], o, 64);
-    gb[0] += __shfl_xor(gb[0], o, 64); gb[1] += __shfl_xor(gb[1], o, 64);
-    gc[0] += __shfl_xor(gc[0], o, 64); gc[1] += __shfl_xor(gc[1], o, 64);
-  }
-  if (f < F && sub == 0) {
-    float* o = dface + ((size_t)n * F + f) * 6;
-    o[0] = ga[0]; o[1] = ga[1]; o[2] = gb[0]; o[3] = gb[1]; o[4] = gc[0]; o[5] = gc[1];
+  // The six sums over the face's 16 lanes, as a reduce-scatter.  An xor butterfly (o = 8, 4, 2, 1) adds a + b in one partner and
+  // b + a in the other, the same float: after every step all lanes of a coset hold one value, and only lane 0's was ever stored.
+  // So a lane keeps the half of its values its side of the step owns and sends the other half -- 3, 2, 1, 1 exchanges instead of
+  // 6 per step, every sum the same tree of the same additions -- and each sum ends in a lane of its own, which stores it:
+  //   o = 8: bit 3 of the lane picks (ga0, ga1, gb0) or (gb1, gc0, gc1) as (x, y, z);  o = 4: x in both halves, bit 2 picks y or z
+  //   as w;  o = 2: bit 1 picks x or w;  o = 1: the pair of lanes holds one sum.  Lanes 0, 2, 6 | 8, 10, 14 store dface[0..2 | 3..5]
+  // (idle 16-lane groups of the last wave, and whole waves past the last frame, shuffle zeros among themselves and store nothing)
+  {
+    const bool b3 = sub & 8, b2 = sub & 4, b1 = sub & 2;
+    float x = b3 ? gb[1] : ga[0], y = b3 ? gc[0] : ga[1], z = b3 ? gc[1] : gb[0];
+    x += __shfl_xor(b3 ? ga[0] : gb[1], 8, 64);
+    y += __shfl_xor(b3 ? ga[1] : gc[0], 8, 64);
+    z += __shfl_xor(b3 ? gb[0] : gc[1], 8, 64);
+    x += __shfl_xor(x, 4, 64);
+    float w = b2 ? z : y;
+    w += __shfl_xor(b2 ? y : z, 4, 64);
+    float v = b1 ? w : x;
+    v += __shfl_xor(b1 ? x : w, 2, 64);
+    v += __shfl_xor(v, 1, 64);
+    const int k = (b3 ? 3 : 0) + (b1 ? (b2 ? 2 : 1) : 0);
+    if (f < F && (sub & 1) == 0 && (b1 || !b2))
+      *reinterpret_cast<float*>(out_n + ((unsigned)f * (unsigned)(6 * sizeof(float)) + (unsigned)k * (unsigned)sizeof(float))) = v;
   }
   SMALFIT_WORK({ const int anylive = wb_live > 0 ? 1 : 0; int fl = anylive;
                  for (int o = 8; o > 0; o >>= 1) fl |= __shfl_xor(fl, o, 64);

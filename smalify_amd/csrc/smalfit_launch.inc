@@ -144,10 +144,11 @@ namespace smalfit {
 static void launch_raster_bwd(smalfit_engine* e, hipStream_t st, int M) {
   const ModelDev& m = e->model->dev;
   const unsigned grid = (unsigned)raster_bwd_grid(m.F, M), block = kBwdLanes * kBwdFaces;
+  const float inv_s = raster_bwd_inv_s(e->S);
   if (e->unclamped_edge_t)
-    raster_bwd_kernel<true><<<grid, block, 0, st>>>(m.F, M, e->S, e->frec, e->fbox, e->zc, e->gz, e->plist, e->pcount, e->dface);
+    raster_bwd_kernel<true><<<grid, block, 0, st>>>(m.F, M, e->S, inv_s, e->frec, e->fbox, e->zc, e->gz, e->plist, e->pcount, e->dface);
   else
-    raster_bwd_kernel<false><<<grid, block, 0, st>>>(m.F, M, e->S, e->frec, e->fbox, e->zc, e->gz, e->plist, e->pcount, e->dface);
+    raster_bwd_kernel<false><<<grid, block, 0, st>>>(m.F, M, e->S, inv_s, e->frec, e->fbox, e->zc, e->gz, e->plist, e->pcount, e->dface);
 }
 }  // namespace smalfit
 
@@ -1071,6 +1072,13 @@ int smalfit_render_backward(smalfit_engine* e, void* stream, int M, const float*
   launch_raster_bwd(e, st, M);
   raster_vertex_grad_kernel<<<dim3(elem_blocks(m.V), M), 256, 0, st>>>(m, e->proj, e->dface, dverts);
   LAUNCH_OK("render_backward kernels");
+  return 0;
+}
+
+int smalfit_engine_face_list_lengths(smalfit_engine* e, void* stream, int M, unsigned char* lengths) {
+  if (refused("smalfit_engine_face_list_lengths", null_argument_refusal(e && lengths))) return 1;
+  if (refused("smalfit_engine_face_list_lengths", render_frames_refusal(M, e->maxM))) return 1;
+  HIP_OK(hipMemcpyAsync(lengths, e->pcount, (size_t)M * e->model->dev.F, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 

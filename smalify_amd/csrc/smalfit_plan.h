@@ -126,6 +126,12 @@ constexpr int kBwdLanes = 16;                // lanes per face of the backward g
 constexpr int kBwdFaces = 4;                 // faces per workgroup
 constexpr int raster_bwd_blocks_per_frame(int F) { return (F + kBwdFaces - 1) / kBwdFaces; }
 constexpr int raster_bwd_grid(int F, int M) { return xcd_grid(raster_bwd_blocks_per_frame(F), M); }
+// 1 / S for its pixel-to-NDC map, divided here once: IEEE division, the bits the device's correctly rounded sequence gave in every wave
+inline float raster_bwd_inv_s(int S) { return 1.0f / (float)S; }
+// It addresses what a face owns in its frame -- record, box, candidate list, list length, adjoint row -- by an unsigned 32-bit
+// byte offset from the frame's base.  The largest is the list's: 128 bytes per face (kListCap of kernels_raster.inc, which
+// asserts the product), so a model may have 2^25 faces.  model_dims_refusal turns larger ones away
+constexpr int kMaxModelFaces = 1 << 25;
 
 // vertex_bwd_kernel
 constexpr int vertex_bwd_grid(int Vp, int M) { return xcd_grid(vertex_blocks(Vp), M); }
@@ -241,6 +247,8 @@ constexpr int kFitBetas = 20;
 // -> why smalfit_model_create refuses a model of these dimensions (the text behind "smalfit_model_create: "), or nullptr
 inline const char* model_dims_refusal(int num_verts, int num_faces, int num_betas) {
   if (num_verts <= 0 || num_faces <= 0 || num_betas <= 0) return "bad dimensions";
+  static_assert(kMaxModelFaces == 33554432, "the message below names the limit");
+  if (num_faces > kMaxModelFaces) return "num_faces above 33554432 is not supported (the backward gather addresses a frame's faces by 32-bit byte offsets)";
   static_assert(kMaxModelBetas == 64, "the message below names the limit");
   if (num_betas > kMaxModelBetas) return "num_betas above 64 is not supported (the rest-joint path of d/d betas reduces 64 shape directions)";
   return nullptr;

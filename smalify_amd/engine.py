@@ -385,6 +385,14 @@ class Engine:
                                                _ptr(dsil), _ptr(dverts)), "smalfit_render_backward")
         return dverts
 
+    def face_list_lengths(self, M):
+        """(M, F) uint8: per face the length of the candidate list the last silhouette forward handed to the backward gather
+        (0..128), 254 = candidate masks, 255 = the whole box is walked (diagnostics; results never depend on the form)"""
+        out = torch.empty(int(M), self.model.num_faces, dtype=torch.uint8, device="cuda")
+        check(self.lib.smalfit_engine_face_list_lengths(self.handle, _stream(), int(M), _ptr_u8(out)),
+              "smalfit_engine_face_list_lengths")
+        return out
+
     def project_points_backward(self, points, dproj):
         dpoints = torch.empty_like(points)
         count = int(points.numel() // 3)
