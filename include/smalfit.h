@@ -37,7 +37,9 @@ typedef struct smalfit_engine smalfit_engine;
  * total_frames; smalfit_engine_clear_joint_limits, smalfit_shard_local_step; 4 = smalfit_shard_run (the sharded loop of a
  * whole stage in one call, the collective supplied by the host as a function pointer), smalfit_rccl_allgather;
  * 5 = smalfit_engine_set_option; 6 = smalfit_fit_args.subject_frames / losses_per_frame (a batch of independent images,
- * each with its own shape; one row of loss terms per frame). */
+ * each with its own shape; one row of loss terms per frame).  Added within version 6, no struct of it changing its layout:
+ * smalfit_fit_eval_windows (smalfit_window_rows); smalfit_fit_metrics (smalfit_metrics_args: silhouette IoU counts and PCK
+ * per frame). */
 #define SMALFIT_ABI_VERSION 6
 int smalfit_version(void);
 const char* smalfit_last_error(void);
@@ -282,6 +284,43 @@ typedef struct smalfit_window_rows {
   float* g_log_beta_scales;      /* (W, 6) or NULL; logscale_mode 1 only, refused when non-NULL in modes 0 / 2 */
 } smalfit_window_rows;
 int smalfit_fit_eval_windows(smalfit_engine* engine, void* stream, const smalfit_fit_args* args, const smalfit_window_rows* rows);
+
+/* ---- how good a fit is: silhouette intersection / union and PCK per frame -------------------------------------------
+ * No counterpart in the reference, which contains no evaluation code: the definitions below are THIS PROJECT'S.  (The PCK
+ * normaliser -- the square root of the ground-truth silhouette's area -- is the convention the BADJA / StanfordExtra results
+ * are recalled to use; no parity with anyone's evaluation script is claimed.)
+ *   covered        a pixel is covered exactly when smalfit_render_color on the same vertices would not leave it white (the
+ *                  hard rasterisation of p3d_renderer.py:41-59: blur_radius 0, one face per pixel; the same per-face record,
+ *                  the same clipped pixel box, the same inclusion test -- one device function serves both entry points)
+ *   target on      a float target pixel t is on when t > 0.5f, a byte target pixel b when b >= 128
+ *   sil_counts     row n = pixels of frame n in: covered AND on | covered OR on | covered | on.  Integer counts: no quotient is
+ *                  formed on the device (IoU = sil_counts[n][0] / sil_counts[n][1] is the host's, as is what an empty union means)
+ *   keypoint_dist  [n][k] = hypot(proj - target) / sqrtf((float)sil_counts[n][3]) in float32, for all 25 keypoints whether
+ *                  visible or not; +inf for every keypoint of a frame whose target is empty
+ *   visible        target_visibility > 0
+ *   pck_counts     row n = visible keypoints, then for each t the visible keypoints with keypoint_dist <= thresholds[t]
+ * Everything is enqueued on `stream`; nothing synchronises.  A refused block launches nothing and leaves every output alone.
+ * The call uses the engine's projection workspace, as smalfit_render_color does: it must not overlap another call on the same
+ * engine (calls enqueued on one stream never do). */
+#define SMALFIT_MAX_PCK_THRESHOLDS 8
+typedef struct smalfit_metrics_args {
+  unsigned struct_size;                /* sizeof(smalfit_metrics_args) of the caller's header; checked before any other field */
+  int num_frames;                      /* M <= the engine's max_frames */
+  const float* verts;                  /* (M,V,3) world, translation applied: verts_out of smalfit_fit_eval */
+  const float* target_sil;             /* (M,S,S) float, or NULL */
+  const unsigned char* target_sil_u8;  /* (M,S,S) bytes, used when not NULL (as in smalfit_fit_args) */
+  unsigned* sil_counts;                /* (M,4): intersection, union, rendered, target -- pixels */
+  unsigned char* mask_out;             /* (M,S,S) 0/1 hard coverage, or NULL */
+  /* keypoints: all of the next three given, or all NULL (silhouette only; the outputs below must then be NULL too) */
+  const float* proj_joints;            /* (M,25,2) (row, col): proj_out of smalfit_fit_eval */
+  const float* target_joints;          /* (M,25,2) */
+  const float* target_visibility;      /* (M,25) */
+  int num_thresholds;                  /* T in 1..8 when keypoints are given */
+  float thresholds[SMALFIT_MAX_PCK_THRESHOLDS];   /* host values, each finite and > 0 */
+  float* keypoint_dist;                /* (M,25) or NULL: distance / sqrt(target pixels) of EVERY keypoint */
+  int* pck_counts;                     /* (M,1+T) or NULL: visible keypoints, then those with dist <= thresholds[t] */
+} smalfit_metrics_args;
+int smalfit_fit_metrics(smalfit_engine* engine, void* stream, const smalfit_metrics_args* args);
 
 /* ---- the epoch loop: loss + backward + optimizer.step(), `iterations` times in one call ---------------------------
  * replaces: the body of the epoch loop                        reference smal_fitter/optimize_to_joints.py:113-137

@@ -60,6 +60,22 @@ class WindowRows(C.Structure):
         self.struct_size = C.sizeof(WindowRows)
 
 
+MAX_PCK_THRESHOLDS = 8            # SMALFIT_MAX_PCK_THRESHOLDS
+
+
+class MetricsArgs(C.Structure):
+    """smalfit_metrics_args: silhouette counts and PCK per frame (smalfit_fit_metrics)"""
+    _fields_ = [("struct_size", C.c_uint), ("num_frames", C.c_int), ("verts", C.c_void_p), ("target_sil", C.c_void_p),
+                ("target_sil_u8", C.c_void_p), ("sil_counts", C.c_void_p), ("mask_out", C.c_void_p),
+                ("proj_joints", C.c_void_p), ("target_joints", C.c_void_p), ("target_visibility", C.c_void_p),
+                ("num_thresholds", C.c_int), ("thresholds", C.c_float * MAX_PCK_THRESHOLDS),
+                ("keypoint_dist", C.c_void_p), ("pck_counts", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(MetricsArgs)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -139,6 +155,7 @@ SIGNATURES = {
     "smalfit_project_points_backward": (_I, [_VP, _I, _I, _VP, _VP, _VP]),
     "smalfit_fit_eval": (_I, [_VP, _VP, C.POINTER(FitArgs)]),
     "smalfit_fit_eval_windows": (_I, [_VP, _VP, C.POINTER(FitArgs), C.POINTER(WindowRows)]),
+    "smalfit_fit_metrics": (_I, [_VP, _VP, C.POINTER(MetricsArgs)]),
     "smalfit_fit_run": (_I, [_VP, _VP, C.POINTER(FitArgs), C.POINTER(AdamArgs), _I]),
     "smalfit_engine_set_graph": (_I, [_VP, _I]),
     "smalfit_adam_segments": (_I, [_VP, C.POINTER(AdamArgs)]),
@@ -163,7 +180,7 @@ SIGNATURES = {
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
 # built before them loads, and resolve() names the symbol when one is asked for
-LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows"])
+LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics"])
 
 
 class SmalfitError(RuntimeError):

@@ -87,6 +87,7 @@ struct smalfit_engine {
   unsigned char* pcount;  // their lengths (kNoList: evaluate the whole box): [M][F]
   unsigned long long* zbuf = nullptr;   // colour render only, allocated on first use: [M][S*S]
   float* vnorm = nullptr;               // colour render only: vertex normals [M][3][Vp]
+  unsigned char* cover = nullptr;       // smalfit_fit_metrics only, allocated on first use: hard coverage, a byte per pixel [M][S*S]
   int *qcount, *frect, *queue, *bqueue;
   long long* qloss;
   int nrb = 0;
@@ -456,6 +457,7 @@ void smalfit_engine_destroy(smalfit_engine* e) {
   if (e->slab) (void)hipFree(e->slab);
   if (e->blist) (void)hipFree(e->blist);
   if (e->zbuf) (void)hipFree(e->zbuf);
+  if (e->cover) (void)hipFree(e->cover);
   if (e->vnorm) (void)hipFree(e->vnorm);
   delete e;
 }
@@ -1055,6 +1057,36 @@ int smalfit_render_color(smalfit_engine* e, void* stream, int M, const float* ve
   color_shade_kernel<<<dim3((unsigned)elem_blocks((long long)npx), M), 256, 0, st>>>(m, e->S, e->proj, e->verts, e->vnorm, e->zbuf, rgb[0], rgb[1],
                                                                             rgb[2], image);
   LAUNCH_OK("colour render kernels");
+  return 0;
+}
+
+// silhouette intersection / union counts and PCK per frame (definitions: include/smalfit.h; rules and grids: smalfit_plan.h)
+// Like smalfit_render_color it projects into the engine's own workspace (e->proj) and keeps its mask there (e->cover): the call
+// must not overlap another call on the same engine (calls on one stream never do); an evaluation after it projects afresh
+int smalfit_fit_metrics(smalfit_engine* e, void* stream, const smalfit_metrics_args* a) {
+  if (refused("smalfit_fit_metrics", null_argument_refusal(e && a))) return 1;
+  if (refused("smalfit_fit_metrics", metrics_args_refusal(a, e->maxM))) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  const ModelDev& m = e->model->dev;
+  const int M = a->num_frames, S = e->S;
+  const size_t npx = (size_t)S * S;
+  if (!e->cover && hipMalloc(&e->cover, (size_t)e->maxM * npx) != hipSuccess)
+    return fail("smalfit_fit_metrics: hipMalloc of the coverage mask failed");
+  project_verts_kernel<<<dim3(vertex_blocks(m.Vp), M), 256, 0, st>>>(M, m.V, m.Vp, a->verts, e->proj);
+  HIP_OK(hipMemsetAsync(e->cover, 0, (size_t)M * npx, st));
+  HIP_OK(hipMemsetAsync(a->sil_counts, 0, (size_t)M * 4 * sizeof(unsigned), st));
+  const Grid2 cg = cover_grid(m.F, M), sg = sil_counts_grid(S, M);
+  cover_kernel<<<dim3(cg.x, cg.y), 256, 0, st>>>(m, S, e->proj, e->cover);
+  if (a->target_sil_u8) sil_counts_kernel<unsigned char><<<dim3(sg.x, sg.y), 256, 0, st>>>(S, e->cover, a->target_sil_u8, a->sil_counts);
+  else sil_counts_kernel<float><<<dim3(sg.x, sg.y), 256, 0, st>>>(S, e->cover, a->target_sil, a->sil_counts);
+  if (metrics_keypoints(a) && (a->keypoint_dist || a->pck_counts)) {
+    PckThresholds thr{};
+    for (int t = 0; t < a->num_thresholds; ++t) thr.t[t] = a->thresholds[t];
+    pck_kernel<<<pck_grid(M), 64, 0, st>>>(a->proj_joints, a->target_joints, a->target_visibility, a->sil_counts, a->num_thresholds, thr,
+                                          a->keypoint_dist, a->pck_counts);
+  }
+  LAUNCH_OK("metrics kernels");
+  if (a->mask_out) HIP_OK(hipMemcpyAsync(a->mask_out, e->cover, (size_t)M * npx, hipMemcpyDeviceToDevice, st));
   return 0;
 }
 

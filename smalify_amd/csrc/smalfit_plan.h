@@ -6,6 +6,7 @@
 // (smalfit_launch.inc, smalfit_mesh3d.inc) and the CPU tests (tests/host_plan_shim.cpp, compiled by g++) call the same code.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "../../include/smalfit.h"
@@ -77,13 +78,20 @@ constexpr int xcd_grid(int blocks_per_frame, int M) { return blocks_per_frame * 
 constexpr int elem_blocks(long long elements) { return (int)((elements + 255) / 256); }
 constexpr int vertex_blocks(int Vp) { return Vp / 256; }
 constexpr int rigid_blocks(int count) { return (count + 63) / 64; }           // global_rigid_kernel and its adjoint: one wave per workgroup, a lane per chain
+struct Grid2 { int x, y; };
 constexpr int color_face_blocks(int F) { return (F + 15) / 16; }             // color_zbuf_kernel: 16 faces per workgroup
+// smalfit_fit_metrics: cover_kernel walks the faces as color_zbuf_kernel does; sil_counts_kernel gives a thread kSilCountPixels
+// pixels of one frame (one 16-byte read of the mask), 256 threads per slab; pck_kernel one wave per frame
+constexpr int kSilCountPixels = 16;
+constexpr Grid2 cover_grid(int F, int M) { return Grid2{color_face_blocks(F), M}; }
+constexpr int sil_count_slabs(int S) { return ((S * S + kSilCountPixels - 1) / kSilCountPixels + 255) / 256; }
+constexpr Grid2 sil_counts_grid(int S, int M) { return Grid2{sil_count_slabs(S), M}; }
+constexpr int pck_grid(int M) { return M; }
 
 // skinning: (vertex blocks, frame tiles) of the form skin_form chose
 constexpr int kSkinGroups = 2;               // skin_mfma_split_kernel: 16-vertex groups per workgroup (4 waves each): they share the staged transforms of the 16 frames
 constexpr int kSkinVerts = 16 * kSkinGroups;       // its vertices per workgroup
 constexpr int kSkinThreads = 256 * kSkinGroups;    // and its threads
-struct Grid2 { int x, y; };
 constexpr Grid2 skin_grid(SkinForm form, int M, int Vp) {
   return form == SkinForm::Wide ? Grid2{Vp / 64, (M + 15) / 16} : form == SkinForm::Split ? Grid2{Vp / kSkinVerts, (M + 15) / 16} : Grid2{Vp / 64, (M + 7) / 8};
 }
@@ -362,6 +370,28 @@ inline const char* window_rows_refusal(const smalfit_fit_args* a, const smalfit_
     return "smalfit_window_rows.num_windows is not the number of windows these frames belong to";
   if (r->g_log_beta_scales && a->logscale_mode != 1)
     return "smalfit_window_rows.g_log_beta_scales needs shared log_beta_scales (logscale_mode 1)";
+  return nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// smalfit_metrics_args: which blocks are refused (smalfit_fit_metrics)
+// ------------------------------------------------------------------------------------------------
+inline bool metrics_keypoints(const smalfit_metrics_args* a) { return a->proj_joints && a->target_joints && a->target_visibility; }
+// -> why smalfit_fit_metrics refuses the block (the text behind "smalfit_fit_metrics: "), or nullptr.  struct_size first: with a
+// block laid out by another header no other field can be trusted
+inline const char* metrics_args_refusal(const smalfit_metrics_args* a, int max_frames) {
+  if (a->struct_size != (unsigned)sizeof(smalfit_metrics_args))
+    return "smalfit_metrics_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (a->num_frames <= 0 || a->num_frames > max_frames) return "num_frames exceeds the engine's max_frames";
+  if (!a->verts || !a->sil_counts) return "verts / sil_counts missing";
+  if (!a->target_sil && !a->target_sil_u8) return "target_sil missing (give target_sil or target_sil_u8)";
+  const bool any = a->proj_joints || a->target_joints || a->target_visibility;
+  if (any && !metrics_keypoints(a)) return "give all of proj_joints, target_joints and target_visibility, or none of them";
+  if (!any) return a->keypoint_dist || a->pck_counts ? "keypoint_dist / pck_counts given without the keypoint inputs" : nullptr;
+  static_assert(SMALFIT_MAX_PCK_THRESHOLDS == 8, "the message below names the limit");
+  if (a->num_thresholds < 1 || a->num_thresholds > SMALFIT_MAX_PCK_THRESHOLDS) return "num_thresholds must be 1..8";
+  for (int t = 0; t < a->num_thresholds; ++t)
+    if (!(std::isfinite(a->thresholds[t]) && a->thresholds[t] > 0.f)) return "every threshold must be finite and > 0";
   return nullptr;
 }
 

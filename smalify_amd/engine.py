@@ -379,6 +379,60 @@ class Engine:
               "smalfit_render_color")
         return image
 
+    def fit_metrics(self, verts, target_sil, proj_joints=None, target_joints=None, target_visibility=None,
+                    thresholds=(0.15,), want_mask=False):
+        """How good a fit is, per frame (smalfit_fit_metrics; the definitions are this project's, include/smalfit.h).
+        verts (M,V,3) with the translation applied and proj_joints (M,25,2): verts_out / proj_out of an evaluation;
+        target_sil (M,S,S) float32 (on above 0.5) or uint8 (on from 128); keypoints: all three tensors or none.
+        -> dict of device tensors: sil_counts (M,4) int32 = pixels in [rendered & target, rendered | target, rendered, target]
+        (the hard render: covered exactly where render_color is not white); with keypoints keypoint_dist (M,25) = distance /
+        sqrt(target pixels) of every keypoint (+inf where the target is empty) and pck_counts (M,1+T) int32 = visible
+        keypoints, then those within thresholds[t]; with want_mask the hard coverage mask (M,S,S) uint8.  No quotient is
+        formed on the device: smalify_amd.metrics.summarise turns the counts into IoU and PCK."""
+        fn = _lib.resolve(self.lib, "smalfit_fit_metrics")
+        M, S, V = int(verts.shape[0]), self.image_size, self.model.num_verts
+        if tuple(verts.shape) != (M, V, 3):
+            raise SmalfitError("verts must be (num_frames, %d, 3)" % V)
+        # the library cannot know the extent, the element type or the device of a pointer
+        if not (isinstance(target_sil, torch.Tensor) and tuple(target_sil.shape) == (M, S, S)
+                and target_sil.dtype in (torch.float32, torch.uint8)):
+            raise SmalfitError("target_sil must be a (num_frames, %d, %d) tensor of float32 or uint8" % (S, S))
+        kp = (proj_joints, target_joints, target_visibility)
+        for t, shape in zip(kp, ((M, 25, 2), (M, 25, 2), (M, 25))):
+            if t is not None and not (isinstance(t, torch.Tensor) and tuple(t.shape) == shape):
+                raise SmalfitError("keypoint tensors must be (num_frames,25,2), (num_frames,25,2) and (num_frames,25)")
+        for t in (target_sil,) + kp:
+            if t is not None and t.device != verts.device:
+                raise SmalfitError("target_sil and the keypoint tensors must be on the device of verts (%s)" % verts.device)
+        thr = [float(t) for t in thresholds]
+        if len(thr) > _lib.MAX_PCK_THRESHOLDS:
+            raise SmalfitError("at most %d thresholds" % _lib.MAX_PCK_THRESHOLDS)
+        dev = verts.device
+        have_kp = all(t is not None for t in kp)
+        out = {"sil_counts": torch.empty(M, 4, dtype=torch.int32, device=dev)}
+        if have_kp:
+            out["keypoint_dist"] = torch.empty(M, 25, device=dev)
+            out["pck_counts"] = torch.empty(M, 1 + len(thr), dtype=torch.int32, device=dev)
+        if want_mask:
+            out["mask"] = torch.empty(M, S, S, dtype=torch.uint8, device=dev)
+        a = _lib.MetricsArgs()
+        a.num_frames, a.verts = M, _ptr(verts)
+        if target_sil.dtype == torch.uint8:
+            a.target_sil_u8 = _ptr_u8(target_sil)
+        else:
+            a.target_sil = _ptr(target_sil)
+        a.sil_counts = C.c_void_p(out["sil_counts"].data_ptr())
+        a.mask_out = C.c_void_p(out["mask"].data_ptr()) if want_mask else None
+        a.proj_joints, a.target_joints, a.target_visibility = _ptr(proj_joints), _ptr(target_joints), _ptr(target_visibility)
+        a.num_thresholds = len(thr)
+        for i, t in enumerate(thr):
+            a.thresholds[i] = t
+        if have_kp:
+            a.keypoint_dist = _ptr(out["keypoint_dist"])
+            a.pck_counts = C.c_void_p(out["pck_counts"].data_ptr())
+        check(fn(self.handle, _stream(), C.byref(a)), "smalfit_fit_metrics")
+        return out
+
     def render_backward(self, verts, sil, dsil):
         dverts = torch.empty_like(verts)
         check(self.lib.smalfit_render_backward(self.handle, _stream(), int(verts.shape[0]), _ptr(verts), _ptr(sil),

@@ -372,24 +372,46 @@ class FusedFitter:
             return self.target_sil.to(torch.float32) / 255.0
         return self.target_sil
 
+    def _forward_kwargs(self):
+        """how the frames relate in a forward-only evaluation: no temporal term, no halos"""
+        return dict(window=self.window, temporal=False)
+
+    def _forward_only(self, **outs):
+        """one evaluation at the current parameters with every weight 0, into the caller's output tensors (sil_out, proj_out,
+        verts_out) and a scratch loss vector: the fit's losses and gradients are left alone.  snapshot and metrics both go through here"""
+        self.e.fit_eval(betas=self.p["betas"], log_beta_scales=self.p["log_beta_scales"],
+                        global_rotation=self.p["global_rotation"], joint_rotations=self.p["joint_rotations"],
+                        trans=self.p["trans"], target_joints=None, target_visibility=None, target_sil=None,
+                        weights=(0, 0, 0, 0, 0, 0), w_temp=0.0, global_mask=self.global_mask, rotation_mask=self.rotation_mask,
+                        losses=torch.empty(eng.NUM_LOSS_TERMS, device=self.flat.device), grads={}, want=(),
+                        **self._forward_kwargs(), **outs)
+
     def snapshot(self):
         """-> (verts (N,V,3) translated, silhouettes (N,S,S), projected keypoints (N,25,2)) at the current parameters.
         Forward only, into scratch buffers: the fit's loss vector and gradients are left alone."""
         dev = self.flat.device
-        V = self.e.model.num_verts
-        verts = torch.empty(self.N, V, 3, device=dev)
+        verts = torch.empty(self.N, self.e.model.num_verts, 3, device=dev)
         sil = torch.empty(self.N, self.S, self.S, device=dev)
         proj = torch.empty(self.N, 25, 2, device=dev)
-        self.e.fit_eval(betas=self.p["betas"], log_beta_scales=self.p["log_beta_scales"],
-                        global_rotation=self.p["global_rotation"], joint_rotations=self.p["joint_rotations"],
-                        trans=self.p["trans"], target_joints=None, target_visibility=None, target_sil=None,
-                        weights=(0, 0, 0, 0, 0, 0), w_temp=0.0, window=self.window, temporal=False,
-                        global_mask=self.global_mask, rotation_mask=self.rotation_mask,
-                        losses=torch.empty(eng.NUM_LOSS_TERMS, device=dev), grads={}, want=(), sil_out=sil, proj_out=proj, verts_out=verts)
+        self._forward_only(sil_out=sil, proj_out=proj, verts_out=verts)
         return verts, sil, proj
 
-    def run_schedule(self, opt_weights=None, iters_scale=1.0, on_visualize=None, vis_frequency=None):
-        """The reference's full stage loop. Returns per-stage final loss vectors (host)."""
+    def metrics(self, thresholds=(0.15,), want_mask=False):
+        """How good the fit is at the current parameters, per frame (Engine.fit_metrics; smalify_amd.metrics.summarise turns
+        the result into IoU and PCK): one forward-only evaluation for the vertices and the projected keypoints -- the
+        rasteriser does not run, the fit's loss vector and gradients are left alone -- then one smalfit_fit_metrics call
+        against the target silhouettes as they are stored and the full visibility (not stage 0's torso subset).
+        -> dict of device tensors: sil_counts (N,4), keypoint_dist (N,25), pck_counts (N,1+T), mask (N,S,S) if asked for."""
+        dev = self.flat.device
+        verts = torch.empty(self.N, self.e.model.num_verts, 3, device=dev)
+        proj = torch.empty(self.N, 25, 2, device=dev)
+        self._forward_only(proj_out=proj, verts_out=verts)
+        return self.e.fit_metrics(verts, self.target_sil, proj, self.target_joints, self.visibility_full,
+                                  thresholds=thresholds, want_mask=want_mask)
+
+    def run_schedule(self, opt_weights=None, iters_scale=1.0, on_visualize=None, vis_frequency=None, on_stage_end=None):
+        """The reference's full stage loop. Returns per-stage final loss vectors (host).
+        on_stage_end(fitter, stage_id): called after the last epoch of every stage (e.g. to report metrics)."""
         W = np.array(config.OPT_WEIGHTS if opt_weights is None else opt_weights).T
         vis_frequency = config.VIS_FREQUENCY if vis_frequency is None else vis_frequency
         history = []
@@ -408,6 +430,8 @@ class FusedFitter:
                     on_visualize(self, stage_id, epoch_id)
                 epoch_id += n
             history.append(self.losses.cpu().numpy().copy())
+            if on_stage_end is not None:
+                on_stage_end(self, stage_id)
         return history
 
     # ---- checkpoints (smal_fitter.py:192-219, optimize_to_joints.py:43-53) -------------------------------------

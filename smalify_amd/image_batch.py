@@ -126,19 +126,13 @@ class ImageBatchFitter(fit.FusedFitter):
         self.evaluate(weights, 0.0, stage_id, want=self.trainable(stage_id), losses_per_frame=self.losses_per_image)
         return self.losses_per_image
 
-    def snapshot(self):
-        dev = self.flat.device
-        V = self.e.model.num_verts
-        verts = torch.empty(self.N, V, 3, device=dev)
-        sil = torch.empty(self.N, self.S, self.S, device=dev)
-        proj = torch.empty(self.N, 25, 2, device=dev)
-        self.e.fit_eval(betas=self.p["betas"], log_beta_scales=self.p["log_beta_scales"],
-                        global_rotation=self.p["global_rotation"], joint_rotations=self.p["joint_rotations"],
-                        trans=self.p["trans"], target_joints=None, target_visibility=None, target_sil=None,
-                        weights=(0, 0, 0, 0, 0, 0), w_temp=0.0, global_mask=self.global_mask, rotation_mask=self.rotation_mask,
-                        losses=torch.empty(eng.NUM_LOSS_TERMS, device=dev), grads={}, want=(), sil_out=sil, proj_out=proj,
-                        verts_out=verts, **self._sequence_kwargs())
-        return verts, sil, proj
+    def _forward_kwargs(self):
+        return self._sequence_kwargs()
+
+    def image_metrics(self, thresholds=(0.15,), want_mask=False):
+        """FusedFitter.metrics with one row per image: row n of sil_counts / keypoint_dist / pck_counts is image n's, and
+        does not depend on which other images share its batch.  The first thing to ask after a batch: which fits failed."""
+        return self.metrics(thresholds=thresholds, want_mask=want_mask)
 
     # ---- what only a sequence has ---------------------------------------------------------------------------------
     def _not_for_images(self, *a, **k):

@@ -272,6 +272,32 @@ class SMALFitter(nn.Module):
                             "trans": self.trans[i].cpu().numpy()})
             return out
 
+    def metrics(self, batch_range=None, thresholds=(0.15,), want_mask=False):
+        """How good the fit is at the current parameters, for the frames of batch_range (None: all of them), at most a window
+        per library call: the hard render against sil_imgs and the projected keypoints against target_joints
+        (Engine.fit_metrics; smalify_amd.metrics.summarise turns the counts into IoU and PCK).  No counterpart in the reference,
+        which has no evaluation code.  -> dict of device tensors with one row per frame: sil_counts (n,4), keypoint_dist
+        (n,25), pck_counts (n,1+T), mask (n,S,S) if asked for."""
+        frames = list(range(self.num_images)) if batch_range is None else list(batch_range)
+        parts = []
+        with torch.no_grad():
+            for j in range(0, len(frames), self.batch_size):
+                idx = frames[j:j + self.batch_size]
+                theta = torch.cat([(self.global_rotation[idx] * self.global_mask).unsqueeze(1),
+                                   self.joint_rotations[idx] * self.rotation_mask], dim=1)
+                ls = self.log_beta_scales
+                ls = ls.expand(len(idx), 6) if ls.dim() == 1 else ls[idx]
+                verts, joints, _, _ = self.smal_model(self.betas.expand(len(idx), self.n_betas).contiguous(), theta.contiguous(),
+                                                      betas_logscale=ls.contiguous())
+                trans = self.trans[idx].unsqueeze(1)
+                verts = (verts + trans).contiguous().float()
+                proj = self.renderer._project((joints + trans)[:, config.CANONICAL_MODEL_JOINTS].contiguous().float())
+                sil = self.sil_imgs[idx].reshape(len(idx), self.image_size, self.image_size).contiguous()
+                parts.append(self._engine(len(idx)).fit_metrics(
+                    verts, sil, proj, self.target_joints[idx].contiguous(), self.target_visibility[idx].float().contiguous(),
+                    thresholds=thresholds, want_mask=want_mask))
+        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
     @staticmethod
     def _draw_joints(images, landmarks, visible=None):
         """Marks keypoints on (B,3,S,S) images in [0,1]: landmarks (B,25,2) as (row, col).  Stands in for the reference's
