@@ -297,26 +297,8 @@ __global__ __launch_bounds__(256) void mesh3d_sample_kernel(MeshTargetsDev t, in
 }
 
 // ---- Adam on all trained parameters of a Stage.step in one launch ----------------------------------------------------
-// torch.optim.Adam (adam_update) over the trained parameters, one launch; a segment's gradient may be a column block of a
-// wider row-major buffer (global_rot / joint_rot are columns 0..2 / 3..104 of d theta [N][105])
-struct Fit3dAdamSeg {
-  float* p;
-  const float* g;
-  float* m;
-  float* v;
-  int count, row_len, g_stride, g_offset;
-  float step_size;   // lr / (1 - beta1^t)
-  int block0;        // first block of this segment
-};
-
-constexpr int kFit3dParams = 5;   // betas, global_rot, joint_rot, trans, deform_verts
-
-struct Fit3dAdamArgs {
-  Fit3dAdamSeg seg[kFit3dParams];
-  int nseg;
-  float b1, b2, eps, bc2_sqrt;
-};
-
+// torch.optim.Adam (adam_update) over the trained parameters, one launch (Fit3dAdamArgs: smalfit_plan.h, beside plan_fit3d, which
+// sizes its segments)
 __global__ __launch_bounds__(256) void fit3d_adam_kernel(Fit3dAdamArgs a) {
   int s = 0;
   while (s + 1 < a.nseg && (int)blockIdx.x >= a.seg[s + 1].block0) ++s;

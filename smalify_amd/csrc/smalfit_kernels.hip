@@ -10,10 +10,12 @@
 //
 // One translation unit: this file holds the shared device helpers and includes the kernels by subsystem
 // (kernels_lbs_forward.inc, kernels_raster.inc, kernels_color.inc, kernels_lbs_backward.inc, kernels_mesh3d.inc), then
-// the host side (smalfit_launch.inc, smalfit_mesh3d.inc: pointer plumbing, launches, C entry points).  What the host DECIDES
-// before it launches -- loop, fold, routes, an evaluation's plan, kernel forms, grids, refused arguments -- is smalfit_plan.h:
-// plain C++ that the CPU tests compile and call (tests/host_plan_shim.cpp).  The constants a launch is sized by and a kernel decodes
-// its block roles by (kSweepFaces, kResEdge, kAsmElem, PBM_SPLITS, ...) are defined there, once, and read by both sides.
+// the host side (smalfit_launch.inc, smalfit_mesh3d.inc: pointer plumbing, allocations, copies, launches, C entry points).  What
+// the host DECIDES before it launches -- loop, fold, routes, the plan of an evaluation and of a fit3d step, kernel forms, grids,
+// refused arguments -- is smalfit_plan.h, and what it COMPUTES before it uploads -- a model's tables, a mesh's topology -- is
+// smal_model_pack.h and mesh3d_topology.h: plain C++ that the CPU tests compile and call (tests/host_plan_shim.cpp,
+// tests/host_mesh3d_shim.cpp).  The constants a launch is sized by and a kernel decodes its block roles by (kSweepFaces, kResEdge,
+// kAsmElem, PBM_SPLITS, ...) are defined in smalfit_plan.h, once, and read by both sides.
 //
 // Kernel -> reference map (file:line into /root/reference):
 //   lbs_head_kernel     pose blocks: batch_lbs.py:33-52 (Rodrigues), :105-129 (limb scales), :131-168 (chain, A);

@@ -1,7 +1,8 @@
 // Host side of libsmalfit.so: model upload, workspace carving, kernel sequencing, C-ABI.
 // Included at the end of smalfit_kernels.hip (same translation unit as the kernels).  Every choice between launches (plan_eval
 // for an evaluation), every grid that depends on the problem's size and every refusal of an argument is a function of
-// smalfit_plan.h; here are the pointers and the launches.  (Errors of the runtime -- allocations, copies, launches -- are worded here.)
+// smalfit_plan.h, and the tables of a model are built by smal_model_pack.h; here are the pointers, the allocations, the copies and
+// the launches.  (Errors of the runtime -- allocations, copies, launches -- are worded here.)
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -10,6 +11,7 @@
 
 #include "../../include/smalfit.h"
 #include "smalfit_plan.h"
+#include "smal_model_pack.h"
 
 namespace smalfit {
 
@@ -41,20 +43,35 @@ static int refused(const char* who, const char* why) { return why ? fail(std::st
     if (_e != hipSuccess) return fail(std::string("launch ") + what + ": " + hipGetErrorString(_e)); \
   } while (0)
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// one device allocation holding `b` -> its base, or nullptr with the runtime's error worded under the entry point's name
+static unsigned char* upload_blob(const Blob& b, const char* who) {
+  void* dev = nullptr;
+  if (hipMalloc(&dev, b.bytes.size()) != hipSuccess) { fail(std::string(who) + ": hipMalloc failed (no HIP device?)"); return nullptr; }
+  if (hipMemcpy(dev, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(dev);
+    fail(std::string(who) + ": hipMemcpy failed");
+    return nullptr;
+  }
+  return (unsigned char*)dev;
+}
 
-// host-side staging buffer that later becomes one device allocation
-struct Blob {
-  std::vector<unsigned char> bytes;
-  size_t add(const void* src, size_t n) {
-    const size_t off = align_up(bytes.size(), 256);
-    bytes.resize(off + n);
-    if (src) std::memcpy(bytes.data() + off, src, n);
-    return off;
+// a workspace of many buffers in one device allocation: list the fields (each starts at a multiple of 256 bytes), allocate
+// `bytes` (the end of the last field) or more, point() the fields into the slab
+struct Carver {
+  struct Item { void** ptr; size_t off; };
+  std::vector<Item> items;
+  size_t bytes = 0;
+  template <class T>
+  void field(T*& ptr, size_t count) {
+    const size_t off = align_up(bytes, 256);
+    items.push_back({(void**)&ptr, off});
+    bytes = off + count * sizeof(T);
+  }
+  void point(void* slab) const {
+    for (const Item& it : items) *it.ptr = (unsigned char*)slab + it.off;
   }
 };
 
-static const int kDefaultLandmarks[6] = {1863, 26, 2124, 150, 3055, 1097};            // smal_torch.py:176-184
 static const int kCanonical[25] = {10, 9, 8, 20, 19, 18, 14, 13, 12, 24, 23, 22, 25,   // config.py:77-88
                                    31, 33, 34, 35, 36, 38, 37, 39, 40, 15, 15, 28};
 
@@ -190,150 +207,33 @@ const char* smalfit_last_error(void) { return g_err.c_str(); }
 // ------------------------------------------------------------------------------------------------
 int smalfit_model_create(const smalfit_model_desc* d, smalfit_model** out) {
   if (refused("smalfit_model_create", null_argument_refusal(d && out))) return 1;
-  const int V = d->num_verts, F = d->num_faces, NB = d->num_betas;
-  if (refused("smalfit_model_create", model_dims_refusal(V, F, NB))) return 1;
-  if (!parents_ordered(d->parents, 35)) return refused("smalfit_model_create", "parents must satisfy 0 <= parents[i] < i");
-  for (int i = 0; i < F * 3; ++i)
-    if (d->faces[i] < 0 || d->faces[i] >= V) return refused("smalfit_model_create", "face index out of range");
-  const int* lms = kDefaultLandmarks;
-  for (int i = 0; i < 6; ++i)
-    if (lms[i] >= V) return refused("smalfit_model_create", "model has fewer vertices than the SMAL landmark ids");
-  const int Vp = padded_verts(V);
+  if (refused("smalfit_model_create", model_dims_refusal(d->num_verts, d->num_faces, d->num_betas))) return 1;
+  if (refused("smalfit_model_create", model_desc_refusal(d, kDefaultLandmarks, 6))) return 1;
+  const ModelPackHost p = pack_smal_model(d);
   Blob b;
-  // planar bases
-  std::vector<float> vt((size_t)3 * Vp, 0.f), sd((size_t)NB * 3 * Vp, 0.f), pd((size_t)306 * 3 * Vp, 0.f);
-  for (int v = 0; v < V; ++v)
-    for (int a = 0; a < 3; ++a) vt[(size_t)a * Vp + v] = d->v_template[v * 3 + a];
-  for (int k = 0; k < NB; ++k)
-    for (int v = 0; v < V; ++v)
-      for (int a = 0; a < 3; ++a) sd[((size_t)k * 3 + a) * Vp + v] = d->shapedirs[(size_t)k * 3 * V + 3 * v + a];
-  for (int k = 0; k < 306; ++k)
-    for (int v = 0; v < V; ++v)
-      for (int a = 0; a < 3; ++a) pd[((size_t)k * 3 + a) * Vp + v] = d->posedirs[(size_t)k * 3 * V + 3 * v + a];
-  // sparse forms of weights and regressor
-  auto build = [&](const float* dense, int& K, std::vector<int>& ell_j, std::vector<float>& ell_v,
-                   std::vector<int>& off, std::vector<int>& cv, std::vector<float>& cval) {
-    K = 1;
-    for (int v = 0; v < V; ++v) {
-      int c = 0;
-      for (int j = 0; j < 35; ++j) c += dense[v * 35 + j] != 0.f;
-      K = std::max(K, c);
-    }
-    ell_j.assign((size_t)K * Vp, 0);
-    ell_v.assign((size_t)K * Vp, 0.f);
-    for (int v = 0; v < V; ++v) {
-      int c = 0;
-      for (int j = 0; j < 35; ++j)
-        if (dense[v * 35 + j] != 0.f) { ell_j[(size_t)c * Vp + v] = j; ell_v[(size_t)c * Vp + v] = dense[v * 35 + j]; ++c; }
-    }
-    off.assign(36, 0);
-    cv.clear(); cval.clear();
-    for (int j = 0; j < 35; ++j) {
-      for (int v = 0; v < V; ++v)
-        if (dense[v * 35 + j] != 0.f) { cv.push_back(v); cval.push_back(dense[v * 35 + j]); }
-      off[j + 1] = (int)cv.size();
-    }
-    if (cv.empty()) { cv.push_back(0); cval.push_back(0.f); }
-  };
-  int Kw, Kj;
-  std::vector<int> w_j, wc_off, wc_v, jrv_j, jr_off, jr_v;
-  std::vector<float> w_val, wc_val, jrv_val, jr_val;
-  build(d->weights, Kw, w_j, w_val, wc_off, wc_v, wc_val);
-  build(d->J_regressor, Kj, jrv_j, jrv_val, jr_off, jr_v, jr_val);
-  // rest joints as an affine function of beta (float64 accumulation)
-  std::vector<double> Jt64(105, 0.0), JS64((size_t)105 * NB, 0.0);
-  for (int j = 0; j < 35; ++j)
-    for (int i = jr_off[j]; i < jr_off[j + 1]; ++i) {
-      const int v = jr_v[i];
-      const double c = jr_val[i];
-      for (int a = 0; a < 3; ++a) {
-        Jt64[j * 3 + a] += c * d->v_template[v * 3 + a];
-        for (int k = 0; k < NB; ++k) JS64[(size_t)(j * 3 + a) * NB + k] += c * d->shapedirs[(size_t)k * 3 * V + 3 * v + a];
-      }
-    }
-  std::vector<float> Jt(105), JS((size_t)105 * NB);
-  for (int i = 0; i < 105; ++i) Jt[i] = (float)Jt64[i];
-  for (size_t i = 0; i < JS.size(); ++i) JS[i] = (float)JS64[i];
-  // internal face order: Morton order of the template's face centroids, so that consecutive faces are
-  // neighbours on the surface (hence on screen, in any pose) -- the rasteriser's sweep blocks rely on it.
-  // Face ids never leave the library (gradients are gathered per vertex), so the order is free to choose.
-  std::vector<int> faces_int((size_t)F * 3);
-  {
-    float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
-    std::vector<float> cen((size_t)F * 3);
-    for (int f = 0; f < F; ++f)
-      for (int a = 0; a < 3; ++a) {
-        const float c = (d->v_template[d->faces[f * 3] * 3 + a] + d->v_template[d->faces[f * 3 + 1] * 3 + a] +
-                         d->v_template[d->faces[f * 3 + 2] * 3 + a]) / 3.0f;
-        cen[(size_t)f * 3 + a] = c;
-        lo[a] = std::min(lo[a], c); hi[a] = std::max(hi[a], c);
-      }
-    std::vector<std::pair<unsigned long long, int>> keyed(F);
-    for (int f = 0; f < F; ++f) {
-      unsigned long long code = 0;
-      for (int a = 0; a < 3; ++a) {
-        const float span = hi[a] - lo[a];
-        const unsigned q = span > 0.f ? (unsigned)std::min(1023.0f, (cen[(size_t)f * 3 + a] - lo[a]) / span * 1023.0f) : 0u;
-        for (int bit = 0; bit < 10; ++bit) code |= (unsigned long long)((q >> bit) & 1u) << (3 * bit + a);
-      }
-      keyed[f] = {code, f};
-    }
-    std::stable_sort(keyed.begin(), keyed.end());
-    for (int f = 0; f < F; ++f)
-      for (int k = 0; k < 3; ++k) faces_int[(size_t)f * 3 + k] = d->faces[keyed[f].second * 3 + k];
-  }
-  // vertex -> (face, corner) adjacency (internal face ids).  vf_idx ends with one zero entry past the 3 F corners: vertex_bwd_kernel's
-  // clamped unconditional loads read vf_idx[vf_off[V]] when the last vertices have no incident face
-  std::vector<int> vf_off(V + 1, 0), vf_idx((size_t)F * 3 + 1, 0);
-  for (int i = 0; i < F * 3; ++i) vf_off[faces_int[i] + 1]++;
-  for (int v = 0; v < V; ++v) vf_off[v + 1] += vf_off[v];
-  {
-    std::vector<int> cur(vf_off.begin(), vf_off.end() - 1);
-    for (int i = 0; i < F * 3; ++i) vf_idx[cur[faces_int[i]]++] = i;
-  }
-  // limb-scale index per (joint, axis)   (batch_lbs.py:107-121)
-  std::vector<int> sidx(105, -1);
-  auto set = [&](int j, int a, int c) { sidx[j * 3 + a] = c; };
-  for (int j = 7; j < 25; ++j) {
-    if (j == 15 || j == 16) continue;
-    set(j, 2, 0); set(j, 0, 1); set(j, 1, 1);
-  }
-  for (int j = 25; j < 32; ++j) { set(j, 0, 2); set(j, 1, 3); set(j, 2, 3); }
-  for (int j = 33; j < 35; ++j) { set(j, 1, 4); set(j, 2, 5); }
-
-  const size_t o_vt = b.add(vt.data(), vt.size() * 4), o_sd = b.add(sd.data(), sd.size() * 4);
-  const size_t o_pd = b.add(pd.data(), pd.size() * 4);
-  const size_t o_wj = b.add(w_j.data(), w_j.size() * 4), o_wv = b.add(w_val.data(), w_val.size() * 4);
-  const size_t o_wco = b.add(wc_off.data(), 36 * 4), o_wcv = b.add(wc_v.data(), wc_v.size() * 4);
-  const size_t o_wcl = b.add(wc_val.data(), wc_val.size() * 4);
-  const size_t o_jro = b.add(jr_off.data(), 36 * 4), o_jrv = b.add(jr_v.data(), jr_v.size() * 4);
-  const size_t o_jrl = b.add(jr_val.data(), jr_val.size() * 4);
-  const size_t o_jvj = b.add(jrv_j.data(), jrv_j.size() * 4), o_jvv = b.add(jrv_val.data(), jrv_val.size() * 4);
-  const size_t o_jt = b.add(Jt.data(), 105 * 4), o_js = b.add(JS.data(), JS.size() * 4);
-  const size_t o_par = b.add(d->parents, 35 * 4), o_f = b.add(faces_int.data(), (size_t)F * 3 * 4);
-  const size_t o_vfo = b.add(vf_off.data(), vf_off.size() * 4), o_vfi = b.add(vf_idx.data(), vf_idx.size() * 4);
-  const size_t o_si = b.add(sidx.data(), 105 * 4);
-
+  size_t off[kModelTables];
+  const auto tables = model_tables(p, d->parents);
+  for (int i = 0; i < kModelTables; ++i) off[i] = b.add(tables[i].data, tables[i].bytes);
+  unsigned char* base = upload_blob(b, "smalfit_model_create");
+  if (!base) return 1;
   smalfit_model* m = new smalfit_model();
-  if (hipMalloc(&m->blob, b.bytes.size()) != hipSuccess) { delete m; return fail("smalfit_model_create: hipMalloc failed (no HIP device?)"); }
-  if (hipMemcpy(m->blob, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(m->blob); delete m; return fail("smalfit_model_create: hipMemcpy failed");
-  }
-  unsigned char* base = (unsigned char*)m->blob;
+  m->blob = base;
   ModelDev& g = m->dev;
-  g.V = V; g.Vp = Vp; g.F = F; g.NBall = NB;
-  g.vt = (const float*)(base + o_vt); g.sd = (const float*)(base + o_sd); g.pd = (const float*)(base + o_pd);
-  g.Kw = Kw; g.w_j = (const int*)(base + o_wj); g.w_val = (const float*)(base + o_wv);
-  g.wc_off = (const int*)(base + o_wco); g.wc_v = (const int*)(base + o_wcv); g.wc_val = (const float*)(base + o_wcl);
-  g.jr_off = (const int*)(base + o_jro); g.jr_v = (const int*)(base + o_jrv); g.jr_val = (const float*)(base + o_jrl);
-  g.Kj = Kj; g.jrv_j = (const int*)(base + o_jvj); g.jrv_val = (const float*)(base + o_jvv);
-  g.Jt = (const float*)(base + o_jt); g.JS = (const float*)(base + o_js);
-  g.parents = (const int*)(base + o_par); g.faces = (const int*)(base + o_f);
-  g.vf_off = (const int*)(base + o_vfo); g.vf_idx = (const int*)(base + o_vfi);
-  g.scale_idx = (const int*)(base + o_si);
-  for (int i = 0; i < 6; ++i) g.landmarks[i] = lms[i];
+  auto floats = [&](ModelTable t) { return (const float*)(base + off[t]); };
+  auto ints = [&](ModelTable t) { return (const int*)(base + off[t]); };
+  g.V = p.V; g.Vp = p.Vp; g.F = p.F; g.NBall = p.NB;
+  g.vt = floats(kT_vt); g.sd = floats(kT_sd); g.pd = floats(kT_pd);
+  g.Kw = p.Kw; g.w_j = ints(kT_w_j); g.w_val = floats(kT_w_val);
+  g.wc_off = ints(kT_wc_off); g.wc_v = ints(kT_wc_v); g.wc_val = floats(kT_wc_val);
+  g.jr_off = ints(kT_jr_off); g.jr_v = ints(kT_jr_v); g.jr_val = floats(kT_jr_val);
+  g.Kj = p.Kj; g.jrv_j = ints(kT_jrv_j); g.jrv_val = floats(kT_jrv_val);
+  g.Jt = floats(kT_Jt); g.JS = floats(kT_JS);
+  g.parents = ints(kT_parents); g.faces = ints(kT_faces);
+  g.vf_off = ints(kT_vf_off); g.vf_idx = ints(kT_vf_idx);
+  g.scale_idx = ints(kT_sidx);
+  for (int i = 0; i < 6; ++i) g.landmarks[i] = kDefaultLandmarks[i];
   g.tree = tree_levels(d->parents);
-  m->V = V; m->Vp = Vp; m->F = F; m->NBall = NB;
+  m->V = p.V; m->Vp = p.Vp; m->F = p.F; m->NBall = p.NB;
   *out = m;
   return 0;
 }
@@ -360,85 +260,81 @@ int smalfit_engine_create(smalfit_model* model, int max_frames, int image_size, 
   e->nvt = vertex_blocks(model->Vp);
   e->nblk_beta = nblk_beta(model->Vp);
   const size_t M = max_frames, Vp = model->Vp, F = model->F, S = image_size, T = e->T;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-  struct Item { void** ptr; size_t off; };
-  std::vector<Item> items;
-#define CARVE(field, count, type) items.push_back({(void**)&e->field, carve((size_t)(count) * sizeof(type))})
-  CARVE(theta, M * 105, float);
-  CARVE(v_shaped, M * 3 * Vp, float);
-  CARVE(Jrest, M * 105, float);
-  CARVE(Rm, M * 315, float);
-  CARVE(Gm, M * 420, float);
-  CARVE(scm, M * 105, float);
-  CARVE(Am, M * 420, float);
-  CARVE(pfT, (size_t)308 * e->Mp, float);
-  CARVE(vposed, M * 3 * Vp, float);
-  CARVE(verts, M * 3 * Vp, float);
-  CARVE(proj, M * 3 * Vp, float);
-  CARVE(joints, M * 123, float);
-  CARVE(fbox, M * F, int2);
-  CARVE(frec, M * F * kRecVecs, float4);
-  CARVE(brect, M * rect_count(model->F), int4);
-  CARVE(plist, M * F * kListCap, unsigned char);
-  CARVE(pcount, M * F, unsigned char);
-  CARVE(gacc, M * S * S, unsigned long long);
-  CARVE(bcnt, M * S * S, unsigned);
-  CARVE(zband, M * S * S, float2);
-  CARVE(qcount, kQCountInts, int);
-  CARVE(frect, M * 4, int);
-  CARVE(queue, M * S * S, int);
-  CARVE(bqueue, M * S * S, int);
-  CARVE(qloss, kQueueLossBlocks, long long);
-  CARVE(status, 8, int);
-  CARVE(gz, M * S * S, float2);
-  CARVE(silbuf, M * S * S, float);
-  CARVE(tile_loss, M * (size_t)e->nrb, float);
-  CARVE(dface, M * F * 6, float);
-  CARVE(dJ41, M * 123, float);
-  CARVE(dvert, M * 3 * Vp, float);
-  CARVE(dvp, M * 3 * Vp, float);
-  CARVE(dext, M * 3 * Vp, float);
-  CARVE(dA, M * 420, float);
-  CARVE(dpf_part, (size_t)e->CS * M * 308, float);
-  CARVE(dbeta_part, dbeta_rows(max_frames) * e->nblk_beta * model->NBall, float);
-  CARVE(dtheta, M * 105, float);
-  CARVE(dls, M * 6, float);
-  CARVE(dJrest, M * 105, float);
-  CARVE(dbetaJ, M * (size_t)model->NBall, float);
-  CARVE(dth_direct, M * 105, float);
-  CARVE(dtr_direct, M * 3, float);
-  CARVE(dtr_part, (size_t)e->nvt * M * 3, float);
-  CARVE(loss_part, M * 8, float);
-  CARVE(loss_betas, 4, float);
-  CARVE(lpart, 64, float);
-  CARVE(qpart, 64, long long);
-  CARVE(zc, M, float);
-  CARVE(asm_counter, 4, int);
-  CARVE(shstate, 2 * kSharedSlotFloats, float);
-  CARVE(step_counter, 4, int);
-  CARVE(gb_prior, 64, float);
-  CARVE(gls_prior, 16, float);
-  CARVE(loss_betas_pf, M, float);
-  CARVE(gb_prior_pf, M * 32, float);
-  CARVE(gls_prior_pf, M * 8, float);
-  CARVE(frame_qloss, M * kFrameLossStride, unsigned long long);
-  CARVE(win_gb, M * kWindowRowBetas, float);      // (a window holds at least one frame: at most M rows)
-  CARVE(win_gls, M * kWindowRowScales, float);
-  CARVE(ones, 128, float);
-  CARVE(zeros, M * 128, float);
-  CARVE(canon, 32, int);
-  CARVE(pose_prec, 105 * 105, float);
-  CARVE(pose_mean, 105, float);
-  CARVE(pose_mask, 105, float);
-  CARVE(lim_min, 102, float);
-  CARVE(lim_max, 102, float);
-  CARVE(shape_prec, 41 * 41, float);
-  CARVE(shape_mean, 41, float);
-#undef CARVE
-  if (hipMalloc(&e->slab, off) != hipSuccess) { delete e; return fail("smalfit_engine_create: hipMalloc of workspace failed"); }
-  for (auto& it : items) *it.ptr = (unsigned char*)e->slab + it.off;
-  if (hipMemset(e->slab, 0, off) != hipSuccess) { (void)hipFree(e->slab); delete e; return fail("smalfit_engine_create: hipMemset failed"); }
+  Carver w;
+  w.field(e->theta, M * 105);
+  w.field(e->v_shaped, M * 3 * Vp);
+  w.field(e->Jrest, M * 105);
+  w.field(e->Rm, M * 315);
+  w.field(e->Gm, M * 420);
+  w.field(e->scm, M * 105);
+  w.field(e->Am, M * 420);
+  w.field(e->pfT, (size_t)308 * e->Mp);
+  w.field(e->vposed, M * 3 * Vp);
+  w.field(e->verts, M * 3 * Vp);
+  w.field(e->proj, M * 3 * Vp);
+  w.field(e->joints, M * 123);
+  w.field(e->fbox, M * F);
+  w.field(e->frec, M * F * kRecVecs);
+  w.field(e->brect, M * rect_count(model->F));
+  w.field(e->plist, M * F * kListCap);
+  w.field(e->pcount, M * F);
+  w.field(e->gacc, M * S * S);
+  w.field(e->bcnt, M * S * S);
+  w.field(e->zband, M * S * S);
+  w.field(e->qcount, kQCountInts);
+  w.field(e->frect, M * 4);
+  w.field(e->queue, M * S * S);
+  w.field(e->bqueue, M * S * S);
+  w.field(e->qloss, kQueueLossBlocks);
+  w.field(e->status, 8);
+  w.field(e->gz, M * S * S);
+  w.field(e->silbuf, M * S * S);
+  w.field(e->tile_loss, M * (size_t)e->nrb);
+  w.field(e->dface, M * F * 6);
+  w.field(e->dJ41, M * 123);
+  w.field(e->dvert, M * 3 * Vp);
+  w.field(e->dvp, M * 3 * Vp);
+  w.field(e->dext, M * 3 * Vp);
+  w.field(e->dA, M * 420);
+  w.field(e->dpf_part, (size_t)e->CS * M * 308);
+  w.field(e->dbeta_part, dbeta_rows(max_frames) * e->nblk_beta * model->NBall);
+  w.field(e->dtheta, M * 105);
+  w.field(e->dls, M * 6);
+  w.field(e->dJrest, M * 105);
+  w.field(e->dbetaJ, M * (size_t)model->NBall);
+  w.field(e->dth_direct, M * 105);
+  w.field(e->dtr_direct, M * 3);
+  w.field(e->dtr_part, (size_t)e->nvt * M * 3);
+  w.field(e->loss_part, M * 8);
+  w.field(e->loss_betas, 4);
+  w.field(e->lpart, 64);
+  w.field(e->qpart, 64);
+  w.field(e->zc, M);
+  w.field(e->asm_counter, 4);
+  w.field(e->shstate, 2 * kSharedSlotFloats);
+  w.field(e->step_counter, 4);
+  w.field(e->gb_prior, 64);
+  w.field(e->gls_prior, 16);
+  w.field(e->loss_betas_pf, M);
+  w.field(e->gb_prior_pf, M * 32);
+  w.field(e->gls_prior_pf, M * 8);
+  w.field(e->frame_qloss, M * kFrameLossStride);
+  w.field(e->win_gb, M * kWindowRowBetas);      // (a window holds at least one frame: at most M rows)
+  w.field(e->win_gls, M * kWindowRowScales);
+  w.field(e->ones, 128);
+  w.field(e->zeros, M * 128);
+  w.field(e->canon, 32);
+  w.field(e->pose_prec, 105 * 105);
+  w.field(e->pose_mean, 105);
+  w.field(e->pose_mask, 105);
+  w.field(e->lim_min, 102);
+  w.field(e->lim_max, 102);
+  w.field(e->shape_prec, 41 * 41);
+  w.field(e->shape_mean, 41);
+  const size_t slab_bytes = align_up(w.bytes, 256);
+  if (hipMalloc(&e->slab, slab_bytes) != hipSuccess) { delete e; return fail("smalfit_engine_create: hipMalloc of workspace failed"); }
+  w.point(e->slab);
+  if (hipMemset(e->slab, 0, slab_bytes) != hipSuccess) { (void)hipFree(e->slab); delete e; return fail("smalfit_engine_create: hipMemset failed"); }
   if (hipMemsetD32((hipDeviceptr_t)e->zband, 0x7f800000, (size_t)M * S * S * 2) != hipSuccess ||
       hipMalloc(&e->blist, (size_t)M * S * S * kBandCap * sizeof(float2)) != hipSuccess) {
     (void)hipFree(e->slab); delete e; return fail("smalfit_engine_create: allocation of the band lists failed");
@@ -673,6 +569,20 @@ static int run_lbs_backward(smalfit_engine* e, hipStream_t st, int M, int nb, in
                                                     need_ls ? e->dls : nullptr, e->dJrest, need_beta ? e->dbetaJ : nullptr, dRs_out,
                                                     nb, betas_shared, db.bx, db.by, db.bz, e->dvp, e->dbeta_part);
   LAUNCH_OK("chain_bwd_kernel");
+  return 0;
+}
+
+// d/d betas of M frames with their own shapes, nb floats each, from the partials run_lbs_backward (betas_shared 0) left:
+// assemble_kernel with only its per-frame betas roles
+static int launch_frame_betas_assembly(smalfit_engine* e, hipStream_t st, int M, int nb, float* g_betas) {
+  const ModelDev& m = e->model->dev;
+  AssembleArgs g;
+  std::memset(&g, 0, sizeof(g));
+  g.M = M; g.nb = nb; g.NBall = m.NBall; g.nblk_beta = e->nblk_beta; g.betas_shared = 0;
+  g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = 1; g.g_betas = g_betas;
+  g.win = WinMap{1, 0, M};
+  assemble_kernel<false><<<frame_betas_grid(M), 256, 0, st>>>(g, AssembleExt{});
+  LAUNCH_OK("assemble_kernel");
   return 0;
 }
 
@@ -934,15 +844,7 @@ int smalfit_lbs_backward_ex(smalfit_engine* e, void* stream, const smalfit_lbs_a
     if (a->logscale) HIP_OK(hipMemcpyAsync(a->dlogscale, e->dls, (size_t)M * 6 * 4, hipMemcpyDeviceToDevice, st));
     else HIP_OK(hipMemsetAsync(a->dlogscale, 0, (size_t)M * 6 * 4, st));
   }
-  if (a->dbeta) {
-    AssembleArgs g;
-    std::memset(&g, 0, sizeof(g));
-    g.M = M; g.nb = nb; g.NBall = m.NBall; g.nblk_beta = e->nblk_beta; g.betas_shared = 0;
-    g.dbeta_part = e->dbeta_part; g.dJrest = e->dJrest; g.JS = m.JS; g.dbetaJ = e->dbetaJ; g.ngrp_beta = 1; g.g_betas = a->dbeta;
-    g.win = WinMap{1, 0, M};
-    assemble_kernel<false><<<M, 256, 0, st>>>(g, AssembleExt{});   // only the per-frame betas roles
-    LAUNCH_OK("assemble_kernel");
-  }
+  if (a->dbeta && launch_frame_betas_assembly(e, st, M, nb, a->dbeta)) return 1;
   if (a->dv_offset) {
     offset_grad_kernel<<<dim3(elem_blocks(m.V), M), 256, 0, st>>>(m, M, e->dvp, e->dJrest, a->dv_offset);
     LAUNCH_OK("offset_grad_kernel");
@@ -981,7 +883,7 @@ int smalfit_rodrigues(void* stream, int count, const float* theta, float* R) {
 namespace smalfit {
 // the caller's parent table as a kernel argument, checked
 static int pack_parents(const int* parents, Parents35& par, const char* who) {
-  if (!parents_ordered(parents, 35)) return refused(who, "parents must satisfy 0 <= parents[i] < i");
+  if (!parents_ordered(parents, 35)) return refused(who, kParentsRefusal);
   par.p[0] = -1;
   for (int i = 1; i < 35; ++i) par.p[i] = parents[i];
   return 0;

@@ -2,8 +2,11 @@
 // smalfit_fit_run runs, whether an optimiser step can ride in the next head launch and where the shared parameters then
 // travel, which skinning kernel runs, what an evaluation launches and with which switches (plan_eval), the geometry of the
 // launches that depends on the problem's size -- with the constants the kernels decode their block roles by, defined here once --
-// and which arguments are refused.  Plain C++17 over include/smalfit.h and the standard library -- no HIP -- so that the library
-// (smalfit_launch.inc, smalfit_mesh3d.inc) and the CPU tests (tests/host_plan_shim.cpp, compiled by g++) call the same code.
+// which arguments every entry point refuses (the mesh objective's and smalfit_model_create's data checks included), and the shape
+// of a smalfit_fit3d_step (plan_fit3d, with the layout of its Adam launch's argument).  Plain C++17 over include/smalfit.h and the
+// standard library -- no HIP -- so that the library (smalfit_launch.inc, smalfit_mesh3d.inc) and the CPU tests
+// (tests/host_plan_shim.cpp, compiled by g++) call the same code.  Its siblings under the same rule build the host's tables:
+// smal_model_pack.h (a model's), mesh3d_topology.h (a mesh objective's and its targets').
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -261,6 +264,17 @@ inline const char* model_dims_refusal(int num_verts, int num_faces, int num_beta
   if (num_betas > kMaxModelBetas) return "num_betas above 64 is not supported (the rest-joint path of d/d betas reduces 64 shape directions)";
   return nullptr;
 }
+// -> why smalfit_model_create refuses the data of a model whose dimensions model_dims_refusal accepts, or nullptr.  Reads the 35
+// parents and the 3 F face indices; `landmarks`: the vertex ids ModelDev carries (kDefaultLandmarks of smal_model_pack.h)
+constexpr const char* kParentsRefusal = "parents must satisfy 0 <= parents[i] < i";
+inline const char* model_desc_refusal(const smalfit_model_desc* d, const int* landmarks, int num_landmarks) {
+  if (!parents_ordered(d->parents, 35)) return kParentsRefusal;
+  for (int i = 0; i < d->num_faces * 3; ++i)
+    if (d->faces[i] < 0 || d->faces[i] >= d->num_verts) return "face index out of range";
+  for (int i = 0; i < num_landmarks; ++i)
+    if (landmarks[i] >= d->num_verts) return "model has fewer vertices than the SMAL landmark ids";
+  return nullptr;
+}
 // -> why the fitter refuses a model of `model_betas` shape directions (the text behind "smalfit_fit_eval: "), or nullptr
 inline const char* fit_model_refusal(int model_betas) {
   static_assert(kFitBetas == 20, "the message below names the count");
@@ -276,6 +290,149 @@ inline MeshGrids mesh_grids(int S, int V, int P) {
 }
 inline float mesh_weight(float w) { return std::max(w, 0.f); }                                  // negative weights count as 0
 inline int mesh_points(float w_chamfer, int num_points) { return w_chamfer > 0.f ? num_points : 1; }   // chamfer off: a grid of one block's worth, never launched
+// the elementwise launches round the objective, 256 threads each: compose over the N V 3 coordinates, the sampler over the S points
+// of a mesh (x the meshes), Adam over a trained tensor's floats
+inline int mesh_compose_blocks(int N, int V) { return elem_blocks((long long)N * V * 3); }
+inline Grid2 mesh_sample_grid(int S, int N) { return Grid2{elem_blocks(S), N}; }
+constexpr int fit3d_adam_blocks(int count) { return elem_blocks(count); }
+// assemble_kernel with only its per-frame-betas roles (smalfit_lbs_backward_ex, smalfit_fit3d_step): one block per frame
+constexpr int frame_betas_grid(int M) { return M; }
+
+// ------------------------------------------------------------------------------------------------
+// the mesh objective's entry points: which arguments are refused (the text behind "<entry point>: " or nullptr, the first fault;
+// handles and pointers are asked for as null_argument_refusal / null_handle_refusal before these read a capacity)
+// ------------------------------------------------------------------------------------------------
+inline const char* null_handle_refusal(bool given) { return given ? nullptr : "null handle"; }
+inline const char* mesh_objective_create_refusal(bool given, int max_meshes, int max_points) {
+  if (!given) return "null argument";
+  return max_meshes > 0 && max_points > 0 ? nullptr : "max_meshes and max_points must be positive";
+}
+inline const char* mesh_eval_refusal(int num_meshes, int max_meshes, float w_chamfer, bool points, int num_points, int max_points) {
+  if (num_meshes <= 0 || num_meshes > max_meshes) return "num_meshes out of range";
+  if (w_chamfer > 0.f && (!points || num_points <= 0 || num_points > max_points))
+    return "the chamfer term needs 1 <= num_points <= max_points target points";
+  return nullptr;
+}
+// (reads the num_meshes counts of both tables)
+inline const char* mesh_targets_create_refusal(bool given, int num_meshes, const int* vert_counts, const int* face_counts) {
+  if (!given) return "null argument";
+  if (num_meshes <= 0) return "no meshes";
+  for (int n = 0; n < num_meshes; ++n)
+    if (vert_counts[n] <= 0 || face_counts[n] <= 0) return "empty target mesh";
+  return nullptr;
+}
+inline const char* mesh_sample_refusal(bool given, int num_points) {
+  if (!given) return "null argument";
+  return num_points > 0 ? nullptr : "num_points must be positive";
+}
+
+// ------------------------------------------------------------------------------------------------
+// smalfit_fit3d_step: which blocks are refused, and what a step launches
+// ------------------------------------------------------------------------------------------------
+constexpr int kFit3dParams = 5;   // betas, global_rot, joint_rot, trans, deform_verts
+// fit3d_adam_kernel's argument (kernels_mesh3d.inc): torch.optim.Adam over the trained parameters, one launch; a segment's
+// gradient may be a column block of a wider row-major buffer (global_rot / joint_rot are columns 0..2 / 3..104 of d theta [N][105])
+struct Fit3dAdamSeg {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int count, row_len, g_stride, g_offset;
+  float step_size;   // lr / (1 - beta1^t)
+  int block0;        // first block of this segment
+};
+struct Fit3dAdamArgs {
+  Fit3dAdamSeg seg[kFit3dParams];
+  int nseg;
+  float b1, b2, eps, bc2_sqrt;
+};
+
+struct Fit3dFacts {
+  int max_frames, model_verts, model_betas;          // the engine and its model
+  int max_meshes, max_points, objective_verts;       // the objective
+  bool targets;                                      // target meshes were given
+  int target_meshes;                                 // how many (read only with `targets`)
+};
+// -> why smalfit_fit3d_step refuses the block (the text behind "smalfit_fit3d_step: "), or nullptr
+inline const char* fit3d_args_refusal(const smalfit_fit3d_args* a, const Fit3dFacts& f) {
+  const int N = a->num_meshes, nb = a->num_betas, S = a->num_points;
+  if (N <= 0 || N > f.max_frames || N > f.max_meshes) return "num_meshes exceeds the engine's max_frames or the objective's max_meshes";
+  if (f.model_verts != f.objective_verts) return "engine and objective were built for different meshes";
+  if (nb <= 0 || nb > f.model_betas || nb > 64) return "num_betas out of range";
+  if (!a->betas || !a->global_rot || !a->joint_rot || !a->trans || !a->losses) return "missing parameter / losses pointer";
+  if (a->weights[0] > 0.f) {
+    if (S <= 0 || S > f.max_points) return "the chamfer term needs 1 <= num_points <= max_points";
+    if (!a->points && !f.targets) return "neither target points nor target meshes given";
+    if (!a->points && f.target_meshes != N) return "number of target meshes differs from num_meshes";
+  }
+  bool any = false;
+  if (a->lr_betas > 0.f) {
+    if (!a->betas || !a->m_betas || !a->v_betas) return "betas is trained (lr > 0) but its parameter or Adam state is missing";
+    any = true;
+  }
+  if (a->lr_global_rot > 0.f) {
+    if (!a->global_rot || !a->m_global_rot || !a->v_global_rot) return "global_rot is trained (lr > 0) but its parameter or Adam state is missing";
+    any = true;
+  }
+  if (a->lr_joint_rot > 0.f) {
+    if (!a->joint_rot || !a->m_joint_rot || !a->v_joint_rot) return "joint_rot is trained (lr > 0) but its parameter or Adam state is missing";
+    any = true;
+  }
+  if (a->lr_trans > 0.f) {
+    if (!a->trans || !a->m_trans || !a->v_trans) return "trans is trained (lr > 0) but its parameter or Adam state is missing";
+    any = true;
+  }
+  if (a->lr_deform_verts > 0.f) {
+    if (!a->deform_verts || !a->m_deform_verts || !a->v_deform_verts) return "deform_verts is trained (lr > 0) but its parameter or Adam state is missing";
+    any = true;
+  }
+  if (any && a->adam_t <= 0) return "adam_t must be the 1-based step count";
+  return nullptr;
+}
+
+// where the chamfer term's target points come from
+enum class Fit3dPoints {
+  None = 0,            // chamfer off: none are read
+  SampleToObjective,   // sampled from the target meshes into the objective's buffer
+  SampleToCaller,      // ... into points_out
+  Callers,             // the caller's, read in place
+  CallersCopied,       // ... and copied to points_out
+};
+struct Fit3dAdamGeometry { int tensor, count, row_len, g_stride, g_offset, block0; };   // (tensor: index in the order of kFit3dParams)
+struct Fit3dPlan {
+  bool chamfer;
+  Fit3dPoints points;
+  bool need_pose, need_beta;   // the LBS adjoint runs for either; need_beta: with the shape-blend adjoint and the per-frame betas assembly
+  bool planar_vertex_grad;     // the gather kernel leaves a planar copy of d verts where the LBS adjoint reads it
+  bool any_trained;            // else the step ends behind the objective
+  int nseg;                    // trained tensors, in the order of kFit3dParams
+  Fit3dAdamGeometry seg[kFit3dParams];
+  int adam_blocks;             // grid of fit3d_adam_kernel
+};
+// -> the plan of a block that fit3d_args_refusal accepts, on a model of `model_verts` vertices
+inline Fit3dPlan plan_fit3d(const smalfit_fit3d_args* a, int model_verts) {
+  Fit3dPlan p{};
+  const int N = a->num_meshes, nb = a->num_betas, V3 = model_verts * 3;
+  p.chamfer = a->weights[0] > 0.f;
+  if (!p.chamfer) p.points = Fit3dPoints::None;
+  else if (!a->points) p.points = a->points_out ? Fit3dPoints::SampleToCaller : Fit3dPoints::SampleToObjective;
+  else p.points = a->points_out && a->points_out != a->points ? Fit3dPoints::CallersCopied : Fit3dPoints::Callers;
+  p.need_pose = a->lr_global_rot > 0.f || a->lr_joint_rot > 0.f;
+  p.need_beta = a->lr_betas > 0.f;
+  p.planar_vertex_grad = p.need_pose || p.need_beta;
+  const float lr[kFit3dParams] = {a->lr_betas, a->lr_global_rot, a->lr_joint_rot, a->lr_trans, a->lr_deform_verts};
+  const int counts[kFit3dParams] = {N * nb, N * 3, N * 102, N * 3, N * V3};
+  const int row_len[kFit3dParams] = {nb, 3, 102, 3, V3};
+  const int g_stride[kFit3dParams] = {nb, 105, 105, 3, V3};
+  const int g_offset[kFit3dParams] = {0, 0, 3, 0, 0};
+  for (int k = 0; k < kFit3dParams; ++k) {
+    if (!(lr[k] > 0.f)) continue;
+    p.seg[p.nseg++] = Fit3dAdamGeometry{k, counts[k], row_len[k], g_stride[k], g_offset[k], p.adam_blocks};
+    p.adam_blocks += fit3d_adam_blocks(counts[k]);
+  }
+  p.any_trained = p.nseg > 0;
+  return p;
+}
 
 // ------------------------------------------------------------------------------------------------
 // smalfit_fit_args: which blocks are refused

@@ -667,7 +667,6 @@ class MeshTargets:
                                                    ff.ctypes.data, C.byref(h)), "smalfit_mesh_targets_create")
         self.handle = h
         self.device = torch.device("cuda", torch.cuda.current_device())
-        self.joint_limits_owner = None      # whoever set the engine's joint-limit table last (None: no table)
 
     def __len__(self):
         return len(self.verts_list)

@@ -1,22 +1,14 @@
-"""smalfit_plan.h's rules and grids for smalfit_fit_metrics as Python calls: tests/host_metrics_shim.cpp built by g++ the way
-tests/host_plan.py builds its shim, loaded through ctypes.  Nothing here needs a GPU."""
+"""smalfit_plan.h's rules and grids for smalfit_fit_metrics as Python calls: tests/host_metrics_shim.cpp built
+and loaded by tests/host_shim.py.  Nothing here needs a GPU."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_metrics_shim.cpp")
-SO = os.path.join(HERE, "_build", "libhost_metrics_shim.so")
-DEPS = (SRC, os.path.join(HERE, "..", "smalify_amd", "csrc", "smalfit_plan.h"), os.path.join(HERE, "..", "include", "smalfit.h"))
+from tests import host_shim
 
 
 def load():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in DEPS):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", SRC, "-o", SO], check=True)
-    lib = C.CDLL(SO)
+    lib = host_shim.build("host_metrics_shim.cpp", "host_metrics_shim")
     lib.hm_metrics_args_refusal.restype = C.c_char_p
     lib.hm_metrics_args_refusal.argtypes = [C.c_void_p, C.c_int]
     return lib

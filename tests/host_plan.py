@@ -1,20 +1,17 @@
-"""The host's launch decisions (smalify_amd/csrc/smalfit_plan.h) as Python calls: tests/host_plan_shim.cpp built by g++ the way
-tests/test_host_math.py builds its shim, loaded through ctypes, each function returning what the restatements of
+"""The host's launch decisions (smalify_amd/csrc/smalfit_plan.h) and the model packer (smal_model_pack.h) as Python calls:
+tests/host_plan_shim.cpp built and loaded by tests/host_shim.py, each function returning what the restatements of
 tests/fold_forms.py, lbs_forms.py and mesh3d_forms.py return, so that a test compares the two with `==`.  The CPU tests call
 load() from a module fixture; nothing here needs a GPU, and nothing the GPU tests import needs this file."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
+
+import numpy as np
 
 from smalify_amd import _lib
 from tests import fold_forms as ff
+from tests import host_shim
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_plan_shim.cpp")
-SO = os.path.join(HERE, "_build", "libhost_plan_shim.so")
-DEPS = (SRC, os.path.join(HERE, "..", "smalify_amd", "csrc", "smalfit_plan.h"), os.path.join(HERE, "..", "include", "smalfit.h"))
 
 LOOPS = ("graph", "folded", "plain")                                  # RunLoop
 SKIN_FORMS = ("plain", "split", "wide")                               # SkinForm
@@ -35,6 +32,15 @@ EVAL_NAMED = {"head_prior": ("none", "shared", "per_frame"), "head": HEAD_KERNEL
 GRID_CONSTANTS = ("SWEEP_FACES", "BWD_FACES", "BWD_LANES", "RES_EDGE", "RECT_FACES", "ASM_ELEM", "ASM_LOSS", "ASM_ROWS", "BAND_BLOCKS",
                   "SELECT_BLOCKS", "SEL_WAVES", "SEL_GROUPS", "PBM_SPLITS", "PBM_TILES", "FRAME_LOSS_STRIDE", "JOINT_BLOCKS", "SKIN_VERTS",
                   "SKIN_THREADS", "QUEUE_LOSS_BLOCKS")
+# model_tables of smal_model_pack.h: the order of the model's device blob
+MODEL_TABLES = ("vt", "sd", "pd", "w_j", "w_val", "wc_off", "wc_v", "wc_val", "jr_off", "jr_v", "jr_val", "jrv_j", "jrv_val", "Jt", "JS",
+                "parents", "faces_int", "vf_off", "vf_idx", "sidx")
+FIT3D_TENSORS = ("betas", "global_rot", "joint_rot", "trans", "deform_verts")           # the order of kFit3dParams
+FIT3D_POINTS = ("none", "sample_to_objective", "sample_to_caller", "callers", "callers_copied")   # Fit3dPoints
+# Fit3dFacts: an engine of 4 frames on the stand-in's dimensions, an objective over the same mesh, two target meshes
+FIT3D_FACT_NAMES = ("max_frames", "model_verts", "model_betas", "max_meshes", "max_points", "objective_verts", "targets", "target_meshes")
+FIT3D_FACTS = dict(max_frames=4, model_verts=3889, model_betas=41, max_meshes=4, max_points=64, objective_verts=3889, targets=True,
+                   target_meshes=2)
 
 
 class Plan:
@@ -46,8 +52,19 @@ class Plan:
                      "hp_option_refusal", "hp_profile_begin_refusal", "hp_lbs_args_refusal", "hp_lbs_outputs_refusal",
                      "hp_render_frames_refusal", "hp_temporal_frames_refusal", "hp_pose_prior_refusal", "hp_graph_subject_refusal",
                      "hp_shard_subject_refusal", "hp_shard_record_refusal", "hp_shard_reduce_refusal", "hp_shard_run_refusal",
-                     "hp_adam_step_refusal", "hp_window_rows_refusal"):
+                     "hp_adam_step_refusal", "hp_window_rows_refusal", "hp_model_desc_refusal", "hp_null_handle_refusal",
+                     "hp_mesh_objective_create_refusal", "hp_mesh_eval_refusal", "hp_mesh_targets_create_refusal",
+                     "hp_mesh_sample_refusal", "hp_fit3d_args_refusal"):
             getattr(lib, name).restype = C.c_char_p
+        lib.hp_mesh_eval_refusal.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
+        lib.hp_mesh_targets_create_refusal.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        lib.hp_pack_model.restype = C.c_void_p
+        lib.hp_pack_model.argtypes = [C.c_void_p]
+        lib.hp_pack_free.argtypes = [C.c_void_p]
+        lib.hp_pack_dims.argtypes = [C.c_void_p, C.c_void_p]
+        lib.hp_pack_table.restype = lib.hp_pack_blob.restype = C.c_void_p
+        lib.hp_pack_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.hp_pack_blob.argtypes = [C.c_void_p, C.c_void_p]
         lib.hp_elem_blocks.argtypes = [C.c_longlong]
         lib.hp_joint_limits_refusal.argtypes = [C.c_void_p, C.c_void_p]
         out = (C.c_int * len(GRID_CONSTANTS))()
@@ -174,6 +191,77 @@ class Plan:
     def mesh_points(self, w_chamfer, num_points):
         return self.lib.hp_mesh_points(w_chamfer, num_points)
 
+    # ---- smalfit_model_create ----
+    def _desc(self, md):
+        """(smalfit_model_desc of a SMALModelData, the arrays it points into), laid out as engine.DeviceModel lays it out"""
+        keep = [np.ascontiguousarray(np.asarray(getattr(md, k)), dtype=dt)
+                for k, dt in (("v_template", np.float32), ("shapedirs", np.float32), ("posedirs", np.float32), ("J_regressor", np.float32),
+                              ("weights", np.float32), ("parents", np.int32), ("faces", np.int32))]
+        return _lib.ModelDesc(keep[0].shape[0], keep[6].shape[0], keep[1].shape[0], *[a.ctypes.data for a in keep]), keep
+
+    def model_desc_refusal(self, md):
+        desc, keep = self._desc(md)
+        why = self.lib.hp_model_desc_refusal(C.byref(desc))
+        return why.decode() if why else None
+
+    def default_landmarks(self):
+        return self._ints(self.lib.hp_default_landmarks, 6)
+
+    def pack_model(self, md):
+        """pack_smal_model of a SMALModelData -> (dims: V, Vp, F, NB, Kw, Kj; tables by MODEL_TABLES name as uint8 arrays; their
+        offsets in the blob; the blob smalfit_model_create uploads, as bytes)"""
+        desc, keep = self._desc(md)
+        h = self.lib.hp_pack_model(C.addressof(desc))
+        try:
+            assert self.lib.hp_pack_num_tables() == len(MODEL_TABLES)
+            dims = (C.c_int * 6)()
+            self.lib.hp_pack_dims(h, dims)
+            n, off = C.c_ulonglong(), C.c_ulonglong()
+            tables, offsets = {}, {}
+            for i, name in enumerate(MODEL_TABLES):
+                ptr = self.lib.hp_pack_table(h, i, C.byref(n), C.byref(off))
+                tables[name], offsets[name] = C.string_at(ptr, n.value), off.value
+            ptr = self.lib.hp_pack_blob(h, C.byref(n))
+            blob = C.string_at(ptr, n.value)
+        finally:
+            self.lib.hp_pack_free(h)
+        return dict(zip(("V", "Vp", "F", "NB", "Kw", "Kj"), dims)), tables, offsets, blob
+
+    # ---- the mesh objective and smalfit_fit3d_step ----
+    def fit3d_args_refusal(self, args, **facts):
+        f = dict(FIT3D_FACTS, **facts)
+        why = self.lib.hp_fit3d_args_refusal(C.byref(args), (C.c_int * 8)(*[int(f[k]) for k in FIT3D_FACT_NAMES]))
+        return why.decode() if why else None
+
+    def plan_fit3d(self, args, model_verts):
+        """Fit3dPlan as a dict; points by name, seg: a list of dicts (tensor by name)"""
+        ints, segs = (C.c_int * 8)(), (C.c_int * 30)()
+        self.lib.hp_plan_fit3d(C.byref(args), model_verts, ints, segs)
+        out = dict(zip(("chamfer", "points", "need_pose", "need_beta", "planar_vertex_grad", "any_trained", "nseg", "adam_blocks"), ints))
+        for k in ("chamfer", "need_pose", "need_beta", "planar_vertex_grad", "any_trained"):
+            out[k] = bool(out[k])
+        out["points"] = FIT3D_POINTS[out["points"]]
+        out["seg"] = [dict(zip(("tensor", "count", "row_len", "g_stride", "g_offset", "block0"), segs[6 * s:6 * s + 6])) for s in range(out.pop("nseg"))]
+        for sg in out["seg"]:
+            sg["tensor"] = FIT3D_TENSORS[sg["tensor"]]
+        return out
+
+    def fit3d_constants(self):
+        """(kFit3dParams, sizeof Fit3dAdamSeg, sizeof Fit3dAdamArgs, sizeof smalfit_fit3d_args)"""
+        return self._ints(self.lib.hp_fit3d_constants, 4)
+
+    def mesh_compose_blocks(self, N, V):
+        return self.lib.hp_mesh_compose_blocks(N, V)
+
+    def mesh_sample_grid(self, S, N):
+        return self._ints(self.lib.hp_mesh_sample_grid, 2, S, N)
+
+    def fit3d_adam_blocks(self, count):
+        return self.lib.hp_fit3d_adam_blocks(count)
+
+    def frame_betas_grid(self, M):
+        return self.lib.hp_frame_betas_grid(M)
+
     # ---- smalfit_fit_args ----
     def fit_args_refusal(self, args, max_frames, has_pose_prior, shape_dim):
         why = self.lib.hp_fit_args_refusal(C.byref(args), max_frames, int(has_pose_prior), shape_dim)
@@ -262,10 +350,24 @@ class Plan:
 
 
 def load():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in DEPS):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", SRC, "-o", SO], check=True)
-    return Plan(C.CDLL(SO))
+    return Plan(host_shim.build("host_plan_shim.cpp", "host_plan_shim"))
+
+
+def valid_fit3d_args(**fields):
+    """a block smalfit_fit3d_step accepts under FIT3D_FACTS (dummy non-null pointers: nothing dereferences them): two meshes, 20
+    betas, chamfer on with points sampled from the targets, every tensor trained at step 1; with `fields` changed"""
+    a = _lib.Fit3dArgs()
+    a.num_meshes, a.num_betas, a.num_points, a.adam_t = 2, 20, 64, 1
+    a.beta1, a.beta2, a.eps = 0.9, 0.999, 1e-8
+    a.weights = (C.c_float * 4)(1.0, 1.0, 0.01, 0.1)
+    names = [n + t for t in FIT3D_TENSORS for n in ("", "m_", "v_")] + ["losses"]
+    for i, name in enumerate(names):
+        setattr(a, name, 0x1000 * (i + 1))
+    for t in FIT3D_TENSORS:
+        setattr(a, "lr_" + t, 0.01)
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
 
 
 def valid_fit_args(**fields):

@@ -1,9 +1,11 @@
-// TEST-ONLY host build (g++) of the host's launch decisions (smalify_amd/csrc/smalfit_plan.h): extern "C" wrappers over the
-// very functions smalfit_launch.inc and smalfit_mesh3d.inc call, so that the CPU tests compare the Python restatements
-// (tests/fold_forms.py, lbs_forms.py, mesh3d_forms.py) with the rules themselves.  Never part of the product.
+// TEST-ONLY host build (g++) of the host's launch decisions (smalify_amd/csrc/smalfit_plan.h) and of the model packer
+// (smal_model_pack.h): extern "C" wrappers over the very functions smalfit_launch.inc and smalfit_mesh3d.inc call, so that the CPU
+// tests compare the Python restatements (tests/fold_forms.py, lbs_forms.py, mesh3d_forms.py, model_forms.py) with the rules
+// themselves.  Never part of the product.
 #include <cstdint>
 #include <cstring>
 
+#include "../smalify_amd/csrc/smal_model_pack.h"
 #include "../smalify_amd/csrc/smalfit_plan.h"
 
 using namespace smalfit;
@@ -188,5 +190,78 @@ const char* hp_shard_run_refusal(const smalfit_fit_args* a, const smalfit_adam_a
 }
 const char* hp_adam_step_refusal(int count, int given, int t) { return adam_step_refusal(count, given != 0, t); }
 const char* hp_window_rows_refusal(const smalfit_fit_args* a, const smalfit_window_rows* r) { return window_rows_refusal(a, r); }
+
+
+// ---- smalfit_model_create: the data refusals and the packer ----
+const char* hp_model_desc_refusal(const smalfit_model_desc* d) { return model_desc_refusal(d, kDefaultLandmarks, 6); }
+void hp_default_landmarks(int* out6) { for (int i = 0; i < 6; ++i) out6[i] = kDefaultLandmarks[i]; }
+// pack_smal_model and the blob as smalfit_model_create lays it out (the descriptor's arrays must outlive the handle: the parent
+// table is referenced, not copied)
+struct Packed {
+  ModelPackHost p;
+  std::array<TableRef, kModelTables> tables;
+  size_t off[kModelTables];
+  Blob blob;
+};
+void* hp_pack_model(const smalfit_model_desc* d) {
+  Packed* k = new Packed{pack_smal_model(d), {}, {}, {}};
+  k->tables = model_tables(k->p, d->parents);
+  for (int i = 0; i < kModelTables; ++i) k->off[i] = k->blob.add(k->tables[i].data, k->tables[i].bytes);
+  return k;
+}
+void hp_pack_free(void* h) { delete (Packed*)h; }
+int hp_pack_num_tables(void) { return kModelTables; }
+// [V, Vp, F, NB, Kw, Kj]
+void hp_pack_dims(const void* h, int* out6) {
+  const ModelPackHost& p = ((const Packed*)h)->p;
+  const int v[6] = {p.V, p.Vp, p.F, p.NB, p.Kw, p.Kj};
+  for (int i = 0; i < 6; ++i) out6[i] = v[i];
+}
+// table i in the order of model_tables -> its bytes; its offset in the blob
+const void* hp_pack_table(const void* h, int i, unsigned long long* bytes, unsigned long long* offset) {
+  const Packed* k = (const Packed*)h;
+  *bytes = k->tables[i].bytes; *offset = k->off[i];
+  return k->tables[i].data;
+}
+const void* hp_pack_blob(const void* h, unsigned long long* bytes) {
+  const Packed* k = (const Packed*)h;
+  *bytes = k->blob.bytes.size();
+  return k->blob.bytes.data();
+}
+
+// ---- the mesh objective and smalfit_fit3d_step ----
+const char* hp_null_handle_refusal(int given) { return null_handle_refusal(given != 0); }
+const char* hp_mesh_objective_create_refusal(int given, int max_meshes, int max_points) { return mesh_objective_create_refusal(given != 0, max_meshes, max_points); }
+const char* hp_mesh_eval_refusal(int num_meshes, int max_meshes, float w_chamfer, int points, int num_points, int max_points) {
+  return mesh_eval_refusal(num_meshes, max_meshes, w_chamfer, points != 0, num_points, max_points);
+}
+const char* hp_mesh_targets_create_refusal(int given, int num_meshes, const int* vert_counts, const int* face_counts) {
+  return mesh_targets_create_refusal(given != 0, num_meshes, vert_counts, face_counts);
+}
+const char* hp_mesh_sample_refusal(int given, int num_points) { return mesh_sample_refusal(given != 0, num_points); }
+// facts8: max_frames, model_verts, model_betas, max_meshes, max_points, objective_verts, targets given, target meshes
+const char* hp_fit3d_args_refusal(const smalfit_fit3d_args* a, const int* f) {
+  return fit3d_args_refusal(a, Fit3dFacts{f[0], f[1], f[2], f[3], f[4], f[5], f[6] != 0, f[7]});
+}
+// plan_fit3d -> ints8: chamfer, points, need_pose, need_beta, planar_vertex_grad, any_trained, nseg, adam_blocks;
+// segs: nseg x (tensor, count, row_len, g_stride, g_offset, block0)
+void hp_plan_fit3d(const smalfit_fit3d_args* a, int model_verts, int* ints8, int* segs30) {
+  const Fit3dPlan p = plan_fit3d(a, model_verts);
+  const int v[8] = {p.chamfer, (int)p.points, p.need_pose, p.need_beta, p.planar_vertex_grad, p.any_trained, p.nseg, p.adam_blocks};
+  for (int i = 0; i < 8; ++i) ints8[i] = v[i];
+  for (int s = 0; s < p.nseg; ++s) {
+    const Fit3dAdamGeometry& g = p.seg[s];
+    const int w[6] = {g.tensor, g.count, g.row_len, g.g_stride, g.g_offset, g.block0};
+    for (int i = 0; i < 6; ++i) segs30[s * 6 + i] = w[i];
+  }
+}
+// [kFit3dParams, sizeof(Fit3dAdamSeg), sizeof(Fit3dAdamArgs), sizeof(smalfit_fit3d_args)]
+void hp_fit3d_constants(int* out4) {
+  out4[0] = kFit3dParams; out4[1] = (int)sizeof(Fit3dAdamSeg); out4[2] = (int)sizeof(Fit3dAdamArgs); out4[3] = (int)sizeof(smalfit_fit3d_args);
+}
+int hp_mesh_compose_blocks(int N, int V) { return mesh_compose_blocks(N, V); }
+void hp_mesh_sample_grid(int S, int N, int* out2) { const Grid2 g = mesh_sample_grid(S, N); out2[0] = g.x; out2[1] = g.y; }
+int hp_fit3d_adam_blocks(int count) { return fit3d_adam_blocks(count); }
+int hp_frame_betas_grid(int M) { return frame_betas_grid(M); }
 
 }  // extern "C"

@@ -143,7 +143,8 @@ def valence_model(hub_list=HUBS, rings=HUB_RINGS):
 
 def internal_face_order(md):
     """smalfit_model_create's face order (Morton order of the template's face centroids on a 1024^3 grid, ties by face index),
-    restated in float32: the order in which vertex_bwd_kernel meets a vertex's corners"""
+    restated in float32: the order in which vertex_bwd_kernel meets a vertex's corners (tests/test_model_pack_cpu.py holds it to
+    pack_smal_model's faces on every variant)"""
     vt = np.asarray(md.v_template, np.float32)
     f = np.asarray(md.faces)
     cen = ((vt[f[:, 0]] + vt[f[:, 1]]) + vt[f[:, 2]]) / np.float32(3.0)

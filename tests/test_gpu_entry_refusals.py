@@ -1,7 +1,9 @@
 """GPU: the refusals smalfit_plan.h words for the entry points beside smalfit_fit_eval (tests/test_host_plan_cpu.py holds the
 texts and their order on the CPU) reach smalfit_last_error() behind the name of the entry point that met them.  An engine of 2
 frames at 32 x 32 without priors; every call is refused before anything is launched, so the pointers are dummies of the smallest
-valid shapes and a case takes no time."""
+valid shapes and a case takes no time.  The mesh entry points get two objectives of capacity 2 meshes x 8 points: a tetrahedron
+(the create, eval and sample rules, and "different meshes" against the engine) and one over the model's own faces (the rules of
+smalfit_fit3d_step behind that one), with target sets of one and of two tetrahedra."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +16,9 @@ from smalify_amd import _lib, engine as eng  # noqa: E402
 from tests import parity_cases as pc  # noqa: E402
 
 M, S = 2, 32
+POINTS = 8
+TET_V = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)
+TET_F = np.array([[0, 2, 1], [0, 1, 3], [1, 2, 3], [0, 3, 2]], np.int32)
 _CTX = {}
 
 
@@ -23,6 +28,15 @@ def _ctx():
         _CTX["dm"], _CTX["e"] = dm, eng.Engine(dm, M, S)
         _CTX["buf"] = torch.zeros(M * 4096, device="cuda")
         _CTX["lo"], _CTX["hi"] = np.full(102, -1.0, np.float32), np.full(102, 1.0, np.float32)
+        _CTX["tet"] = eng.MeshObjective(4, TET_F, M, POINTS)
+        _CTX["obj"] = eng.MeshObjective(dm.num_verts, np.asarray(dm.data.faces, np.int32), M, POINTS)
+        _CTX["tgt1"], _CTX["tgt2"] = eng.MeshTargets([TET_V], [TET_F]), eng.MeshTargets([TET_V, TET_V], [TET_F, TET_F])
+        # host arrays the mesh cases point at: faces (good, an index out of range, a repeated vertex), counts, vertices, weights
+        far, twice = TET_F.copy(), TET_F.copy()
+        far[2, 1], twice[1, 2] = 4, twice[1, 1]
+        _CTX["host"] = dict(F=TET_F, F_FAR=far, F_TWICE=twice, V=TET_V, V_FLAT=np.zeros_like(TET_V), C4=np.array([4], np.int32),
+                            C0=np.array([0], np.int32), W_ON=np.array([1.0, 1.0, 0.01, 0.1], np.float32),
+                            W_OFF=np.array([0.0, 1.0, 0.01, 0.1], np.float32))
     return _CTX
 
 
@@ -59,6 +73,47 @@ def _shard(D, **fields):
     return sh
 
 
+FIT3D_TENSORS = ("betas", "global_rot", "joint_rot", "trans", "deform_verts")
+
+
+def _fit3d(D, **fields):
+    """a block smalfit_fit3d_step accepts with the model-face objective and two target meshes: every tensor trained at step 1"""
+    a = _lib.Fit3dArgs()
+    a.num_meshes, a.num_betas, a.num_points, a.adam_t = M, 20, POINTS, 1
+    a.beta1, a.beta2, a.eps = 0.9, 0.999, 1e-8
+    a.weights = (C.c_float * 4)(1.0, 1.0, 0.01, 0.1)
+    a.losses = D
+    for t in FIT3D_TENSORS:
+        for prefix in ("", "m_", "v_"):
+            setattr(a, prefix + t, D)
+        setattr(a, "lr_" + t, 0.01)
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def _eval(k, **bent):
+    """arguments of smalfit_mesh_objective_eval the tetrahedron objective accepts, bent"""
+    a = dict(m=k.TET, st=k.ST, N=M, lbs=k.D, trans=k.D, deform=None, points=k.D, S=POINTS, w=k.H["W_ON"], verts=None, losses=k.D, dverts=k.D,
+             dtrans=k.D)
+    a.update(bent)
+    return tuple(a.values())
+
+
+def _targets(k, **bent):
+    a = dict(N=1, vc=k.H["C4"], fc=k.H["C4"], verts=k.H["V"], faces=k.H["F"], out=C.byref(C.c_void_p()))
+    a.update(bent)
+    return tuple(a.values())
+
+
+def _step(k, m=None, t="TGT2", **fields):
+    return (k.E, k.OBJ if m is None else m, getattr(k, t) if t else None, k.ST, C.byref(_fit3d(k.D, **fields)))
+
+
+MESHES_TEXT = "num_meshes exceeds the engine's max_frames or the objective's max_meshes"
+EVAL_POINTS_TEXT = "the chamfer term needs 1 <= num_points <= max_points target points"
+POSITIVE_TEXT = "max_meshes and max_points must be positive"
+TRAINED_TEXT = "%s is trained (lr > 0) but its parameter or Adam state is missing"
 SHARD_TEXT = "subject_frames != 0 cannot be sharded (independent images need no collective: give each rank its own batch)"
 FRAMES_TEXT = "num_frames exceeds the engine's max_frames"
 ONE_OF_TEXT = "give exactly one of theta (axis-angle) and Rs (rotation matrices)"
@@ -131,6 +186,63 @@ CASES = {
                                                         C.byref(_shard(k.D)), 1), "adam_local and adam_shared must carry the same step >= 0"),
     "shard_run subject": ("smalfit_shard_run", lambda k: (k.E, k.ST, C.byref(_fit(subject_frames=1)), C.byref(_adam(k.D)), C.byref(_adam(k.D)),
                                                           C.byref(_shard(k.D)), 1), SHARD_TEXT),
+    # ---- the mesh objective
+    "mesh_objective_create null": ("smalfit_mesh_objective_create", lambda k: (4, 4, None, M, POINTS, C.byref(C.c_void_p())), "null argument"),
+    "mesh_objective_create out": ("smalfit_mesh_objective_create", lambda k: (4, 4, k.H["F"], M, POINTS, None), "null argument"),
+    "mesh_objective_create meshes": ("smalfit_mesh_objective_create", lambda k: (4, 4, k.H["F"], 0, POINTS, C.byref(C.c_void_p())), POSITIVE_TEXT),
+    "mesh_objective_create points": ("smalfit_mesh_objective_create", lambda k: (4, 4, k.H["F"], M, 0, C.byref(C.c_void_p())), POSITIVE_TEXT),
+    "mesh_objective_create null first": ("smalfit_mesh_objective_create", lambda k: (4, 4, None, 0, 0, C.byref(C.c_void_p())), "null argument"),
+    "mesh_objective_create empty": ("smalfit_mesh_objective_create", lambda k: (0, 4, k.H["F"], M, POINTS, C.byref(C.c_void_p())),
+                                    "mesh topology: empty mesh"),
+    "mesh_objective_create index": ("smalfit_mesh_objective_create", lambda k: (4, 4, k.H["F_FAR"], M, POINTS, C.byref(C.c_void_p())),
+                                    "mesh topology: face index out of range"),
+    "mesh_objective_create repeated": ("smalfit_mesh_objective_create", lambda k: (4, 4, k.H["F_TWICE"], M, POINTS, C.byref(C.c_void_p())),
+                                       "mesh topology: degenerate face (repeated vertex)"),
+    "mesh_objective_create capacity first": ("smalfit_mesh_objective_create", lambda k: (4, 4, k.H["F_FAR"], M, 0, C.byref(C.c_void_p())), POSITIVE_TEXT),
+    "mesh_objective_counts": ("smalfit_mesh_objective_counts", lambda k: (None, None, None), "null handle"),
+    "mesh_objective_eval null": ("smalfit_mesh_objective_eval", lambda k: _eval(k, lbs=None), "null argument"),
+    "mesh_objective_eval handle": ("smalfit_mesh_objective_eval", lambda k: _eval(k, m=None), "null argument"),
+    "mesh_objective_eval weights": ("smalfit_mesh_objective_eval", lambda k: _eval(k, w=None), "null argument"),
+    "mesh_objective_eval losses": ("smalfit_mesh_objective_eval", lambda k: _eval(k, losses=None, N=0), "null argument"),
+    "mesh_objective_eval meshes 0": ("smalfit_mesh_objective_eval", lambda k: _eval(k, N=0), "num_meshes out of range"),
+    "mesh_objective_eval meshes": ("smalfit_mesh_objective_eval", lambda k: _eval(k, N=M + 1, S=POINTS + 1), "num_meshes out of range"),
+    "mesh_objective_eval no points": ("smalfit_mesh_objective_eval", lambda k: _eval(k, points=None), EVAL_POINTS_TEXT),
+    "mesh_objective_eval points 0": ("smalfit_mesh_objective_eval", lambda k: _eval(k, S=0), EVAL_POINTS_TEXT),
+    "mesh_objective_eval points": ("smalfit_mesh_objective_eval", lambda k: _eval(k, S=POINTS + 1), EVAL_POINTS_TEXT),
+    "mesh_targets_create null": ("smalfit_mesh_targets_create", lambda k: _targets(k, verts=None), "null argument"),
+    "mesh_targets_create out": ("smalfit_mesh_targets_create", lambda k: _targets(k, out=None, N=0), "null argument"),
+    "mesh_targets_create none": ("smalfit_mesh_targets_create", lambda k: _targets(k, N=0), "no meshes"),
+    "mesh_targets_create empty": ("smalfit_mesh_targets_create", lambda k: _targets(k, vc=k.H["C0"]), "empty target mesh"),
+    "mesh_targets_create faceless": ("smalfit_mesh_targets_create", lambda k: _targets(k, fc=k.H["C0"], faces=k.H["F_FAR"]), "empty target mesh"),
+    "mesh_targets_create index": ("smalfit_mesh_targets_create", lambda k: _targets(k, faces=k.H["F_FAR"]), "target mesh: face index out of range"),
+    "mesh_targets_create flat": ("smalfit_mesh_targets_create", lambda k: _targets(k, verts=k.H["V_FLAT"]), "target mesh: zero surface area"),
+    "mesh_targets_sample null": ("smalfit_mesh_targets_sample", lambda k: (None, k.ST, POINTS, 1, 0, k.D), "null argument"),
+    "mesh_targets_sample out": ("smalfit_mesh_targets_sample", lambda k: (k.TGT2, k.ST, 0, 1, 0, None), "null argument"),
+    "mesh_targets_sample points": ("smalfit_mesh_targets_sample", lambda k: (k.TGT2, k.ST, 0, 1, 0, k.D), "num_points must be positive"),
+    # ---- smalfit_fit3d_step
+    "fit3d_step null": ("smalfit_fit3d_step", lambda k: (k.E, k.OBJ, k.TGT2, k.ST, None), "null argument"),
+    "fit3d_step objective": ("smalfit_fit3d_step", lambda k: (k.E, None, k.TGT2, k.ST, C.byref(_fit3d(k.D))), "null argument"),
+    "fit3d_step meshes 0": ("smalfit_fit3d_step", lambda k: _step(k, num_meshes=0), MESHES_TEXT),
+    "fit3d_step meshes": ("smalfit_fit3d_step", lambda k: _step(k, m=k.TET, num_meshes=M + 1), MESHES_TEXT),
+    "fit3d_step different meshes": ("smalfit_fit3d_step", lambda k: _step(k, m=k.TET), "engine and objective were built for different meshes"),
+    "fit3d_step different meshes first": ("smalfit_fit3d_step", lambda k: _step(k, m=k.TET, num_betas=0, betas=None),
+                                          "engine and objective were built for different meshes"),
+    "fit3d_step betas 0": ("smalfit_fit3d_step", lambda k: _step(k, num_betas=0), "num_betas out of range"),
+    "fit3d_step betas": ("smalfit_fit3d_step", lambda k: _step(k, num_betas=42, trans=None), "num_betas out of range"),
+    "fit3d_step parameter": ("smalfit_fit3d_step", lambda k: _step(k, joint_rot=None, num_points=0), "missing parameter / losses pointer"),
+    "fit3d_step losses": ("smalfit_fit3d_step", lambda k: _step(k, losses=None), "missing parameter / losses pointer"),
+    "fit3d_step points 0": ("smalfit_fit3d_step", lambda k: _step(k, num_points=0), "the chamfer term needs 1 <= num_points <= max_points"),
+    "fit3d_step points": ("smalfit_fit3d_step", lambda k: _step(k, t=None, num_points=POINTS + 1), "the chamfer term needs 1 <= num_points <= max_points"),
+    "fit3d_step no targets": ("smalfit_fit3d_step", lambda k: _step(k, t=None, m_betas=None), "neither target points nor target meshes given"),
+    "fit3d_step target count": ("smalfit_fit3d_step", lambda k: _step(k, t="TGT1", adam_t=0), "number of target meshes differs from num_meshes"),
+    "fit3d_step betas state": ("smalfit_fit3d_step", lambda k: _step(k, m_betas=None, v_trans=None), TRAINED_TEXT % "betas"),
+    "fit3d_step global_rot state": ("smalfit_fit3d_step", lambda k: _step(k, v_global_rot=None, m_joint_rot=None), TRAINED_TEXT % "global_rot"),
+    "fit3d_step joint_rot state": ("smalfit_fit3d_step", lambda k: _step(k, m_joint_rot=None, deform_verts=None), TRAINED_TEXT % "joint_rot"),
+    "fit3d_step trans state": ("smalfit_fit3d_step", lambda k: _step(k, v_trans=None, adam_t=0), TRAINED_TEXT % "trans"),
+    "fit3d_step deform_verts": ("smalfit_fit3d_step", lambda k: _step(k, deform_verts=None), TRAINED_TEXT % "deform_verts"),
+    "fit3d_step deform_verts state": ("smalfit_fit3d_step", lambda k: _step(k, points=k.D, t=None, m_deform_verts=None, adam_t=0),
+                                      TRAINED_TEXT % "deform_verts"),
+    "fit3d_step adam_t": ("smalfit_fit3d_step", lambda k: _step(k, adam_t=0), "adam_t must be the 1-based step count"),
 }
 
 
@@ -139,6 +251,8 @@ class _Handles:
         c = _ctx()
         self.E, self.MODEL, self.ST = c["e"].handle, c["dm"].handle, eng._stream()
         self.D, self.LO, self.HI = c["buf"].data_ptr(), c["lo"].ctypes.data, c["hi"].ctypes.data
+        self.TET, self.OBJ, self.TGT1, self.TGT2 = c["tet"].handle, c["obj"].handle, c["tgt1"].handle, c["tgt2"].handle
+        self.H = {name: a.ctypes.data for name, a in c["host"].items()}
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -6,7 +6,6 @@ Tolerances (float32 engine vs float64 oracle): loss terms 2e-5 relative, d/dvert
 the loop 1e-4 rel-L2 (north_star's bar)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ pytestmark = pytest.mark.gpu
 from oracle import mesh3d_oracle as mo  # noqa: E402
 from oracle import smal_oracle as so  # noqa: E402
 from smalify_amd import engine as eng  # noqa: E402
+from tests import host_shim  # noqa: E402
 from tests import mesh3d_cases as mc  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -82,11 +82,7 @@ def test_objective_rejects_bad_arguments():
 
 
 def test_sampler_matches_host_emulation_and_is_deterministic():
-    src = os.path.join(HERE, "host_mesh3d_shim.cpp")
-    so_path = os.path.join(HERE, "_build", "libhost_mesh3d_shim.so")
-    os.makedirs(os.path.dirname(so_path), exist_ok=True)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", src, "-o", so_path], check=True)
-    shim = C.CDLL(so_path)
+    shim = host_shim.mesh3d()
     md = mc.synthetic.synthetic_model(seed=0, shape_family_id=1)
     tv, tf = mc.target_meshes_from_smal(md, 2, seed=4)
     cube_v = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], np.float32)

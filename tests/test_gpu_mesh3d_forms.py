@@ -13,8 +13,6 @@ Bars (those of tests/test_gpu_fit3d.py): loss terms 2e-5 relative, d/d verts 2e-
 2e-4 max|g| + 1e-7, LBS-level gradients 5e-4 rel-L2, stage-loop loss 1e-4 per iteration and parameters 1e-4, sampler
 1e-6.  The worst value of each is printed at the end of the module."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -26,10 +24,10 @@ from oracle import mesh3d_oracle as mo  # noqa: E402
 from oracle import smal_oracle as so  # noqa: E402
 from smalify_amd import _lib  # noqa: E402
 from smalify_amd import engine as eng  # noqa: E402
+from tests import host_shim  # noqa: E402
 from tests import mesh3d_cases as mc  # noqa: E402
 from tests import mesh3d_forms as mf  # noqa: E402
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 TERMS = ("chamfer", "edge", "normal", "laplacian")
 WORST = {}
 
@@ -160,11 +158,7 @@ def test_negative_weight_equals_zero_weight(name, neg, zero):
 # ---- sampler -----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(HERE, "host_mesh3d_shim.cpp")
-    so_path = os.path.join(HERE, "_build", "libhost_mesh3d_shim.so")
-    os.makedirs(os.path.dirname(so_path), exist_ok=True)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", src, "-o", so_path], check=True)
-    return C.CDLL(so_path)
+    return host_shim.mesh3d()
 
 
 def sampler_meshes():

@@ -3,8 +3,6 @@ g++, test-only shim) against the oracle: Rodrigues fwd/bwd, camera fwd/bwd, the 
 silhouette evaluation incl. the K-nearest depth threshold, on the full-size synthetic mesh, and Adam."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,19 +11,12 @@ import torch
 from oracle import raster_naive as rn
 from oracle import smal_oracle as so
 from smalify_amd import model_io
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_math_shim.cpp")
-SO = os.path.join(HERE, "_build", "libhost_math_shim.so")
+from tests import host_shim
 
 
 @pytest.fixture(scope="module")
 def shim():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    hdr = os.path.join(HERE, "..", "smalify_amd", "csrc", "smalfit_math.h")
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(hdr)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", SRC, "-o", SO], check=True)
-    return C.CDLL(SO)
+    return host_shim.build("host_math_shim.cpp", "host_math_shim")
 
 
 def _p(a):

@@ -458,3 +458,195 @@ def test_window_rows_refusals(plan):
     assert plan.refusal("window_rows", valid_fit_args(logscale_mode=2), rows()) == "smalfit_window_rows.g_log_beta_scales needs shared log_beta_scales (logscale_mode 1)"
     assert plan.refusal("window_rows", valid_fit_args(logscale_mode=2), rows(g_log_beta_scales=None)) is None
     assert [plan.window_rows_count(2, off, 4) for off in (0, 1, 2, 3)] == [2, 3, 2, 3] and plan.window_rows_count(8, 3, 1) == 1
+
+
+# ------------------------------------------------------------------------------------------------
+# the mesh objective's entry points and smalfit_fit3d_step
+# ------------------------------------------------------------------------------------------------
+def test_mesh_entry_refusals(plan):
+    positive = "max_meshes and max_points must be positive"
+    _table(plan, "mesh_objective_create", (1, 1, 1), (((0, 1, 1), "null argument"), ((1, 0, 1), positive), ((1, 1, 0), positive),
+                                                      ((1, -1, 8), positive), ((0, 0, 0), "null argument")))
+    assert plan.refusal("null_handle", 1) is None and plan.refusal("null_handle", 0) == "null handle"
+    meshes, points = "num_meshes out of range", "the chamfer term needs 1 <= num_points <= max_points target points"
+    # (num_meshes, max_meshes, w_chamfer, points given, num_points, max_points)
+    _table(plan, "mesh_eval", (2, 2, 1.0, 1, 8, 8), (((0, 2, 1.0, 1, 8, 8), meshes), ((3, 2, 1.0, 1, 8, 8), meshes), ((-1, 2, 0.0, 0, 0, 8), meshes),
+                                                     ((2, 2, 1.0, 0, 8, 8), points), ((2, 2, 1.0, 1, 0, 8), points), ((2, 2, 1.0, 1, 9, 8), points),
+                                                     ((2, 2, 0.5, 1, -1, 8), points), ((3, 2, 1.0, 0, 0, 8), meshes)))
+    for w in (0.0, -1.0):                                       # chamfer off: the points are not looked at
+        assert plan.refusal("mesh_eval", 1, 2, w, 0, 0, 8) is None and plan.refusal("mesh_eval", 1, 2, w, 1, 9, 8) is None
+    assert plan.refusal("mesh_eval", 1, 2, 1.0, 1, 1, 8) is None
+
+    def counts(*values):
+        return (C.c_int * len(values))(*values) if values else None      # (the array itself: it must outlive the call)
+    good = (1, 2, counts(4, 3), counts(4, 1))
+    _table(plan, "mesh_targets_create", good, (((0, 2, counts(4, 3), counts(4, 1)), "null argument"), ((1, 0, counts(4), counts(4)), "no meshes"),
+                                               ((1, -1, counts(4), counts(4)), "no meshes"), ((1, 2, counts(4, 0), counts(4, 1)), "empty target mesh"),
+                                               ((1, 2, counts(4, 3), counts(0, 1)), "empty target mesh"), ((1, 2, counts(-1, 3), counts(4, 1)), "empty target mesh"),
+                                               ((0, 0, None, None), "null argument"), ((1, 0, counts(0), counts(0)), "no meshes")))
+    _table(plan, "mesh_sample", (1, 1), (((0, 1), "null argument"), ((1, 0), "num_points must be positive"), ((1, -5), "num_points must be positive"),
+                                         ((0, 0), "null argument")))
+
+
+FIT3D_TRAINED = "%s is trained (lr > 0) but its parameter or Adam state is missing"
+# (fields bent on the accepted block, facts bent, the refusal), in the order the host checks them
+FIT3D_REFUSALS = (
+    (dict(num_meshes=0), {}, "num_meshes exceeds the engine's max_frames or the objective's max_meshes"),
+    (dict(num_meshes=3), dict(max_frames=2), "num_meshes exceeds the engine's max_frames or the objective's max_meshes"),
+    (dict(num_meshes=3), dict(max_meshes=2, target_meshes=3), "num_meshes exceeds the engine's max_frames or the objective's max_meshes"),
+    ({}, dict(objective_verts=4), "engine and objective were built for different meshes"),
+    (dict(num_betas=0), {}, "num_betas out of range"),
+    (dict(num_betas=42), {}, "num_betas out of range"),
+    (dict(num_betas=65), dict(model_betas=80), "num_betas out of range"),
+    (dict(betas=None), {}, "missing parameter / losses pointer"),
+    (dict(global_rot=None), {}, "missing parameter / losses pointer"),
+    (dict(joint_rot=None), {}, "missing parameter / losses pointer"),
+    (dict(trans=None), {}, "missing parameter / losses pointer"),
+    (dict(losses=None), {}, "missing parameter / losses pointer"),
+    (dict(num_points=0), {}, "the chamfer term needs 1 <= num_points <= max_points"),
+    (dict(num_points=65), {}, "the chamfer term needs 1 <= num_points <= max_points"),
+    ({}, dict(targets=False), "neither target points nor target meshes given"),
+    ({}, dict(target_meshes=3), "number of target meshes differs from num_meshes"),
+    (dict(m_betas=None), {}, "betas is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(v_betas=None), {}, "betas is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(m_global_rot=None), {}, "global_rot is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(v_global_rot=None), {}, "global_rot is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(m_joint_rot=None), {}, "joint_rot is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(v_joint_rot=None), {}, "joint_rot is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(m_trans=None), {}, "trans is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(v_trans=None), {}, "trans is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(deform_verts=None), {}, "deform_verts is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(m_deform_verts=None), {}, "deform_verts is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(v_deform_verts=None), {}, "deform_verts is trained (lr > 0) but its parameter or Adam state is missing"),
+    (dict(adam_t=0), {}, "adam_t must be the 1-based step count"),
+    (dict(adam_t=-1), {}, "adam_t must be the 1-based step count"),
+)
+
+
+def test_fit3d_refusals_whole_and_in_order(plan):
+    assert plan.fit3d_args_refusal(host_plan.valid_fit3d_args()) is None
+    for name in host_plan.FIT3D_TENSORS:
+        assert FIT3D_TRAINED % name in [msg for _, _, msg in FIT3D_REFUSALS]
+    order = list(dict.fromkeys(msg for _, _, msg in FIT3D_REFUSALS))
+    for i, (fields, facts, msg) in enumerate(FIT3D_REFUSALS):
+        assert plan.fit3d_args_refusal(host_plan.valid_fit3d_args(**fields), **facts) == msg, (fields, facts)
+        # two faults at once: the one that comes first in the host's order
+        for later, later_facts, other in FIT3D_REFUSALS[i + 1:]:
+            if order.index(other) > order.index(msg) and not set(later) & set(fields) and not set(later_facts) & set(facts):
+                got = plan.fit3d_args_refusal(host_plan.valid_fit3d_args(**dict(later, **fields)), **dict(later_facts, **facts))
+                assert got == msg, (fields, facts, later, later_facts)
+
+
+def test_fit3d_accepts_what_the_rules_leave_open(plan):
+    ok = lambda facts=None, **fields: plan.fit3d_args_refusal(host_plan.valid_fit3d_args(**fields), **(facts or {})) is None  # noqa: E731
+    assert ok(dict(max_frames=2, max_meshes=2), num_meshes=2) and ok(num_points=64) and ok(num_points=1)
+    assert ok(num_betas=41) and ok(dict(model_betas=80), num_betas=64) and ok(num_betas=1)
+    # chamfer off: neither the points nor the targets are looked at
+    off = (C.c_float * 4)(0.0, 1.0, 0.01, 0.1)
+    assert ok(dict(targets=False), weights=off, num_points=0) and ok(dict(target_meshes=7), weights=off, num_points=1000)
+    # the caller's points: no targets needed, and their number is not compared
+    assert ok(dict(targets=False), points=0x777000) and ok(dict(target_meshes=3), points=0x777000)
+    # a frozen tensor needs no state, deform_verts not even the parameter; nothing trained: no step count
+    for name in host_plan.FIT3D_TENSORS:
+        assert ok(**{"lr_" + name: 0.0, "m_" + name: None, "v_" + name: None})
+        assert ok(**{"lr_" + name: -1.0, "m_" + name: None})
+    assert ok(lr_deform_verts=0.0, deform_verts=None)
+    assert ok(adam_t=0, **{"lr_" + name: 0.0 for name in host_plan.FIT3D_TENSORS})
+    assert not ok(adam_t=0, lr_betas=0.0)
+
+
+V_STANDIN = 3889
+# fitter_3d's schemes (SMALParamGroup.param_map without log_beta_scales, which no scheme trains through the step) and the step
+# that trains nothing
+SCHEMES = {"init": ("global_rot", "trans"), "default": ("betas", "global_rot", "joint_rot", "trans"), "shape": ("betas", "global_rot", "trans"),
+           "pose": ("global_rot", "joint_rot", "trans"), "deform": ("deform_verts",), "none": ()}
+
+
+def _seg(tensor, count, row_len, g_stride, g_offset, block0):
+    return dict(tensor=tensor, count=count, row_len=row_len, g_stride=g_stride, g_offset=g_offset, block0=block0)
+
+
+# 3 meshes, 20 betas, the stand-in's 3889 vertices: (need_pose, need_beta, segments, blocks of the Adam launch)
+PLANS_N3 = {
+    "init": (True, False, [_seg("global_rot", 9, 3, 105, 0, 0), _seg("trans", 9, 3, 3, 0, 1)], 2),
+    "default": (True, True, [_seg("betas", 60, 20, 20, 0, 0), _seg("global_rot", 9, 3, 105, 0, 1), _seg("joint_rot", 306, 102, 105, 3, 2),
+                             _seg("trans", 9, 3, 3, 0, 4)], 5),
+    "shape": (True, True, [_seg("betas", 60, 20, 20, 0, 0), _seg("global_rot", 9, 3, 105, 0, 1), _seg("trans", 9, 3, 3, 0, 2)], 3),
+    "pose": (True, False, [_seg("global_rot", 9, 3, 105, 0, 0), _seg("joint_rot", 306, 102, 105, 3, 1), _seg("trans", 9, 3, 3, 0, 3)], 4),
+    "deform": (False, False, [_seg("deform_verts", 35001, 11667, 11667, 0, 0)], 137),
+    "none": (False, False, [], 0),
+}
+# the other sizes: per tensor (count, row_len, g_stride, g_offset, blocks)
+GEOMETRY = {
+    (1, 20): dict(betas=(20, 20, 20, 0, 1), global_rot=(3, 3, 105, 0, 1), joint_rot=(102, 102, 105, 3, 1), trans=(3, 3, 3, 0, 1),
+                  deform_verts=(11667, 11667, 11667, 0, 46)),
+    (1, 41): dict(betas=(41, 41, 41, 0, 1), global_rot=(3, 3, 105, 0, 1), joint_rot=(102, 102, 105, 3, 1), trans=(3, 3, 3, 0, 1),
+                  deform_verts=(11667, 11667, 11667, 0, 46)),
+    (3, 20): dict(betas=(60, 20, 20, 0, 1), global_rot=(9, 3, 105, 0, 1), joint_rot=(306, 102, 105, 3, 2), trans=(9, 3, 3, 0, 1),
+                  deform_verts=(35001, 11667, 11667, 0, 137)),
+    (3, 41): dict(betas=(123, 41, 41, 0, 1), global_rot=(9, 3, 105, 0, 1), joint_rot=(306, 102, 105, 3, 2), trans=(9, 3, 3, 0, 1),
+                  deform_verts=(35001, 11667, 11667, 0, 137)),
+}
+POINTS = (  # (chamfer on, the caller's points, points_out) -> Fit3dPlan::points
+    ((True, None, None), "sample_to_objective"), ((True, None, 0x888000), "sample_to_caller"), ((True, 0x777000, None), "callers"),
+    ((True, 0x777000, 0x888000), "callers_copied"), ((True, 0x777000, 0x777000), "callers"),
+    ((False, None, None), "none"), ((False, 0x777000, 0x888000), "none"), ((False, None, 0x888000), "none"),
+)
+
+
+def _scheme_args(scheme, **fields):
+    lrs = {"lr_" + t: (0.01 if t in SCHEMES[scheme] else 0.0) for t in host_plan.FIT3D_TENSORS}
+    return host_plan.valid_fit3d_args(**dict(lrs, **fields))
+
+
+@pytest.mark.parametrize("scheme", list(SCHEMES))
+def test_plan_fit3d_of_every_scheme(plan, scheme):
+    need_pose, need_beta, seg, blocks = PLANS_N3[scheme]
+    for (chamfer, points, points_out), where in POINTS:
+        w = (C.c_float * 4)(1.0 if chamfer else 0.0, 1.0, 0.01, 0.1)
+        a = _scheme_args(scheme, num_meshes=3, weights=w, points=points, points_out=points_out)
+        assert plan.fit3d_args_refusal(a, target_meshes=3) is None
+        assert plan.plan_fit3d(a, V_STANDIN) == dict(chamfer=chamfer, points=where, need_pose=need_pose, need_beta=need_beta,
+                                                     planar_vertex_grad=need_pose or need_beta, any_trained=bool(seg), seg=seg,
+                                                     adam_blocks=blocks)
+
+
+@pytest.mark.parametrize("N,nb", list(GEOMETRY))
+@pytest.mark.parametrize("scheme", list(SCHEMES))
+def test_plan_fit3d_adam_geometry(plan, scheme, N, nb):
+    got = plan.plan_fit3d(_scheme_args(scheme, num_meshes=N, num_betas=nb), V_STANDIN)
+    want, block0 = [], 0
+    for t in host_plan.FIT3D_TENSORS:
+        if t in SCHEMES[scheme]:
+            count, row_len, g_stride, g_offset, blocks = GEOMETRY[(N, nb)][t]
+            want.append(_seg(t, count, row_len, g_stride, g_offset, block0))
+            block0 += blocks
+    assert got["seg"] == want and got["adam_blocks"] == block0
+    if (N, nb) == (3, 20):
+        assert want == PLANS_N3[scheme][2]
+
+
+def test_plan_fit3d_negative_and_nan_rates_train_nothing(plan):
+    a = _scheme_args("none", lr_betas=-0.5, lr_trans=float("nan"))
+    got = plan.plan_fit3d(a, V_STANDIN)
+    assert not got["any_trained"] and got["seg"] == [] and got["adam_blocks"] == 0 and not got["need_beta"]
+
+
+def test_fit3d_adam_argument_layout(plan):
+    """the kernel argument moved to smalfit_plan.h whole: four pointers, six 4-byte fields per segment; five segments and five
+    4-byte fields, padded to the pointers' alignment"""
+    params, seg, args, block = plan.fit3d_constants()
+    assert params == len(host_plan.FIT3D_TENSORS) == 5
+    assert seg == 4 * 8 + 6 * 4 == 56 and args == 5 * 56 + 5 * 4 + 4 == 304
+    assert block == C.sizeof(_lib.Fit3dArgs)
+
+
+def test_mesh_launch_grids_on_both_sides_of_256(plan):
+    # compose: N V 3 coordinates, one thread each
+    assert [plan.mesh_compose_blocks(1, v) for v in (1, 85, 86, 170, 171)] == [1, 1, 2, 2, 3]      # 3, 255, 258, 510, 513
+    assert plan.mesh_compose_blocks(2, 128) == 3 and plan.mesh_compose_blocks(256, 1) == 3 and plan.mesh_compose_blocks(3, V_STANDIN) == 137
+    assert plan.mesh_compose_blocks(1024, 1 << 20) == 1024 * (1 << 20) * 3 // 256                  # past 2^31 coordinates
+    # the sampler: S points x N meshes
+    assert [plan.mesh_sample_grid(s, 3) for s in (1, 255, 256, 257, 512, 513, 3000)] == [(1, 3), (1, 3), (1, 3), (2, 3), (2, 3), (3, 3), (12, 3)]
+    assert [plan.fit3d_adam_blocks(c) for c in (1, 255, 256, 257, 511, 512, 513)] == [1, 1, 1, 2, 2, 2, 3]
+    assert [plan.frame_betas_grid(m) for m in (1, 3, 256, 257)] == [1, 3, 256, 257]

@@ -8,7 +8,6 @@
 3. the sampler: Philox known answers, area-proportional face frequencies, determinism."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,21 +15,15 @@ import torch
 
 from oracle import mesh3d_oracle as mo
 from smalify_amd import synthetic
+from tests import host_shim
 from tests import mesh3d_cases as mc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_mesh3d_shim.cpp")
-SO = os.path.join(HERE, "_build", "libhost_mesh3d_shim.so")
-CSRC = os.path.join(HERE, "..", "smalify_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def shim():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("mesh3d_math.h", "mesh3d_topology.h", "smalfit_math.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", SRC, "-o", SO], check=True)
-    return C.CDLL(SO)
+    return host_shim.mesh3d()
 
 
 def _p(a):

@@ -6,20 +6,18 @@ import ctypes as C
 import itertools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import mesh3d_oracle as mo
 from tests import host_plan
+from tests import host_shim
 from tests import mesh3d_cases as mc
 from tests import mesh3d_forms as mf
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "smalify_amd", "csrc")
-SHIM_SRC = os.path.join(HERE, "host_mesh3d_shim.cpp")
-SHIM_SO = os.path.join(HERE, "_build", "libhost_mesh3d_shim.so")
 
 
 def _src(name):
@@ -29,12 +27,7 @@ def _src(name):
 
 @pytest.fixture(scope="module")
 def shim():
-    os.makedirs(os.path.dirname(SHIM_SO), exist_ok=True)
-    deps = [SHIM_SRC] + [os.path.join(CSRC, f) for f in ("mesh3d_math.h", "mesh3d_topology.h", "smalfit_math.h")]
-    if not os.path.exists(SHIM_SO) or os.path.getmtime(SHIM_SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", SHIM_SRC, "-o", SHIM_SO],
-                       check=True)
-    return C.CDLL(SHIM_SO)
+    return host_shim.mesh3d()
 
 
 def _p(a):

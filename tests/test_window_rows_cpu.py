@@ -12,13 +12,11 @@ import torch
 from oracle import smal_oracle as so
 from smalify_amd import _lib
 from smalify_amd.smal_fitter.epoch import StateKey, WindowPartition
+from tests import host_shim
 from tests.host_plan import valid_fit_args
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_DIR = os.path.join(HERE, "..", "include")
-SRC = os.path.join(HERE, "window_rows_shim.cpp")
-SO = os.path.join(HERE, "_build", "libwindow_rows_shim.so")
-DEPS = (SRC, os.path.join(HERE, "..", "smalify_amd", "csrc", "smalfit_plan.h"), os.path.join(HEADER_DIR, "smalfit.h"))
 
 SIZE_TEXT = "smalfit_window_rows.struct_size does not match this library (built against another smalfit.h?)"
 LOSSES_TEXT = "smalfit_window_rows.losses missing"
@@ -29,10 +27,7 @@ SCALES_TEXT = "smalfit_window_rows.g_log_beta_scales needs shared log_beta_scale
 
 @pytest.fixture(scope="module")
 def shim():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in DEPS):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", SRC, "-o", SO], check=True)
-    lib = C.CDLL(SO)
+    lib = host_shim.build("window_rows_shim.cpp", "window_rows_shim")
     lib.wr_refusal.restype = C.c_char_p
     lib.wr_window_rows_size_refusal.restype = C.c_char_p
     return lib
