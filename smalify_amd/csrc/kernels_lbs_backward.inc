@@ -304,6 +304,54 @@ lbs_bwd_mid_kernel(ModelDev m, int M, int nPB, const float* __restrict__ dvert, 
   PHASE_MARK(pd1); PHASE_END(PH_MID_DA, pd0, pd1);
 }
 
+// The chain adjoint's work on joint i with parent p, lane e of the joint's 12, in two steps with a wave barrier between them
+// (step 1 reads the dR' / dj of all the joint's lanes).  Both tree walks of chain_bwd_kernel call it; the LDS arrays are the kernel's.
+struct ChainLds {
+  const float (*R)[9], (*G)[12], (*sc)[3], (*isc)[3], (*J)[3], (*dG)[12];
+  float (*dR)[9], (*cG)[12], (*cJ)[3], (*cS)[3], (*sOwn)[3], (*dRp)[9], (*djv)[3];
+};
+template <int kStep>
+__device__ __forceinline__ void chain_joint_adjoint(const ChainLds& s, int i, int p, int e) {
+  const auto R = s.R; const auto G = s.G; const auto sc = s.sc; const auto isc = s.isc; const auto J = s.J; const auto dG = s.dG;
+  const auto dRp = s.dRp; const auto djv = s.djv;
+  if constexpr (kStep == 0) {
+    // dR' = G_p.R^T dG_i.R ; dj = G_p.R^T dG_i.t
+    if (e < 9) {
+      const int a = e / 3, b = e % 3;
+      dRp[i][e] = G[p][0 * 4 + a] * dG[i][0 * 4 + b] + G[p][1 * 4 + a] * dG[i][1 * 4 + b] + G[p][2 * 4 + a] * dG[i][2 * 4 + b];
+    } else {
+      const int a = e - 9;
+      djv[i][a] = G[p][0 * 4 + a] * dG[i][3] + G[p][1 * 4 + a] * dG[i][7] + G[p][2 * 4 + a] * dG[i][11];
+    }
+  } else if (e < 9) {
+    const int a = e / 3, c = e % 3;
+    // owed to dG_p.R[a][c]: sum_b dG_i.R[a][b] R'[c][b] + dG_i.t[a] (J_i - J_p)[c]
+    float acc = dG[i][a * 4 + 3] * (J[i][c] - J[p][c]);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) acc = fmaf(dG[i][a * 4 + b], R[i][c * 3 + b] * sc[i][b] * isc[p][c], acc);
+    s.cG[i][a * 4 + c] = acc;
+    // dR_i[a][c] += dR'[a][c] s_i[c] / s_p[a]
+    s.dR[i][a * 3 + c] += dRp[i][a * 3 + c] * sc[i][c] * isc[p][a];
+  } else {
+    const int a = e - 9;
+    s.cG[i][a * 4 + 3] = dG[i][a * 4 + 3];
+    s.cJ[i][a] = djv[i][a];                          // dJ_i += dj, dJ_p -= dj (applied after the walk)
+    {                                                // ds_i[b] += sum_a dR'[a][b] R_i[a][b] / s_p[a]   (b = a here)
+      const int b = a;
+      float acc = 0.f;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) acc = fmaf(dRp[i][r * 3 + b], R[i][r * 3 + b] * isc[p][r], acc);
+      s.sOwn[i][b] = acc;
+    }
+    {                                                // ds_p[a] -= sum_b dR'[a][b] R'[a][b] / s_p[a]
+      float acc = 0.f;
+#pragma unroll
+      for (int b = 0; b < 3; ++b) acc = fmaf(dRp[i][a * 3 + b], R[i][a * 3 + b] * sc[i][b] * isc[p][a], acc);
+      s.cS[i][a] = acc * isc[p][a];
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K10: per-frame chain adjoint: dA, dpf -> d theta, d logscale, d rest joints
 // ------------------------------------------------------------------------------------------------
@@ -448,14 +496,16 @@ chain_bwd_kernel(ModelDev m, int M, const float* __restrict__ theta, const float
   __syncthreads();
   PHASE_MARK(pc2);                      // dG / dJ set up
   const int slot = l / 12, e = l % 12;
+  const ChainLds cl{R, G, sc, isc, J, dG, dR, cG, cJ, cS, sOwn, dRp, djv};
   if (l < 64 && tl.fast) {
     // Round 6: the lane's joint, parent and children of a pass are ONE 8-byte read (TreeLevels::pass_*, packed into t_sch below),
     // requested a pass ahead -- inside a pass the level offsets -> joint -> parent -> child list chase cost more than the
     // arithmetic (19 k cycles of the block's 42 k for 12 passes, profiles/r6_lbs_phase_breakdown.txt).  Passes run deepest level
     // first; the loop stays rolled (straight-line code run once by one wave pays an instruction-cache miss per line: the unrolled
-    // form was slower than the table-driven loop).  The operations and their order are meant to be those of the loop below; no test
-    // compares the two walks' bits (a tree takes one or the other) -- each is held to the float64 oracle on trees that reach it, this one
-    // with kTreeMaxChildren children per joint and kTreeMaxPass passes too (tests/test_gpu_model_forms.py).
+    // form was slower than the table-driven loop).  Both walks do a joint's work in chain_joint_adjoint; theirs are the schedule, the
+    // gather of the children's cG and the fences.  No test compares the two walks' bits (a tree takes one or the other) -- each is
+    // held to the float64 oracle on trees that reach it, this one with kTreeMaxChildren children per joint and kTreeMaxPass passes
+    // too (tests/test_gpu_model_forms.py).
     const int npass = tl.npass;
     const int slot_c = min(slot, 7);
     uint2 sch_n = t_sch[max(npass - 1, 0)][slot_c];
@@ -478,45 +528,10 @@ chain_bwd_kernel(ModelDev m, int M, const float* __restrict__ theta, const float
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      // dR' = G_p.R^T dG_i.R ; dj = G_p.R^T dG_i.t
-      if (live) {
-        if (e < 9) {
-          const int a = e / 3, b = e % 3;
-          dRp[i][e] = G[p][0 * 4 + a] * dG[i][0 * 4 + b] + G[p][1 * 4 + a] * dG[i][1 * 4 + b] + G[p][2 * 4 + a] * dG[i][2 * 4 + b];
-        } else {
-          const int a = e - 9;
-          djv[i][a] = G[p][0 * 4 + a] * dG[i][3] + G[p][1 * 4 + a] * dG[i][7] + G[p][2 * 4 + a] * dG[i][11];
-        }
-      }
+      if (live) chain_joint_adjoint<0>(cl, i, p, e);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (live) {
-        if (e < 9) {
-          const int a = e / 3, c = e % 3;
-          float acc = dG[i][a * 4 + 3] * (J[i][c] - J[p][c]);
-#pragma unroll
-          for (int b = 0; b < 3; ++b) acc = fmaf(dG[i][a * 4 + b], R[i][c * 3 + b] * sc[i][b] * isc[p][c], acc);
-          cG[i][a * 4 + c] = acc;
-          dR[i][a * 3 + c] += dRp[i][a * 3 + c] * sc[i][c] * isc[p][a];
-        } else {
-          const int a = e - 9;
-          cG[i][a * 4 + 3] = dG[i][a * 4 + 3];
-          cJ[i][a] = djv[i][a];
-          {
-            const int b = a;
-            float acc = 0.f;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) acc = fmaf(dRp[i][r * 3 + b], R[i][r * 3 + b] * isc[p][r], acc);
-            sOwn[i][b] = acc;
-          }
-          {
-            float acc = 0.f;
-#pragma unroll
-            for (int b = 0; b < 3; ++b) acc = fmaf(dRp[i][a * 3 + b], R[i][a * 3 + b] * sc[i][b] * isc[p][a], acc);
-            cS[i][a] = acc * isc[p][a];
-          }
-        }
-      }
+      if (live) chain_joint_adjoint<1>(cl, i, p, e);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
@@ -535,47 +550,10 @@ chain_bwd_kernel(ModelDev m, int M, const float* __restrict__ theta, const float
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       __builtin_amdgcn_wave_barrier();
-      // dR' = G_p.R^T dG_i.R ; dj = G_p.R^T dG_i.t
-      if (live) {
-        if (e < 9) {
-          const int a = e / 3, b = e % 3;
-          dRp[i][e] = G[p][0 * 4 + a] * dG[i][0 * 4 + b] + G[p][1 * 4 + a] * dG[i][1 * 4 + b] + G[p][2 * 4 + a] * dG[i][2 * 4 + b];
-        } else {
-          const int a = e - 9;
-          djv[i][a] = G[p][0 * 4 + a] * dG[i][3] + G[p][1 * 4 + a] * dG[i][7] + G[p][2 * 4 + a] * dG[i][11];
-        }
-      }
+      if (live) chain_joint_adjoint<0>(cl, i, p, e);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       __builtin_amdgcn_wave_barrier();
-      if (live) {
-        if (e < 9) {
-          const int a = e / 3, c = e % 3;
-          // owed to dG_p.R[a][c]: sum_b dG_i.R[a][b] R'[c][b] + dG_i.t[a] (J_i - J_p)[c]
-          float acc = dG[i][a * 4 + 3] * (J[i][c] - J[p][c]);
-#pragma unroll
-          for (int b = 0; b < 3; ++b) acc = fmaf(dG[i][a * 4 + b], R[i][c * 3 + b] * sc[i][b] * isc[p][c], acc);
-          cG[i][a * 4 + c] = acc;
-          // dR_i[a][c] += dR'[a][c] s_i[c] / s_p[a]
-          dR[i][a * 3 + c] += dRp[i][a * 3 + c] * sc[i][c] * isc[p][a];
-        } else {
-          const int a = e - 9;
-          cG[i][a * 4 + 3] = dG[i][a * 4 + 3];
-          cJ[i][a] = djv[i][a];                          // dJ_i += dj, dJ_p -= dj (applied after the walk)
-          {                                              // ds_i[b] += sum_a dR'[a][b] R_i[a][b] / s_p[a]   (b = a here)
-            const int b = a;
-            float acc = 0.f;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) acc = fmaf(dRp[i][r * 3 + b], R[i][r * 3 + b] * isc[p][r], acc);
-            sOwn[i][b] = acc;
-          }
-          {                                              // ds_p[a] -= sum_b dR'[a][b] R'[a][b] / s_p[a]
-            float acc = 0.f;
-#pragma unroll
-            for (int b = 0; b < 3; ++b) acc = fmaf(dRp[i][a * 3 + b], R[i][a * 3 + b] * sc[i][b] * isc[p][a], acc);
-            cS[i][a] = acc * isc[p][a];
-          }
-        }
-      }
+      if (live) chain_joint_adjoint<1>(cl, i, p, e);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
       __builtin_amdgcn_wave_barrier();
     }

@@ -353,9 +353,11 @@ pose_block(const ModelDev& m, const HeadArgs& a, int n, const PendingStep* pend,
     // 16-byte read of the parent's row, three multiply-adds and one write (until then: level offsets -> joint -> parent ->
     // operands, five dependent trips per pass; 8.2 k cycles of the block's 14.5 k, profiles/r6_lbs_phase_breakdown.txt).  The loop
     // stays rolled: one wave running straight-line code once pays an instruction-cache miss per line (the unrolled form of this
-    // walk was slower than the table-driven one).  The operations and their order are meant to be those of the table-driven loop below;
-    // no test compares the two walks' bits (a tree takes one or the other, smalfit_plan.h: tree_levels) -- each is held to the float64
-    // oracle on trees that reach it, this one at exactly kTreeMaxPass passes too (tests/test_gpu_model_forms.py).
+    // walk was slower than the table-driven one).  The two walks share no code: this one forms the factors (a column of S_p^-1 R_i S_i,
+    // or J_i - J_p) a pass ahead and a pass is three multiply-adds on the parent's row, the table-driven loop below forms them in place.
+    // Written out they are the same products folded in the same order, but nothing enforces that and no test compares the two walks'
+    // bits (a tree takes one or the other, smalfit_plan.h: tree_levels) -- each is held to the float64 oracle on trees that reach it,
+    // this one at exactly kTreeMaxPass passes too (tests/test_gpu_model_forms.py).
     const int slot_c = min(l / 12, 7), e = l % 12, r = e >> 2, c = e & 3, cc = min(c, 2);
     const int npass = tl.npass;
     auto fetch = [&](int k, int& ijp, float (&kc)[3]) {
@@ -433,11 +435,52 @@ pose_block(const ModelDev& m, const HeadArgs& a, int n, const PendingStep* pend,
   PHASE_END(PH_HEAD_POSE, ph0, ph4);
 }
 
+// One shape-prior term by one wave: loss = w mean_c(r_c^2) with r = (x - mean) prec, and its gradient 2 w / D (prec r) wrt x
+// (entries 0..19 of x are betas, the rest log scales).  xm is lane's x - mean (lanes >= D: unused), xs / rs two LDS rows of 32 the
+// wave owns.  prec is read through a pointer (global memory or an LDS copy; loops rolled to D), or -- kHeld -- from the lane's
+// column pcol[r] = prec[r][lane] and row prow[c] = prec[lane][c] held in registers (26 entries, loops unrolled and guarded by D).
+// The shared prior of lbs_head_kernel, the step kernel's and the per-image terms of prior_frames_block are all this function,
+// so one image gives the bits a one-frame shared fit gives.
+template <bool kHeld>
+__device__ __forceinline__ void shape_prior_term(float xm, int lane, int D, float* xs, float* rs, const float* prec, const float* pcol,
+                                                 const float* prow, float w, bool use_ls, float* loss, float* gb, float* gls) {
+  if (lane < D) xs[lane] = xm;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  float lv = 0.f;
+  if (lane < D) {
+    float acc = 0.f;
+    if constexpr (kHeld) {
+#pragma unroll
+      for (int r = 0; r < 26; ++r) if (r < D) acc = fmaf(xs[r], pcol[r], acc);
+    } else {
+      for (int r = 0; r < D; ++r) acc = fmaf(xs[r], prec[r * D + lane], acc);
+    }
+    rs[lane] = acc;
+    lv = acc * acc;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  lv = wave_sum(lv);
+  if (lane == 0) *loss = w * lv / (float)D;
+  if (lane < D) {
+    float acc = 0.f;
+    if constexpr (kHeld) {
+#pragma unroll
+      for (int c = 0; c < 26; ++c) if (c < D) acc = fmaf(rs[c], prow[c], acc);
+    } else {
+      for (int c = 0; c < D; ++c) acc = fmaf(rs[c], prec[lane * D + c], acc);
+    }
+    acc *= 2.0f * w / (float)D;
+    if (lane < 20) gb[lane] = acc; else if (use_ls) gls[lane - 20] = acc;
+  }
+}
+
 // Shape prior of independent images: w mean_c(((x_n - mean) prec)_c ^2) with x_n = [betas_n | log scales_n], one term per frame.
 // A block takes kPriorFrames frames, one wave every fourth of them; prec and mean are staged in LDS once per block (2.7 KB; the
-// shared-shape block below reads them from memory once, here that would be once per frame).  Per frame the operations and their
-// order are those of the shared block, so one image gives the bits a one-frame shared fit gives.  Each frame's loss is a plain
-// store; who adds them up (assemble_kernel) does so in a fixed order.
+// shared-shape block below reads them from memory once, here that would be once per frame).  Each frame's term is the shared
+// block's shape_prior_term, so one image gives the bits a one-frame shared fit gives.  Each frame's loss is a plain store; who
+// adds them up (assemble_kernel) does so in a fixed order.
 // Its arguments travel beside HeadArgs (lbs_head_kernel only): the step kernel's argument block stays what it is.
 constexpr int kPriorFrames = 16;
 struct PriorFrames {
@@ -453,28 +496,11 @@ __device__ __forceinline__ void prior_frames_block(const HeadArgs& a, const Prio
   __syncthreads();
   const int n_end = min((pb + 1) * kPriorFrames, a.M);
   for (int n = pb * kPriorFrames + w; n < n_end; n += 4) {       // (n is uniform over the wave)
+    float xm = 0.f;
     if (lane < D)
-      xs[w][lane] = ((lane < 20) ? a.betas[(size_t)n * a.betas_stride + lane] : a.logscale[(size_t)n * a.ls_stride + lane - 20]) - mean[lane];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    float lv = 0.f;
-    if (lane < D) {
-      float acc = 0.f;
-      for (int r = 0; r < D; ++r) acc = fmaf(xs[w][r], prec[r * D + lane], acc);
-      rs[w][lane] = acc;
-      lv = acc * acc;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    lv = wave_sum(lv);
-    if (lane == 0) pf.loss[n] = a.prior_w * lv / (float)D;
-    if (lane < D) {
-      float acc = 0.f;
-      for (int c = 0; c < D; ++c) acc = fmaf(rs[w][c], prec[lane * D + c], acc);
-      acc *= 2.0f * a.prior_w / (float)D;
-      if (lane < 20) pf.gb[(size_t)n * pf.gb_stride + lane] = acc;
-      else if (a.prior_use_ls) pf.gls[(size_t)n * pf.gls_stride + lane - 20] = acc;
-    }
+      xm = ((lane < 20) ? a.betas[(size_t)n * a.betas_stride + lane] : a.logscale[(size_t)n * a.ls_stride + lane - 20]) - mean[lane];
+    shape_prior_term<false>(xm, lane, D, xs[w], rs[w], prec, nullptr, nullptr, a.prior_w, a.prior_use_ls, pf.loss + n,
+                            pf.gb + (size_t)n * pf.gb_stride, pf.gls + (size_t)n * pf.gls_stride);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // the next frame of this wave overwrites xs / rs
     __builtin_amdgcn_wave_barrier();
   }
@@ -525,28 +551,9 @@ head_block(const ModelDev& m, const HeadArgs& a, const PendingStep* pend, HeadSh
     // shape prior, as below with the operands held
     if (a.prior_prec && t < 64) {
       __shared__ float x[32], res[32];
-      if (t < D) x[t] = ((t < 20) ? sh->beta[t] : sh->ls[t - 20]) - pmean;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      float lv = 0.f;
-      if (t < D) {
-        float acc = 0.f;
-#pragma unroll
-        for (int r = 0; r < 26; ++r) if (r < D) acc = fmaf(x[r], pcol[r], acc);
-        res[t] = acc;
-        lv = acc * acc;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      lv = wave_sum(lv);
-      if (t == 0) *a.prior_loss = a.prior_w * lv / (float)D;
-      if (t < D) {
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < 26; ++c) if (c < D) acc = fmaf(res[c], prow[c], acc);
-        acc *= 2.0f * a.prior_w / (float)D;
-        if (t < 20) a.prior_gb[t] = acc; else if (a.prior_use_ls) a.prior_gls[t - 20] = acc;
-      }
+      float xm = 0.f;
+      if (t < D) xm = ((t < 20) ? sh->beta[t] : sh->ls[t - 20]) - pmean;
+      shape_prior_term<true>(xm, t, D, x, res, nullptr, pcol, prow, a.prior_w, a.prior_use_ls, a.prior_loss, a.prior_gb, a.prior_gls);
     }
     return;
   }
@@ -575,26 +582,9 @@ head_block(const ModelDev& m, const HeadArgs& a, const PendingStep* pend, HeadSh
   if (a.prior_prec && threadIdx.x < 64) {
     __shared__ float x[32], res[32];
     const int t = threadIdx.x, D = a.prior_D;
-    if (t < D) x[t] = ((t < 20) ? a.betas[t] : a.logscale[t - 20]) - a.prior_mean[t];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    float lv = 0.f;
-    if (t < D) {
-      float acc = 0.f;
-      for (int r = 0; r < D; ++r) acc = fmaf(x[r], a.prior_prec[r * D + t], acc);
-      res[t] = acc;
-      lv = acc * acc;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    lv = wave_sum(lv);
-    if (t == 0) *a.prior_loss = a.prior_w * lv / (float)D;
-    if (t < D) {
-      float acc = 0.f;
-      for (int c = 0; c < D; ++c) acc = fmaf(res[c], a.prior_prec[t * D + c], acc);
-      acc *= 2.0f * a.prior_w / (float)D;
-      if (t < 20) a.prior_gb[t] = acc; else if (a.prior_use_ls) a.prior_gls[t - 20] = acc;
-    }
+    float xm = 0.f;
+    if (t < D) xm = ((t < 20) ? a.betas[t] : a.logscale[t - 20]) - a.prior_mean[t];
+    shape_prior_term<false>(xm, t, D, x, res, a.prior_prec, nullptr, nullptr, a.prior_w, a.prior_use_ls, a.prior_loss, a.prior_gb, a.prior_gls);
   }
 }
 
@@ -635,12 +625,79 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Round 6, the SPLIT form for evaluations of few frames (a rank of a multi-GPU fit): the K = 306 contraction is split over four
 // waves (in the wide form below a wave owns 16 vertices and walks all 77 k-steps: 231 dependent matrix instructions behind seven
 // batches of operand loads -- 5.9 us of a workgroup's 10.4, and only 64 workgroups at 8 frames: profiles/r6_lbs_phase_breakdown.txt).
+// What the two matrix-core forms request at their top besides the GEMM operands, for a workgroup of kThreads threads: the 16
+// frames' skinning transforms (one contiguous run of A as float4: clamped reads in fetch, zero fill of frames past M in stage)
+// and the first min(Kw, 8) ELL weights of the lane's vertex (clamped: entries past Kw repeat the last and are never used).
+template <int kThreads>
+struct SkinSide {
+  static constexpr int kStage = (16 * 105 + kThreads - 1) / kThreads;    // float4 words of the transforms a thread stages
+  float4 a_stage[kStage];
+  int wj[8], Kw, nvalid;
+  float wv[8];
+  __device__ __forceinline__ void fetch(const ModelDev& m, int M, int n0, int v, const float* __restrict__ Am) {
+    nvalid = min(16, M - n0) * 105;                   // float4 words of A that exist
+    const float4* src = reinterpret_cast<const float4*>(Am + (size_t)n0 * 420);
+#pragma unroll
+    for (int r = 0; r < kStage; ++r) a_stage[r] = src[min((int)threadIdx.x + kThreads * r, nvalid - 1)];
+    Kw = min(m.Kw, 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int ee = max(min(e, Kw - 1), 0);
+      wj[e] = m.w_j[ee * m.Vp + v];
+      wv[e] = m.w_val[ee * m.Vp + v];
+    }
+  }
+  __device__ __forceinline__ void stage(float (*As)[420]) const {
+    float4* dst = reinterpret_cast<float4*>(&As[0][0]);
+#pragma unroll
+    for (int r = 0; r < kStage; ++r) {
+      const int i4 = threadIdx.x + kThreads * r;
+      if (i4 < 16 * 105) dst[i4] = (i4 < nvalid) ? a_stage[r] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+};
+
+// The finish of one (vertex v, frame n) pair, the same in all three skin forms: store the posed rest vertex vp, blend the 12
+// entries of the transform from the ELL weights and the frame's staged transforms Af = As[f], apply it and store verts, project
+// (+ tr) and store proj.  The first min(Kw, kHeld) weights are the caller's registers (wj, wv; Kw_held = min(Kw, kHeld)), the
+// rest are read from memory: kHeld = 8 in the matrix-core forms, 0 in the plain one.
+template <int kHeld>
+__device__ __forceinline__ void skin_finish(const ModelDev& m, int v, int n, const float (&vp)[3], const float* Af, const int* wj,
+                                            const float* wv, int Kw_held, const float* tr, float* __restrict__ vposed,
+                                            float* __restrict__ verts, float* __restrict__ proj) {
+  const int Vp = m.Vp;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) vposed[((size_t)n * 3 + a) * Vp + v] = vp[a];
+  float T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = 0.f;
+  auto blend = [&](int j, float wx) {
+    const float* A = Af + j * 12;
+#pragma unroll
+    for (int c = 0; c < 12; ++c) T[c] = fmaf(wx, A[c], T[c]);
+  };
+#pragma unroll
+  for (int e = 0; e < kHeld; ++e)
+    if (e < Kw_held) blend(wj[e], wv[e]);
+  for (int e = kHeld; e < m.Kw; ++e) blend(m.w_j[e * Vp + v], m.w_val[e * Vp + v]);     // (models with more weights per vertex than are held)
+  float o[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    o[a] = fmaf(T[a * 4], vp[0], fmaf(T[a * 4 + 1], vp[1], fmaf(T[a * 4 + 2], vp[2], T[a * 4 + 3])));
+    verts[((size_t)n * 3 + a) * Vp + v] = o[a];
+  }
+  float xn, yn, zv;
+  world_to_ndc(o[0] + tr[0], o[1] + tr[1], o[2] + tr[2], xn, yn, zv);
+  proj[((size_t)n * 3 + 0) * Vp + v] = xn;
+  proj[((size_t)n * 3 + 1) * Vp + v] = yn;
+  proj[((size_t)n * 3 + 2) * Vp + v] = zv;
+}
+
 // Four waves own 16 vertices x 16 frames (kSkinGroups such groups per workgroup share the frames' staged transforms);
 // wave w takes k-steps [20 w, 20 w + 20) -- ONE batch of operand loads, 60 matrix instructions -- the four partial tiles meet in LDS
 // and are added in wave order (fixed: deterministic), and wave w finishes frame 4 (lane >> 4) + w of its lanes' vertices: one
 // (vertex, frame) pair per lane for the skinning instead of four.  Four times the workgroups, a quarter of the chain each.
 // (kSkinGroups, kSkinVerts, kSkinThreads: smalfit_plan.h, which sizes the launch by them)
-constexpr int kSkinStage = (16 * 105 + kSkinThreads - 1) / kSkinThreads;   // float4 words of the transforms a thread stages
 __global__ void __launch_bounds__(kSkinThreads)
 skin_mfma_split_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_shaped, int vs_stride /*0 | 3*Vp*/,
                  const float* __restrict__ pfT, const float* __restrict__ Am, const float* __restrict__ trans,
@@ -656,22 +713,8 @@ skin_mfma_split_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_sh
   // everything besides the GEMM operands is requested here, unconditionally (clamped indices, masked where it is used): the 16
   // frames' skinning transforms (one contiguous run of A, as float4), the lane's skinning weights, the rest vertex and the
   // translation of ITS frame
-  const int nvalid = min(16, M - n0) * 105;                   // float4 words of A that exist
-  float4 a_stage[kSkinStage];
-  {
-    const float4* src = reinterpret_cast<const float4*>(Am + (size_t)n0 * 420);
-#pragma unroll
-    for (int r = 0; r < kSkinStage; ++r) a_stage[r] = src[min((int)threadIdx.x + kSkinThreads * r, nvalid - 1)];
-  }
-  int wj[8];
-  float wv[8];
-  const int Kw = min(m.Kw, 8);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int ee = max(min(e, Kw - 1), 0);
-    wj[e] = m.w_j[ee * Vp + v];
-    wv[e] = m.w_val[ee * Vp + v];
-  }
+  SkinSide<kSkinThreads> sd;
+  sd.fetch(m, M, n0, v, Am);
   const int f = 4 * kq + w, n = n0 + f, nn = min(n, M - 1);  // this lane's frame after the reduction
   float vs_r[3], tr_r[3];
   {
@@ -693,14 +736,7 @@ skin_mfma_split_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_sh
     const float* b = pb + (size_t)(min(st * 4 + kq, 305) - kq) * 3 * Vp;
     x0[u] = b[0]; x1[u] = b[Vp]; x2[u] = b[2 * Vp];
   }
-  {
-    float4* dst = reinterpret_cast<float4*>(&As[0][0]);
-#pragma unroll
-    for (int r = 0; r < kSkinStage; ++r) {
-      const int i4 = threadIdx.x + kSkinThreads * r;
-      if (i4 < 16 * 105) dst[i4] = (i4 < nvalid) ? a_stage[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
+  sd.stage(As);
   PHASE_MARK(pk1);                      // side operands requested and staged
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0;
 #pragma unroll
@@ -721,37 +757,7 @@ skin_mfma_split_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_sh
 #pragma unroll
     for (int a = 0; a < 3; ++a) bl[a] = ((red[grp * 4][a * 4 + w][lane] + red[grp * 4 + 1][a * 4 + w][lane]) + red[grp * 4 + 2][a * 4 + w][lane]) + red[grp * 4 + 3][a * 4 + w][lane];
     const float vp[3] = {vs_r[0] + bl[0], vs_r[1] + bl[1], vs_r[2] + bl[2]};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) vposed[((size_t)n * 3 + a) * Vp + v] = vp[a];
-    float T[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) T[e] = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if (e < Kw) {
-        const float* A = &As[f][wj[e] * 12];
-#pragma unroll
-        for (int c = 0; c < 12; ++c) T[c] = fmaf(wv[e], A[c], T[c]);
-      }
-    }
-    for (int e = 8; e < m.Kw; ++e) {            // models with more than 8 weights per vertex
-      const int j = m.w_j[e * Vp + v];
-      const float wx = m.w_val[e * Vp + v];
-      const float* A = &As[f][j * 12];
-#pragma unroll
-      for (int c = 0; c < 12; ++c) T[c] = fmaf(wx, A[c], T[c]);
-    }
-    float o[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      o[a] = fmaf(T[a * 4], vp[0], fmaf(T[a * 4 + 1], vp[1], fmaf(T[a * 4 + 2], vp[2], T[a * 4 + 3])));
-      verts[((size_t)n * 3 + a) * Vp + v] = o[a];
-    }
-    float xn, yn, zv;
-    world_to_ndc(o[0] + tr_r[0], o[1] + tr_r[1], o[2] + tr_r[2], xn, yn, zv);
-    proj[((size_t)n * 3 + 0) * Vp + v] = xn;
-    proj[((size_t)n * 3 + 1) * Vp + v] = yn;
-    proj[((size_t)n * 3 + 2) * Vp + v] = zv;
+    skin_finish<8>(m, v, n, vp, As[f], sd.wj, sd.wv, sd.Kw, tr_r, vposed, verts, proj);
   }
   PHASE_MARK(pk3);
   PHASE_ADD(PH_SKIN, 0, pk0, pk1); PHASE_ADD(PH_SKIN, 1, pk1, pk2); PHASE_ADD(PH_SKIN, 2, pk2, pk3);
@@ -777,22 +783,8 @@ skin_mfma_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_shaped, 
   // rest vertex / translation of its four frames.  As conditional loads each of them was compiled into a branch with an
   // s_waitcnt vmcnt(0) behind it -- 7 dependent trips before the first matrix instruction and ~16 after the last
   // (tools/isa_loads.py); now they are in flight together, underneath the GEMM's own operand stream.
-  const int nvalid = min(16, M - n0) * 105;                   // float4 words of A that exist
-  float4 a_stage[7];
-  {
-    const float4* src = reinterpret_cast<const float4*>(Am + (size_t)n0 * 420);
-#pragma unroll
-    for (int r = 0; r < 7; ++r) a_stage[r] = src[min((int)threadIdx.x + 256 * r, nvalid - 1)];
-  }
-  int wj[8];
-  float wv[8];
-  const int Kw = min(m.Kw, 8);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int ee = max(min(e, Kw - 1), 0);
-    wj[e] = m.w_j[ee * Vp + v];
-    wv[e] = m.w_val[ee * Vp + v];
-  }
+  SkinSide<256> sd;
+  sd.fetch(m, M, n0, v, Am);
   float vs_r[4][3], tr_r[4][3];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -801,14 +793,7 @@ skin_mfma_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_shaped, 
 #pragma unroll
     for (int a = 0; a < 3; ++a) { vs_r[r][a] = vs[a * Vp + v]; tr_r[r][a] = trans[nn * 3 + a]; }
   }
-  {
-    float4* dst = reinterpret_cast<float4*>(&As[0][0]);
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-      const int i4 = threadIdx.x + 256 * r;
-      if (i4 < 16 * 105) dst[i4] = (i4 < nvalid) ? a_stage[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
+  sd.stage(As);
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0;
   const float* pa = pfT + (size_t)kq * Mp + n0 + (lane & 15);
   const float* pb = m.pd + (size_t)kq * 3 * Vp + v;
@@ -856,37 +841,7 @@ skin_mfma_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_shaped, 
     const int f = 4 * kq + r, n = n0 + f;
     if (n >= M) break;
     const float vp[3] = {vs_r[r][0] + acc0[r], vs_r[r][1] + acc1[r], vs_r[r][2] + acc2[r]};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) vposed[((size_t)n * 3 + a) * Vp + v] = vp[a];
-    float T[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) T[e] = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if (e < Kw) {
-        const float* A = &As[f][wj[e] * 12];
-#pragma unroll
-        for (int c = 0; c < 12; ++c) T[c] = fmaf(wv[e], A[c], T[c]);
-      }
-    }
-    for (int e = 8; e < m.Kw; ++e) {            // models with more than 8 weights per vertex
-      const int j = m.w_j[e * Vp + v];
-      const float wx = m.w_val[e * Vp + v];
-      const float* A = &As[f][j * 12];
-#pragma unroll
-      for (int c = 0; c < 12; ++c) T[c] = fmaf(wx, A[c], T[c]);
-    }
-    float o[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      o[a] = fmaf(T[a * 4], vp[0], fmaf(T[a * 4 + 1], vp[1], fmaf(T[a * 4 + 2], vp[2], T[a * 4 + 3])));
-      verts[((size_t)n * 3 + a) * Vp + v] = o[a];
-    }
-    float xn, yn, zv;
-    world_to_ndc(o[0] + tr_r[r][0], o[1] + tr_r[r][1], o[2] + tr_r[r][2], xn, yn, zv);
-    proj[((size_t)n * 3 + 0) * Vp + v] = xn;
-    proj[((size_t)n * 3 + 1) * Vp + v] = yn;
-    proj[((size_t)n * 3 + 2) * Vp + v] = zv;
+    skin_finish<8>(m, v, n, vp, As[f], sd.wj, sd.wv, sd.Kw, tr_r[r], vposed, verts, proj);
   }
   PHASE_MARK(pk3);
   PHASE_ADD(PH_SKIN, 0, pk0, pk1); PHASE_ADD(PH_SKIN, 1, pk1, pk2); PHASE_ADD(PH_SKIN, 2, pk2, pk3);
@@ -939,32 +894,10 @@ skin_kernel(ModelDev m, int M, int Mp, const float* __restrict__ v_shaped, int v
     const float* vs = v_shaped + (size_t)n * vs_stride;
     float vp[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < 3; ++a)
       vp[a] = vs[a * Vp + v] + ((red[0][f * 3 + a][lane] + red[1][f * 3 + a][lane]) +
                                 (red[2][f * 3 + a][lane] + red[3][f * 3 + a][lane]));
-      vposed[((size_t)n * 3 + a) * Vp + v] = vp[a];
-    }
-    float T[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) T[e] = 0.f;
-    for (int e = 0; e < m.Kw; ++e) {
-      const int j = m.w_j[e * Vp + v];
-      const float wv = m.w_val[e * Vp + v];
-      const float* A = &As[f][j * 12];
-#pragma unroll
-      for (int c = 0; c < 12; ++c) T[c] = fmaf(wv, A[c], T[c]);
-    }
-    float o[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      o[a] = fmaf(T[a * 4], vp[0], fmaf(T[a * 4 + 1], vp[1], fmaf(T[a * 4 + 2], vp[2], T[a * 4 + 3])));
-      verts[((size_t)n * 3 + a) * Vp + v] = o[a];
-    }
-    float xn, yn, zv;
-    world_to_ndc(o[0] + trans[n * 3], o[1] + trans[n * 3 + 1], o[2] + trans[n * 3 + 2], xn, yn, zv);
-    proj[((size_t)n * 3 + 0) * Vp + v] = xn;
-    proj[((size_t)n * 3 + 1) * Vp + v] = yn;
-    proj[((size_t)n * 3 + 2) * Vp + v] = zv;
+    skin_finish<0>(m, v, n, vp, As[f], nullptr, nullptr, 0, trans + n * 3, vposed, verts, proj);
   }
 }
 

@@ -157,6 +157,20 @@ __device__ __forceinline__ unsigned long long pack_candidate(float d) {
   return (1ull << kCountShift) | (unsigned long long)(unsigned)fmaf(f, kLogFix, 0.5f);
 }
 
+// A finished pixel: its silhouette value, |sil - target| and the adjoint seed of the squared distances,
+// gx = -wn sgn(sil - target) alpha / sigma with wn = w_sil / (Bn S S) formed by the caller.  Resolve, the band ranking and the
+// exact selection all finish their pixels here; the loss bookkeeping, the stores and the depth bounds are each caller's own.
+struct PixelSeed { float sil, adiff, gx; };
+__device__ __forceinline__ PixelSeed pixel_no_target(float alpha) { return {1.0f - alpha, 0.f, 0.f}; }
+__device__ __forceinline__ PixelSeed pixel_seed(float alpha, float ts, float wn) {
+  PixelSeed p = pixel_no_target(alpha);
+  const float diff = p.sil - ts;
+  p.adiff = fabsf(diff);
+  const float sgn = (diff > 0.f) ? 1.0f : ((diff < 0.f) ? -1.0f : 0.0f);
+  p.gx = -wn * sgn * alpha * (1.0f / kSigma);
+  return p;
+}
+
 // p = sigmoid(-d / sigma) with the hardware exp2 / rcp (backward sweep)
 __device__ __forceinline__ float prob_fast(float d) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(d * (1.4426950408889634f / kSigma)));
@@ -713,16 +727,13 @@ raster_resolve_kernel(int S, int M, WinMap win, float w_sil, unsigned long long*
       }
       if (act == 0) {
         const float alpha = (c > 0) ? alpha_from_log_sum(vb & kSumMask) : 1.0f;
-        const float sil = 1.0f - alpha;
-        if (sil_out) sil_out[pi] = sil;
-        float gx = 0.f;
+        PixelSeed p = pixel_no_target(alpha);
+        if (sil_out) sil_out[pi] = p.sil;
         if (tsil) {
-          const float diff = sil - tss[s];
-          l += fabsf(diff);
-          const float sgn = (diff > 0.f) ? 1.0f : ((diff < 0.f) ? -1.0f : 0.0f);
-          gx = -(w_sil / ((float)frame_window_size(n, win) * (float)S * (float)S)) * sgn * alpha * (1.0f / kSigma);
+          p = pixel_seed(alpha, tss[s], w_sil / ((float)frame_window_size(n, win) * (float)S * (float)S));
+          l += p.adiff;
         }
-        gz[pi] = make_float2(gx, zthr);
+        gz[pi] = make_float2(p.gx, zthr);
       } else {
         slot[s] = atomicAdd(&qn[act - 1], 1);
       }
@@ -873,20 +884,17 @@ band_role(int bi, int nblocks, float (*zs)[64], int S, int M, WinMap win, float 
       if (taken == need && zin < zout) {
         const unsigned long long sum = (vb & kSumMask) + ((unsigned long long)(unsigned)s_hi << 24) + (unsigned long long)(unsigned)s_lo;
         const float alpha = alpha_from_log_sum(sum);
-        const float sil = 1.0f - alpha;
-        if (sil_out) sil_out[pi] = sil;
-        float gx = 0.f;
+        PixelSeed p = pixel_no_target(alpha);
+        if (sil_out) sil_out[pi] = p.sil;
         if (tsil) {
           const int n = gp / npix;
           const float wn = w_sil / ((float)frame_window_size(n, win) * (float)S * (float)S);
-          const float diff = sil - ts;
-          const long long lp = (long long)(fabsf(diff) * wn * kLossFix);
+          p = pixel_seed(alpha, ts, wn);
+          const long long lp = (long long)(p.adiff * wn * kLossFix);
           lacc += lp;
           if constexpr (kFrameLoss) frame_loss_add(floss, fl, n, lp);
-          const float sgn = (diff > 0.f) ? 1.0f : ((diff < 0.f) ? -1.0f : 0.0f);
-          gx = -wn * sgn * alpha * (1.0f / kSigma);
         }
-        gz[pi] = make_float2(gx, zin);
+        gz[pi] = make_float2(p.gx, zin);
         // re-centre the pixel's bounds on the depth of its K-th nearest as just determined (zin), keeping the
         // half-width (or narrowing it when it holds more candidates than the current pose motion calls for): the band
         // follows the surface from iteration to iteration.  Bounds are hints -- any value is valid.
@@ -1059,7 +1067,7 @@ __device__ __forceinline__ long long select_pixel(const SelCtx& c, const SelLds&
         if (live) {
           FaceRec r;
           unpack_face_rec(a, b, c, d, r);
-          ok = face_pixel_candidate(r, ppx, ppy, e.d);       // decision + signed distance only (same bits as face_pixel_eval)
+          ok = face_pixel_candidate(r, ppx, ppy, e.d);       // decision + signed distance only (face_pixel_bary / face_pixel_edges, as face_pixel_eval)
           e.pz = face_pixel_depth(r, ppx, ppy);
         }
         fn(ok, e.pz - zcn, e.d, cur_ff);
@@ -1269,18 +1277,15 @@ __device__ __forceinline__ long long select_pixel(const SelCtx& c, const SelLds&
   }
   if (lane == 0) {
     const size_t pi = (size_t)gp;
-    const float sil = 1.0f - a;
-    if (c.sil_out) c.sil_out[pi] = sil;
-    float gx = 0.f, l = 0.f;
+    PixelSeed p = pixel_no_target(a);
+    if (c.sil_out) c.sil_out[pi] = p.sil;
+    float l = 0.f;
     if (c.tsil) {
-      const float diff = sil - ts;
-      const int Bn = frame_window_size(n, c.win);
-      const float wn = c.w_sil / ((float)Bn * (float)S * (float)S);
-      l = fabsf(diff) * wn;
-      const float sgn = (diff > 0.f) ? 1.0f : ((diff < 0.f) ? -1.0f : 0.0f);
-      gx = -wn * sgn * a * (1.0f / kSigma);
+      const float wn = c.w_sil / ((float)frame_window_size(n, c.win) * (float)S * (float)S);
+      p = pixel_seed(a, ts, wn);
+      l = p.adiff * wn;
     }
-    c.gz[pi] = make_float2(gx, zmid);
+    c.gz[pi] = make_float2(p.gx, zmid);
     c.zband[pi] = make_float2(blo, bhi);
     loss_fp = (long long)(l * kLossFix);
   }
@@ -1460,7 +1465,7 @@ raster_bwd_kernel(int F, int M, int S, float inv_s /*1 / S, divided on the host:
         if (g.x == 0.f) return;
         SMALFIT_WORK(++wb_live;)
         // depth first: it is five instructions and rejects the far side of the animal before the distance maths
-        // (same expression as in face_pixel_eval, so the comparison agrees bitwise with the forward's)
+        // (face_depth, as in face_pixel_eval, so the comparison agrees bitwise with the forward's)
         const float ppx = fmaf(colf, ndc_a, ndc_b), ppy = fmaf(rowf, ndc_a, ndc_b);
         if (face_pixel_depth(r, ppx, ppy) - zcn > g.y) return;           // not among the pixel's K nearest
         SMALFIT_WORK(++wb_eval;)

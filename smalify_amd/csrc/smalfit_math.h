@@ -305,7 +305,7 @@ SMALFIT_HD bool make_face_rec(float ax, float ay, float az, float bx, float by, 
   return (fabsf(r.area) > kEps) && (zmax >= 0.0f);
 }
 
-// depth of face r at pixel centre (px, py): the same expression face_pixel_eval uses (cheap pre-test)
+// depth of face r at pixel centre (px, py): face_depth, as face_pixel_eval calls it (cheap pre-test)
 SMALFIT_HD float face_pixel_depth(const FaceRec& r, float px, float py) { return face_depth(r, px - r.ax, py - r.ay); }
 
 struct PixEval {
@@ -317,64 +317,65 @@ struct PixEval {
   bool inside;
 };
 
-// true when the face contributes to pixel centre (px, py) (pytorch3d naive rasteriser inclusion test).
-// Every multiply-add is an explicit fmaf and no other a*b+c pattern is left for the compiler to contract: the
-// two-pixel packed form in the kernels (face_pixel_eval2) performs the same IEEE operations in the same order, so the
-// two agree bitwise (the K-nearest bookkeeping relies on every kernel seeing the same candidate set and depths).
-SMALFIT_HD bool face_pixel_eval(const FaceRec& r, float px, float py, PixEval& o) {
-  const float dx = px - r.ax, dy = py - r.ay;
+// What face r yields at pixel centre p, with (dx, dy) = p - a, before anyone takes a minimum: the barycentric terms w (over
+// area + eps) from face_pixel_bary and, per edge (0: a-b, 1: a-c, 2: b-c), the clamped parameter t, the offset q = p - closest
+// point and its squared length d from face_pixel_edges.  Every multiply-add is an explicit fmaf and no other a*b+c pattern is left
+// for the compiler to contract.  face_pixel_eval and face_pixel_candidate both call these two, so every kernel sees the same
+// candidate set, distances and depths to the bit (the K-nearest bookkeeping relies on that).  They are two functions, called
+// around the inside test and face_depth, because that is the order the sweep kernel was scheduled in: as one function behind
+// which the inside test came last, raster_sweep_kernel ran 0.8 us (0.7 %) longer (profiles/one_definition_parent_vs_branch.txt).
+struct FacePixelTerms {
+  float w0, w1, w2;
+  float t[3], qx[3], qy[3], d[3];
+};
+
+SMALFIT_HD void face_edge_terms(float ex, float ey, float vx, float vy, float il, float t0, int e, FacePixelTerms& o) {
+  const float t = fminf(fmaxf(fmaf(fmaf(ey, vy, ex * vx), il, t0), 0.0f), 1.0f);
+  const float qx = fmaf(-t, vx, ex), qy = fmaf(-t, vy, ey);
+  o.t[e] = t;  o.qx[e] = qx;  o.qy[e] = qy;
+  o.d[e] = fmaf(qy, qy, qx * qx);
+}
+SMALFIT_HD void face_pixel_bary(const FaceRec& r, float dx, float dy, FacePixelTerms& o) {
   const float c1 = fmaf(dx, r.e1y, -(dy * r.e1x));   // E(p; a, b)
   const float c2 = fmaf(dx, r.e2y, -(dy * r.e2x));   // -E(p; c, a)
-  const float w2 = c1 * r.inv_den;
-  const float w1 = -c2 * r.inv_den;
-  const float w0 = ((c2 - c1) + r.area) * r.inv_den; // E(p; b, c) / (area + eps)
-  o.inside = (w0 > 0.0f) && (w1 > 0.0f) && (w2 > 0.0f);
+  o.w2 = c1 * r.inv_den;
+  o.w1 = -c2 * r.inv_den;
+  o.w0 = ((c2 - c1) + r.area) * r.inv_den;           // E(p; b, c) / (area + eps)
+}
+SMALFIT_HD void face_pixel_edges(const FaceRec& r, float dx, float dy, FacePixelTerms& o) {
+  face_edge_terms(dx, dy, r.e1x, r.e1y, r.il1, r.t01, 0, o);
+  face_edge_terms(dx, dy, r.e2x, r.e2y, r.il2, r.t02, 1, o);
+  face_edge_terms(dx - r.e1x, dy - r.e1y, r.e3x, r.e3y, r.il3, r.t03, 2, o);
+}
+
+// true when the face contributes to pixel centre (px, py) (pytorch3d naive rasteriser inclusion test); the nearest edge by
+// compare/select, first edge winning ties, with its q, t and index for the backward.
+SMALFIT_HD bool face_pixel_eval(const FaceRec& r, float px, float py, PixEval& o) {
+  FacePixelTerms f;
+  const float dx = px - r.ax, dy = py - r.ay;
+  face_pixel_bary(r, dx, dy, f);
+  o.inside = (f.w0 > 0.0f) && (f.w1 > 0.0f) && (f.w2 > 0.0f);
   const float pz = face_depth(r, dx, dy);
   o.pz = pz;
-  // edge a-b
-  const float t1 = fminf(fmaxf(fmaf(fmaf(dy, r.e1y, dx * r.e1x), r.il1, r.t01), 0.0f), 1.0f);
-  const float q1x = fmaf(-t1, r.e1x, dx), q1y = fmaf(-t1, r.e1y, dy);
-  const float d1 = fmaf(q1y, q1y, q1x * q1x);
-  // edge a-c
-  const float t2 = fminf(fmaxf(fmaf(fmaf(dy, r.e2y, dx * r.e2x), r.il2, r.t02), 0.0f), 1.0f);
-  const float q2x = fmaf(-t2, r.e2x, dx), q2y = fmaf(-t2, r.e2y, dy);
-  const float d2 = fmaf(q2y, q2y, q2x * q2x);
-  // edge b-c
-  const float ex = dx - r.e1x, ey = dy - r.e1y;
-  const float t3 = fminf(fmaxf(fmaf(fmaf(ey, r.e3y, ex * r.e3x), r.il3, r.t03), 0.0f), 1.0f);
-  const float q3x = fmaf(-t3, r.e3x, ex), q3y = fmaf(-t3, r.e3y, ey);
-  const float d3 = fmaf(q3y, q3y, q3x * q3x);
-  float dist = d1; o.qx = q1x; o.qy = q1y; o.tc = t1; o.edge = 0;
-  if (d2 < dist) { dist = d2; o.qx = q2x; o.qy = q2y; o.tc = t2; o.edge = 1; }
-  if (d3 < dist) { dist = d3; o.qx = q3x; o.qy = q3y; o.tc = t3; o.edge = 2; }
+  face_pixel_edges(r, dx, dy, f);
+  float dist = f.d[0]; o.qx = f.qx[0]; o.qy = f.qy[0]; o.tc = f.t[0]; o.edge = 0;
+  if (f.d[1] < dist) { dist = f.d[1]; o.qx = f.qx[1]; o.qy = f.qy[1]; o.tc = f.t[1]; o.edge = 1; }
+  if (f.d[2] < dist) { dist = f.d[2]; o.qx = f.qx[2]; o.qy = f.qy[2]; o.tc = f.t[2]; o.edge = 2; }
   o.d = o.inside ? -dist : dist;
   return (pz >= 0.0f) && (o.inside || dist < kBlur);
 }
 
-// The forward sweep's form of face_pixel_eval: the candidate decision and the signed squared distance only.  The same IEEE
-// operations in the same order produce t, q and the three edge distances (so d and the decision agree bitwise with
-// face_pixel_eval, which the selection and the backward use); the minimum over the edges and the inside test are taken
-// with min3 instead of compare/select chains -- identical values, a third fewer instructions around them.
+// The forward sweep's form of face_pixel_eval: the candidate decision and the signed squared distance only, from the same
+// face_pixel_bary and face_pixel_edges.  The minimum over the edges and the inside test are taken with min3 instead of
+// compare/select chains -- identical values, a third fewer instructions around them.
 SMALFIT_HD bool face_pixel_candidate(const FaceRec& r, float px, float py, float& d_out) {
+  FacePixelTerms f;
   const float dx = px - r.ax, dy = py - r.ay;
-  const float c1 = fmaf(dx, r.e1y, -(dy * r.e1x));
-  const float c2 = fmaf(dx, r.e2y, -(dy * r.e2x));
-  const float w2 = c1 * r.inv_den;
-  const float w1 = -c2 * r.inv_den;
-  const float w0 = ((c2 - c1) + r.area) * r.inv_den;
-  const bool inside = fminf(w0, fminf(w1, w2)) > 0.0f;
+  face_pixel_bary(r, dx, dy, f);
+  const bool inside = fminf(f.w0, fminf(f.w1, f.w2)) > 0.0f;
   const float pz = face_depth(r, dx, dy);
-  const float t1 = fminf(fmaxf(fmaf(fmaf(dy, r.e1y, dx * r.e1x), r.il1, r.t01), 0.0f), 1.0f);
-  const float q1x = fmaf(-t1, r.e1x, dx), q1y = fmaf(-t1, r.e1y, dy);
-  const float d1 = fmaf(q1y, q1y, q1x * q1x);
-  const float t2 = fminf(fmaxf(fmaf(fmaf(dy, r.e2y, dx * r.e2x), r.il2, r.t02), 0.0f), 1.0f);
-  const float q2x = fmaf(-t2, r.e2x, dx), q2y = fmaf(-t2, r.e2y, dy);
-  const float d2 = fmaf(q2y, q2y, q2x * q2x);
-  const float ex = dx - r.e1x, ey = dy - r.e1y;
-  const float t3 = fminf(fmaxf(fmaf(fmaf(ey, r.e3y, ex * r.e3x), r.il3, r.t03), 0.0f), 1.0f);
-  const float q3x = fmaf(-t3, r.e3x, ex), q3y = fmaf(-t3, r.e3y, ey);
-  const float d3 = fmaf(q3y, q3y, q3x * q3x);
-  const float dist = fminf(d1, fminf(d2, d3));
+  face_pixel_edges(r, dx, dy, f);
+  const float dist = fminf(f.d[0], fminf(f.d[1], f.d[2]));
   d_out = inside ? -dist : dist;
   return (pz >= 0.0f) && (inside || dist < kBlur);
 }
