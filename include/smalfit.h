@@ -39,7 +39,7 @@ typedef struct smalfit_engine smalfit_engine;
  * 5 = smalfit_engine_set_option; 6 = smalfit_fit_args.subject_frames / losses_per_frame (a batch of independent images,
  * each with its own shape; one row of loss terms per frame).  Added within version 6, no struct of it changing its layout:
  * smalfit_fit_eval_windows (smalfit_window_rows); smalfit_fit_metrics (smalfit_metrics_args: silhouette IoU counts and PCK
- * per frame). */
+ * per frame); smalfit_mesh_score (smalfit_mesh_score_args: point-to-surface distances both ways, per mesh). */
 #define SMALFIT_ABI_VERSION 6
 int smalfit_version(void);
 const char* smalfit_last_error(void);
@@ -462,8 +462,47 @@ void smalfit_mesh_targets_destroy(smalfit_mesh_targets* targets);
 int smalfit_mesh_targets_sample(smalfit_mesh_targets* targets, void* stream, int num_points,
                                 unsigned long long seed, unsigned int iteration, float* points);
 
+/* ---- how good a 3-D fit is: exact surface distances both ways, per mesh -------------------------------------------------
+ * No counterpart in the reference, whose fitter_3d contains no evaluation code: the definitions below are THIS PROJECT'S.
+ *   distance       from a point p to the closed triangle (a, b, c): the square root of the minimum of
+ *                    - the three squared point-to-segment distances, the segment's parameter clamped to [0, 1] (a segment of
+ *                      zero length is its end point), and
+ *                    - the squared distance to the plane, when the normal n = (b - a) x (c - a) is not zero and p projects
+ *                      inside: <(b - a) x (p - a), n>, <(c - b) x (p - b), n> and <(a - c) x (p - c), n> are all >= 0.
+ *                  A degenerate triangle (collinear or coincident corners) is exactly its three segments.  float32 throughout.
+ *   vert_dist      [n][v] = the least distance from fitted vertex v of mesh n to the triangles of TARGET mesh n
+ *   point_dist     [n][s] = the least distance from points[n][s] to the triangles of the FITTED mesh n (verts[n] with the
+ *                  faces given to the objective's create call)
+ *                  Both are minima over float32 values: bit-reproducible, whatever order the triangles are scanned in.  No
+ *                  face index is returned: on a shared edge or vertex several faces are equally near.
+ *   sums           [n][dir] = sum d, sum d^2, max d over the queries of direction dir (0: the V fitted vertices, 1: the S
+ *                  points), float32 sums in a fixed order
+ *   within         [n][dir][t] = queries of that direction with d <= thresholds[t]
+ * Quotients are the host's: mean = sum d / count, RMS = sqrt(sum d^2 / count), Hausdorff = the larger of the two maxima,
+ * precision / recall / F-score at t from `within` (smalify_amd/metrics.py::summarise_mesh_score forms them in float64).
+ * Without points only direction 0 is scored; the rows of direction 1 are zero.
+ * Everything is enqueued on `stream`; nothing synchronises.  A refused block launches nothing and leaves every output alone.
+ * The call uses the objective's work buffers: it must not overlap another call on the same objective (calls enqueued on one
+ * stream never do). */
+#define SMALFIT_MAX_SCORE_THRESHOLDS 8
+typedef struct smalfit_mesh_score_args {
+  unsigned struct_size;       /* sizeof(smalfit_mesh_score_args) of the caller's header; checked before any other field */
+  int num_meshes;             /* N <= the objective's max_meshes, == the targets' mesh count */
+  const float* verts;         /* (N,V,3) fitted vertices: verts_out of smalfit_mesh_objective_eval / smalfit_fit3d_step */
+  const float* points;        /* (N,S,3) points on the target surfaces (smalfit_mesh_targets_sample), or NULL: one direction only */
+  int num_points;             /* S <= the objective's max_points; 0 when points is NULL */
+  int num_thresholds;         /* T in 0..8 */
+  float thresholds[SMALFIT_MAX_SCORE_THRESHOLDS];  /* host values, each finite and > 0, in the model's units */
+  float* vert_dist;           /* (N,V) or NULL: fitted vertex -> target surface */
+  float* point_dist;          /* (N,S) or NULL: target point -> fitted surface; must be NULL without points */
+  float* sums;                /* (N,2,3): per direction sum d, sum d^2, max d; the rows of direction 1 are zero without points */
+  int* within;                /* (N,2,T) or NULL; must be NULL when T == 0 */
+} smalfit_mesh_score_args;
+int smalfit_mesh_score(smalfit_mesh_objective* objective, smalfit_mesh_targets* targets, void* stream,
+                       const smalfit_mesh_score_args* args);
+
 /* ---- Stage.step in one call ------------------------------------------------------------------------------------
- * replaces: one iteration of Stage.run                       reference fitter_3d/trainer.py:229-241,257-262
+ * replaces: one iteration of Stage.run                      reference fitter_3d/trainer.py:229-241,257-262
  *   new_src_verts = smal_3d_fitter(); loss = forward(...); loss.backward(); optimizer.step()
  * = SMAL forward on [global_rot | joint_rot], target points sampled (or taken from `points`), the four-term objective,
  * its gradient back through the SMAL model, torch.optim.Adam on every parameter whose learning rate is > 0 (the

@@ -76,6 +76,20 @@ class MetricsArgs(C.Structure):
         self.struct_size = C.sizeof(MetricsArgs)
 
 
+MAX_SCORE_THRESHOLDS = 8          # SMALFIT_MAX_SCORE_THRESHOLDS
+
+
+class MeshScoreArgs(C.Structure):
+    """smalfit_mesh_score_args: point-to-surface distances both ways, per mesh (smalfit_mesh_score)"""
+    _fields_ = [("struct_size", C.c_uint), ("num_meshes", C.c_int), ("verts", C.c_void_p), ("points", C.c_void_p),
+                ("num_points", C.c_int), ("num_thresholds", C.c_int), ("thresholds", C.c_float * MAX_SCORE_THRESHOLDS),
+                ("vert_dist", C.c_void_p), ("point_dist", C.c_void_p), ("sums", C.c_void_p), ("within", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(MeshScoreArgs)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -175,12 +189,13 @@ SIGNATURES = {
     "smalfit_mesh_targets_create": (_I, [_I, _VP, _VP, _VP, _VP, C.POINTER(_VP)]),
     "smalfit_mesh_targets_destroy": (None, [_VP]),
     "smalfit_mesh_targets_sample": (_I, [_VP, _VP, _I, C.c_ulonglong, C.c_uint, _VP]),
+    "smalfit_mesh_score": (_I, [_VP, _VP, _VP, C.POINTER(MeshScoreArgs)]),
     "smalfit_fit3d_step": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
 # built before them loads, and resolve() names the symbol when one is asked for
-LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics"])
+LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "smalfit_mesh_score"])
 
 
 class SmalfitError(RuntimeError):

@@ -296,6 +296,114 @@ __global__ __launch_bounds__(256) void mesh3d_sample_kernel(MeshTargetsDev t, in
   dst[2] = out[2];
 }
 
+// ---- smalfit_mesh_score: exact point-to-surface distances both ways, per mesh ------------------------------------------
+// 3 launches: mesh3d_surface_dist<0> (every fitted vertex against the triangles of its target mesh), mesh3d_surface_dist<1>
+// (every target point against the triangles of the fitted mesh; skipped without points), mesh3d_score_reduce (one block per
+// direction and mesh: sum d, sum d^2, max d, counts within the thresholds).  O(V F_target + S F) pair tests per mesh, each
+// point_scan_tri_dist2 of mesh3d_math.h; a minimum has no order and every sum a fixed one, so the results are reproducible.
+struct MeshScoreArgs {
+  int N, V, S, F;           // meshes, fitted vertices, points per mesh (0: none), faces of the fitted topology
+  const float* verts;       // [N][V][3]
+  const float* points;      // [N][S][3] or null
+  const int* faces;         // [F][3] of the fitted topology
+  MeshTargetsDev t;
+  float* vert_dist;         // [N][V]
+  float* point_dist;        // [N][S]
+  float* sums;              // [N][2][3]
+  int* within;              // [N][2][T] or null
+  int T;
+  float thr[SMALFIT_MAX_SCORE_THRESHOLDS];
+};
+
+// ROLE 0: queries = fitted vertices, scanned = the triangles of target mesh n (its own slice of the packed targets).
+// ROLE 1: queries = the caller's points, scanned = the triangles of the fitted mesh n.
+template <int ROLE>
+__global__ __launch_bounds__(256) void mesh3d_surface_dist_kernel(MeshScoreArgs a) {
+  __shared__ ScanTri st[kSurfaceChunk];
+  __shared__ float sd[4][kChamQueries];
+  const int n = blockIdx.y, lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave index in an SGPR: the scan loop is scalar
+  const int nq = ROLE == 0 ? a.V : a.S;
+  const float* q = ROLE == 0 ? a.verts + (size_t)n * a.V * 3 : a.points + (size_t)n * a.S * 3;
+  const int f0 = ROLE == 0 ? a.t.foff[n] : 0;
+  const int nf = ROLE == 0 ? a.t.foff[n + 1] - f0 : a.F;
+  const int* faces = (ROLE == 0 ? a.t.faces : a.faces) + 3 * (size_t)f0;
+  const float* corners = ROLE == 0 ? a.t.verts + 3 * (size_t)a.t.voff[n] : a.verts + (size_t)n * a.V * 3;
+  const int qi = blockIdx.x * kChamQueries + lane;
+  const bool active = qi < nq;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (active) {
+    qx = q[3 * (size_t)qi];
+    qy = q[3 * (size_t)qi + 1];
+    qz = q[3 * (size_t)qi + 2];
+  }
+  float best = INFINITY;
+  for (int base = 0; base < nf; base += kSurfaceChunk) {
+    const int cnt = min(kSurfaceChunk, nf - base);
+    __syncthreads();
+    for (int i = threadIdx.x; i < cnt; i += 256) {
+      const int* fc = faces + 3 * (size_t)(base + i);
+      st[i] = make_scan_tri(corners + 3 * (size_t)fc[0], corners + 3 * (size_t)fc[1], corners + 3 * (size_t)fc[2]);
+    }
+    __syncthreads();
+    const int per = (cnt + 3) >> 2;
+    const int b = min(w * per, cnt), e = min(b + per, cnt);
+    // b, e are wave-uniform: every lane reads the same four 16-byte rows of a record (broadcast, conflict free)
+    best = surface_scan(qx, qy, qz, st, b, e, best);
+  }
+  sd[w][lane] = best;
+  __syncthreads();
+  if (w != 0) return;
+#pragma unroll
+  for (int s = 1; s < 4; ++s) best = fminf(best, sd[s][lane]);
+  if (active) (ROLE == 0 ? a.vert_dist + (size_t)n * a.V : a.point_dist + (size_t)n * a.S)[qi] = sqrtf(best);
+}
+
+// block (dir, n): thread-strided partials in a fixed order, then the fixed tree of block_sum; the maximum and the integer
+// counts have no order.  Direction 1 without points has no queries: its rows are zeros
+__global__ __launch_bounds__(256) void mesh3d_score_reduce_kernel(MeshScoreArgs a) {
+  __shared__ float red[16];
+  __shared__ float wmax[4];
+  __shared__ int wcnt[4][SMALFIT_MAX_SCORE_THRESHOLDS];
+  const int dir = blockIdx.x, n = blockIdx.y;
+  const int nq = dir == 0 ? a.V : a.S;
+  const float* d = dir == 0 ? a.vert_dist + (size_t)n * a.V : a.point_dist + (size_t)n * a.S;
+  float s1 = 0.f, s2 = 0.f, mx = 0.f;
+  int cnt[SMALFIT_MAX_SCORE_THRESHOLDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = threadIdx.x; i < nq; i += 256) {
+    const float v = d[i];
+    s1 += v;
+    s2 += v * v;
+    mx = fmaxf(mx, v);
+#pragma unroll
+    for (int t = 0; t < SMALFIT_MAX_SCORE_THRESHOLDS; ++t) cnt[t] += (t < a.T && v <= a.thr[t]) ? 1 : 0;
+  }
+  const float t1 = block_sum(s1, red);
+  const float t2 = block_sum(s2, red);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+#pragma unroll
+  for (int t = 0; t < SMALFIT_MAX_SCORE_THRESHOLDS; ++t)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt[t] += __shfl_xor(cnt[t], o, 64);
+  if (lane == 0) {
+    wmax[w] = mx;
+#pragma unroll
+    for (int t = 0; t < SMALFIT_MAX_SCORE_THRESHOLDS; ++t) wcnt[w][t] = cnt[t];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* out = a.sums + ((size_t)n * kScoreDirections + dir) * 3;
+    out[0] = t1;
+    out[1] = t2;
+    out[2] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+  }
+  if (a.within != nullptr && (int)threadIdx.x < a.T)
+    a.within[((size_t)n * kScoreDirections + dir) * a.T + threadIdx.x] =
+        wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] + wcnt[3][threadIdx.x];
+}
+
 // ---- Adam on all trained parameters of a Stage.step in one launch ----------------------------------------------------
 // torch.optim.Adam (adam_update) over the trained parameters, one launch (Fit3dAdamArgs: smalfit_plan.h, beside plan_fit3d, which
 // sizes its segments)

@@ -105,6 +105,90 @@ SMALFIT_HD void nearest_merge(float& best, int& best_idx, float d2, int idx) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// point to triangle (smalfit_mesh_score; no counterpart in the reference: the definition is worded in include/smalfit.h).
+// The squared distance from p to the closed triangle (a, b, c) is the minimum of
+//   the three point-to-segment distances, the parameter clamped to [0, 1] (a zero-length segment is its end point), and
+//   the distance to the plane, when the normal n = (b - a) x (c - a) is not zero and p projects inside: the three edge
+//   functions <(b - a) x (p - a), n>, <(c - b) x (p - b), n>, <(a - c) x (p - c), n> are all >= 0.
+// A degenerate triangle is exactly its three segments: no special case, nothing is divided by a value that can be zero.
+// NOT the region walk (Ericson's closest point on a triangle): its cross terms cancel on slivers, and in float32 it was
+// measured 3e4 ulp of the largest coordinate off where this form stays within 23 (tests/test_mesh_score_cpu.py).
+// The staged record: four 16-byte rows, each one broadcast LDS read in the scan of mesh3d_surface_dist_kernel.
+// ------------------------------------------------------------------------------------------------
+struct alignas(16) ScanTri {
+  float ax, ay, az, inv_ab;   // corner a | 1 / |b - a|^2
+  float bx, by, bz, inv_bc;   // corner b | 1 / |c - b|^2
+  float cx, cy, cz, inv_ca;   // corner c | 1 / |a - c|^2
+  float nx, ny, nz, inv_nn;   // (b - a) x (c - a) | 1 / |n|^2      (every reciprocal: 0 where the squared length is 0)
+};
+
+SMALFIT_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) { return fmaf(az, bz, fmaf(ay, by, ax * bx)); }
+SMALFIT_HD float recip_or_zero(float x) { return x > 0.f ? 1.0f / x : 0.f; }
+
+SMALFIT_HD ScanTri make_scan_tri(const float* a, const float* b, const float* c) {
+  ScanTri t;
+  t.ax = a[0]; t.ay = a[1]; t.az = a[2];
+  t.bx = b[0]; t.by = b[1]; t.bz = b[2];
+  t.cx = c[0]; t.cy = c[1]; t.cz = c[2];
+  const float e0[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+  const float e1[3] = {c[0] - b[0], c[1] - b[1], c[2] - b[2]};
+  const float e2[3] = {a[0] - c[0], a[1] - c[1], a[2] - c[2]};
+  const float ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+  const float n[3] = {e0[1] * ac[2] - e0[2] * ac[1], e0[2] * ac[0] - e0[0] * ac[2], e0[0] * ac[1] - e0[1] * ac[0]};
+  t.nx = n[0]; t.ny = n[1]; t.nz = n[2];
+  t.inv_ab = recip_or_zero(dot3(e0[0], e0[1], e0[2], e0[0], e0[1], e0[2]));
+  t.inv_bc = recip_or_zero(dot3(e1[0], e1[1], e1[2], e1[0], e1[1], e1[2]));
+  t.inv_ca = recip_or_zero(dot3(e2[0], e2[1], e2[2], e2[0], e2[1], e2[2]));
+  t.inv_nn = recip_or_zero(dot3(n[0], n[1], n[2], n[0], n[1], n[2]));
+  return t;
+}
+
+// d = p - (start of the segment), e = end - start, inv = 1 / |e|^2 or 0.  fmaxf / fminf: a NaN parameter (0 x inf, the
+// reciprocal of a subnormal squared length) counts as 0, the start point
+SMALFIT_HD float point_segment_dist2(float dx, float dy, float dz, float ex, float ey, float ez, float inv) {
+  const float t = fminf(fmaxf(dot3(dx, dy, dz, ex, ey, ez) * inv, 0.f), 1.0f);
+  const float rx = fmaf(-t, ex, dx), ry = fmaf(-t, ey, dy), rz = fmaf(-t, ez, dz);
+  return dot3(rx, ry, rz, rx, ry, rz);
+}
+
+// <e x d, n>: the edge function of the edge e, d = p - (start of the edge)
+SMALFIT_HD float edge_function(float ex, float ey, float ez, float dx, float dy, float dz, float nx, float ny, float nz) {
+  const float cx = ey * dz - ez * dy, cy = ez * dx - ex * dz, cz = ex * dy - ey * dx;
+  return dot3(cx, cy, cz, nx, ny, nz);
+}
+
+SMALFIT_HD float point_scan_tri_dist2(float px, float py, float pz, const ScanTri& t) {
+  const float pax = px - t.ax, pay = py - t.ay, paz = pz - t.az;
+  const float pbx = px - t.bx, pby = py - t.by, pbz = pz - t.bz;
+  const float pcx = px - t.cx, pcy = py - t.cy, pcz = pz - t.cz;
+  const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
+  const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
+  const float cax = t.ax - t.cx, cay = t.ay - t.cy, caz = t.az - t.cz;
+  float d2 = point_segment_dist2(pax, pay, paz, abx, aby, abz, t.inv_ab);
+  d2 = fminf(d2, point_segment_dist2(pbx, pby, pbz, bcx, bcy, bcz, t.inv_bc));
+  d2 = fminf(d2, point_segment_dist2(pcx, pcy, pcz, cax, cay, caz, t.inv_ca));
+  // (all three evaluated, then combined: no divergent branch inside the scan loop)
+  const float s0 = edge_function(abx, aby, abz, pax, pay, paz, t.nx, t.ny, t.nz);
+  const float s1 = edge_function(bcx, bcy, bcz, pbx, pby, pbz, t.nx, t.ny, t.nz);
+  const float s2 = edge_function(cax, cay, caz, pcx, pcy, pcz, t.nx, t.ny, t.nz);
+  const bool inside = (t.inv_nn > 0.f) & (s0 >= 0.f) & (s1 >= 0.f) & (s2 >= 0.f);
+  const float h = dot3(pax, pay, paz, t.nx, t.ny, t.nz);
+  // (fminf: a NaN plane distance -- 0 x inf under a subnormal |n|^2 -- leaves the segments' value)
+  return inside ? fminf(h * h * t.inv_nn, d2) : d2;
+}
+
+SMALFIT_HD float point_triangle_dist2(const float* p, const float* a, const float* b, const float* c) {
+  return point_scan_tri_dist2(p[0], p[1], p[2], make_scan_tri(a, b, c));
+}
+
+// nearest of the staged triangles t[begin .. end): a minimum over float32 values does not depend on the scan's order
+SMALFIT_HD float surface_scan(float px, float py, float pz, const ScanTri* t, int begin, int end, float best) {
+#pragma unroll 2
+  for (int j = begin; j < end; ++j) best = fminf(best, point_scan_tri_dist2(px, py, pz, t[j]));
+  return best;
+}
+
+// ------------------------------------------------------------------------------------------------
 // one-ring of a vertex (neighbours through unique edges, ascending): everything the edge and Laplacian terms need
 // ------------------------------------------------------------------------------------------------
 struct RingEval {

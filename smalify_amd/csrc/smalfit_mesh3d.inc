@@ -5,11 +5,14 @@
 #include "mesh3d_topology.h"
 
 static_assert(kMeshQueries == kChamQueries && kMeshThreads == kMeshBlock, "smalfit_plan.h sizes the grids of the mesh3d kernels");
+static_assert(sizeof(ScanTri) == 64 && kSurfaceChunk * sizeof(ScanTri) == 32768, "smalfit_plan.h sizes kSurfaceChunk for 64-byte records");
 
 struct smalfit_mesh_objective {
   Mesh3dTables t{};
   void* tables = nullptr;     // one allocation behind t.*
   void* work = nullptr;       // one allocation behind the work buffers below
+  const int* faces = nullptr; // [F][3] as given to create, in the tables' allocation (smalfit_mesh_score scans them)
+  int num_faces = 0;
   int max_meshes = 0, max_points = 0;
   int bx = 0, by = 0, bv = 0, bp = 0;
   float* verts = nullptr;
@@ -19,6 +22,8 @@ struct smalfit_mesh_objective {
         *part_dtr = nullptr;
   // smalfit_fit3d_step only: sampled points, gradients handed to Adam
   float *points = nullptr, *dverts = nullptr, *dtrans = nullptr, *gbetas = nullptr;
+  // smalfit_mesh_score only: the distances when the caller does not ask for them
+  float *vert_dist = nullptr, *point_dist = nullptr;
 };
 
 struct smalfit_mesh_targets {
@@ -94,6 +99,7 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   const size_t o_pr = b.add(h.pairs.data(), h.pairs.size() * sizeof(int));
   const size_t o_io = b.add(h.inc_off.data(), h.inc_off.size() * sizeof(int));
   const size_t o_in = b.add(h.inc.data(), h.inc.size() * sizeof(int));
+  const size_t o_fc = b.add(faces, (size_t)num_faces * 3 * sizeof(int));   // (build_mesh_topology has checked every index)
   unsigned char* base = upload_blob(b, "smalfit_mesh_objective_create");
   if (!base) return 1;
   auto* m = new smalfit_mesh_objective();
@@ -102,6 +108,7 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   m->t.nbr_off = (const int*)(base + o_no); m->t.nbr = (const int*)(base + o_nb);
   m->t.pairs = (const int*)(base + o_pr);
   m->t.inc_off = (const int*)(base + o_io); m->t.inc = (const int*)(base + o_in);
+  m->faces = (const int*)(base + o_fc); m->num_faces = num_faces;
   m->max_meshes = max_meshes; m->max_points = max_points;
   const size_t N = max_meshes, V = h.V, P = std::max(h.P, 1), S = max_points;
   const MeshGrids grids = mesh_grids(max_points, h.V, h.P);   // (bx: the capacity; an evaluation's own follows its num_points)
@@ -123,6 +130,8 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   w.field(m->dverts, N * V * 3);
   w.field(m->dtrans, N * 3);
   w.field(m->gbetas, N * 64);
+  w.field(m->vert_dist, N * V);
+  w.field(m->point_dist, N * S);
   auto bail = [&](const char* what) {
     smalfit_mesh_objective_destroy(m);
     return refused("smalfit_mesh_objective_create", what);
@@ -207,6 +216,32 @@ int smalfit_mesh_targets_sample(smalfit_mesh_targets* t, void* stream, int num_p
                                 unsigned int iteration, float* points) {
   if (refused("smalfit_mesh_targets_sample", mesh_sample_refusal(t && points, num_points))) return 1;
   return launch_mesh_sampler(t, (hipStream_t)stream, num_points, seed, iteration, points);
+}
+
+// ---- how good a fit is: point-to-surface distances both ways, per mesh -------------------------------------------------
+int smalfit_mesh_score(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream, const smalfit_mesh_score_args* a) {
+  if (refused("smalfit_mesh_score", null_argument_refusal(m && t && a))) return 1;
+  if (refused("smalfit_mesh_score", mesh_score_args_refusal(a, MeshScoreFacts{m->max_meshes, m->max_points, t->d.N}))) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  MeshScoreArgs k{};
+  k.N = a->num_meshes; k.V = m->t.V; k.S = a->points ? a->num_points : 0; k.F = m->num_faces;
+  k.verts = a->verts; k.points = a->points; k.faces = m->faces; k.t = t->d;
+  k.vert_dist = a->vert_dist ? a->vert_dist : m->vert_dist;
+  k.point_dist = a->point_dist ? a->point_dist : m->point_dist;
+  k.sums = a->sums; k.within = a->within; k.T = a->num_thresholds;
+  for (int i = 0; i < k.T; ++i) k.thr[i] = a->thresholds[i];
+  const Grid2 g0 = surface_dist_grid(k.V, k.N);
+  mesh3d_surface_dist_kernel<0><<<dim3(g0.x, g0.y), 256, 0, st>>>(k);
+  LAUNCH_OK("mesh3d_surface_dist_kernel<0>");
+  if (k.S > 0) {
+    const Grid2 g1 = surface_dist_grid(k.S, k.N);
+    mesh3d_surface_dist_kernel<1><<<dim3(g1.x, g1.y), 256, 0, st>>>(k);
+    LAUNCH_OK("mesh3d_surface_dist_kernel<1>");
+  }
+  const Grid2 gr = score_reduce_grid(k.N);
+  mesh3d_score_reduce_kernel<<<dim3(gr.x, gr.y), 256, 0, st>>>(k);
+  LAUNCH_OK("mesh3d_score_reduce_kernel");
+  return 0;
 }
 
 // ---- Stage.step in one call ------------------------------------------------------------------------------------------

@@ -297,6 +297,15 @@ inline Grid2 mesh_sample_grid(int S, int N) { return Grid2{elem_blocks(S), N}; }
 constexpr int fit3d_adam_blocks(int count) { return elem_blocks(count); }
 // assemble_kernel with only its per-frame-betas roles (smalfit_lbs_backward_ex, smalfit_fit3d_step): one block per frame
 constexpr int frame_betas_grid(int M) { return M; }
+// smalfit_mesh_score: mesh3d_surface_dist_kernel takes kMeshQueries queries per block, like the chamfer kernels, and stages the
+// scanned triangles kSurfaceChunk records of 64 bytes at a time: 32 KB of LDS, so four blocks (16 waves) share a CU's 160 KB --
+// the scan is vector arithmetic (some 95 instructions per pair against four broadcast LDS reads), and four waves per SIMD
+// are taken to be enough to cover those reads; a larger chunk would save barriers (one pair per 512 triangles already) and cost residency.
+// mesh3d_score_reduce_kernel: one block per (direction, mesh)
+constexpr int kSurfaceChunk = 512;
+constexpr int kScoreDirections = 2;          // 0: fitted vertex -> target surface, 1: target point -> fitted surface
+inline Grid2 surface_dist_grid(int queries, int N) { return Grid2{mesh_query_blocks(queries), N}; }
+constexpr Grid2 score_reduce_grid(int N) { return Grid2{kScoreDirections, N}; }
 
 // ------------------------------------------------------------------------------------------------
 // the mesh objective's entry points: which arguments are refused (the text behind "<entry point>: " or nullptr, the first fault;
@@ -324,6 +333,25 @@ inline const char* mesh_targets_create_refusal(bool given, int num_meshes, const
 inline const char* mesh_sample_refusal(bool given, int num_points) {
   if (!given) return "null argument";
   return num_points > 0 ? nullptr : "num_points must be positive";
+}
+// -> why smalfit_mesh_score refuses the block (the text behind "smalfit_mesh_score: "), or nullptr.  struct_size first: with a
+// block laid out by another header no other field can be trusted
+struct MeshScoreFacts { int max_meshes, max_points, target_meshes; };   // the objective's capacities, the targets' mesh count
+inline const char* mesh_score_args_refusal(const smalfit_mesh_score_args* a, const MeshScoreFacts& f) {
+  if (a->struct_size != (unsigned)sizeof(smalfit_mesh_score_args))
+    return "smalfit_mesh_score_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (a->num_meshes <= 0 || a->num_meshes > f.max_meshes) return "num_meshes exceeds the objective's max_meshes";
+  if (a->num_meshes != f.target_meshes) return "number of target meshes differs from num_meshes";
+  if (!a->verts || !a->sums) return "verts / sums missing";
+  if (!a->points && a->num_points != 0) return "num_points must be 0 without points";
+  if (!a->points && a->point_dist) return "point_dist given without points";
+  if (a->points && (a->num_points <= 0 || a->num_points > f.max_points)) return "points need 1 <= num_points <= max_points";
+  static_assert(SMALFIT_MAX_SCORE_THRESHOLDS == 8, "the message below names the limit");
+  if (a->num_thresholds < 0 || a->num_thresholds > SMALFIT_MAX_SCORE_THRESHOLDS) return "num_thresholds must be 0..8";
+  for (int t = 0; t < a->num_thresholds; ++t)
+    if (!(std::isfinite(a->thresholds[t]) && a->thresholds[t] > 0.f)) return "every threshold must be finite and > 0";
+  if (a->num_thresholds == 0 && a->within) return "within given with num_thresholds = 0";
+  return nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------

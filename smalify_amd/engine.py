@@ -643,6 +643,50 @@ class MeshObjective:
               "smalfit_mesh_objective_eval")
         return o
 
+    def score(self, verts, targets, points=None, thresholds=()):
+        """How good a 3-D fit is, per mesh (smalfit_mesh_score; the definitions are this project's, include/smalfit.h).
+        verts (N,V,3): the fitted vertices (verts of eval / a Stage's forward); targets: the MeshTargets (or a TargetMeshes)
+        the meshes were fitted to, one per mesh; points (N,S,3), S <= max_points: points ON the target surfaces
+        (MeshTargets.sample), or None for one direction only; thresholds: up to 8 distances in the model's units.
+        -> dict of device tensors: vert_dist (N,V) = exact distance from every fitted vertex to the target's surface, with
+        points point_dist (N,S) = from every point to the fitted surface, sums (N,2,3) = per direction sum d, sum d^2, max d
+        (direction 1 zero without points), with thresholds within (N,2,T) int32 = queries with d <= thresholds[t].  No
+        quotient is formed on the device: smalify_amd.metrics.summarise_mesh_score turns these into mean, RMS, Hausdorff,
+        chamfer and F-score."""
+        fn = _lib.resolve(self.lib, "smalfit_mesh_score")
+        targets = getattr(targets, "_dev", targets)
+        if not isinstance(targets, MeshTargets):
+            raise SmalfitError("targets must be the MeshTargets the meshes were fitted to")
+        N, V = int(verts.shape[0]), self.num_verts
+        if tuple(verts.shape) != (N, V, 3):
+            raise SmalfitError("verts must be (num_meshes, %d, 3)" % V)
+        S = 0
+        if points is not None:
+            # the library cannot know the extent or the device of a pointer
+            if not (isinstance(points, torch.Tensor) and points.dim() == 3 and int(points.shape[0]) == N and int(points.shape[2]) == 3):
+                raise SmalfitError("points must be (num_meshes, S, 3)")
+            if points.device != verts.device:
+                raise SmalfitError("points must be on the device of verts (%s)" % verts.device)
+            S = int(points.shape[1])
+        thr = [float(t) for t in thresholds]
+        if len(thr) > _lib.MAX_SCORE_THRESHOLDS:
+            raise SmalfitError("at most %d thresholds" % _lib.MAX_SCORE_THRESHOLDS)
+        a = _lib.MeshScoreArgs()
+        a.num_meshes, a.verts, a.points, a.num_points = N, _ptr(verts), _ptr(points), S
+        a.num_thresholds = len(thr)
+        for i, t in enumerate(thr):
+            a.thresholds[i] = t
+        dev = verts.device
+        out = {"vert_dist": torch.empty(N, V, device=dev), "sums": torch.empty(N, 2, 3, device=dev)}
+        if points is not None:
+            out["point_dist"] = torch.empty(N, S, device=dev)
+        if thr:
+            out["within"] = torch.empty(N, 2, len(thr), dtype=torch.int32, device=dev)
+            a.within = C.c_void_p(out["within"].data_ptr())
+        a.vert_dist, a.point_dist, a.sums = _ptr(out["vert_dist"]), _ptr(out.get("point_dist")), _ptr(out["sums"])
+        check(fn(self.handle, targets.handle, _stream(), C.byref(a)), "smalfit_mesh_score")
+        return out
+
 
 class MeshTargets:
     """Target meshes resident in HBM + the area-weighted point sampler (smalfit_mesh_targets; reference

@@ -9,7 +9,7 @@ from __future__ import annotations
 import argparse
 import os
 
-from .trainer import SMAL3DFitter, SMALParamGroup, Stage, StageManager
+from .trainer import DEFAULT_METRIC_THRESHOLDS, SMAL3DFitter, SMALParamGroup, Stage, StageManager
 from .utils import load_meshes
 
 
@@ -28,6 +28,11 @@ def build_parser():
     parser.add_argument("--nits", type=int, default=100)
     parser.add_argument("--seed", type=int, default=0, help="seed of the target-point sampler")
     parser.add_argument("--no_plots", action="store_true", help="skip the per-stage mesh figures")
+    parser.add_argument("--metrics", action="store_true",
+                        help="score the fit after every stage (exact point-to-surface distances both ways, per mesh) and write "
+                             "metrics.json into results_dir")
+    parser.add_argument("--metric_thresholds", type=float, nargs="+", default=list(DEFAULT_METRIC_THRESHOLDS),
+                        help="distance thresholds of the F-score, in the units of the normalised targets (at most 8)")
     return parser
 
 
@@ -58,7 +63,8 @@ def main(args, model_data=None, smal_data=None):
     else:
         print("No YAML provided. Loading from system args. ")
         manager.add_stage(Stage(scheme=args.scheme, nits=args.nits, lr=args.lr, **stage_kwargs))
-    manager.run(plot=not getattr(args, "no_plots", False))
+    manager.run(plot=not getattr(args, "no_plots", False), metrics=getattr(args, "metrics", False),
+                metric_thresholds=tuple(getattr(args, "metric_thresholds", DEFAULT_METRIC_THRESHOLDS)))
     return manager
 
 

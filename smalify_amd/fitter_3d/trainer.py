@@ -19,19 +19,25 @@ CPU path (on its CUDA path `nn.Parameter(...).to(device)` yields a non-leaf tens
 from __future__ import annotations
 
 import ctypes as C
+import json
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib, config, engine as eng, model_io, runtime
+from .. import _lib, config, engine as eng, metrics as fit_metrics, model_io, runtime
 from ..smal_model.smal_torch import SMAL
 
 default_weights = dict(w_chamfer=1.0, w_edge=1.0, w_normal=0.01, w_laplacian=0.1)     # trainer.py:31
 _WEIGHT_ORDER = ("w_chamfer", "w_edge", "w_normal", "w_laplacian")
 N_SAMPLE_POINTS = 3000                                                                 # trainer.py:209
 _PARAM_ORDER = ("betas", "log_beta_scales", "global_rot", "joint_rot", "trans", "deform_verts")
+# Stage.metrics draws its target points with a key of its own: the counter-based sampler gives the same points for the same
+# (seed, iteration), so a score does not depend on where the fit's sampler stands -- and never repeats one of its draws
+METRICS_SEED_OFFSET = 0x6D657472         # added to the stage's seed when no seed is given
+METRICS_ITERATION = 0xFFFFFFFF
+DEFAULT_METRIC_THRESHOLDS = (0.01, 0.02, 0.05)      # of the target's half-extent: load_meshes scales every target to [-1, 1]
 
 
 class SMAL3DFitter(nn.Module):
@@ -239,6 +245,20 @@ class Stage:
             eng.adam_step(p.data, g, st["m"], st["v"], st["lr"], self._t, beta1=0.9, beta2=0.999, eps=1e-8)
         return loss
 
+    def metrics(self, thresholds=DEFAULT_METRIC_THRESHOLDS, num_points=N_SAMPLE_POINTS, seed=None):
+        """How good the fit is now, per mesh (no counterpart in the reference; definitions: include/smalfit.h).  One forward
+        (smal_3d_fitter()), num_points target points drawn with a seed and iteration of their own, one smalfit_mesh_score call:
+        exact point-to-surface distances both ways.  Changes nothing a later step reads.  -> the dict of
+        smalify_amd.metrics.summarise_mesh_score (host floats; reading it synchronises)"""
+        verts = self.smal_3d_fitter()
+        key = (self.seed + METRICS_SEED_OFFSET if seed is None else int(seed)) & (2 ** 64 - 1)
+        points = self.target_meshes.sample(int(num_points), key, METRICS_ITERATION) if num_points else None
+        objective = _objective_for(self.smal_3d_fitter, max(int(num_points), N_SAMPLE_POINTS))
+        thresholds = tuple(float(t) for t in thresholds)
+        o = objective.score(verts, self.target_meshes, points, thresholds)
+        return fit_metrics.summarise_mesh_score(o["sums"], o.get("within"), num_verts=self.n_verts, num_points=int(num_points),
+                                                thresholds=thresholds)
+
     def _sample_buffer(self):
         """the one (N, 3000, 3) tensor the sampler writes into, allocated once and kept for the life of the stage (the cached
         argument block of step() holds its device pointer)"""
@@ -327,11 +347,27 @@ class StageManager:
         self.out_dir = out_dir
         self.labels = labels
 
-    def run(self, plot=True, progress=True):
+    def run(self, plot=True, progress=True, metrics=False, metric_thresholds=DEFAULT_METRIC_THRESHOLDS):
+        """metrics: score the fit after every stage (Stage.metrics) and write metrics.json beside the .npz files: per stage
+        the thresholds, one row per mesh and the batch figures.  Off by default, and then nothing is computed or written."""
+        report = {}
         for stage in self.stages:
             stage.run(plot=plot, progress=progress)
             stage.save_npz(labels=self.labels)
+            if metrics:
+                summary = stage.metrics(thresholds=metric_thresholds)
+                names = self._mesh_names(stage, summary["batch"]["meshes"])
+                report[stage.name] = fit_metrics.mesh_score_report(summary, metric_thresholds, names)
+                print("%s: %s" % (stage.name, fit_metrics.mesh_score_line(summary, metric_thresholds)))
+        if metrics:
+            os.makedirs(self.out_dir, exist_ok=True)
+            with open(os.path.join(self.out_dir, "metrics.json"), "w") as fh:
+                json.dump(dict(stages=report), fh, indent=1)
         self.plot_losses()
+
+    def _mesh_names(self, stage, count):
+        names = [str(n) for n in (self.labels if self.labels is not None else stage.mesh_names or [])]
+        return names if len(names) == count and len(set(names)) == count else ["mesh_%d" % i for i in range(count)]
 
     def plot_losses(self, out_src="losses"):
         """semilog plot of the total loss over all stages (trainer.py:299-319)"""

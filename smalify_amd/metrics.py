@@ -86,6 +86,72 @@ def summarise(counts, dist=None, visibility=None, thresholds=()):
     return out
 
 
+def summarise_mesh_score(sums, within=None, *, num_verts, num_points=0, thresholds=()):
+    """From MeshObjective.score (smalfit_mesh_score) to the figures a 3-D fit is reported in, float64, per mesh.
+    sums (N,2,3) = per direction [sum d, sum d^2, max d] (0: fitted vertex -> target surface over num_verts vertices, 1: target
+    point -> fitted surface over num_points points); within (N,2,T) = queries with d <= thresholds[t], or None.  Device
+    tensors or arrays.  num_points = 0: direction 1 was not asked for -- every figure that needs it is nan.  -> dict:
+        vert_mean, vert_rms, vert_max, point_mean, point_rms, point_max (N,)
+        hausdorff (N,)    the larger of the two maxima
+        chamfer_l2 (N,)   the sum of the two mean squared distances
+        precision (N,T)   share of the fitted vertices within t;  recall (N,T)  share of the target points within t
+        fscore (N,T)      their harmonic mean, 0 when both are 0
+        batch: {meshes, the means over the meshes of the above (rms: root of the mean square; max, hausdorff: the maximum),
+                worst_mesh: the index of the largest hausdorff (of vert_max for one direction)}"""
+    s = _host(sums).astype(np.float64).reshape(-1, 2, 3)
+    N, T = len(s), len(thresholds)
+    w = np.zeros((N, 2, T), np.int64) if within is None else _host(within).astype(np.int64).reshape(N, 2, T)
+    counts = np.array([float(num_verts), float(num_points)])
+    out = {}
+    for d, name in enumerate(("vert", "point")):
+        out[name + "_mean"] = _ratio(s[:, d, 0], counts[d])
+        out[name + "_rms"] = np.sqrt(_ratio(s[:, d, 1], counts[d]))
+        out[name + "_max"] = s[:, d, 2] if counts[d] > 0 else np.full(N, np.nan)
+    out["hausdorff"] = np.maximum(out["vert_max"], out["point_max"])          # nan without the second direction
+    out["chamfer_l2"] = _ratio(s[:, 0, 1], counts[0]) + _ratio(s[:, 1, 1], counts[1])
+    prec, rec = _ratio(w[:, 0], counts[0]), _ratio(w[:, 1], counts[1])
+    out["precision"], out["recall"] = prec, rec
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["fscore"] = np.where(prec + rec > 0, 2.0 * prec * rec / np.where(prec + rec > 0, prec + rec, 1.0),
+                                 np.where(np.isnan(prec + rec), np.nan, 0.0))
+
+    def mean(x):
+        return x.mean(0) if N else np.full(x.shape[1:], np.nan)
+    batch = dict(meshes=N)
+    for name in ("vert", "point"):
+        batch[name + "_mean"] = mean(out[name + "_mean"])
+        batch[name + "_rms"] = np.sqrt(mean(out[name + "_rms"] ** 2))
+        batch[name + "_max"] = out[name + "_max"].max() if N else np.nan
+    batch["hausdorff"] = out["hausdorff"].max() if N else np.nan
+    batch["chamfer_l2"] = mean(out["chamfer_l2"])
+    for k in ("precision", "recall", "fscore"):
+        batch[k] = mean(out[k])
+    key = out["hausdorff"] if num_points > 0 else out["vert_max"]
+    batch["worst_mesh"] = int(np.argmax(key)) if N else -1
+    out["batch"] = batch
+    return out
+
+
+_MESH_ROW_KEYS = ("vert_mean", "vert_rms", "vert_max", "point_mean", "point_rms", "point_max", "hausdorff", "chamfer_l2",
+                  "precision", "recall", "fscore")
+
+
+def mesh_score_report(summary, thresholds, names):
+    """the document fitter_3d writes as metrics.json: thresholds, one row per mesh keyed by its name, the batch figures"""
+    meshes = {name: {k: summary[k][i] for k in _MESH_ROW_KEYS} for i, name in enumerate(names)}
+    return _plain(dict(thresholds=[float(t) for t in thresholds], meshes=meshes, batch=summary["batch"]))
+
+
+def mesh_score_line(summary, thresholds):
+    """one line for a log: the batch figures"""
+    b = summary["batch"]
+    text = "%d mesh(es): vertex->target mean %.5f max %.5f" % (b["meshes"], b["vert_mean"], b["vert_max"])
+    if not np.isnan(b["point_mean"]):
+        text += "  target->surface mean %.5f max %.5f  Hausdorff %.5f" % (b["point_mean"], b["point_max"], b["hausdorff"])
+        text += "".join("  F@%g %.4f" % (float(t), f) for t, f in zip(thresholds, np.atleast_1d(b["fscore"])))
+    return text
+
+
 def _plain(x):
     """numpy -> what json writes; nan stays nan (json's NaN literal, which json.load reads back)"""
     if isinstance(x, dict):
