@@ -39,7 +39,8 @@ typedef struct smalfit_engine smalfit_engine;
  * 5 = smalfit_engine_set_option; 6 = smalfit_fit_args.subject_frames / losses_per_frame (a batch of independent images,
  * each with its own shape; one row of loss terms per frame).  Added within version 6, no struct of it changing its layout:
  * smalfit_fit_eval_windows (smalfit_window_rows); smalfit_fit_metrics (smalfit_metrics_args: silhouette IoU counts and PCK
- * per frame); smalfit_mesh_score (smalfit_mesh_score_args: point-to-surface distances both ways, per mesh). */
+ * per frame); smalfit_mesh_score (smalfit_mesh_score_args: point-to-surface distances both ways, per mesh);
+ * smalfit_mesh_surface_eval / smalfit_fit3d_step_surface (smalfit_surface_term_args: the same distances as a term to descend on). */
 #define SMALFIT_ABI_VERSION 6
 int smalfit_version(void);
 const char* smalfit_last_error(void);
@@ -501,6 +502,51 @@ typedef struct smalfit_mesh_score_args {
 int smalfit_mesh_score(smalfit_mesh_objective* objective, smalfit_mesh_targets* targets, void* stream,
                        const smalfit_mesh_score_args* args);
 
+/* ---- an opt-in point-to-surface term, both ways, with its gradient -----------------------------------------------------
+ * No counterpart in the reference (PyTorch3D grew point_mesh_face_distance after the 0.2.5 it pins): THIS PROJECT'S definition.
+ * With d(p, T) the distance of smalfit_mesh_score above from a point to a closed triangle and d(p, M) its minimum over the
+ * faces of the mesh M:
+ *   L_ps = 1/(N S) sum_n sum_s d^2(points[n][s], fitted mesh n)      "point -> surface"
+ *   L_vs = 1/(N V) sum_n sum_v d^2(verts[n][v],  target mesh n)      "vertex -> surface"
+ *   term = w_point_surface L_ps + w_vert_surface L_vs                 (a weight <= 0 skips its direction: its loss reads 0)
+ * the normalisation of the chamfer term.  Unlike that term it is zero for a perfect fit.
+ *   nearest face   the lowest face index among equal float32 d^2.  The closest point q is the one of the candidate that
+ *                  reaches the minimum, the first in the order (segment ab, bc, ca, plane): a segment's clamped parameter t
+ *                  gives the barycentrics (1 - t, t, 0) on that edge; the plane gives (s1, s2, s0) / (s0 + s1 + s2) with the
+ *                  three edge functions of smalfit_mesh_score (their sum is |n|^2 up to rounding: over the sum, the weights add
+ *                  up to 1).  The residual r = p - q is formed from the winner's own intermediates.
+ *   gradient       by the envelope theorem, nothing is differentiated through the barycentrics:
+ *                    vertex -> surface:  d term / d verts[n][v] += w_vert_surface 2/(N V) r
+ *                    point -> surface:   the corners i of the winning fitted face each receive -w_point_surface 2/(N S) b_i r
+ *                  A degenerate triangle remains its three segments.
+ * Every minimum is unique (distance, then face index) and every sum has a fixed order: the same call gives the same bits.
+ * Cost: linear in the scanned faces (V F_target + S F pair tests per mesh), no acceleration structure.
+ * A refused block launches nothing and leaves every output alone.  The call uses the objective's work buffers. */
+typedef struct smalfit_surface_term_args {
+  unsigned struct_size;       /* sizeof(smalfit_surface_term_args) of the caller's header; checked before any other field */
+  int num_meshes;             /* N <= the objective's max_meshes (in a step: the step's num_meshes) */
+  float w_point_surface;      /* <= 0: the direction is skipped, its targets' points are not read */
+  float w_vert_surface;       /* <= 0: skipped; > 0 needs the targets, one per mesh */
+  const float* verts;         /* (N,V,3) fitted vertices; must be NULL in a step (its composed vertices are used) */
+  const float* points;        /* (N,S,3) points on the target surfaces; must be NULL in a step (its own points are used) */
+  int num_points;             /* S <= the objective's max_points; not read in a step */
+  float* losses;              /* (3, device): L_ps, L_vs, the weighted term */
+  float* rows;                /* optional (N,2): per mesh sum d^2 of the points | of the vertices, not normalised */
+  float* dverts;              /* optional (N,V,3): d term / d verts, written, not accumulated */
+  float* dtrans;              /* optional (N,3): its sum over the vertices of a mesh */
+  int* point_face;            /* optional (N,S): face of the fitted topology nearest to every point */
+  float* point_bary;          /* optional (N,S,3), only with point_face: where on it */
+  int* vert_face;             /* optional (N,V): face of TARGET mesh n (index within that mesh) nearest to every vertex */
+  float* vert_bary;           /* optional (N,V,3), only with vert_face */
+  float* point_residual;      /* optional (N,S,3), only with point_face: r = point - (its closest point), as the gradient uses it */
+  float* vert_residual;       /* optional (N,V,3), only with vert_face */
+  float* step_total;          /* optional (1), a step only: args->losses[4] + the weighted term, what the step descends on;
+                                 smalfit_mesh_surface_eval does not write it */
+} smalfit_surface_term_args;
+/* the term alone.  `targets` may be NULL when w_vert_surface <= 0.  The correspondences of a skipped direction are not written */
+int smalfit_mesh_surface_eval(smalfit_mesh_objective* objective, smalfit_mesh_targets* targets, void* stream,
+                              const smalfit_surface_term_args* args);
+
 /* ---- Stage.step in one call ------------------------------------------------------------------------------------
  * replaces: one iteration of Stage.run                      reference fitter_3d/trainer.py:229-241,257-262
  *   new_src_verts = smal_3d_fitter(); loss = forward(...); loss.backward(); optimizer.step()
@@ -536,6 +582,15 @@ typedef struct smalfit_fit3d_args {
 /* `targets` may be NULL when args->points is given or w_chamfer <= 0 */
 int smalfit_fit3d_step(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
                        void* stream, const smalfit_fit3d_args* args);
+/* smalfit_fit3d_step with the surface term added to what the step descends on.  surface == NULL, or both of its weights <= 0:
+ * exactly smalfit_fit3d_step, launch for launch and bit for bit (which IS this call with surface = NULL).  Otherwise the term is
+ * evaluated at the step's composed vertices against the step's own points -- sampled or taken from the caller as before, also
+ * when w_chamfer <= 0 -- and its vertex gradient is added to the step's (one float32 addition per coordinate, as a caller of
+ * smalfit_mesh_surface_eval would add it) before the SMAL adjoint and Adam read it, so trans, deform_verts and the SMAL
+ * parameters all descend on the sum.  args->losses keeps its five entries WITHOUT the term; surface->losses (3) carries the
+ * term, and the caller adds the two (or asks for surface->step_total).  `targets` is needed when w_vert_surface > 0 or points are to be sampled. */
+int smalfit_fit3d_step_surface(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
+                               void* stream, const smalfit_fit3d_args* args, const smalfit_surface_term_args* surface);
 
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137

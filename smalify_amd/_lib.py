@@ -90,6 +90,19 @@ class MeshScoreArgs(C.Structure):
         self.struct_size = C.sizeof(MeshScoreArgs)
 
 
+class SurfaceTermArgs(C.Structure):
+    """smalfit_surface_term_args: the point-to-surface term both ways (smalfit_mesh_surface_eval, smalfit_fit3d_step_surface)"""
+    _fields_ = [("struct_size", C.c_uint), ("num_meshes", C.c_int), ("w_point_surface", C.c_float), ("w_vert_surface", C.c_float),
+                ("verts", C.c_void_p), ("points", C.c_void_p), ("num_points", C.c_int), ("losses", C.c_void_p),
+                ("rows", C.c_void_p), ("dverts", C.c_void_p), ("dtrans", C.c_void_p), ("point_face", C.c_void_p),
+                ("point_bary", C.c_void_p), ("vert_face", C.c_void_p), ("vert_bary", C.c_void_p), ("point_residual", C.c_void_p),
+                ("vert_residual", C.c_void_p), ("step_total", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(SurfaceTermArgs)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -191,11 +204,14 @@ SIGNATURES = {
     "smalfit_mesh_targets_sample": (_I, [_VP, _VP, _I, C.c_ulonglong, C.c_uint, _VP]),
     "smalfit_mesh_score": (_I, [_VP, _VP, _VP, C.POINTER(MeshScoreArgs)]),
     "smalfit_fit3d_step": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs)]),
+    "smalfit_mesh_surface_eval": (_I, [_VP, _VP, _VP, C.POINTER(SurfaceTermArgs)]),
+    "smalfit_fit3d_step_surface": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
 # built before them loads, and resolve() names the symbol when one is asked for
-LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "smalfit_mesh_score"])
+LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "smalfit_mesh_score", "smalfit_mesh_surface_eval",
+                          "smalfit_fit3d_step_surface"])
 
 
 class SmalfitError(RuntimeError):

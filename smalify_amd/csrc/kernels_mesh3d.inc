@@ -404,6 +404,256 @@ __global__ __launch_bounds__(256) void mesh3d_score_reduce_kernel(MeshScoreArgs 
         wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] + wcnt[3][threadIdx.x];
 }
 
+// ---- the surface term: the same distances as a term to descend on, every iteration -------------------------------------------
+// One memset of the keys, then per direction mesh3d_surface_near<ROLE> (the scan, split over the triangles: grid z) and
+// mesh3d_surface_hit<ROLE> (one query per thread: the winner's barycentrics and residual, per-block sums of d^2), then
+// mesh3d_surface_grad (one vertex per lane: its own residual + the hits of the points that chose a face it is a corner of,
+// gathered in a fixed order -- no scatter, no floating-point atomics) and mesh3d_surface_reduce (one block).  The slices of a
+// query meet in a 64-bit key, d^2's bits high and the face index low: d^2 >= 0, so the order of the bits is the order of the
+// values, and the integer minimum is the lowest face among equal distances whatever order the blocks run in.
+struct SurfaceTermArgs {
+  int N, V, S, F;            // meshes, fitted vertices, points per mesh, faces of the fitted topology
+  const float* verts;        // [N][V][3]
+  const float* points;       // [N][S][3] (read when w_ps > 0)
+  const int* faces;          // [F][3] of the fitted topology
+  MeshTargetsDev t;          // (read when w_vs > 0)
+  const ScanTri* target_tris;// packed [sum F]: the targets' staged records, built once at smalfit_mesh_targets_create
+  float w_ps, w_vs;          // both clamped at 0
+  unsigned long long* keys_v;// [N][V]
+  unsigned long long* keys_p;// [N][S]
+  SurfaceHit* hits;          // [N][S]
+  float* res_v;              // [N][V][3] residual of every vertex
+  int* point_face; float* point_bary; int* vert_face; float* vert_bary;   // optional
+  float* point_residual; float* vert_residual;                            // optional
+  float* part_ps;            // [N][hp] per-block sums of d^2, hp = blocks of mesh3d_surface_hit<1>
+  float* part_vs;            // [N][hv]
+  float* part_dtr;           // [N][gv][3]
+  int hp, hv, gv;
+  float* acc_dverts;         // [N][V][3] or null: the step's d verts, the term's gradient is added to it ...
+  float* acc_planar;         // [N][3][Vp] or null: ... and to its planar copy for the LBS adjoint ...
+  float* acc_dtrans;         // [N][3] or null: ... and its sum over a mesh to the step's d trans
+  int Vp;
+  float* dverts;             // [N][V][3] or null: written
+  float* dtrans;             // [N][3] or null
+  float* losses;             // [3]
+  float* rows;               // [N][2] or null
+  const float* step_losses;  // [5] of the step this term rides on, or null
+  float* step_total;         // [1] or null: step_losses[4] + the weighted term
+};
+
+// ROLE 0: queries = fitted vertices, scanned = the staged records of target mesh n.  ROLE 1: queries = the points, scanned = the
+// triangles of the fitted mesh n, staged from its vertices as in mesh3d_surface_dist_kernel.  Block (x, n, z) scans slice z
+template <int ROLE>
+__global__ __launch_bounds__(256) void mesh3d_surface_near_kernel(SurfaceTermArgs a) {
+  __shared__ ScanTri st[kSurfaceChunk];
+  __shared__ float sd[4][kChamQueries];
+  __shared__ int si[4][kChamQueries];
+  const int n = blockIdx.y, lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nq = ROLE == 0 ? a.V : a.S;
+  const float* q = ROLE == 0 ? a.verts + (size_t)n * a.V * 3 : a.points + (size_t)n * a.S * 3;
+  const int f0 = ROLE == 0 ? a.t.foff[n] : 0;
+  const int nf = ROLE == 0 ? a.t.foff[n + 1] - f0 : a.F;
+  const int span = surface_slice_span(nf, (int)gridDim.z);
+  const int sb = (int)blockIdx.z * span;
+  if (sb >= nf) return;                              // (block-uniform, before any barrier) a smaller mesh of a ragged batch
+  const int se = min(sb + span, nf);
+  const int* faces = a.faces;
+  const float* corners = a.verts + (size_t)n * a.V * 3;
+  const float4* recs = reinterpret_cast<const float4*>(a.target_tris + (ROLE == 0 ? f0 : 0));
+  const int qi = blockIdx.x * kChamQueries + lane;
+  const bool active = qi < nq;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (active) {
+    qx = q[3 * (size_t)qi];
+    qy = q[3 * (size_t)qi + 1];
+    qz = q[3 * (size_t)qi + 2];
+  }
+  float best = INFINITY;
+  int bidx = 0x7fffffff;
+  for (int base = sb; base < se; base += kSurfaceChunk) {
+    const int cnt = min(kSurfaceChunk, se - base);
+    __syncthreads();
+    if (ROLE == 0) {
+      float4* dst = reinterpret_cast<float4*>(st);
+      for (int i = threadIdx.x; i < 4 * cnt; i += 256) dst[i] = recs[4 * (size_t)base + i];
+    } else {
+      for (int i = threadIdx.x; i < cnt; i += 256) {
+        const int* fc = faces + 3 * (size_t)(base + i);
+        st[i] = make_scan_tri(corners + 3 * (size_t)fc[0], corners + 3 * (size_t)fc[1], corners + 3 * (size_t)fc[2]);
+      }
+    }
+    __syncthreads();
+    const int per = (cnt + 3) >> 2;
+    const int b = min(w * per, cnt), e = min(b + per, cnt);
+    surface_scan_nearest(qx, qy, qz, st, b, e, base, best, bidx);
+  }
+  sd[w][lane] = best;
+  si[w][lane] = bidx;
+  __syncthreads();
+  if (w != 0) return;
+#pragma unroll
+  for (int s = 1; s < 4; ++s) nearest_merge(best, bidx, sd[s][lane], si[s][lane]);
+  if (active && bidx != 0x7fffffff) {                // (no finite distance -- NaN input: the key stays all ones)
+    unsigned long long* keys = ROLE == 0 ? a.keys_v + (size_t)n * a.V : a.keys_p + (size_t)n * a.S;
+    atomicMin(&keys[qi], ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bidx);
+  }
+}
+
+// one query per thread: the closest point on the face its key names
+template <int ROLE>
+__global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceTermArgs a) {
+  __shared__ float red[16];
+  const int n = blockIdx.y;
+  const int nq = ROLE == 0 ? a.V : a.S;
+  const int qi = blockIdx.x * kMeshBlock + threadIdx.x;
+  float d2 = 0.f;
+  if (qi < nq) {
+    const size_t o = (size_t)n * nq + qi;
+    const float* q = (ROLE == 0 ? a.verts : a.points) + 3 * o;
+    const unsigned long long key = (ROLE == 0 ? a.keys_v : a.keys_p)[o];
+    const int f0 = ROLE == 0 ? a.t.foff[n] : 0;
+    const int nf = ROLE == 0 ? a.t.foff[n + 1] - f0 : a.F;
+    int face = (int)(unsigned)(key & 0xFFFFFFFFull);
+    if (key == ~0ull || face >= nf) face = 0;        // no finite distance: stay in bounds
+    const int* fc = (ROLE == 0 ? a.t.faces + 3 * (size_t)f0 : a.faces) + 3 * (size_t)face;
+    ScanTri tri;
+    if (ROLE == 0) {
+      tri = a.target_tris[f0 + face];
+    } else {
+      const float* corners = a.verts + (size_t)n * a.V * 3;
+      tri = make_scan_tri(corners + 3 * (size_t)fc[0], corners + 3 * (size_t)fc[1], corners + 3 * (size_t)fc[2]);
+    }
+    const TriHit h = point_scan_tri_closest(q[0], q[1], q[2], tri);
+    d2 = key == ~0ull ? h.d2 : __uint_as_float((unsigned)(key >> 32));   // the scan's own bits
+    if (ROLE == 0) {
+      a.res_v[3 * o] = h.r[0];
+      a.res_v[3 * o + 1] = h.r[1];
+      a.res_v[3 * o + 2] = h.r[2];
+    } else {
+      SurfaceHit s;
+      s.c0 = fc[0]; s.c1 = fc[1]; s.c2 = fc[2];
+      s.b0 = h.b[0]; s.b1 = h.b[1]; s.b2 = h.b[2];
+      s.rx = h.r[0]; s.ry = h.r[1]; s.rz = h.r[2];
+      s.pad0 = s.pad1 = s.pad2 = 0.f;
+      a.hits[o] = s;
+    }
+    int* of = ROLE == 0 ? a.vert_face : a.point_face;
+    float* ob = ROLE == 0 ? a.vert_bary : a.point_bary;
+    if (of != nullptr) of[o] = face;
+    if (ob != nullptr) {
+      ob[3 * o] = h.b[0];
+      ob[3 * o + 1] = h.b[1];
+      ob[3 * o + 2] = h.b[2];
+    }
+    float* orr = ROLE == 0 ? a.vert_residual : a.point_residual;
+    if (orr != nullptr) {
+      orr[3 * o] = h.r[0];
+      orr[3 * o + 1] = h.r[1];
+      orr[3 * o + 2] = h.r[2];
+    }
+  }
+  const float tot = block_sum(d2, red);
+  if (threadIdx.x == 0) (ROLE == 0 ? a.part_vs : a.part_ps)[(size_t)n * gridDim.x + blockIdx.x] = tot;
+}
+
+// the term's gradient of one vertex in one thread: 2 w_vs / (N V) r_v  -  2 w_ps / (N S) sum over the points whose face has
+// this vertex as corner i of b_i r.  64 vertices per block, the staged hits split over its kSurfaceGradWaves waves (as
+// mesh3d_chamfer_kernel<1> gathers by owner over 4); the waves' partial sums are added in wave order
+constexpr int kGradThreads = 64 * kSurfaceGradWaves;
+__global__ __launch_bounds__(kGradThreads) void mesh3d_surface_grad_kernel(SurfaceTermArgs a) {
+  __shared__ SurfaceHit sh[kSurfaceHitChunk];
+  __shared__ float sg[kSurfaceGradWaves][kChamQueries][3];
+  const int n = blockIdx.y, lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int v = blockIdx.x * kChamQueries + lane;
+  const bool active = v < a.V;
+  float g[3] = {0.f, 0.f, 0.f};
+  if (a.w_ps > 0.f) {
+    const float4* src = reinterpret_cast<const float4*>(a.hits + (size_t)n * a.S);
+    for (int base = 0; base < a.S; base += kSurfaceHitChunk) {
+      const int cnt = min(kSurfaceHitChunk, a.S - base);
+      __syncthreads();
+      float4* dst = reinterpret_cast<float4*>(sh);
+      for (int i = threadIdx.x; i < 3 * cnt; i += kGradThreads) dst[i] = src[3 * (size_t)base + i];
+      __syncthreads();
+      const int per = (cnt + kSurfaceGradWaves - 1) / kSurfaceGradWaves;
+      const int b = min(w * per, cnt), e = min(b + per, cnt);
+      surface_hit_gather(sh, b, e, active ? v : -1, g);
+    }
+  }
+  sg[w][lane][0] = g[0];
+  sg[w][lane][1] = g[1];
+  sg[w][lane][2] = g[2];
+  __syncthreads();
+  if (w != 0) return;
+  const float cps = a.w_ps * 2.0f / ((float)a.S * (float)a.N);
+  const float cvs = a.w_vs * 2.0f / ((float)a.V * (float)a.N);
+  const size_t o = ((size_t)n * a.V + (active ? v : 0)) * 3;
+  float out[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float gp = sg[0][lane][k];
+#pragma unroll
+    for (int s = 1; s < kSurfaceGradWaves; ++s) gp += sg[s][lane][k];
+    const float rv = (active && a.w_vs > 0.f) ? a.res_v[o + k] : 0.f;
+    out[k] = active ? cvs * rv - cps * gp : 0.f;
+  }
+  if (active) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (a.acc_dverts != nullptr) a.acc_dverts[o + k] += out[k];     // (this thread alone writes the vertex)
+      if (a.acc_planar != nullptr) a.acc_planar[((size_t)n * 3 + k) * a.Vp + v] += out[k];
+      if (a.dverts != nullptr) a.dverts[o + k] = out[k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float t = wave_sum(out[k]);
+    if (lane == 0) a.part_dtr[((size_t)n * a.gv + blockIdx.x) * 3 + k] = t;
+  }
+}
+
+// one block: per mesh the sums of d^2, the two means and the weighted term (every sum in a fixed order); d term / d trans
+__global__ __launch_bounds__(256) void mesh3d_surface_reduce_kernel(SurfaceTermArgs a) {
+  __shared__ float red[16];
+  // a mesh per thread: its few per-block sums one after the other; then the meshes thread-strided and the tree of block_sum
+  float tp = 0.f, tv = 0.f;
+  for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
+    float sp = 0.f, sv = 0.f;
+    if (a.w_ps > 0.f)
+      for (int b = 0; b < a.hp; ++b) sp += a.part_ps[(size_t)n * a.hp + b];
+    if (a.w_vs > 0.f)
+      for (int b = 0; b < a.hv; ++b) sv += a.part_vs[(size_t)n * a.hv + b];
+    tp += sp;
+    tv += sv;
+    if (a.rows != nullptr) {
+      a.rows[2 * n] = sp;
+      a.rows[2 * n + 1] = sv;
+    }
+  }
+  tp = block_sum(tp, red);
+  tv = block_sum(tv, red);
+  if (threadIdx.x == 0) {
+    const float lps = a.w_ps > 0.f ? tp / ((float)a.S * (float)a.N) : 0.f;
+    const float lvs = a.w_vs > 0.f ? tv / ((float)a.V * (float)a.N) : 0.f;
+    a.losses[0] = lps;
+    a.losses[1] = lvs;
+    const float term = a.w_ps * lps + a.w_vs * lvs;
+    a.losses[2] = term;
+    if (a.step_total != nullptr && a.step_losses != nullptr) *a.step_total = a.step_losses[4] + term;   // (mesh3d_reduce_kernel ran before)
+  }
+  if (a.dtrans != nullptr || a.acc_dtrans != nullptr) {
+    for (int o = threadIdx.x; o < 3 * a.N; o += blockDim.x) {
+      const int n = o / 3, k = o % 3;
+      float s = 0.f;
+      for (int b = 0; b < a.gv; ++b) s += a.part_dtr[((size_t)n * a.gv + b) * 3 + k];
+      if (a.dtrans != nullptr) a.dtrans[o] = s;
+      if (a.acc_dtrans != nullptr) a.acc_dtrans[o] += s;
+    }
+  }
+}
+
 // ---- Adam on all trained parameters of a Stage.step in one launch ----------------------------------------------------
 // torch.optim.Adam (adam_update) over the trained parameters, one launch (Fit3dAdamArgs: smalfit_plan.h, beside plan_fit3d, which
 // sizes its segments)

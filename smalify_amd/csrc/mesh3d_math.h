@@ -188,6 +188,101 @@ SMALFIT_HD float surface_scan(float px, float py, float pz, const ScanTri* t, in
   return best;
 }
 
+// The same distance with WHERE on the triangle it is reached (the surface term of smalfit_mesh_surface_eval /
+// smalfit_fit3d_step_surface; worded in include/smalfit.h).  d2 is formed by the expressions of point_scan_tri_dist2 in their
+// order, so the two agree bit for bit; the winner is the first of (ab, bc, ca, plane) to reach that minimum.  Its barycentrics
+// over (a, b, c): a segment's clamped parameter t gives (1 - t, t, 0) on that edge; the plane gives (s1, s2, s0) over their own
+// sum (= |n|^2 up to rounding: divided by the sum, the weights add up to 1 on a sliver too).  The residual r = p - q comes from
+// the winner's own intermediates, d - t e or (h / |n|^2) n: no closest point is subtracted from p.
+struct TriHit {
+  float d2;
+  float b[3];   // weights of the corners a, b, c
+  float r[3];   // p - (closest point)
+};
+
+SMALFIT_HD TriHit point_scan_tri_closest(float px, float py, float pz, const ScanTri& t) {
+  const float pax = px - t.ax, pay = py - t.ay, paz = pz - t.az;
+  const float pbx = px - t.bx, pby = py - t.by, pbz = pz - t.bz;
+  const float pcx = px - t.cx, pcy = py - t.cy, pcz = pz - t.cz;
+  const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
+  const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
+  const float cax = t.ax - t.cx, cay = t.ay - t.cy, caz = t.az - t.cz;
+  // the three segments: parameter, residual d - t e, its squared length (the expressions of point_segment_dist2)
+  const float t0 = fminf(fmaxf(dot3(pax, pay, paz, abx, aby, abz) * t.inv_ab, 0.f), 1.0f);
+  const float r0x = fmaf(-t0, abx, pax), r0y = fmaf(-t0, aby, pay), r0z = fmaf(-t0, abz, paz);
+  const float d0 = dot3(r0x, r0y, r0z, r0x, r0y, r0z);
+  const float t1 = fminf(fmaxf(dot3(pbx, pby, pbz, bcx, bcy, bcz) * t.inv_bc, 0.f), 1.0f);
+  const float r1x = fmaf(-t1, bcx, pbx), r1y = fmaf(-t1, bcy, pby), r1z = fmaf(-t1, bcz, pbz);
+  const float d1 = dot3(r1x, r1y, r1z, r1x, r1y, r1z);
+  const float t2 = fminf(fmaxf(dot3(pcx, pcy, pcz, cax, cay, caz) * t.inv_ca, 0.f), 1.0f);
+  const float r2x = fmaf(-t2, cax, pcx), r2y = fmaf(-t2, cay, pcy), r2z = fmaf(-t2, caz, pcz);
+  const float d2c = dot3(r2x, r2y, r2z, r2x, r2y, r2z);
+  const float dseg = fminf(fminf(d0, d1), d2c);
+  const float s0 = edge_function(abx, aby, abz, pax, pay, paz, t.nx, t.ny, t.nz);
+  const float s1 = edge_function(bcx, bcy, bcz, pbx, pby, pbz, t.nx, t.ny, t.nz);
+  const float s2 = edge_function(cax, cay, caz, pcx, pcy, pcz, t.nx, t.ny, t.nz);
+  const bool inside = (t.inv_nn > 0.f) & (s0 >= 0.f) & (s1 >= 0.f) & (s2 >= 0.f);
+  const float h = dot3(pax, pay, paz, t.nx, t.ny, t.nz);
+  const float dp = h * h * t.inv_nn;
+  // the winner: the first of (ab, bc, ca, plane) to reach the minimum (selects, no branch)
+  const bool k1 = d1 < d0;
+  const float sel1 = k1 ? d1 : d0;
+  const bool k2 = d2c < sel1;
+  const float sel2 = k2 ? d2c : sel1;
+  const float ssum = s0 + s1 + s2;
+  const bool kp = inside & (dp < sel2) & (ssum > 0.f);
+  const float is = kp ? 1.0f / ssum : 0.f, k = h * t.inv_nn;
+  TriHit o;
+  o.d2 = inside ? fminf(dp, dseg) : dseg;
+  o.b[0] = kp ? s1 * is : (k2 ? t2 : (k1 ? 0.f : 1.0f - t0));
+  o.b[1] = kp ? s2 * is : (k2 ? 0.f : (k1 ? 1.0f - t1 : t0));
+  o.b[2] = kp ? s0 * is : (k2 ? 1.0f - t2 : (k1 ? t1 : 0.f));
+  o.r[0] = kp ? k * t.nx : (k2 ? r2x : (k1 ? r1x : r0x));
+  o.r[1] = kp ? k * t.ny : (k2 ? r2y : (k1 ? r1y : r0y));
+  o.r[2] = kp ? k * t.nz : (k2 ? r2z : (k1 ? r1z : r0z));
+  return o;
+}
+
+SMALFIT_HD TriHit point_triangle_closest(const float* p, const float* a, const float* b, const float* c) {
+  return point_scan_tri_closest(p[0], p[1], p[2], make_scan_tri(a, b, c));
+}
+
+// nearest of the staged triangles t[begin .. end) WITH its index: strict '<' over ascending indices keeps the lowest index among
+// equal distances; disjoint ranges combine through nearest_merge or an integer minimum of (distance bits, index) keys
+SMALFIT_HD void surface_scan_nearest(float px, float py, float pz, const ScanTri* t, int begin, int end, int index_base,
+                                     float& best, int& best_idx) {
+#pragma unroll 2
+  for (int j = begin; j < end; ++j) {
+    const float d2 = point_scan_tri_dist2(px, py, pz, t[j]);
+    if (d2 < best) {
+      best = d2;
+      best_idx = index_base + j;
+    }
+  }
+}
+
+// what a point -> surface query leaves for the vertices of the face it chose (48 bytes: three 16-byte rows, broadcast LDS reads
+// in mesh3d_surface_grad_kernel): every corner i receives -b_i r
+struct alignas(16) SurfaceHit {
+  int c0, c1, c2;      // vertex ids of the winning face's corners
+  float b0;
+  float b1, b2, rx, ry;
+  float rz, pad0, pad1, pad2;
+};
+
+// the share of vertex `self` in sum_j -b_i(j) r(j) over the staged hits h[begin .. end), in index order.  A face has three
+// distinct corners, so at most one of the three weights is taken: the selection is exact
+SMALFIT_HD void surface_hit_gather(const SurfaceHit* h, int begin, int end, int self, float g[3]) {
+#pragma unroll 4
+  for (int j = begin; j < end; ++j) {
+    const SurfaceHit s = h[j];
+    const float w = (s.c0 == self ? s.b0 : 0.f) + (s.c1 == self ? s.b1 : 0.f) + (s.c2 == self ? s.b2 : 0.f);
+    g[0] = fmaf(w, s.rx, g[0]);
+    g[1] = fmaf(w, s.ry, g[1]);
+    g[2] = fmaf(w, s.rz, g[2]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // one-ring of a vertex (neighbours through unique edges, ascending): everything the edge and Laplacian terms need
 // ------------------------------------------------------------------------------------------------

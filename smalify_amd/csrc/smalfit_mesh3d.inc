@@ -24,12 +24,66 @@ struct smalfit_mesh_objective {
   float *points = nullptr, *dverts = nullptr, *dtrans = nullptr, *gbetas = nullptr;
   // smalfit_mesh_score only: the distances when the caller does not ask for them
   float *vert_dist = nullptr, *point_dist = nullptr;
+  // the surface term only: keys [N][V] then [N][S] (one memset), the points' hits, the vertices' residuals, per-block partials
+  unsigned long long* surf_keys = nullptr;
+  SurfaceHit* surf_hits = nullptr;
+  float *surf_res = nullptr, *surf_part_ps = nullptr, *surf_part_vs = nullptr, *surf_part_dtr = nullptr;
 };
 
 struct smalfit_mesh_targets {
   MeshTargetsDev d{};
   void* blob = nullptr;
+  const ScanTri* tris = nullptr;   // packed [sum F]: the staged records of the surface term's vertex -> surface scan, in the blob
+  int max_faces = 0;               // of the largest mesh: what that scan's slice count is sized by
 };
+
+// the launches of the surface term on `verts`; the block validated by the callers.  In a step the term's gradient is ADDED to
+// the step's d verts, its planar copy (stride Vp) and d trans, after run_mesh_objective has written them: one float32 addition
+// per coordinate, the addition Stage.step_unfused performs on the stand-alone call's outputs -- the two paths form the same bits
+static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_targets* t, hipStream_t st, const smalfit_surface_term_args* a,
+                            const float* verts, const float* points, int num_points, float* acc_dverts = nullptr,
+                            float* acc_planar = nullptr, int Vp = 0, float* acc_dtrans = nullptr,
+                            const float* step_losses = nullptr) {
+  SurfaceTermArgs k{};
+  k.N = a->num_meshes; k.V = m->t.V; k.F = m->num_faces;
+  k.w_ps = mesh_weight(a->w_point_surface); k.w_vs = mesh_weight(a->w_vert_surface);
+  k.S = k.w_ps > 0.f ? num_points : 1;
+  k.verts = verts; k.points = points; k.faces = m->faces;
+  if (k.w_vs > 0.f) { k.t = t->d; k.target_tris = t->tris; }
+  k.keys_v = m->surf_keys; k.keys_p = m->surf_keys + (size_t)k.N * k.V;
+  k.hits = m->surf_hits; k.res_v = m->surf_res;
+  k.point_face = a->point_face; k.point_bary = a->point_bary; k.vert_face = a->vert_face; k.vert_bary = a->vert_bary;
+  k.point_residual = a->point_residual; k.vert_residual = a->vert_residual;
+  k.part_ps = m->surf_part_ps; k.part_vs = m->surf_part_vs; k.part_dtr = m->surf_part_dtr;
+  const Grid2 hv = surface_hit_grid(k.V, k.N), hp = surface_hit_grid(k.S, k.N), gg = surface_grad_grid(k.V, k.N);
+  k.hv = hv.x; k.hp = hp.x; k.gv = gg.x;
+  k.acc_dverts = acc_dverts; k.acc_planar = acc_planar; k.Vp = Vp; k.acc_dtrans = acc_dtrans;
+  k.dverts = a->dverts; k.dtrans = a->dtrans; k.losses = a->losses; k.rows = a->rows;
+  k.step_losses = step_losses; k.step_total = step_losses ? a->step_total : nullptr;
+  // the keys of the directions that run, all ones: the vertices' come first, the points' behind them
+  unsigned long long* first = k.w_vs > 0.f ? k.keys_v : k.keys_p;
+  const size_t keys = (size_t)k.N * ((k.w_vs > 0.f ? (size_t)k.V : 0) + (k.w_ps > 0.f ? (size_t)k.S : 0));
+  if (keys > 0) HIP_OK(hipMemsetAsync(first, 0xFF, keys * sizeof(unsigned long long), st));
+  if (k.w_vs > 0.f) {
+    const Grid3 g = surface_near_grid(k.V, t->max_faces, k.N);
+    mesh3d_surface_near_kernel<0><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    LAUNCH_OK("mesh3d_surface_near_kernel<0>");
+    mesh3d_surface_hit_kernel<0><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
+    LAUNCH_OK("mesh3d_surface_hit_kernel<0>");
+  }
+  if (k.w_ps > 0.f) {
+    const Grid3 g = surface_near_grid(k.S, k.F, k.N);
+    mesh3d_surface_near_kernel<1><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    LAUNCH_OK("mesh3d_surface_near_kernel<1>");
+    mesh3d_surface_hit_kernel<1><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
+    LAUNCH_OK("mesh3d_surface_hit_kernel<1>");
+  }
+  mesh3d_surface_grad_kernel<<<dim3(gg.x, gg.y), 64 * kSurfaceGradWaves, 0, st>>>(k);
+  LAUNCH_OK("mesh3d_surface_grad_kernel");
+  mesh3d_surface_reduce_kernel<<<1, 256, 0, st>>>(k);
+  LAUNCH_OK("mesh3d_surface_reduce_kernel");
+  return 0;
+}
 
 // the 6 launches of one evaluation; arguments validated by the callers
 static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num_meshes, const float* lbs_verts,
@@ -132,6 +186,12 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   w.field(m->gbetas, N * 64);
   w.field(m->vert_dist, N * V);
   w.field(m->point_dist, N * S);
+  w.field(m->surf_keys, N * (V + S));
+  w.field(m->surf_hits, N * S);
+  w.field(m->surf_res, N * V * 3);
+  w.field(m->surf_part_ps, N * (size_t)surface_hit_grid((int)S, 1).x);
+  w.field(m->surf_part_vs, N * (size_t)surface_hit_grid((int)V, 1).x);
+  w.field(m->surf_part_dtr, N * m->by * 3);
   auto bail = [&](const char* what) {
     smalfit_mesh_objective_destroy(m);
     return refused("smalfit_mesh_objective_create", what);
@@ -188,12 +248,23 @@ int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const in
   } catch (const std::exception& ex) {
     return refused("smalfit_mesh_targets_create", ex.what());
   }
+  // the surface term's vertex -> surface scan reads the targets' triangles every iteration: they never move, so their records
+  // are staged here, once
+  std::vector<ScanTri> tris((size_t)foff[num_meshes]);
+  int max_faces = 0;
+  for (int n = 0; n < num_meshes; ++n) {
+    max_faces = std::max(max_faces, face_counts[n]);
+    const float* base = verts + 3 * (size_t)voff[n];
+    for (int f = foff[n]; f < foff[n + 1]; ++f)   // (area_thresholds has checked every index)
+      tris[f] = make_scan_tri(base + 3 * (size_t)faces[3 * f], base + 3 * (size_t)faces[3 * f + 1], base + 3 * (size_t)faces[3 * f + 2]);
+  }
   Blob b;
   const size_t o_vo = b.add(voff.data(), voff.size() * sizeof(int));
   const size_t o_fo = b.add(foff.data(), foff.size() * sizeof(int));
   const size_t o_v = b.add(verts, (size_t)voff[num_meshes] * 3 * sizeof(float));
   const size_t o_f = b.add(faces, (size_t)foff[num_meshes] * 3 * sizeof(int));
   const size_t o_t = b.add(thr.data(), thr.size() * sizeof(uint32_t));
+  const size_t o_s = b.add(tris.data(), tris.size() * sizeof(ScanTri));
   unsigned char* base = upload_blob(b, "smalfit_mesh_targets_create");
   if (!base) return 1;
   auto* t = new smalfit_mesh_targets();
@@ -202,6 +273,7 @@ int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const in
   t->d.voff = (const int*)(base + o_vo); t->d.foff = (const int*)(base + o_fo);
   t->d.verts = (const float*)(base + o_v); t->d.faces = (const int*)(base + o_f);
   t->d.thr = (const uint32_t*)(base + o_t);
+  t->tris = (const ScanTri*)(base + o_s); t->max_faces = max_faces;
   *out = t;
   return 0;
 }
@@ -244,15 +316,34 @@ int smalfit_mesh_score(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void*
   return 0;
 }
 
+// ---- the surface term alone --------------------------------------------------------------------------------------------
+int smalfit_mesh_surface_eval(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream, const smalfit_surface_term_args* a) {
+  if (refused("smalfit_mesh_surface_eval", null_argument_refusal(m && a))) return 1;
+  if (refused("smalfit_mesh_surface_eval", surface_term_args_refusal(a, SurfaceTermFacts{m->max_meshes, m->max_points, t != nullptr,
+                                                                                         t ? t->d.N : 0, false, 0, 0, false})))
+    return 1;
+  return run_surface_term(m, t, (hipStream_t)stream, a, a->verts, a->points, a->num_points);
+}
+
 // ---- Stage.step in one call ------------------------------------------------------------------------------------------
 int smalfit_fit3d_step(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
                        const smalfit_fit3d_args* a) {
-  if (refused("smalfit_fit3d_step", null_argument_refusal(e && m && a))) return 1;
+  return smalfit_fit3d_step_surface(e, m, t, stream, a, nullptr);
+}
+
+int smalfit_fit3d_step_surface(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
+                               const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf) {
+  const char* who = sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
+  if (refused(who, null_argument_refusal(e && m && a))) return 1;
   const ModelDev& md = e->model->dev;
-  if (refused("smalfit_fit3d_step", fit3d_args_refusal(a, Fit3dFacts{e->maxM, md.V, md.NBall, m->max_meshes, m->max_points, m->t.V,
-                                                                    t != nullptr, t ? t->d.N : 0})))
+  if (refused(who, fit3d_args_refusal(a, Fit3dFacts{e->maxM, md.V, md.NBall, m->max_meshes, m->max_points, m->t.V,
+                                                    t != nullptr, t ? t->d.N : 0})))
     return 1;
-  const Fit3dPlan plan = plan_fit3d(a, md.V);
+  if (sf && refused(who, surface_term_args_refusal(sf, SurfaceTermFacts{m->max_meshes, m->max_points, t != nullptr, t ? t->d.N : 0, true,
+                                                                        a->num_meshes, a->num_points, a->points != nullptr})))
+    return 1;
+  const bool surface = surface_term_on(sf);   // a block with both weights <= 0 is the step without it: nothing of it is launched or written
+  const Fit3dPlan plan = plan_fit3d(a, md.V, surface && sf->w_point_surface > 0.f);
   const int N = a->num_meshes, nb = a->num_betas, S = a->num_points;
   hipStream_t st = (hipStream_t)stream;
 
@@ -276,6 +367,9 @@ int smalfit_fit3d_step(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mes
   // vertex gradient where the LBS adjoint expects it: no layout-conversion launches in between)
   if (run_mesh_objective(m, st, N, nullptr, a->trans, a->deform_verts, pts, S, a->weights, a->verts_out, a->losses,
                          m->dverts, m->dtrans, e->verts, md.Vp, plan.planar_vertex_grad ? e->dext : nullptr)) return 1;
+  // the surface term at the vertices the objective composed; its gradient joins the step's in all three places it is read from
+  if (surface && run_surface_term(m, t, st, sf, a->verts_out ? a->verts_out : m->verts, pts, S, m->dverts,
+                                  plan.planar_vertex_grad ? e->dext : nullptr, md.Vp, m->dtrans, a->losses)) return 1;
   if (!plan.any_trained) return 0;
 
   // back through the LBS (forward state is still in the engine)

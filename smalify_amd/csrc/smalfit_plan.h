@@ -306,6 +306,34 @@ constexpr int kSurfaceChunk = 512;
 constexpr int kScoreDirections = 2;          // 0: fitted vertex -> target surface, 1: target point -> fitted surface
 inline Grid2 surface_dist_grid(int queries, int N) { return Grid2{mesh_query_blocks(queries), N}; }
 constexpr Grid2 score_reduce_grid(int N) { return Grid2{kScoreDirections, N}; }
+// the surface term (smalfit_mesh_surface_eval, smalfit_fit3d_step_surface) runs every iteration, where the grid above leaves
+// three quarters of the CUs idle at one mesh (61 and 47 blocks).  mesh3d_surface_near_kernel keeps the 64 queries and the staged
+// chunk and takes a third grid dimension: the scanned triangles in `slices` contiguous spans, whose minima meet in one 64-bit
+// (distance bits, face) key per query.  The slice count aims at the 1024 blocks the 256 CUs hold at once (four a CU by the 34 KB
+// of LDS: 16 waves, four a SIMD to cover the broadcast LDS reads) without going over them -- a fifth block on some CUs would be a
+// tail of a quarter of the launch --, keeps at least kSurfaceMinSlice triangles a slice -- below that the staging and the atomic
+// outweigh the scan -- and is rounded so that no slice is empty.  A ragged batch of targets is sliced by its largest mesh; a
+// smaller mesh's surplus blocks return before they stage anything.
+constexpr int kSurfaceTargetBlocks = 1024;
+constexpr int kSurfaceMinSlice = 64;
+constexpr int kSurfaceHitChunk = 512;        // SurfaceHit records (48 bytes) staged at a time by mesh3d_surface_grad_kernel: 24 KB
+constexpr int surface_slice_span(int faces, int slices) { return (faces + slices - 1) / slices; }   // triangles per slice
+inline int surface_slices(int queries, int faces, int N) {
+  const long long blocks = std::max(1LL, (long long)mesh_query_blocks(queries) * N);
+  long long want = kSurfaceTargetBlocks / blocks;
+  want = std::max(1LL, std::min(want, (long long)(faces / kSurfaceMinSlice)));
+  const int span = surface_slice_span(faces, (int)want);
+  return std::max(1, surface_slice_span(faces, std::max(span, 1)));   // = ceil(faces / span): the last slice starts inside the mesh
+}
+struct Grid3 { int x, y, z; };
+inline Grid3 surface_near_grid(int queries, int faces, int N) { return Grid3{mesh_query_blocks(queries), N, surface_slices(queries, faces, N)}; }
+// one query per thread: the winner's barycentrics and residual, per-block sums of d^2
+inline Grid2 surface_hit_grid(int queries, int N) { return Grid2{mesh_element_blocks(queries), N}; }
+// the term's vertex gradient: 64 vertices per block, one per lane, the same 64 in each of its kSurfaceGradWaves waves, which split
+// the staged hits between them (the chamfer kernels' scheme with 16 waves for 4: 61 blocks of 4 waves are a quarter of the chip's
+// SIMDs at one mesh, and the gather is as long as a chamfer scan)
+constexpr int kSurfaceGradWaves = 16;
+inline Grid2 surface_grad_grid(int V, int N) { return Grid2{mesh_query_blocks(V), N}; }
 
 // ------------------------------------------------------------------------------------------------
 // the mesh objective's entry points: which arguments are refused (the text behind "<entry point>: " or nullptr, the first fault;
@@ -351,6 +379,47 @@ inline const char* mesh_score_args_refusal(const smalfit_mesh_score_args* a, con
   for (int t = 0; t < a->num_thresholds; ++t)
     if (!(std::isfinite(a->thresholds[t]) && a->thresholds[t] > 0.f)) return "every threshold must be finite and > 0";
   if (a->num_thresholds == 0 && a->within) return "within given with num_thresholds = 0";
+  return nullptr;
+}
+
+// -> why smalfit_mesh_surface_eval / smalfit_fit3d_step_surface refuse the surface block (the text behind "<entry point>: "), or
+// nullptr.  In a step the vertices and the points are the step's own: the block must carry neither, and what the points need is
+// asked of the step's block (step_points: its num_points; step_has_points: its `points` is given)
+struct SurfaceTermFacts {
+  int max_meshes, max_points;   // the objective's capacities
+  bool targets;                 // target meshes were given
+  int target_meshes;            // how many (read only with `targets`)
+  bool step;                    // the block rides on a smalfit_fit3d_args
+  int step_meshes, step_points;
+  bool step_has_points;
+};
+inline bool surface_term_on(const smalfit_surface_term_args* s) { return s && (s->w_point_surface > 0.f || s->w_vert_surface > 0.f); }
+inline const char* surface_term_args_refusal(const smalfit_surface_term_args* a, const SurfaceTermFacts& f) {
+  if (a->struct_size != (unsigned)sizeof(smalfit_surface_term_args))
+    return "smalfit_surface_term_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (a->num_meshes <= 0 || a->num_meshes > f.max_meshes) return "num_meshes exceeds the objective's max_meshes";
+  if (f.step && a->num_meshes != f.step_meshes) return "num_meshes differs from the step's";
+  if (a->w_vert_surface > 0.f) {
+    if (!f.targets) return "the vertex-surface term needs the target meshes";
+    if (f.target_meshes != a->num_meshes) return "number of target meshes differs from num_meshes";
+  }
+  if (!a->losses) return "losses missing";
+  if (f.step) {
+    if (a->verts || a->points) return "verts and points must be NULL in a step: it uses its own";
+    if (a->w_point_surface > 0.f) {
+      if (f.step_points <= 0 || f.step_points > f.max_points) return "the point-surface term needs 1 <= num_points <= max_points";
+      if (!f.step_has_points && !f.targets) return "neither target points nor target meshes given";
+      if (!f.step_has_points && f.target_meshes != a->num_meshes) return "number of target meshes differs from num_meshes";
+    }
+  } else {
+    if (!a->verts) return "verts missing";
+    if (a->w_point_surface > 0.f && (!a->points || a->num_points <= 0 || a->num_points > f.max_points))
+      return "the point-surface term needs 1 <= num_points <= max_points points";
+  }
+  if (a->point_bary && !a->point_face) return "point_bary given without point_face";
+  if (a->vert_bary && !a->vert_face) return "vert_bary given without vert_face";
+  if (a->point_residual && !a->point_face) return "point_residual given without point_face";
+  if (a->vert_residual && !a->vert_face) return "vert_residual given without vert_face";
   return nullptr;
 }
 
@@ -420,7 +489,7 @@ inline const char* fit3d_args_refusal(const smalfit_fit3d_args* a, const Fit3dFa
 
 // where the chamfer term's target points come from
 enum class Fit3dPoints {
-  None = 0,            // chamfer off: none are read
+  None = 0,            // chamfer and the point-surface term off: none are read
   SampleToObjective,   // sampled from the target meshes into the objective's buffer
   SampleToCaller,      // ... into points_out
   Callers,             // the caller's, read in place
@@ -437,12 +506,13 @@ struct Fit3dPlan {
   Fit3dAdamGeometry seg[kFit3dParams];
   int adam_blocks;             // grid of fit3d_adam_kernel
 };
-// -> the plan of a block that fit3d_args_refusal accepts, on a model of `model_verts` vertices
-inline Fit3dPlan plan_fit3d(const smalfit_fit3d_args* a, int model_verts) {
+// -> the plan of a block that fit3d_args_refusal accepts, on a model of `model_verts` vertices.  point_surface: the step carries
+// a surface block with w_point_surface > 0, which reads the step's points whether the chamfer term runs or not
+inline Fit3dPlan plan_fit3d(const smalfit_fit3d_args* a, int model_verts, bool point_surface = false) {
   Fit3dPlan p{};
   const int N = a->num_meshes, nb = a->num_betas, V3 = model_verts * 3;
   p.chamfer = a->weights[0] > 0.f;
-  if (!p.chamfer) p.points = Fit3dPoints::None;
+  if (!p.chamfer && !point_surface) p.points = Fit3dPoints::None;
   else if (!a->points) p.points = a->points_out ? Fit3dPoints::SampleToCaller : Fit3dPoints::SampleToObjective;
   else p.points = a->points_out && a->points_out != a->points ? Fit3dPoints::CallersCopied : Fit3dPoints::Callers;
   p.need_pose = a->lr_global_rot > 0.f || a->lr_joint_rot > 0.f;

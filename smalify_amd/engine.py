@@ -687,6 +687,53 @@ class MeshObjective:
         check(fn(self.handle, targets.handle, _stream(), C.byref(a)), "smalfit_mesh_score")
         return out
 
+    def surface(self, verts, targets, points, w_point_surface, w_vert_surface, correspondences=False):
+        """The point-to-surface term both ways and its gradient (smalfit_mesh_surface_eval; the definition is this project's,
+        include/smalfit.h): L_ps = mean over the points of d^2(point, fitted surface), L_vs = mean over the fitted vertices of
+        d^2(vertex, target surface), term = w_point_surface L_ps + w_vert_surface L_vs; a weight <= 0 skips its direction.
+        verts (N,V,3); targets: the MeshTargets (or a TargetMeshes), may be None when w_vert_surface <= 0; points (N,S,3) on
+        the target surfaces, may be None when w_point_surface <= 0.
+        -> dict of device tensors: losses (3,) = L_ps, L_vs, term; rows (N,2) = per mesh sum d^2 of the points | the vertices;
+        dverts (N,V,3), dtrans (N,3) = the term's gradient; with correspondences, for every direction that ran, point_face (N,S)
+        int32 / point_bary (N,S,3) on the fitted topology and vert_face (N,V) / vert_bary (N,V,3) on target mesh n, each with its
+        residual (point_residual, vert_residual: the query minus its closest point, as the gradient uses it)."""
+        fn = _lib.resolve(self.lib, "smalfit_mesh_surface_eval")
+        targets = getattr(targets, "_dev", targets)
+        if targets is not None and not isinstance(targets, MeshTargets):
+            raise SmalfitError("targets must be the MeshTargets the meshes are fitted to")
+        N, V = int(verts.shape[0]), self.num_verts
+        if tuple(verts.shape) != (N, V, 3):
+            raise SmalfitError("verts must be (num_meshes, %d, 3)" % V)
+        S = 0
+        if points is not None:
+            if not (isinstance(points, torch.Tensor) and points.dim() == 3 and int(points.shape[0]) == N and int(points.shape[2]) == 3):
+                raise SmalfitError("points must be (num_meshes, S, 3)")
+            if points.device != verts.device:
+                raise SmalfitError("points must be on the device of verts (%s)" % verts.device)
+            S = int(points.shape[1])
+        dev = verts.device
+        a = _lib.SurfaceTermArgs()
+        a.num_meshes, a.w_point_surface, a.w_vert_surface = N, float(w_point_surface), float(w_vert_surface)
+        a.verts, a.points, a.num_points = _ptr(verts), _ptr(points), S
+        out = {"losses": torch.empty(3, device=dev), "rows": torch.empty(N, 2, device=dev),
+               "dverts": torch.empty(N, V, 3, device=dev), "dtrans": torch.empty(N, 3, device=dev)}
+        a.losses, a.rows, a.dverts, a.dtrans = (_ptr(out[k]) for k in ("losses", "rows", "dverts", "dtrans"))
+        if correspondences:
+            if w_point_surface > 0 and points is not None:
+                out["point_face"] = torch.empty(N, S, dtype=torch.int32, device=dev)
+                out["point_bary"] = torch.empty(N, S, 3, device=dev)
+                out["point_residual"] = torch.empty(N, S, 3, device=dev)
+                a.point_face, a.point_bary = C.c_void_p(out["point_face"].data_ptr()), _ptr(out["point_bary"])
+                a.point_residual = _ptr(out["point_residual"])
+            if w_vert_surface > 0:
+                out["vert_face"] = torch.empty(N, V, dtype=torch.int32, device=dev)
+                out["vert_bary"] = torch.empty(N, V, 3, device=dev)
+                out["vert_residual"] = torch.empty(N, V, 3, device=dev)
+                a.vert_face, a.vert_bary = C.c_void_p(out["vert_face"].data_ptr()), _ptr(out["vert_bary"])
+                a.vert_residual = _ptr(out["vert_residual"])
+        check(fn(self.handle, targets.handle if targets is not None else None, _stream(), C.byref(a)), "smalfit_mesh_surface_eval")
+        return out
+
 
 class MeshTargets:
     """Target meshes resident in HBM + the area-weighted point sampler (smalfit_mesh_targets; reference

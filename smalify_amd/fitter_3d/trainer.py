@@ -31,6 +31,10 @@ from ..smal_model.smal_torch import SMAL
 
 default_weights = dict(w_chamfer=1.0, w_edge=1.0, w_normal=0.01, w_laplacian=0.1)     # trainer.py:31
 _WEIGHT_ORDER = ("w_chamfer", "w_edge", "w_normal", "w_laplacian")
+# the opt-in point-to-surface term (no counterpart in the reference; include/smalfit.h): accepted in `loss_weights` beside the
+# four keys above, kept apart from them, off by default
+default_surface_weights = dict(w_point_surface=0.0, w_vert_surface=0.0)
+_SURFACE_ORDER = ("w_point_surface", "w_vert_surface")
 N_SAMPLE_POINTS = 3000                                                                 # trainer.py:209
 _PARAM_ORDER = ("betas", "log_beta_scales", "global_rot", "joint_rot", "trans", "deform_verts")
 # Stage.metrics draws its target points with a key of its own: the counter-based sampler gives the same points for the same
@@ -136,10 +140,14 @@ class Stage:
         self.smal_3d_fitter = smal_3d_fitter
         self.device = smal_3d_fitter.device
         self.loss_weights = default_weights.copy()
+        self.surface_weights = default_surface_weights.copy()
         if loss_weights is not None:
             for k, v in loss_weights.items():
+                if k in self.surface_weights:
+                    self.surface_weights[k] = float(v)
+                    continue
                 if k not in self.loss_weights:
-                    raise KeyError("unknown loss weight %r (have %s)" % (k, sorted(self.loss_weights)))
+                    raise KeyError("unknown loss weight %r (have %s)" % (k, sorted(self.loss_weights) + sorted(self.surface_weights)))
                 self.loss_weights[k] = float(v)
         if custom_lrs is not None:
             for attr in custom_lrs:
@@ -170,6 +178,8 @@ class Stage:
         self._done = 0
         self._t = 0              # Adam step count of this stage
         self._args = None        # smalfit_fit3d_args, built on the first step
+        self._surface_args = None      # smalfit_surface_term_args of step(), built with it when a surface weight is positive
+        self._surface_losses = None
         self.consider_loss = lambda loss_name: self.loss_weights[f"w_{loss_name}"] > 0
 
     # ---- evaluation ----------------------------------------------------------------------------------------------
@@ -188,6 +198,16 @@ class Stage:
         """device tensor (5,): chamfer, edge, normal, laplacian (unweighted) and the weighted total"""
         return self._buffers.get("losses")
 
+    @property
+    def last_surface_terms(self):
+        """device tensor (3,): L_ps, L_vs and the weighted surface term of the most recent evaluation or step; None while the
+        term is off"""
+        return self._surface_losses
+
+    @property
+    def surface_on(self):
+        return any(self.surface_weights[k] > 0 for k in _SURFACE_ORDER)
+
     def _weights(self):
         return [self.loss_weights[k] for k in _WEIGHT_ORDER]
 
@@ -199,16 +219,25 @@ class Stage:
         ls = fit.log_beta_scales.detach().contiguous()
         theta = fit._pack_theta()
         lbs = e.lbs_forward(betas, theta, ls, want_Rs=False, want_v_shaped=False)[0]
-        if points is None and self.loss_weights["w_chamfer"] > 0:
+        if points is None and (self.loss_weights["w_chamfer"] > 0 or self.surface_weights["w_point_surface"] > 0):
             points = self.target_meshes.sample(N_SAMPLE_POINTS, self.seed, self.iteration_offset + iteration, out=self._sample_buffer())
         self._last_points = points            # the sampler's buffer is never rebound: smalfit_fit3d_step writes through its raw pointer
         o = self._objective.eval(lbs, fit.trans.detach().contiguous(), fit.deform_verts.detach().contiguous(), points,
                                  self._weights(), out=self._buffers)
         self._buffers = o
+        total = o["losses"][4]
+        if self.surface_on:
+            # the stand-alone call's gradient joins the objective's before the LBS adjoint
+            wp, wv = (self.surface_weights[k] for k in _SURFACE_ORDER)
+            sf = self._objective.surface(o["verts"], self.target_meshes, points if wp > 0 else None, wp, wv)
+            o["dverts"] += sf["dverts"]
+            o["dtrans"] += sf["dtrans"]
+            self._surface_losses = sf["losses"]
+            total = total + sf["losses"][2]
         dbeta, dtheta, dls = e.lbs_backward(betas, theta, ls, o["dverts"], None)
         grads = {"betas": dbeta, "global_rot": dtheta[:, 0].contiguous(), "joint_rot": dtheta[:, 1:].contiguous(),
                  "log_beta_scales": dls, "trans": o["dtrans"], "deform_verts": o["dverts"]}
-        return o["losses"][4], grads
+        return total, grads
 
     def forward(self, src_mesh=None):
         """total loss at the current parameters (the reference takes the offset source mesh; the engine composes it)"""
@@ -227,10 +256,18 @@ class Stage:
         self._t += 1
         a.adam_t = self._t
         dev_targets = getattr(self.target_meshes, "_dev", self.target_meshes)
-        eng.check(e.lib.smalfit_fit3d_step(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a)),
-                  "smalfit_fit3d_step")
+        if not self.surface_on:
+            eng.check(e.lib.smalfit_fit3d_step(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a)),
+                      "smalfit_fit3d_step")
+            self._last_points = self._points
+            return self._buffers["losses"][4]
+        sf = self._surface_block()
+        sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
+        fn = _lib.resolve(e.lib, "smalfit_fit3d_step_surface")
+        eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a), C.byref(sf)),
+                  "smalfit_fit3d_step_surface")
         self._last_points = self._points
-        return self._buffers["losses"][4]
+        return self._step_total[0]          # the grand total, formed by the step: the four terms + the surface term
 
     def step_unfused(self, epoch):
         """the same iteration as five separate C-ABI calls + one smalfit_adam_step per parameter; leaves the gradients
@@ -289,6 +326,18 @@ class Stage:
             a.verts_out = None
             self._args = a
         return self._args
+
+    def _surface_block(self):
+        """the smalfit_surface_term_args of step(): the step's own vertices and points, the term's three figures"""
+        if self._surface_args is None:
+            sf = _lib.SurfaceTermArgs()
+            sf.num_meshes = self.smal_3d_fitter.batch_size
+            self._step_losses = torch.zeros(3, device=self.device)
+            self._step_total = torch.zeros(1, device=self.device)
+            sf.losses, sf.step_total = self._step_losses.data_ptr(), self._step_total.data_ptr()
+            self._surface_args = sf
+        self._surface_losses = self._step_losses
+        return self._surface_args
 
     def run(self, plot=False, progress=True, report_every=50):
         """Run the entire Stage (trainer.py:257-270).  The description line is refreshed every `report_every`

@@ -3,9 +3,10 @@
 batch of N target meshes, "default" scheme (trainer.py:115), all four loss terms, 3000 target points per mesh, and the
 share of each of the five C-ABI calls of a step (torch events on the launch stream, separate short run).
 
-    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300]
+    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface]
 
-Prints one JSON line per batch size.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
+Prints one JSON line per batch size.  --surface adds the point-to-surface term both ways (w_point_surface = w_vert_surface = 1:
+every step is smalfit_fit3d_step_surface) and two fields to the line; without it the run and the line are those of before.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
 import argparse
 import json
 import os
@@ -37,6 +38,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", type=int, nargs="+", default=[1, 8, 32])
     ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--surface", action="store_true", help="add the point-to-surface term both ways to every step")
     args = ap.parse_args()
     import torch
     from smalify_amd import synthetic
@@ -48,7 +50,8 @@ def main():
         fit = SMAL3DFitter(batch_size=N, shape_family=-1, model_data=md, smal_data=smal_data)
         tv = targets_for(md, N, seed=N)
         targets = TargetMeshes(tv, [np.asarray(md.faces)] * N)
-        stage = Stage(args.iters, "default", fit, targets, lr=0.01, custom_lrs={"joint_rot": 0.005})
+        weights = {"w_point_surface": 1.0, "w_vert_surface": 1.0} if args.surface else None
+        stage = Stage(args.iters, "default", fit, targets, lr=0.01, custom_lrs={"joint_rot": 0.005}, loss_weights=weights)
         for i in range(10):
             stage.step(i)
         torch.cuda.synchronize()
@@ -78,11 +81,15 @@ def main():
             acc += [ev[k].elapsed_time(ev[k + 1]) for k in range(4)]
         sec = dict(zip(("lbs_forward", "sample", "objective", "lbs_backward"), (acc / reps).tolist()))
         V, S = md.num_verts, 3000
-        print(json.dumps({"meshes": N, "iterations_per_s": args.iters / dt, "ms_per_iteration": 1e3 * dt / args.iters,
-                          "mesh_iterations_per_s": N * args.iters / dt,
-                          "host_issue_ms_per_iteration": 1e3 * t_issue / args.iters, "section_ms": sec,
-                          "chamfer_point_pairs_per_s": 2.0 * N * V * S / (sec["objective"] * 1e-3),
-                          "final_total_loss": float(stage.last_terms[4])}))
+        line = {"meshes": N, "iterations_per_s": args.iters / dt, "ms_per_iteration": 1e3 * dt / args.iters,
+                "mesh_iterations_per_s": N * args.iters / dt,
+                "host_issue_ms_per_iteration": 1e3 * t_issue / args.iters, "section_ms": sec,
+                "chamfer_point_pairs_per_s": 2.0 * N * V * S / (sec["objective"] * 1e-3),
+                "final_total_loss": float(stage.last_terms[4])}
+        if args.surface:
+            line["surface"] = True
+            line["final_surface_terms"] = [float(x) for x in stage.last_surface_terms]
+        print(json.dumps(line))
         del stage, targets, fit
 
 
