@@ -40,7 +40,9 @@ typedef struct smalfit_engine smalfit_engine;
  * each with its own shape; one row of loss terms per frame).  Added within version 6, no struct of it changing its layout:
  * smalfit_fit_eval_windows (smalfit_window_rows); smalfit_fit_metrics (smalfit_metrics_args: silhouette IoU counts and PCK
  * per frame); smalfit_mesh_score (smalfit_mesh_score_args: point-to-surface distances both ways, per mesh);
- * smalfit_mesh_surface_eval / smalfit_fit3d_step_surface (smalfit_surface_term_args: the same distances as a term to descend on). */
+ * smalfit_mesh_surface_eval / smalfit_fit3d_step_surface (smalfit_surface_term_args: the same distances as a term to descend on);
+ * smalfit_mesh_surface_eval_gated / smalfit_fit3d_step_gated / smalfit_mesh_targets_sample_normals (smalfit_surface_gate_args: that
+ * term gated for partial scans). */
 #define SMALFIT_ABI_VERSION 6
 int smalfit_version(void);
 const char* smalfit_last_error(void);
@@ -462,6 +464,10 @@ void smalfit_mesh_targets_destroy(smalfit_mesh_targets* targets);
  * (sample, mesh, iteration): the same (seed, iteration) always gives the same points.  points (N,S,3) device. */
 int smalfit_mesh_targets_sample(smalfit_mesh_targets* targets, void* stream, int num_points,
                                 unsigned long long seed, unsigned int iteration, float* points);
+/* the same points, bit for bit (the same Philox draws, the same face), and with every point the unit normal of the face it was
+ * sampled on: that face's (b - a) x (c - a) over its length, the zero vector for a degenerate face.  normals (N,S,3) device. */
+int smalfit_mesh_targets_sample_normals(smalfit_mesh_targets* targets, void* stream, int num_points,
+                                        unsigned long long seed, unsigned int iteration, float* points, float* normals);
 
 /* ---- how good a 3-D fit is: exact surface distances both ways, per mesh -------------------------------------------------
  * No counterpart in the reference, whose fitter_3d contains no evaluation code: the definitions below are THIS PROJECT'S.
@@ -591,6 +597,55 @@ int smalfit_fit3d_step(smalfit_engine* engine, smalfit_mesh_objective* objective
  * term, and the caller adds the two (or asks for surface->step_total).  `targets` is needed when w_vert_surface > 0 or points are to be sampled. */
 int smalfit_fit3d_step_surface(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
                                void* stream, const smalfit_fit3d_args* args, const smalfit_surface_term_args* surface);
+
+/* ---- the surface term gated for partial scans ---------------------------------------------------------------------------
+ * A target with holes, an unseen side or thin sheets pulls the fitted surface to whatever is nearest.  Three opt-in gates decide
+ * which matches count; THIS PROJECT'S definitions.  d(p, T), the candidate order (ab, bc, ca, plane), the lowest-face tie rule
+ * and the residual r are those of the term above and do not change.  Both meshes are taken to be wound consistently outward.
+ *   compatibility  A query carries a unit normal u, a scanned triangle its record normal n = (b - a) x (c - a), unnormalised.
+ *                  With g = <u, n> the pair is compatible with threshold c when  g |g| / |n|^2 >= c |c|  (the signed squared
+ *                  cosine, monotone in the cosine).  A degenerate triangle or a zero u gives 0 on the left: compatible exactly
+ *                  when c <= 0.  c <= -1 switches the test off for its direction: no normals are read or computed.
+ *   gated nearest  the nearest face among the compatible ones, by the same (d^2 bits, face index) key; a query with no
+ *                  compatible face finds none.
+ *   query normals  fitted vertex: the sum over its incident faces, in ascending face index, of their unnormalised normals n,
+ *                  over its length (a zero length gives the zero vector).  Target point: the unit normal of the target face it
+ *                  was sampled on (smalfit_mesh_targets_sample_normals); for the caller's points the caller supplies them.
+ *   truncation     a query is dropped when d^2 > tau^2, tau^2 formed once on the host in float32; tau <= 0 or not finite
+ *                  switches truncation off for its direction.
+ *   boundary       vertex -> target only.  A target's boundary edges are the undirected vertex pairs used by exactly one of its
+ *                  faces, its boundary vertices their end points.  A vertex is dropped when the winning candidate of its nearest
+ *                  face is a segment and that segment is a boundary edge, or its clamped parameter is exactly 0 and the start
+ *                  corner is a boundary vertex, or exactly 1 and the end corner is one.
+ *   kept           a query is kept when it found a face and no gate dropped it.  A dropped query contributes 0 to L_ps / L_vs
+ *                  and to `rows`; its residual and barycentrics are 0, so it contributes nothing to any gradient; its optional
+ *                  face output is -1.  The denominators stay N S and N V, not the kept counts: a kept query's gradient is what
+ *                  it is ungated, and the loss does not jump when a count changes.  `kept` lets a caller renormalise.
+ * No gate is differentiated through (they are piecewise constant, as the envelope theorem already assumes).  gate == NULL, or
+ * every gate off: exactly the ungated call, launch for launch and bit for bit; with a block whose gates are all off `kept` reads
+ * (S, V) for the directions that ran (0 for a skipped one) without anything being counted.
+ * Not here: a soft robust kernel (Geman-McClure and the like), gates for smalfit_mesh_score, any spatial acceleration. */
+typedef struct smalfit_surface_gate_args {
+  unsigned struct_size;       /* sizeof(smalfit_surface_gate_args) of the caller's header; checked before any other field */
+  float max_dist_point;       /* tau of point -> surface; <= 0 or not finite: off */
+  float max_dist_vert;        /* tau of vertex -> surface */
+  float min_cos_point;        /* c of point -> surface, <= 1; <= -1: off */
+  float min_cos_vert;         /* c of vertex -> surface */
+  int reject_boundary;        /* != 0: the boundary rule */
+  const float* point_normals; /* (N,S,3) unit normals of the caller's points, needed when min_cos_point is on and the points are
+                                 the caller's; must be NULL in a step that samples its points (it draws the normals with them) */
+  int* kept;                  /* (N,2): kept points | kept vertices of every mesh (0 for a skipped direction) */
+  unsigned char* point_kept;  /* optional (N,S): 1 kept, 0 dropped */
+  unsigned char* vert_kept;   /* optional (N,V) */
+  float* vert_normals;        /* optional (N,V,3), only with min_cos_vert on: the fitted normals the gate used */
+} smalfit_surface_gate_args;
+/* smalfit_mesh_surface_eval / smalfit_fit3d_step_surface with the gates; those two ARE these calls with gate = NULL.  A refused
+ * block launches nothing and leaves every output alone */
+int smalfit_mesh_surface_eval_gated(smalfit_mesh_objective* objective, smalfit_mesh_targets* targets, void* stream,
+                                    const smalfit_surface_term_args* args, const smalfit_surface_gate_args* gate);
+int smalfit_fit3d_step_gated(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
+                             void* stream, const smalfit_fit3d_args* args, const smalfit_surface_term_args* surface,
+                             const smalfit_surface_gate_args* gate);
 
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137

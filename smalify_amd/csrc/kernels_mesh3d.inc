@@ -277,8 +277,11 @@ struct MeshTargetsDev {
   const uint32_t* thr;      // packed [sum F] cumulative-area thresholds (mesh3d_topology.h)
 };
 
+// NORMALS: also the unit normal of the sampled face (smalfit_mesh_targets_sample_normals; the points are those of <false>)
+template <bool NORMALS>
 __global__ __launch_bounds__(256) void mesh3d_sample_kernel(MeshTargetsDev t, int S, uint32_t seed_lo, uint32_t seed_hi,
-                                                           uint32_t iteration, float* points /* [N][S][3] */) {
+                                                           uint32_t iteration, float* points /* [N][S][3] */,
+                                                           float* normals /* [N][S][3], NORMALS only */) {
   const int n = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= S) return;
@@ -294,6 +297,14 @@ __global__ __launch_bounds__(256) void mesh3d_sample_kernel(MeshTargetsDev t, in
   dst[0] = out[0];
   dst[1] = out[1];
   dst[2] = out[2];
+  if (NORMALS) {
+    float u[3];
+    face_unit_normal(base + 3 * (size_t)fc[0], base + 3 * (size_t)fc[1], base + 3 * (size_t)fc[2], u);
+    float* dn = normals + ((size_t)n * S + i) * 3;
+    dn[0] = u[0];
+    dn[1] = u[1];
+    dn[2] = u[2];
+  }
 }
 
 // ---- smalfit_mesh_score: exact point-to-surface distances both ways, per mesh ------------------------------------------
@@ -439,11 +450,27 @@ struct SurfaceTermArgs {
   float* rows;               // [N][2] or null
   const float* step_losses;  // [5] of the step this term rides on, or null
   float* step_total;         // [1] or null: step_losses[4] + the weighted term
+  // the gates (smalfit_surface_gate_args, planned by plan_surface_gates); read by the GATED instantiations and, `kept`, by the reduce
+  const float* normals_v;    // [N][V][3] unit normals of the fitted vertices (mesh3d_vertex_normal_kernel), near<0, true> only
+  const float* normals_p;    // [N][S][3] unit normals of the points, near<1, true> only
+  float cc_v, cc_p;          // c |c| of the compatibility test
+  float tau2_v, tau2_p;      // +inf: no truncation
+  const unsigned char* bflags; // packed [sum F] boundary flags of the targets, or null: no boundary rule
+  int* part_kv;              // [N][hv] per-block kept counts of hit<0, true>, null where hit<0, false> ran
+  int* part_kp;              // [N][hp]
+  unsigned char* vert_kept;  // [N][V] or null
+  unsigned char* point_kept; // [N][S] or null
+  int* kept;                 // [N][2] or null
+  const int* vf_off;         // [V+1], [3F]: vertex -> incident faces of the fitted topology (mesh3d_vertex_normal_kernel)
+  const int* vf;
+  float* normals_out;        // [N][V][3] what mesh3d_vertex_normal_kernel writes (= normals_v)
 };
 
 // ROLE 0: queries = fitted vertices, scanned = the staged records of target mesh n.  ROLE 1: queries = the points, scanned = the
 // triangles of the fitted mesh n, staged from its vertices as in mesh3d_surface_dist_kernel.  Block (x, n, z) scans slice z
-template <int ROLE>
+// GATED: the nearest COMPATIBLE triangle -- the lane's unit normal in three registers, c |c| a scalar; a query with no compatible
+// triangle leaves its key all ones.  <ROLE, false> is the scan of the ungated term
+template <int ROLE, bool GATED>
 __global__ __launch_bounds__(256) void mesh3d_surface_near_kernel(SurfaceTermArgs a) {
   __shared__ ScanTri st[kSurfaceChunk];
   __shared__ float sd[4][kChamQueries];
@@ -469,6 +496,14 @@ __global__ __launch_bounds__(256) void mesh3d_surface_near_kernel(SurfaceTermArg
     qy = q[3 * (size_t)qi + 1];
     qz = q[3 * (size_t)qi + 2];
   }
+  float ux = 0.f, uy = 0.f, uz = 0.f;
+  const float cc = ROLE == 0 ? a.cc_v : a.cc_p;
+  if (GATED && active) {
+    const float* u = (ROLE == 0 ? a.normals_v : a.normals_p) + ((size_t)n * nq + qi) * 3;
+    ux = u[0];
+    uy = u[1];
+    uz = u[2];
+  }
   float best = INFINITY;
   int bidx = 0x7fffffff;
   for (int base = sb; base < se; base += kSurfaceChunk) {
@@ -486,7 +521,8 @@ __global__ __launch_bounds__(256) void mesh3d_surface_near_kernel(SurfaceTermArg
     __syncthreads();
     const int per = (cnt + 3) >> 2;
     const int b = min(w * per, cnt), e = min(b + per, cnt);
-    surface_scan_nearest(qx, qy, qz, st, b, e, base, best, bidx);
+    if (GATED) surface_scan_nearest_compatible(qx, qy, qz, ux, uy, uz, cc, st, b, e, base, best, bidx);
+    else surface_scan_nearest(qx, qy, qz, st, b, e, base, best, bidx);
   }
   sd[w][lane] = best;
   si[w][lane] = bidx;
@@ -500,14 +536,17 @@ __global__ __launch_bounds__(256) void mesh3d_surface_near_kernel(SurfaceTermArg
   }
 }
 
-// one query per thread: the closest point on the face its key names
-template <int ROLE>
+// one query per thread: the closest point on the face its key names.  GATED: a query is DROPPED when its key is all ones (no
+// face, or none compatible), when d^2 > tau^2, or (ROLE 0) by the boundary rule; a dropped query leaves d^2 = 0, a zero residual
+// and zero weights -- mesh3d_surface_grad_kernel runs unchanged -- and face -1; the block's kept count goes beside its sum of d^2
+template <int ROLE, bool GATED>
 __global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceTermArgs a) {
   __shared__ float red[16];
   const int n = blockIdx.y;
   const int nq = ROLE == 0 ? a.V : a.S;
   const int qi = blockIdx.x * kMeshBlock + threadIdx.x;
   float d2 = 0.f;
+  int kept = 0;
   if (qi < nq) {
     const size_t o = (size_t)n * nq + qi;
     const float* q = (ROLE == 0 ? a.verts : a.points) + 3 * o;
@@ -524,8 +563,27 @@ __global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceT
       const float* corners = a.verts + (size_t)n * a.V * 3;
       tri = make_scan_tri(corners + 3 * (size_t)fc[0], corners + 3 * (size_t)fc[1], corners + 3 * (size_t)fc[2]);
     }
-    const TriHit h = point_scan_tri_closest(q[0], q[1], q[2], tri);
-    d2 = key == ~0ull ? h.d2 : __uint_as_float((unsigned)(key >> 32));   // the scan's own bits
+    TriHit h;
+    if (GATED) {
+      const TriHitWhere hw = point_scan_tri_closest_where(q[0], q[1], q[2], tri);
+      h = hw.h;
+      d2 = __uint_as_float((unsigned)(key >> 32));
+      bool keep = key != ~0ull && (int)(unsigned)(key & 0xFFFFFFFFull) < nf;
+      keep = keep && !(d2 > (ROLE == 0 ? a.tau2_v : a.tau2_p));
+      if (ROLE == 0 && a.bflags != nullptr) keep = keep && !boundary_match(a.bflags[f0 + face], hw.winner, hw.t);
+      if (!keep) {
+        d2 = 0.f;
+        face = -1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) h.b[k] = h.r[k] = 0.f;
+      }
+      kept = keep ? 1 : 0;
+      unsigned char* ok = ROLE == 0 ? a.vert_kept : a.point_kept;
+      if (ok != nullptr) ok[o] = (unsigned char)kept;
+    } else {
+      h = point_scan_tri_closest(q[0], q[1], q[2], tri);
+      d2 = key == ~0ull ? h.d2 : __uint_as_float((unsigned)(key >> 32));   // the scan's own bits
+    }
     if (ROLE == 0) {
       a.res_v[3 * o] = h.r[0];
       a.res_v[3 * o + 1] = h.r[1];
@@ -555,6 +613,23 @@ __global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceT
   }
   const float tot = block_sum(d2, red);
   if (threadIdx.x == 0) (ROLE == 0 ? a.part_vs : a.part_ps)[(size_t)n * gridDim.x + blockIdx.x] = tot;
+  if (GATED) {
+    const int cnt = __syncthreads_count(kept);      // (an integer count: no order to fix)
+    if (threadIdx.x == 0) (ROLE == 0 ? a.part_kv : a.part_kp)[(size_t)n * gridDim.x + blockIdx.x] = cnt;
+  }
+}
+
+// the unit normal of every fitted vertex, one per thread: a gather over its incident faces in ascending face index, no atomics
+__global__ __launch_bounds__(kMeshBlock) void mesh3d_vertex_normal_kernel(SurfaceTermArgs a) {
+  const int n = blockIdx.y;
+  const int v = blockIdx.x * kMeshBlock + threadIdx.x;
+  if (v >= a.V) return;
+  float u[3];
+  vertex_normal(a.verts + (size_t)n * a.V * 3, a.faces, a.vf_off, a.vf, v, u);
+  float* dst = a.normals_out + ((size_t)n * a.V + v) * 3;
+  dst[0] = u[0];
+  dst[1] = u[1];
+  dst[2] = u[2];
 }
 
 // the term's gradient of one vertex in one thread: 2 w_vs / (N V) r_v  -  2 w_ps / (N S) sum over the points whose face has
@@ -630,6 +705,20 @@ __global__ __launch_bounds__(256) void mesh3d_surface_reduce_kernel(SurfaceTermA
     if (a.rows != nullptr) {
       a.rows[2 * n] = sp;
       a.rows[2 * n + 1] = sv;
+    }
+    if (a.kept != nullptr) {
+      // counted by the gated hit kernels; where the ungated one ran nothing was dropped and nothing counted: every query
+      int kp = a.w_ps > 0.f ? a.S : 0, kv = a.w_vs > 0.f ? a.V : 0;
+      if (a.part_kp != nullptr) {
+        kp = 0;
+        for (int b = 0; b < a.hp; ++b) kp += a.part_kp[(size_t)n * a.hp + b];
+      }
+      if (a.part_kv != nullptr) {
+        kv = 0;
+        for (int b = 0; b < a.hv; ++b) kv += a.part_kv[(size_t)n * a.hv + b];
+      }
+      a.kept[2 * n] = kp;
+      a.kept[2 * n + 1] = kv;
     }
   }
   tp = block_sum(tp, red);

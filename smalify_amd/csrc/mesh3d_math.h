@@ -125,6 +125,16 @@ struct alignas(16) ScanTri {
 SMALFIT_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) { return fmaf(az, bz, fmaf(ay, by, ax * bx)); }
 SMALFIT_HD float recip_or_zero(float x) { return x > 0.f ? 1.0f / x : 0.f; }
 
+// the record normal n = (b - a) x (c - a), unnormalised: the one expression behind ScanTri's n and the query normals of the
+// gated surface term (face_unit_normal, vertex_normal below)
+SMALFIT_HD void scan_tri_normal(const float* a, const float* b, const float* c, float n[3]) {
+  const float e0[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+  const float ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+  n[0] = e0[1] * ac[2] - e0[2] * ac[1];
+  n[1] = e0[2] * ac[0] - e0[0] * ac[2];
+  n[2] = e0[0] * ac[1] - e0[1] * ac[0];
+}
+
 SMALFIT_HD ScanTri make_scan_tri(const float* a, const float* b, const float* c) {
   ScanTri t;
   t.ax = a[0]; t.ay = a[1]; t.az = a[2];
@@ -133,8 +143,8 @@ SMALFIT_HD ScanTri make_scan_tri(const float* a, const float* b, const float* c)
   const float e0[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
   const float e1[3] = {c[0] - b[0], c[1] - b[1], c[2] - b[2]};
   const float e2[3] = {a[0] - c[0], a[1] - c[1], a[2] - c[2]};
-  const float ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-  const float n[3] = {e0[1] * ac[2] - e0[2] * ac[1], e0[2] * ac[0] - e0[0] * ac[2], e0[0] * ac[1] - e0[1] * ac[0]};
+  float n[3];
+  scan_tri_normal(a, b, c, n);
   t.nx = n[0]; t.ny = n[1]; t.nz = n[2];
   t.inv_ab = recip_or_zero(dot3(e0[0], e0[1], e0[2], e0[0], e0[1], e0[2]));
   t.inv_bc = recip_or_zero(dot3(e1[0], e1[1], e1[2], e1[0], e1[1], e1[2]));
@@ -200,7 +210,15 @@ struct TriHit {
   float r[3];   // p - (closest point)
 };
 
-SMALFIT_HD TriHit point_scan_tri_closest(float px, float py, float pz, const ScanTri& t) {
+// ... and WHICH candidate won (0 ab, 1 bc, 2 ca, 3 plane) with its clamped parameter (0 for the plane): what the boundary rule
+// of the gated term asks.  point_scan_tri_closest is this function without the two: its outputs keep their bits
+struct TriHitWhere {
+  TriHit h;
+  int winner;
+  float t;
+};
+
+SMALFIT_HD TriHitWhere point_scan_tri_closest_where(float px, float py, float pz, const ScanTri& t) {
   const float pax = px - t.ax, pay = py - t.ay, paz = pz - t.az;
   const float pbx = px - t.bx, pby = py - t.by, pbz = pz - t.bz;
   const float pcx = px - t.cx, pcy = py - t.cy, pcz = pz - t.cz;
@@ -232,7 +250,10 @@ SMALFIT_HD TriHit point_scan_tri_closest(float px, float py, float pz, const Sca
   const float ssum = s0 + s1 + s2;
   const bool kp = inside & (dp < sel2) & (ssum > 0.f);
   const float is = kp ? 1.0f / ssum : 0.f, k = h * t.inv_nn;
-  TriHit o;
+  TriHitWhere ow;
+  ow.winner = kp ? 3 : (k2 ? 2 : (k1 ? 1 : 0));
+  ow.t = kp ? 0.f : (k2 ? t2 : (k1 ? t1 : t0));
+  TriHit& o = ow.h;
   o.d2 = inside ? fminf(dp, dseg) : dseg;
   o.b[0] = kp ? s1 * is : (k2 ? t2 : (k1 ? 0.f : 1.0f - t0));
   o.b[1] = kp ? s2 * is : (k2 ? 0.f : (k1 ? 1.0f - t1 : t0));
@@ -240,7 +261,11 @@ SMALFIT_HD TriHit point_scan_tri_closest(float px, float py, float pz, const Sca
   o.r[0] = kp ? k * t.nx : (k2 ? r2x : (k1 ? r1x : r0x));
   o.r[1] = kp ? k * t.ny : (k2 ? r2y : (k1 ? r1y : r0y));
   o.r[2] = kp ? k * t.nz : (k2 ? r2z : (k1 ? r1z : r0z));
-  return o;
+  return ow;
+}
+
+SMALFIT_HD TriHit point_scan_tri_closest(float px, float py, float pz, const ScanTri& t) {
+  return point_scan_tri_closest_where(px, py, pz, t).h;
 }
 
 SMALFIT_HD TriHit point_triangle_closest(const float* p, const float* a, const float* b, const float* c) {
@@ -259,6 +284,75 @@ SMALFIT_HD void surface_scan_nearest(float px, float py, float pz, const ScanTri
       best_idx = index_base + j;
     }
   }
+}
+
+// ---- the gates of the surface term (smalfit_surface_gate_args; worded in include/smalfit.h) ---------------------------------
+// Compatibility of a query's unit normal u with a record's unnormalised normal n: the signed squared cosine
+// g |g| / |n|^2, g = <u, n>, against c |c| -- monotone in the cosine, one branch-free expression, no square root in the scan.
+// A degenerate record (inv_nn = 0) or a zero u gives 0: compatible exactly when c <= 0.  A NaN compares false: incompatible
+SMALFIT_HD float signed_sq_cos(float ux, float uy, float uz, float nx, float ny, float nz, float inv_nn) {
+  const float g = dot3(ux, uy, uz, nx, ny, nz);
+  return g * fabsf(g) * inv_nn;
+}
+SMALFIT_HD float cos_threshold(float c) { return c * fabsf(c); }
+SMALFIT_HD bool normal_compatible(float ux, float uy, float uz, float nx, float ny, float nz, float inv_nn, float cc) {
+  return signed_sq_cos(ux, uy, uz, nx, ny, nz, inv_nn) >= cc;
+}
+
+// surface_scan_nearest over the compatible records only (cc = cos_threshold(c)): the same strict '<', the same key
+SMALFIT_HD void surface_scan_nearest_compatible(float px, float py, float pz, float ux, float uy, float uz, float cc, const ScanTri* t,
+                                                int begin, int end, int index_base, float& best, int& best_idx) {
+#pragma unroll 2
+  for (int j = begin; j < end; ++j) {
+    const float d2 = point_scan_tri_dist2(px, py, pz, t[j]);
+    const bool ok = normal_compatible(ux, uy, uz, t[j].nx, t[j].ny, t[j].nz, t[j].inv_nn, cc);
+    if (ok & (d2 < best)) {
+      best = d2;
+      best_idx = index_base + j;
+    }
+  }
+}
+
+// Boundary rule.  flags of the winning face (mesh3d_topology.h::boundary_flags): bits 0-2 the edges ab, bc, ca used by no other
+// face, bits 3-5 the corners a, b, c that end such an edge.  A match is on the boundary when its winning candidate is a segment
+// and that segment is a boundary edge, or its clamped parameter is exactly 0 / exactly 1 and the segment's start / end corner is
+// a boundary vertex (segment k runs from corner k to corner (k + 1) % 3)
+SMALFIT_HD bool boundary_match(unsigned flags, int winner, float t) {
+  if (winner > 2) return false;
+  const int start = winner, end = winner == 2 ? 0 : winner + 1;
+  const bool edge = (flags >> winner) & 1u;
+  const bool at_start = (t == 0.f) & (((flags >> (3 + start)) & 1u) != 0u);
+  const bool at_end = (t == 1.0f) & (((flags >> (3 + end)) & 1u) != 0u);
+  return edge | at_start | at_end;
+}
+
+// v / |v|, the zero vector for a zero (or NaN) length
+SMALFIT_HD void unit_or_zero(const float v[3], float out[3]) {
+  const float len = sqrtf(dot3(v[0], v[1], v[2], v[0], v[1], v[2]));
+  const float inv = len > 0.f ? 1.0f / len : 0.f;
+  out[0] = v[0] * inv;
+  out[1] = v[1] * inv;
+  out[2] = v[2] * inv;
+}
+// the unit normal of a face: its record normal over its length (a target point carries the one of the face it was sampled on)
+SMALFIT_HD void face_unit_normal(const float* a, const float* b, const float* c, float out[3]) {
+  float n[3];
+  scan_tri_normal(a, b, c, n);
+  unit_or_zero(n, out);
+}
+// the normal of fitted vertex v: the sum of the record normals of its incident faces (CSR of mesh3d_topology.h, ascending face
+// index) over its length
+SMALFIT_HD void vertex_normal(const float* verts, const int* faces, const int* vf_off, const int* vf, int v, float out[3]) {
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int i = vf_off[v]; i < vf_off[v + 1]; ++i) {
+    const int* fc = faces + 3 * (size_t)vf[i];
+    float n[3];
+    scan_tri_normal(verts + 3 * (size_t)fc[0], verts + 3 * (size_t)fc[1], verts + 3 * (size_t)fc[2], n);
+    s[0] += n[0];
+    s[1] += n[1];
+    s[2] += n[2];
+  }
+  unit_or_zero(s, out);
 }
 
 // what a point -> surface query leaves for the vertices of the face it chose (48 bytes: three 16-byte rows, broadcast LDS reads

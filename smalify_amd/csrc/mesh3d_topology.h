@@ -20,6 +20,8 @@ struct MeshTopologyHost {
                               //        faces of an edge in ascending face order; an edge with k faces gives k(k-1)/2 rows
   std::vector<int> inc_off;   // [V+1]  vertex -> the (pair * 4 + role) slots it occupies, ascending
   std::vector<int> inc;       // [4P]
+  std::vector<int> vf_off;    // [V+1]  vertex -> the faces it is a corner of, ascending face index (the vertex normals of the
+  std::vector<int> vf;        // [3F]   gated surface term are gathered over it in that order)
 };
 
 inline MeshTopologyHost build_mesh_topology(int V, int F, const int* faces) {
@@ -88,7 +90,54 @@ inline MeshTopologyHost build_mesh_topology(int V, int F, const int* faces) {
     std::vector<int> fill(t.inc_off.begin(), t.inc_off.end() - 1);
     for (size_t s = 0; s < t.pairs.size(); ++s) t.inc[fill[t.pairs[s]]++] = (int)s;
   }
+  // vertex -> incident faces (faces visited in ascending order: every row is ascending)
+  t.vf_off.assign(V + 1, 0);
+  for (int i = 0; i < 3 * F; ++i) ++t.vf_off[faces[i] + 1];
+  for (int v = 0; v < V; ++v) t.vf_off[v + 1] += t.vf_off[v];
+  t.vf.assign((size_t)3 * F, 0);
+  {
+    std::vector<int> fill(t.vf_off.begin(), t.vf_off.end() - 1);
+    for (int f = 0; f < F; ++f)
+      for (int k = 0; k < 3; ++k) t.vf[fill[faces[3 * f + k]]++] = f;
+  }
   return t;
+}
+
+// Where a mesh ends: one byte per face.  Bits 0-2: the edge ab, bc, ca is a boundary edge -- its undirected vertex pair is used by
+// exactly one face of the mesh (an edge shared by three faces is not one).  Bits 3-5: the corner a, b, c is a boundary vertex, an
+// end point of some boundary edge.  What the boundary rule of the gated surface term reads (mesh3d_math.h::boundary_match)
+inline std::vector<uint8_t> boundary_flags(int V, int F, const int* faces) {
+  if (V <= 0 || F <= 0 || faces == nullptr) throw std::invalid_argument("boundary flags: empty mesh");
+  struct Use {
+    int lo, hi, slot;   // slot = 3 * face + edge
+  };
+  std::vector<Use> use;
+  use.reserve((size_t)3 * F);
+  for (int f = 0; f < F; ++f)
+    for (int k = 0; k < 3; ++k) {
+      const int p = faces[3 * f + k], q = faces[3 * f + (k + 1) % 3];
+      if (p < 0 || p >= V || q < 0 || q >= V) throw std::invalid_argument("boundary flags: face index out of range");
+      use.push_back({std::min(p, q), std::max(p, q), 3 * f + k});
+    }
+  std::sort(use.begin(), use.end(), [](const Use& a, const Use& b) {
+    if (a.lo != b.lo) return a.lo < b.lo;
+    if (a.hi != b.hi) return a.hi < b.hi;
+    return a.slot < b.slot;
+  });
+  std::vector<uint8_t> flags((size_t)F, 0), on_rim((size_t)V, 0);
+  for (size_t i = 0; i < use.size();) {
+    size_t j = i;
+    while (j < use.size() && use[j].lo == use[i].lo && use[j].hi == use[i].hi) ++j;
+    if (j - i == 1) {
+      flags[use[i].slot / 3] |= (uint8_t)(1u << (use[i].slot % 3));
+      on_rim[use[i].lo] = on_rim[use[i].hi] = 1;
+    }
+    i = j;
+  }
+  for (int f = 0; f < F; ++f)
+    for (int k = 0; k < 3; ++k)
+      if (on_rim[faces[3 * f + k]]) flags[f] |= (uint8_t)(1u << (3 + k));
+  return flags;
 }
 
 // cumulative-area thresholds of one target mesh for sample_face(): thr[f] = floor(2^32 * area(0..f) / total), the last

@@ -28,6 +28,11 @@ struct smalfit_mesh_objective {
   unsigned long long* surf_keys = nullptr;
   SurfaceHit* surf_hits = nullptr;
   float *surf_res = nullptr, *surf_part_ps = nullptr, *surf_part_vs = nullptr, *surf_part_dtr = nullptr;
+  // its gates only: vertex -> incident faces of the fitted topology (in the tables' allocation), the query normals of both
+  // directions, per-block kept counts
+  const int *vf_off = nullptr, *vf = nullptr;
+  float *surf_vnorm = nullptr, *surf_pnorm = nullptr;
+  int *surf_part_kp = nullptr, *surf_part_kv = nullptr;
 };
 
 struct smalfit_mesh_targets {
@@ -35,15 +40,19 @@ struct smalfit_mesh_targets {
   void* blob = nullptr;
   const ScanTri* tris = nullptr;   // packed [sum F]: the staged records of the surface term's vertex -> surface scan, in the blob
   int max_faces = 0;               // of the largest mesh: what that scan's slice count is sized by
+  const unsigned char* bflags = nullptr;   // packed [sum F]: boundary_flags of every mesh, beside the records
 };
 
 // the launches of the surface term on `verts`; the block validated by the callers.  In a step the term's gradient is ADDED to
 // the step's d verts, its planar copy (stride Vp) and d trans, after run_mesh_objective has written them: one float32 addition
 // per coordinate, the addition Stage.step_unfused performs on the stand-alone call's outputs -- the two paths form the same bits
+// With a gate block (validated by the callers; point_normals: the caller's or the sampler's) the gated instantiations take the
+// place of the ungated ones where plan_surface_gates says so; with none, or every gate off, the launches are those of before
 static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_targets* t, hipStream_t st, const smalfit_surface_term_args* a,
                             const float* verts, const float* points, int num_points, float* acc_dverts = nullptr,
                             float* acc_planar = nullptr, int Vp = 0, float* acc_dtrans = nullptr,
-                            const float* step_losses = nullptr) {
+                            const float* step_losses = nullptr, const smalfit_surface_gate_args* gate = nullptr,
+                            const float* point_normals = nullptr) {
   SurfaceTermArgs k{};
   k.N = a->num_meshes; k.V = m->t.V; k.F = m->num_faces;
   k.w_ps = mesh_weight(a->w_point_surface); k.w_vs = mesh_weight(a->w_vert_surface);
@@ -60,22 +69,43 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
   k.acc_dverts = acc_dverts; k.acc_planar = acc_planar; k.Vp = Vp; k.acc_dtrans = acc_dtrans;
   k.dverts = a->dverts; k.dtrans = a->dtrans; k.losses = a->losses; k.rows = a->rows;
   k.step_losses = step_losses; k.step_total = step_losses ? a->step_total : nullptr;
+  const SurfaceGatePlan gp = plan_surface_gates(gate, k.w_ps > 0.f, k.w_vs > 0.f);
+  k.cc_v = gp.cc_vert; k.cc_p = gp.cc_point; k.tau2_v = gp.tau2_vert; k.tau2_p = gp.tau2_point;
+  k.vf_off = m->vf_off; k.vf = m->vf;
+  if (gate) k.kept = gate->kept;
+  if (gp.any) {
+    if (k.w_vs > 0.f) { k.part_kv = m->surf_part_kv; k.vert_kept = gate->vert_kept; }
+    if (k.w_ps > 0.f) { k.part_kp = m->surf_part_kp; k.point_kept = gate->point_kept; }
+    if (gp.boundary) k.bflags = t->bflags;
+    if (gp.cos_vert) { k.normals_out = gate->vert_normals ? gate->vert_normals : m->surf_vnorm; k.normals_v = k.normals_out; }
+    if (gp.cos_point) k.normals_p = point_normals;
+  }
   // the keys of the directions that run, all ones: the vertices' come first, the points' behind them
   unsigned long long* first = k.w_vs > 0.f ? k.keys_v : k.keys_p;
   const size_t keys = (size_t)k.N * ((k.w_vs > 0.f ? (size_t)k.V : 0) + (k.w_ps > 0.f ? (size_t)k.S : 0));
   if (keys > 0) HIP_OK(hipMemsetAsync(first, 0xFF, keys * sizeof(unsigned long long), st));
   if (k.w_vs > 0.f) {
     const Grid3 g = surface_near_grid(k.V, t->max_faces, k.N);
-    mesh3d_surface_near_kernel<0><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    if (gp.cos_vert) {
+      const Grid2 gn = vertex_normal_grid(k.V, k.N);
+      mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
+      LAUNCH_OK("mesh3d_vertex_normal_kernel");
+      mesh3d_surface_near_kernel<0, true><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    } else {
+      mesh3d_surface_near_kernel<0, false><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    }
     LAUNCH_OK("mesh3d_surface_near_kernel<0>");
-    mesh3d_surface_hit_kernel<0><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
+    if (gp.any) mesh3d_surface_hit_kernel<0, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
+    else mesh3d_surface_hit_kernel<0, false><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
     LAUNCH_OK("mesh3d_surface_hit_kernel<0>");
   }
   if (k.w_ps > 0.f) {
     const Grid3 g = surface_near_grid(k.S, k.F, k.N);
-    mesh3d_surface_near_kernel<1><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    if (gp.cos_point) mesh3d_surface_near_kernel<1, true><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    else mesh3d_surface_near_kernel<1, false><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
     LAUNCH_OK("mesh3d_surface_near_kernel<1>");
-    mesh3d_surface_hit_kernel<1><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
+    if (gp.any) mesh3d_surface_hit_kernel<1, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
+    else mesh3d_surface_hit_kernel<1, false><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
     LAUNCH_OK("mesh3d_surface_hit_kernel<1>");
   }
   mesh3d_surface_grad_kernel<<<dim3(gg.x, gg.y), 64 * kSurfaceGradWaves, 0, st>>>(k);
@@ -125,11 +155,13 @@ static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num
 }
 
 // sample_points_from_meshes: num_points per target mesh into points (N,S,3)
+// ... and, with `normals` (N,S,3), the unit normal of every point's face
 static int launch_mesh_sampler(const smalfit_mesh_targets* t, hipStream_t st, int num_points, unsigned long long seed,
-                               unsigned int iteration, float* points) {
+                               unsigned int iteration, float* points, float* normals = nullptr) {
   const Grid2 grid = mesh_sample_grid(num_points, t->d.N);
-  mesh3d_sample_kernel<<<dim3(grid.x, grid.y), 256, 0, st>>>(t->d, num_points, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32),
-                                                            iteration, points);
+  const uint32_t lo = (uint32_t)(seed & 0xFFFFFFFFull), hi = (uint32_t)(seed >> 32);
+  if (normals) mesh3d_sample_kernel<true><<<dim3(grid.x, grid.y), 256, 0, st>>>(t->d, num_points, lo, hi, iteration, points, normals);
+  else mesh3d_sample_kernel<false><<<dim3(grid.x, grid.y), 256, 0, st>>>(t->d, num_points, lo, hi, iteration, points, nullptr);
   LAUNCH_OK("mesh3d_sample_kernel");
   return 0;
 }
@@ -154,6 +186,8 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   const size_t o_io = b.add(h.inc_off.data(), h.inc_off.size() * sizeof(int));
   const size_t o_in = b.add(h.inc.data(), h.inc.size() * sizeof(int));
   const size_t o_fc = b.add(faces, (size_t)num_faces * 3 * sizeof(int));   // (build_mesh_topology has checked every index)
+  const size_t o_vo = b.add(h.vf_off.data(), h.vf_off.size() * sizeof(int));
+  const size_t o_vf = b.add(h.vf.data(), h.vf.size() * sizeof(int));
   unsigned char* base = upload_blob(b, "smalfit_mesh_objective_create");
   if (!base) return 1;
   auto* m = new smalfit_mesh_objective();
@@ -163,6 +197,7 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   m->t.pairs = (const int*)(base + o_pr);
   m->t.inc_off = (const int*)(base + o_io); m->t.inc = (const int*)(base + o_in);
   m->faces = (const int*)(base + o_fc); m->num_faces = num_faces;
+  m->vf_off = (const int*)(base + o_vo); m->vf = (const int*)(base + o_vf);
   m->max_meshes = max_meshes; m->max_points = max_points;
   const size_t N = max_meshes, V = h.V, P = std::max(h.P, 1), S = max_points;
   const MeshGrids grids = mesh_grids(max_points, h.V, h.P);   // (bx: the capacity; an evaluation's own follows its num_points)
@@ -192,6 +227,10 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   w.field(m->surf_part_ps, N * (size_t)surface_hit_grid((int)S, 1).x);
   w.field(m->surf_part_vs, N * (size_t)surface_hit_grid((int)V, 1).x);
   w.field(m->surf_part_dtr, N * m->by * 3);
+  w.field(m->surf_vnorm, N * V * 3);
+  w.field(m->surf_pnorm, N * S * 3);
+  w.field(m->surf_part_kp, N * (size_t)surface_hit_grid((int)S, 1).x);
+  w.field(m->surf_part_kv, N * (size_t)surface_hit_grid((int)V, 1).x);
   auto bail = [&](const char* what) {
     smalfit_mesh_objective_destroy(m);
     return refused("smalfit_mesh_objective_create", what);
@@ -258,6 +297,12 @@ int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const in
     for (int f = foff[n]; f < foff[n + 1]; ++f)   // (area_thresholds has checked every index)
       tris[f] = make_scan_tri(base + 3 * (size_t)faces[3 * f], base + 3 * (size_t)faces[3 * f + 1], base + 3 * (size_t)faces[3 * f + 2]);
   }
+  // where every target ends, for the boundary rule of the gated term (area_thresholds has checked every index)
+  std::vector<uint8_t> bflags((size_t)foff[num_meshes]);
+  for (int n = 0; n < num_meshes; ++n) {
+    const std::vector<uint8_t> fl = boundary_flags(vert_counts[n], face_counts[n], faces + 3 * (size_t)foff[n]);
+    std::copy(fl.begin(), fl.end(), bflags.begin() + foff[n]);
+  }
   Blob b;
   const size_t o_vo = b.add(voff.data(), voff.size() * sizeof(int));
   const size_t o_fo = b.add(foff.data(), foff.size() * sizeof(int));
@@ -265,6 +310,7 @@ int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const in
   const size_t o_f = b.add(faces, (size_t)foff[num_meshes] * 3 * sizeof(int));
   const size_t o_t = b.add(thr.data(), thr.size() * sizeof(uint32_t));
   const size_t o_s = b.add(tris.data(), tris.size() * sizeof(ScanTri));
+  const size_t o_b = b.add(bflags.data(), bflags.size());
   unsigned char* base = upload_blob(b, "smalfit_mesh_targets_create");
   if (!base) return 1;
   auto* t = new smalfit_mesh_targets();
@@ -274,6 +320,7 @@ int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const in
   t->d.verts = (const float*)(base + o_v); t->d.faces = (const int*)(base + o_f);
   t->d.thr = (const uint32_t*)(base + o_t);
   t->tris = (const ScanTri*)(base + o_s); t->max_faces = max_faces;
+  t->bflags = (const unsigned char*)(base + o_b);
   *out = t;
   return 0;
 }
@@ -288,6 +335,12 @@ int smalfit_mesh_targets_sample(smalfit_mesh_targets* t, void* stream, int num_p
                                 unsigned int iteration, float* points) {
   if (refused("smalfit_mesh_targets_sample", mesh_sample_refusal(t && points, num_points))) return 1;
   return launch_mesh_sampler(t, (hipStream_t)stream, num_points, seed, iteration, points);
+}
+
+int smalfit_mesh_targets_sample_normals(smalfit_mesh_targets* t, void* stream, int num_points, unsigned long long seed,
+                                        unsigned int iteration, float* points, float* normals) {
+  if (refused("smalfit_mesh_targets_sample_normals", mesh_sample_refusal(t && points && normals, num_points))) return 1;
+  return launch_mesh_sampler(t, (hipStream_t)stream, num_points, seed, iteration, points, normals);
 }
 
 // ---- how good a fit is: point-to-surface distances both ways, per mesh -------------------------------------------------
@@ -318,11 +371,19 @@ int smalfit_mesh_score(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void*
 
 // ---- the surface term alone --------------------------------------------------------------------------------------------
 int smalfit_mesh_surface_eval(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream, const smalfit_surface_term_args* a) {
-  if (refused("smalfit_mesh_surface_eval", null_argument_refusal(m && a))) return 1;
-  if (refused("smalfit_mesh_surface_eval", surface_term_args_refusal(a, SurfaceTermFacts{m->max_meshes, m->max_points, t != nullptr,
-                                                                                         t ? t->d.N : 0, false, 0, 0, false})))
+  return smalfit_mesh_surface_eval_gated(m, t, stream, a, nullptr);
+}
+
+int smalfit_mesh_surface_eval_gated(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream, const smalfit_surface_term_args* a,
+                                    const smalfit_surface_gate_args* g) {
+  const char* who = g ? "smalfit_mesh_surface_eval_gated" : "smalfit_mesh_surface_eval";
+  if (refused(who, null_argument_refusal(m && a))) return 1;
+  if (refused(who, surface_term_args_refusal(a, SurfaceTermFacts{m->max_meshes, m->max_points, t != nullptr, t ? t->d.N : 0, false, 0, 0,
+                                                                 false})))
     return 1;
-  return run_surface_term(m, t, (hipStream_t)stream, a, a->verts, a->points, a->num_points);
+  if (g && refused(who, surface_gate_args_refusal(g, a, SurfaceGateFacts{t != nullptr, false, false}))) return 1;
+  return run_surface_term(m, t, (hipStream_t)stream, a, a->verts, a->points, a->num_points, nullptr, nullptr, 0, nullptr, nullptr, g,
+                          g ? g->point_normals : nullptr);
 }
 
 // ---- Stage.step in one call ------------------------------------------------------------------------------------------
@@ -333,7 +394,12 @@ int smalfit_fit3d_step(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mes
 
 int smalfit_fit3d_step_surface(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
                                const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf) {
-  const char* who = sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
+  return smalfit_fit3d_step_gated(e, m, t, stream, a, sf, nullptr);
+}
+
+int smalfit_fit3d_step_gated(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
+                             const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate) {
+  const char* who = gate ? "smalfit_fit3d_step_gated" : sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
   if (refused(who, null_argument_refusal(e && m && a))) return 1;
   const ModelDev& md = e->model->dev;
   if (refused(who, fit3d_args_refusal(a, Fit3dFacts{e->maxM, md.V, md.NBall, m->max_meshes, m->max_points, m->t.V,
@@ -342,6 +408,8 @@ int smalfit_fit3d_step_surface(smalfit_engine* e, smalfit_mesh_objective* m, sma
   if (sf && refused(who, surface_term_args_refusal(sf, SurfaceTermFacts{m->max_meshes, m->max_points, t != nullptr, t ? t->d.N : 0, true,
                                                                         a->num_meshes, a->num_points, a->points != nullptr})))
     return 1;
+  if (gate && !sf) return refused(who, "a gate block needs the surface block it gates");
+  if (gate && refused(who, surface_gate_args_refusal(gate, sf, SurfaceGateFacts{t != nullptr, true, a->points != nullptr}))) return 1;
   const bool surface = surface_term_on(sf);   // a block with both weights <= 0 is the step without it: nothing of it is launched or written
   const Fit3dPlan plan = plan_fit3d(a, md.V, surface && sf->w_point_surface > 0.f);
   const int N = a->num_meshes, nb = a->num_betas, S = a->num_points;
@@ -354,9 +422,13 @@ int smalfit_fit3d_step_surface(smalfit_engine* e, smalfit_mesh_objective* m, sma
 
   // target points of this iteration
   const float* pts = a->points;
+  const float* pnormals = gate ? gate->point_normals : nullptr;
   if (plan.points == Fit3dPoints::SampleToCaller || plan.points == Fit3dPoints::SampleToObjective) {
     float* dst = plan.points == Fit3dPoints::SampleToCaller ? a->points_out : m->points;
-    if (launch_mesh_sampler(t, st, S, a->seed, a->iteration, dst)) return 1;
+    // (with the point direction's compatibility test on, the normals are drawn with the points)
+    const bool draw_normals = surface && plan_surface_gates(gate, sf->w_point_surface > 0.f, false).cos_point;
+    if (launch_mesh_sampler(t, st, S, a->seed, a->iteration, dst, draw_normals ? m->surf_pnorm : nullptr)) return 1;
+    if (draw_normals) pnormals = m->surf_pnorm;
     pts = dst;
   } else if (plan.points == Fit3dPoints::CallersCopied) {
     HIP_OK(hipMemcpyAsync(a->points_out, a->points, (size_t)N * S * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -369,7 +441,7 @@ int smalfit_fit3d_step_surface(smalfit_engine* e, smalfit_mesh_objective* m, sma
                          m->dverts, m->dtrans, e->verts, md.Vp, plan.planar_vertex_grad ? e->dext : nullptr)) return 1;
   // the surface term at the vertices the objective composed; its gradient joins the step's in all three places it is read from
   if (surface && run_surface_term(m, t, st, sf, a->verts_out ? a->verts_out : m->verts, pts, S, m->dverts,
-                                  plan.planar_vertex_grad ? e->dext : nullptr, md.Vp, m->dtrans, a->losses)) return 1;
+                                  plan.planar_vertex_grad ? e->dext : nullptr, md.Vp, m->dtrans, a->losses, gate, pnormals)) return 1;
   if (!plan.any_trained) return 0;
 
   // back through the LBS (forward state is still in the engine)

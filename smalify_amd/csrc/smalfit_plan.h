@@ -423,6 +423,64 @@ inline const char* surface_term_args_refusal(const smalfit_surface_term_args* a,
   return nullptr;
 }
 
+// The gates of the surface term (smalfit_surface_gate_args): what a block switches on, in the form the kernels take it.
+// tau^2 and c |c| are formed here, once, in float32; an open truncation is tau2 = +inf (no d^2 exceeds it), an open
+// compatibility test is cos_* = false (the scan of that direction is the ungated instantiation and reads no normals)
+struct SurfaceGatePlan {
+  bool any;                    // some gate is on, or a kept mask is asked for: the gated hit kernels run and count
+  bool cos_point, cos_vert;    // the compatibility test of a direction is on
+  float cc_point, cc_vert;     // c |c|
+  float tau2_point, tau2_vert;
+  bool boundary;
+};
+inline bool surface_gate_dist_on(float tau) { return tau > 0.f && std::isfinite(tau); }
+inline bool surface_gate_cos_on(float c) { return c > -1.0f; }
+// of a block surface_gate_args_refusal accepts (g may be NULL: everything off); a gate of a skipped direction is off
+inline SurfaceGatePlan plan_surface_gates(const smalfit_surface_gate_args* g, bool point_dir, bool vert_dir) {
+  SurfaceGatePlan p{};
+  p.tau2_point = p.tau2_vert = INFINITY;
+  if (!g) return p;
+  p.cos_point = point_dir && surface_gate_cos_on(g->min_cos_point);
+  p.cos_vert = vert_dir && surface_gate_cos_on(g->min_cos_vert);
+  p.cc_point = g->min_cos_point * std::fabs(g->min_cos_point);
+  p.cc_vert = g->min_cos_vert * std::fabs(g->min_cos_vert);
+  if (point_dir && surface_gate_dist_on(g->max_dist_point)) p.tau2_point = g->max_dist_point * g->max_dist_point;
+  if (vert_dir && surface_gate_dist_on(g->max_dist_vert)) p.tau2_vert = g->max_dist_vert * g->max_dist_vert;
+  p.boundary = vert_dir && g->reject_boundary != 0;
+  p.any = p.cos_point || p.cos_vert || p.tau2_point != INFINITY || p.tau2_vert != INFINITY || p.boundary ||
+          (point_dir && g->point_kept) || (vert_dir && g->vert_kept);
+  return p;
+}
+
+// -> why the gated entry points refuse the gate block (the text behind "<entry point>: "), or nullptr; asked after
+// surface_term_args_refusal has accepted the term's block `a`
+struct SurfaceGateFacts {
+  bool targets;           // target meshes were given
+  bool step;              // the block rides on a step
+  bool step_has_points;   // ... whose points are the caller's
+};
+inline const char* surface_gate_args_refusal(const smalfit_surface_gate_args* g, const smalfit_surface_term_args* a,
+                                             const SurfaceGateFacts& f) {
+  if (g->struct_size != (unsigned)sizeof(smalfit_surface_gate_args))
+    return "smalfit_surface_gate_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (!(g->min_cos_point <= 1.0f)) return "min_cos_point must be <= 1 and not NaN";
+  if (!(g->min_cos_vert <= 1.0f)) return "min_cos_vert must be <= 1 and not NaN";
+  if (!g->kept) return "kept missing";
+  const bool vert_gate = g->reject_boundary != 0 || surface_gate_cos_on(g->min_cos_vert) || surface_gate_dist_on(g->max_dist_vert);
+  if (vert_gate && !f.targets) return "a vertex gate needs the target meshes";
+  const bool point_dir = a->w_point_surface > 0.f, vert_dir = a->w_vert_surface > 0.f;
+  const bool sampled = f.step && !f.step_has_points;
+  if (sampled && g->point_normals) return "point_normals must be NULL in a step that samples its points: it draws its own";
+  if (point_dir && surface_gate_cos_on(g->min_cos_point) && !sampled && !g->point_normals)
+    return "min_cos_point needs point_normals with the caller's points";
+  if (g->point_kept && !point_dir) return "point_kept given while the point direction is skipped";
+  if (g->vert_kept && !vert_dir) return "vert_kept given while the vertex direction is skipped";
+  if (g->vert_normals && !(vert_dir && surface_gate_cos_on(g->min_cos_vert))) return "vert_normals given without min_cos_vert";
+  return nullptr;
+}
+// mesh3d_vertex_normal_kernel: one vertex per thread
+inline Grid2 vertex_normal_grid(int V, int N) { return Grid2{mesh_element_blocks(V), N}; }
+
 // ------------------------------------------------------------------------------------------------
 // smalfit_fit3d_step: which blocks are refused, and what a step launches
 // ------------------------------------------------------------------------------------------------

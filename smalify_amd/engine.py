@@ -687,7 +687,8 @@ class MeshObjective:
         check(fn(self.handle, targets.handle, _stream(), C.byref(a)), "smalfit_mesh_score")
         return out
 
-    def surface(self, verts, targets, points, w_point_surface, w_vert_surface, correspondences=False):
+    def surface(self, verts, targets, points, w_point_surface, w_vert_surface, correspondences=False, gates=None,
+                point_normals=None):
         """The point-to-surface term both ways and its gradient (smalfit_mesh_surface_eval; the definition is this project's,
         include/smalfit.h): L_ps = mean over the points of d^2(point, fitted surface), L_vs = mean over the fitted vertices of
         d^2(vertex, target surface), term = w_point_surface L_ps + w_vert_surface L_vs; a weight <= 0 skips its direction.
@@ -696,8 +697,12 @@ class MeshObjective:
         -> dict of device tensors: losses (3,) = L_ps, L_vs, term; rows (N,2) = per mesh sum d^2 of the points | the vertices;
         dverts (N,V,3), dtrans (N,3) = the term's gradient; with correspondences, for every direction that ran, point_face (N,S)
         int32 / point_bary (N,S,3) on the fitted topology and vert_face (N,V) / vert_bary (N,V,3) on target mesh n, each with its
-        residual (point_residual, vert_residual: the query minus its closest point, as the gradient uses it)."""
-        fn = _lib.resolve(self.lib, "smalfit_mesh_surface_eval")
+        residual (point_residual, vert_residual: the query minus its closest point, as the gradient uses it).
+        gates: None, or a dict of max_dist_point, max_dist_vert, min_cos_point, min_cos_vert, reject_boundary (surface_gates();
+        smalfit_mesh_surface_eval_gated): which matches count on a partial scan.  min_cos_point needs point_normals (N,S,3), the
+        unit normals of the points (MeshTargets.sample_normals).  Adds kept (N,2) int32 = kept points | kept vertices, and for
+        every direction that ran point_kept (N,S) / vert_kept (N,V) uint8; vert_normals (N,V,3) when min_cos_vert is on."""
+        fn = _lib.resolve(self.lib, "smalfit_mesh_surface_eval_gated" if gates is not None else "smalfit_mesh_surface_eval")
         targets = getattr(targets, "_dev", targets)
         if targets is not None and not isinstance(targets, MeshTargets):
             raise SmalfitError("targets must be the MeshTargets the meshes are fitted to")
@@ -731,8 +736,51 @@ class MeshObjective:
                 out["vert_residual"] = torch.empty(N, V, 3, device=dev)
                 a.vert_face, a.vert_bary = C.c_void_p(out["vert_face"].data_ptr()), _ptr(out["vert_bary"])
                 a.vert_residual = _ptr(out["vert_residual"])
-        check(fn(self.handle, targets.handle if targets is not None else None, _stream(), C.byref(a)), "smalfit_mesh_surface_eval")
+        th = targets.handle if targets is not None else None
+        if gates is None:
+            check(fn(self.handle, th, _stream(), C.byref(a)), "smalfit_mesh_surface_eval")
+            return out
+        g = surface_gate_block(gates)
+        if point_normals is not None:
+            if tuple(point_normals.shape) != (N, S, 3) or point_normals.device != dev:
+                raise SmalfitError("point_normals must be (num_meshes, S, 3) on the device of verts")
+            g.point_normals = _ptr(point_normals)
+        out["kept"] = torch.zeros(N, 2, dtype=torch.int32, device=dev)
+        g.kept = C.c_void_p(out["kept"].data_ptr())
+        if w_point_surface > 0 and points is not None:
+            out["point_kept"] = torch.empty(N, S, dtype=torch.uint8, device=dev)
+            g.point_kept = C.c_void_p(out["point_kept"].data_ptr())
+        if w_vert_surface > 0:
+            out["vert_kept"] = torch.empty(N, V, dtype=torch.uint8, device=dev)
+            g.vert_kept = C.c_void_p(out["vert_kept"].data_ptr())
+            if g.min_cos_vert > -1.0:
+                out["vert_normals"] = torch.empty(N, V, 3, device=dev)
+                g.vert_normals = _ptr(out["vert_normals"])
+        check(fn(self.handle, th, _stream(), C.byref(a), C.byref(g)), "smalfit_mesh_surface_eval_gated")
         return out
+
+
+SURFACE_GATE_KEYS = ("max_dist_point", "max_dist_vert", "min_cos_point", "min_cos_vert", "reject_boundary")
+
+
+def surface_gates(gates=None):
+    """the gates of the surface term with every one off, overridden by `gates`; an unknown key raises"""
+    out = dict(max_dist_point=0.0, max_dist_vert=0.0, min_cos_point=-1.0, min_cos_vert=-1.0, reject_boundary=False)
+    for k, v in (gates or {}).items():
+        if k not in out:
+            raise KeyError("unknown surface gate %r (have %s)" % (k, sorted(out)))
+        out[k] = bool(v) if k == "reject_boundary" else float(v)
+    return out
+
+
+def surface_gate_block(gates):
+    """a smalfit_surface_gate_args with the switches of `gates` (a dict as surface_gates takes it); the pointers are the caller's"""
+    gd = surface_gates(gates)
+    g = _lib.SurfaceGateArgs()
+    g.max_dist_point, g.max_dist_vert = gd["max_dist_point"], gd["max_dist_vert"]
+    g.min_cos_point, g.min_cos_vert = gd["min_cos_point"], gd["min_cos_vert"]
+    g.reject_boundary = int(gd["reject_boundary"])
+    return g
 
 
 class MeshTargets:
@@ -778,3 +826,16 @@ class MeshTargets:
         check(self.lib.smalfit_mesh_targets_sample(self.handle, _stream(), int(num_points), int(seed) & (2 ** 64 - 1),
                                                    int(iteration) & 0xFFFFFFFF, _ptr(out)), "smalfit_mesh_targets_sample")
         return out
+
+    def sample_normals(self, num_points, seed, iteration, out=None, normals_out=None):
+        """-> (points, normals), both (N, num_points, 3): the points of sample() bit for bit, and with every point the unit
+        normal of the target face it lies on (smalfit_mesh_targets_sample_normals)"""
+        fn = _lib.resolve(self.lib, "smalfit_mesh_targets_sample_normals")
+        shape = (len(self), int(num_points), 3)
+        if out is None or tuple(out.shape) != shape:
+            out = torch.empty(*shape, device=self.device)
+        if normals_out is None or tuple(normals_out.shape) != shape:
+            normals_out = torch.empty(*shape, device=self.device)
+        check(fn(self.handle, _stream(), int(num_points), int(seed) & (2 ** 64 - 1), int(iteration) & 0xFFFFFFFF, _ptr(out),
+                 _ptr(normals_out)), "smalfit_mesh_targets_sample_normals")
+        return out, normals_out

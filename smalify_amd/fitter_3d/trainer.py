@@ -131,7 +131,7 @@ class Stage:
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes, mesh_names=[],
                  name="optimise", loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None,
-                 device="cuda", seed=0, iteration_offset=0):
+                 device="cuda", seed=0, iteration_offset=0, surface_gates=None):
         self.n_it = int(nits)
         self.name = name
         self.out_dir = out_dir
@@ -149,6 +149,9 @@ class Stage:
                 if k not in self.loss_weights:
                     raise KeyError("unknown loss weight %r (have %s)" % (k, sorted(self.loss_weights) + sorted(self.surface_weights)))
                 self.loss_weights[k] = float(v)
+        # the gates of the surface term for partial scans (include/smalfit.h): all off unless given, here or as a `surface_gates`
+        # block of the stage's YAML; an unknown key raises, as an unknown loss weight does
+        self.surface_gates = eng.surface_gates(surface_gates)
         if custom_lrs is not None:
             for attr in custom_lrs:
                 assert hasattr(smal_3d_fitter, attr), f"attr '{attr}' not in SMAL."
@@ -180,6 +183,9 @@ class Stage:
         self._args = None        # smalfit_fit3d_args, built on the first step
         self._surface_args = None      # smalfit_surface_term_args of step(), built with it when a surface weight is positive
         self._surface_losses = None
+        self._gate_args = None         # smalfit_surface_gate_args of step(), built with the surface block while a gate is on
+        self._surface_kept = None
+        self._point_normals = None
         self.consider_loss = lambda loss_name: self.loss_weights[f"w_{loss_name}"] > 0
 
     # ---- evaluation ----------------------------------------------------------------------------------------------
@@ -208,6 +214,20 @@ class Stage:
     def surface_on(self):
         return any(self.surface_weights[k] > 0 for k in _SURFACE_ORDER)
 
+    @property
+    def gates_on(self):
+        """some gate of the surface term is switched on (with all of them off a step is the ungated call)"""
+        g = self.surface_gates
+        return (g["reject_boundary"] or g["min_cos_point"] > -1 or g["min_cos_vert"] > -1 or
+                (g["max_dist_point"] > 0 and np.isfinite(g["max_dist_point"])) or
+                (g["max_dist_vert"] > 0 and np.isfinite(g["max_dist_vert"])))
+
+    @property
+    def last_surface_kept(self):
+        """device tensor (N,2) int32: the kept points | kept vertices of every mesh in the most recent gated evaluation or step;
+        None while the term or its gates are off"""
+        return self._surface_kept
+
     def _weights(self):
         return [self.loss_weights[k] for k in _WEIGHT_ORDER]
 
@@ -219,7 +239,13 @@ class Stage:
         ls = fit.log_beta_scales.detach().contiguous()
         theta = fit._pack_theta()
         lbs = e.lbs_forward(betas, theta, ls, want_Rs=False, want_v_shaped=False)[0]
-        if points is None and (self.loss_weights["w_chamfer"] > 0 or self.surface_weights["w_point_surface"] > 0):
+        gated = self.surface_on and self.gates_on
+        normals = None
+        if points is None and gated and self.surface_weights["w_point_surface"] > 0 and self.surface_gates["min_cos_point"] > -1:
+            points, normals = self.target_meshes.sample_normals(N_SAMPLE_POINTS, self.seed, self.iteration_offset + iteration,
+                                                                out=self._sample_buffer(), normals_out=self._point_normals)
+            self._point_normals = normals
+        elif points is None and (self.loss_weights["w_chamfer"] > 0 or self.surface_weights["w_point_surface"] > 0):
             points = self.target_meshes.sample(N_SAMPLE_POINTS, self.seed, self.iteration_offset + iteration, out=self._sample_buffer())
         self._last_points = points            # the sampler's buffer is never rebound: smalfit_fit3d_step writes through its raw pointer
         o = self._objective.eval(lbs, fit.trans.detach().contiguous(), fit.deform_verts.detach().contiguous(), points,
@@ -229,7 +255,9 @@ class Stage:
         if self.surface_on:
             # the stand-alone call's gradient joins the objective's before the LBS adjoint
             wp, wv = (self.surface_weights[k] for k in _SURFACE_ORDER)
-            sf = self._objective.surface(o["verts"], self.target_meshes, points if wp > 0 else None, wp, wv)
+            sf = self._objective.surface(o["verts"], self.target_meshes, points if wp > 0 else None, wp, wv,
+                                         gates=self.surface_gates if gated else None, point_normals=normals if wp > 0 else None)
+            self._surface_kept = sf.get("kept")
             o["dverts"] += sf["dverts"]
             o["dtrans"] += sf["dtrans"]
             self._surface_losses = sf["losses"]
@@ -263,9 +291,14 @@ class Stage:
             return self._buffers["losses"][4]
         sf = self._surface_block()
         sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
-        fn = _lib.resolve(e.lib, "smalfit_fit3d_step_surface")
-        eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a), C.byref(sf)),
-                  "smalfit_fit3d_step_surface")
+        if self.gates_on:
+            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_gated")
+            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a), C.byref(sf),
+                         C.byref(self._gate_block())), "smalfit_fit3d_step_gated")
+        else:
+            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_surface")
+            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a), C.byref(sf)),
+                      "smalfit_fit3d_step_surface")
         self._last_points = self._points
         return self._step_total[0]          # the grand total, formed by the step: the four terms + the surface term
 
@@ -338,6 +371,16 @@ class Stage:
             self._surface_args = sf
         self._surface_losses = self._step_losses
         return self._surface_args
+
+    def _gate_block(self):
+        """the smalfit_surface_gate_args of step(): the stage's switches, the kept counts (the step samples its own points and
+        draws their normals with them)"""
+        if self._gate_args is None:
+            self._gate_args = eng.surface_gate_block(self.surface_gates)
+            self._step_kept = torch.zeros(self.smal_3d_fitter.batch_size, 2, dtype=torch.int32, device=self.device)
+            self._gate_args.kept = self._step_kept.data_ptr()
+        self._surface_kept = self._step_kept
+        return self._gate_args
 
     def run(self, plot=False, progress=True, report_every=50):
         """Run the entire Stage (trainer.py:257-270).  The description line is refreshed every `report_every`

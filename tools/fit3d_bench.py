@@ -3,10 +3,12 @@
 batch of N target meshes, "default" scheme (trainer.py:115), all four loss terms, 3000 target points per mesh, and the
 share of each of the five C-ABI calls of a step (torch events on the launch stream, separate short run).
 
-    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface]
+    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface [--gates]]
 
 Prints one JSON line per batch size.  --surface adds the point-to-surface term both ways (w_point_surface = w_vert_surface = 1:
-every step is smalfit_fit3d_step_surface) and two fields to the line; without it the run and the line are those of before.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
+every step is smalfit_fit3d_step_surface) and two fields to the line; without it the run and the line are those of before.
+--gates (with --surface) switches every gate of that term on (GATES below: every step is smalfit_fit3d_step_gated) and adds the
+kept counts of the last step.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
 import argparse
 import json
 import os
@@ -34,12 +36,19 @@ def targets_for(md, N, seed):
     return out
 
 
+# every gate on, none of them tight on a complete target: the cost of the gated kernels, not of what they drop
+GATES = dict(max_dist_point=0.5, max_dist_vert=0.5, min_cos_point=0.0, min_cos_vert=0.0, reject_boundary=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", type=int, nargs="+", default=[1, 8, 32])
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--surface", action="store_true", help="add the point-to-surface term both ways to every step")
+    ap.add_argument("--gates", action="store_true", help="with --surface: gate the term (truncation, compatibility, boundary)")
     args = ap.parse_args()
+    if args.gates and not args.surface:
+        ap.error("--gates needs --surface")
     import torch
     from smalify_amd import synthetic
     from smalify_amd.fitter_3d import SMAL3DFitter, Stage, TargetMeshes
@@ -51,7 +60,8 @@ def main():
         tv = targets_for(md, N, seed=N)
         targets = TargetMeshes(tv, [np.asarray(md.faces)] * N)
         weights = {"w_point_surface": 1.0, "w_vert_surface": 1.0} if args.surface else None
-        stage = Stage(args.iters, "default", fit, targets, lr=0.01, custom_lrs={"joint_rot": 0.005}, loss_weights=weights)
+        stage = Stage(args.iters, "default", fit, targets, lr=0.01, custom_lrs={"joint_rot": 0.005}, loss_weights=weights,
+                      surface_gates=GATES if args.gates else None)
         for i in range(10):
             stage.step(i)
         torch.cuda.synchronize()
@@ -89,6 +99,9 @@ def main():
         if args.surface:
             line["surface"] = True
             line["final_surface_terms"] = [float(x) for x in stage.last_surface_terms]
+        if args.gates:
+            line["gates"] = GATES
+            line["final_surface_kept"] = stage.last_surface_kept.cpu().tolist()
         print(json.dumps(line))
         del stage, targets, fit
 
