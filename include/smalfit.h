@@ -42,7 +42,8 @@ typedef struct smalfit_engine smalfit_engine;
  * per frame); smalfit_mesh_score (smalfit_mesh_score_args: point-to-surface distances both ways, per mesh);
  * smalfit_mesh_surface_eval / smalfit_fit3d_step_surface (smalfit_surface_term_args: the same distances as a term to descend on);
  * smalfit_mesh_surface_eval_gated / smalfit_fit3d_step_gated / smalfit_mesh_targets_sample_normals (smalfit_surface_gate_args: that
- * term gated for partial scans). */
+ * term gated for partial scans); smalfit_mesh_objective_eval_gated / smalfit_fit3d_step_partial / smalfit_mesh_targets_sample_attrs
+ * (smalfit_chamfer_gate_args: the chamfer term gated the same way). */
 #define SMALFIT_ABI_VERSION 6
 int smalfit_version(void);
 const char* smalfit_last_error(void);
@@ -468,6 +469,62 @@ int smalfit_mesh_targets_sample(smalfit_mesh_targets* targets, void* stream, int
  * sampled on: that face's (b - a) x (c - a) over its length, the zero vector for a degenerate face.  normals (N,S,3) device. */
 int smalfit_mesh_targets_sample_normals(smalfit_mesh_targets* targets, void* stream, int num_points,
                                         unsigned long long seed, unsigned int iteration, float* points, float* normals);
+/* ... and, beside them, one boundary byte per point: 1 when the face it was sampled on has a boundary edge (an edge no other face
+ * of its mesh uses) or a corner that ends one, else 0.  normals (N,S,3) and boundary (N,S bytes) may each be NULL; the two
+ * samplers above ARE this call with NULLs, and the points are theirs bit for bit. */
+int smalfit_mesh_targets_sample_attrs(smalfit_mesh_targets* targets, void* stream, int num_points, unsigned long long seed,
+                                      unsigned int iteration, float* points, float* normals, unsigned char* boundary);
+
+/* ---- the chamfer term gated for partial scans ---------------------------------------------------------------------------
+ * The chamfer term matches every target point to its nearest fitted vertex and every fitted vertex to its nearest target point,
+ * whatever that is: on a target with a hole the vertices over the hole are pulled to its rim.  Three opt-in gates per direction
+ * decide which matches count; THIS PROJECT'S definitions (the reference has none).  Per mesh: target points x_s, s < S, each with
+ * a unit normal m_s and a boundary byte b_s; fitted (composed) vertices y_v, v < V, each with a unit normal u_v.
+ *   u_v            the fitted vertex normal of the gated surface term above (sum of the incident faces' normals over its length).
+ *   m_s, b_s       the unit normal of the target face the point was sampled on, and 1 when that face has a boundary edge or a
+ *                  corner that ends one, else 0 (smalfit_mesh_targets_sample_attrs); for the caller's points the caller's.
+ *   d^2            the term's own float32 expression fma(dz, dz, fma(dy, dy, dx dx)); nearest = the lowest index among equal d^2.
+ *   compatible     <a, b> >= c for the two unit normals, in float32; a zero normal gives 0 on the left, a NaN compares false.
+ *                  c <= -1 switches the test off for its direction: no normal is read, staged or computed for it.  c <= 1.
+ *   point -> vertex   nn(s) = the nearest vertex among those compatible with m_s under min_cos_point.  Point s is KEPT when such a
+ *                  vertex exists and (max_dist_point is off or d^2 <= tau^2); tau^2 is formed once on the host in float32; tau <= 0
+ *                  or not finite: off.  A dropped point has nn = -1.  No boundary rule here: a rim point is real data.
+ *   vertex -> point   nn'(v) = the nearest point among those compatible with u_v under min_cos_vert.  Vertex v is KEPT when such a
+ *                  point exists, (max_dist_vert is off or d^2 <= tau^2), and not (reject_boundary and b of nn'(v) != 0).  The
+ *                  boundary rule judges the WINNER; it does not filter candidates (that would only match the vertex to the next
+ *                  ring of points inwards).
+ *   loss           chamfer = 1/(N S) sum over kept s of d^2 + 1/(N V) sum over kept v of d^2.  The denominators stay N S and N V:
+ *                  a kept match's gradient is what it is ungated, and the loss does not jump with a count.
+ *   gradient       d chamfer / d y_v = 2/(N V) [v kept] (y_v - x_nn'(v)) + 2/(N S) sum over kept s with nn(s) = v of (y_v - x_s),
+ *                  times w_chamfer.  No gate and no normal is differentiated through.
+ *   kept           kept[n] = (kept points, kept vertices) lets a caller renormalise.
+ * gate == NULL, or every gate off and no mask asked for: exactly the ungated call, launch for launch and bit for bit; `kept` then
+ * reads (S, V) without anything being counted.  With w_chamfer <= 0 a gate block is accepted and ignored, and `kept` reads (0, 0).
+ * Not here: a soft robust kernel, gates for the edge, normal or Laplacian terms or for smalfit_mesh_score, spatial acceleration. */
+typedef struct smalfit_chamfer_gate_args {
+  unsigned struct_size;       /* sizeof(smalfit_chamfer_gate_args) of the caller's header; checked before any other field */
+  float max_dist_point;       /* tau of point -> vertex; <= 0 or not finite: off */
+  float max_dist_vert;        /* tau of vertex -> point */
+  float min_cos_point;        /* c of point -> vertex, <= 1; <= -1: off */
+  float min_cos_vert;         /* c of vertex -> point */
+  int reject_boundary;        /* != 0: the boundary rule (vertex -> point) */
+  const float* point_normals; /* (N,S,3) m_s of the caller's points: needed when a min_cos gate is on and the points are the caller's;
+                                 must be NULL in a step that samples its points (it draws them with the points) */
+  const unsigned char* point_boundary; /* (N,S) b_s of the caller's points: needed with reject_boundary; NULL in a sampling step */
+  int* kept;                  /* (N,2): kept points | kept vertices of every mesh */
+  unsigned char* point_kept;  /* optional (N,S): 1 kept, 0 dropped */
+  unsigned char* vert_kept;   /* optional (N,V) */
+  int* point_nn;              /* optional (N,S): nn(s), -1 for a dropped point */
+  int* vert_nn;               /* optional (N,V): nn'(v), -1 when no compatible point was found */
+} smalfit_chamfer_gate_args;
+/* smalfit_mesh_objective_eval with the gates; that call IS this one with gate = NULL.  targets may be NULL (the points, their normals
+ * and boundary bytes are the caller's); when given, its mesh count must be num_meshes.  A refused block launches nothing and
+ * leaves every output alone */
+int smalfit_mesh_objective_eval_gated(smalfit_mesh_objective* objective, void* stream, int num_meshes,
+                                      const float* lbs_verts, const float* trans, const float* deform_verts,
+                                      const float* points, int num_points, const float* weights /*host*/,
+                                      float* verts_out, float* losses, float* dverts, float* dtrans,
+                                      smalfit_mesh_targets* targets, const smalfit_chamfer_gate_args* gate);
 
 /* ---- how good a 3-D fit is: exact surface distances both ways, per mesh -------------------------------------------------
  * No counterpart in the reference, whose fitter_3d contains no evaluation code: the definitions below are THIS PROJECT'S.
@@ -646,6 +703,11 @@ int smalfit_mesh_surface_eval_gated(smalfit_mesh_objective* objective, smalfit_m
 int smalfit_fit3d_step_gated(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
                              void* stream, const smalfit_fit3d_args* args, const smalfit_surface_term_args* surface,
                              const smalfit_surface_gate_args* gate);
+/* ... and with the gates of the chamfer term; smalfit_fit3d_step_gated IS this call with chamfer_gate = NULL.  A chamfer gate block
+ * needs no surface block.  Where both gate sets want the fitted vertex normals or the sampled normals, they are produced once */
+int smalfit_fit3d_step_partial(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
+                               void* stream, const smalfit_fit3d_args* args, const smalfit_surface_term_args* surface,
+                               const smalfit_surface_gate_args* surface_gate, const smalfit_chamfer_gate_args* chamfer_gate);
 
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137

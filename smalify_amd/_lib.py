@@ -119,6 +119,23 @@ class SurfaceGateArgs(C.Structure):
             self.min_cos_vert = -1.0
 
 
+class ChamferGateArgs(C.Structure):
+    """smalfit_chamfer_gate_args: the gates of the chamfer term for partial scans (smalfit_mesh_objective_eval_gated,
+    smalfit_fit3d_step_partial)"""
+    _fields_ = [("struct_size", C.c_uint), ("max_dist_point", C.c_float), ("max_dist_vert", C.c_float), ("min_cos_point", C.c_float),
+                ("min_cos_vert", C.c_float), ("reject_boundary", C.c_int), ("point_normals", C.c_void_p), ("point_boundary", C.c_void_p),
+                ("kept", C.c_void_p), ("point_kept", C.c_void_p), ("vert_kept", C.c_void_p), ("point_nn", C.c_void_p),
+                ("vert_nn", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(ChamferGateArgs)
+        if "min_cos_point" not in kw:
+            self.min_cos_point = -1.0          # off (0 would be a gate: the front-facing half)
+        if "min_cos_vert" not in kw:
+            self.min_cos_vert = -1.0
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -225,13 +242,19 @@ SIGNATURES = {
     "smalfit_mesh_surface_eval_gated": (_I, [_VP, _VP, _VP, C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs)]),
     "smalfit_fit3d_step_gated": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs)]),
     "smalfit_mesh_targets_sample_normals": (_I, [_VP, _VP, _I, C.c_ulonglong, C.c_uint, _VP, _VP]),
+    "smalfit_mesh_targets_sample_attrs": (_I, [_VP, _VP, _I, C.c_ulonglong, C.c_uint, _VP, _VP, _VP]),
+    "smalfit_mesh_objective_eval_gated": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP,
+                                               C.POINTER(ChamferGateArgs)]),
+    "smalfit_fit3d_step_partial": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs),
+                                        C.POINTER(ChamferGateArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
 # built before them loads, and resolve() names the symbol when one is asked for
 LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "smalfit_mesh_score", "smalfit_mesh_surface_eval",
                           "smalfit_fit3d_step_surface", "smalfit_mesh_surface_eval_gated", "smalfit_fit3d_step_gated",
-                          "smalfit_mesh_targets_sample_normals"])
+                          "smalfit_mesh_targets_sample_normals", "smalfit_mesh_targets_sample_attrs",
+                          "smalfit_mesh_objective_eval_gated", "smalfit_fit3d_step_partial"])
 
 
 class SmalfitError(RuntimeError):

@@ -53,10 +53,25 @@ struct Mesh3dArgs {
   float* part_normal;      // [N][bp]
   float* part_dtr;         // [N][bv][3]
   int bx, by, bv, bp;
+  // the gates of the chamfer term (smalfit_chamfer_gate_args, planned by plan_chamfer_gates); read by the GATED instantiations and,
+  // `kept`, by the reduce
+  const float* normals_v;        // [N][V][3] unit normals of the fitted vertices, or null: the compatibility tests are off
+  const float* normals_p;        // [N][S][3] unit normals of the points, or null
+  const unsigned char* bound_p;  // [N][S] boundary bytes of the points, or null: no boundary rule
+  float cos_p, cos_v;            // c of point -> vertex | vertex -> point; -inf: off
+  float tau2_p, tau2_v;          // +inf: no truncation
+  int* part_kx;                  // [N][bx] per-block kept counts of chamfer<0, true>, null where chamfer<0, false> ran
+  int* part_ky;                  // [N][by]
+  int* kept;                     // [N][2] or null
+  unsigned char* point_kept;     // [N][S] or null
+  unsigned char* vert_kept;      // [N][V] or null
+  int* point_nn;                 // [N][S] or null: a copy of nn_idx
+  int* vert_nn;                  // [N][V] or null
 };
 
 constexpr int kChamQueries = 64;    // queries per block: one per lane, the same 64 in each of the 4 waves
 constexpr int kChamChunk = 1024;    // points of the scanned set staged in LDS at a time; a wave scans a quarter
+static_assert(kChamGateChunk * sizeof(GatedScanPoint) == kChamChunk * sizeof(ScanPoint), "the gated chunk fills the ungated one's LDS");
 constexpr int kMeshBlock = 256;
 
 __global__ __launch_bounds__(256) void mesh3d_compose_kernel(Mesh3dArgs a) {
@@ -73,9 +88,14 @@ __global__ __launch_bounds__(256) void mesh3d_compose_kernel(Mesh3dArgs a) {
 }
 
 // ROLE 0: queries = target points, scanned set = vertices.  ROLE 1: queries = vertices, scanned set = target points.
-template <int ROLE>
+// <ROLE, false> is the ungated term's kernel: ScanPoint records, kChamChunk at a time.
+// GATED: the 32-byte GatedScanPoint, kChamGateChunk at a time -- the same 16 KB, so a block's LDS (21 KB with the waves' partial
+// results) and its four blocks a CU do not change -- and the nearest COMPATIBLE element (the query's unit normal in three registers, c a scalar; with c = -inf no normal is read
+// and every record is compatible); the waves' minima meet as before, then wave 0 decides once per query: found, truncation,
+// (ROLE 1) the boundary rule on the winner.  A dropped point writes nn_idx = -1, so no vertex gathers it; a dropped query adds
+// nothing to the sum of d^2 or to its own gradient term; the block's kept count goes beside its sum
+template <int ROLE, bool GATED>
 __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
-  __shared__ ScanPoint sp[kChamChunk];
   __shared__ float sd[4][kChamQueries];
   __shared__ int si[4][kChamQueries];
   __shared__ float sg[ROLE == 1 ? 4 : 1][kChamQueries][3];
@@ -93,26 +113,69 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
     qy = q[3 * (size_t)qi + 1];
     qz = q[3 * (size_t)qi + 2];
   }
+  // GATED: the query's unit normal and the scanned set's, read only while this direction's compatibility test is on
+  const float c = ROLE == 0 ? a.cos_p : a.cos_v;
+  const bool use_normals = GATED && c != -INFINITY;
+  const float* on = ROLE == 0 ? a.normals_v + (size_t)n * a.V * 3 : a.normals_p + (size_t)n * a.S * 3;
+  const unsigned char* ob = ROLE == 1 && a.bound_p != nullptr ? a.bound_p + (size_t)n * a.S : nullptr;
+  float ux = 0.f, uy = 0.f, uz = 0.f;
+  if (use_normals && active) {
+    const float* u = (ROLE == 0 ? a.normals_p : a.normals_v) + ((size_t)n * nq + qi) * 3;
+    ux = u[0];
+    uy = u[1];
+    uz = u[2];
+  }
   float best = INFINITY;
-  int bidx = 0x7fffffff;
+  int bidx = 0x7fffffff;   // GATED: the winner's tag (gated_tag: ascending with the index)
   float g[3] = {0.f, 0.f, 0.f};
-  for (int base = 0; base < no; base += kChamChunk) {
-    const int cnt = min(kChamChunk, no - base);
-    __syncthreads();
-    for (int i = threadIdx.x; i < cnt; i += 256) {
-      const float* src = o + 3 * (size_t)(base + i);
-      ScanPoint s;
-      s.x = src[0];
-      s.y = src[1];
-      s.z = src[2];
-      s.owner = ROLE == 1 ? own[base + i] : 0;
-      sp[i] = s;
+  if constexpr (GATED) {
+    __shared__ GatedScanPoint gp[kChamGateChunk];
+    for (int base = 0; base < no; base += kChamGateChunk) {
+      const int cnt = min(kChamGateChunk, no - base);
+      __syncthreads();
+      for (int i = threadIdx.x; i < cnt; i += 256) {
+        const float* src = o + 3 * (size_t)(base + i);
+        GatedScanPoint s;
+        s.x = src[0];
+        s.y = src[1];
+        s.z = src[2];
+        s.owner = ROLE == 1 ? own[base + i] : 0;
+        s.nx = s.ny = s.nz = 0.f;
+        if (use_normals) {
+          const float* sn = on + 3 * (size_t)(base + i);
+          s.nx = sn[0];
+          s.ny = sn[1];
+          s.nz = sn[2];
+        }
+        s.tag = gated_tag(base + i, ob != nullptr ? ob[base + i] : 0);
+        gp[i] = s;
+      }
+      __syncthreads();
+      const int per = (cnt + 3) >> 2;
+      const int b = min(w * per, cnt), e = min(b + per, cnt);
+      // (wave-uniform as below: two broadcast 16-byte LDS reads per record)
+      nearest_scan_gated<ROLE == 1>(qx, qy, qz, ux, uy, uz, c, gp, b, e, best, bidx, qi, g);
     }
-    __syncthreads();
-    const int per = (cnt + 3) >> 2;
-    const int b = min(w * per, cnt), e = min(b + per, cnt);
-    // b, e are wave-uniform: every lane reads the same 16-byte LDS record (broadcast, conflict free)
-    nearest_scan<ROLE == 1>(qx, qy, qz, sp, b, e, base, best, bidx, qi, g);
+  } else {
+    __shared__ ScanPoint sp[kChamChunk];
+    for (int base = 0; base < no; base += kChamChunk) {
+      const int cnt = min(kChamChunk, no - base);
+      __syncthreads();
+      for (int i = threadIdx.x; i < cnt; i += 256) {
+        const float* src = o + 3 * (size_t)(base + i);
+        ScanPoint s;
+        s.x = src[0];
+        s.y = src[1];
+        s.z = src[2];
+        s.owner = ROLE == 1 ? own[base + i] : 0;
+        sp[i] = s;
+      }
+      __syncthreads();
+      const int per = (cnt + 3) >> 2;
+      const int b = min(w * per, cnt), e = min(b + per, cnt);
+      // b, e are wave-uniform: every lane reads the same 16-byte LDS record (broadcast, conflict free)
+      nearest_scan<ROLE == 1>(qx, qy, qz, sp, b, e, base, best, bidx, qi, g);
+    }
   }
   sd[w][lane] = best;
   si[w][lane] = bidx;
@@ -131,6 +194,36 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
       g[1] += sg[s][lane][1];
       g[2] += sg[s][lane][2];
     }
+  }
+  if constexpr (GATED) {
+    const GatedMatch mt = gated_match(best, bidx, ROLE == 0 ? a.tau2_p : a.tau2_v, ob != nullptr ? 1 : 0);
+    const bool kept = active && mt.kept;
+    if (active) {
+      const size_t oq = (size_t)n * nq + qi;
+      if (ROLE == 0) {
+        const int nn = kept ? mt.index : -1;
+        a.nn_idx[oq] = nn;
+        if (a.point_nn != nullptr) a.point_nn[oq] = nn;
+        if (a.point_kept != nullptr) a.point_kept[oq] = kept ? 1 : 0;
+      } else {
+        if (a.vert_nn != nullptr) a.vert_nn[oq] = mt.index;
+        if (a.vert_kept != nullptr) a.vert_kept[oq] = kept ? 1 : 0;
+        const float cy = kept ? a.w_chamfer * 2.0f / ((float)a.V * (float)a.N) : 0.f;   // a dropped vertex keeps only what it gathered
+        const float cx = a.w_chamfer * 2.0f / ((float)a.S * (float)a.N);
+        const float* xn = o + 3 * (size_t)(kept ? mt.index : 0);
+        float* out = a.gcham + oq * 3;
+        out[0] = cy * (qx - xn[0]) + cx * g[0];
+        out[1] = cy * (qy - xn[1]) + cx * g[1];
+        out[2] = cy * (qz - xn[2]) + cx * g[2];
+      }
+    }
+    const float tot = wave_sum(kept ? best : 0.f);
+    const int cnt = __popcll(__ballot(kept));   // (an integer count: no order to fix)
+    if (lane == 0) {
+      (ROLE == 0 ? a.part_cx : a.part_cy)[(size_t)n * gridDim.x + blockIdx.x] = tot;
+      (ROLE == 0 ? a.part_kx : a.part_ky)[(size_t)n * gridDim.x + blockIdx.x] = cnt;
+    }
+    return;
   }
   if (active) {
     if (ROLE == 0) {
@@ -265,6 +358,22 @@ __global__ __launch_bounds__(256) void mesh3d_reduce_kernel(Mesh3dArgs a) {
     for (int b = 0; b < a.bv; ++b) s += a.part_dtr[((size_t)n * a.bv + b) * 3 + k];
     a.dtrans[o] = s;
   }
+  if (a.kept != nullptr) {
+    // counted by the gated chamfer kernels; where the ungated one ran nothing was dropped and nothing counted: every query
+    for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
+      int kp = a.w_chamfer > 0.f ? a.S : 0, kv = a.w_chamfer > 0.f ? a.V : 0;
+      if (a.part_kx != nullptr) {
+        kp = 0;
+        for (int b = 0; b < a.bx; ++b) kp += a.part_kx[(size_t)n * a.bx + b];
+      }
+      if (a.part_ky != nullptr) {
+        kv = 0;
+        for (int b = 0; b < a.by; ++b) kv += a.part_ky[(size_t)n * a.by + b];
+      }
+      a.kept[2 * n] = kp;
+      a.kept[2 * n + 1] = kv;
+    }
+  }
 }
 
 // ---- sample_points_from_meshes ----------------------------------------------------------------------------------
@@ -277,11 +386,14 @@ struct MeshTargetsDev {
   const uint32_t* thr;      // packed [sum F] cumulative-area thresholds (mesh3d_topology.h)
 };
 
-// NORMALS: also the unit normal of the sampled face (smalfit_mesh_targets_sample_normals; the points are those of <false>)
-template <bool NORMALS>
+// ATTRS: also what the gates ask of a point (smalfit_mesh_targets_sample_attrs; the points are those of <false>): the unit normal
+// of the sampled face (normals != null) and its boundary byte, bflags of that face != 0 (boundary != null)
+template <bool ATTRS>
 __global__ __launch_bounds__(256) void mesh3d_sample_kernel(MeshTargetsDev t, int S, uint32_t seed_lo, uint32_t seed_hi,
                                                            uint32_t iteration, float* points /* [N][S][3] */,
-                                                           float* normals /* [N][S][3], NORMALS only */) {
+                                                           float* normals /* [N][S][3] or null, ATTRS only */,
+                                                           unsigned char* boundary /* [N][S] or null, ATTRS only */,
+                                                           const unsigned char* bflags /* packed [sum F], ATTRS only */) {
   const int n = blockIdx.y;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= S) return;
@@ -297,13 +409,16 @@ __global__ __launch_bounds__(256) void mesh3d_sample_kernel(MeshTargetsDev t, in
   dst[0] = out[0];
   dst[1] = out[1];
   dst[2] = out[2];
-  if (NORMALS) {
-    float u[3];
-    face_unit_normal(base + 3 * (size_t)fc[0], base + 3 * (size_t)fc[1], base + 3 * (size_t)fc[2], u);
-    float* dn = normals + ((size_t)n * S + i) * 3;
-    dn[0] = u[0];
-    dn[1] = u[1];
-    dn[2] = u[2];
+  if (ATTRS) {
+    if (normals != nullptr) {
+      float u[3];
+      face_unit_normal(base + 3 * (size_t)fc[0], base + 3 * (size_t)fc[1], base + 3 * (size_t)fc[2], u);
+      float* dn = normals + ((size_t)n * S + i) * 3;
+      dn[0] = u[0];
+      dn[1] = u[1];
+      dn[2] = u[2];
+    }
+    if (boundary != nullptr) boundary[(size_t)n * S + i] = bflags[f0 + f] != 0 ? 1 : 0;
   }
 }
 

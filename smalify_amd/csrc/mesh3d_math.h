@@ -104,6 +104,72 @@ SMALFIT_HD void nearest_merge(float& best, int& best_idx, float d2, int idx) {
   }
 }
 
+// ---- the gated chamfer scan (smalfit_chamfer_gate_args; worded in include/smalfit.h) --------------------------------------
+// The staged record of nearest_scan with the scanned element's unit normal behind it: two 16-byte rows, each one broadcast LDS
+// read.  `tag` = 2 * (index in the scanned set) + (its boundary byte != 0): ascending with the index, so the lowest-index tie
+// rule holds on tags as it does on indices, and the winner brings its boundary bit along without a register of its own.
+struct alignas(16) GatedScanPoint {
+  float x, y, z;
+  int owner;
+  float nx, ny, nz;
+  int tag;
+};
+SMALFIT_HD float dot3(float ax, float ay, float az, float bx, float by, float bz);   // (defined with the triangle records below)
+typedef float GatedRow __attribute__((vector_size(16), may_alias));   // one 16-byte row of the record, read whole
+SMALFIT_HD int float_bits(float f) {
+  int i;
+  __builtin_memcpy(&i, &f, sizeof(i));
+  return i;
+}
+constexpr int kNoTag = 0x7fffffff;  // no candidate yet (nearest_scan's "no index"); an index stays below 2^30
+SMALFIT_HD int gated_tag(int index, int boundary) { return 2 * index + (boundary != 0 ? 1 : 0); }
+
+// the two unit normals are compatible with threshold c when <a, b> >= c: float32, branch-free; a zero normal gives 0 on the
+// left, a NaN compares false.  c = -inf with both normals zero (never read) is the test switched off
+SMALFIT_HD bool unit_normals_compatible(float ax, float ay, float az, float bx, float by, float bz, float c) {
+  return dot3(ax, ay, az, bx, by, bz) >= c;
+}
+
+// nearest_scan over the records compatible with the query's normal (ux, uy, uz): the same d^2 expression, the same strict '<',
+// the same lowest-index tie rule; best_tag is the winner's tag.  The owner gather keeps its mask over ALL staged records,
+// compatible or not: those matches were vetted in the other direction
+template <bool OWNER>
+SMALFIT_HD void nearest_scan_gated(float qx, float qy, float qz, float ux, float uy, float uz, float c, const GatedScanPoint* p,
+                                   int begin, int end, float& best, int& best_tag, int self, float g[3]) {
+#pragma unroll 4
+  for (int j = begin; j < end; ++j) {
+    // each row as ONE 16-byte read, the tag with the normal it shares a row with: read field by field, the tag's load is sunk
+    // into the branch that takes it, the loop falls into a block per record and no read overlaps the arithmetic before it
+    const GatedRow r0 = *reinterpret_cast<const GatedRow*>(&p[j].x), r1 = *reinterpret_cast<const GatedRow*>(&p[j].nx);
+    const float dx = qx - r0[0], dy = qy - r0[1], dz = qz - r0[2];
+    const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+    const bool ok = unit_normals_compatible(ux, uy, uz, r1[0], r1[1], r1[2], c);
+    const bool take = ok & (d2 < best);
+    best = take ? d2 : best;
+    best_tag = take ? float_bits(r1[3]) : best_tag;
+    if (OWNER) {
+      const float mk = float_bits(r0[3]) == self ? 1.0f : 0.0f;
+      g[0] = fmaf(mk, dx, g[0]);
+      g[1] = fmaf(mk, dy, g[1]);
+      g[2] = fmaf(mk, dz, g[2]);
+    }
+  }
+}
+
+// what is decided once per query after the waves' minima have met: found (a compatible candidate exists), truncation
+// (d^2 > tau^2 drops; tau2 = +inf: off) and, boundary != 0, the boundary rule on the WINNER's bit
+struct GatedMatch {
+  int index;   // of the winner, -1 when none was found
+  bool kept;
+};
+SMALFIT_HD GatedMatch gated_match(float best, int best_tag, float tau2, int reject_boundary) {
+  GatedMatch m;
+  const bool found = best_tag != kNoTag;
+  m.index = found ? best_tag >> 1 : -1;
+  m.kept = found & !(best > tau2) & !((reject_boundary != 0) & ((best_tag & 1) != 0));
+  return m;
+}
+
 // ------------------------------------------------------------------------------------------------
 // point to triangle (smalfit_mesh_score; no counterpart in the reference: the definition is worded in include/smalfit.h).
 // The squared distance from p to the closed triangle (a, b, c) is the minimum of

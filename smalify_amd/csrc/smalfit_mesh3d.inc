@@ -33,6 +33,9 @@ struct smalfit_mesh_objective {
   const int *vf_off = nullptr, *vf = nullptr;
   float *surf_vnorm = nullptr, *surf_pnorm = nullptr;
   int *surf_part_kp = nullptr, *surf_part_kv = nullptr;
+  // the gates of the chamfer term only: the sampled points' boundary bytes, per-block kept counts (the normals are the two above)
+  unsigned char* cham_pbound = nullptr;
+  int *part_kx = nullptr, *part_ky = nullptr;
 };
 
 struct smalfit_mesh_targets {
@@ -52,7 +55,7 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
                             const float* verts, const float* points, int num_points, float* acc_dverts = nullptr,
                             float* acc_planar = nullptr, int Vp = 0, float* acc_dtrans = nullptr,
                             const float* step_losses = nullptr, const smalfit_surface_gate_args* gate = nullptr,
-                            const float* point_normals = nullptr) {
+                            const float* point_normals = nullptr, const float* ready_vnorm = nullptr) {
   SurfaceTermArgs k{};
   k.N = a->num_meshes; k.V = m->t.V; k.F = m->num_faces;
   k.w_ps = mesh_weight(a->w_point_surface); k.w_vs = mesh_weight(a->w_vert_surface);
@@ -77,7 +80,8 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
     if (k.w_vs > 0.f) { k.part_kv = m->surf_part_kv; k.vert_kept = gate->vert_kept; }
     if (k.w_ps > 0.f) { k.part_kp = m->surf_part_kp; k.point_kept = gate->point_kept; }
     if (gp.boundary) k.bflags = t->bflags;
-    if (gp.cos_vert) { k.normals_out = gate->vert_normals ? gate->vert_normals : m->surf_vnorm; k.normals_v = k.normals_out; }
+    // (ready_vnorm: the step's chamfer gates have already gathered the vertex normals of these vertices, where this term wants them)
+    if (gp.cos_vert) { k.normals_out = gate->vert_normals ? gate->vert_normals : m->surf_vnorm; k.normals_v = ready_vnorm ? ready_vnorm : k.normals_out; }
     if (gp.cos_point) k.normals_p = point_normals;
   }
   // the keys of the directions that run, all ones: the vertices' come first, the points' behind them
@@ -87,9 +91,11 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
   if (k.w_vs > 0.f) {
     const Grid3 g = surface_near_grid(k.V, t->max_faces, k.N);
     if (gp.cos_vert) {
-      const Grid2 gn = vertex_normal_grid(k.V, k.N);
-      mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
-      LAUNCH_OK("mesh3d_vertex_normal_kernel");
+      if (!ready_vnorm) {
+        const Grid2 gn = vertex_normal_grid(k.V, k.N);
+        mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
+        LAUNCH_OK("mesh3d_vertex_normal_kernel");
+      }
       mesh3d_surface_near_kernel<0, true><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
     } else {
       mesh3d_surface_near_kernel<0, false><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
@@ -115,11 +121,16 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
   return 0;
 }
 
-// the 6 launches of one evaluation; arguments validated by the callers
+// the 6 launches of one evaluation; arguments validated by the callers.  With a chamfer gate block (validated by the callers;
+// point_normals / point_boundary: the caller's or the sampler's; vnorm: where the fitted vertex normals go when a compatibility
+// test asks for them) the gated chamfer instantiations take the place of the ungated ones where plan_chamfer_gates says so, and
+// mesh3d_vertex_normal_kernel runs between compose and them; with none, or every gate off, the launches are those of before
 static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num_meshes, const float* lbs_verts,
                               const float* trans, const float* deform_verts, const float* points, int num_points,
                               const float* weights, float* verts_out, float* losses, float* dverts, float* dtrans,
-                              const float* lbs_planar = nullptr, int Vp = 0, float* dverts_planar = nullptr) {
+                              const float* lbs_planar = nullptr, int Vp = 0, float* dverts_planar = nullptr,
+                              const smalfit_chamfer_gate_args* gate = nullptr, const float* point_normals = nullptr,
+                              const unsigned char* point_boundary = nullptr, float* vnorm = nullptr) {
   const float wc = mesh_weight(weights[0]);
   Mesh3dArgs a{};
   a.N = num_meshes; a.V = m->t.V; a.S = mesh_points(wc, num_points);
@@ -135,12 +146,28 @@ static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num
   a.part_cx = m->part_cx; a.part_cy = m->part_cy; a.part_edge = m->part_edge; a.part_lap = m->part_lap;
   a.part_normal = m->part_normal; a.part_dtr = m->part_dtr;
   a.bx = mesh_query_blocks(a.S); a.by = m->by; a.bv = m->bv; a.bp = m->bp;
+  const ChamferGatePlan gp = plan_chamfer_gates(gate, wc > 0.f);
+  a.cos_p = gp.c_point; a.cos_v = gp.c_vert; a.tau2_p = gp.tau2_point; a.tau2_v = gp.tau2_vert;
+  if (gate) a.kept = gate->kept;
+  if (gp.gated_point) { a.part_kx = m->part_kx; a.point_kept = gate->point_kept; a.point_nn = gate->point_nn; }
+  if (gp.gated_vert) { a.part_ky = m->part_ky; a.vert_kept = gate->vert_kept; a.vert_nn = gate->vert_nn; }
+  if (gp.point_boundary) a.bound_p = point_boundary;
+  if (gp.vert_normals) { a.normals_v = vnorm; a.normals_p = point_normals; }
   mesh3d_compose_kernel<<<dim3(mesh_compose_blocks(a.N, a.V)), 256, 0, st>>>(a);
   LAUNCH_OK("mesh3d_compose_kernel");
+  if (gp.vert_normals) {
+    SurfaceTermArgs k{};
+    k.N = a.N; k.V = a.V; k.verts = a.verts; k.faces = m->faces; k.vf_off = m->vf_off; k.vf = m->vf; k.normals_out = vnorm;
+    const Grid2 gn = vertex_normal_grid(k.V, k.N);
+    mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
+    LAUNCH_OK("mesh3d_vertex_normal_kernel");
+  }
   if (wc > 0.f) {
-    mesh3d_chamfer_kernel<0><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
+    if (gp.gated_point) mesh3d_chamfer_kernel<0, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
+    else mesh3d_chamfer_kernel<0, false><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
     LAUNCH_OK("mesh3d_chamfer_kernel<0>");
-    mesh3d_chamfer_kernel<1><<<dim3(a.by, a.N), 256, 0, st>>>(a);
+    if (gp.gated_vert) mesh3d_chamfer_kernel<1, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
+    else mesh3d_chamfer_kernel<1, false><<<dim3(a.by, a.N), 256, 0, st>>>(a);
     LAUNCH_OK("mesh3d_chamfer_kernel<1>");
   } else {
     HIP_OK(hipMemsetAsync(m->gcham, 0, (size_t)a.N * a.V * 3 * sizeof(float), st));
@@ -155,13 +182,14 @@ static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num
 }
 
 // sample_points_from_meshes: num_points per target mesh into points (N,S,3)
-// ... and, with `normals` (N,S,3), the unit normal of every point's face
+// ... and, with `normals` (N,S,3) / `boundary` (N,S), the unit normal / the boundary byte of every point's face
 static int launch_mesh_sampler(const smalfit_mesh_targets* t, hipStream_t st, int num_points, unsigned long long seed,
-                               unsigned int iteration, float* points, float* normals = nullptr) {
+                               unsigned int iteration, float* points, float* normals = nullptr, unsigned char* boundary = nullptr) {
   const Grid2 grid = mesh_sample_grid(num_points, t->d.N);
   const uint32_t lo = (uint32_t)(seed & 0xFFFFFFFFull), hi = (uint32_t)(seed >> 32);
-  if (normals) mesh3d_sample_kernel<true><<<dim3(grid.x, grid.y), 256, 0, st>>>(t->d, num_points, lo, hi, iteration, points, normals);
-  else mesh3d_sample_kernel<false><<<dim3(grid.x, grid.y), 256, 0, st>>>(t->d, num_points, lo, hi, iteration, points, nullptr);
+  if (normals || boundary)
+    mesh3d_sample_kernel<true><<<dim3(grid.x, grid.y), 256, 0, st>>>(t->d, num_points, lo, hi, iteration, points, normals, boundary, t->bflags);
+  else mesh3d_sample_kernel<false><<<dim3(grid.x, grid.y), 256, 0, st>>>(t->d, num_points, lo, hi, iteration, points, nullptr, nullptr, nullptr);
   LAUNCH_OK("mesh3d_sample_kernel");
   return 0;
 }
@@ -231,6 +259,9 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   w.field(m->surf_pnorm, N * S * 3);
   w.field(m->surf_part_kp, N * (size_t)surface_hit_grid((int)S, 1).x);
   w.field(m->surf_part_kv, N * (size_t)surface_hit_grid((int)V, 1).x);
+  w.field(m->cham_pbound, N * S);
+  w.field(m->part_kx, N * m->bx);
+  w.field(m->part_ky, N * m->by);
   auto bail = [&](const char* what) {
     smalfit_mesh_objective_destroy(m);
     return refused("smalfit_mesh_objective_create", what);
@@ -260,11 +291,22 @@ int smalfit_mesh_objective_eval(smalfit_mesh_objective* m, void* stream, int num
                                 const float* trans, const float* deform_verts, const float* points, int num_points,
                                 const float* weights /* host [4] */, float* verts_out, float* losses, float* dverts,
                                 float* dtrans) {
-  if (refused("smalfit_mesh_objective_eval", null_argument_refusal(m && lbs_verts && trans && weights && losses && dverts && dtrans))) return 1;
-  if (refused("smalfit_mesh_objective_eval", mesh_eval_refusal(num_meshes, m->max_meshes, weights[0], points != nullptr, num_points, m->max_points)))
-    return 1;
+  return smalfit_mesh_objective_eval_gated(m, stream, num_meshes, lbs_verts, trans, deform_verts, points, num_points, weights, verts_out,
+                                           losses, dverts, dtrans, nullptr, nullptr);
+}
+
+int smalfit_mesh_objective_eval_gated(smalfit_mesh_objective* m, void* stream, int num_meshes, const float* lbs_verts,
+                                      const float* trans, const float* deform_verts, const float* points, int num_points,
+                                      const float* weights /* host [4] */, float* verts_out, float* losses, float* dverts,
+                                      float* dtrans, smalfit_mesh_targets* t, const smalfit_chamfer_gate_args* g) {
+  const char* who = g ? "smalfit_mesh_objective_eval_gated" : "smalfit_mesh_objective_eval";
+  if (refused(who, null_argument_refusal(m && lbs_verts && trans && weights && losses && dverts && dtrans))) return 1;
+  if (refused(who, mesh_eval_refusal(num_meshes, m->max_meshes, weights[0], points != nullptr, num_points, m->max_points))) return 1;
+  if (g && refused(who, chamfer_gate_args_refusal(g, ChamferGateFacts{weights[0] > 0.f, false, false}))) return 1;
+  if (g && t && t->d.N != num_meshes) return refused(who, "number of target meshes differs from num_meshes");
   return run_mesh_objective(m, (hipStream_t)stream, num_meshes, lbs_verts, trans, deform_verts, points, num_points, weights,
-                            verts_out, losses, dverts, dtrans);
+                            verts_out, losses, dverts, dtrans, nullptr, 0, nullptr, g, g ? g->point_normals : nullptr,
+                            g ? g->point_boundary : nullptr, m->surf_vnorm);
 }
 
 int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const int* face_counts, const float* verts,
@@ -343,6 +385,12 @@ int smalfit_mesh_targets_sample_normals(smalfit_mesh_targets* t, void* stream, i
   return launch_mesh_sampler(t, (hipStream_t)stream, num_points, seed, iteration, points, normals);
 }
 
+int smalfit_mesh_targets_sample_attrs(smalfit_mesh_targets* t, void* stream, int num_points, unsigned long long seed,
+                                      unsigned int iteration, float* points, float* normals, unsigned char* boundary) {
+  if (refused("smalfit_mesh_targets_sample_attrs", mesh_sample_refusal(t && points, num_points))) return 1;
+  return launch_mesh_sampler(t, (hipStream_t)stream, num_points, seed, iteration, points, normals, boundary);
+}
+
 // ---- how good a fit is: point-to-surface distances both ways, per mesh -------------------------------------------------
 int smalfit_mesh_score(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream, const smalfit_mesh_score_args* a) {
   if (refused("smalfit_mesh_score", null_argument_refusal(m && t && a))) return 1;
@@ -399,7 +447,13 @@ int smalfit_fit3d_step_surface(smalfit_engine* e, smalfit_mesh_objective* m, sma
 
 int smalfit_fit3d_step_gated(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
                              const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate) {
-  const char* who = gate ? "smalfit_fit3d_step_gated" : sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
+  return smalfit_fit3d_step_partial(e, m, t, stream, a, sf, gate, nullptr);
+}
+
+int smalfit_fit3d_step_partial(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
+                               const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
+                               const smalfit_chamfer_gate_args* cg) {
+  const char* who = cg ? "smalfit_fit3d_step_partial" : gate ? "smalfit_fit3d_step_gated" : sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
   if (refused(who, null_argument_refusal(e && m && a))) return 1;
   const ModelDev& md = e->model->dev;
   if (refused(who, fit3d_args_refusal(a, Fit3dFacts{e->maxM, md.V, md.NBall, m->max_meshes, m->max_points, m->t.V,
@@ -410,6 +464,7 @@ int smalfit_fit3d_step_gated(smalfit_engine* e, smalfit_mesh_objective* m, smalf
     return 1;
   if (gate && !sf) return refused(who, "a gate block needs the surface block it gates");
   if (gate && refused(who, surface_gate_args_refusal(gate, sf, SurfaceGateFacts{t != nullptr, true, a->points != nullptr}))) return 1;
+  if (cg && refused(who, chamfer_gate_args_refusal(cg, ChamferGateFacts{a->weights[0] > 0.f, true, a->points != nullptr}))) return 1;
   const bool surface = surface_term_on(sf);   // a block with both weights <= 0 is the step without it: nothing of it is launched or written
   const Fit3dPlan plan = plan_fit3d(a, md.V, surface && sf->w_point_surface > 0.f);
   const int N = a->num_meshes, nb = a->num_betas, S = a->num_points;
@@ -423,12 +478,24 @@ int smalfit_fit3d_step_gated(smalfit_engine* e, smalfit_mesh_objective* m, smalf
   // target points of this iteration
   const float* pts = a->points;
   const float* pnormals = gate ? gate->point_normals : nullptr;
+  // the chamfer gates' view of the same points: their normals, their boundary bytes, and where the fitted vertex normals go --
+  // where the surface term's gates ask for a copy when they want them too, so that one gather serves both
+  const ChamferGatePlan cplan = plan_chamfer_gates(cg, a->weights[0] > 0.f);
+  const float* cnormals = cg ? cg->point_normals : nullptr;
+  const unsigned char* cbound = cg ? cg->point_boundary : nullptr;
+  const bool surface_cos_vert = surface && plan_surface_gates(gate, false, sf->w_vert_surface > 0.f).cos_vert;
+  float* vnorm = surface_cos_vert && gate->vert_normals ? gate->vert_normals : m->surf_vnorm;
   if (plan.points == Fit3dPoints::SampleToCaller || plan.points == Fit3dPoints::SampleToObjective) {
     float* dst = plan.points == Fit3dPoints::SampleToCaller ? a->points_out : m->points;
-    // (with the point direction's compatibility test on, the normals are drawn with the points)
-    const bool draw_normals = surface && plan_surface_gates(gate, sf->w_point_surface > 0.f, false).cos_point;
-    if (launch_mesh_sampler(t, st, S, a->seed, a->iteration, dst, draw_normals ? m->surf_pnorm : nullptr)) return 1;
-    if (draw_normals) pnormals = m->surf_pnorm;
+    // (with a compatibility test that reads them on, in either term, the normals are drawn with the points, once; the boundary
+    // bytes with the chamfer term's boundary rule)
+    const bool surface_normals = surface && plan_surface_gates(gate, sf->w_point_surface > 0.f, false).cos_point;
+    const bool draw_normals = surface_normals || cplan.point_normals;
+    if (launch_mesh_sampler(t, st, S, a->seed, a->iteration, dst, draw_normals ? m->surf_pnorm : nullptr,
+                            cplan.point_boundary ? m->cham_pbound : nullptr)) return 1;
+    if (surface_normals) pnormals = m->surf_pnorm;
+    if (cplan.point_normals) cnormals = m->surf_pnorm;
+    if (cplan.point_boundary) cbound = m->cham_pbound;
     pts = dst;
   } else if (plan.points == Fit3dPoints::CallersCopied) {
     HIP_OK(hipMemcpyAsync(a->points_out, a->points, (size_t)N * S * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -438,10 +505,12 @@ int smalfit_fit3d_step_gated(smalfit_engine* e, smalfit_mesh_objective* m, smalf
   // (the compose kernel reads the engine's planar vertices in place; the gather kernel leaves a planar copy of the
   // vertex gradient where the LBS adjoint expects it: no layout-conversion launches in between)
   if (run_mesh_objective(m, st, N, nullptr, a->trans, a->deform_verts, pts, S, a->weights, a->verts_out, a->losses,
-                         m->dverts, m->dtrans, e->verts, md.Vp, plan.planar_vertex_grad ? e->dext : nullptr)) return 1;
+                         m->dverts, m->dtrans, e->verts, md.Vp, plan.planar_vertex_grad ? e->dext : nullptr, cg, cnormals, cbound,
+                         vnorm)) return 1;
   // the surface term at the vertices the objective composed; its gradient joins the step's in all three places it is read from
   if (surface && run_surface_term(m, t, st, sf, a->verts_out ? a->verts_out : m->verts, pts, S, m->dverts,
-                                  plan.planar_vertex_grad ? e->dext : nullptr, md.Vp, m->dtrans, a->losses, gate, pnormals)) return 1;
+                                  plan.planar_vertex_grad ? e->dext : nullptr, md.Vp, m->dtrans, a->losses, gate, pnormals,
+                                  cplan.vert_normals && surface_cos_vert ? vnorm : nullptr)) return 1;
   if (!plan.any_trained) return 0;
 
   // back through the LBS (forward state is still in the engine)

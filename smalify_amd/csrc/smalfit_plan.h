@@ -481,6 +481,70 @@ inline const char* surface_gate_args_refusal(const smalfit_surface_gate_args* g,
 // mesh3d_vertex_normal_kernel: one vertex per thread
 inline Grid2 vertex_normal_grid(int V, int N) { return Grid2{mesh_element_blocks(V), N}; }
 
+// The gates of the chamfer term (smalfit_chamfer_gate_args).  mesh3d_chamfer_kernel<ROLE, true> stages 32-byte records (position,
+// owner | unit normal, tag) where the ungated kernel stages 16: half as many at a time fill the same 16 KB, so a block's LDS --
+// the chunk, the four waves' minima (2 KB) and, in the vertex direction, their gathered sums (3 KB) -- stays 21 KB, under the
+// 32 KB that four blocks a CU allow
+constexpr int kChamGateRecordBytes = 32;
+constexpr int kChamGateChunk = 512;
+constexpr int kChamGateLdsBytes = kChamGateChunk * kChamGateRecordBytes + 2 * 4 * kMeshQueries * 4 + 4 * kMeshQueries * 3 * 4;
+static_assert(kChamGateLdsBytes <= 32 * 1024, "four gated chamfer blocks share a CU");
+// what a block switches on, in the form the kernels take it: tau^2 formed here, once, in float32 (+inf: no truncation); an open
+// compatibility test is c = -inf (every record passes and no normal is read).  A direction runs the gated instantiation when one
+// of its gates is on or one of its per-query outputs is asked for; otherwise it is the ungated kernel, and its kept count is
+// every query
+struct ChamferGatePlan {
+  bool gated_point, gated_vert;   // point -> vertex | vertex -> point runs mesh3d_chamfer_kernel<., true>
+  bool cos_point, cos_vert;
+  float c_point, c_vert;
+  float tau2_point, tau2_vert;
+  bool boundary;
+  bool vert_normals, point_normals;   // u_v / m_s are read: some compatibility test is on (each reads both sets)
+  bool point_boundary;                // b_s is read
+  bool any() const { return gated_point || gated_vert; }
+};
+// of a block chamfer_gate_args_refusal accepts (g may be NULL: everything off); with the chamfer term off everything is off
+inline ChamferGatePlan plan_chamfer_gates(const smalfit_chamfer_gate_args* g, bool chamfer_on) {
+  ChamferGatePlan p{};
+  p.c_point = p.c_vert = -INFINITY;
+  p.tau2_point = p.tau2_vert = INFINITY;
+  if (!g || !chamfer_on) return p;
+  p.cos_point = surface_gate_cos_on(g->min_cos_point);
+  p.cos_vert = surface_gate_cos_on(g->min_cos_vert);
+  if (p.cos_point) p.c_point = g->min_cos_point;
+  if (p.cos_vert) p.c_vert = g->min_cos_vert;
+  if (surface_gate_dist_on(g->max_dist_point)) p.tau2_point = g->max_dist_point * g->max_dist_point;
+  if (surface_gate_dist_on(g->max_dist_vert)) p.tau2_vert = g->max_dist_vert * g->max_dist_vert;
+  p.boundary = g->reject_boundary != 0;
+  p.gated_point = p.cos_point || p.tau2_point != INFINITY || g->point_kept || g->point_nn;
+  p.gated_vert = p.cos_vert || p.tau2_vert != INFINITY || p.boundary || g->vert_kept || g->vert_nn;
+  p.vert_normals = p.point_normals = p.cos_point || p.cos_vert;
+  p.point_boundary = p.boundary;
+  return p;
+}
+// -> why the gated entry points refuse the chamfer gate block (the text behind "<entry point>: "), or nullptr; asked after the
+// call's own arguments have been accepted
+struct ChamferGateFacts {
+  bool chamfer_on;        // w_chamfer > 0
+  bool step;              // the block rides on a step
+  bool step_has_points;   // ... whose points are the caller's
+};
+inline const char* chamfer_gate_args_refusal(const smalfit_chamfer_gate_args* g, const ChamferGateFacts& f) {
+  if (g->struct_size != (unsigned)sizeof(smalfit_chamfer_gate_args))
+    return "smalfit_chamfer_gate_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (!(g->min_cos_point <= 1.0f)) return "min_cos_point must be <= 1 and not NaN";
+  if (!(g->min_cos_vert <= 1.0f)) return "min_cos_vert must be <= 1 and not NaN";
+  if (!g->kept) return "kept missing";
+  const bool sampled = f.step && !f.step_has_points;
+  if (sampled && (g->point_normals || g->point_boundary))
+    return "point_normals and point_boundary must be NULL in a step that samples its points: it draws its own";
+  if (!f.chamfer_on) return nullptr;   // accepted and ignored
+  const bool cos_on = surface_gate_cos_on(g->min_cos_point) || surface_gate_cos_on(g->min_cos_vert);
+  if (cos_on && !sampled && !g->point_normals) return "a min_cos gate needs point_normals with the caller's points";
+  if (g->reject_boundary != 0 && !sampled && !g->point_boundary) return "reject_boundary needs point_boundary with the caller's points";
+  return nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------
 // smalfit_fit3d_step: which blocks are refused, and what a step launches
 // ------------------------------------------------------------------------------------------------

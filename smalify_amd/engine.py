@@ -618,9 +618,15 @@ class MeshObjective:
         except Exception:
             pass
 
-    def eval(self, lbs_verts, trans, deform_verts, points, weights, out=None):
+    def eval(self, lbs_verts, trans, deform_verts, points, weights, out=None, chamfer_gates=None, point_normals=None,
+             point_boundary=None, targets=None):
         """-> dict(losses (5,), verts (N,V,3), dverts (N,V,3), dtrans (N,3)); `weights` = (w_chamfer, w_edge, w_normal,
-        w_laplacian) host floats; `out` may carry preallocated tensors under the same keys"""
+        w_laplacian) host floats; `out` may carry preallocated tensors under the same keys.
+        chamfer_gates: None, or a dict of max_dist_point, max_dist_vert, min_cos_point, min_cos_vert, reject_boundary
+        (chamfer_gates(); smalfit_mesh_objective_eval_gated, include/smalfit.h): which chamfer matches count on a partial scan.  A
+        min_cos gate needs point_normals (N,S,3), reject_boundary point_boundary (N,S) uint8 (MeshTargets.sample_attrs).  Adds
+        kept (N,2) int32 = kept points | kept vertices and, while w_chamfer > 0 and some gate is on, point_kept (N,S) / vert_kept (N,V) uint8 and
+        point_nn (N,S) / vert_nn (N,V) int32 (-1: dropped point / no compatible point found)."""
         N, V = int(lbs_verts.shape[0]), self.num_verts
         if tuple(lbs_verts.shape) != (N, V, 3) or tuple(trans.shape) != (N, 3):
             raise SmalfitError("lbs_verts must be (N,%d,3) and trans (N,3)" % V)
@@ -637,10 +643,33 @@ class MeshObjective:
             if k not in o or tuple(o[k].shape) != shape:
                 o[k] = torch.empty(shape, device=dev)
         w = _host(weights, np.float32).reshape(4)
-        check(self.lib.smalfit_mesh_objective_eval(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans),
-                                                   _ptr(deform_verts), _ptr(points), S, w.ctypes.data, _ptr(o["verts"]),
-                                                   _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"])),
-              "smalfit_mesh_objective_eval")
+        if chamfer_gates is None:
+            check(self.lib.smalfit_mesh_objective_eval(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans),
+                                                       _ptr(deform_verts), _ptr(points), S, w.ctypes.data, _ptr(o["verts"]),
+                                                       _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"])),
+                  "smalfit_mesh_objective_eval")
+            return o
+        fn = _lib.resolve(self.lib, "smalfit_mesh_objective_eval_gated")
+        chamfer_gates_dict = _chamfer_gates_of(chamfer_gates)
+        g = chamfer_gate_block(chamfer_gates_dict)
+        if point_normals is not None:
+            if tuple(point_normals.shape) != (N, S, 3) or point_normals.device != dev or point_normals.dtype != torch.float32:
+                raise SmalfitError("point_normals must be float32 (N, S, 3) on the device of lbs_verts")
+            g.point_normals = _ptr(point_normals)
+        if point_boundary is not None:
+            if tuple(point_boundary.shape) != (N, S) or point_boundary.device != dev or point_boundary.dtype != torch.uint8:
+                raise SmalfitError("point_boundary must be uint8 (N, S) on the device of lbs_verts")
+            g.point_boundary = C.c_void_p(point_boundary.data_ptr())
+        masks = (("point_kept", (N, S), torch.uint8), ("vert_kept", (N, V), torch.uint8), ("point_nn", (N, S), torch.int32),
+                 ("vert_nn", (N, V), torch.int32)) if float(w[0]) > 0 and S > 0 and chamfer_gates_on(chamfer_gates_dict) else ()
+        for k, shape, dt in (("kept", (N, 2), torch.int32),) + masks:
+            if k not in o or tuple(o[k].shape) != shape or o[k].dtype != dt:
+                o[k] = torch.zeros(shape, dtype=dt, device=dev)
+            setattr(g, k, C.c_void_p(o[k].data_ptr()))
+        targets = getattr(targets, "_dev", targets)
+        check(fn(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans), _ptr(deform_verts), _ptr(points), S, w.ctypes.data,
+                 _ptr(o["verts"]), _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"]),
+                 targets.handle if targets is not None else None, C.byref(g)), "smalfit_mesh_objective_eval_gated")
         return o
 
     def score(self, verts, targets, points=None, thresholds=()):
@@ -783,6 +812,39 @@ def surface_gate_block(gates):
     return g
 
 
+CHAMFER_GATE_KEYS = SURFACE_GATE_KEYS
+
+
+def chamfer_gates(gates=None):
+    """the gates of the chamfer term with every one off, overridden by `gates`; an unknown key raises"""
+    out = dict(max_dist_point=0.0, max_dist_vert=0.0, min_cos_point=-1.0, min_cos_vert=-1.0, reject_boundary=False)
+    for k, v in (gates or {}).items():
+        if k not in out:
+            raise KeyError("unknown chamfer gate %r (have %s)" % (k, sorted(out)))
+        out[k] = bool(v) if k == "reject_boundary" else float(v)
+    return out
+
+
+_chamfer_gates_of = chamfer_gates      # (for callers whose own keyword is named chamfer_gates)
+
+
+def chamfer_gates_on(gates):
+    """some gate of the dict (as chamfer_gates returns it) is switched on"""
+    return bool(gates["reject_boundary"] or gates["min_cos_point"] > -1 or gates["min_cos_vert"] > -1 or
+                (gates["max_dist_point"] > 0 and np.isfinite(gates["max_dist_point"])) or
+                (gates["max_dist_vert"] > 0 and np.isfinite(gates["max_dist_vert"])))
+
+
+def chamfer_gate_block(gates):
+    """a smalfit_chamfer_gate_args with the switches of `gates` (a dict as chamfer_gates takes it); the pointers are the caller's"""
+    gd = chamfer_gates(gates)
+    g = _lib.ChamferGateArgs()
+    g.max_dist_point, g.max_dist_vert = gd["max_dist_point"], gd["max_dist_vert"]
+    g.min_cos_point, g.min_cos_vert = gd["min_cos_point"], gd["min_cos_vert"]
+    g.reject_boundary = int(gd["reject_boundary"])
+    return g
+
+
 class MeshTargets:
     """Target meshes resident in HBM + the area-weighted point sampler (smalfit_mesh_targets; reference
     fitter_3d/utils.py:253 Meshes(...) and trainer.py:209 sample_points_from_meshes)."""
@@ -839,3 +901,20 @@ class MeshTargets:
         check(fn(self.handle, _stream(), int(num_points), int(seed) & (2 ** 64 - 1), int(iteration) & 0xFFFFFFFF, _ptr(out),
                  _ptr(normals_out)), "smalfit_mesh_targets_sample_normals")
         return out, normals_out
+
+    def sample_attrs(self, num_points, seed, iteration, out=None, normals_out=None, boundary_out=None, normals=True, boundary=True):
+        """-> (points, normals or None, boundary or None): the points of sample() bit for bit, with every point the unit normal
+        of the target face it lies on (N, num_points, 3) and its boundary byte (N, num_points) uint8: 1 when that face has a
+        boundary edge or a corner that ends one (smalfit_mesh_targets_sample_attrs)"""
+        fn = _lib.resolve(self.lib, "smalfit_mesh_targets_sample_attrs")
+        shape = (len(self), int(num_points), 3)
+        if out is None or tuple(out.shape) != shape:
+            out = torch.empty(*shape, device=self.device)
+        if normals and (normals_out is None or tuple(normals_out.shape) != shape):
+            normals_out = torch.empty(*shape, device=self.device)
+        if boundary and (boundary_out is None or tuple(boundary_out.shape) != shape[:2]):
+            boundary_out = torch.empty(*shape[:2], dtype=torch.uint8, device=self.device)
+        check(fn(self.handle, _stream(), int(num_points), int(seed) & (2 ** 64 - 1), int(iteration) & 0xFFFFFFFF, _ptr(out),
+                 _ptr(normals_out) if normals else None, C.c_void_p(boundary_out.data_ptr()) if boundary else None),
+              "smalfit_mesh_targets_sample_attrs")
+        return out, (normals_out if normals else None), (boundary_out if boundary else None)

@@ -131,7 +131,7 @@ class Stage:
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes, mesh_names=[],
                  name="optimise", loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None,
-                 device="cuda", seed=0, iteration_offset=0, surface_gates=None):
+                 device="cuda", seed=0, iteration_offset=0, surface_gates=None, chamfer_gates=None):
         self.n_it = int(nits)
         self.name = name
         self.out_dir = out_dir
@@ -152,6 +152,8 @@ class Stage:
         # the gates of the surface term for partial scans (include/smalfit.h): all off unless given, here or as a `surface_gates`
         # block of the stage's YAML; an unknown key raises, as an unknown loss weight does
         self.surface_gates = eng.surface_gates(surface_gates)
+        # ... and the same three kinds of gate on the chamfer term's two scans (constructor or a `chamfer_gates` block of the YAML)
+        self.chamfer_gates = eng.chamfer_gates(chamfer_gates)
         if custom_lrs is not None:
             for attr in custom_lrs:
                 assert hasattr(smal_3d_fitter, attr), f"attr '{attr}' not in SMAL."
@@ -186,6 +188,9 @@ class Stage:
         self._gate_args = None         # smalfit_surface_gate_args of step(), built with the surface block while a gate is on
         self._surface_kept = None
         self._point_normals = None
+        self._cgate_args = None        # smalfit_chamfer_gate_args of step(), built on the first step while a chamfer gate is on
+        self._chamfer_kept = None
+        self._point_boundary = None
         self.consider_loss = lambda loss_name: self.loss_weights[f"w_{loss_name}"] > 0
 
     # ---- evaluation ----------------------------------------------------------------------------------------------
@@ -228,6 +233,20 @@ class Stage:
         None while the term or its gates are off"""
         return self._surface_kept
 
+    @property
+    def chamfer_gates_on(self):
+        """some gate of the chamfer term is switched on (with all of them off a step is the call of before)"""
+        return eng.chamfer_gates_on(self.chamfer_gates)
+
+    @property
+    def last_chamfer_kept(self):
+        """device tensor (N,2) int32: the kept points | kept vertices of every mesh in the chamfer term of the most recent gated
+        evaluation or step; None while the term or its gates are off"""
+        return self._chamfer_kept
+
+    def _chamfer_gated(self):
+        return self.chamfer_gates_on and self.loss_weights["w_chamfer"] > 0
+
     def _weights(self):
         return [self.loss_weights[k] for k in _WEIGHT_ORDER]
 
@@ -240,8 +259,19 @@ class Stage:
         theta = fit._pack_theta()
         lbs = e.lbs_forward(betas, theta, ls, want_Rs=False, want_v_shaped=False)[0]
         gated = self.surface_on and self.gates_on
-        normals = None
-        if points is None and gated and self.surface_weights["w_point_surface"] > 0 and self.surface_gates["min_cos_point"] > -1:
+        cgated = self._chamfer_gated()
+        cg = self.chamfer_gates
+        normals = boundary = None
+        surface_normals = gated and self.surface_weights["w_point_surface"] > 0 and self.surface_gates["min_cos_point"] > -1
+        chamfer_normals = cgated and (cg["min_cos_point"] > -1 or cg["min_cos_vert"] > -1)
+        if points is None and cgated and (chamfer_normals or cg["reject_boundary"]):
+            # the points with what the chamfer gates ask of them (and the surface gates' normals, drawn once)
+            points, normals, boundary = self.target_meshes.sample_attrs(
+                N_SAMPLE_POINTS, self.seed, self.iteration_offset + iteration, out=self._sample_buffer(), normals_out=self._point_normals,
+                boundary_out=self._point_boundary, normals=bool(chamfer_normals or surface_normals), boundary=bool(cg["reject_boundary"]))
+            self._point_normals = normals if normals is not None else self._point_normals
+            self._point_boundary = boundary if boundary is not None else self._point_boundary
+        elif points is None and surface_normals:
             points, normals = self.target_meshes.sample_normals(N_SAMPLE_POINTS, self.seed, self.iteration_offset + iteration,
                                                                 out=self._sample_buffer(), normals_out=self._point_normals)
             self._point_normals = normals
@@ -249,14 +279,18 @@ class Stage:
             points = self.target_meshes.sample(N_SAMPLE_POINTS, self.seed, self.iteration_offset + iteration, out=self._sample_buffer())
         self._last_points = points            # the sampler's buffer is never rebound: smalfit_fit3d_step writes through its raw pointer
         o = self._objective.eval(lbs, fit.trans.detach().contiguous(), fit.deform_verts.detach().contiguous(), points,
-                                 self._weights(), out=self._buffers)
+                                 self._weights(), out=self._buffers, chamfer_gates=cg if cgated else None,
+                                 point_normals=normals if chamfer_normals else None, point_boundary=boundary if cgated else None,
+                                 targets=self.target_meshes if cgated else None)
         self._buffers = o
+        self._chamfer_kept = o["kept"] if cgated else None
         total = o["losses"][4]
         if self.surface_on:
             # the stand-alone call's gradient joins the objective's before the LBS adjoint
             wp, wv = (self.surface_weights[k] for k in _SURFACE_ORDER)
             sf = self._objective.surface(o["verts"], self.target_meshes, points if wp > 0 else None, wp, wv,
-                                         gates=self.surface_gates if gated else None, point_normals=normals if wp > 0 else None)
+                                         gates=self.surface_gates if gated else None,
+                                         point_normals=normals if wp > 0 and surface_normals else None)
             self._surface_kept = sf.get("kept")
             o["dverts"] += sf["dverts"]
             o["dtrans"] += sf["dtrans"]
@@ -284,6 +318,19 @@ class Stage:
         self._t += 1
         a.adam_t = self._t
         dev_targets = getattr(self.target_meshes, "_dev", self.target_meshes)
+        if self._chamfer_gated():
+            # (the surface block and its gate block ride along when they are on; a chamfer gate block needs neither)
+            sf = gate = None
+            if self.surface_on:
+                sf = self._surface_block()
+                sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
+                gate = self._gate_block() if self.gates_on else None
+            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_partial")
+            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a),
+                         C.byref(sf) if sf is not None else None, C.byref(gate) if gate is not None else None,
+                         C.byref(self._chamfer_gate_block())), "smalfit_fit3d_step_partial")
+            self._last_points = self._points
+            return self._step_total[0] if sf is not None else self._buffers["losses"][4]
         if not self.surface_on:
             eng.check(e.lib.smalfit_fit3d_step(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a)),
                       "smalfit_fit3d_step")
@@ -381,6 +428,16 @@ class Stage:
             self._gate_args.kept = self._step_kept.data_ptr()
         self._surface_kept = self._step_kept
         return self._gate_args
+
+    def _chamfer_gate_block(self):
+        """the smalfit_chamfer_gate_args of step(): the stage's switches, the kept counts (the step samples its own points and
+        draws their normals and boundary bytes with them)"""
+        if self._cgate_args is None:
+            self._cgate_args = eng.chamfer_gate_block(self.chamfer_gates)
+            self._step_chamfer_kept = torch.zeros(self.smal_3d_fitter.batch_size, 2, dtype=torch.int32, device=self.device)
+            self._cgate_args.kept = self._step_chamfer_kept.data_ptr()
+        self._chamfer_kept = self._step_chamfer_kept
+        return self._cgate_args
 
     def run(self, plot=False, progress=True, report_every=50):
         """Run the entire Stage (trainer.py:257-270).  The description line is refreshed every `report_every`

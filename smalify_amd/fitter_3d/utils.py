@@ -94,6 +94,9 @@ class TargetMeshes:
     def sample_normals(self, num_points, seed, iteration, out=None, normals_out=None):
         return self._dev.sample_normals(num_points, seed, iteration, out=out, normals_out=normals_out)
 
+    def sample_attrs(self, num_points, seed, iteration, **kw):
+        return self._dev.sample_attrs(num_points, seed, iteration, **kw)
+
 
 def load_meshes(mesh_dir: str, sorting=lambda arr: arr, n_meshes=None, frame_step=1, device="cuda:0"):
     """Given a dir of .obj files, loads all and returns (mesh_names, target_meshes) like fitter_3d/utils.py:204-255.

@@ -3,12 +3,13 @@
 batch of N target meshes, "default" scheme (trainer.py:115), all four loss terms, 3000 target points per mesh, and the
 share of each of the five C-ABI calls of a step (torch events on the launch stream, separate short run).
 
-    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface [--gates]]
+    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface [--gates]] [--chamfer-gates]
 
 Prints one JSON line per batch size.  --surface adds the point-to-surface term both ways (w_point_surface = w_vert_surface = 1:
 every step is smalfit_fit3d_step_surface) and two fields to the line; without it the run and the line are those of before.
 --gates (with --surface) switches every gate of that term on (GATES below: every step is smalfit_fit3d_step_gated) and adds the
-kept counts of the last step.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
+kept counts of the last step.  --chamfer-gates, alone or with the others, switches every gate of the chamfer term on (every step is
+smalfit_fit3d_step_partial) and adds its kept counts.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
 import argparse
 import json
 import os
@@ -46,6 +47,7 @@ def main():
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--surface", action="store_true", help="add the point-to-surface term both ways to every step")
     ap.add_argument("--gates", action="store_true", help="with --surface: gate the term (truncation, compatibility, boundary)")
+    ap.add_argument("--chamfer-gates", action="store_true", help="gate the chamfer term (truncation, compatibility, boundary)")
     args = ap.parse_args()
     if args.gates and not args.surface:
         ap.error("--gates needs --surface")
@@ -61,7 +63,7 @@ def main():
         targets = TargetMeshes(tv, [np.asarray(md.faces)] * N)
         weights = {"w_point_surface": 1.0, "w_vert_surface": 1.0} if args.surface else None
         stage = Stage(args.iters, "default", fit, targets, lr=0.01, custom_lrs={"joint_rot": 0.005}, loss_weights=weights,
-                      surface_gates=GATES if args.gates else None)
+                      surface_gates=GATES if args.gates else None, chamfer_gates=GATES if args.chamfer_gates else None)
         for i in range(10):
             stage.step(i)
         torch.cuda.synchronize()
@@ -102,6 +104,9 @@ def main():
         if args.gates:
             line["gates"] = GATES
             line["final_surface_kept"] = stage.last_surface_kept.cpu().tolist()
+        if args.chamfer_gates:
+            line["chamfer_gates"] = GATES
+            line["final_chamfer_kept"] = stage.last_chamfer_kept.cpu().tolist()
         print(json.dumps(line))
         del stage, targets, fit
 
