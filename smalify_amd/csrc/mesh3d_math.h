@@ -56,12 +56,15 @@ SMALFIT_HD int sample_face(const uint32_t* thr, int F, uint32_t r) {
   return lo;
 }
 
-// the barycentric map of pytorch3d's _rand_barycentric_coords
+// the barycentric map of pytorch3d's _rand_barycentric_coords.  The multiply-adds are explicit fmaf, in the order the device
+// compiler contracted `w0 a + w1 b + w2 c` to (the kernel's instructions are unchanged): written as plain products and sums the
+// host, which does not contract, was a last bit away from the device on a fifth of the coordinates -- now a point drawn on the
+// host is the device's point to the bit (tests/test_gpu_template_mesh.py)
 SMALFIT_HD void barycentric_sample(const float* a, const float* b, const float* c, float u, float v, float out[3]) {
   const float su = sqrtf(u);
   const float w0 = 1.0f - su, w1 = su * (1.0f - v), w2 = su * v;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) out[k] = w0 * a[k] + w1 * b[k] + w2 * c[k];
+  for (int k = 0; k < 3; ++k) out[k] = fmaf(w2, c[k], fmaf(w0, a[k], w1 * b[k]));
 }
 
 // ------------------------------------------------------------------------------------------------
