@@ -500,7 +500,8 @@ int smalfit_mesh_targets_sample_attrs(smalfit_mesh_targets* targets, void* strea
  *   kept           kept[n] = (kept points, kept vertices) lets a caller renormalise.
  * gate == NULL, or every gate off and no mask asked for: exactly the ungated call, launch for launch and bit for bit; `kept` then
  * reads (S, V) without anything being counted.  With w_chamfer <= 0 a gate block is accepted and ignored, and `kept` reads (0, 0).
- * Not here: a soft robust kernel, gates for the edge, normal or Laplacian terms or for smalfit_mesh_score, spatial acceleration. */
+ * Not here: gates for the edge, normal or Laplacian terms or for smalfit_mesh_score, spatial acceleration.  The soft robust kernel
+ * is smalfit_robust_args below. */
 typedef struct smalfit_chamfer_gate_args {
   unsigned struct_size;       /* sizeof(smalfit_chamfer_gate_args) of the caller's header; checked before any other field */
   float max_dist_point;       /* tau of point -> vertex; <= 0 or not finite: off */
@@ -681,7 +682,7 @@ int smalfit_fit3d_step_surface(smalfit_engine* engine, smalfit_mesh_objective* o
  * No gate is differentiated through (they are piecewise constant, as the envelope theorem already assumes).  gate == NULL, or
  * every gate off: exactly the ungated call, launch for launch and bit for bit; with a block whose gates are all off `kept` reads
  * (S, V) for the directions that ran (0 for a skipped one) without anything being counted.
- * Not here: a soft robust kernel (Geman-McClure and the like), gates for smalfit_mesh_score, any spatial acceleration. */
+ * Not here: gates for smalfit_mesh_score, any spatial acceleration.  The soft robust kernel is smalfit_robust_args below. */
 typedef struct smalfit_surface_gate_args {
   unsigned struct_size;       /* sizeof(smalfit_surface_gate_args) of the caller's header; checked before any other field */
   float max_dist_point;       /* tau of point -> surface; <= 0 or not finite: off */
@@ -708,6 +709,71 @@ int smalfit_fit3d_step_gated(smalfit_engine* engine, smalfit_mesh_objective* obj
 int smalfit_fit3d_step_partial(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
                                void* stream, const smalfit_fit3d_args* args, const smalfit_surface_term_args* surface,
                                const smalfit_surface_gate_args* surface_gate, const smalfit_chamfer_gate_args* chamfer_gate);
+
+/* ---- a Geman-McClure robust kernel on both data terms -------------------------------------------------------------------
+ * A hard cap leaves a match in or out: it jumps when a query crosses tau and leaves a dropped vertex to the regularisers.  The
+ * robust kernel keeps every match, is quadratic near the surface and lets the pull of a far match fade smoothly to nothing --
+ * stray clusters (a floor, a stand) and a second animal show neither a rim nor a flipped normal.  THIS PROJECT'S definitions.
+ * For a KEPT match with float32 squared distance d^2 (the term's own bits) and its direction's scale sigma, the host forms
+ * s^2 = sigma sigma once, in float32; then, in float32,
+ *   u   = s^2 / (s^2 + d^2)      one add, one correctly rounded divide
+ *   rho = d^2 u                  what the sums take in place of d^2: sigma^2 d^2 / (sigma^2 + d^2), -> sigma^2 far away
+ *   w   = u u                    = d rho / d (d^2): what the match's gradient is multiplied by
+ * d^2 = 0 gives u = 1, rho = 0, w = 1.
+ *   matching       untouched: rho is monotone in d^2, so the nearest vertex / point / face, the compatibility tests, the tie rule,
+ *                  truncation, the boundary rule, `kept`, nn, faces, barycentrics and residuals are those of the same call
+ *                  without the block.  With the gates the kernel applies to the matches they keep.
+ *   normalisation  the denominators stay N S and N V.
+ *   chamfer        loss = 1/(N S) sum over kept s of rho(d^2_s) + 1/(N V) sum over kept v of rho(d^2_v);
+ *                  d chamfer / d y_v = 2/(N V) [v kept] w(d^2_v) (y_v - x_nn'(v)) + 2/(N S) sum over kept s with nn(s) = v of
+ *                  w(d^2_s) (y_v - x_s), times w_chamfer.  sigma_chamfer_point governs the sum over the points (both its loss
+ *                  and the second gradient sum), sigma_chamfer_vert the vertices' own matches.
+ *   surface term   L_ps and L_vs (and `rows`) sum rho; a vertex receives w_vert_surface 2/(N V) w r, the corners of a point's
+ *                  face -w_point_surface 2/(N S) w b_i r.  The optional vert_residual / point_residual stay the geometric r.
+ *   w              is not differentiated through beyond what it is: w is exactly the derivative of rho.
+ *   scales         four, independent.  A scale is OFF when sigma <= 0 or sigma is not finite, and for a direction that is
+ *                  skipped; it is REFUSED when sigma > 0 is finite but its float32 square is not a normal number.
+ *   losses         with a scale on, args->losses (chamfer, and through it the total) and surface->losses carry the robust values.
+ *   weight sums    chamfer_weight_sums / surface_weight_sums [n] = (sum of w over the kept points, over the kept vertices) of
+ *                  mesh n: float32 sums of per-block partials in block order, the way `kept` is counted; how much of the data
+ *                  still pulls.  A direction that ran with its scale off reads its kept count as a float (every weight is 1), a
+ *                  skipped direction 0.
+ *   weights        the four optional per-query outputs hold w, 0 for a dropped query; one given for a direction whose scale is
+ *                  off is refused.
+ * robust == NULL, or every scale off and no output asked for: the launches and the bits of the call without the block.  A
+ * refused block launches nothing and leaves every output alone.  Non-finite coordinates stay in bounds, value unspecified.
+ * Not here: other kernels (Huber, Cauchy), annealing sigma, robust forms of the edge, normal or Laplacian terms or of
+ * smalfit_mesh_score. */
+typedef struct smalfit_robust_args {
+  unsigned struct_size;          /* sizeof(smalfit_robust_args) of the caller's header; checked before any other field */
+  float sigma_chamfer_point;     /* sigma of chamfer point -> vertex; <= 0 or not finite: off */
+  float sigma_chamfer_vert;      /* sigma of chamfer vertex -> point */
+  float sigma_surface_point;     /* sigma of point -> surface */
+  float sigma_surface_vert;      /* sigma of vertex -> surface */
+  float* chamfer_weight_sums;    /* optional (N,2): sum of w over the kept points | kept vertices of the chamfer term */
+  float* surface_weight_sums;    /* optional (N,2): ... of the surface term */
+  float* chamfer_point_weights;  /* optional (N,S): w of every point's chamfer match, 0 for a dropped point */
+  float* chamfer_vert_weights;   /* optional (N,V) */
+  float* surface_point_weights;  /* optional (N,S) */
+  float* surface_vert_weights;   /* optional (N,V) */
+} smalfit_robust_args;
+/* the gated calls with the robust kernel; smalfit_mesh_objective_eval_gated, smalfit_mesh_surface_eval_gated and
+ * smalfit_fit3d_step_partial ARE these calls with robust = NULL.  Any of the gate blocks may be NULL as before.  The chamfer
+ * call reads the two chamfer scales and outputs, the surface call the two surface ones (outputs of the other term are refused);
+ * a step reads all of them, the surface ones only with a surface block */
+int smalfit_mesh_objective_eval_robust(smalfit_mesh_objective* objective, void* stream, int num_meshes,
+                                       const float* lbs_verts, const float* trans, const float* deform_verts,
+                                       const float* points, int num_points, const float* weights /*host*/,
+                                       float* verts_out, float* losses, float* dverts, float* dtrans,
+                                       smalfit_mesh_targets* targets, const smalfit_chamfer_gate_args* gate,
+                                       const smalfit_robust_args* robust);
+int smalfit_mesh_surface_eval_robust(smalfit_mesh_objective* objective, smalfit_mesh_targets* targets, void* stream,
+                                     const smalfit_surface_term_args* args, const smalfit_surface_gate_args* gate,
+                                     const smalfit_robust_args* robust);
+int smalfit_fit3d_step_robust(smalfit_engine* engine, smalfit_mesh_objective* objective, smalfit_mesh_targets* targets,
+                              void* stream, const smalfit_fit3d_args* args, const smalfit_surface_term_args* surface,
+                              const smalfit_surface_gate_args* surface_gate, const smalfit_chamfer_gate_args* chamfer_gate,
+                              const smalfit_robust_args* robust);
 
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137

@@ -136,6 +136,19 @@ class ChamferGateArgs(C.Structure):
             self.min_cos_vert = -1.0
 
 
+class RobustArgs(C.Structure):
+    """smalfit_robust_args: the Geman-McClure kernel on the chamfer and the surface term (smalfit_mesh_objective_eval_robust,
+    smalfit_mesh_surface_eval_robust, smalfit_fit3d_step_robust); every scale 0 = off"""
+    _fields_ = [("struct_size", C.c_uint), ("sigma_chamfer_point", C.c_float), ("sigma_chamfer_vert", C.c_float),
+                ("sigma_surface_point", C.c_float), ("sigma_surface_vert", C.c_float), ("chamfer_weight_sums", C.c_void_p),
+                ("surface_weight_sums", C.c_void_p), ("chamfer_point_weights", C.c_void_p), ("chamfer_vert_weights", C.c_void_p),
+                ("surface_point_weights", C.c_void_p), ("surface_vert_weights", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(RobustArgs)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -247,6 +260,12 @@ SIGNATURES = {
                                                C.POINTER(ChamferGateArgs)]),
     "smalfit_fit3d_step_partial": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs),
                                         C.POINTER(ChamferGateArgs)]),
+    "smalfit_mesh_objective_eval_robust": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP,
+                                                C.POINTER(ChamferGateArgs), C.POINTER(RobustArgs)]),
+    "smalfit_mesh_surface_eval_robust": (_I, [_VP, _VP, _VP, C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs),
+                                              C.POINTER(RobustArgs)]),
+    "smalfit_fit3d_step_robust": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs),
+                                       C.POINTER(ChamferGateArgs), C.POINTER(RobustArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
@@ -254,7 +273,8 @@ SIGNATURES = {
 LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "smalfit_mesh_score", "smalfit_mesh_surface_eval",
                           "smalfit_fit3d_step_surface", "smalfit_mesh_surface_eval_gated", "smalfit_fit3d_step_gated",
                           "smalfit_mesh_targets_sample_normals", "smalfit_mesh_targets_sample_attrs",
-                          "smalfit_mesh_objective_eval_gated", "smalfit_fit3d_step_partial"])
+                          "smalfit_mesh_objective_eval_gated", "smalfit_fit3d_step_partial", "smalfit_mesh_objective_eval_robust",
+                          "smalfit_mesh_surface_eval_robust", "smalfit_fit3d_step_robust"])
 
 
 class SmalfitError(RuntimeError):

@@ -67,6 +67,14 @@ struct Mesh3dArgs {
   unsigned char* vert_kept;      // [N][V] or null
   int* point_nn;                 // [N][S] or null: a copy of nn_idx
   int* vert_nn;                  // [N][V] or null
+  // the robust kernel (smalfit_robust_args, planned by plan_robust); read by the ROBUST instantiations and, `weight_sums`, by the reduce
+  float s2_p, s2_v;              // sigma^2 of point -> vertex | vertex -> point; 0: off (w = 1, rho = d^2)
+  float* wts;                    // [N][S] w_s of every point's match (0: dropped), written by chamfer<0, ., true>, staged by <1, ., true>
+  float* part_wx;                // [N][bx] per-block sums of w of chamfer<0, ., true>, null where no ROBUST instantiation ran
+  float* part_wy;                // [N][by]
+  float* weight_sums;            // [N][2] or null
+  float* point_w;                // [N][S] or null: a copy of wts
+  float* vert_w;                 // [N][V] or null
 };
 
 constexpr int kChamQueries = 64;    // queries per block: one per lane, the same 64 in each of the 4 waves
@@ -94,7 +102,12 @@ __global__ __launch_bounds__(256) void mesh3d_compose_kernel(Mesh3dArgs a) {
 // and every record is compatible); the waves' minima meet as before, then wave 0 decides once per query: found, truncation,
 // (ROLE 1) the boundary rule on the winner.  A dropped point writes nn_idx = -1, so no vertex gathers it; a dropped query adds
 // nothing to the sum of d^2 or to its own gradient term; the block's kept count goes beside its sum
-template <int ROLE, bool GATED>
+// ROBUST (either way gated): the scan and the match are those of <ROLE, GATED, false>; wave 0 then applies robust_gm once per
+// query -- s2 = 0 stands for this direction's scale being off: w = 1, rho = d^2 -- sums rho in place of d^2 and w beside it.
+// ROLE 0 leaves w_s per point (0 for a dropped one); ROLE 1 stages those in a float array beside the records (4 KB at
+// kChamChunk, 2 KB at kChamGateChunk) and gathers sum w_s (y_v - x_s) with the same branch-free mask, and multiplies its own
+// match by w(best): no divide enters the scan
+template <int ROLE, bool GATED, bool ROBUST = false>
 __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
   __shared__ float sd[4][kChamQueries];
   __shared__ int si[4][kChamQueries];
@@ -128,6 +141,9 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
   float best = INFINITY;
   int bidx = 0x7fffffff;   // GATED: the winner's tag (gated_tag: ascending with the index)
   float g[3] = {0.f, 0.f, 0.f};
+  constexpr bool kWeighted = ROBUST && ROLE == 1;
+  __shared__ float sw[kWeighted ? (GATED ? kChamGateChunk : kChamChunk) : 1];   // (not used, and not allocated, unless kWeighted)
+  const float* wsrc = a.wts + (size_t)n * a.S;
   if constexpr (GATED) {
     __shared__ GatedScanPoint gp[kChamGateChunk];
     for (int base = 0; base < no; base += kChamGateChunk) {
@@ -149,12 +165,14 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
         }
         s.tag = gated_tag(base + i, ob != nullptr ? ob[base + i] : 0);
         gp[i] = s;
+        if constexpr (kWeighted) sw[i] = wsrc[base + i];
       }
       __syncthreads();
       const int per = (cnt + 3) >> 2;
       const int b = min(w * per, cnt), e = min(b + per, cnt);
       // (wave-uniform as below: two broadcast 16-byte LDS reads per record)
-      nearest_scan_gated<ROLE == 1>(qx, qy, qz, ux, uy, uz, c, gp, b, e, best, bidx, qi, g);
+      if constexpr (kWeighted) nearest_scan_gated<true, true>(qx, qy, qz, ux, uy, uz, c, gp, b, e, best, bidx, qi, g, sw);
+      else nearest_scan_gated<ROLE == 1>(qx, qy, qz, ux, uy, uz, c, gp, b, e, best, bidx, qi, g);
     }
   } else {
     __shared__ ScanPoint sp[kChamChunk];
@@ -169,12 +187,14 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
         s.z = src[2];
         s.owner = ROLE == 1 ? own[base + i] : 0;
         sp[i] = s;
+        if constexpr (kWeighted) sw[i] = wsrc[base + i];
       }
       __syncthreads();
       const int per = (cnt + 3) >> 2;
       const int b = min(w * per, cnt), e = min(b + per, cnt);
       // b, e are wave-uniform: every lane reads the same 16-byte LDS record (broadcast, conflict free)
-      nearest_scan<ROLE == 1>(qx, qy, qz, sp, b, e, base, best, bidx, qi, g);
+      if constexpr (kWeighted) nearest_scan<true, true>(qx, qy, qz, sp, b, e, base, best, bidx, qi, g, sw);
+      else nearest_scan<ROLE == 1>(qx, qy, qz, sp, b, e, base, best, bidx, qi, g);
     }
   }
   sd[w][lane] = best;
@@ -194,6 +214,53 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
       g[1] += sg[s][lane][1];
       g[2] += sg[s][lane][2];
     }
+  }
+  if constexpr (ROBUST) {
+    // the match of <ROLE, GATED, false>, then the kernel on it
+    bool kept = active;
+    int index = bidx;
+    if constexpr (GATED) {
+      const GatedMatch mt = gated_match(best, bidx, ROLE == 0 ? a.tau2_p : a.tau2_v, ob != nullptr ? 1 : 0);
+      kept = active && mt.kept;
+      index = mt.index;
+    }
+    const float s2 = ROLE == 0 ? a.s2_p : a.s2_v;
+    float rho = best, wq = 1.0f;
+    if (s2 > 0.f) robust_gm(best, s2, rho, wq);
+    rho = kept ? rho : 0.f;
+    wq = kept ? wq : 0.f;
+    if (active) {
+      const size_t oq = (size_t)n * nq + qi;
+      if (ROLE == 0) {
+        const int nn = GATED ? (kept ? index : -1) : index;
+        a.nn_idx[oq] = nn;
+        a.wts[oq] = wq;
+        if (a.point_w != nullptr) a.point_w[oq] = wq;
+        if (GATED && a.point_nn != nullptr) a.point_nn[oq] = nn;
+        if (GATED && a.point_kept != nullptr) a.point_kept[oq] = kept ? 1 : 0;
+      } else {
+        if (a.vert_w != nullptr) a.vert_w[oq] = wq;
+        if (GATED && a.vert_nn != nullptr) a.vert_nn[oq] = index;
+        if (GATED && a.vert_kept != nullptr) a.vert_kept[oq] = kept ? 1 : 0;
+        const float cy = (a.w_chamfer * 2.0f / ((float)a.V * (float)a.N)) * wq;   // (wq = 0: a dropped vertex keeps only what it gathered)
+        const float cx = a.w_chamfer * 2.0f / ((float)a.S * (float)a.N);
+        const float* xn = o + 3 * (size_t)(kept && index >= 0 && index < no ? index : 0);   // no finite distance (NaN input): stay in bounds
+        float* out = a.gcham + oq * 3;
+        out[0] = cy * (qx - xn[0]) + cx * g[0];
+        out[1] = cy * (qy - xn[1]) + cx * g[1];
+        out[2] = cy * (qz - xn[2]) + cx * g[2];
+      }
+    }
+    const float tot = wave_sum(rho);
+    const float wtot = wave_sum(wq);
+    const int cnt = __popcll(__ballot(kept));
+    if (lane == 0) {
+      const size_t slot = (size_t)n * gridDim.x + blockIdx.x;
+      (ROLE == 0 ? a.part_cx : a.part_cy)[slot] = tot;
+      (ROLE == 0 ? a.part_wx : a.part_wy)[slot] = wtot;
+      if (GATED) (ROLE == 0 ? a.part_kx : a.part_ky)[slot] = cnt;
+    }
+    return;
   }
   if constexpr (GATED) {
     const GatedMatch mt = gated_match(best, bidx, ROLE == 0 ? a.tau2_p : a.tau2_v, ob != nullptr ? 1 : 0);
@@ -372,6 +439,30 @@ __global__ __launch_bounds__(256) void mesh3d_reduce_kernel(Mesh3dArgs a) {
       }
       a.kept[2 * n] = kp;
       a.kept[2 * n + 1] = kv;
+    }
+  }
+  if (a.weight_sums != nullptr) {
+    // summed by the ROBUST chamfer kernels, per mesh in block order; where none ran every weight is 1: the kept count, as a float
+    for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
+      float wp = 0.f, wv = 0.f;
+      if (a.part_wx != nullptr) {
+        for (int b = 0; b < a.bx; ++b) wp += a.part_wx[(size_t)n * a.bx + b];
+        for (int b = 0; b < a.by; ++b) wv += a.part_wy[(size_t)n * a.by + b];
+      } else if (a.w_chamfer > 0.f) {
+        int kp = a.S, kv = a.V;
+        if (a.part_kx != nullptr) {
+          kp = 0;
+          for (int b = 0; b < a.bx; ++b) kp += a.part_kx[(size_t)n * a.bx + b];
+        }
+        if (a.part_ky != nullptr) {
+          kv = 0;
+          for (int b = 0; b < a.by; ++b) kv += a.part_ky[(size_t)n * a.by + b];
+        }
+        wp = (float)kp;
+        wv = (float)kv;
+      }
+      a.weight_sums[2 * n] = wp;
+      a.weight_sums[2 * n + 1] = wv;
     }
   }
 }
@@ -579,6 +670,13 @@ struct SurfaceTermArgs {
   const int* vf_off;         // [V+1], [3F]: vertex -> incident faces of the fitted topology (mesh3d_vertex_normal_kernel)
   const int* vf;
   float* normals_out;        // [N][V][3] what mesh3d_vertex_normal_kernel writes (= normals_v)
+  // the robust kernel (smalfit_robust_args, planned by plan_robust); read by the ROBUST instantiations and, `weight_sums`, by the reduce
+  float s2_v, s2_p;          // sigma^2 of vertex -> surface | point -> surface (> 0 where the ROBUST instantiation runs)
+  float* part_wv;            // [N][hv] per-block sums of w of hit<0, ., true>, null where hit<0, ., false> ran
+  float* part_wp;            // [N][hp]
+  float* weight_sums;        // [N][2] or null
+  float* vert_w;             // [N][V] or null
+  float* point_w;            // [N][S] or null
 };
 
 // ROLE 0: queries = fitted vertices, scanned = the staged records of target mesh n.  ROLE 1: queries = the points, scanned = the
@@ -654,7 +752,10 @@ __global__ __launch_bounds__(256) void mesh3d_surface_near_kernel(SurfaceTermArg
 // one query per thread: the closest point on the face its key names.  GATED: a query is DROPPED when its key is all ones (no
 // face, or none compatible), when d^2 > tau^2, or (ROLE 0) by the boundary rule; a dropped query leaves d^2 = 0, a zero residual
 // and zero weights -- mesh3d_surface_grad_kernel runs unchanged -- and face -1; the block's kept count goes beside its sum of d^2
-template <int ROLE, bool GATED>
+// ROBUST: robust_gm on the match's d^2 (the scan's own bits): the block sums rho in place of d^2 and w beside it, and what
+// mesh3d_surface_grad_kernel reads (res_v / hits) carries w r, so that kernel runs unchanged; the optional residual outputs
+// keep the geometric r, and a dropped query's weight is 0
+template <int ROLE, bool GATED, bool ROBUST = false>
 __global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceTermArgs a) {
   __shared__ float red[16];
   const int n = blockIdx.y;
@@ -662,6 +763,7 @@ __global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceT
   const int qi = blockIdx.x * kMeshBlock + threadIdx.x;
   float d2 = 0.f;
   int kept = 0;
+  float wq = 0.f;   // ROBUST only
   if (qi < nq) {
     const size_t o = (size_t)n * nq + qi;
     const float* q = (ROLE == 0 ? a.verts : a.points) + 3 * o;
@@ -699,15 +801,26 @@ __global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceT
       h = point_scan_tri_closest(q[0], q[1], q[2], tri);
       d2 = key == ~0ull ? h.d2 : __uint_as_float((unsigned)(key >> 32));   // the scan's own bits
     }
+    float wr[3] = {h.r[0], h.r[1], h.r[2]};   // what the gradient gathers: r, ROBUST: w r
+    if constexpr (ROBUST) {
+      float rho;
+      robust_gm(d2, ROLE == 0 ? a.s2_v : a.s2_p, rho, wq);
+      d2 = rho;
+      if (GATED && kept == 0) wq = 0.f;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) wr[k] = wq * h.r[k];
+      float* ow = ROLE == 0 ? a.vert_w : a.point_w;
+      if (ow != nullptr) ow[o] = wq;
+    }
     if (ROLE == 0) {
-      a.res_v[3 * o] = h.r[0];
-      a.res_v[3 * o + 1] = h.r[1];
-      a.res_v[3 * o + 2] = h.r[2];
+      a.res_v[3 * o] = wr[0];
+      a.res_v[3 * o + 1] = wr[1];
+      a.res_v[3 * o + 2] = wr[2];
     } else {
       SurfaceHit s;
       s.c0 = fc[0]; s.c1 = fc[1]; s.c2 = fc[2];
       s.b0 = h.b[0]; s.b1 = h.b[1]; s.b2 = h.b[2];
-      s.rx = h.r[0]; s.ry = h.r[1]; s.rz = h.r[2];
+      s.rx = wr[0]; s.ry = wr[1]; s.rz = wr[2];
       s.pad0 = s.pad1 = s.pad2 = 0.f;
       a.hits[o] = s;
     }
@@ -731,6 +844,10 @@ __global__ __launch_bounds__(kMeshBlock) void mesh3d_surface_hit_kernel(SurfaceT
   if (GATED) {
     const int cnt = __syncthreads_count(kept);      // (an integer count: no order to fix)
     if (threadIdx.x == 0) (ROLE == 0 ? a.part_kv : a.part_kp)[(size_t)n * gridDim.x + blockIdx.x] = cnt;
+  }
+  if constexpr (ROBUST) {
+    const float wtot = block_sum(wq, red);
+    if (threadIdx.x == 0) (ROLE == 0 ? a.part_wv : a.part_wp)[(size_t)n * gridDim.x + blockIdx.x] = wtot;
   }
 }
 
@@ -834,6 +951,36 @@ __global__ __launch_bounds__(256) void mesh3d_surface_reduce_kernel(SurfaceTermA
       }
       a.kept[2 * n] = kp;
       a.kept[2 * n + 1] = kv;
+    }
+    if (a.weight_sums != nullptr) {
+      // summed by the ROBUST hit kernels in block order; where the other one ran every weight is 1: the kept count, as a float
+      float wp = 0.f, wv = 0.f;
+      if (a.w_ps > 0.f) {
+        if (a.part_wp != nullptr) {
+          for (int b = 0; b < a.hp; ++b) wp += a.part_wp[(size_t)n * a.hp + b];
+        } else {
+          int kp = a.S;
+          if (a.part_kp != nullptr) {
+            kp = 0;
+            for (int b = 0; b < a.hp; ++b) kp += a.part_kp[(size_t)n * a.hp + b];
+          }
+          wp = (float)kp;
+        }
+      }
+      if (a.w_vs > 0.f) {
+        if (a.part_wv != nullptr) {
+          for (int b = 0; b < a.hv; ++b) wv += a.part_wv[(size_t)n * a.hv + b];
+        } else {
+          int kv = a.V;
+          if (a.part_kv != nullptr) {
+            kv = 0;
+            for (int b = 0; b < a.hv; ++b) kv += a.part_kv[(size_t)n * a.hv + b];
+          }
+          wv = (float)kv;
+        }
+      }
+      a.weight_sums[2 * n] = wp;
+      a.weight_sums[2 * n + 1] = wv;
     }
   }
   tp = block_sum(tp, red);

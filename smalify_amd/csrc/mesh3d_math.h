@@ -78,9 +78,11 @@ struct alignas(16) ScanPoint {
   int owner;
 };
 
-template <bool OWNER>
+// WEIGHTED (the robust kernel below): wt[j] is the weight w_s of staged point j, and the gather becomes sum w_s (q - p_j): the
+// mask carries the weight in place of 1, so the loop stays branch-free and no divide enters it
+template <bool OWNER, bool WEIGHTED = false>
 SMALFIT_HD void nearest_scan(float qx, float qy, float qz, const ScanPoint* p, int begin, int end, int index_base,
-                             float& best, int& best_idx, int self, float g[3]) {
+                             float& best, int& best_idx, int self, float g[3], const float* wt = nullptr) {
 #pragma unroll 4
   for (int j = begin; j < end; ++j) {
     const ScanPoint s = p[j];
@@ -91,7 +93,8 @@ SMALFIT_HD void nearest_scan(float qx, float qy, float qz, const ScanPoint* p, i
       best_idx = index_base + j;
     }
     if (OWNER) {
-      const float mk = s.owner == self ? 1.0f : 0.0f;   // branch-free: g + 1 * d and g + 0 * d are exact
+      float mk = s.owner == self ? 1.0f : 0.0f;   // branch-free: g + 1 * d and g + 0 * d are exact
+      if (WEIGHTED) mk = s.owner == self ? wt[j] : 0.0f;
       g[0] = fmaf(mk, dx, g[0]);
       g[1] = fmaf(mk, dy, g[1]);
       g[2] = fmaf(mk, dz, g[2]);
@@ -136,9 +139,9 @@ SMALFIT_HD bool unit_normals_compatible(float ax, float ay, float az, float bx, 
 // nearest_scan over the records compatible with the query's normal (ux, uy, uz): the same d^2 expression, the same strict '<',
 // the same lowest-index tie rule; best_tag is the winner's tag.  The owner gather keeps its mask over ALL staged records,
 // compatible or not: those matches were vetted in the other direction
-template <bool OWNER>
+template <bool OWNER, bool WEIGHTED = false>
 SMALFIT_HD void nearest_scan_gated(float qx, float qy, float qz, float ux, float uy, float uz, float c, const GatedScanPoint* p,
-                                   int begin, int end, float& best, int& best_tag, int self, float g[3]) {
+                                   int begin, int end, float& best, int& best_tag, int self, float g[3], const float* wt = nullptr) {
 #pragma unroll 4
   for (int j = begin; j < end; ++j) {
     // each row as ONE 16-byte read, the tag with the normal it shares a row with: read field by field, the tag's load is sunk
@@ -151,7 +154,8 @@ SMALFIT_HD void nearest_scan_gated(float qx, float qy, float qz, float ux, float
     best = take ? d2 : best;
     best_tag = take ? float_bits(r1[3]) : best_tag;
     if (OWNER) {
-      const float mk = float_bits(r0[3]) == self ? 1.0f : 0.0f;
+      float mk = float_bits(r0[3]) == self ? 1.0f : 0.0f;
+      if (WEIGHTED) mk = float_bits(r0[3]) == self ? wt[j] : 0.0f;   // (as in nearest_scan)
       g[0] = fmaf(mk, dx, g[0]);
       g[1] = fmaf(mk, dy, g[1]);
       g[2] = fmaf(mk, dz, g[2]);
@@ -171,6 +175,18 @@ SMALFIT_HD GatedMatch gated_match(float best, int best_tag, float tau2, int reje
   m.index = found ? best_tag >> 1 : -1;
   m.kept = found & !(best > tau2) & !((reject_boundary != 0) & ((best_tag & 1) != 0));
   return m;
+}
+
+// ---- the robust kernel of both data terms (smalfit_robust_args; worded in include/smalfit.h) -----------------------------
+// Geman-McClure on a kept match's float32 d^2 with s2 = sigma * sigma (formed once on the host, in float32):
+//   u = s2 / (s2 + d2)     one float32 add, one correctly rounded float32 divide
+//   rho = d2 * u           what the sums take in place of d^2 (-> s2 far away)
+//   w = u * u              = d rho / d (d^2): what the match's gradient is multiplied by
+// d2 = 0 gives u = 1, rho = 0, w = 1.  The one definition: every kernel that applies the kernel and the host shim call this
+SMALFIT_HD void robust_gm(float d2, float s2, float& rho, float& w) {
+  const float u = s2 / (s2 + d2);
+  rho = d2 * u;
+  w = u * u;
 }
 
 // ------------------------------------------------------------------------------------------------

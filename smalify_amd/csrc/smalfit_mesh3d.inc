@@ -36,6 +36,8 @@ struct smalfit_mesh_objective {
   // the gates of the chamfer term only: the sampled points' boundary bytes, per-block kept counts (the normals are the two above)
   unsigned char* cham_pbound = nullptr;
   int *part_kx = nullptr, *part_ky = nullptr;
+  // the robust kernel only: the points' chamfer weights, per-block sums of w of both terms
+  float *cham_w = nullptr, *part_wx = nullptr, *part_wy = nullptr, *surf_part_wp = nullptr, *surf_part_wv = nullptr;
 };
 
 struct smalfit_mesh_targets {
@@ -51,11 +53,15 @@ struct smalfit_mesh_targets {
 // per coordinate, the addition Stage.step_unfused performs on the stand-alone call's outputs -- the two paths form the same bits
 // With a gate block (validated by the callers; point_normals: the caller's or the sampler's) the gated instantiations take the
 // place of the ungated ones where plan_surface_gates says so; with none, or every gate off, the launches are those of before
+// With a robust block (validated by the callers) the hit kernel of a direction is its ROBUST instantiation where plan_robust
+// says so; with none, or its scales off, the launches are those of before (the reduce then reads the weight sums, if asked for,
+// off the kept counts)
 static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_targets* t, hipStream_t st, const smalfit_surface_term_args* a,
                             const float* verts, const float* points, int num_points, float* acc_dverts = nullptr,
                             float* acc_planar = nullptr, int Vp = 0, float* acc_dtrans = nullptr,
                             const float* step_losses = nullptr, const smalfit_surface_gate_args* gate = nullptr,
-                            const float* point_normals = nullptr, const float* ready_vnorm = nullptr) {
+                            const float* point_normals = nullptr, const float* ready_vnorm = nullptr,
+                            const smalfit_robust_args* robust = nullptr) {
   SurfaceTermArgs k{};
   k.N = a->num_meshes; k.V = m->t.V; k.F = m->num_faces;
   k.w_ps = mesh_weight(a->w_point_surface); k.w_vs = mesh_weight(a->w_vert_surface);
@@ -84,6 +90,11 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
     if (gp.cos_vert) { k.normals_out = gate->vert_normals ? gate->vert_normals : m->surf_vnorm; k.normals_v = ready_vnorm ? ready_vnorm : k.normals_out; }
     if (gp.cos_point) k.normals_p = point_normals;
   }
+  const RobustPlan rp = plan_robust(robust, RobustFacts{false, true, false, k.w_ps > 0.f, k.w_vs > 0.f});
+  k.s2_v = rp.s2_surface_vert; k.s2_p = rp.s2_surface_point;
+  if (robust) k.weight_sums = robust->surface_weight_sums;
+  if (rp.surface_vert) { k.part_wv = m->surf_part_wv; k.vert_w = robust->surface_vert_weights; }
+  if (rp.surface_point) { k.part_wp = m->surf_part_wp; k.point_w = robust->surface_point_weights; }
   // the keys of the directions that run, all ones: the vertices' come first, the points' behind them
   unsigned long long* first = k.w_vs > 0.f ? k.keys_v : k.keys_p;
   const size_t keys = (size_t)k.N * ((k.w_vs > 0.f ? (size_t)k.V : 0) + (k.w_ps > 0.f ? (size_t)k.S : 0));
@@ -101,7 +112,10 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
       mesh3d_surface_near_kernel<0, false><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
     }
     LAUNCH_OK("mesh3d_surface_near_kernel<0>");
-    if (gp.any) mesh3d_surface_hit_kernel<0, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
+    if (rp.surface_vert) {
+      if (gp.any) mesh3d_surface_hit_kernel<0, true, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
+      else mesh3d_surface_hit_kernel<0, false, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
+    } else if (gp.any) mesh3d_surface_hit_kernel<0, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
     else mesh3d_surface_hit_kernel<0, false><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
     LAUNCH_OK("mesh3d_surface_hit_kernel<0>");
   }
@@ -110,7 +124,10 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
     if (gp.cos_point) mesh3d_surface_near_kernel<1, true><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
     else mesh3d_surface_near_kernel<1, false><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
     LAUNCH_OK("mesh3d_surface_near_kernel<1>");
-    if (gp.any) mesh3d_surface_hit_kernel<1, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
+    if (rp.surface_point) {
+      if (gp.any) mesh3d_surface_hit_kernel<1, true, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
+      else mesh3d_surface_hit_kernel<1, false, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
+    } else if (gp.any) mesh3d_surface_hit_kernel<1, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
     else mesh3d_surface_hit_kernel<1, false><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
     LAUNCH_OK("mesh3d_surface_hit_kernel<1>");
   }
@@ -125,12 +142,15 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
 // point_normals / point_boundary: the caller's or the sampler's; vnorm: where the fitted vertex normals go when a compatibility
 // test asks for them) the gated chamfer instantiations take the place of the ungated ones where plan_chamfer_gates says so, and
 // mesh3d_vertex_normal_kernel runs between compose and them; with none, or every gate off, the launches are those of before
+// With a robust block (validated by the callers) whose plan has a chamfer scale on, both chamfer launches are the ROBUST
+// instantiations of the kernel the gates chose; with none, or both scales off, the launches are those of before
 static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num_meshes, const float* lbs_verts,
                               const float* trans, const float* deform_verts, const float* points, int num_points,
                               const float* weights, float* verts_out, float* losses, float* dverts, float* dtrans,
                               const float* lbs_planar = nullptr, int Vp = 0, float* dverts_planar = nullptr,
                               const smalfit_chamfer_gate_args* gate = nullptr, const float* point_normals = nullptr,
-                              const unsigned char* point_boundary = nullptr, float* vnorm = nullptr) {
+                              const unsigned char* point_boundary = nullptr, float* vnorm = nullptr,
+                              const smalfit_robust_args* robust = nullptr) {
   const float wc = mesh_weight(weights[0]);
   Mesh3dArgs a{};
   a.N = num_meshes; a.V = m->t.V; a.S = mesh_points(wc, num_points);
@@ -153,6 +173,13 @@ static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num
   if (gp.gated_vert) { a.part_ky = m->part_ky; a.vert_kept = gate->vert_kept; a.vert_nn = gate->vert_nn; }
   if (gp.point_boundary) a.bound_p = point_boundary;
   if (gp.vert_normals) { a.normals_v = vnorm; a.normals_p = point_normals; }
+  const RobustPlan rp = plan_robust(robust, RobustFacts{true, false, wc > 0.f, false, false});
+  a.s2_p = rp.s2_chamfer_point; a.s2_v = rp.s2_chamfer_vert;
+  if (robust) a.weight_sums = robust->chamfer_weight_sums;
+  if (rp.chamfer) {
+    a.wts = m->cham_w; a.part_wx = m->part_wx; a.part_wy = m->part_wy;
+    a.point_w = robust->chamfer_point_weights; a.vert_w = robust->chamfer_vert_weights;
+  }
   mesh3d_compose_kernel<<<dim3(mesh_compose_blocks(a.N, a.V)), 256, 0, st>>>(a);
   LAUNCH_OK("mesh3d_compose_kernel");
   if (gp.vert_normals) {
@@ -163,10 +190,16 @@ static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num
     LAUNCH_OK("mesh3d_vertex_normal_kernel");
   }
   if (wc > 0.f) {
-    if (gp.gated_point) mesh3d_chamfer_kernel<0, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
+    if (rp.chamfer) {
+      if (gp.gated_point) mesh3d_chamfer_kernel<0, true, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
+      else mesh3d_chamfer_kernel<0, false, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
+    } else if (gp.gated_point) mesh3d_chamfer_kernel<0, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
     else mesh3d_chamfer_kernel<0, false><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
     LAUNCH_OK("mesh3d_chamfer_kernel<0>");
-    if (gp.gated_vert) mesh3d_chamfer_kernel<1, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
+    if (rp.chamfer) {
+      if (gp.gated_vert) mesh3d_chamfer_kernel<1, true, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
+      else mesh3d_chamfer_kernel<1, false, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
+    } else if (gp.gated_vert) mesh3d_chamfer_kernel<1, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
     else mesh3d_chamfer_kernel<1, false><<<dim3(a.by, a.N), 256, 0, st>>>(a);
     LAUNCH_OK("mesh3d_chamfer_kernel<1>");
   } else {
@@ -262,6 +295,11 @@ int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces
   w.field(m->cham_pbound, N * S);
   w.field(m->part_kx, N * m->bx);
   w.field(m->part_ky, N * m->by);
+  w.field(m->cham_w, N * S);
+  w.field(m->part_wx, N * m->bx);
+  w.field(m->part_wy, N * m->by);
+  w.field(m->surf_part_wp, N * (size_t)surface_hit_grid((int)S, 1).x);
+  w.field(m->surf_part_wv, N * (size_t)surface_hit_grid((int)V, 1).x);
   auto bail = [&](const char* what) {
     smalfit_mesh_objective_destroy(m);
     return refused("smalfit_mesh_objective_create", what);
@@ -299,14 +337,24 @@ int smalfit_mesh_objective_eval_gated(smalfit_mesh_objective* m, void* stream, i
                                       const float* trans, const float* deform_verts, const float* points, int num_points,
                                       const float* weights /* host [4] */, float* verts_out, float* losses, float* dverts,
                                       float* dtrans, smalfit_mesh_targets* t, const smalfit_chamfer_gate_args* g) {
-  const char* who = g ? "smalfit_mesh_objective_eval_gated" : "smalfit_mesh_objective_eval";
+  return smalfit_mesh_objective_eval_robust(m, stream, num_meshes, lbs_verts, trans, deform_verts, points, num_points, weights, verts_out,
+                                            losses, dverts, dtrans, t, g, nullptr);
+}
+
+int smalfit_mesh_objective_eval_robust(smalfit_mesh_objective* m, void* stream, int num_meshes, const float* lbs_verts,
+                                       const float* trans, const float* deform_verts, const float* points, int num_points,
+                                       const float* weights /* host [4] */, float* verts_out, float* losses, float* dverts,
+                                       float* dtrans, smalfit_mesh_targets* t, const smalfit_chamfer_gate_args* g,
+                                       const smalfit_robust_args* rb) {
+  const char* who = rb ? "smalfit_mesh_objective_eval_robust" : g ? "smalfit_mesh_objective_eval_gated" : "smalfit_mesh_objective_eval";
   if (refused(who, null_argument_refusal(m && lbs_verts && trans && weights && losses && dverts && dtrans))) return 1;
   if (refused(who, mesh_eval_refusal(num_meshes, m->max_meshes, weights[0], points != nullptr, num_points, m->max_points))) return 1;
   if (g && refused(who, chamfer_gate_args_refusal(g, ChamferGateFacts{weights[0] > 0.f, false, false}))) return 1;
   if (g && t && t->d.N != num_meshes) return refused(who, "number of target meshes differs from num_meshes");
+  if (rb && refused(who, robust_args_refusal(rb, RobustFacts{true, false, weights[0] > 0.f, false, false}))) return 1;
   return run_mesh_objective(m, (hipStream_t)stream, num_meshes, lbs_verts, trans, deform_verts, points, num_points, weights,
                             verts_out, losses, dverts, dtrans, nullptr, 0, nullptr, g, g ? g->point_normals : nullptr,
-                            g ? g->point_boundary : nullptr, m->surf_vnorm);
+                            g ? g->point_boundary : nullptr, m->surf_vnorm, rb);
 }
 
 int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const int* face_counts, const float* verts,
@@ -424,14 +472,21 @@ int smalfit_mesh_surface_eval(smalfit_mesh_objective* m, smalfit_mesh_targets* t
 
 int smalfit_mesh_surface_eval_gated(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream, const smalfit_surface_term_args* a,
                                     const smalfit_surface_gate_args* g) {
-  const char* who = g ? "smalfit_mesh_surface_eval_gated" : "smalfit_mesh_surface_eval";
+  return smalfit_mesh_surface_eval_robust(m, t, stream, a, g, nullptr);
+}
+
+int smalfit_mesh_surface_eval_robust(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream, const smalfit_surface_term_args* a,
+                                     const smalfit_surface_gate_args* g, const smalfit_robust_args* rb) {
+  const char* who = rb ? "smalfit_mesh_surface_eval_robust" : g ? "smalfit_mesh_surface_eval_gated" : "smalfit_mesh_surface_eval";
   if (refused(who, null_argument_refusal(m && a))) return 1;
   if (refused(who, surface_term_args_refusal(a, SurfaceTermFacts{m->max_meshes, m->max_points, t != nullptr, t ? t->d.N : 0, false, 0, 0,
                                                                  false})))
     return 1;
   if (g && refused(who, surface_gate_args_refusal(g, a, SurfaceGateFacts{t != nullptr, false, false}))) return 1;
+  if (rb && refused(who, robust_args_refusal(rb, RobustFacts{false, true, false, a->w_point_surface > 0.f, a->w_vert_surface > 0.f})))
+    return 1;
   return run_surface_term(m, t, (hipStream_t)stream, a, a->verts, a->points, a->num_points, nullptr, nullptr, 0, nullptr, nullptr, g,
-                          g ? g->point_normals : nullptr);
+                          g ? g->point_normals : nullptr, nullptr, rb);
 }
 
 // ---- Stage.step in one call ------------------------------------------------------------------------------------------
@@ -453,7 +508,13 @@ int smalfit_fit3d_step_gated(smalfit_engine* e, smalfit_mesh_objective* m, smalf
 int smalfit_fit3d_step_partial(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
                                const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
                                const smalfit_chamfer_gate_args* cg) {
-  const char* who = cg ? "smalfit_fit3d_step_partial" : gate ? "smalfit_fit3d_step_gated" : sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
+  return smalfit_fit3d_step_robust(e, m, t, stream, a, sf, gate, cg, nullptr);
+}
+
+int smalfit_fit3d_step_robust(smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
+                              const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
+                              const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb) {
+  const char* who = rb ? "smalfit_fit3d_step_robust" : cg ? "smalfit_fit3d_step_partial" : gate ? "smalfit_fit3d_step_gated" : sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
   if (refused(who, null_argument_refusal(e && m && a))) return 1;
   const ModelDev& md = e->model->dev;
   if (refused(who, fit3d_args_refusal(a, Fit3dFacts{e->maxM, md.V, md.NBall, m->max_meshes, m->max_points, m->t.V,
@@ -466,6 +527,9 @@ int smalfit_fit3d_step_partial(smalfit_engine* e, smalfit_mesh_objective* m, sma
   if (gate && refused(who, surface_gate_args_refusal(gate, sf, SurfaceGateFacts{t != nullptr, true, a->points != nullptr}))) return 1;
   if (cg && refused(who, chamfer_gate_args_refusal(cg, ChamferGateFacts{a->weights[0] > 0.f, true, a->points != nullptr}))) return 1;
   const bool surface = surface_term_on(sf);   // a block with both weights <= 0 is the step without it: nothing of it is launched or written
+  if (rb && refused(who, robust_args_refusal(rb, RobustFacts{true, true, a->weights[0] > 0.f, surface && sf->w_point_surface > 0.f,
+                                                             surface && sf->w_vert_surface > 0.f})))
+    return 1;
   const Fit3dPlan plan = plan_fit3d(a, md.V, surface && sf->w_point_surface > 0.f);
   const int N = a->num_meshes, nb = a->num_betas, S = a->num_points;
   hipStream_t st = (hipStream_t)stream;
@@ -506,11 +570,13 @@ int smalfit_fit3d_step_partial(smalfit_engine* e, smalfit_mesh_objective* m, sma
   // vertex gradient where the LBS adjoint expects it: no layout-conversion launches in between)
   if (run_mesh_objective(m, st, N, nullptr, a->trans, a->deform_verts, pts, S, a->weights, a->verts_out, a->losses,
                          m->dverts, m->dtrans, e->verts, md.Vp, plan.planar_vertex_grad ? e->dext : nullptr, cg, cnormals, cbound,
-                         vnorm)) return 1;
+                         vnorm, rb)) return 1;
   // the surface term at the vertices the objective composed; its gradient joins the step's in all three places it is read from
   if (surface && run_surface_term(m, t, st, sf, a->verts_out ? a->verts_out : m->verts, pts, S, m->dverts,
                                   plan.planar_vertex_grad ? e->dext : nullptr, md.Vp, m->dtrans, a->losses, gate, pnormals,
-                                  cplan.vert_normals && surface_cos_vert ? vnorm : nullptr)) return 1;
+                                  cplan.vert_normals && surface_cos_vert ? vnorm : nullptr, rb)) return 1;
+  // (a step without the term skips both of its directions: their weight sums read 0)
+  if (!surface && rb && rb->surface_weight_sums) HIP_OK(hipMemsetAsync(rb->surface_weight_sums, 0, (size_t)N * 2 * sizeof(float), st));
   if (!plan.any_trained) return 0;
 
   // back through the LBS (forward state is still in the engine)

@@ -545,6 +545,71 @@ inline const char* chamfer_gate_args_refusal(const smalfit_chamfer_gate_args* g,
   return nullptr;
 }
 
+// The robust kernel of both data terms (smalfit_robust_args; robust_gm of mesh3d_math.h).  The ROBUST instantiations of
+// mesh3d_chamfer_kernel<1, ., .> stage the points' weights in a float array beside the records: 4 KB more at kChamChunk, 2 KB at
+// kChamGateChunk, so a block stays under the 32 KB that four blocks a CU allow
+constexpr int kChamRobustLdsBytes = kChamGateLdsBytes + 1024 * 4;
+static_assert(kChamRobustLdsBytes <= 32 * 1024, "four robust chamfer blocks share a CU");
+// a scale is on when sigma > 0 and finite; its float32 square, formed here, once, is what the kernels take
+inline bool robust_scale_on(float sigma) { return sigma > 0.f && std::isfinite(sigma); }
+inline float robust_scale_sq(float sigma) { return sigma * sigma; }
+// what a call computes of the two terms: a scale of a skipped direction is off
+struct RobustFacts {
+  bool chamfer_call, surface_call;   // the entry point evaluates the chamfer term | the surface term at all
+  bool chamfer_on;                   // w_chamfer > 0
+  bool point_dir, vert_dir;          // w_point_surface > 0 | w_vert_surface > 0 (in a step: of a surface block that is on)
+};
+// what a block switches on, in the form the kernels take it (r may be NULL: everything off).  s2 = 0: off.  The chamfer term
+// runs its ROBUST instantiations in BOTH directions when either of its scales is on (the vertices' kernel gathers the weights
+// the points' kernel wrote; a direction whose own scale is off takes w = 1, rho = d^2 there); the surface term's hit kernel of a
+// direction is the ROBUST one exactly when that direction's scale is on.  A ROBUST instantiation writes per-block partial sums
+// of w beside its partial sums of rho; where none ran, the weight sums are read off the kept counts
+struct RobustPlan {
+  bool chamfer;                      // mesh3d_chamfer_kernel<0, ., true> and <1, ., true> run and write weight partials
+  bool surface_point, surface_vert;  // mesh3d_surface_hit_kernel<1, ., true> | <0, ., true> runs and writes weight partials
+  float s2_chamfer_point, s2_chamfer_vert, s2_surface_point, s2_surface_vert;
+  bool any() const { return chamfer || surface_point || surface_vert; }
+};
+inline RobustPlan plan_robust(const smalfit_robust_args* r, const RobustFacts& f) {
+  RobustPlan p{};
+  if (!r) return p;
+  if (f.chamfer_call && f.chamfer_on) {
+    if (robust_scale_on(r->sigma_chamfer_point)) p.s2_chamfer_point = robust_scale_sq(r->sigma_chamfer_point);
+    if (robust_scale_on(r->sigma_chamfer_vert)) p.s2_chamfer_vert = robust_scale_sq(r->sigma_chamfer_vert);
+  }
+  if (f.surface_call && f.point_dir && robust_scale_on(r->sigma_surface_point)) p.s2_surface_point = robust_scale_sq(r->sigma_surface_point);
+  if (f.surface_call && f.vert_dir && robust_scale_on(r->sigma_surface_vert)) p.s2_surface_vert = robust_scale_sq(r->sigma_surface_vert);
+  p.chamfer = p.s2_chamfer_point > 0.f || p.s2_chamfer_vert > 0.f;
+  p.surface_point = p.s2_surface_point > 0.f;
+  p.surface_vert = p.s2_surface_vert > 0.f;
+  return p;
+}
+// -> why the robust entry points refuse the block (the text behind "<entry point>: "), or nullptr; asked after the call's other
+// blocks have been accepted.  The order: the struct's size, the four squares (chamfer point, chamfer vertex, surface point,
+// surface vertex), outputs of a term the call does not evaluate, the four per-query outputs against their scales
+inline const char* robust_args_refusal(const smalfit_robust_args* r, const RobustFacts& f) {
+  if (r->struct_size != (unsigned)sizeof(smalfit_robust_args))
+    return "smalfit_robust_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (robust_scale_on(r->sigma_chamfer_point) && !std::isnormal(robust_scale_sq(r->sigma_chamfer_point)))
+    return "the float32 square of sigma_chamfer_point is not a normal number";
+  if (robust_scale_on(r->sigma_chamfer_vert) && !std::isnormal(robust_scale_sq(r->sigma_chamfer_vert)))
+    return "the float32 square of sigma_chamfer_vert is not a normal number";
+  if (robust_scale_on(r->sigma_surface_point) && !std::isnormal(robust_scale_sq(r->sigma_surface_point)))
+    return "the float32 square of sigma_surface_point is not a normal number";
+  if (robust_scale_on(r->sigma_surface_vert) && !std::isnormal(robust_scale_sq(r->sigma_surface_vert)))
+    return "the float32 square of sigma_surface_vert is not a normal number";
+  if (!f.chamfer_call && (r->chamfer_weight_sums || r->chamfer_point_weights || r->chamfer_vert_weights))
+    return "chamfer weight outputs given to a call that does not evaluate the chamfer term";
+  if (!f.surface_call && (r->surface_weight_sums || r->surface_point_weights || r->surface_vert_weights))
+    return "surface weight outputs given to a call that does not evaluate the surface term";
+  const RobustPlan p = plan_robust(r, f);
+  if (r->chamfer_point_weights && !(p.s2_chamfer_point > 0.f)) return "chamfer_point_weights given while sigma_chamfer_point is off";
+  if (r->chamfer_vert_weights && !(p.s2_chamfer_vert > 0.f)) return "chamfer_vert_weights given while sigma_chamfer_vert is off";
+  if (r->surface_point_weights && !(p.s2_surface_point > 0.f)) return "surface_point_weights given while sigma_surface_point is off";
+  if (r->surface_vert_weights && !(p.s2_surface_vert > 0.f)) return "surface_vert_weights given while sigma_surface_vert is off";
+  return nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------
 // smalfit_fit3d_step: which blocks are refused, and what a step launches
 // ------------------------------------------------------------------------------------------------

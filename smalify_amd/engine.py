@@ -619,14 +619,18 @@ class MeshObjective:
             pass
 
     def eval(self, lbs_verts, trans, deform_verts, points, weights, out=None, chamfer_gates=None, point_normals=None,
-             point_boundary=None, targets=None):
+             point_boundary=None, targets=None, robust=None):
         """-> dict(losses (5,), verts (N,V,3), dverts (N,V,3), dtrans (N,3)); `weights` = (w_chamfer, w_edge, w_normal,
         w_laplacian) host floats; `out` may carry preallocated tensors under the same keys.
         chamfer_gates: None, or a dict of max_dist_point, max_dist_vert, min_cos_point, min_cos_vert, reject_boundary
         (chamfer_gates(); smalfit_mesh_objective_eval_gated, include/smalfit.h): which chamfer matches count on a partial scan.  A
         min_cos gate needs point_normals (N,S,3), reject_boundary point_boundary (N,S) uint8 (MeshTargets.sample_attrs).  Adds
         kept (N,2) int32 = kept points | kept vertices and, while w_chamfer > 0 and some gate is on, point_kept (N,S) / vert_kept (N,V) uint8 and
-        point_nn (N,S) / vert_nn (N,V) int32 (-1: dropped point / no compatible point found)."""
+        point_nn (N,S) / vert_nn (N,V) int32 (-1: dropped point / no compatible point found).
+        robust: None, or a dict of sigma_chamfer_point, sigma_chamfer_vert (robust(); smalfit_mesh_objective_eval_robust): the
+        Geman-McClure kernel on the kept matches; the surface scales of the dict are not read here.  Adds chamfer_weight_sums
+        (N,2) = sum of w over the kept points | kept vertices and, for a direction whose scale is on, point_weights (N,S) /
+        vert_weights (N,V); losses[0] and losses[4] then carry the robust values.  With chamfer_gates None no gate block is passed."""
         N, V = int(lbs_verts.shape[0]), self.num_verts
         if tuple(lbs_verts.shape) != (N, V, 3) or tuple(trans.shape) != (N, 3):
             raise SmalfitError("lbs_verts must be (N,%d,3) and trans (N,3)" % V)
@@ -643,13 +647,35 @@ class MeshObjective:
             if k not in o or tuple(o[k].shape) != shape:
                 o[k] = torch.empty(shape, device=dev)
         w = _host(weights, np.float32).reshape(4)
-        if chamfer_gates is None:
+        if chamfer_gates is None and robust is None:
             check(self.lib.smalfit_mesh_objective_eval(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans),
                                                        _ptr(deform_verts), _ptr(points), S, w.ctypes.data, _ptr(o["verts"]),
                                                        _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"])),
                   "smalfit_mesh_objective_eval")
             return o
-        fn = _lib.resolve(self.lib, "smalfit_mesh_objective_eval_gated")
+        rb = None
+        if robust is not None:
+            rd = _robust_of(robust)
+            rb = robust_block(rd)
+            on = float(w[0]) > 0 and S > 0
+            outs = (("chamfer_weight_sums", "chamfer_weight_sums", (N, 2)),)
+            if on and _scale_on(rd["sigma_chamfer_point"]):
+                outs += (("point_weights", "chamfer_point_weights", (N, S)),)
+            if on and _scale_on(rd["sigma_chamfer_vert"]):
+                outs += (("vert_weights", "chamfer_vert_weights", (N, V)),)
+            for k, field, shape in outs:
+                if k not in o or tuple(o[k].shape) != shape or o[k].dtype != torch.float32:
+                    o[k] = torch.zeros(shape, device=dev)
+                setattr(rb, field, _ptr(o[k]))
+        if chamfer_gates is None:
+            fn = _lib.resolve(self.lib, "smalfit_mesh_objective_eval_robust")
+            targets = getattr(targets, "_dev", targets)
+            check(fn(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans), _ptr(deform_verts), _ptr(points), S, w.ctypes.data,
+                     _ptr(o["verts"]), _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"]),
+                     targets.handle if targets is not None else None, None, C.byref(rb)), "smalfit_mesh_objective_eval_robust")
+            return o
+        name = "smalfit_mesh_objective_eval_robust" if rb is not None else "smalfit_mesh_objective_eval_gated"
+        fn = _lib.resolve(self.lib, name)
         chamfer_gates_dict = _chamfer_gates_of(chamfer_gates)
         g = chamfer_gate_block(chamfer_gates_dict)
         if point_normals is not None:
@@ -667,9 +693,10 @@ class MeshObjective:
                 o[k] = torch.zeros(shape, dtype=dt, device=dev)
             setattr(g, k, C.c_void_p(o[k].data_ptr()))
         targets = getattr(targets, "_dev", targets)
-        check(fn(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans), _ptr(deform_verts), _ptr(points), S, w.ctypes.data,
-                 _ptr(o["verts"]), _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"]),
-                 targets.handle if targets is not None else None, C.byref(g)), "smalfit_mesh_objective_eval_gated")
+        args = (self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans), _ptr(deform_verts), _ptr(points), S, w.ctypes.data,
+                _ptr(o["verts"]), _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"]),
+                targets.handle if targets is not None else None, C.byref(g))
+        check(fn(*args, C.byref(rb)) if rb is not None else fn(*args), name)
         return o
 
     def score(self, verts, targets, points=None, thresholds=()):
@@ -717,7 +744,7 @@ class MeshObjective:
         return out
 
     def surface(self, verts, targets, points, w_point_surface, w_vert_surface, correspondences=False, gates=None,
-                point_normals=None):
+                point_normals=None, robust=None):
         """The point-to-surface term both ways and its gradient (smalfit_mesh_surface_eval; the definition is this project's,
         include/smalfit.h): L_ps = mean over the points of d^2(point, fitted surface), L_vs = mean over the fitted vertices of
         d^2(vertex, target surface), term = w_point_surface L_ps + w_vert_surface L_vs; a weight <= 0 skips its direction.
@@ -730,8 +757,14 @@ class MeshObjective:
         gates: None, or a dict of max_dist_point, max_dist_vert, min_cos_point, min_cos_vert, reject_boundary (surface_gates();
         smalfit_mesh_surface_eval_gated): which matches count on a partial scan.  min_cos_point needs point_normals (N,S,3), the
         unit normals of the points (MeshTargets.sample_normals).  Adds kept (N,2) int32 = kept points | kept vertices, and for
-        every direction that ran point_kept (N,S) / vert_kept (N,V) uint8; vert_normals (N,V,3) when min_cos_vert is on."""
-        fn = _lib.resolve(self.lib, "smalfit_mesh_surface_eval_gated" if gates is not None else "smalfit_mesh_surface_eval")
+        every direction that ran point_kept (N,S) / vert_kept (N,V) uint8; vert_normals (N,V,3) when min_cos_vert is on.
+        robust: None, or a dict of sigma_surface_point, sigma_surface_vert (robust(); smalfit_mesh_surface_eval_robust): the
+        Geman-McClure kernel on the kept matches; the chamfer scales of the dict are not read here.  Adds surface_weight_sums
+        (N,2) and, for a direction that ran with its scale on, point_weights (N,S) / vert_weights (N,V); losses, rows and the
+        gradient then carry the robust values, the residuals stay geometric."""
+        name = ("smalfit_mesh_surface_eval_robust" if robust is not None else
+                "smalfit_mesh_surface_eval_gated" if gates is not None else "smalfit_mesh_surface_eval")
+        fn = _lib.resolve(self.lib, name)
         targets = getattr(targets, "_dev", targets)
         if targets is not None and not isinstance(targets, MeshTargets):
             raise SmalfitError("targets must be the MeshTargets the meshes are fitted to")
@@ -766,7 +799,22 @@ class MeshObjective:
                 a.vert_face, a.vert_bary = C.c_void_p(out["vert_face"].data_ptr()), _ptr(out["vert_bary"])
                 a.vert_residual = _ptr(out["vert_residual"])
         th = targets.handle if targets is not None else None
+        rb = None
+        if robust is not None:
+            rd = _robust_of(robust)
+            rb = robust_block(rd)
+            out["surface_weight_sums"] = torch.zeros(N, 2, device=dev)
+            rb.surface_weight_sums = _ptr(out["surface_weight_sums"])
+            if w_point_surface > 0 and points is not None and _scale_on(rd["sigma_surface_point"]):
+                out["point_weights"] = torch.zeros(N, S, device=dev)
+                rb.surface_point_weights = _ptr(out["point_weights"])
+            if w_vert_surface > 0 and _scale_on(rd["sigma_surface_vert"]):
+                out["vert_weights"] = torch.zeros(N, V, device=dev)
+                rb.surface_vert_weights = _ptr(out["vert_weights"])
         if gates is None:
+            if rb is not None:
+                check(fn(self.handle, th, _stream(), C.byref(a), None, C.byref(rb)), name)
+                return out
             check(fn(self.handle, th, _stream(), C.byref(a)), "smalfit_mesh_surface_eval")
             return out
         g = surface_gate_block(gates)
@@ -785,6 +833,9 @@ class MeshObjective:
             if g.min_cos_vert > -1.0:
                 out["vert_normals"] = torch.empty(N, V, 3, device=dev)
                 g.vert_normals = _ptr(out["vert_normals"])
+        if rb is not None:
+            check(fn(self.handle, th, _stream(), C.byref(a), C.byref(g), C.byref(rb)), name)
+            return out
         check(fn(self.handle, th, _stream(), C.byref(a), C.byref(g)), "smalfit_mesh_surface_eval_gated")
         return out
 
@@ -843,6 +894,41 @@ def chamfer_gate_block(gates):
     g.min_cos_point, g.min_cos_vert = gd["min_cos_point"], gd["min_cos_vert"]
     g.reject_boundary = int(gd["reject_boundary"])
     return g
+
+
+ROBUST_KEYS = ("sigma_chamfer_point", "sigma_chamfer_vert", "sigma_surface_point", "sigma_surface_vert")
+
+
+def robust(scales=None):
+    """the four scales of the Geman-McClure kernel (smalfit_robust_args) with every one off, overridden by `scales`; an unknown
+    key raises"""
+    out = dict.fromkeys(ROBUST_KEYS, 0.0)
+    for k, v in (scales or {}).items():
+        if k not in out:
+            raise KeyError("unknown robust key %r (have %s)" % (k, sorted(out)))
+        out[k] = float(v)
+    return out
+
+
+_robust_of = robust      # (for callers whose own keyword is named robust)
+
+
+def _scale_on(sigma):
+    return bool(sigma > 0 and np.isfinite(sigma))
+
+
+def robust_on(scales):
+    """some scale of the dict (as robust returns it) is switched on"""
+    return any(_scale_on(scales[k]) for k in ROBUST_KEYS)
+
+
+def robust_block(scales):
+    """a smalfit_robust_args with the scales of `scales` (a dict as robust takes it); the pointers are the caller's"""
+    rd = robust(scales)
+    r = _lib.RobustArgs()
+    for k in ROBUST_KEYS:
+        setattr(r, k, rd[k])
+    return r
 
 
 class MeshTargets:

@@ -131,7 +131,7 @@ class Stage:
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes, mesh_names=[],
                  name="optimise", loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None,
-                 device="cuda", seed=0, iteration_offset=0, surface_gates=None, chamfer_gates=None):
+                 device="cuda", seed=0, iteration_offset=0, surface_gates=None, chamfer_gates=None, robust=None):
         self.n_it = int(nits)
         self.name = name
         self.out_dir = out_dir
@@ -154,6 +154,9 @@ class Stage:
         self.surface_gates = eng.surface_gates(surface_gates)
         # ... and the same three kinds of gate on the chamfer term's two scans (constructor or a `chamfer_gates` block of the YAML)
         self.chamfer_gates = eng.chamfer_gates(chamfer_gates)
+        # the Geman-McClure kernel on the matches the gates keep (include/smalfit.h): four scales, all off unless given, here or as
+        # a `robust` block of the stage's YAML; with or without the gates
+        self.robust = eng.robust(robust)
         if custom_lrs is not None:
             for attr in custom_lrs:
                 assert hasattr(smal_3d_fitter, attr), f"attr '{attr}' not in SMAL."
@@ -191,6 +194,8 @@ class Stage:
         self._cgate_args = None        # smalfit_chamfer_gate_args of step(), built on the first step while a chamfer gate is on
         self._chamfer_kept = None
         self._point_boundary = None
+        self._robust_args = None       # smalfit_robust_args of step(), built on the first step while a scale applies
+        self._robust_weights = None
         self.consider_loss = lambda loss_name: self.loss_weights[f"w_{loss_name}"] > 0
 
     # ---- evaluation ----------------------------------------------------------------------------------------------
@@ -244,6 +249,30 @@ class Stage:
         evaluation or step; None while the term or its gates are off"""
         return self._chamfer_kept
 
+    @property
+    def robust_on(self):
+        """some scale of the robust kernel is switched on"""
+        return eng.robust_on(self.robust)
+
+    def _robust_chamfer(self):
+        r = self.robust
+        return self.loss_weights["w_chamfer"] > 0 and (eng._scale_on(r["sigma_chamfer_point"]) or eng._scale_on(r["sigma_chamfer_vert"]))
+
+    def _robust_surface(self):
+        r, sw = self.robust, self.surface_weights
+        return ((sw["w_point_surface"] > 0 and eng._scale_on(r["sigma_surface_point"])) or
+                (sw["w_vert_surface"] > 0 and eng._scale_on(r["sigma_surface_vert"])))
+
+    def _robust_applies(self):
+        """a scale is on for a term that is on: otherwise evaluations and steps are the calls of before"""
+        return self._robust_chamfer() or self._robust_surface()
+
+    @property
+    def last_robust_weights(self):
+        """dict(chamfer=, surface=) of device tensors (N,2): the sums of w over the kept points | kept vertices of every mesh in
+        the most recent robust evaluation or step (a term without a scale on: None); None while no scale applies"""
+        return self._robust_weights
+
     def _chamfer_gated(self):
         return self.chamfer_gates_on and self.loss_weights["w_chamfer"] > 0
 
@@ -281,17 +310,23 @@ class Stage:
         o = self._objective.eval(lbs, fit.trans.detach().contiguous(), fit.deform_verts.detach().contiguous(), points,
                                  self._weights(), out=self._buffers, chamfer_gates=cg if cgated else None,
                                  point_normals=normals if chamfer_normals else None, point_boundary=boundary if cgated else None,
-                                 targets=self.target_meshes if cgated else None)
+                                 targets=self.target_meshes if cgated else None,
+                                 robust=self.robust if self._robust_chamfer() else None)
         self._buffers = o
         self._chamfer_kept = o["kept"] if cgated else None
+        self._robust_weights = (dict(chamfer=o["chamfer_weight_sums"] if self._robust_chamfer() else None, surface=None)
+                                if self._robust_applies() else None)
         total = o["losses"][4]
         if self.surface_on:
             # the stand-alone call's gradient joins the objective's before the LBS adjoint
             wp, wv = (self.surface_weights[k] for k in _SURFACE_ORDER)
             sf = self._objective.surface(o["verts"], self.target_meshes, points if wp > 0 else None, wp, wv,
                                          gates=self.surface_gates if gated else None,
-                                         point_normals=normals if wp > 0 and surface_normals else None)
+                                         point_normals=normals if wp > 0 and surface_normals else None,
+                                         robust=self.robust if self._robust_surface() else None)
             self._surface_kept = sf.get("kept")
+            if self._robust_surface():
+                self._robust_weights["surface"] = sf["surface_weight_sums"]
             o["dverts"] += sf["dverts"]
             o["dtrans"] += sf["dtrans"]
             self._surface_losses = sf["losses"]
@@ -318,6 +353,21 @@ class Stage:
         self._t += 1
         a.adam_t = self._t
         dev_targets = getattr(self.target_meshes, "_dev", self.target_meshes)
+        if self._robust_applies():
+            # (every block that is on rides along, as in the calls below; the robust block needs none of them)
+            sf = gate = cgate = None
+            if self.surface_on:
+                sf = self._surface_block()
+                sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
+                gate = self._gate_block() if self.gates_on else None
+            if self._chamfer_gated():
+                cgate = self._chamfer_gate_block()
+            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_robust")
+            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a),
+                         C.byref(sf) if sf is not None else None, C.byref(gate) if gate is not None else None,
+                         C.byref(cgate) if cgate is not None else None, C.byref(self._robust_block())), "smalfit_fit3d_step_robust")
+            self._last_points = self._points
+            return self._step_total[0] if sf is not None else self._buffers["losses"][4]
         if self._chamfer_gated():
             # (the surface block and its gate block ride along when they are on; a chamfer gate block needs neither)
             sf = gate = None
@@ -438,6 +488,18 @@ class Stage:
             self._cgate_args.kept = self._step_chamfer_kept.data_ptr()
         self._chamfer_kept = self._step_chamfer_kept
         return self._cgate_args
+
+    def _robust_block(self):
+        """the smalfit_robust_args of step(): the stage's scales, the weight sums of both terms"""
+        if self._robust_args is None:
+            self._robust_args = eng.robust_block(self.robust)
+            N = self.smal_3d_fitter.batch_size
+            self._step_robust = dict(chamfer=torch.zeros(N, 2, device=self.device), surface=torch.zeros(N, 2, device=self.device))
+            self._robust_args.chamfer_weight_sums = self._step_robust["chamfer"].data_ptr()
+            self._robust_args.surface_weight_sums = self._step_robust["surface"].data_ptr()
+        self._robust_weights = dict(chamfer=self._step_robust["chamfer"] if self._robust_chamfer() else None,
+                                    surface=self._step_robust["surface"] if self._robust_surface() else None)
+        return self._robust_args
 
     def run(self, plot=False, progress=True, report_every=50):
         """Run the entire Stage (trainer.py:257-270).  The description line is refreshed every `report_every`

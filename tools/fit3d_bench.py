@@ -3,13 +3,14 @@
 batch of N target meshes, "default" scheme (trainer.py:115), all four loss terms, 3000 target points per mesh, and the
 share of each of the five C-ABI calls of a step (torch events on the launch stream, separate short run).
 
-    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface [--gates]] [--chamfer-gates]
+    python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface [--gates]] [--chamfer-gates] [--robust]
 
 Prints one JSON line per batch size.  --surface adds the point-to-surface term both ways (w_point_surface = w_vert_surface = 1:
 every step is smalfit_fit3d_step_surface) and two fields to the line; without it the run and the line are those of before.
 --gates (with --surface) switches every gate of that term on (GATES below: every step is smalfit_fit3d_step_gated) and adds the
 kept counts of the last step.  --chamfer-gates, alone or with the others, switches every gate of the chamfer term on (every step is
-smalfit_fit3d_step_partial) and adds its kept counts.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
+smalfit_fit3d_step_partial) and adds its kept counts.  --robust, alone or with the others, switches the Geman-McClure kernel on for
+every data term that runs (ROBUST below: every step is smalfit_fit3d_step_robust) and adds the weight sums of the last step.  Synthetic SMAL-topology model and targets (posed copies of it), as bench.py."""
 import argparse
 import json
 import os
@@ -41,6 +42,10 @@ def targets_for(md, N, seed):
 GATES = dict(max_dist_point=0.5, max_dist_vert=0.5, min_cos_point=0.0, min_cos_vert=0.0, reject_boundary=True)
 
 
+# every scale on, wide against a complete target (the targets fill [-1, 1]): the cost of the robust kernels, not of what they let go
+ROBUST = dict(sigma_chamfer_point=0.5, sigma_chamfer_vert=0.5, sigma_surface_point=0.5, sigma_surface_vert=0.5)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", type=int, nargs="+", default=[1, 8, 32])
@@ -48,6 +53,7 @@ def main():
     ap.add_argument("--surface", action="store_true", help="add the point-to-surface term both ways to every step")
     ap.add_argument("--gates", action="store_true", help="with --surface: gate the term (truncation, compatibility, boundary)")
     ap.add_argument("--chamfer-gates", action="store_true", help="gate the chamfer term (truncation, compatibility, boundary)")
+    ap.add_argument("--robust", action="store_true", help="the Geman-McClure kernel on every data term that runs")
     args = ap.parse_args()
     if args.gates and not args.surface:
         ap.error("--gates needs --surface")
@@ -63,7 +69,8 @@ def main():
         targets = TargetMeshes(tv, [np.asarray(md.faces)] * N)
         weights = {"w_point_surface": 1.0, "w_vert_surface": 1.0} if args.surface else None
         stage = Stage(args.iters, "default", fit, targets, lr=0.01, custom_lrs={"joint_rot": 0.005}, loss_weights=weights,
-                      surface_gates=GATES if args.gates else None, chamfer_gates=GATES if args.chamfer_gates else None)
+                      surface_gates=GATES if args.gates else None, chamfer_gates=GATES if args.chamfer_gates else None,
+                      **(dict(robust=ROBUST) if args.robust else {}))
         for i in range(10):
             stage.step(i)
         torch.cuda.synchronize()
@@ -107,6 +114,9 @@ def main():
         if args.chamfer_gates:
             line["chamfer_gates"] = GATES
             line["final_chamfer_kept"] = stage.last_chamfer_kept.cpu().tolist()
+        if args.robust:
+            line["robust"] = ROBUST
+            line["final_robust_weights"] = {k: (None if v is None else v.cpu().tolist()) for k, v in stage.last_robust_weights.items()}
         print(json.dumps(line))
         del stage, targets, fit
 
