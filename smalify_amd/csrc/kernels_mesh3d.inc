@@ -96,17 +96,16 @@ __global__ __launch_bounds__(256) void mesh3d_compose_kernel(Mesh3dArgs a) {
 }
 
 // ROLE 0: queries = target points, scanned set = vertices.  ROLE 1: queries = vertices, scanned set = target points.
-// <ROLE, false> is the ungated term's kernel: ScanPoint records, kChamChunk at a time.
-// GATED: the 32-byte GatedScanPoint, kChamGateChunk at a time -- the same 16 KB, so a block's LDS (21 KB with the waves' partial
-// results) and its four blocks a CU do not change -- and the nearest COMPATIBLE element (the query's unit normal in three registers, c a scalar; with c = -inf no normal is read
-// and every record is compatible); the waves' minima meet as before, then wave 0 decides once per query: found, truncation,
-// (ROLE 1) the boundary rule on the winner.  A dropped point writes nn_idx = -1, so no vertex gathers it; a dropped query adds
-// nothing to the sum of d^2 or to its own gradient term; the block's kept count goes beside its sum
-// ROBUST (either way gated): the scan and the match are those of <ROLE, GATED, false>; wave 0 then applies robust_gm once per
-// query -- s2 = 0 stands for this direction's scale being off: w = 1, rho = d^2 -- sums rho in place of d^2 and w beside it.
-// ROLE 0 leaves w_s per point (0 for a dropped one); ROLE 1 stages those in a float array beside the records (4 KB at
-// kChamChunk, 2 KB at kChamGateChunk) and gathers sum w_s (y_v - x_s) with the same branch-free mask, and multiplies its own
-// match by w(best): no divide enters the scan
+// One staging loop, one scan call, one tail; the flags choose the record, the decision and the outputs:
+//   record    <., false, .> stages ScanPoint, kChamChunk at a time; GATED the 32-byte GatedScanPoint, kChamGateChunk at a time -- the
+//             same 16 KB, so a block's LDS and its four blocks a CU do not change -- and scans for the nearest COMPATIBLE element
+//             (the query's unit normal in three registers, c a scalar; c = -inf: no normal is read, every record is compatible).
+//             ROBUST ROLE 1 stages the points' weights w_s in a float array beside the records and gathers sum w_s (y_v - x_s)
+//             with the same branch-free mask: no divide enters the scan
+//   decision  the waves' minima meet, then wave 0 decides once per query: chamfer_match<GATED, ROBUST> (mesh3d_math.h)
+//   outputs   a dropped point writes nn_idx = -1, so no vertex gathers it; a dropped query adds nothing to the block's sum or to
+//             its own gradient term (chamfer_vertex_grad); GATED puts the block's kept count beside its sum, ROBUST the block's
+//             sum of w, and ROLE 0 leaves w_s per point (0 for a dropped one)
 template <int ROLE, bool GATED, bool ROBUST = false>
 __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
   __shared__ float sd[4][kChamQueries];
@@ -141,21 +140,24 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
   float best = INFINITY;
   int bidx = 0x7fffffff;   // GATED: the winner's tag (gated_tag: ascending with the index)
   float g[3] = {0.f, 0.f, 0.f};
+  // one staging loop for both record types: the chunk is sized so that either fills the same 16 KB
+  using Record = typename std::conditional<GATED, GatedScanPoint, ScanPoint>::type;
+  constexpr int kChunk = GATED ? kChamGateChunk : kChamChunk;
   constexpr bool kWeighted = ROBUST && ROLE == 1;
-  __shared__ float sw[kWeighted ? (GATED ? kChamGateChunk : kChamChunk) : 1];   // (not used, and not allocated, unless kWeighted)
+  __shared__ float sw[kWeighted ? kChunk : 1];   // (not used, and not allocated, unless kWeighted)
+  __shared__ Record rec[kChunk];
   const float* wsrc = a.wts + (size_t)n * a.S;
-  if constexpr (GATED) {
-    __shared__ GatedScanPoint gp[kChamGateChunk];
-    for (int base = 0; base < no; base += kChamGateChunk) {
-      const int cnt = min(kChamGateChunk, no - base);
-      __syncthreads();
-      for (int i = threadIdx.x; i < cnt; i += 256) {
-        const float* src = o + 3 * (size_t)(base + i);
-        GatedScanPoint s;
-        s.x = src[0];
-        s.y = src[1];
-        s.z = src[2];
-        s.owner = ROLE == 1 ? own[base + i] : 0;
+  for (int base = 0; base < no; base += kChunk) {
+    const int cnt = min(kChunk, no - base);
+    __syncthreads();
+    for (int i = threadIdx.x; i < cnt; i += 256) {
+      const float* src = o + 3 * (size_t)(base + i);
+      Record s;
+      s.x = src[0];
+      s.y = src[1];
+      s.z = src[2];
+      s.owner = ROLE == 1 ? own[base + i] : 0;
+      if constexpr (GATED) {
         s.nx = s.ny = s.nz = 0.f;
         if (use_normals) {
           const float* sn = on + 3 * (size_t)(base + i);
@@ -164,38 +166,14 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
           s.nz = sn[2];
         }
         s.tag = gated_tag(base + i, ob != nullptr ? ob[base + i] : 0);
-        gp[i] = s;
-        if constexpr (kWeighted) sw[i] = wsrc[base + i];
       }
-      __syncthreads();
-      const int per = (cnt + 3) >> 2;
-      const int b = min(w * per, cnt), e = min(b + per, cnt);
-      // (wave-uniform as below: two broadcast 16-byte LDS reads per record)
-      if constexpr (kWeighted) nearest_scan_gated<true, true>(qx, qy, qz, ux, uy, uz, c, gp, b, e, best, bidx, qi, g, sw);
-      else nearest_scan_gated<ROLE == 1>(qx, qy, qz, ux, uy, uz, c, gp, b, e, best, bidx, qi, g);
+      rec[i] = s;
+      if constexpr (kWeighted) sw[i] = wsrc[base + i];
     }
-  } else {
-    __shared__ ScanPoint sp[kChamChunk];
-    for (int base = 0; base < no; base += kChamChunk) {
-      const int cnt = min(kChamChunk, no - base);
-      __syncthreads();
-      for (int i = threadIdx.x; i < cnt; i += 256) {
-        const float* src = o + 3 * (size_t)(base + i);
-        ScanPoint s;
-        s.x = src[0];
-        s.y = src[1];
-        s.z = src[2];
-        s.owner = ROLE == 1 ? own[base + i] : 0;
-        sp[i] = s;
-        if constexpr (kWeighted) sw[i] = wsrc[base + i];
-      }
-      __syncthreads();
-      const int per = (cnt + 3) >> 2;
-      const int b = min(w * per, cnt), e = min(b + per, cnt);
-      // b, e are wave-uniform: every lane reads the same 16-byte LDS record (broadcast, conflict free)
-      if constexpr (kWeighted) nearest_scan<true, true>(qx, qy, qz, sp, b, e, base, best, bidx, qi, g, sw);
-      else nearest_scan<ROLE == 1>(qx, qy, qz, sp, b, e, base, best, bidx, qi, g);
-    }
+    __syncthreads();
+    // the span is wave-uniform: every lane reads the same 16-byte LDS rows of a record (broadcast, conflict free)
+    const Span sp = quarter_span(w, cnt);
+    scan_records<ROLE == 1, kWeighted>(qx, qy, qz, ux, uy, uz, c, rec, sp.b, sp.e, base, best, bidx, qi, g, kWeighted ? sw : nullptr);
   }
   sd[w][lane] = best;
   si[w][lane] = bidx;
@@ -215,99 +193,50 @@ __global__ __launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a) {
       g[2] += sg[s][lane][2];
     }
   }
-  if constexpr (ROBUST) {
-    // the match of <ROLE, GATED, false>, then the kernel on it
-    bool kept = active;
-    int index = bidx;
-    if constexpr (GATED) {
-      const GatedMatch mt = gated_match(best, bidx, ROLE == 0 ? a.tau2_p : a.tau2_v, ob != nullptr ? 1 : 0);
-      kept = active && mt.kept;
-      index = mt.index;
-    }
-    const float s2 = ROLE == 0 ? a.s2_p : a.s2_v;
-    float rho = best, wq = 1.0f;
-    if (s2 > 0.f) robust_gm(best, s2, rho, wq);
-    rho = kept ? rho : 0.f;
-    wq = kept ? wq : 0.f;
-    if (active) {
-      const size_t oq = (size_t)n * nq + qi;
-      if (ROLE == 0) {
-        const int nn = GATED ? (kept ? index : -1) : index;
-        a.nn_idx[oq] = nn;
-        a.wts[oq] = wq;
-        if (a.point_w != nullptr) a.point_w[oq] = wq;
-        if (GATED && a.point_nn != nullptr) a.point_nn[oq] = nn;
-        if (GATED && a.point_kept != nullptr) a.point_kept[oq] = kept ? 1 : 0;
-      } else {
-        if (a.vert_w != nullptr) a.vert_w[oq] = wq;
-        if (GATED && a.vert_nn != nullptr) a.vert_nn[oq] = index;
-        if (GATED && a.vert_kept != nullptr) a.vert_kept[oq] = kept ? 1 : 0;
-        const float cy = (a.w_chamfer * 2.0f / ((float)a.V * (float)a.N)) * wq;   // (wq = 0: a dropped vertex keeps only what it gathered)
-        const float cx = a.w_chamfer * 2.0f / ((float)a.S * (float)a.N);
-        const float* xn = o + 3 * (size_t)(kept && index >= 0 && index < no ? index : 0);   // no finite distance (NaN input): stay in bounds
-        float* out = a.gcham + oq * 3;
-        out[0] = cy * (qx - xn[0]) + cx * g[0];
-        out[1] = cy * (qy - xn[1]) + cx * g[1];
-        out[2] = cy * (qz - xn[2]) + cx * g[2];
-      }
-    }
-    const float tot = wave_sum(rho);
-    const float wtot = wave_sum(wq);
-    const int cnt = __popcll(__ballot(kept));
-    if (lane == 0) {
-      const size_t slot = (size_t)n * gridDim.x + blockIdx.x;
-      (ROLE == 0 ? a.part_cx : a.part_cy)[slot] = tot;
-      (ROLE == 0 ? a.part_wx : a.part_wy)[slot] = wtot;
-      if (GATED) (ROLE == 0 ? a.part_kx : a.part_ky)[slot] = cnt;
-    }
-    return;
-  }
-  if constexpr (GATED) {
-    const GatedMatch mt = gated_match(best, bidx, ROLE == 0 ? a.tau2_p : a.tau2_v, ob != nullptr ? 1 : 0);
-    const bool kept = active && mt.kept;
-    if (active) {
-      const size_t oq = (size_t)n * nq + qi;
-      if (ROLE == 0) {
-        const int nn = kept ? mt.index : -1;
-        a.nn_idx[oq] = nn;
-        if (a.point_nn != nullptr) a.point_nn[oq] = nn;
-        if (a.point_kept != nullptr) a.point_kept[oq] = kept ? 1 : 0;
-      } else {
-        if (a.vert_nn != nullptr) a.vert_nn[oq] = mt.index;
-        if (a.vert_kept != nullptr) a.vert_kept[oq] = kept ? 1 : 0;
-        const float cy = kept ? a.w_chamfer * 2.0f / ((float)a.V * (float)a.N) : 0.f;   // a dropped vertex keeps only what it gathered
-        const float cx = a.w_chamfer * 2.0f / ((float)a.S * (float)a.N);
-        const float* xn = o + 3 * (size_t)(kept ? mt.index : 0);
-        float* out = a.gcham + oq * 3;
-        out[0] = cy * (qx - xn[0]) + cx * g[0];
-        out[1] = cy * (qy - xn[1]) + cx * g[1];
-        out[2] = cy * (qz - xn[2]) + cx * g[2];
-      }
-    }
-    const float tot = wave_sum(kept ? best : 0.f);
-    const int cnt = __popcll(__ballot(kept));   // (an integer count: no order to fix)
-    if (lane == 0) {
-      (ROLE == 0 ? a.part_cx : a.part_cy)[(size_t)n * gridDim.x + blockIdx.x] = tot;
-      (ROLE == 0 ? a.part_kx : a.part_ky)[(size_t)n * gridDim.x + blockIdx.x] = cnt;
-    }
-    return;
-  }
+  // one tail: the decision of this instantiation, then the outputs it has
+  const ChamferMatch m = chamfer_match<GATED, ROBUST>(best, bidx, ROLE == 0 ? a.tau2_p : a.tau2_v, ob != nullptr ? 1 : 0,
+                                                      ROLE == 0 ? a.s2_p : a.s2_v, active);
   if (active) {
+    const size_t oq = (size_t)n * nq + qi;
     if (ROLE == 0) {
-      a.nn_idx[(size_t)n * a.S + qi] = bidx;
+      const int nn = GATED && !m.kept ? -1 : m.index;   // a dropped point is gathered by no vertex
+      a.nn_idx[oq] = nn;
+      if constexpr (ROBUST) {
+        a.wts[oq] = m.w;
+        if (a.point_w != nullptr) a.point_w[oq] = m.w;
+      }
+      if constexpr (GATED) {
+        if (a.point_nn != nullptr) a.point_nn[oq] = nn;
+        if (a.point_kept != nullptr) a.point_kept[oq] = m.kept ? 1 : 0;
+      }
     } else {
-      // d/dy_j of [ (1/(V N)) |y_j - x_nn(j)|^2 + (1/(S N)) sum_{i: nn(i) = j} |x_i - y_j|^2 ]
-      const float cy = a.w_chamfer * 2.0f / ((float)a.V * (float)a.N);
+      if constexpr (ROBUST) {
+        if (a.vert_w != nullptr) a.vert_w[oq] = m.w;
+      }
+      if constexpr (GATED) {
+        if (a.vert_nn != nullptr) a.vert_nn[oq] = m.index;
+        if (a.vert_kept != nullptr) a.vert_kept[oq] = m.kept ? 1 : 0;
+      }
+      // d/dy_j of [ (1/(V N)) rho(|y_j - x_nn(j)|^2) + (1/(S N)) sum_{i: nn(i) = j} rho(|x_i - y_j|^2) ]; a dropped vertex keeps only
+      // what it gathered
+      float cy = a.w_chamfer * 2.0f / ((float)a.V * (float)a.N);
+      if constexpr (ROBUST) cy = cy * m.w;
+      else if constexpr (GATED) cy = m.kept ? cy : 0.f;
       const float cx = a.w_chamfer * 2.0f / ((float)a.S * (float)a.N);
-      const float* xn = o + 3 * (size_t)(bidx < no ? bidx : 0);   // no finite distance (NaN input): stay in bounds
-      float* out = a.gcham + ((size_t)n * a.V + qi) * 3;
-      out[0] = cy * (qx - xn[0]) + cx * g[0];
-      out[1] = cy * (qy - xn[1]) + cx * g[1];
-      out[2] = cy * (qz - xn[2]) + cx * g[2];
+      const float y[3] = {qx, qy, qz};
+      chamfer_vertex_grad(cy, cx, y, o, no, m.kept, m.index, g, a.gcham + oq * 3);
     }
   }
-  const float tot = wave_sum(active ? best : 0.f);
-  if (lane == 0) (ROLE == 0 ? a.part_cx : a.part_cy)[(size_t)n * gridDim.x + blockIdx.x] = tot;
+  const float tot = wave_sum(m.kept ? m.rho : 0.f);
+  float wtot = 0.f;
+  if constexpr (ROBUST) wtot = wave_sum(m.w);
+  const int cnt = GATED ? __popcll(__ballot(m.kept)) : 0;   // (an integer count: no order to fix)
+  if (lane == 0) {
+    const size_t slot = (size_t)n * gridDim.x + blockIdx.x;
+    (ROLE == 0 ? a.part_cx : a.part_cy)[slot] = tot;
+    if constexpr (ROBUST) (ROLE == 0 ? a.part_wx : a.part_wy)[slot] = wtot;
+    if constexpr (GATED) (ROLE == 0 ? a.part_kx : a.part_ky)[slot] = cnt;
+  }
 }
 
 // blocks [0, bv): one vertex per thread; blocks [bv, bv + bp): one face pair per thread
@@ -402,6 +331,38 @@ __device__ __forceinline__ float mesh3d_sum(const float* p, int count, float* re
   return block_sum(s, red);
 }
 
+// a mesh's total of per-block partials, in block order, one thread per mesh; `otherwise` where no kernel wrote any (part == null)
+template <typename T>
+__device__ __forceinline__ T mesh_total(const T* part, int n, int blocks, T otherwise) {
+  if (part == nullptr) return otherwise;
+  T s = 0;
+  for (int b = 0; b < blocks; ++b) s += part[(size_t)n * blocks + b];
+  return s;
+}
+// what a reduce reports of one direction of a data term on mesh n: the kept count, summed from the counting (GATED) kernel's
+// partials -- where none ran nothing was dropped and nothing counted: every query of a direction that is on -- and the sum of
+// the weights, from the ROBUST kernel's partials -- where none ran every weight is 1: the kept count, as a float
+struct DirectionTotals { int kept; float w; };
+__device__ __forceinline__ DirectionTotals direction_totals(const int* part_kept, const float* part_w, int n, int blocks, bool on,
+                                                            int queries) {
+  DirectionTotals t;
+  t.kept = mesh_total(part_kept, n, blocks, on ? queries : 0);
+  t.w = mesh_total(part_w, n, blocks, (float)t.kept);
+  return t;
+}
+// rows [n][2] = points | vertices of the outputs that were asked for
+__device__ __forceinline__ void write_direction_totals(int* kept, float* weight_sums, int n, const DirectionTotals& p,
+                                                       const DirectionTotals& v) {
+  if (kept != nullptr) {
+    kept[2 * n] = p.kept;
+    kept[2 * n + 1] = v.kept;
+  }
+  if (weight_sums != nullptr) {
+    weight_sums[2 * n] = p.w;
+    weight_sums[2 * n + 1] = v.w;
+  }
+}
+
 __global__ __launch_bounds__(256) void mesh3d_reduce_kernel(Mesh3dArgs a) {
   __shared__ float red[16];
   const float fn = (float)a.N;
@@ -425,44 +386,11 @@ __global__ __launch_bounds__(256) void mesh3d_reduce_kernel(Mesh3dArgs a) {
     for (int b = 0; b < a.bv; ++b) s += a.part_dtr[((size_t)n * a.bv + b) * 3 + k];
     a.dtrans[o] = s;
   }
-  if (a.kept != nullptr) {
-    // counted by the gated chamfer kernels; where the ungated one ran nothing was dropped and nothing counted: every query
+  if (a.kept != nullptr || a.weight_sums != nullptr) {
     for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
-      int kp = a.w_chamfer > 0.f ? a.S : 0, kv = a.w_chamfer > 0.f ? a.V : 0;
-      if (a.part_kx != nullptr) {
-        kp = 0;
-        for (int b = 0; b < a.bx; ++b) kp += a.part_kx[(size_t)n * a.bx + b];
-      }
-      if (a.part_ky != nullptr) {
-        kv = 0;
-        for (int b = 0; b < a.by; ++b) kv += a.part_ky[(size_t)n * a.by + b];
-      }
-      a.kept[2 * n] = kp;
-      a.kept[2 * n + 1] = kv;
-    }
-  }
-  if (a.weight_sums != nullptr) {
-    // summed by the ROBUST chamfer kernels, per mesh in block order; where none ran every weight is 1: the kept count, as a float
-    for (int n = threadIdx.x; n < a.N; n += blockDim.x) {
-      float wp = 0.f, wv = 0.f;
-      if (a.part_wx != nullptr) {
-        for (int b = 0; b < a.bx; ++b) wp += a.part_wx[(size_t)n * a.bx + b];
-        for (int b = 0; b < a.by; ++b) wv += a.part_wy[(size_t)n * a.by + b];
-      } else if (a.w_chamfer > 0.f) {
-        int kp = a.S, kv = a.V;
-        if (a.part_kx != nullptr) {
-          kp = 0;
-          for (int b = 0; b < a.bx; ++b) kp += a.part_kx[(size_t)n * a.bx + b];
-        }
-        if (a.part_ky != nullptr) {
-          kv = 0;
-          for (int b = 0; b < a.by; ++b) kv += a.part_ky[(size_t)n * a.by + b];
-        }
-        wp = (float)kp;
-        wv = (float)kv;
-      }
-      a.weight_sums[2 * n] = wp;
-      a.weight_sums[2 * n + 1] = wv;
+      const DirectionTotals p = direction_totals(a.part_kx, a.part_wx, n, a.bx, a.w_chamfer > 0.f, a.S);
+      const DirectionTotals v = direction_totals(a.part_ky, a.part_wy, n, a.by, a.w_chamfer > 0.f, a.V);
+      write_direction_totals(a.kept, a.weight_sums, n, p, v);
     }
   }
 }
@@ -563,10 +491,9 @@ __global__ __launch_bounds__(256) void mesh3d_surface_dist_kernel(MeshScoreArgs 
       st[i] = make_scan_tri(corners + 3 * (size_t)fc[0], corners + 3 * (size_t)fc[1], corners + 3 * (size_t)fc[2]);
     }
     __syncthreads();
-    const int per = (cnt + 3) >> 2;
-    const int b = min(w * per, cnt), e = min(b + per, cnt);
-    // b, e are wave-uniform: every lane reads the same four 16-byte rows of a record (broadcast, conflict free)
-    best = surface_scan(qx, qy, qz, st, b, e, best);
+    // the span is wave-uniform: every lane reads the same four 16-byte rows of a record (broadcast, conflict free)
+    const Span sp = quarter_span(w, cnt);
+    best = surface_scan(qx, qy, qz, st, sp.b, sp.e, best);
   }
   sd[w][lane] = best;
   __syncthreads();
@@ -732,10 +659,9 @@ __global__ __launch_bounds__(256) void mesh3d_surface_near_kernel(SurfaceTermArg
       }
     }
     __syncthreads();
-    const int per = (cnt + 3) >> 2;
-    const int b = min(w * per, cnt), e = min(b + per, cnt);
-    if (GATED) surface_scan_nearest_compatible(qx, qy, qz, ux, uy, uz, cc, st, b, e, base, best, bidx);
-    else surface_scan_nearest(qx, qy, qz, st, b, e, base, best, bidx);
+    const Span sp = quarter_span(w, cnt);
+    if (GATED) surface_scan_nearest_compatible(qx, qy, qz, ux, uy, uz, cc, st, sp.b, sp.e, base, best, bidx);
+    else surface_scan_nearest(qx, qy, qz, st, sp.b, sp.e, base, best, bidx);
   }
   sd[w][lane] = best;
   si[w][lane] = bidx;
@@ -938,50 +864,9 @@ __global__ __launch_bounds__(256) void mesh3d_surface_reduce_kernel(SurfaceTermA
       a.rows[2 * n] = sp;
       a.rows[2 * n + 1] = sv;
     }
-    if (a.kept != nullptr) {
-      // counted by the gated hit kernels; where the ungated one ran nothing was dropped and nothing counted: every query
-      int kp = a.w_ps > 0.f ? a.S : 0, kv = a.w_vs > 0.f ? a.V : 0;
-      if (a.part_kp != nullptr) {
-        kp = 0;
-        for (int b = 0; b < a.hp; ++b) kp += a.part_kp[(size_t)n * a.hp + b];
-      }
-      if (a.part_kv != nullptr) {
-        kv = 0;
-        for (int b = 0; b < a.hv; ++b) kv += a.part_kv[(size_t)n * a.hv + b];
-      }
-      a.kept[2 * n] = kp;
-      a.kept[2 * n + 1] = kv;
-    }
-    if (a.weight_sums != nullptr) {
-      // summed by the ROBUST hit kernels in block order; where the other one ran every weight is 1: the kept count, as a float
-      float wp = 0.f, wv = 0.f;
-      if (a.w_ps > 0.f) {
-        if (a.part_wp != nullptr) {
-          for (int b = 0; b < a.hp; ++b) wp += a.part_wp[(size_t)n * a.hp + b];
-        } else {
-          int kp = a.S;
-          if (a.part_kp != nullptr) {
-            kp = 0;
-            for (int b = 0; b < a.hp; ++b) kp += a.part_kp[(size_t)n * a.hp + b];
-          }
-          wp = (float)kp;
-        }
-      }
-      if (a.w_vs > 0.f) {
-        if (a.part_wv != nullptr) {
-          for (int b = 0; b < a.hv; ++b) wv += a.part_wv[(size_t)n * a.hv + b];
-        } else {
-          int kv = a.V;
-          if (a.part_kv != nullptr) {
-            kv = 0;
-            for (int b = 0; b < a.hv; ++b) kv += a.part_kv[(size_t)n * a.hv + b];
-          }
-          wv = (float)kv;
-        }
-      }
-      a.weight_sums[2 * n] = wp;
-      a.weight_sums[2 * n + 1] = wv;
-    }
+    if (a.kept != nullptr || a.weight_sums != nullptr)
+      write_direction_totals(a.kept, a.weight_sums, n, direction_totals(a.part_kp, a.part_wp, n, a.hp, a.w_ps > 0.f, a.S),
+                             direction_totals(a.part_kv, a.part_wv, n, a.hv, a.w_vs > 0.f, a.V));
   }
   tp = block_sum(tp, red);
   tv = block_sum(tv, red);

@@ -102,6 +102,15 @@ SMALFIT_HD void nearest_scan(float qx, float qy, float qz, const ScanPoint* p, i
   }
 }
 
+// the share [b, e) of wave w of 4 in a staged chunk of cnt records: quarters rounded up, the last ones short or empty.  The one
+// definition for every kernel that splits a chunk over its four waves, and for the host shims that walk the same split
+struct Span { int b, e; };
+SMALFIT_HD Span quarter_span(int w, int cnt) {
+  const int per = (cnt + 3) >> 2;
+  const int b = w * per < cnt ? w * per : cnt;
+  return Span{b, b + per < cnt ? b + per : cnt};
+}
+
 // lexicographic (distance, index) minimum: combines the scans of disjoint index ranges in any order
 SMALFIT_HD void nearest_merge(float& best, int& best_idx, float d2, int idx) {
   if (d2 < best || (d2 == best && idx < best_idx)) {
@@ -187,6 +196,51 @@ SMALFIT_HD void robust_gm(float d2, float s2, float& rho, float& w) {
   const float u = s2 / (s2 + d2);
   rho = d2 * u;
   w = u * u;
+}
+
+// ---- mesh3d_chamfer_kernel<ROLE, GATED, ROBUST> in pieces: how it scans either record type, what it decides per query -------
+// the scan of either record type over p[begin .. end), staged from element index_base on (u, c: read by the gated scan alone)
+template <bool OWNER, bool WEIGHTED>
+SMALFIT_HD void scan_records(float qx, float qy, float qz, float, float, float, float, const ScanPoint* p, int begin, int end,
+                             int index_base, float& best, int& best_idx, int self, float g[3], const float* wt) {
+  nearest_scan<OWNER, WEIGHTED>(qx, qy, qz, p, begin, end, index_base, best, best_idx, self, g, wt);
+}
+template <bool OWNER, bool WEIGHTED>
+SMALFIT_HD void scan_records(float qx, float qy, float qz, float ux, float uy, float uz, float c, const GatedScanPoint* p, int begin,
+                             int end, int, float& best, int& best_tag, int self, float g[3], const float* wt) {
+  nearest_scan_gated<OWNER, WEIGHTED>(qx, qy, qz, ux, uy, uz, c, p, begin, end, best, best_tag, self, g, wt);
+}
+
+// what is decided once per query after the waves' minima have met.  Ungated: the match is the nearest element and every active
+// query is kept.  GATED: gated_match on the winner's tag.  ROBUST: robust_gm on the match's d^2 under s2 (s2 = 0: this direction's
+// scale is off, w = 1 and rho = d^2).  Without ROBUST rho = d^2 and w = 1; a dropped query's w is 0.  The sums take rho of the kept
+struct ChamferMatch { int index; bool kept; float rho, w; };   // index: of the matched element (GATED: -1 when none was found)
+template <bool GATED, bool ROBUST>
+SMALFIT_HD ChamferMatch chamfer_match(float best, int bidx, float tau2, int reject_boundary, float s2, bool active) {
+  ChamferMatch m;
+  m.index = bidx;
+  m.kept = active;
+  if constexpr (GATED) {
+    const GatedMatch mt = gated_match(best, bidx, tau2, reject_boundary);
+    m.index = mt.index;
+    m.kept = active && mt.kept;
+  }
+  float rho = best, w = 1.0f;
+  if constexpr (ROBUST) {
+    if (s2 > 0.f) robust_gm(best, s2, rho, w);
+  }
+  m.rho = rho;
+  m.w = m.kept ? w : 0.f;
+  return m;
+}
+
+// d/dy of a vertex's chamfer terms: cy (y - x_match) for its own match + cx sum (y - x_s) over the points that chose it (g, as the
+// scans gathered it).  A vertex that is not kept, or whose match is no element (no finite distance: NaN input), reads x_0: in bounds
+SMALFIT_HD void chamfer_vertex_grad(float cy, float cx, const float y[3], const float* x, int count, bool kept, int index,
+                                    const float g[3], float out[3]) {
+  const float* xn = x + 3 * (size_t)(kept && (unsigned)index < (unsigned)count ? index : 0);   // (one compare: a negative index is a large unsigned one)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = cy * (y[k] - xn[k]) + cx * g[k];
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -34,6 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "smalfit_internal.h"
 #include "mesh3d_math.h"
 #include "smalfit_plan.h"

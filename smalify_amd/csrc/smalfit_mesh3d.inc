@@ -1,7 +1,7 @@
 // Host side of the 3D mesh-fitting objective (SURVEY.md §8f row 3): topology upload, target meshes + sampler,
 // kernel sequencing, C-ABI.  Included at the end of smalfit_kernels.hip after smalfit_launch.inc.  The tables are built by
-// mesh3d_topology.h; which arguments are refused, the grids and the shape of a fit3d step (plan_fit3d) are smalfit_plan.h; here are
-// the pointers, the allocations, the copies and the launches.
+// mesh3d_topology.h; which arguments are refused, the grids, the shape of a fit3d step (plan_fit3d) and what its opt-in blocks
+// share (plan_fit3d_riders) are smalfit_plan.h; here are the pointers, the allocations, the copies and the launches.
 #include "mesh3d_topology.h"
 
 static_assert(kMeshQueries == kChamQueries && kMeshThreads == kMeshBlock, "smalfit_plan.h sizes the grids of the mesh3d kernels");
@@ -48,25 +48,54 @@ struct smalfit_mesh_targets {
   const unsigned char* bflags = nullptr;   // packed [sum F]: boundary_flags of every mesh, beside the records
 };
 
-// the launches of the surface term on `verts`; the block validated by the callers.  In a step the term's gradient is ADDED to
-// the step's d verts, its planar copy (stride Vp) and d trans, after run_mesh_objective has written them: one float32 addition
-// per coordinate, the addition Stage.step_unfused performs on the stand-alone call's outputs -- the two paths form the same bits
-// With a gate block (validated by the callers; point_normals: the caller's or the sampler's) the gated instantiations take the
-// place of the ungated ones where plan_surface_gates says so; with none, or every gate off, the launches are those of before
-// With a robust block (validated by the callers) the hit kernel of a direction is its ROBUST instantiation where plan_robust
-// says so; with none, or its scales off, the launches are those of before (the reduce then reads the weight sums, if asked for,
-// off the kept counts)
-static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_targets* t, hipStream_t st, const smalfit_surface_term_args* a,
-                            const float* verts, const float* points, int num_points, float* acc_dverts = nullptr,
-                            float* acc_planar = nullptr, int Vp = 0, float* acc_dtrans = nullptr,
-                            const float* step_losses = nullptr, const smalfit_surface_gate_args* gate = nullptr,
-                            const float* point_normals = nullptr, const float* ready_vnorm = nullptr,
-                            const smalfit_robust_args* robust = nullptr) {
+// (gated, robust) -> the template instantiation: f is called with the two flags as std::bool_constant
+template <typename F>
+static void with_flags(bool gated, bool robust, F&& f) {
+  if (gated && robust) f(std::true_type{}, std::true_type{});
+  else if (gated) f(std::true_type{}, std::false_type{});
+  else if (robust) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+// one dispatcher per templated kernel
+template <int ROLE>
+static void launch_chamfer(bool gated, bool robust, int blocks, hipStream_t st, const Mesh3dArgs& a) {
+  with_flags(gated, robust, [&](auto g, auto r) { mesh3d_chamfer_kernel<ROLE, g.value, r.value><<<dim3(blocks, a.N), 256, 0, st>>>(a); });
+}
+template <int ROLE>
+static void launch_surface_near(bool gated, const Grid3& g3, hipStream_t st, const SurfaceTermArgs& k) {
+  with_flags(gated, false, [&](auto g, auto) { mesh3d_surface_near_kernel<ROLE, g.value><<<dim3(g3.x, g3.y, g3.z), 256, 0, st>>>(k); });
+}
+template <int ROLE>
+static void launch_surface_hit(bool gated, bool robust, const Grid2& g2, hipStream_t st, const SurfaceTermArgs& k) {
+  with_flags(gated, robust, [&](auto g, auto r) { mesh3d_surface_hit_kernel<ROLE, g.value, r.value><<<dim3(g2.x, g2.y), kMeshBlock, 0, st>>>(k); });
+}
+
+// one run of the surface term: the block (validated by the callers), what it is evaluated on, and what rides along
+struct SurfaceTermRun {
+  const smalfit_surface_term_args* term = nullptr;
+  const float *verts = nullptr, *points = nullptr;     // [N][V][3] | [N][S][3]
+  int num_points = 0;
+  // in a step the term's gradient is ADDED to the step's d verts, its planar copy (stride Vp) and d trans, after
+  // run_mesh_objective has written them: one float32 addition per coordinate, the addition Stage.step_unfused performs on the
+  // stand-alone call's outputs -- the two paths form the same bits
+  float *acc_dverts = nullptr, *acc_planar = nullptr, *acc_dtrans = nullptr;
+  int Vp = 0;
+  const float* step_losses = nullptr;                  // [5] of the step, or null: term->step_total is not written
+  const smalfit_surface_gate_args* gate = nullptr;     // validated by the callers; plan_surface_gates says what it switches on
+  const smalfit_robust_args* robust = nullptr;         // validated by the callers; plan_robust says what it switches on
+  const float* point_normals = nullptr;                // the caller's or the sampler's
+  const float* ready_vert_normals = nullptr;           // the step's chamfer gates have gathered them: no gather here
+};
+// the launches of the surface term.  With no gate block, or every gate off, and no robust block, or its scales off, the launches
+// are those of the plain term (the reduce then reads the kept counts and weight sums, if asked for, off the query counts)
+static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_targets* t, hipStream_t st, const SurfaceTermRun& r) {
+  const smalfit_surface_term_args* a = r.term;
+  const smalfit_surface_gate_args* gate = r.gate;
   SurfaceTermArgs k{};
   k.N = a->num_meshes; k.V = m->t.V; k.F = m->num_faces;
   k.w_ps = mesh_weight(a->w_point_surface); k.w_vs = mesh_weight(a->w_vert_surface);
-  k.S = k.w_ps > 0.f ? num_points : 1;
-  k.verts = verts; k.points = points; k.faces = m->faces;
+  k.S = k.w_ps > 0.f ? r.num_points : 1;
+  k.verts = r.verts; k.points = r.points; k.faces = m->faces;
   if (k.w_vs > 0.f) { k.t = t->d; k.target_tris = t->tris; }
   k.keys_v = m->surf_keys; k.keys_p = m->surf_keys + (size_t)k.N * k.V;
   k.hits = m->surf_hits; k.res_v = m->surf_res;
@@ -75,9 +104,9 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
   k.part_ps = m->surf_part_ps; k.part_vs = m->surf_part_vs; k.part_dtr = m->surf_part_dtr;
   const Grid2 hv = surface_hit_grid(k.V, k.N), hp = surface_hit_grid(k.S, k.N), gg = surface_grad_grid(k.V, k.N);
   k.hv = hv.x; k.hp = hp.x; k.gv = gg.x;
-  k.acc_dverts = acc_dverts; k.acc_planar = acc_planar; k.Vp = Vp; k.acc_dtrans = acc_dtrans;
+  k.acc_dverts = r.acc_dverts; k.acc_planar = r.acc_planar; k.Vp = r.Vp; k.acc_dtrans = r.acc_dtrans;
   k.dverts = a->dverts; k.dtrans = a->dtrans; k.losses = a->losses; k.rows = a->rows;
-  k.step_losses = step_losses; k.step_total = step_losses ? a->step_total : nullptr;
+  k.step_losses = r.step_losses; k.step_total = r.step_losses ? a->step_total : nullptr;
   const SurfaceGatePlan gp = plan_surface_gates(gate, k.w_ps > 0.f, k.w_vs > 0.f);
   k.cc_v = gp.cc_vert; k.cc_p = gp.cc_point; k.tau2_v = gp.tau2_vert; k.tau2_p = gp.tau2_point;
   k.vf_off = m->vf_off; k.vf = m->vf;
@@ -86,49 +115,33 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
     if (k.w_vs > 0.f) { k.part_kv = m->surf_part_kv; k.vert_kept = gate->vert_kept; }
     if (k.w_ps > 0.f) { k.part_kp = m->surf_part_kp; k.point_kept = gate->point_kept; }
     if (gp.boundary) k.bflags = t->bflags;
-    // (ready_vnorm: the step's chamfer gates have already gathered the vertex normals of these vertices, where this term wants them)
-    if (gp.cos_vert) { k.normals_out = gate->vert_normals ? gate->vert_normals : m->surf_vnorm; k.normals_v = ready_vnorm ? ready_vnorm : k.normals_out; }
-    if (gp.cos_point) k.normals_p = point_normals;
+    if (gp.cos_vert) { k.normals_out = gate->vert_normals ? gate->vert_normals : m->surf_vnorm; k.normals_v = r.ready_vert_normals ? r.ready_vert_normals : k.normals_out; }
+    if (gp.cos_point) k.normals_p = r.point_normals;
   }
-  const RobustPlan rp = plan_robust(robust, RobustFacts{false, true, false, k.w_ps > 0.f, k.w_vs > 0.f});
+  const RobustPlan rp = plan_robust(r.robust, RobustFacts{false, true, false, k.w_ps > 0.f, k.w_vs > 0.f});
   k.s2_v = rp.s2_surface_vert; k.s2_p = rp.s2_surface_point;
-  if (robust) k.weight_sums = robust->surface_weight_sums;
-  if (rp.surface_vert) { k.part_wv = m->surf_part_wv; k.vert_w = robust->surface_vert_weights; }
-  if (rp.surface_point) { k.part_wp = m->surf_part_wp; k.point_w = robust->surface_point_weights; }
+  if (r.robust) k.weight_sums = r.robust->surface_weight_sums;
+  if (rp.surface_vert) { k.part_wv = m->surf_part_wv; k.vert_w = r.robust->surface_vert_weights; }
+  if (rp.surface_point) { k.part_wp = m->surf_part_wp; k.point_w = r.robust->surface_point_weights; }
   // the keys of the directions that run, all ones: the vertices' come first, the points' behind them
   unsigned long long* first = k.w_vs > 0.f ? k.keys_v : k.keys_p;
   const size_t keys = (size_t)k.N * ((k.w_vs > 0.f ? (size_t)k.V : 0) + (k.w_ps > 0.f ? (size_t)k.S : 0));
   if (keys > 0) HIP_OK(hipMemsetAsync(first, 0xFF, keys * sizeof(unsigned long long), st));
   if (k.w_vs > 0.f) {
-    const Grid3 g = surface_near_grid(k.V, t->max_faces, k.N);
-    if (gp.cos_vert) {
-      if (!ready_vnorm) {
-        const Grid2 gn = vertex_normal_grid(k.V, k.N);
-        mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
-        LAUNCH_OK("mesh3d_vertex_normal_kernel");
-      }
-      mesh3d_surface_near_kernel<0, true><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
-    } else {
-      mesh3d_surface_near_kernel<0, false><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    if (gp.cos_vert && !r.ready_vert_normals) {
+      const Grid2 gn = vertex_normal_grid(k.V, k.N);
+      mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
+      LAUNCH_OK("mesh3d_vertex_normal_kernel");
     }
+    launch_surface_near<0>(gp.cos_vert, surface_near_grid(k.V, t->max_faces, k.N), st, k);
     LAUNCH_OK("mesh3d_surface_near_kernel<0>");
-    if (rp.surface_vert) {
-      if (gp.any) mesh3d_surface_hit_kernel<0, true, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
-      else mesh3d_surface_hit_kernel<0, false, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
-    } else if (gp.any) mesh3d_surface_hit_kernel<0, true><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
-    else mesh3d_surface_hit_kernel<0, false><<<dim3(hv.x, hv.y), kMeshBlock, 0, st>>>(k);
+    launch_surface_hit<0>(gp.any, rp.surface_vert, hv, st, k);
     LAUNCH_OK("mesh3d_surface_hit_kernel<0>");
   }
   if (k.w_ps > 0.f) {
-    const Grid3 g = surface_near_grid(k.S, k.F, k.N);
-    if (gp.cos_point) mesh3d_surface_near_kernel<1, true><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
-    else mesh3d_surface_near_kernel<1, false><<<dim3(g.x, g.y, g.z), 256, 0, st>>>(k);
+    launch_surface_near<1>(gp.cos_point, surface_near_grid(k.S, k.F, k.N), st, k);
     LAUNCH_OK("mesh3d_surface_near_kernel<1>");
-    if (rp.surface_point) {
-      if (gp.any) mesh3d_surface_hit_kernel<1, true, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
-      else mesh3d_surface_hit_kernel<1, false, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
-    } else if (gp.any) mesh3d_surface_hit_kernel<1, true><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
-    else mesh3d_surface_hit_kernel<1, false><<<dim3(hp.x, hp.y), kMeshBlock, 0, st>>>(k);
+    launch_surface_hit<1>(gp.any, rp.surface_point, hp, st, k);
     LAUNCH_OK("mesh3d_surface_hit_kernel<1>");
   }
   mesh3d_surface_grad_kernel<<<dim3(gg.x, gg.y), 64 * kSurfaceGradWaves, 0, st>>>(k);
@@ -138,69 +151,70 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
   return 0;
 }
 
-// the 6 launches of one evaluation; arguments validated by the callers.  With a chamfer gate block (validated by the callers;
-// point_normals / point_boundary: the caller's or the sampler's; vnorm: where the fitted vertex normals go when a compatibility
-// test asks for them) the gated chamfer instantiations take the place of the ungated ones where plan_chamfer_gates says so, and
-// mesh3d_vertex_normal_kernel runs between compose and them; with none, or every gate off, the launches are those of before
-// With a robust block (validated by the callers) whose plan has a chamfer scale on, both chamfer launches are the ROBUST
-// instantiations of the kernel the gates chose; with none, or both scales off, the launches are those of before
-static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, int num_meshes, const float* lbs_verts,
-                              const float* trans, const float* deform_verts, const float* points, int num_points,
-                              const float* weights, float* verts_out, float* losses, float* dverts, float* dtrans,
-                              const float* lbs_planar = nullptr, int Vp = 0, float* dverts_planar = nullptr,
-                              const smalfit_chamfer_gate_args* gate = nullptr, const float* point_normals = nullptr,
-                              const unsigned char* point_boundary = nullptr, float* vnorm = nullptr,
-                              const smalfit_robust_args* robust = nullptr) {
-  const float wc = mesh_weight(weights[0]);
+// one evaluation of the objective: inputs, outputs, the opt-in blocks (validated by the callers) and what rides along
+struct MeshObjectiveRun {
+  int num_meshes = 0, num_points = 0;
+  const float* lbs_verts = nullptr;      // [N][V][3], or ...
+  const float* lbs_planar = nullptr;     // ... [N][3][Vp]: the engine's planar vertices, read in place
+  int Vp = 0;
+  const float *trans = nullptr, *deform_verts = nullptr, *points = nullptr;
+  const float* weights = nullptr;        // host [4]
+  float* verts_out = nullptr;            // or null: the objective's own buffer
+  float *losses = nullptr, *dverts = nullptr, *dtrans = nullptr;
+  float* dverts_planar = nullptr;        // [N][3][Vp] or null: a second copy where the LBS adjoint reads it
+  const smalfit_chamfer_gate_args* gate = nullptr;   // plan_chamfer_gates says what it switches on
+  const smalfit_robust_args* robust = nullptr;       // plan_robust says what it switches on
+  const float* point_normals = nullptr;              // the caller's or the sampler's
+  const unsigned char* point_boundary = nullptr;
+  float* vert_normals = nullptr;                     // where the fitted vertex normals go when a compatibility test asks for them
+};
+// the 6 launches of one evaluation.  Where plan_chamfer_gates / plan_robust switch a direction on, its chamfer launch is the GATED
+// / ROBUST instantiation, and mesh3d_vertex_normal_kernel runs between compose and them when a compatibility test reads the
+// vertex normals; with the blocks absent or everything off, the launches are those of the plain objective
+static int run_mesh_objective(smalfit_mesh_objective* m, hipStream_t st, const MeshObjectiveRun& r) {
+  const float wc = mesh_weight(r.weights[0]);
   Mesh3dArgs a{};
-  a.N = num_meshes; a.V = m->t.V; a.S = mesh_points(wc, num_points);
+  a.N = r.num_meshes; a.V = m->t.V; a.S = mesh_points(wc, r.num_points);
   a.t = m->t;
-  a.lbs_verts = lbs_verts; a.lbs_planar = lbs_planar; a.Vp = Vp; a.dverts_planar = dverts_planar;
-  a.trans = trans; a.deform = deform_verts;
-  a.verts = verts_out ? verts_out : m->verts;
-  a.points = points; a.nn_idx = m->nn_idx;
+  a.lbs_verts = r.lbs_verts; a.lbs_planar = r.lbs_planar; a.Vp = r.Vp; a.dverts_planar = r.dverts_planar;
+  a.trans = r.trans; a.deform = r.deform_verts;
+  a.verts = r.verts_out ? r.verts_out : m->verts;
+  a.points = r.points; a.nn_idx = m->nn_idx;
   a.gcham = m->gcham; a.gedge = m->gedge; a.lap_unit = m->lap_unit; a.gpair = m->gpair;
-  a.dverts = dverts; a.dtrans = dtrans; a.losses = losses;
-  a.w_chamfer = wc; a.w_edge = mesh_weight(weights[1]); a.w_normal = mesh_weight(weights[2]);
-  a.w_laplacian = mesh_weight(weights[3]);
+  a.dverts = r.dverts; a.dtrans = r.dtrans; a.losses = r.losses;
+  a.w_chamfer = wc; a.w_edge = mesh_weight(r.weights[1]); a.w_normal = mesh_weight(r.weights[2]);
+  a.w_laplacian = mesh_weight(r.weights[3]);
   a.part_cx = m->part_cx; a.part_cy = m->part_cy; a.part_edge = m->part_edge; a.part_lap = m->part_lap;
   a.part_normal = m->part_normal; a.part_dtr = m->part_dtr;
   a.bx = mesh_query_blocks(a.S); a.by = m->by; a.bv = m->bv; a.bp = m->bp;
+  const smalfit_chamfer_gate_args* gate = r.gate;
   const ChamferGatePlan gp = plan_chamfer_gates(gate, wc > 0.f);
   a.cos_p = gp.c_point; a.cos_v = gp.c_vert; a.tau2_p = gp.tau2_point; a.tau2_v = gp.tau2_vert;
   if (gate) a.kept = gate->kept;
   if (gp.gated_point) { a.part_kx = m->part_kx; a.point_kept = gate->point_kept; a.point_nn = gate->point_nn; }
   if (gp.gated_vert) { a.part_ky = m->part_ky; a.vert_kept = gate->vert_kept; a.vert_nn = gate->vert_nn; }
-  if (gp.point_boundary) a.bound_p = point_boundary;
-  if (gp.vert_normals) { a.normals_v = vnorm; a.normals_p = point_normals; }
-  const RobustPlan rp = plan_robust(robust, RobustFacts{true, false, wc > 0.f, false, false});
+  if (gp.point_boundary) a.bound_p = r.point_boundary;
+  if (gp.vert_normals) { a.normals_v = r.vert_normals; a.normals_p = r.point_normals; }
+  const RobustPlan rp = plan_robust(r.robust, RobustFacts{true, false, wc > 0.f, false, false});
   a.s2_p = rp.s2_chamfer_point; a.s2_v = rp.s2_chamfer_vert;
-  if (robust) a.weight_sums = robust->chamfer_weight_sums;
+  if (r.robust) a.weight_sums = r.robust->chamfer_weight_sums;
   if (rp.chamfer) {
     a.wts = m->cham_w; a.part_wx = m->part_wx; a.part_wy = m->part_wy;
-    a.point_w = robust->chamfer_point_weights; a.vert_w = robust->chamfer_vert_weights;
+    a.point_w = r.robust->chamfer_point_weights; a.vert_w = r.robust->chamfer_vert_weights;
   }
   mesh3d_compose_kernel<<<dim3(mesh_compose_blocks(a.N, a.V)), 256, 0, st>>>(a);
   LAUNCH_OK("mesh3d_compose_kernel");
   if (gp.vert_normals) {
     SurfaceTermArgs k{};
-    k.N = a.N; k.V = a.V; k.verts = a.verts; k.faces = m->faces; k.vf_off = m->vf_off; k.vf = m->vf; k.normals_out = vnorm;
+    k.N = a.N; k.V = a.V; k.verts = a.verts; k.faces = m->faces; k.vf_off = m->vf_off; k.vf = m->vf; k.normals_out = r.vert_normals;
     const Grid2 gn = vertex_normal_grid(k.V, k.N);
     mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
     LAUNCH_OK("mesh3d_vertex_normal_kernel");
   }
   if (wc > 0.f) {
-    if (rp.chamfer) {
-      if (gp.gated_point) mesh3d_chamfer_kernel<0, true, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
-      else mesh3d_chamfer_kernel<0, false, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
-    } else if (gp.gated_point) mesh3d_chamfer_kernel<0, true><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
-    else mesh3d_chamfer_kernel<0, false><<<dim3(a.bx, a.N), 256, 0, st>>>(a);
+    launch_chamfer<0>(gp.gated_point, rp.chamfer, a.bx, st, a);
     LAUNCH_OK("mesh3d_chamfer_kernel<0>");
-    if (rp.chamfer) {
-      if (gp.gated_vert) mesh3d_chamfer_kernel<1, true, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
-      else mesh3d_chamfer_kernel<1, false, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
-    } else if (gp.gated_vert) mesh3d_chamfer_kernel<1, true><<<dim3(a.by, a.N), 256, 0, st>>>(a);
-    else mesh3d_chamfer_kernel<1, false><<<dim3(a.by, a.N), 256, 0, st>>>(a);
+    launch_chamfer<1>(gp.gated_vert, rp.chamfer, a.by, st, a);
     LAUNCH_OK("mesh3d_chamfer_kernel<1>");
   } else {
     HIP_OK(hipMemsetAsync(m->gcham, 0, (size_t)a.N * a.V * 3 * sizeof(float), st));
@@ -352,9 +366,14 @@ int smalfit_mesh_objective_eval_robust(smalfit_mesh_objective* m, void* stream, 
   if (g && refused(who, chamfer_gate_args_refusal(g, ChamferGateFacts{weights[0] > 0.f, false, false}))) return 1;
   if (g && t && t->d.N != num_meshes) return refused(who, "number of target meshes differs from num_meshes");
   if (rb && refused(who, robust_args_refusal(rb, RobustFacts{true, false, weights[0] > 0.f, false, false}))) return 1;
-  return run_mesh_objective(m, (hipStream_t)stream, num_meshes, lbs_verts, trans, deform_verts, points, num_points, weights,
-                            verts_out, losses, dverts, dtrans, nullptr, 0, nullptr, g, g ? g->point_normals : nullptr,
-                            g ? g->point_boundary : nullptr, m->surf_vnorm, rb);
+  MeshObjectiveRun r;
+  r.num_meshes = num_meshes; r.lbs_verts = lbs_verts; r.trans = trans; r.deform_verts = deform_verts;
+  r.points = points; r.num_points = num_points; r.weights = weights;
+  r.verts_out = verts_out; r.losses = losses; r.dverts = dverts; r.dtrans = dtrans;
+  r.gate = g; r.robust = rb;
+  if (g) { r.point_normals = g->point_normals; r.point_boundary = g->point_boundary; }
+  r.vert_normals = m->surf_vnorm;
+  return run_mesh_objective(m, (hipStream_t)stream, r);
 }
 
 int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const int* face_counts, const float* verts,
@@ -485,8 +504,11 @@ int smalfit_mesh_surface_eval_robust(smalfit_mesh_objective* m, smalfit_mesh_tar
   if (g && refused(who, surface_gate_args_refusal(g, a, SurfaceGateFacts{t != nullptr, false, false}))) return 1;
   if (rb && refused(who, robust_args_refusal(rb, RobustFacts{false, true, false, a->w_point_surface > 0.f, a->w_vert_surface > 0.f})))
     return 1;
-  return run_surface_term(m, t, (hipStream_t)stream, a, a->verts, a->points, a->num_points, nullptr, nullptr, 0, nullptr, nullptr, g,
-                          g ? g->point_normals : nullptr, nullptr, rb);
+  SurfaceTermRun r;
+  r.term = a; r.verts = a->verts; r.points = a->points; r.num_points = a->num_points;
+  r.gate = g; r.robust = rb;
+  if (g) r.point_normals = g->point_normals;
+  return run_surface_term(m, t, (hipStream_t)stream, r);
 }
 
 // ---- Stage.step in one call ------------------------------------------------------------------------------------------
@@ -539,42 +561,43 @@ int smalfit_fit3d_step_robust(smalfit_engine* e, smalfit_mesh_objective* m, smal
   ex.grot = a->global_rot; ex.jrot = a->joint_rot; ex.gmask = e->ones; ex.rmask = e->ones;
   if (run_lbs_forward(e, st, N, a->betas, nb, nb, a->log_beta_scales, 6, e->zeros, nullptr, &ex)) return 1;
 
-  // target points of this iteration
+  // target points of this iteration, with what plan_fit3d_riders says the gates of both terms share
+  const Fit3dRiders riders = plan_fit3d_riders(sf, gate, cg, a->weights[0], plan.points);
   const float* pts = a->points;
-  const float* pnormals = gate ? gate->point_normals : nullptr;
-  // the chamfer gates' view of the same points: their normals, their boundary bytes, and where the fitted vertex normals go --
-  // where the surface term's gates ask for a copy when they want them too, so that one gather serves both
-  const ChamferGatePlan cplan = plan_chamfer_gates(cg, a->weights[0] > 0.f);
-  const float* cnormals = cg ? cg->point_normals : nullptr;
-  const unsigned char* cbound = cg ? cg->point_boundary : nullptr;
-  const bool surface_cos_vert = surface && plan_surface_gates(gate, false, sf->w_vert_surface > 0.f).cos_vert;
-  float* vnorm = surface_cos_vert && gate->vert_normals ? gate->vert_normals : m->surf_vnorm;
   if (plan.points == Fit3dPoints::SampleToCaller || plan.points == Fit3dPoints::SampleToObjective) {
     float* dst = plan.points == Fit3dPoints::SampleToCaller ? a->points_out : m->points;
-    // (with a compatibility test that reads them on, in either term, the normals are drawn with the points, once; the boundary
-    // bytes with the chamfer term's boundary rule)
-    const bool surface_normals = surface && plan_surface_gates(gate, sf->w_point_surface > 0.f, false).cos_point;
-    const bool draw_normals = surface_normals || cplan.point_normals;
-    if (launch_mesh_sampler(t, st, S, a->seed, a->iteration, dst, draw_normals ? m->surf_pnorm : nullptr,
-                            cplan.point_boundary ? m->cham_pbound : nullptr)) return 1;
-    if (surface_normals) pnormals = m->surf_pnorm;
-    if (cplan.point_normals) cnormals = m->surf_pnorm;
-    if (cplan.point_boundary) cbound = m->cham_pbound;
+    if (launch_mesh_sampler(t, st, S, a->seed, a->iteration, dst, riders.draw_normals ? m->surf_pnorm : nullptr,
+                            riders.draw_boundary ? m->cham_pbound : nullptr)) return 1;
     pts = dst;
   } else if (plan.points == Fit3dPoints::CallersCopied) {
     HIP_OK(hipMemcpyAsync(a->points_out, a->points, (size_t)N * S * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
+  float* vnorm = riders.vert_normals == VertNormalsDest::SurfaceGateBlock ? gate->vert_normals : m->surf_vnorm;
 
   // Stage.forward and its gradient wrt the vertices
   // (the compose kernel reads the engine's planar vertices in place; the gather kernel leaves a planar copy of the
   // vertex gradient where the LBS adjoint expects it: no layout-conversion launches in between)
-  if (run_mesh_objective(m, st, N, nullptr, a->trans, a->deform_verts, pts, S, a->weights, a->verts_out, a->losses,
-                         m->dverts, m->dtrans, e->verts, md.Vp, plan.planar_vertex_grad ? e->dext : nullptr, cg, cnormals, cbound,
-                         vnorm, rb)) return 1;
+  MeshObjectiveRun ob;
+  ob.num_meshes = N; ob.lbs_planar = e->verts; ob.Vp = md.Vp; ob.trans = a->trans; ob.deform_verts = a->deform_verts;
+  ob.points = pts; ob.num_points = S; ob.weights = a->weights;
+  ob.verts_out = a->verts_out; ob.losses = a->losses; ob.dverts = m->dverts; ob.dtrans = m->dtrans;
+  ob.dverts_planar = plan.planar_vertex_grad ? e->dext : nullptr;
+  ob.gate = cg; ob.robust = rb;
+  ob.point_normals = riders.chamfer_normals == RiderSource::Drawn ? m->surf_pnorm : cg ? cg->point_normals : nullptr;
+  ob.point_boundary = riders.chamfer_boundary == RiderSource::Drawn ? m->cham_pbound : cg ? cg->point_boundary : nullptr;
+  ob.vert_normals = vnorm;
+  if (run_mesh_objective(m, st, ob)) return 1;
   // the surface term at the vertices the objective composed; its gradient joins the step's in all three places it is read from
-  if (surface && run_surface_term(m, t, st, sf, a->verts_out ? a->verts_out : m->verts, pts, S, m->dverts,
-                                  plan.planar_vertex_grad ? e->dext : nullptr, md.Vp, m->dtrans, a->losses, gate, pnormals,
-                                  cplan.vert_normals && surface_cos_vert ? vnorm : nullptr, rb)) return 1;
+  if (surface) {
+    SurfaceTermRun sr;
+    sr.term = sf; sr.verts = a->verts_out ? a->verts_out : m->verts; sr.points = pts; sr.num_points = S;
+    sr.acc_dverts = m->dverts; sr.acc_planar = ob.dverts_planar; sr.Vp = md.Vp; sr.acc_dtrans = m->dtrans;
+    sr.step_losses = a->losses;
+    sr.gate = gate; sr.robust = rb;
+    sr.point_normals = riders.surface_normals == RiderSource::Drawn ? m->surf_pnorm : gate ? gate->point_normals : nullptr;
+    sr.ready_vert_normals = riders.surface_reuses_vert_normals ? vnorm : nullptr;
+    if (run_surface_term(m, t, st, sr)) return 1;
+  }
   // (a step without the term skips both of its directions: their weight sums read 0)
   if (!surface && rb && rb->surface_weight_sums) HIP_OK(hipMemsetAsync(rb->surface_weight_sums, 0, (size_t)N * 2 * sizeof(float), st));
   if (!plan.any_trained) return 0;

@@ -719,6 +719,39 @@ inline Fit3dPlan plan_fit3d(const smalfit_fit3d_args* a, int model_verts, bool p
   return p;
 }
 
+// What the opt-in blocks of a step share (blocks the refusals accept; any may be NULL).  The points' unit normals and boundary
+// bytes are drawn WITH the points, once, when the step samples them and a compatibility test of either term (the boundary rule
+// of the chamfer term) reads them; with the caller's points each term reads its own gate block's pointers.  The fitted vertex
+// normals are gathered once: behind compose when the chamfer gates read them -- into the surface gate block's vert_normals where
+// the surface term's min_cos_vert wants a copy, else into the objective's buffer -- and the surface term then reads those
+// instead of gathering its own
+enum class RiderSource { Callers = 0, Drawn = 1 };              // the gate block's pointer (may be NULL) | what the sampler drew
+enum class VertNormalsDest { Objective = 0, SurfaceGateBlock = 1 };
+struct Fit3dRiders {
+  bool draw_normals, draw_boundary;        // the sampler also writes the points' unit normals | boundary bytes
+  RiderSource surface_normals;             // the point normals the surface gates read
+  RiderSource chamfer_normals, chamfer_boundary;
+  VertNormalsDest vert_normals;            // where the fitted vertex normals are written, whichever term gathers them
+  bool surface_reuses_vert_normals;        // the chamfer gates gathered them: the surface term launches no gather of its own
+};
+inline Fit3dRiders plan_fit3d_riders(const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
+                                     const smalfit_chamfer_gate_args* cg, float w_chamfer, Fit3dPoints points) {
+  Fit3dRiders r{};
+  const bool surface = surface_term_on(sf);   // a block with both weights <= 0 is the step without it, its gates included
+  const SurfaceGatePlan sp = plan_surface_gates(surface ? gate : nullptr, surface && sf->w_point_surface > 0.f, surface && sf->w_vert_surface > 0.f);
+  const ChamferGatePlan cp = plan_chamfer_gates(cg, w_chamfer > 0.f);
+  if (points == Fit3dPoints::SampleToCaller || points == Fit3dPoints::SampleToObjective) {
+    r.draw_normals = sp.cos_point || cp.point_normals;
+    r.draw_boundary = cp.point_boundary;
+    if (sp.cos_point) r.surface_normals = RiderSource::Drawn;
+    if (cp.point_normals) r.chamfer_normals = RiderSource::Drawn;
+    if (cp.point_boundary) r.chamfer_boundary = RiderSource::Drawn;
+  }
+  if (sp.cos_vert && gate->vert_normals) r.vert_normals = VertNormalsDest::SurfaceGateBlock;
+  r.surface_reuses_vert_normals = cp.vert_normals && sp.cos_vert;
+  return r;
+}
+
 // ------------------------------------------------------------------------------------------------
 // smalfit_fit_args: which blocks are refused
 // ------------------------------------------------------------------------------------------------

@@ -644,59 +644,45 @@ class MeshObjective:
         dev = lbs_verts.device
         o = out if out is not None else {}
         for k, shape in (("losses", (5,)), ("verts", (N, V, 3)), ("dverts", (N, V, 3)), ("dtrans", (N, 3))):
-            if k not in o or tuple(o[k].shape) != shape:
-                o[k] = torch.empty(shape, device=dev)
+            _out_tensor(o, k, shape, torch.float32, dev)
         w = _host(weights, np.float32).reshape(4)
-        if chamfer_gates is None and robust is None:
-            check(self.lib.smalfit_mesh_objective_eval(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans),
-                                                       _ptr(deform_verts), _ptr(points), S, w.ctypes.data, _ptr(o["verts"]),
-                                                       _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"])),
-                  "smalfit_mesh_objective_eval")
-            return o
-        rb = None
+        on = float(w[0]) > 0 and S > 0
+        # the blocks that are on, each with its outputs attached
+        g = rb = None
         if robust is not None:
             rd = _robust_of(robust)
             rb = robust_block(rd)
-            on = float(w[0]) > 0 and S > 0
             outs = (("chamfer_weight_sums", "chamfer_weight_sums", (N, 2)),)
             if on and _scale_on(rd["sigma_chamfer_point"]):
                 outs += (("point_weights", "chamfer_point_weights", (N, S)),)
             if on and _scale_on(rd["sigma_chamfer_vert"]):
                 outs += (("vert_weights", "chamfer_vert_weights", (N, V)),)
             for k, field, shape in outs:
-                if k not in o or tuple(o[k].shape) != shape or o[k].dtype != torch.float32:
-                    o[k] = torch.zeros(shape, device=dev)
-                setattr(rb, field, _ptr(o[k]))
-        if chamfer_gates is None:
-            fn = _lib.resolve(self.lib, "smalfit_mesh_objective_eval_robust")
+                setattr(rb, field, _ptr(_out_tensor(o, k, shape, torch.float32, dev, zero=True)))
+        if chamfer_gates is not None:
+            chamfer_gates_dict = _chamfer_gates_of(chamfer_gates)
+            g = chamfer_gate_block(chamfer_gates_dict)
+            if point_normals is not None:
+                if tuple(point_normals.shape) != (N, S, 3) or point_normals.device != dev or point_normals.dtype != torch.float32:
+                    raise SmalfitError("point_normals must be float32 (N, S, 3) on the device of lbs_verts")
+                g.point_normals = _ptr(point_normals)
+            if point_boundary is not None:
+                if tuple(point_boundary.shape) != (N, S) or point_boundary.device != dev or point_boundary.dtype != torch.uint8:
+                    raise SmalfitError("point_boundary must be uint8 (N, S) on the device of lbs_verts")
+                g.point_boundary = C.c_void_p(point_boundary.data_ptr())
+            masks = (("point_kept", (N, S), torch.uint8), ("vert_kept", (N, V), torch.uint8), ("point_nn", (N, S), torch.int32),
+                     ("vert_nn", (N, V), torch.int32)) if on and chamfer_gates_on(chamfer_gates_dict) else ()
+            for k, shape, dt in (("kept", (N, 2), torch.int32),) + masks:
+                setattr(g, k, C.c_void_p(_out_tensor(o, k, shape, dt, dev, zero=True).data_ptr()))
+        # one call, through the narrowest entry point whose signature holds the last block that is on
+        name, blocks = _narrowest(_EVAL_ENTRY_POINTS, g, rb)
+        tail = ()
+        if blocks:
             targets = getattr(targets, "_dev", targets)
-            check(fn(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans), _ptr(deform_verts), _ptr(points), S, w.ctypes.data,
-                     _ptr(o["verts"]), _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"]),
-                     targets.handle if targets is not None else None, None, C.byref(rb)), "smalfit_mesh_objective_eval_robust")
-            return o
-        name = "smalfit_mesh_objective_eval_robust" if rb is not None else "smalfit_mesh_objective_eval_gated"
-        fn = _lib.resolve(self.lib, name)
-        chamfer_gates_dict = _chamfer_gates_of(chamfer_gates)
-        g = chamfer_gate_block(chamfer_gates_dict)
-        if point_normals is not None:
-            if tuple(point_normals.shape) != (N, S, 3) or point_normals.device != dev or point_normals.dtype != torch.float32:
-                raise SmalfitError("point_normals must be float32 (N, S, 3) on the device of lbs_verts")
-            g.point_normals = _ptr(point_normals)
-        if point_boundary is not None:
-            if tuple(point_boundary.shape) != (N, S) or point_boundary.device != dev or point_boundary.dtype != torch.uint8:
-                raise SmalfitError("point_boundary must be uint8 (N, S) on the device of lbs_verts")
-            g.point_boundary = C.c_void_p(point_boundary.data_ptr())
-        masks = (("point_kept", (N, S), torch.uint8), ("vert_kept", (N, V), torch.uint8), ("point_nn", (N, S), torch.int32),
-                 ("vert_nn", (N, V), torch.int32)) if float(w[0]) > 0 and S > 0 and chamfer_gates_on(chamfer_gates_dict) else ()
-        for k, shape, dt in (("kept", (N, 2), torch.int32),) + masks:
-            if k not in o or tuple(o[k].shape) != shape or o[k].dtype != dt:
-                o[k] = torch.zeros(shape, dtype=dt, device=dev)
-            setattr(g, k, C.c_void_p(o[k].data_ptr()))
-        targets = getattr(targets, "_dev", targets)
-        args = (self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans), _ptr(deform_verts), _ptr(points), S, w.ctypes.data,
-                _ptr(o["verts"]), _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"]),
-                targets.handle if targets is not None else None, C.byref(g))
-        check(fn(*args, C.byref(rb)) if rb is not None else fn(*args), name)
+            tail = (targets.handle if targets is not None else None,) + _refs(blocks)
+        check(_lib.resolve(self.lib, name)(self.handle, _stream(), N, _ptr(lbs_verts), _ptr(trans), _ptr(deform_verts), _ptr(points), S,
+                                           w.ctypes.data, _ptr(o["verts"]), _ptr(o["losses"]), _ptr(o["dverts"]), _ptr(o["dtrans"]),
+                                           *tail), name)
         return o
 
     def score(self, verts, targets, points=None, thresholds=()):
@@ -762,9 +748,7 @@ class MeshObjective:
         Geman-McClure kernel on the kept matches; the chamfer scales of the dict are not read here.  Adds surface_weight_sums
         (N,2) and, for a direction that ran with its scale on, point_weights (N,S) / vert_weights (N,V); losses, rows and the
         gradient then carry the robust values, the residuals stay geometric."""
-        name = ("smalfit_mesh_surface_eval_robust" if robust is not None else
-                "smalfit_mesh_surface_eval_gated" if gates is not None else "smalfit_mesh_surface_eval")
-        fn = _lib.resolve(self.lib, name)
+        fn = _lib.resolve(self.lib, _narrowest(_SURFACE_ENTRY_POINTS, gates, robust)[0])
         targets = getattr(targets, "_dev", targets)
         if targets is not None and not isinstance(targets, MeshTargets):
             raise SmalfitError("targets must be the MeshTargets the meshes are fitted to")
@@ -782,62 +766,69 @@ class MeshObjective:
         a = _lib.SurfaceTermArgs()
         a.num_meshes, a.w_point_surface, a.w_vert_surface = N, float(w_point_surface), float(w_vert_surface)
         a.verts, a.points, a.num_points = _ptr(verts), _ptr(points), S
-        out = {"losses": torch.empty(3, device=dev), "rows": torch.empty(N, 2, device=dev),
-               "dverts": torch.empty(N, V, 3, device=dev), "dtrans": torch.empty(N, 3, device=dev)}
-        a.losses, a.rows, a.dverts, a.dtrans = (_ptr(out[k]) for k in ("losses", "rows", "dverts", "dtrans"))
+        out = {}
+        new = lambda k, shape, dtype=torch.float32, zero=False: _out_tensor(out, k, shape, dtype, dev, zero=zero)
+        a.losses, a.rows, a.dverts, a.dtrans = (_ptr(new(k, shape)) for k, shape in (("losses", (3,)), ("rows", (N, 2)), ("dverts", (N, V, 3)),
+                                                                                    ("dtrans", (N, 3))))
+        point_dir, vert_dir = w_point_surface > 0 and points is not None, w_vert_surface > 0
         if correspondences:
-            if w_point_surface > 0 and points is not None:
-                out["point_face"] = torch.empty(N, S, dtype=torch.int32, device=dev)
-                out["point_bary"] = torch.empty(N, S, 3, device=dev)
-                out["point_residual"] = torch.empty(N, S, 3, device=dev)
-                a.point_face, a.point_bary = C.c_void_p(out["point_face"].data_ptr()), _ptr(out["point_bary"])
-                a.point_residual = _ptr(out["point_residual"])
-            if w_vert_surface > 0:
-                out["vert_face"] = torch.empty(N, V, dtype=torch.int32, device=dev)
-                out["vert_bary"] = torch.empty(N, V, 3, device=dev)
-                out["vert_residual"] = torch.empty(N, V, 3, device=dev)
-                a.vert_face, a.vert_bary = C.c_void_p(out["vert_face"].data_ptr()), _ptr(out["vert_bary"])
-                a.vert_residual = _ptr(out["vert_residual"])
-        th = targets.handle if targets is not None else None
-        rb = None
+            if point_dir:
+                a.point_face, a.point_bary = C.c_void_p(new("point_face", (N, S), torch.int32).data_ptr()), _ptr(new("point_bary", (N, S, 3)))
+                a.point_residual = _ptr(new("point_residual", (N, S, 3)))
+            if vert_dir:
+                a.vert_face, a.vert_bary = C.c_void_p(new("vert_face", (N, V), torch.int32).data_ptr()), _ptr(new("vert_bary", (N, V, 3)))
+                a.vert_residual = _ptr(new("vert_residual", (N, V, 3)))
+        # the blocks that are on, each with its outputs attached
+        g = rb = None
         if robust is not None:
             rd = _robust_of(robust)
             rb = robust_block(rd)
-            out["surface_weight_sums"] = torch.zeros(N, 2, device=dev)
-            rb.surface_weight_sums = _ptr(out["surface_weight_sums"])
-            if w_point_surface > 0 and points is not None and _scale_on(rd["sigma_surface_point"]):
-                out["point_weights"] = torch.zeros(N, S, device=dev)
-                rb.surface_point_weights = _ptr(out["point_weights"])
-            if w_vert_surface > 0 and _scale_on(rd["sigma_surface_vert"]):
-                out["vert_weights"] = torch.zeros(N, V, device=dev)
-                rb.surface_vert_weights = _ptr(out["vert_weights"])
-        if gates is None:
-            if rb is not None:
-                check(fn(self.handle, th, _stream(), C.byref(a), None, C.byref(rb)), name)
-                return out
-            check(fn(self.handle, th, _stream(), C.byref(a)), "smalfit_mesh_surface_eval")
-            return out
-        g = surface_gate_block(gates)
-        if point_normals is not None:
-            if tuple(point_normals.shape) != (N, S, 3) or point_normals.device != dev:
-                raise SmalfitError("point_normals must be (num_meshes, S, 3) on the device of verts")
-            g.point_normals = _ptr(point_normals)
-        out["kept"] = torch.zeros(N, 2, dtype=torch.int32, device=dev)
-        g.kept = C.c_void_p(out["kept"].data_ptr())
-        if w_point_surface > 0 and points is not None:
-            out["point_kept"] = torch.empty(N, S, dtype=torch.uint8, device=dev)
-            g.point_kept = C.c_void_p(out["point_kept"].data_ptr())
-        if w_vert_surface > 0:
-            out["vert_kept"] = torch.empty(N, V, dtype=torch.uint8, device=dev)
-            g.vert_kept = C.c_void_p(out["vert_kept"].data_ptr())
-            if g.min_cos_vert > -1.0:
-                out["vert_normals"] = torch.empty(N, V, 3, device=dev)
-                g.vert_normals = _ptr(out["vert_normals"])
-        if rb is not None:
-            check(fn(self.handle, th, _stream(), C.byref(a), C.byref(g), C.byref(rb)), name)
-            return out
-        check(fn(self.handle, th, _stream(), C.byref(a), C.byref(g)), "smalfit_mesh_surface_eval_gated")
+            rb.surface_weight_sums = _ptr(new("surface_weight_sums", (N, 2), zero=True))
+            if point_dir and _scale_on(rd["sigma_surface_point"]):
+                rb.surface_point_weights = _ptr(new("point_weights", (N, S), zero=True))
+            if vert_dir and _scale_on(rd["sigma_surface_vert"]):
+                rb.surface_vert_weights = _ptr(new("vert_weights", (N, V), zero=True))
+        if gates is not None:
+            g = surface_gate_block(gates)
+            if point_normals is not None:
+                if tuple(point_normals.shape) != (N, S, 3) or point_normals.device != dev:
+                    raise SmalfitError("point_normals must be (num_meshes, S, 3) on the device of verts")
+                g.point_normals = _ptr(point_normals)
+            g.kept = C.c_void_p(new("kept", (N, 2), torch.int32, zero=True).data_ptr())
+            if point_dir:
+                g.point_kept = C.c_void_p(new("point_kept", (N, S), torch.uint8).data_ptr())
+            if vert_dir:
+                g.vert_kept = C.c_void_p(new("vert_kept", (N, V), torch.uint8).data_ptr())
+                if g.min_cos_vert > -1.0:
+                    g.vert_normals = _ptr(new("vert_normals", (N, V, 3)))
+        # one call, through the narrowest entry point whose signature holds the last block that is on
+        name, blocks = _narrowest(_SURFACE_ENTRY_POINTS, g, rb)
+        check(fn(self.handle, targets.handle if targets is not None else None, _stream(), C.byref(a), *_refs(blocks)), name)
         return out
+
+
+# the entry points of an evaluation by the number of opt-in blocks their signatures hold: none, the gate block, the robust block
+_EVAL_ENTRY_POINTS = ("smalfit_mesh_objective_eval", "smalfit_mesh_objective_eval_gated", "smalfit_mesh_objective_eval_robust")
+_SURFACE_ENTRY_POINTS = ("smalfit_mesh_surface_eval", "smalfit_mesh_surface_eval_gated", "smalfit_mesh_surface_eval_robust")
+
+
+def _narrowest(names, *blocks):
+    """-> (the narrowest entry point of `names` whose signature holds the last block that is not None, the blocks it takes: a
+    library built before the later symbols still serves the calls it could serve)"""
+    while blocks and blocks[-1] is None:
+        blocks = blocks[:-1]
+    return names[len(blocks)], blocks
+
+
+def _refs(blocks):
+    return tuple(C.byref(b) if b is not None else None for b in blocks)
+
+
+def _out_tensor(o, key, shape, dtype, dev, zero=False):
+    """o[key] when it has this shape and dtype, else a new tensor (zeroed on request) put there; -> the tensor"""
+    if key not in o or tuple(o[key].shape) != tuple(shape) or o[key].dtype != dtype:
+        o[key] = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=dev)
+    return o[key]
 
 
 SURFACE_GATE_KEYS = ("max_dist_point", "max_dist_vert", "min_cos_point", "min_cos_vert", "reject_boundary")

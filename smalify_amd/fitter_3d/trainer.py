@@ -126,6 +126,12 @@ class SMALParamGroup:
         return iter(out)
 
 
+# smalfit_fit3d_step and its wider forms, by the number of opt-in blocks their signatures hold behind the step's own: the surface
+# block, its gate block, the chamfer gate block, the robust block
+_STEP_ENTRY_POINTS = ("smalfit_fit3d_step", "smalfit_fit3d_step_surface", "smalfit_fit3d_step_gated", "smalfit_fit3d_step_partial",
+                      "smalfit_fit3d_step_robust")
+
+
 class Stage:
     """One stage of optimisation (trainer.py:157-262)."""
 
@@ -353,51 +359,21 @@ class Stage:
         self._t += 1
         a.adam_t = self._t
         dev_targets = getattr(self.target_meshes, "_dev", self.target_meshes)
-        if self._robust_applies():
-            # (every block that is on rides along, as in the calls below; the robust block needs none of them)
-            sf = gate = cgate = None
-            if self.surface_on:
-                sf = self._surface_block()
-                sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
-                gate = self._gate_block() if self.gates_on else None
-            if self._chamfer_gated():
-                cgate = self._chamfer_gate_block()
-            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_robust")
-            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a),
-                         C.byref(sf) if sf is not None else None, C.byref(gate) if gate is not None else None,
-                         C.byref(cgate) if cgate is not None else None, C.byref(self._robust_block())), "smalfit_fit3d_step_robust")
-            self._last_points = self._points
-            return self._step_total[0] if sf is not None else self._buffers["losses"][4]
-        if self._chamfer_gated():
-            # (the surface block and its gate block ride along when they are on; a chamfer gate block needs neither)
-            sf = gate = None
-            if self.surface_on:
-                sf = self._surface_block()
-                sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
-                gate = self._gate_block() if self.gates_on else None
-            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_partial")
-            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a),
-                         C.byref(sf) if sf is not None else None, C.byref(gate) if gate is not None else None,
-                         C.byref(self._chamfer_gate_block())), "smalfit_fit3d_step_partial")
-            self._last_points = self._points
-            return self._step_total[0] if sf is not None else self._buffers["losses"][4]
-        if not self.surface_on:
-            eng.check(e.lib.smalfit_fit3d_step(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a)),
-                      "smalfit_fit3d_step")
-            self._last_points = self._points
-            return self._buffers["losses"][4]
-        sf = self._surface_block()
-        sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
-        if self.gates_on:
-            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_gated")
-            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a), C.byref(sf),
-                         C.byref(self._gate_block())), "smalfit_fit3d_step_gated")
-        else:
-            fn = _lib.resolve(e.lib, "smalfit_fit3d_step_surface")
-            eng.check(fn(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a), C.byref(sf)),
-                      "smalfit_fit3d_step_surface")
+        # the blocks that are on, in the order the entry points take them; the surface gates ride on the surface block
+        sf = gate = None
+        if self.surface_on:
+            sf = self._surface_block()
+            sf.w_point_surface, sf.w_vert_surface = (self.surface_weights[k] for k in _SURFACE_ORDER)
+            gate = self._gate_block() if self.gates_on else None
+        cgate = self._chamfer_gate_block() if self._chamfer_gated() else None
+        rb = self._robust_block() if self._robust_applies() else None
+        # one call, through the narrowest entry point whose signature holds the last block that is on
+        name, blocks = eng._narrowest(_STEP_ENTRY_POINTS, sf, gate, cgate, rb)
+        eng.check(_lib.resolve(e.lib, name)(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a),
+                                            *eng._refs(blocks)), name)
         self._last_points = self._points
-        return self._step_total[0]          # the grand total, formed by the step: the four terms + the surface term
+        # with the surface term the grand total is formed by the step: the four terms + the surface term
+        return self._step_total[0] if sf is not None else self._buffers["losses"][4]
 
     def step_unfused(self, epoch):
         """the same iteration as five separate C-ABI calls + one smalfit_adam_step per parameter; leaves the gradients

@@ -1,5 +1,5 @@
 // The host side of the gated chamfer term as C functions for tests/test_chamfer_gate_cpu.py and tests/test_gpu_chamfer_gate.py:
-// mesh3d_math.h (GatedScanPoint, nearest_scan_gated, nearest_merge, gated_match, the compatibility predicate) and smalfit_plan.h
+// mesh3d_math.h (GatedScanPoint, quarter_span, scan_records, nearest_merge, chamfer_match, the compatibility predicate) and smalfit_plan.h
 // (the gate block's rules, its plan, the staging constants).  Built by g++ (tests/host_chamfer_gate.py), no HIP: the kernels and
 // this shim evaluate the same code.
 #include <algorithm>
@@ -18,7 +18,7 @@ static_assert(sizeof(GatedScanPoint) == kChamGateRecordBytes, "smalfit_plan.h si
 extern "C" {
 // every query against the scanned set as mesh3d_chamfer_kernel<ROLE, true> does it: the set staged kChamGateChunk records at a
 // time, every chunk split in quarters over four waves, each wave with its own running minimum; the four meet through nearest_merge
-// and gated_match decides once.  qn / xn may be NULL (use_cos == 0: nothing is read, c = -inf), xb NULL (no boundary rule), owner
+// and chamfer_match<true, false> decides once.  qn / xn may be NULL (use_cos == 0: nothing is read, c = -inf), xb NULL (no boundary rule), owner
 // NULL (no gather).  index: the winner or -1; kept; d2: the winner's d^2 (+inf when none); gather (Q,3): sum (q - x_j) over owner[j] == query
 void hcg_scan(int num_queries, const float* q, const float* qn, int num_scanned, const float* x, const float* xn,
               const unsigned char* xb, const int* owner, int use_cos, float c, float tau2, int* index, unsigned char* kept, float* d2,
@@ -45,18 +45,17 @@ void hcg_scan(int num_queries, const float* q, const float* qn, int num_scanned,
         s.tag = gated_tag(base + j, xb ? xb[base + j] : 0);
         sp[j] = s;
       }
-      const int per = (cnt + 3) >> 2;
       for (int w = 0; w < 4; ++w) {
-        const int b = std::min(w * per, cnt), e = std::min(b + per, cnt);
-        if (owner) nearest_scan_gated<true>(q[3 * i], q[3 * i + 1], q[3 * i + 2], ux, uy, uz, cc, sp.data(), b, e, best[w], tag[w], i, g[w]);
-        else nearest_scan_gated<false>(q[3 * i], q[3 * i + 1], q[3 * i + 2], ux, uy, uz, cc, sp.data(), b, e, best[w], tag[w], i, g[w]);
+        const Span s = quarter_span(w, cnt);
+        if (owner) scan_records<true, false>(q[3 * i], q[3 * i + 1], q[3 * i + 2], ux, uy, uz, cc, sp.data(), s.b, s.e, base, best[w], tag[w], i, g[w], nullptr);
+        else scan_records<false, false>(q[3 * i], q[3 * i + 1], q[3 * i + 2], ux, uy, uz, cc, sp.data(), s.b, s.e, base, best[w], tag[w], i, g[w], nullptr);
       }
     }
     for (int w = 1; w < 4; ++w) {
       nearest_merge(best[0], tag[0], best[w], tag[w]);
       for (int k = 0; k < 3; ++k) g[0][k] += g[w][k];
     }
-    const GatedMatch m = gated_match(best[0], tag[0], tau2, xb != nullptr);
+    const ChamferMatch m = chamfer_match<true, false>(best[0], tag[0], tau2, xb != nullptr, 0.f, true);
     index[i] = m.index;
     kept[i] = m.kept ? 1 : 0;
     d2[i] = best[0];

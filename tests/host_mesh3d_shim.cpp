@@ -35,11 +35,10 @@ void chamfer_query(const float q[3], const float* others, int no, const int* own
       sp[i].z = others[3 * (size_t)(base + i) + 2];
       sp[i].owner = owner ? owner[base + i] : 0;
     }
-    const int per = (cnt + 3) >> 2;
     for (int w = 0; w < kSlices; ++w) {
-      const int b = std::min(w * per, cnt), e = std::min(b + per, cnt);
-      if (owner) nearest_scan<true>(q[0], q[1], q[2], sp.data(), b, e, base, sb[w], si[w], self, sg[w]);
-      else nearest_scan<false>(q[0], q[1], q[2], sp.data(), b, e, base, sb[w], si[w], self, sg[w]);
+      const Span s = quarter_span(w, cnt);
+      if (owner) nearest_scan<true>(q[0], q[1], q[2], sp.data(), s.b, s.e, base, sb[w], si[w], self, sg[w]);
+      else nearest_scan<false>(q[0], q[1], q[2], sp.data(), s.b, s.e, base, sb[w], si[w], self, sg[w]);
     }
   }
   best = sb[0];
@@ -104,16 +103,18 @@ int hm3_eval(int V, int F, const int* faces, int N, const float* lbs_verts, cons
         float best, g[3];
         int bi;
         chamfer_query(pn + 3 * i, vn, V, nullptr, i, best, bi, g);
-        nn[(size_t)n * S + i] = bi;
-        scx += best;
+        const ChamferMatch m = chamfer_match<false, false>(best, bi, INFINITY, 0, 0.f, true);
+        nn[(size_t)n * S + i] = m.index;
+        scx += m.rho;
       }
       for (int v = 0; v < V; ++v) {
         float best, g[3];
         int bi;
         chamfer_query(vn + 3 * v, pn, S, nn.data() + (size_t)n * S, v, best, bi, g);
-        scy += best;
+        const ChamferMatch m = chamfer_match<false, false>(best, bi, INFINITY, 0, 0.f, true);
+        scy += m.rho;
         const float cy = wc * 2.0f / ((float)V * (float)N), cx = wc * 2.0f / ((float)S * (float)N);
-        for (int k = 0; k < 3; ++k) gcham[((size_t)n * V + v) * 3 + k] = cy * (vn[3 * v + k] - pn[3 * bi + k]) + cx * g[k];
+        chamfer_vertex_grad(cy, cx, vn + 3 * v, pn, S, m.kept, m.index, g, gcham.data() + ((size_t)n * V + v) * 3);
       }
     }
     for (int v = 0; v < V; ++v) {

@@ -37,6 +37,8 @@ MODEL_TABLES = ("vt", "sd", "pd", "w_j", "w_val", "wc_off", "wc_v", "wc_val", "j
                 "parents", "faces_int", "vf_off", "vf_idx", "sidx")
 FIT3D_TENSORS = ("betas", "global_rot", "joint_rot", "trans", "deform_verts")           # the order of kFit3dParams
 FIT3D_POINTS = ("none", "sample_to_objective", "sample_to_caller", "callers", "callers_copied")   # Fit3dPoints
+RIDER_SOURCES = ("callers", "drawn")                                  # RiderSource
+VERT_NORMALS_DESTS = ("objective", "surface_gate_block")              # VertNormalsDest
 # Fit3dFacts: an engine of 4 frames on the stand-in's dimensions, an objective over the same mesh, two target meshes
 FIT3D_FACT_NAMES = ("max_frames", "model_verts", "model_betas", "max_meshes", "max_points", "objective_verts", "targets", "target_meshes")
 FIT3D_FACTS = dict(max_frames=4, model_verts=3889, model_betas=41, max_meshes=4, max_points=64, objective_verts=3889, targets=True,
@@ -74,6 +76,7 @@ class Plan:
         lib.hp_mesh_weight.restype = C.c_float
         lib.hp_mesh_weight.argtypes = [C.c_float]
         lib.hp_mesh_points.argtypes = [C.c_float, C.c_int]
+        lib.hp_plan_fit3d_riders.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]
         out = (C.c_int * 8)()
         lib.hp_constants(out)
         (self.BETA_GROUPS, self.MAX_IMAGE_SIZE, self.MESH_QUERIES, self.MESH_THREADS, self.HEAD_PRIOR_FRAMES, self.CALLER,
@@ -244,6 +247,22 @@ class Plan:
         out["seg"] = [dict(zip(("tensor", "count", "row_len", "g_stride", "g_offset", "block0"), segs[6 * s:6 * s + 6])) for s in range(out.pop("nseg"))]
         for sg in out["seg"]:
             sg["tensor"] = FIT3D_TENSORS[sg["tensor"]]
+        return out
+
+    def plan_fit3d_riders(self, surface, surface_gates, chamfer_gates, w_chamfer, points):
+        """Fit3dRiders as a dict; the blocks are ctypes structs of smalify_amd._lib or None, points a name of FIT3D_POINTS;
+        the sources by name (RIDER_SOURCES), vert_normals by name (VERT_NORMALS_DESTS)"""
+        ref = lambda b: C.byref(b) if b is not None else None
+        ints = (C.c_int * 7)()
+        self.lib.hp_plan_fit3d_riders(ref(surface), ref(surface_gates), ref(chamfer_gates), float(w_chamfer),
+                                      FIT3D_POINTS.index(points), ints)
+        out = dict(zip(("draw_normals", "draw_boundary", "surface_normals", "chamfer_normals", "chamfer_boundary", "vert_normals",
+                        "surface_reuses_vert_normals"), ints))
+        for k in ("draw_normals", "draw_boundary", "surface_reuses_vert_normals"):
+            out[k] = bool(out[k])
+        for k in ("surface_normals", "chamfer_normals", "chamfer_boundary"):
+            out[k] = RIDER_SOURCES[out[k]]
+        out["vert_normals"] = VERT_NORMALS_DESTS[out["vert_normals"]]
         return out
 
     def fit3d_constants(self):

@@ -255,6 +255,15 @@ void hp_plan_fit3d(const smalfit_fit3d_args* a, int model_verts, int* ints8, int
     for (int i = 0; i < 6; ++i) segs30[s * 6 + i] = w[i];
   }
 }
+// plan_fit3d_riders (any block may be NULL; points: Fit3dPoints) -> ints7: draw_normals, draw_boundary, surface_normals,
+// chamfer_normals, chamfer_boundary, vert_normals, surface_reuses_vert_normals
+void hp_plan_fit3d_riders(const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate, const smalfit_chamfer_gate_args* cg,
+                          float w_chamfer, int points, int* ints7) {
+  const Fit3dRiders r = plan_fit3d_riders(sf, gate, cg, w_chamfer, (Fit3dPoints)points);
+  const int v[7] = {r.draw_normals, r.draw_boundary, (int)r.surface_normals, (int)r.chamfer_normals, (int)r.chamfer_boundary,
+                    (int)r.vert_normals, r.surface_reuses_vert_normals};
+  for (int i = 0; i < 7; ++i) ints7[i] = v[i];
+}
 // [kFit3dParams, sizeof(Fit3dAdamSeg), sizeof(Fit3dAdamArgs), sizeof(smalfit_fit3d_args)]
 void hp_fit3d_constants(int* out4) {
   out4[0] = kFit3dParams; out4[1] = (int)sizeof(Fit3dAdamSeg); out4[2] = (int)sizeof(Fit3dAdamArgs); out4[3] = (int)sizeof(smalfit_fit3d_args);

@@ -45,10 +45,9 @@ int hrb_weighted_gather(const float* q, int self, int num_points, const float* x
       sp[j] = ScanPoint{x[3 * (size_t)(base + j)], x[3 * (size_t)(base + j) + 1], x[3 * (size_t)(base + j) + 2], owner[base + j]};
       sw[j] = wt[base + j];
     }
-    const int per = (cnt + 3) >> 2;
     for (int w = 0; w < 4; ++w) {
-      const int b = std::min(w * per, cnt), e = std::min(b + per, cnt);
-      nearest_scan<true, true>(q[0], q[1], q[2], sp.data(), b, e, base, best[w], idx[w], self, g[w], sw.data());
+      const Span s = quarter_span(w, cnt);
+      scan_records<true, true>(q[0], q[1], q[2], 0.f, 0.f, 0.f, 0.f, sp.data(), s.b, s.e, base, best[w], idx[w], self, g[w], sw.data());
     }
   }
   for (int w = 1; w < 4; ++w) {

@@ -650,3 +650,46 @@ def test_mesh_launch_grids_on_both_sides_of_256(plan):
     assert [plan.mesh_sample_grid(s, 3) for s in (1, 255, 256, 257, 512, 513, 3000)] == [(1, 3), (1, 3), (1, 3), (2, 3), (2, 3), (3, 3), (12, 3)]
     assert [plan.fit3d_adam_blocks(c) for c in (1, 255, 256, 257, 511, 512, 513)] == [1, 1, 1, 2, 2, 2, 3]
     assert [plan.frame_betas_grid(m) for m in (1, 3, 256, 257)] == [1, 3, 256, 257]
+
+
+def test_plan_fit3d_riders_every_switch(plan):
+    """what the opt-in blocks of a step share, over every combination of: each surface direction, min_cos_point / min_cos_vert of
+    both gate blocks, the chamfer boundary rule, the chamfer term itself, a vert_normals output, the caller's points against
+    sampled ones.  The rule beside it is written from the step's description: normals and boundary bytes are drawn with the
+    points only in a step that samples them, when a compatibility test that reads them (each chamfer test reads both sets) or the
+    boundary rule is on in a term that runs; the vertex normals go to the surface gate block's output when its own vertex test
+    is on and asks for them; the surface term reuses them when the chamfer gates gathered them"""
+    import itertools
+    checked = 0
+    for wp, wv, scp, scv, ccp, ccv, bound, wc, out, points in itertools.product(
+            (0.0, 0.5), (0.0, 0.25), (False, True), (False, True), (False, True), (False, True), (False, True), (0.0, 1.0),
+            (False, True), ("callers", "callers_copied", "sample_to_caller", "sample_to_objective")):
+        sf = _lib.SurfaceTermArgs()
+        sf.w_point_surface, sf.w_vert_surface = wp, wv
+        sg = _lib.SurfaceGateArgs()
+        sg.min_cos_point, sg.min_cos_vert = (0.3 if scp else -1.0), (0.3 if scv else -1.0)
+        if out and scv and wv > 0:                       # (refused otherwise: vert_normals given without min_cos_vert)
+            sg.vert_normals = 1 << 20
+        cg = _lib.ChamferGateArgs()
+        cg.min_cos_point, cg.min_cos_vert, cg.reject_boundary = (0.3 if ccp else -1.0), (0.3 if ccv else -1.0), int(bound)
+        sampled = points.startswith("sample")
+        s_cos_point, s_cos_vert = wp > 0 and scp, wv > 0 and scv
+        c_cos, c_bound = wc > 0 and (ccp or ccv), wc > 0 and bound
+        src = lambda on: "drawn" if sampled and on else "callers"
+        want = dict(draw_normals=bool(sampled and (s_cos_point or c_cos)), draw_boundary=bool(sampled and c_bound),
+                    surface_normals=src(s_cos_point), chamfer_normals=src(c_cos), chamfer_boundary=src(c_bound),
+                    vert_normals="surface_gate_block" if s_cos_vert and out else "objective",
+                    surface_reuses_vert_normals=bool(c_cos and s_cos_vert))
+        assert plan.plan_fit3d_riders(sf, sg, cg, wc, points) == want, (wp, wv, scp, scv, ccp, ccv, bound, wc, out, points)
+        checked += 1
+    assert checked == 2 ** 9 * 4
+    # absent blocks are blocks with everything off; a gate block without its surface block's weights gates nothing
+    off = dict(draw_normals=False, draw_boundary=False, surface_normals="callers", chamfer_normals="callers", chamfer_boundary="callers",
+               vert_normals="objective", surface_reuses_vert_normals=False)
+    assert plan.plan_fit3d_riders(None, None, None, 1.0, "sample_to_caller") == off
+    sf, sg = _lib.SurfaceTermArgs(), _lib.SurfaceGateArgs()
+    sg.min_cos_point = sg.min_cos_vert = 0.5
+    assert plan.plan_fit3d_riders(sf, sg, None, 1.0, "sample_to_caller") == off
+    sf.w_point_surface = 1.0
+    assert plan.plan_fit3d_riders(sf, None, None, 1.0, "sample_to_caller") == off
+    assert plan.plan_fit3d_riders(sf, sg, None, 0.0, "sample_to_objective") == dict(off, draw_normals=True, surface_normals="drawn")

@@ -55,12 +55,16 @@ def test_the_rules_are_the_kernels():
     assert "__launch_bounds__(256) void mesh3d_chamfer_kernel(Mesh3dArgs a)" in k
     assert "const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);" in k
     assert "const int qi = blockIdx.x * kChamQueries + lane;" in k
-    assert re.search(r"for \(int base = 0; base < no; base \+= kChamChunk\) \{\s*const int cnt = min\(kChamChunk, no - base\);", k)
-    assert "const int per = (cnt + 3) >> 2;" in k
-    assert "const int b = min(w * per, cnt), e = min(b + per, cnt);" in k
+    # one staging loop: the ungated kernel's chunk is kChamChunk, a wave scans quarter_span(w, cnt) of it
+    assert "constexpr int kChunk = GATED ? kChamGateChunk : kChamChunk;" in k
+    assert re.search(r"for \(int base = 0; base < no; base \+= kChunk\) \{\s*const int cnt = min\(kChunk, no - base\);", k)
+    assert len(re.findall(r"for \(int base = 0; base < no;", k)) == 1
+    assert "const Span sp = quarter_span(w, cnt);" in k
+    m = _src("mesh3d_math.h")
+    assert re.search(r"Span quarter_span\(int w, int cnt\) \{\s*const int per = \(cnt \+ 3\) >> 2;\s*"
+                     r"const int b = w \* per < cnt \? w \* per : cnt;\s*return Span\{b, b \+ per < cnt \? b \+ per : cnt\};", m)
     assert re.search(r"for \(int s = 1; s < 4; \+\+s\) \{\s*nearest_merge\(best, bidx, sd\[s\]\[lane\], si\[s\]\[lane\]\);", k)
     # the tie rule: strict '<' over ascending indices, lexicographic merge
-    m = _src("mesh3d_math.h")
     assert re.search(r"for \(int j = begin; j < end; \+\+j\) \{.*?if \(d2 < best\) \{\s*best = d2;\s*best_idx = index_base \+ j;", m, re.S)
     assert "if (d2 < best || (d2 == best && idx < best_idx)) {" in m
     assert "lowest index" in m
