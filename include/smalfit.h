@@ -92,7 +92,7 @@ int smalfit_engine_reset_raster_cache(smalfit_engine* engine, void* stream);
 #define SMALFIT_SEC_RASTER_BWD 3     /* raster_bwd_kernel alone                                   */
 #define SMALFIT_SEC_LBS_BWD 4        /* vertex, mid-stage (dA, pose-blend, shape-blend) and chain adjoints */
 #define SMALFIT_SEC_RASTER_RESOLVE 5 /* raster_resolve_kernel + raster_band_kernel                  */
-#define SMALFIT_SEC_RASTER_BBOX 6    /* face_bbox_kernel (per-face pixel boxes and records)        */
+#define SMALFIT_SEC_RASTER_BBOX 6    /* no launch any more: raster_sweep_kernel forms the boxes    */
 int smalfit_engine_profile_begin(smalfit_engine* engine, int max_evals, int stride);
 int smalfit_engine_profile_end(smalfit_engine* engine, void* stream, float* ms_total, int* counts);
 

@@ -9,10 +9,11 @@
 // pixels does 4.6x more lane evaluations than letting each face walk its own blur-expanded pixel box; one global
 // atomic per candidate is capped at ~50 G/s (memory-side on this multi-XCD part); per-pixel candidate lists in HBM
 // mean 35-50 M scattered 8-byte stores.  Hence:
-//   face_bbox  per-face pixel box + the face's 64-byte record (edge vectors, reciprocals, depth plane), the union box of every
-//              8 consecutive faces, the frame's reference depth and active pixel region.  Faces are Morton-ordered
-//              once at model creation, so consecutive faces are screen-space neighbours in any pose.
-//   sweep      block = 32 consecutive faces, 16 lanes per face walking the box row-major.  Per pixel two cached
+//   sweep      block = 32 consecutive faces.  Prologue: per-face pixel box + the face's 64-byte record (edge vectors, reciprocals,
+//              depth plane) from the projected vertices, the union box of every 8 consecutive faces, the frame's reference
+//              depth; riders: the frame's active pixel region.  Faces are Morton-ordered once at model creation, so
+//              consecutive faces are screen-space neighbours in any pose.  (Until it was folded in: a launch of its own, face_bbox.)
+//              Then 16 lanes per face walking the box row-major.  Per pixel two cached
 //              depth bounds lo <= hi: candidates <= lo go into ONE packed 64-bit integer per pixel
 //              (count << 50 | sum of -log2(1 - p) in 2^-24 fixed point; 32x32-pixel LDS window, one global atomic per
 //              touched pixel), candidates in (lo, hi] into the pixel's band list (<= 64 entries, staged per wave),
@@ -121,9 +122,9 @@ struct SilTarget {
 // share an L2.  Only speed depends on the placement (HIP promises none); results never do.
 //   grid.x = xcd_grid(blocks_per_frame, M) of smalfit_plan.h;   xcd_block(blocks_per_frame, n, bx) -> frame n (may be >= M: exit), block bx
 __device__ __forceinline__ void xcd_block_of(int b /*linear workgroup id; b % 8 must be the workgroup's blockIdx.x % 8*/, int blocks_per_frame, int& n, int& bx) {
-  const int xcd = b & 7, slot = b >> 3;
-  n = (slot / blocks_per_frame) * 8 + xcd;
-  bx = slot - (slot / blocks_per_frame) * blocks_per_frame;
+  const XcdBlock x = xcd_block_at(b, blocks_per_frame);
+  n = x.n;
+  bx = x.bx;
 }
 __device__ __forceinline__ void xcd_block(int blocks_per_frame, int& n, int& bx) { xcd_block_of((int)blockIdx.x, blocks_per_frame, n, bx); }
 
@@ -176,11 +177,12 @@ __device__ __forceinline__ float prob_fast(float d) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(d * (1.4426950408889634f / kSigma)));
 }
 
-// The face record kernels share: face_bbox_kernel evaluates make_face_rec ONCE per face and evaluation and stores the 16
-// floats the per-pixel maths reads (64 bytes, one cache line); sweep, selection and backward load it instead of rebuilding
-// it from the projected vertices (four reciprocals and ~40 instructions -- per covering face and PIXEL in the selection,
-// per lane at the head of every short-lived wave of the backward gather).  One definition also means the kernels cannot
-// disagree on a face's edge constants.  The degenerate-edge offsets t0 are implied: il == 0 exactly when the edge is degenerate.
+// The face record kernels share: raster_sweep_kernel's prologue evaluates make_face_rec ONCE per face and evaluation, keeps the
+// 16 floats the per-pixel maths reads (64 bytes, one cache line) in LDS for its own pixel loop and stores them; selection and
+// backward load them instead of rebuilding them from the projected vertices (four reciprocals and ~40 instructions -- per
+// covering face and PIXEL in the selection, per lane at the head of every short-lived wave of the backward gather).  One
+// definition also means the kernels cannot disagree on a face's edge constants.  The degenerate-edge offsets t0 are implied:
+// il == 0 exactly when the edge is degenerate.
 constexpr int kRecVecs = 4;               // float4 per face record
 __device__ __forceinline__ void store_face_rec(float4* __restrict__ o, const FaceRec& r) {
   o[0] = make_float4(r.ax, r.ay, r.e1x, r.e1y);
@@ -200,131 +202,80 @@ __device__ __forceinline__ void load_face_rec(const float4* __restrict__ fr, Fac
   unpack_face_rec(a, b, c, d, r);
 }
 
-// 5a: per-face validity, conservative pixel box, packed record; union box per 32 faces
-__global__ void __launch_bounds__(256)
-face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2* __restrict__ fbox,
-                 float4* __restrict__ frec /*[M][F][kRecVecs]: see store_face_rec*/, int4* __restrict__ brect /*[M][ceil(F/32)]*/,
-                 float* __restrict__ zc /*[M]*/, int* __restrict__ frect /*[M][4]: S - x0, x1 + 1, S - y0, y1 + 1 of the active region; 0 = empty*/,
-                 int* __restrict__ qcount /*[0..2]: select / band queue lengths, pixels resolve sent to select; [8..15]: the selection's tickets; reset here*/,
-                 const float* __restrict__ jverts, float* __restrict__ joints_out /*[M][41][3] or null: 41 M extra workgroups regress the
-                 posed joints (joints_block) -- independent of the boxes, latency-bound, and otherwise a launch of its own*/) {
-  // grid: [frame riders, a multiple of 8] [face workgroups, frame n on XCD n % 8] [joint riders]  (the joint riders are short:
-  // moving them in front of the face workgroups, as the resolve kernel's loss riders were, measured 0.4 % slower)
-  const int nfr = box_frame_blocks(M);
+// 5a: what the sweep's workgroups form before they walk pixels (until the box launch was folded into the sweep, a kernel of its
+// own that handed the sweep 64 bytes of record and 8 of box per face through HBM): the frame's reference depth, a face's
+// conservative pixel box, and -- one rider workgroup per frame -- the frame's active pixel region.
+
+// reference depth of frame n (mean over 64 spread vertices; pz: the frame's plane of view-space depths), called by a whole wave.
+// The rasteriser orders candidates by pz - zc, which is the same order (the subtraction is exact for depths within a factor
+// two) but keeps the cached per-pixel bounds valid when the whole animal moves along the view axis.
+__device__ __forceinline__ float frame_ref_depth(const float* __restrict__ pz, int V, int lane) {
+  return wave_sum(pz[(int)(((long long)lane * V) >> 6)]) * (1.0f / 64.0f);
+}
+
+// conservative pixel box of a face with projected corners a, b, c that make_face_rec accepted (`ok`): c0 | c1 << 16, r0 | r1 << 16;
+// c0 = 1 > c1 = 0 when nothing of it is on screen
+__device__ __forceinline__ int2 face_pixel_box(bool ok, float ax, float ay, float bx, float by, float cx, float cy, int S) {
+  int2 box = make_int2(1, 1);
+  if (ok) {
+    const float xlo = fminf(ax, fminf(bx, cx)) - kBlurSqrt, xhi = fmaxf(ax, fmaxf(bx, cx)) + kBlurSqrt;
+    const float ylo = fminf(ay, fminf(by, cy)) - kBlurSqrt, yhi = fmaxf(ay, fmaxf(by, cy)) + kBlurSqrt;
+    // pixel centre x_p = 1 - (2c+1)/S  =>  c = ((1 - x_p) S - 1) / 2
+    const float fs = (float)S;
+    // Exactly the pixels whose centres lie inside the expanded bounding box (every candidate's does: inside the
+    // triangle, or closer than sqrt(blur) to it), widened by 1/64 pixel -- two orders of magnitude more than the
+    // rounding of these bounds at any image size the engine accepts.  (A floor / ceil pair would add a ring of up to
+    // one pixel either side: +35 % pixels on the ~9-pixel boxes of the benchmark.)
+    float c0 = ceilf(((1.0f - xhi) * fs - 1.0f) * 0.5f - kBoxSlack);
+    float c1 = floorf(((1.0f - xlo) * fs - 1.0f) * 0.5f + kBoxSlack);
+    float r0 = ceilf(((1.0f - yhi) * fs - 1.0f) * 0.5f - kBoxSlack);
+    float r1 = floorf(((1.0f - ylo) * fs - 1.0f) * 0.5f + kBoxSlack);
+    c0 = fminf(fmaxf(c0, 0.f), fs - 1.f); c1 = fminf(fmaxf(c1, -1.f), fs - 1.f);
+    r0 = fminf(fmaxf(r0, 0.f), fs - 1.f); r1 = fminf(fmaxf(r1, -1.f), fs - 1.f);
+    const bool finite = (xlo == xlo) && (xhi == xhi) && (ylo == ylo) && (yhi == yhi);
+    const bool onscreen = finite && (xhi >= -1.0f) && (xlo <= 1.0f) && (yhi >= -1.0f) && (ylo <= 1.0f) &&
+                          (c1 >= c0) && (r1 >= r0);
+    if (onscreen) box = make_int2((int)c0 | ((int)c1 << 16), (int)r0 | ((int)r1 << 16));
+  }
+  return box;
+}
+
+// One rider workgroup per frame, first in the sweep's grid: the frame's active pixel region, and (frame 0's) the reset of the
+// queue counters.  Both are first read by the resolve launch.  (Until round 3 this was extra work of the frame's first face
+// workgroup, which made that workgroup the kernel's last to finish.)  Called by every thread of a 256-thread workgroup.
+__device__ __forceinline__ void frame_region_block(const ModelDev& m, int S, const float* __restrict__ proj, int* __restrict__ frect,
+                                                   int* __restrict__ qcount, int n, float (*rr)[4] /*4 x 4 floats of LDS*/) {
   const int Vp = m.Vp;
-  if ((int)blockIdx.x < nfr) {
-    // One workgroup per frame, first in the grid: the frame's reference depth and active pixel region.  (Until round 3 this was
-    // extra work of the frame's first face workgroup, which made that workgroup the kernel's last to finish.)
-    const int n = (int)blockIdx.x;
-    if (n >= M) return;
-    if (n == 0) {
-      if (threadIdx.x < 3) qcount[threadIdx.x] = 0;
-      for (int i = threadIdx.x; i < 8 * kSelGroups; i += 256) qcount[kTicketBase + i * kTicketStride] = 0;   // the selection's ticket counters
-    }
-    const float* px = proj + (size_t)n * 3 * Vp;
-    // reference depth of the frame (mean over 64 spread vertices).  The rasteriser orders candidates by pz - zc, which
-    // is the same order (the subtraction is exact for depths within a factor two) but keeps the cached per-pixel
-    // bounds valid when the whole animal moves along the view axis.
-    if (threadIdx.x < 64) {
-      const float zsum = wave_sum(px[2 * Vp + (int)(((long long)threadIdx.x * m.V) >> 6)]);
-      if (threadIdx.x == 0) zc[n] = zsum * (1.0f / 64.0f);
-    }
-    // the frame's active region: pixel box of ALL projected vertices, blur-expanded -- a superset of every face box, so
-    // pixels outside it have no candidate at all (no atomics).
-    __shared__ float rr[4][4];
-    float xlo = 3.0e38f, xhi = -3.0e38f, ylo = 3.0e38f, yhi = -3.0e38f;
-#pragma unroll 8
-    for (int v = threadIdx.x; v < m.V; v += 256) {
-      const float x = px[v], y = px[Vp + v];
-      xlo = fminf(xlo, x); xhi = fmaxf(xhi, x); ylo = fminf(ylo, y); yhi = fmaxf(yhi, y);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      xlo = fminf(xlo, __shfl_xor(xlo, o, 64)); xhi = fmaxf(xhi, __shfl_xor(xhi, o, 64));
-      ylo = fminf(ylo, __shfl_xor(ylo, o, 64)); yhi = fmaxf(yhi, __shfl_xor(yhi, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { float* q = rr[threadIdx.x >> 6]; q[0] = xlo; q[1] = xhi; q[2] = ylo; q[3] = yhi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int w = 1; w < 4; ++w) { xlo = fminf(xlo, rr[w][0]); xhi = fmaxf(xhi, rr[w][1]); ylo = fminf(ylo, rr[w][2]); yhi = fmaxf(yhi, rr[w][3]); }
-      xlo -= kBlurSqrt; xhi += kBlurSqrt; ylo -= kBlurSqrt; yhi += kBlurSqrt;
-      const float fs = (float)S;
-      const float c0 = fmaxf(floorf(((1.0f - xhi) * fs - 1.0f) * 0.5f), 0.f), c1 = fminf(ceilf(((1.0f - xlo) * fs - 1.0f) * 0.5f), fs - 1.f);
-      const float r0 = fmaxf(floorf(((1.0f - yhi) * fs - 1.0f) * 0.5f), 0.f), r1 = fminf(ceilf(((1.0f - ylo) * fs - 1.0f) * 0.5f), fs - 1.f);
-      int4 o = make_int4(0, 0, 0, 0);              // (S - c0, c1 + 1, S - r0, r1 + 1); zeros = empty
-      if (c0 <= c1 && r0 <= r1) o = make_int4(S - (int)c0, (int)c1 + 1, S - (int)r0, (int)r1 + 1);
-      *reinterpret_cast<int4*>(frect + n * 4) = o;
-    }
-    return;
+  if (n == 0) {
+    if (threadIdx.x < 3) qcount[threadIdx.x] = 0;
+    for (int i = threadIdx.x; i < 8 * kSelGroups; i += 256) qcount[kTicketBase + i * kTicketStride] = 0;   // the selection's ticket counters
   }
-  const int nbb = box_face_blocks(m.F, M);
-  if ((int)blockIdx.x >= nfr + nbb) {           // only launched with joints_out
-    __shared__ float jred[16];
-    const int k = (int)blockIdx.x - nfr - nbb;
-    joints_block(m, jverts, joints_out, k % kJointBlocks, k / kJointBlocks, jred);
-    return;
-  }
-  int n, bxi;
-  xcd_block_of((int)blockIdx.x - nfr, box_blocks_per_frame(m.F), n, bxi);
-  if (n >= M) return;
-  __shared__ __attribute__((aligned(16))) float4 recs[256][kRecVecs];
-  const int f = bxi * 256 + threadIdx.x;
   const float* px = proj + (size_t)n * 3 * Vp;
-  int2 box = make_int2(1, 1);     // c0=1 > c1=0 : empty
-  if (f < m.F) {
-    const int i0 = m.faces[f * 3], i1 = m.faces[f * 3 + 1], i2 = m.faces[f * 3 + 2];
-    const float ax = px[i0], ay = px[Vp + i0], az = px[2 * Vp + i0];
-    const float bx = px[i1], by = px[Vp + i1], bz = px[2 * Vp + i1];
-    const float cx = px[i2], cy = px[Vp + i2], cz = px[2 * Vp + i2];
-    FaceRec r;
-    const bool ok = make_face_rec(ax, ay, az, bx, by, bz, cx, cy, cz, r);
-    if (ok) {
-      const float xlo = fminf(ax, fminf(bx, cx)) - kBlurSqrt, xhi = fmaxf(ax, fmaxf(bx, cx)) + kBlurSqrt;
-      const float ylo = fminf(ay, fminf(by, cy)) - kBlurSqrt, yhi = fmaxf(ay, fmaxf(by, cy)) + kBlurSqrt;
-      // pixel centre x_p = 1 - (2c+1)/S  =>  c = ((1 - x_p) S - 1) / 2
-      const float fs = (float)S;
-      // Exactly the pixels whose centres lie inside the expanded bounding box (every candidate's does: inside the
-      // triangle, or closer than sqrt(blur) to it), widened by 1/64 pixel -- two orders of magnitude more than the
-      // rounding of these bounds at any image size the engine accepts.  (A floor / ceil pair would add a ring of up to
-      // one pixel either side: +35 % pixels on the ~9-pixel boxes of the benchmark.)
-      float c0 = ceilf(((1.0f - xhi) * fs - 1.0f) * 0.5f - kBoxSlack);
-      float c1 = floorf(((1.0f - xlo) * fs - 1.0f) * 0.5f + kBoxSlack);
-      float r0 = ceilf(((1.0f - yhi) * fs - 1.0f) * 0.5f - kBoxSlack);
-      float r1 = floorf(((1.0f - ylo) * fs - 1.0f) * 0.5f + kBoxSlack);
-      c0 = fminf(fmaxf(c0, 0.f), fs - 1.f); c1 = fminf(fmaxf(c1, -1.f), fs - 1.f);
-      r0 = fminf(fmaxf(r0, 0.f), fs - 1.f); r1 = fminf(fmaxf(r1, -1.f), fs - 1.f);
-      const bool finite = (xlo == xlo) && (xhi == xhi) && (ylo == ylo) && (yhi == yhi);
-      const bool onscreen = finite && (xhi >= -1.0f) && (xlo <= 1.0f) && (yhi >= -1.0f) && (ylo <= 1.0f) &&
-                            (c1 >= c0) && (r1 >= r0);
-      if (onscreen) box = make_int2((int)c0 | ((int)c1 << 16), (int)r0 | ((int)r1 << 16));
-    }
-    fbox[(size_t)n * m.F + f] = box;
-    store_face_rec(&recs[threadIdx.x][0], r);
+  // the frame's active region: pixel box of ALL projected vertices, blur-expanded -- a superset of every face box, so
+  // pixels outside it have no candidate at all (no atomics).
+  float xlo = 3.0e38f, xhi = -3.0e38f, ylo = 3.0e38f, yhi = -3.0e38f;
+#pragma unroll 8
+  for (int v = threadIdx.x; v < m.V; v += 256) {
+    const float x = px[v], y = px[Vp + v];
+    xlo = fminf(xlo, x); xhi = fmaxf(xhi, x); ylo = fminf(ylo, y); yhi = fmaxf(yhi, y);
   }
-  // The 256 records of the workgroup leave through LDS (round 6): written per face they are four 16-byte pieces at a 64-byte stride
-  // per store instruction -- every 64-byte line is touched by four instructions -- while the workgroup's records are ONE contiguous
-  // 16 KB run: four instructions of 256 x 16 consecutive bytes.
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    xlo = fminf(xlo, __shfl_xor(xlo, o, 64)); xhi = fmaxf(xhi, __shfl_xor(xhi, o, 64));
+    ylo = fminf(ylo, __shfl_xor(ylo, o, 64)); yhi = fmaxf(yhi, __shfl_xor(yhi, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) { float* q = rr[threadIdx.x >> 6]; q[0] = xlo; q[1] = xhi; q[2] = ylo; q[3] = yhi; }
   __syncthreads();
-  {
-    const int nrec = min(256, m.F - bxi * 256);            // faces of this workgroup that exist
-    float4* dst = frec + ((size_t)n * m.F + (size_t)bxi * 256) * kRecVecs;
-#pragma unroll
-    for (int q = 0; q < kRecVecs; ++q) {
-      const int idx = q * 256 + (int)threadIdx.x;
-      if (idx < nrec * kRecVecs) dst[idx] = recs[idx >> 2][idx & 3];
-    }
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) { xlo = fminf(xlo, rr[w][0]); xhi = fmaxf(xhi, rr[w][1]); ylo = fminf(ylo, rr[w][2]); yhi = fmaxf(yhi, rr[w][3]); }
+    xlo -= kBlurSqrt; xhi += kBlurSqrt; ylo -= kBlurSqrt; yhi += kBlurSqrt;
+    const float fs = (float)S;
+    const float c0 = fmaxf(floorf(((1.0f - xhi) * fs - 1.0f) * 0.5f), 0.f), c1 = fminf(ceilf(((1.0f - xlo) * fs - 1.0f) * 0.5f), fs - 1.f);
+    const float r0 = fmaxf(floorf(((1.0f - yhi) * fs - 1.0f) * 0.5f), 0.f), r1 = fminf(ceilf(((1.0f - ylo) * fs - 1.0f) * 0.5f), fs - 1.f);
+    int4 o = make_int4(0, 0, 0, 0);              // (S - c0, c1 + 1, S - r0, r1 + 1); zeros = empty
+    if (c0 <= c1 && r0 <= r1) o = make_int4(S - (int)c0, (int)c1 + 1, S - (int)r0, (int)r1 + 1);
+    *reinterpret_cast<int4*>(frect + n * 4) = o;
   }
-  // union box of each group of kRectFaces consecutive faces (sub-wave shuffle reduction)
-  const bool live = (box.x & 0xffff) <= (box.x >> 16);
-  int x0 = live ? (box.x & 0xffff) : 0x7fff, x1 = live ? (box.x >> 16) : -1;
-  int y0 = live ? (box.y & 0xffff) : 0x7fff, y1 = live ? (box.y >> 16) : -1;
-#pragma unroll
-  for (int o = kRectFaces / 2; o > 0; o >>= 1) {
-    x0 = min(x0, __shfl_xor(x0, o, kRectFaces)); x1 = max(x1, __shfl_xor(x1, o, kRectFaces));
-    y0 = min(y0, __shfl_xor(y0, o, kRectFaces)); y1 = max(y1, __shfl_xor(y1, o, kRectFaces));
-  }
-  if ((threadIdx.x & (kRectFaces - 1)) == 0 && f < m.F)
-    brect[(size_t)n * rect_count(m.F) + f / kRectFaces] = make_int4(x0, x1, y0, y1);
 }
 
 // 5b: sweep.  Each pixel carries two cached depth bounds lo <= hi from the last exact selection (zband; +inf
@@ -332,16 +283,28 @@ face_bbox_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, int2*
 // integer (count << 50 | log sum); candidates in (lo, hi] are appended to the pixel's short band list; farther ones
 // are dropped.  raster_resolve_kernel proves from the counts that the K nearest are {<= lo} + the nearest few of the
 // band, or sends the pixel to the exact selection.
+// The launch also forms what it sweeps (until then face_bbox_kernel's launch, 14 us for 36 MB that this kernel read straight back):
+// grid = sweep_launch_grid: [frame riders: frame_region_block] [sweep blocks] [joint riders, only with joints_out: joints_block --
+// independent of the rasteriser, latency-bound, and otherwise a launch of its own; short, and behind the sweep blocks because in
+// front of the face workgroups of the box launch they measured 0.4 % slower]; sweep_block_at of smalfit_plan.h deals the roles.
 __global__ void __launch_bounds__(256, 1)
-raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const int2* __restrict__ fbox, const int4* __restrict__ brect, const float* __restrict__ zc, const float2* __restrict__ zband,
+raster_sweep_kernel(ModelDev m, int M, int S, const float* __restrict__ proj, float4* __restrict__ frec /*[M][F][kRecVecs]: see store_face_rec*/,
+                    int2* __restrict__ fbox /*[M][F]*/, int4* __restrict__ brect /*[M][ceil(F/8)]*/, float* __restrict__ zc /*[M]*/,
+                    int* __restrict__ frect /*[M][4]: S - x0, x1 + 1, S - y0, y1 + 1 of the active region; 0 = empty*/,
+                    int* __restrict__ qcount /*[0..2]: select / band queue lengths, pixels resolve sent to select; [8..15]: the selection's tickets; reset here*/,
+                    const float* __restrict__ jverts, float* __restrict__ joints_out /*[M][41][3] or null*/,
+                    const float2* __restrict__ zband,
                     unsigned long long* __restrict__ gacc /*[M][S*S]*/, unsigned* __restrict__ bcnt /*[M][S*S]*/,
                     float2* __restrict__ blist /*[M][S*S][kBandCap]*/, unsigned char* __restrict__ plist /*[M][F][kListCap]*/,
                     unsigned char* __restrict__ pcount /*[M][F]*/) {
-  // Prologue (round 4): ONE trip to memory and ONE barrier.  The block's rectangle is the union of its four union boxes
-  // (face_bbox_kernel's 8-face index: uniform, scalar loads); 128 threads fetch one 16-byte quarter of a face record each, 32
-  // more a face box, all issued before the accumulator window is zeroed, and land in LDS behind the same barrier.  (Until
-  // round 4: zero, barrier, 32 threads load box + record while 224 wait, LDS atomics for the rectangle, barrier: 55 us of the
-  // kernel's 155 were this fixed cost of its 15.5 k workgroups, 24.5 us now -- profiles/r4_ab_experiments.txt.)
+  // Prologue: TWO dependent trips to memory, by one wave, and ONE barrier.  Threads 0..31 form the block's 32 face records and
+  // boxes from the frame's projected vertices (46 KB, resident in the L2 of the frame's XCD): the face's three indices, then
+  // its nine coordinates, make_face_rec, face_pixel_box, all into LDS where the pixel loop reads them; the union boxes by
+  // sub-wave shuffles.  The second wave forms the frame's reference depth from static addresses (the same trip as the indices);
+  // waves 1..3 zero the accumulator window meanwhile.  Behind the barrier the records leave for the selection and the backward
+  // gather as ONE contiguous 2 KB run (128 threads x 16 bytes), the boxes as 256 bytes: stores that drain under the pixel loop.
+  // (Round 4 set the shape: one barrier, every load issued before the window is zeroed; each further barrier costs the launch
+  // ~10 us over its 15.5 k workgroups -- profiles/r4_ab_experiments.txt.)
   static_assert(kSweepFaces % kRectFaces == 0, "a sweep block is a whole number of union boxes");
   __shared__ __attribute__((aligned(16))) float4 raw[kSweepFaces][kRecVecs];
   __shared__ int2 boxes[kSweepFaces];
@@ -351,50 +314,94 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
   __shared__ int st_n[4];
   __shared__ __attribute__((aligned(8))) unsigned char lsts[kSweepFaces][kListLds];
   __shared__ int lcn[kSweepFaces];
-  static_assert(sizeof(raw) + sizeof(boxes) + sizeof(acc) + sizeof(st_e) + sizeof(st_p) + sizeof(st_n) + sizeof(lsts) + sizeof(lcn)
-                <= 160 * 1024 / 8, "eight sweep workgroups per CU (160 KB of LDS)");
+  __shared__ int4 brect_s;                                // the block's rectangle: x0, x1, y0, y1
+  __shared__ float zc_s;                                  // the frame's reference depth
+  static_assert(sizeof(raw) + sizeof(boxes) + sizeof(acc) + sizeof(st_e) + sizeof(st_p) + sizeof(st_n) + sizeof(lsts) + sizeof(lcn) +
+                sizeof(brect_s) + 16 /*zc_s, padded*/ <= 160 * 1024 / 8, "eight sweep workgroups per CU (160 KB of LDS)");
   const int t = threadIdx.x;
-  int n, bxi;
-  xcd_block(sweep_blocks_per_frame(F), n, bxi);
-  if (n >= M) return;
+  const int F = m.F;
+  const SweepBlock role = sweep_block_at((int)blockIdx.x, F, M);
+  if (role.role != SweepRole::Faces) {
+    // the riders' few floats of LDS alias the accumulator window
+    if (role.role == SweepRole::Joint) joints_block(m, jverts, joints_out, role.bx, role.n, reinterpret_cast<float*>(acc));
+    else if (role.n < M) frame_region_block(m, S, proj, frect, qcount, role.n, reinterpret_cast<float (*)[4]>(acc));
+    return;
+  }
+  const int n = role.n, bxi = role.bx;
+  if (n >= M) return;                                     // a frame of the padding: stores nothing
   const int f0 = bxi * kSweepFaces;
   SMALFIT_WORK(const unsigned long long ws_t0 = __builtin_amdgcn_s_memtime();)
-  int rect[4] = {0x7fff, -1, 0x7fff, -1};                 // x0, x1, y0, y1 (uniform)
-  {
-    const int nrect = rect_count(F);
-    const int4* br = brect + (size_t)n * nrect + (size_t)bxi * (kSweepFaces / kRectFaces);
-#pragma unroll
-    for (int u = 0; u < kSweepFaces / kRectFaces; ++u) {
-      if (bxi * (kSweepFaces / kRectFaces) + u < nrect) {
-        const int4 b = br[u];
-        rect[0] = min(rect[0], b.x); rect[1] = max(rect[1], b.y); rect[2] = min(rect[2], b.z); rect[3] = max(rect[3], b.w);
+  static_assert(kSweepFaces * kRecVecs <= 128 && kRecVecs == 4 && kSweepFaces <= 32, "faces by threads 0..31; record quarters leave by threads 0..127, boxes by 128..159");
+  const float* px = proj + (size_t)n * 3 * m.Vp;
+  // (the wave's id through readfirstlane: s_setprio is a scalar instruction and must sit behind a provably uniform branch)
+  if ((__builtin_amdgcn_readfirstlane(t) >> 6) == 0) {
+    // the block waits at the barrier for this wave's two trips and ~150 instructions, and the SIMD it shares with seven other
+    // waves is issue-bound in their pixel loops: it issues first until it is through (+0.4 % of the whole iteration)
+    __builtin_amdgcn_s_setprio(3);
+    if (t < kSweepFaces) {
+      const int Vp = m.Vp;
+      const int f = f0 + t;
+      int2 box = make_int2(1, 1);                           // c0 = 1 > c1 = 0: empty
+      if (f < F) {
+        const int i0 = m.faces[f * 3], i1 = m.faces[f * 3 + 1], i2 = m.faces[f * 3 + 2];
+        const float ax = px[i0], ay = px[Vp + i0], az = px[2 * Vp + i0];
+        const float bx = px[i1], by = px[Vp + i1], bz = px[2 * Vp + i1];
+        const float cx = px[i2], cy = px[Vp + i2], cz = px[2 * Vp + i2];
+        FaceRec r;
+        const bool ok = make_face_rec(ax, ay, az, bx, by, bz, cx, cy, cz, r);
+        box = face_pixel_box(ok, ax, ay, bx, by, cx, cy, S);
+        store_face_rec(&raw[t][0], r);
       }
+      boxes[t] = box;
+      lcn[t] = 0;
+      // union box of each group of kRectFaces consecutive faces (sub-wave shuffle reduction): the selection's index; then of all
+      // the block's faces: its rectangle
+      const bool live = (box.x & 0xffff) <= (box.x >> 16);
+      int x0 = live ? (box.x & 0xffff) : 0x7fff, x1 = live ? (box.x >> 16) : -1;
+      int y0 = live ? (box.y & 0xffff) : 0x7fff, y1 = live ? (box.y >> 16) : -1;
+#pragma unroll
+      for (int o = kRectFaces / 2; o > 0; o >>= 1) {
+        x0 = min(x0, __shfl_xor(x0, o, kRectFaces)); x1 = max(x1, __shfl_xor(x1, o, kRectFaces));
+        y0 = min(y0, __shfl_xor(y0, o, kRectFaces)); y1 = max(y1, __shfl_xor(y1, o, kRectFaces));
+      }
+      if ((t & (kRectFaces - 1)) == 0 && f < F)
+        brect[(size_t)n * rect_count(F) + f / kRectFaces] = make_int4(x0, x1, y0, y1);
+#pragma unroll
+      for (int o = kSweepFaces / 2; o >= kRectFaces; o >>= 1) {
+        x0 = min(x0, __shfl_xor(x0, o, kSweepFaces)); x1 = max(x1, __shfl_xor(x1, o, kSweepFaces));
+        y0 = min(y0, __shfl_xor(y0, o, kSweepFaces)); y1 = max(y1, __shfl_xor(y1, o, kSweepFaces));
+      }
+      if (t == 0) brect_s = make_int4(x0, x1, y0, y1);
     }
-  }
-  float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  int2 bq = make_int2(1, 1);                              // c0 = 1 > c1 = 0: empty
-  const bool ld_rec = t < kSweepFaces * kRecVecs && f0 + (t >> 2) < F;
-  const bool ld_box = t >= 128 && t < 128 + kSweepFaces && f0 + (t - 128) < F;
-  static_assert(kSweepFaces * kRecVecs <= 128 && kRecVecs == 4, "record quarters by threads 0..127, boxes by 128..159");
-  if (ld_rec) q4 = frec[((size_t)n * F + f0) * kRecVecs + t];
-  if (ld_box) bq = fbox[(size_t)n * F + f0 + (t - 128)];
-  if (t < 4) st_n[t] = 0;
-  if (t < kSweepFaces) lcn[t] = 0;
-  {
-    // only the rows of the window the block's rectangle reaches are ever touched (and flushed): a block of small faces zeroes a
-    // dozen rows of the 36 (round 6: the window grew from 32 x 32 to 36 x 36, what eight workgroups per CU leave room for -- 21 % of a
-    // crop-filling animal's near pairs fell outside the smaller one, one global atomic each)
-    const int zrows = min(kAccWin, max(rect[3] - rect[2] + 1, 0));
-    for (int i = t; i < zrows * kAccWin; i += 256) acc[i] = 0ull;
+    __builtin_amdgcn_s_setprio(0);
+  } else {
+    // every row of the window is zeroed: the rectangle is not known before the barrier (zeroing only the rows it reaches measured
+    // as no gain in round 6)
+    float zcv = 0.f;
+    if (t < 128) zcv = frame_ref_depth(px + 2 * m.Vp, m.V, t - 64);
+    for (int i = t - 64; i < kAccWin * kAccWin; i += 192) acc[i] = 0ull;
+    if (t == 64) {
+      zc_s = zcv;
+      if (bxi == 0) zc[n] = zcv;                          // for the selection and the backward gather
+    }
+    if (t >= 128 && t < 132) st_n[t - 128] = 0;
   }
   SMALFIT_WORK(const unsigned long long ws_t1 = __builtin_amdgcn_s_memtime();)
-  if (t < kSweepFaces * kRecVecs) raw[t >> 2][t & 3] = q4;
-  if (t >= 128 && t < 128 + kSweepFaces) {
-    boxes[t - 128] = bq;
-    if (ld_box && (bq.x & 0xffff) > (bq.x >> 16)) pcount[(size_t)n * F + f0 + (t - 128)] = 0;   // nothing on screen: an empty list (faces with a box: below)
-  }
   __syncthreads();
   SMALFIT_WORK(const unsigned long long ws_t2 = __builtin_amdgcn_s_memtime();)
+  int rect[4];                                            // x0, x1, y0, y1 (uniform: scalar registers)
+  {
+    const int4 b = brect_s;
+    rect[0] = __builtin_amdgcn_readfirstlane(b.x); rect[1] = __builtin_amdgcn_readfirstlane(b.y);
+    rect[2] = __builtin_amdgcn_readfirstlane(b.z); rect[3] = __builtin_amdgcn_readfirstlane(b.w);
+  }
+  if (t < kSweepFaces * kRecVecs) {
+    if (f0 + (t >> 2) < F) frec[((size_t)n * F + f0) * kRecVecs + t] = raw[t >> 2][t & 3];
+  } else if (t < 128 + kSweepFaces && f0 + (t - 128) < F) {
+    const int2 bq = boxes[t - 128];
+    fbox[(size_t)n * F + f0 + (t - 128)] = bq;
+    if ((bq.x & 0xffff) > (bq.x >> 16)) pcount[(size_t)n * F + f0 + (t - 128)] = 0;   // nothing on screen: an empty list (faces with a box: below)
+  }
   if (rect[1] < rect[0]) return;                        // no face of this block is on screen
   // The LDS window: kAccWin x kAccWin accumulator cells CENTRED on the block's rectangle (round 4; until then anchored at its corner).
   // It matters when the rectangle does not fit -- 32 faces of a crop-filling animal span ~45 x 40 pixels: anchored at the corner,
@@ -411,7 +418,7 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
   const int sub = t & 15, grp = t >> 4;
   const float inv_s = 1.0f / (float)S;
   const int wv = t >> 6, lane = t & 63;
-  float zcn = zc[n];
+  float zcn = zc_s;
   asm volatile("" : "+v"(zcn));        // in a vector register: a float add with a scalar operand issues at half rate
   auto flush_band = [&]() {                              // called with the wave converged
     const int cnt = min(__builtin_amdgcn_readfirstlane(st_n[wv]), kBandStage);
@@ -512,7 +519,7 @@ raster_sweep_kernel(int F, int M, int S, const float4* __restrict__ frec, const 
       const int2 bx = boxes[k2];
       const int npx2 = ((bx.x >> 16) - (bx.x & 0xffff) + 1) * ((bx.y >> 16) - (bx.y & 0xffff) + 1);
       int n2, bx2;
-      xcd_block(sweep_blocks_per_frame(F), n2, bx2);
+      xcd_block_of((int)blockIdx.x - box_frame_blocks(M), sweep_blocks_per_frame(F), n2, bx2);
       const size_t fi = (size_t)n2 * F + bx2 * kSweepFaces + k2;
       // one format for the wave's four faces (= the four faces of one backward wave): lists when every one of them has one
       const bool has_list = npx2 <= 256 && cnt <= kListLds;

@@ -25,7 +25,7 @@
 //   skin_mfma_kernel / skin_kernel   smal_torch.py:138-163 (pose blend, W*A, skinning) + renderer camera transform
 //   joints_kernel       smal_torch.py:171-184
 //   loss_kernel         smal_fitter.py:129-132,140-160,177-190 ; pose_prior_35.py:117-124
-//   face_bbox / raster_sweep / raster_resolve / raster_band / raster_select / raster_bwd
+//   raster_sweep / raster_resolve / raster_band / raster_select / raster_bwd
 //                       p3d_renderer.py:26-39,65-66 (pytorch3d rasterize_meshes + sigmoid_alpha_blend)
 //   vertex_bwd, lbs_bwd_mid, chain_bwd, assemble    autograd of the above (optimize_to_joints.py:136)
 //   adam_segments_kernel  optimize_to_joints.py:96,137 (torch.optim.Adam, betas=(0.5,0.999))

@@ -507,8 +507,8 @@ static void launch_raster_select(hipStream_t st, bool frame_loss, Args... args) 
   else raster_select_kernel<false><<<kSelectBlocks, 64 * kSelWaves, 0, st>>>(args...);
 }
 
-// face boxes / records, sweep (per-pixel count + log-alpha), resolve (K-nearest).  e->proj holds camera-space vertices.
-// `joints_out` / `la`: the joint regression and the per-frame loss terms ride along as extra workgroups of the box and
+// sweep (face boxes / records, per-pixel count + log-alpha), resolve (K-nearest).  e->proj holds camera-space vertices.
+// `joints_out` / `la`: the joint regression and the per-frame loss terms ride along as extra workgroups of the sweep and
 // resolve launches (they depend on the skinned vertices only and are needed by the backward pass only).
 // `queue_loss` / `floss`: the queue kernels write their loss partials / count them per frame too (EvalPlan)
 static int run_raster_forward(smalfit_engine* e, hipStream_t st, int M, WinMap win, float w_sil,
@@ -519,16 +519,13 @@ static int run_raster_forward(smalfit_engine* e, hipStream_t st, int M, WinMap w
   float2* gz = e->gz;
   const ModelDev& m = e->model->dev;
   {
-    Section sec(e, st, SMALFIT_SEC_RASTER_BBOX);
-    // the per-pixel accumulators are zero here: whoever reads them last (resolve / band kernel) clears them; the two
-    // queue counters are reset by face_bbox_kernel
-    face_bbox_kernel<<<box_grid(m.F, M, joints_out != nullptr), 256, 0, st>>>(m, M, e->S, e->proj, e->fbox, e->frec, e->brect, e->zc, e->frect,
-                                                                           e->qcount, e->verts, joints_out);
-    LAUNCH_OK("face_bbox_kernel");
-  }
-  {
+    // (SMALFIT_SEC_RASTER_BBOX records nothing any more: the sweep forms its faces' boxes and records itself)
     Section sec(e, st, SMALFIT_SEC_RASTER_SWEEP);
-    raster_sweep_kernel<<<sweep_grid(m.F, M), 256, 0, st>>>(m.F, M, e->S, e->frec, e->fbox, e->brect, e->zc, e->zband, e->gacc, e->bcnt, e->blist, e->plist, e->pcount);
+    // the per-pixel accumulators are zero here: whoever reads them last (resolve / band kernel) clears them; the two
+    // queue counters are reset by the sweep launch's first frame rider
+    raster_sweep_kernel<<<sweep_launch_grid(m.F, M, joints_out != nullptr), 256, 0, st>>>(m, M, e->S, e->proj, e->frec, e->fbox, e->brect, e->zc, e->frect,
+                                                                                      e->qcount, e->verts, joints_out, e->zband, e->gacc, e->bcnt,
+                                                                                      e->blist, e->plist, e->pcount);
     LAUNCH_OK("raster_sweep_kernel");
   }
   {

@@ -98,21 +98,41 @@ constexpr int kSkinThreads = 256 * kSkinGroups;    // and its threads
 constexpr Grid2 skin_grid(SkinForm form, int M, int Vp) {
   return form == SkinForm::Wide ? Grid2{Vp / 64, (M + 15) / 16} : form == SkinForm::Split ? Grid2{Vp / kSkinVerts, (M + 15) / 16} : Grid2{Vp / 64, (M + 7) / 8};
 }
-constexpr int kJointBlocks = 41;             // joints_kernel / the box kernel's joint riders: one workgroup per regressed joint and frame
+constexpr int kJointBlocks = 41;             // joints_kernel / the sweep launch's joint riders: one workgroup per regressed joint and frame
 
-// face_bbox_kernel: [frame blocks, a multiple of 8] [face blocks of 256 faces, frame n on XCD n % 8] [joint riders, 41 per frame]
+// the riders of the sweep launch (until the box launch was folded into the sweep: of face_bbox_kernel, whose grid was
+// [frame blocks, a multiple of 8] [face blocks of 256 faces, frame n on XCD n % 8] [joint riders, 41 per frame])
 constexpr int box_frame_blocks(int M) { return xcd_frames(M); }
 constexpr int box_blocks_per_frame(int F) { return (F + 255) / 256; }
+// (box_face_blocks and box_grid have no caller in the library any more: tests/host_plan_shim.cpp and tests/test_host_plan_cpu.py pin them)
 constexpr int box_face_blocks(int F, int M) { return xcd_grid(box_blocks_per_frame(F), M); }
 constexpr int box_joint_blocks(int M, bool joints) { return joints ? kJointBlocks * M : 0; }
 constexpr int box_grid(int F, int M, bool joints) { return box_frame_blocks(M) + box_face_blocks(F, M) + box_joint_blocks(M, joints); }
 
-// raster_sweep_kernel
+// workgroup b of an xcd_grid(blocks_per_frame, M) -> its frame (may be >= M: a workgroup of the padding) and its block of that frame
+struct XcdBlock { int n, bx; };
+constexpr XcdBlock xcd_block_at(int b, int blocks_per_frame) {
+  const int xcd = b & 7, slot = b >> 3;
+  return XcdBlock{(slot / blocks_per_frame) * 8 + xcd, slot - (slot / blocks_per_frame) * blocks_per_frame};
+}
+
+// raster_sweep_kernel: [frame riders, a multiple of 8] [sweep blocks of 32 faces, frame n on XCD n % 8] [joint riders, 41 per frame]
 constexpr int kRectFaces = 8;                // faces per entry of the union-box index
 constexpr int kSweepFaces = 32;              // faces per sweep block
 constexpr int rect_count(int F) { return (F + kRectFaces - 1) / kRectFaces; }
 constexpr int sweep_blocks_per_frame(int F) { return (F + kSweepFaces - 1) / kSweepFaces; }
 constexpr int sweep_grid(int F, int M) { return xcd_grid(sweep_blocks_per_frame(F), M); }
+constexpr int sweep_launch_grid(int F, int M, bool joints) { return box_frame_blocks(M) + sweep_grid(F, M) + box_joint_blocks(M, joints); }
+// what workgroup b of that launch does.  Frame: the active region of frame n (n >= M: nothing).  Faces: block bx of frame n
+// (n >= M: nothing).  Joint: regressed joint bx of frame n
+enum class SweepRole { Frame = 0, Faces = 1, Joint = 2 };
+struct SweepBlock { SweepRole role; int n, bx; };
+constexpr SweepBlock sweep_block_at(int b, int F, int M) {
+  if (b < box_frame_blocks(M)) return SweepBlock{SweepRole::Frame, b, 0};
+  const int k = b - box_frame_blocks(M);
+  if (k >= sweep_grid(F, M)) return SweepBlock{SweepRole::Joint, (k - sweep_grid(F, M)) / kJointBlocks, (k - sweep_grid(F, M)) % kJointBlocks};
+  return SweepBlock{SweepRole::Faces, xcd_block_at(k, sweep_blocks_per_frame(F)).n, xcd_block_at(k, sweep_blocks_per_frame(F)).bx};
+}
 
 // raster_resolve_kernel: [loss riders, one per frame, padded to a multiple of 8] [tiles of kResEdge^2 pixels, frame n on XCD n % 8]
 constexpr int kResSub = 2;                   // a resolve workgroup takes (16 kResSub)^2 pixels, kResSub^2 per thread: the launch is
@@ -914,7 +934,7 @@ struct EvalPlan {
   bool raster_backward;
   // loss launch
   LossLaunch loss_launch;
-  bool joints_in_head;       // joints_kernel runs behind the skinning (else its blocks ride in the box kernel)
+  bool joints_in_head;       // joints_kernel runs behind the skinning (else its blocks ride in the sweep launch)
   // effective weights
   float w_temp;              // 0 unless `temporal`
   float w_limit;             // 0 unless the engine has a limit table: the reference's weight table carries w_limit = 100 in stages

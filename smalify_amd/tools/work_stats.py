@@ -39,7 +39,7 @@ def project(verts):
 
 
 def face_boxes(x, y, faces, S):
-    """the pixel box of every face exactly as face_bbox_kernel forms it: the pixels whose centres lie in the sqrt(blur)-expanded
+    """the pixel box of every face exactly as raster_sweep_kernel forms it (face_pixel_box): the pixels whose centres lie in the sqrt(blur)-expanded
     bounding box.  -> c0, c1, r0, r1 (inclusive; empty: c1 < c0)"""
     r = math.sqrt(BLUR)
     fx, fy = x[faces], y[faces]

@@ -20,7 +20,8 @@ for r in rows:
         cur = []
 # bench.py --full times three runs of STEPS iterations at the end of the process: cold, primed, profiled (section events)
 sel = {"cold": its[-3 * steps:-2 * steps], "primed": its[-2 * steps:-steps], "profiled": its[-steps:]}[which]
-cols = ["lbs_head", "skin_mfma", "face_bbox", "raster_sweep", "raster_resolve", "raster_band", "raster_select", "raster_bwd", "vertex_bwd", "lbs_bwd_mid", "chain_bwd", "assemble", "adam_segments"]
+# (raster_sweep forms its faces' boxes and records itself: there is no box kernel to list)
+cols = ["lbs_head", "skin_mfma", "raster_sweep", "raster_resolve", "raster_band", "raster_select", "raster_bwd", "vertex_bwd", "lbs_bwd_mid", "chain_bwd", "assemble", "adam_segments"]
 print("%3s %8s | " % ("it", "wall") + " ".join("%7s" % c.replace("raster_", "")[:7] for c in cols))
 for i, it in enumerate(sel):
     d = {}
