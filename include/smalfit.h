@@ -43,7 +43,8 @@ typedef struct smalfit_engine smalfit_engine;
  * smalfit_mesh_surface_eval / smalfit_fit3d_step_surface (smalfit_surface_term_args: the same distances as a term to descend on);
  * smalfit_mesh_surface_eval_gated / smalfit_fit3d_step_gated / smalfit_mesh_targets_sample_normals (smalfit_surface_gate_args: that
  * term gated for partial scans); smalfit_mesh_objective_eval_gated / smalfit_fit3d_step_partial / smalfit_mesh_targets_sample_attrs
- * (smalfit_chamfer_gate_args: the chamfer term gated the same way). */
+ * (smalfit_chamfer_gate_args: the chamfer term gated the same way); smalfit_mesh_targets_build_index /
+ * smalfit_mesh_targets_index_stats (smalfit_scan_index_args: a grid over the targets that changes no result). */
 #define SMALFIT_ABI_VERSION 6
 int smalfit_version(void);
 const char* smalfit_last_error(void);
@@ -474,6 +475,39 @@ int smalfit_mesh_targets_sample_normals(smalfit_mesh_targets* targets, void* str
  * samplers above ARE this call with NULLs, and the points are theirs bit for bit. */
 int smalfit_mesh_targets_sample_attrs(smalfit_mesh_targets* targets, void* stream, int num_points, unsigned long long seed,
                                       unsigned int iteration, float* points, float* normals, unsigned char* boundary);
+
+/* ---- the scan index: a grid over every target mesh, for dense scans --------------------------------------------------------
+ * The vertex -> surface direction of the surface term (smalfit_mesh_surface_eval*, smalfit_fit3d_step_surface and later) and of
+ * smalfit_mesh_score tests every fitted vertex against every target triangle.  With an index on the targets it walks, per
+ * vertex, the cells of a uniform grid over the target's bounding box outwards from the vertex's own cell -- a triangle is listed
+ * in every cell its bounding box overlaps, a triangle overlapping more than 64 cells on a short list every vertex tests first --
+ * and stops when no triangle it has not tested can be as near as the nearest it has: the distance to the unvisited part of the
+ * box, less 256 ulp of the largest coordinate, exceeds it.  A vertex that is not done once the cells it has walked number twice the
+ * mesh's faces (or after 48 rings) scans the whole mesh as before.  THE INDEX NEVER CHANGES A RESULT: the match of a vertex is the least float32 d^2 over all triangles of its
+ * target, the lowest face among equal values, by the same arithmetic on the same records; every output of every call is bit for
+ * bit what it is without the index (with max_dist_vert on, a vertex whose match lies beyond it may be dropped before its match
+ * is known: it is dropped either way).  Off until asked for; built on the host from the handle's meshes, which are read back
+ * once; all or nothing, every mesh of the handle gets a grid; calling it again rebuilds; a refusal (a non-finite target vertex,
+ * a bad block) leaves the handle as it was and returns 1.  smalfit_mesh_targets_destroy frees it.
+ * The point -> surface direction, the chamfer scans and the sampler do not read it. */
+typedef struct smalfit_scan_index_args {
+  unsigned int struct_size; /* sizeof(smalfit_scan_index_args) */
+  float cell_scale;         /* cell edge = cell_scale * sqrt(surface area / faces); 0 = the library's own (2).  For tests and
+                               tuning: the results do not depend on it */
+} smalfit_scan_index_args;
+typedef struct smalfit_scan_index_stats {
+  unsigned int struct_size; /* sizeof(smalfit_scan_index_stats), set by the caller */
+  int dims[3];              /* cells along x, y, z */
+  int cells;                /* their product */
+  int occupied_cells;       /* cells that list a triangle */
+  int entries;              /* (cell, triangle) pairs listed */
+  int oversize;             /* triangles on the oversize list */
+  int largest_cell;         /* most triangles listed in one cell */
+  unsigned long long bytes; /* device bytes of this mesh's share of the index */
+} smalfit_scan_index_stats;
+int smalfit_mesh_targets_build_index(smalfit_mesh_targets* targets, const smalfit_scan_index_args* args);
+/* the grid of target mesh `mesh`; returns 1 with a message when the handle has no index */
+int smalfit_mesh_targets_index_stats(const smalfit_mesh_targets* targets, int mesh, smalfit_scan_index_stats* out);
 
 /* ---- the chamfer term gated for partial scans ---------------------------------------------------------------------------
  * The chamfer term matches every target point to its nearest fitted vertex and every fitted vertex to its nearest target point,

@@ -149,6 +149,25 @@ class RobustArgs(C.Structure):
         self.struct_size = C.sizeof(RobustArgs)
 
 
+class ScanIndexArgs(C.Structure):
+    """smalfit_scan_index_args: the grid over the targets (smalfit_mesh_targets_build_index); cell_scale 0 = the library's own"""
+    _fields_ = [("struct_size", C.c_uint), ("cell_scale", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(ScanIndexArgs)
+
+
+class ScanIndexStats(C.Structure):
+    """smalfit_scan_index_stats: one target mesh's grid (smalfit_mesh_targets_index_stats)"""
+    _fields_ = [("struct_size", C.c_uint), ("dims", C.c_int * 3), ("cells", C.c_int), ("occupied_cells", C.c_int),
+                ("entries", C.c_int), ("oversize", C.c_int), ("largest_cell", C.c_int), ("bytes", C.c_ulonglong)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(ScanIndexStats)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -266,6 +285,8 @@ SIGNATURES = {
                                               C.POINTER(RobustArgs)]),
     "smalfit_fit3d_step_robust": (_I, [_VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs),
                                        C.POINTER(ChamferGateArgs), C.POINTER(RobustArgs)]),
+    "smalfit_mesh_targets_build_index": (_I, [_VP, C.POINTER(ScanIndexArgs)]),
+    "smalfit_mesh_targets_index_stats": (_I, [_VP, _I, C.POINTER(ScanIndexStats)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
@@ -274,7 +295,8 @@ LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "sm
                           "smalfit_fit3d_step_surface", "smalfit_mesh_surface_eval_gated", "smalfit_fit3d_step_gated",
                           "smalfit_mesh_targets_sample_normals", "smalfit_mesh_targets_sample_attrs",
                           "smalfit_mesh_objective_eval_gated", "smalfit_fit3d_step_partial", "smalfit_mesh_objective_eval_robust",
-                          "smalfit_mesh_surface_eval_robust", "smalfit_fit3d_step_robust"])
+                          "smalfit_mesh_surface_eval_robust", "smalfit_fit3d_step_robust", "smalfit_mesh_targets_build_index",
+                          "smalfit_mesh_targets_index_stats"])
 
 
 class SmalfitError(RuntimeError):

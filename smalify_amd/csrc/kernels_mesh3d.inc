@@ -890,6 +890,174 @@ __global__ __launch_bounds__(256) void mesh3d_surface_reduce_kernel(SurfaceTermA
   }
 }
 
+// ---- the scan index: the vertex direction over a grid of the target (mesh3d_grid.h) ---------------------------------------------
+// Targets that carry an index (smalfit_mesh_targets_build_index) send mesh3d_surface_near_kernel<0, .> and
+// mesh3d_surface_dist_kernel<0> through the two kernels below instead; everything downstream reads the same key / the same
+// distance.  One WAVE per query, kScanGridQueries queries a block, grid (ceil(V / 4), N); no LDS, no barrier: a wave's loops are
+// its own.  grid_nearest: the oversize list, then ring after ring of cells round the query's own -- the lanes take a ring's cells
+// 64 at a time and read their CSR offsets, an inclusive prefix sum over the wave (shuffles) turns the 64 counts into one
+// candidate list, the lanes stride over it, each finding its owner cell by a 6-step search in the prefix row (held in registers,
+// read by lane index) and gathering its record as four 16-byte loads -- until scan_walk_done, or the whole grid is seen, or
+// scan_max_rings(faces) rings are: then the whole record array, lane-strided.  The pair arithmetic is point_scan_tri_dist2 /
+// normal_compatible on the linear scan's records; candidates meet by scan_take in a lane and nearest_merge across lanes: the
+// lexicographic (d^2, face) minimum, whatever order they came in and however often
+struct ScanIndexDev {
+  const ScanGrid* grids;     // [N]
+  const int* cell_off;       // every mesh's [cells + 1], absolute offsets into cell_face
+  const int* cell_face;
+  const int* oversize;
+};
+struct SurfaceGridArgs {
+  int N, V;
+  const float* verts;            // [N][V][3]
+  MeshTargetsDev t;
+  const ScanTri* target_tris;    // packed [sum F] (near: the records the linear scan reads)
+  ScanIndexDev ix;
+  unsigned long long* keys_v;    // [N][V] (near)
+  const float* normals_v;        // [N][V][3] (near<true>)
+  float cc_v, tau2_v;
+  float* vert_dist;              // [N][V] (dist)
+};
+struct NearestFace { float d2; int face; };
+
+// BUILD: the record is formed from the target's corners as mesh3d_surface_dist_kernel<0> stages it (make_scan_tri on the device;
+// the empty asm keeps its values apart from their use, as the trip through LDS does there); else the staged record is loaded
+template <bool BUILD>
+__device__ __forceinline__ ScanTri grid_record(const float4* recs, const int* faces, const float* corners, int f) {
+  ScanTri t;
+  if constexpr (BUILD) {
+    const int* fc = faces + 3 * (size_t)f;
+    t = make_scan_tri(corners + 3 * (size_t)fc[0], corners + 3 * (size_t)fc[1], corners + 3 * (size_t)fc[2]);
+    float* w = reinterpret_cast<float*>(&t);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) asm volatile("" : "+v"(w[k]));
+  } else {
+    float4* d = reinterpret_cast<float4*>(&t);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = recs[4 * (size_t)f + k];
+  }
+  return t;
+}
+
+template <bool GATED, bool BUILD>
+__device__ __forceinline__ NearestFace grid_nearest(const ScanGrid& g, const ScanIndexDev& ix, const float4* recs, const int* faces,
+                                                    const float* corners, int nf, float qx, float qy, float qz, float ux, float uy,
+                                                    float uz, float cc, float tau2, int lane) {
+  float best = INFINITY;
+  int face = kScanNoFace;
+  if (!(isfinite(qx) && isfinite(qy) && isfinite(qz))) return NearestFace{best, face};   // (wave-uniform) no key, as the linear scan
+  auto test = [&](int f) {
+    const ScanTri t = grid_record<BUILD>(recs, faces, corners, f);
+    const float d2 = point_scan_tri_dist2(qx, qy, qz, t);
+    bool ok = true;
+    if constexpr (GATED) ok = normal_compatible(ux, uy, uz, t.nx, t.ny, t.nz, t.inv_nn, cc);
+    if (ok) scan_take(best, face, d2, f);
+  };
+  for (int i = lane; i < g.over_count; i += 64) test(ix.oversize[g.over_base + i]);
+  const float L = scan_extent(g, qx, qy, qz), slack = scan_slack(L), box = scan_box_dist(g, qx, qy, qz, L);
+  const int c[3] = {scan_cell(qx, g.lo[0], g.inv_h, g.dims[0]), scan_cell(qy, g.lo[1], g.inv_h, g.dims[1]),
+                    scan_cell(qz, g.lo[2], g.inv_h, g.dims[2])};
+  const int* cell_off = ix.cell_off + g.cell_base;
+  bool done = false;
+  const int last = scan_max_rings(nf);
+#pragma unroll 1
+  for (int r = 0; r <= last; ++r) {
+    const ScanRing ring = scan_ring_boxes(g, c, r);
+    const int total = ring.start[6];
+#pragma unroll 1
+    for (int base = 0; base < total; base += 64) {
+      const int i = base + lane;
+      const int ci = scan_ring_cell(g, ring, min(i, total - 1));
+      int start = 0, cnt = 0;
+      if (i < total) {
+        start = cell_off[ci];
+        cnt = cell_off[ci + 1] - start;
+      }
+      int inc = cnt;   // inclusive prefix sum of the 64 counts
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += up;
+      }
+      const int excl = inc - cnt;
+      const int T = __builtin_amdgcn_readfirstlane(__shfl(inc, 63, 64));
+#pragma unroll 1
+      for (int jb = 0; jb < T; jb += 64) {
+        const int j = jb + lane, jj = min(j, T - 1);
+        int lo = 0, hi = 63;   // the first lane whose inclusive sum exceeds jj owns candidate jj
+#pragma unroll
+        for (int s = 0; s < 6; ++s) {
+          const int mid = (lo + hi) >> 1;
+          const bool left = __shfl(inc, mid, 64) > jj;
+          hi = left ? mid : hi;
+          lo = left ? lo : mid + 1;
+        }
+        const int f = ix.cell_face[__shfl(start, lo, 64) + (jj - __shfl(excl, lo, 64))];
+        if (j < T) test(f);
+      }
+    }
+    const ScanBlock b = scan_block(g, c, r);
+    if (scan_block_whole(g, b)) {
+      done = true;
+      break;
+    }
+    float wbest = best;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wbest = fminf(wbest, __shfl_xor(wbest, o, 64));
+    const float bound = fmaxf(scan_ring_bound(g, b, qx, qy, qz, L), box);
+    if (scan_walk_done(wbest, bound, slack, tau2)) {
+      done = true;
+      break;
+    }
+  }
+  if (!done)
+    for (int f = lane; f < nf; f += 64) test(f);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float od = __shfl_xor(best, o, 64);
+    const int of = __shfl_xor(face, o, 64);
+    nearest_merge(best, face, od, of);
+  }
+  return NearestFace{best, face};
+}
+
+// ROLE 0 of mesh3d_surface_near_kernel over the index: the same key into keys_v (atomicMin on the all-ones key the memset left:
+// the memset and the hit kernel do not change).  A walk that tau2_v ended early, or whose best is above tau2_v, writes none
+template <bool GATED>
+__global__ __launch_bounds__(64 * kScanGridQueries) void mesh3d_surface_near_grid_kernel(SurfaceGridArgs a) {
+  const int n = blockIdx.y, lane = threadIdx.x & 63;
+  const int qi = blockIdx.x * kScanGridQueries + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (qi >= a.V) return;
+  const size_t o = (size_t)n * a.V + qi;
+  const float qx = a.verts[3 * o], qy = a.verts[3 * o + 1], qz = a.verts[3 * o + 2];
+  float ux = 0.f, uy = 0.f, uz = 0.f;
+  if constexpr (GATED) {
+    ux = a.normals_v[3 * o];
+    uy = a.normals_v[3 * o + 1];
+    uz = a.normals_v[3 * o + 2];
+  }
+  const int f0 = a.t.foff[n], nf = a.t.foff[n + 1] - f0;
+  const ScanGrid g = a.ix.grids[n];
+  const NearestFace h = grid_nearest<GATED, false>(g, a.ix, reinterpret_cast<const float4*>(a.target_tris + f0), nullptr, nullptr, nf, qx,
+                                                   qy, qz, ux, uy, uz, a.cc_v, a.tau2_v, lane);
+  if (lane == 0 && scan_key_written(h.d2, h.face, a.tau2_v))
+    atomicMin(&a.keys_v[o], ((unsigned long long)__float_as_uint(h.d2) << 32) | (unsigned)h.face);
+}
+
+// mesh3d_surface_dist_kernel<0> over the index: vert_dist = sqrt(least d^2), the records formed as that kernel forms them
+__global__ __launch_bounds__(64 * kScanGridQueries) void mesh3d_surface_dist_grid_kernel(SurfaceGridArgs a) {
+  const int n = blockIdx.y, lane = threadIdx.x & 63;
+  const int qi = blockIdx.x * kScanGridQueries + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (qi >= a.V) return;
+  const size_t o = (size_t)n * a.V + qi;
+  const float qx = a.verts[3 * o], qy = a.verts[3 * o + 1], qz = a.verts[3 * o + 2];
+  const int f0 = a.t.foff[n], nf = a.t.foff[n + 1] - f0;
+  const ScanGrid g = a.ix.grids[n];
+  const NearestFace h = grid_nearest<false, true>(g, a.ix, nullptr, a.t.faces + 3 * (size_t)f0, a.t.verts + 3 * (size_t)a.t.voff[n], nf,
+                                                  qx, qy, qz, 0.f, 0.f, 0.f, 0.f, INFINITY, lane);
+  if (lane == 0) a.vert_dist[o] = sqrtf(h.d2);
+}
+
 // ---- Adam on all trained parameters of a Stage.step in one launch ----------------------------------------------------
 // torch.optim.Adam (adam_update) over the trained parameters, one launch (Fit3dAdamArgs: smalfit_plan.h, beside plan_fit3d, which
 // sizes its segments)

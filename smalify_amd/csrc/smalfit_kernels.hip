@@ -38,6 +38,7 @@
 
 #include "smalfit_internal.h"
 #include "mesh3d_math.h"
+#include "mesh3d_grid.h"
 #include "smalfit_plan.h"
 
 namespace smalfit {

@@ -46,6 +46,10 @@ struct smalfit_mesh_targets {
   const ScanTri* tris = nullptr;   // packed [sum F]: the staged records of the surface term's vertex -> surface scan, in the blob
   int max_faces = 0;               // of the largest mesh: what that scan's slice count is sized by
   const unsigned char* bflags = nullptr;   // packed [sum F]: boundary_flags of every mesh, beside the records
+  // the scan index (smalfit_mesh_targets_build_index), or none: one allocation of its own, the grids and their shared arrays in it
+  void* index = nullptr;
+  ScanIndexDev ix{};
+  std::vector<smalfit_scan_index_stats> index_stats;   // per mesh, kept for smalfit_mesh_targets_index_stats
 };
 
 // (gated, robust) -> the template instantiation: f is called with the two flags as std::bool_constant
@@ -68,6 +72,16 @@ static void launch_surface_near(bool gated, const Grid3& g3, hipStream_t st, con
 template <int ROLE>
 static void launch_surface_hit(bool gated, bool robust, const Grid2& g2, hipStream_t st, const SurfaceTermArgs& k) {
   with_flags(gated, robust, [&](auto g, auto r) { mesh3d_surface_hit_kernel<ROLE, g.value, r.value><<<dim3(g2.x, g2.y), kMeshBlock, 0, st>>>(k); });
+}
+
+// the vertex direction over targets with a scan index: what the walk reads of the term's arguments
+static void launch_surface_near_grid(bool gated, const smalfit_mesh_targets* t, hipStream_t st, const SurfaceTermArgs& k) {
+  SurfaceGridArgs a{};
+  a.N = k.N; a.V = k.V; a.verts = k.verts; a.t = k.t; a.target_tris = k.target_tris; a.ix = t->ix;
+  a.keys_v = k.keys_v; a.normals_v = k.normals_v; a.cc_v = k.cc_v; a.tau2_v = k.tau2_v;
+  const Grid2 g = scan_grid_near_grid(k.V, k.N);
+  if (gated) mesh3d_surface_near_grid_kernel<true><<<dim3(g.x, g.y), 64 * kScanGridQueries, 0, st>>>(a);
+  else mesh3d_surface_near_grid_kernel<false><<<dim3(g.x, g.y), 64 * kScanGridQueries, 0, st>>>(a);
 }
 
 // one run of the surface term: the block (validated by the callers), what it is evaluated on, and what rides along
@@ -133,8 +147,13 @@ static int run_surface_term(smalfit_mesh_objective* m, const smalfit_mesh_target
       mesh3d_vertex_normal_kernel<<<dim3(gn.x, gn.y), kMeshBlock, 0, st>>>(k);
       LAUNCH_OK("mesh3d_vertex_normal_kernel");
     }
-    launch_surface_near<0>(gp.cos_vert, surface_near_grid(k.V, t->max_faces, k.N), st, k);
-    LAUNCH_OK("mesh3d_surface_near_kernel<0>");
+    if (t->index) {   // the targets carry a scan index: the same keys by the walk over it
+      launch_surface_near_grid(gp.cos_vert, t, st, k);
+      LAUNCH_OK("mesh3d_surface_near_grid_kernel");
+    } else {
+      launch_surface_near<0>(gp.cos_vert, surface_near_grid(k.V, t->max_faces, k.N), st, k);
+      LAUNCH_OK("mesh3d_surface_near_kernel<0>");
+    }
     launch_surface_hit<0>(gp.any, rp.surface_vert, hv, st, k);
     LAUNCH_OK("mesh3d_surface_hit_kernel<0>");
   }
@@ -437,7 +456,77 @@ int smalfit_mesh_targets_create(int num_meshes, const int* vert_counts, const in
 void smalfit_mesh_targets_destroy(smalfit_mesh_targets* t) {
   if (!t) return;
   if (t->blob) (void)hipFree(t->blob);
+  if (t->index) (void)hipFree(t->index);
   delete t;
+}
+
+// ---- the scan index: a grid per target mesh, built on the host ----------------------------------------------------------------
+// The handle keeps no host copy of its meshes: the builder reads offsets, vertices and faces back from the device, once per
+// build.  The grids, every mesh's CSR and the oversize lists go up as one blob of their own; the handle changes only after all
+// of it is in place
+int smalfit_mesh_targets_build_index(smalfit_mesh_targets* t, const smalfit_scan_index_args* a) {
+  const char* who = "smalfit_mesh_targets_build_index";
+  if (refused(who, null_argument_refusal(t && a))) return 1;
+  const int N = t->d.N;
+  std::vector<int> voff(N + 1), foff(N + 1);
+  HIP_OK(hipMemcpy(voff.data(), t->d.voff, voff.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(foff.data(), t->d.foff, foff.size() * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<float> verts((size_t)voff[N] * 3);
+  std::vector<int> faces((size_t)foff[N] * 3);
+  HIP_OK(hipMemcpy(verts.data(), t->d.verts, verts.size() * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(faces.data(), t->d.faces, faces.size() * sizeof(int), hipMemcpyDeviceToHost));
+  if (refused(who, scan_index_args_refusal(a, ScanIndexFacts{verts.data(), verts.size()}))) return 1;
+  const float scale = a->cell_scale > 0.f ? a->cell_scale : kScanCellScale;
+  std::vector<ScanGrid> grids(N);
+  std::vector<int> cell_off, cell_face, oversize;
+  std::vector<smalfit_scan_index_stats> stats(N);
+  for (int n = 0; n < N; ++n) {
+    ScanGridHost h;
+    if (refused(who, build_scan_grid(verts.data() + 3 * (size_t)voff[n], voff[n + 1] - voff[n], faces.data() + 3 * (size_t)foff[n],
+                                     foff[n + 1] - foff[n], scale, h)))
+      return 1;
+    if (cell_off.size() + h.cell_off.size() > 0x7fffffffull || cell_face.size() + h.cell_face.size() > 0x7fffffffull)
+      return refused(who, "scan index needs more than 2^31 - 1 entries");
+    h.g.cell_base = (int)cell_off.size();
+    h.g.entry_base = (int)cell_face.size();
+    h.g.over_base = (int)oversize.size();
+    for (int off : h.cell_off) cell_off.push_back(h.g.entry_base + off);
+    cell_face.insert(cell_face.end(), h.cell_face.begin(), h.cell_face.end());
+    oversize.insert(oversize.end(), h.oversize.begin(), h.oversize.end());
+    grids[n] = h.g;
+    smalfit_scan_index_stats& s = stats[n];
+    s.struct_size = (unsigned)sizeof(s);
+    for (int k = 0; k < 3; ++k) s.dims[k] = h.g.dims[k];
+    s.cells = h.g.cells; s.occupied_cells = h.occupied; s.entries = (int)h.cell_face.size();
+    s.oversize = (int)h.oversize.size(); s.largest_cell = h.largest;
+    s.bytes = sizeof(ScanGrid) + (h.cell_off.size() + h.cell_face.size() + h.oversize.size()) * sizeof(int);
+  }
+  if (cell_face.empty()) cell_face.push_back(0);   // keep every carve non-empty
+  if (oversize.empty()) oversize.push_back(0);
+  Blob b;
+  const size_t o_g = b.add(grids.data(), grids.size() * sizeof(ScanGrid));
+  const size_t o_o = b.add(cell_off.data(), cell_off.size() * sizeof(int));
+  const size_t o_f = b.add(cell_face.data(), cell_face.size() * sizeof(int));
+  const size_t o_v = b.add(oversize.data(), oversize.size() * sizeof(int));
+  unsigned char* base = upload_blob(b, who);
+  if (!base) return 1;
+  if (t->index) {   // a rebuild: nothing may still be walking the old one
+    (void)hipDeviceSynchronize();
+    (void)hipFree(t->index);
+  }
+  t->index = base;
+  t->ix.grids = (const ScanGrid*)(base + o_g); t->ix.cell_off = (const int*)(base + o_o);
+  t->ix.cell_face = (const int*)(base + o_f); t->ix.oversize = (const int*)(base + o_v);
+  t->index_stats = std::move(stats);
+  return 0;
+}
+
+int smalfit_mesh_targets_index_stats(const smalfit_mesh_targets* t, int mesh, smalfit_scan_index_stats* out) {
+  const char* who = "smalfit_mesh_targets_index_stats";
+  if (refused(who, null_handle_refusal(t != nullptr))) return 1;
+  if (refused(who, scan_index_stats_refusal(out, t->index != nullptr, mesh, t->d.N))) return 1;
+  *out = t->index_stats[mesh];
+  return 0;
 }
 
 int smalfit_mesh_targets_sample(smalfit_mesh_targets* t, void* stream, int num_points, unsigned long long seed,
@@ -471,8 +560,16 @@ int smalfit_mesh_score(smalfit_mesh_objective* m, smalfit_mesh_targets* t, void*
   k.sums = a->sums; k.within = a->within; k.T = a->num_thresholds;
   for (int i = 0; i < k.T; ++i) k.thr[i] = a->thresholds[i];
   const Grid2 g0 = surface_dist_grid(k.V, k.N);
-  mesh3d_surface_dist_kernel<0><<<dim3(g0.x, g0.y), 256, 0, st>>>(k);
-  LAUNCH_OK("mesh3d_surface_dist_kernel<0>");
+  if (t->index) {   // the targets carry a scan index: the same distances by the walk over it
+    SurfaceGridArgs ga{};
+    ga.N = k.N; ga.V = k.V; ga.verts = k.verts; ga.t = k.t; ga.ix = t->ix; ga.vert_dist = k.vert_dist; ga.tau2_v = INFINITY;
+    const Grid2 gg = scan_grid_dist_grid(k.V, k.N);
+    mesh3d_surface_dist_grid_kernel<<<dim3(gg.x, gg.y), 64 * kScanGridQueries, 0, st>>>(ga);
+    LAUNCH_OK("mesh3d_surface_dist_grid_kernel");
+  } else {
+    mesh3d_surface_dist_kernel<0><<<dim3(g0.x, g0.y), 256, 0, st>>>(k);
+    LAUNCH_OK("mesh3d_surface_dist_kernel<0>");
+  }
   if (k.S > 0) {
     const Grid2 g1 = surface_dist_grid(k.S, k.N);
     mesh3d_surface_dist_kernel<1><<<dim3(g1.x, g1.y), 256, 0, st>>>(k);

@@ -354,6 +354,34 @@ inline Grid2 surface_hit_grid(int queries, int N) { return Grid2{mesh_element_bl
 // SIMDs at one mesh, and the gather is as long as a chamfer scan)
 constexpr int kSurfaceGradWaves = 16;
 inline Grid2 surface_grad_grid(int V, int N) { return Grid2{mesh_query_blocks(V), N}; }
+// the vertex direction over targets that carry a scan index (mesh3d_grid.h): one WAVE per query, kScanGridQueries queries per
+// 256-thread block -- a query's candidates come in rings of cells, 64 at a time, and ring counts differ from query to query, so a
+// lane per query would diverge on every load; no slices, no LDS.  The same grid serves the term's scan and the score's
+constexpr int kScanGridQueries = 4;
+inline Grid2 scan_grid_near_grid(int V, int N) { return Grid2{(V + kScanGridQueries - 1) / kScanGridQueries, N}; }
+inline Grid2 scan_grid_dist_grid(int V, int N) { return scan_grid_near_grid(V, N); }
+// -> why smalfit_mesh_targets_build_index refuses (the text behind "smalfit_mesh_targets_build_index: "), or nullptr; reads the
+// num_floats coordinates of the handle's target vertices
+struct ScanIndexFacts {
+  const float* verts;
+  size_t num_floats;
+};
+inline const char* scan_index_args_refusal(const smalfit_scan_index_args* a, const ScanIndexFacts& f) {
+  if (a->struct_size != (unsigned)sizeof(smalfit_scan_index_args))
+    return "smalfit_scan_index_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (!(std::isfinite(a->cell_scale) && a->cell_scale >= 0.f)) return "cell_scale must be finite and >= 0 (0: the library's own)";
+  for (size_t i = 0; i < f.num_floats; ++i)
+    if (!std::isfinite(f.verts[i])) return "scan index needs finite target vertices";
+  return nullptr;
+}
+inline const char* scan_index_stats_refusal(const smalfit_scan_index_stats* out, bool has_index, int mesh, int num_meshes) {
+  if (!out) return "null argument";
+  if (out->struct_size != (unsigned)sizeof(smalfit_scan_index_stats))
+    return "smalfit_scan_index_stats.struct_size does not match this library (built against another smalfit.h?)";
+  if (!has_index) return "the targets have no scan index (smalfit_mesh_targets_build_index)";
+  if (mesh < 0 || mesh >= num_meshes) return "mesh out of range";
+  return nullptr;
+}
 
 // ------------------------------------------------------------------------------------------------
 // the mesh objective's entry points: which arguments are refused (the text behind "<entry point>: " or nullptr, the first fault;

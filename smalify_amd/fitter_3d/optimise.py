@@ -33,6 +33,9 @@ def build_parser():
                              "metrics.json into results_dir")
     parser.add_argument("--metric_thresholds", type=float, nargs="+", default=list(DEFAULT_METRIC_THRESHOLDS),
                         help="distance thresholds of the F-score, in the units of the normalised targets (at most 8)")
+    parser.add_argument("--scan_index", action="store_true",
+                        help="build a grid over the target meshes for the vertex-to-surface scans (dense scan targets); the "
+                             "results are bit for bit those without it")
     return parser
 
 
@@ -49,7 +52,8 @@ def main(args, model_data=None, smal_data=None):
         for arg, val in (yaml_cfg.get("args") or {}).items():       # YAML args overwrite the command line
             setattr(args, arg, val)
 
-    mesh_names, target_meshes = load_meshes(mesh_dir=args.mesh_dir, frame_step=args.frame_step)
+    mesh_names, target_meshes = load_meshes(mesh_dir=args.mesh_dir, frame_step=args.frame_step,
+                                            scan_index=bool(getattr(args, "scan_index", False)))
     n_batch = len(target_meshes)
     os.makedirs(args.results_dir, exist_ok=True)
     manager = StageManager(out_dir=args.results_dir, labels=mesh_names)

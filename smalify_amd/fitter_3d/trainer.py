@@ -137,7 +137,7 @@ class Stage:
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes, mesh_names=[],
                  name="optimise", loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None,
-                 device="cuda", seed=0, iteration_offset=0, surface_gates=None, chamfer_gates=None, robust=None):
+                 device="cuda", seed=0, iteration_offset=0, scan_index=False, surface_gates=None, chamfer_gates=None, robust=None):
         self.n_it = int(nits)
         self.name = name
         self.out_dir = out_dir
@@ -163,6 +163,11 @@ class Stage:
         # the Geman-McClure kernel on the matches the gates keep (include/smalfit.h): four scales, all off unless given, here or as
         # a `robust` block of the stage's YAML; with or without the gates
         self.robust = eng.robust(robust)
+        # a grid over the targets for the vertex -> surface scans of step() and metrics() (include/smalfit.h): for dense scan
+        # targets; it changes no result.  Built here, once per set of targets; the targets carry it from then on
+        self.scan_index = bool(scan_index)
+        if self.scan_index and not target_meshes.has_index:
+            target_meshes.build_index()
         if custom_lrs is not None:
             for attr in custom_lrs:
                 assert hasattr(smal_3d_fitter, attr), f"attr '{attr}' not in SMAL."

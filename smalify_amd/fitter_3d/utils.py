@@ -58,6 +58,21 @@ def normalise_verts(verts):
     return v / np.abs(v).max(0).max()
 
 
+def subdivide_mesh(verts, faces, times=1):
+    """midpoint subdivision, `times` times: every face becomes four, 4^times F faces on the same surface (numpy; a dense
+    stand-in for a scanner mesh in tests and tools/fit3d_bench.py --target-subdiv)"""
+    v, f = np.asarray(verts, np.float32).reshape(-1, 3), np.asarray(faces, np.int32).reshape(-1, 3)
+    for _ in range(int(times)):
+        e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)
+        ue, inv = np.unique(e, axis=0, return_inverse=True)
+        ab, bc, ca = (np.asarray(inv).reshape(-1).reshape(3, len(f)) + len(v)).astype(np.int32)
+        a, b, c = f.T
+        mid = (0.5 * (v[ue[:, 0]].astype(np.float64) + v[ue[:, 1]])).astype(np.float32)
+        f = np.concatenate([np.stack([a, ab, ca], 1), np.stack([ab, b, bc], 1), np.stack([ca, bc, c], 1), np.stack([ab, bc, ca], 1)])
+        v = np.concatenate([v, mid])
+    return np.ascontiguousarray(v, np.float32), np.ascontiguousarray(f, np.int32)
+
+
 class TargetMeshes:
     """The target meshes of a fit: host copies for plotting/saving + the device-resident sampler
     (the role pytorch3d.structures.Meshes plays in fitter_3d/utils.py:253 and trainer.py:209)."""
@@ -88,6 +103,18 @@ class TargetMeshes:
     def faces_list(self):
         return self.faces
 
+    def build_index(self, cell_scale=0.0):
+        """a grid over every target for the vertex -> surface scans (engine.MeshTargets.build_index): changes no result"""
+        self._dev.build_index(cell_scale)
+        return self
+
+    @property
+    def has_index(self):
+        return self._device_targets is not None and self._device_targets.has_index
+
+    def index_stats(self):
+        return self._dev.index_stats()
+
     def sample(self, num_points, seed, iteration, out=None):
         return self._dev.sample(num_points, seed, iteration, out=out)
 
@@ -98,9 +125,10 @@ class TargetMeshes:
         return self._dev.sample_attrs(num_points, seed, iteration, **kw)
 
 
-def load_meshes(mesh_dir: str, sorting=lambda arr: arr, n_meshes=None, frame_step=1, device="cuda:0"):
+def load_meshes(mesh_dir: str, sorting=lambda arr: arr, n_meshes=None, frame_step=1, device="cuda:0", scan_index=False):
     """Given a dir of .obj files, loads all and returns (mesh_names, target_meshes) like fitter_3d/utils.py:204-255.
-    NOTE as in the reference, the default `sorting` keeps os.listdir's order."""
+    NOTE as in the reference, the default `sorting` keeps os.listdir's order.  scan_index: also build the grid over the
+    targets (TargetMeshes.build_index; uploads them)."""
     file_list = [f for f in os.listdir(mesh_dir) if ".obj" in f]
     obj_list = sorting(file_list)[::frame_step]
     if n_meshes is not None:
@@ -114,7 +142,10 @@ def load_meshes(mesh_dir: str, sorting=lambda arr: arr, n_meshes=None, frame_ste
         all_verts.append(normalise_verts(v))
         all_faces.append(f)
     print(f"{len(all_verts)} target meshes loaded.")
-    return mesh_names, TargetMeshes(all_verts, all_faces)
+    targets = TargetMeshes(all_verts, all_faces)
+    if scan_index:
+        targets.build_index()
+    return mesh_names, targets
 
 
 # ---- figures (matplotlib; host side, outside the hot path) --------------------------------------------------------

@@ -5,7 +5,13 @@ share of each of the five C-ABI calls of a step (torch events on the launch stre
 
     python tools/fit3d_bench.py [--meshes 1 8 32] [--iters 300] [--surface [--gates]] [--chamfer-gates] [--robust]
 
-Prints one JSON line per batch size.  --surface adds the point-to-surface term both ways (w_point_surface = w_vert_surface = 1:
+    python tools/fit3d_bench.py --surface --target-subdiv K --scan-index [--gates] [--cell-scale X] [--near-warmup W]
+
+Prints one JSON line per batch size.  --target-subdiv K subdivides every stand-in target K times by midpoint subdivision (7774 x
+4^K faces: a dense scan).  --scan-index (with --surface) makes two handles of the same targets, one with the scan index and one
+without, and times `--iters` steps on each in alternating runs of one process, three runs each, at two states: "far" = the
+first steps of the stage from the template pose, "near" = the steps after --near-warmup steps of the same fit; one JSON line
+per (batch size, state, handle) with the index's statistics and its build time beside the rates.  --surface adds the point-to-surface term both ways (w_point_surface = w_vert_surface = 1:
 every step is smalfit_fit3d_step_surface) and two fields to the line; without it the run and the line are those of before.
 --gates (with --surface) switches every gate of that term on (GATES below: every step is smalfit_fit3d_step_gated) and adds the
 kept counts of the last step.  --chamfer-gates, alone or with the others, switches every gate of the chamfer term on (every step is
@@ -46,6 +52,50 @@ GATES = dict(max_dist_point=0.5, max_dist_vert=0.5, min_cos_point=0.0, min_cos_v
 ROBUST = dict(sigma_chamfer_point=0.5, sigma_chamfer_vert=0.5, sigma_surface_point=0.5, sigma_surface_vert=0.5)
 
 
+def scan_index_runs(args, md, smal_data, N):
+    """the indexed and the linear handle, alternating: -> the JSON lines of one batch size"""
+    import torch
+    from smalify_amd.fitter_3d import SMAL3DFitter, Stage, TargetMeshes
+    from smalify_amd.fitter_3d.utils import subdivide_mesh
+    meshes = [subdivide_mesh(v, np.asarray(md.faces), args.target_subdiv) for v in targets_for(md, N, seed=N)]
+    handles = {"linear": TargetMeshes([m[0] for m in meshes], [m[1] for m in meshes]),
+               "index": TargetMeshes([m[0] for m in meshes], [m[1] for m in meshes])}
+    t0 = time.perf_counter()
+    handles["index"].build_index(args.cell_scale)
+    build_ms = 1e3 * (time.perf_counter() - t0)
+    stats = handles["index"].index_stats()
+    weights = {"w_point_surface": 1.0, "w_vert_surface": 1.0}
+    times = {(st, h): [] for st in ("far", "near") for h in handles}
+    final = {}
+    for st, warm in (("far", 0), ("near", args.near_warmup)):
+        for rep in range(3):
+            for h, targets in handles.items():
+                fit = SMAL3DFitter(batch_size=N, shape_family=-1, model_data=md, smal_data=smal_data)
+                # (the warm-up runs on the indexed handle: the fit it reaches is the same to the bit, and it gets there sooner)
+                stage = Stage(warm + args.iters, "default", fit, handles["index"] if warm else targets, lr=0.01,
+                              custom_lrs={"joint_rot": 0.005}, loss_weights=weights, surface_gates=GATES if args.gates else None)
+                for i in range(warm):
+                    stage.step(i)
+                stage.target_meshes = targets
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(args.iters):
+                    stage.step(warm + i)
+                torch.cuda.synchronize()
+                times[(st, h)].append(1e3 * (time.perf_counter() - t0) / args.iters)
+                final[(st, h)] = float(stage.last_terms[4])
+                del stage, fit
+    lines = []
+    for (st, h), ms in times.items():
+        line = {"meshes": N, "target_subdiv": args.target_subdiv, "target_faces": int(len(meshes[0][1])), "state": st, "handle": h,
+                "iters": args.iters, "ms_per_iteration": ms, "final_total_loss": final[(st, h)], "gates": bool(args.gates)}
+        if h == "index":
+            line.update(cell_scale=args.cell_scale, build_ms=build_ms, index_stats=stats[0],
+                        index_bytes=int(sum(x["bytes"] for x in stats)))
+        lines.append(line)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", type=int, nargs="+", default=[1, 8, 32])
@@ -54,19 +104,34 @@ def main():
     ap.add_argument("--gates", action="store_true", help="with --surface: gate the term (truncation, compatibility, boundary)")
     ap.add_argument("--chamfer-gates", action="store_true", help="gate the chamfer term (truncation, compatibility, boundary)")
     ap.add_argument("--robust", action="store_true", help="the Geman-McClure kernel on every data term that runs")
+    ap.add_argument("--target-subdiv", type=int, default=0, help="subdivide every target this many times (7774 x 4^K faces)")
+    ap.add_argument("--scan-index", action="store_true", help="with --surface: the indexed handle against the linear one, alternating")
+    ap.add_argument("--cell-scale", type=float, default=0.0, help="with --scan-index: the grid's cell scale (0: the library's own)")
+    ap.add_argument("--near-warmup", type=int, default=300, help="with --scan-index: steps of the fit before the near state is timed")
     args = ap.parse_args()
     if args.gates and not args.surface:
         ap.error("--gates needs --surface")
+    if args.scan_index and not args.surface:
+        ap.error("--scan-index needs --surface")
     import torch
     from smalify_amd import synthetic
     from smalify_amd.fitter_3d import SMAL3DFitter, Stage, TargetMeshes
 
     md = synthetic.synthetic_model(seed=0, shape_family_id=-1)
     smal_data = synthetic.synthetic_smal_dicts(seed=0)[1]
+    from smalify_amd.fitter_3d.utils import subdivide_mesh
     for N in args.meshes:
+        if args.scan_index:
+            for line in scan_index_runs(args, md, smal_data, N):
+                print(json.dumps(line), flush=True)
+            continue
         fit = SMAL3DFitter(batch_size=N, shape_family=-1, model_data=md, smal_data=smal_data)
         tv = targets_for(md, N, seed=N)
-        targets = TargetMeshes(tv, [np.asarray(md.faces)] * N)
+        if args.target_subdiv:
+            sub = [subdivide_mesh(v, np.asarray(md.faces), args.target_subdiv) for v in tv]
+            targets = TargetMeshes([m[0] for m in sub], [m[1] for m in sub])
+        else:
+            targets = TargetMeshes(tv, [np.asarray(md.faces)] * N)
         weights = {"w_point_surface": 1.0, "w_vert_surface": 1.0} if args.surface else None
         stage = Stage(args.iters, "default", fit, targets, lr=0.01, custom_lrs={"joint_rot": 0.005}, loss_weights=weights,
                       surface_gates=GATES if args.gates else None, chamfer_gates=GATES if args.chamfer_gates else None,
