@@ -17,71 +17,7 @@ import torch.multiprocessing as mp
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
-
-class OracleLocalFitter:
-    """FusedFitter protocol on top of oracle.smal_oracle for frames [lo, hi) of a problem."""
-
-    def __init__(self, prob_full, params_full, lo, hi, window):
-        from oracle import smal_oracle as so
-        self.so = so
-        m = prob_full.m
-        self.prob = so.FitProblem(m, prob_full.S, prob_full.tj[lo:hi].numpy(), prob_full.vis[lo:hi].numpy(),
-                                  prob_full.sil[lo:hi].numpy(), prob_full.pose_prec.numpy(), prob_full.pose_mean.numpy(),
-                                  prob_full.pose_mask.numpy(), prob_full.shape_prec.numpy(), prob_full.shape_mean.numpy(),
-                                  window, True, frame_offset=lo, total_frames=prob_full.N)
-        self.N = hi - lo
-        self.p = {k: (v[lo:hi].clone() if v.shape[0] == prob_full.N and v.dim() > 1 else v.clone())
-                  for k, v in params_full.items()}
-        self.grads = {}
-        self.halo_prev = self.halo_next = None
-        self.losses = torch.zeros(8, dtype=torch.float64)
-        self._shared = torch.zeros(26, dtype=torch.float64)
-
-    def trainable(self, stage_id):
-        return self.so.trainable_names(stage_id)
-
-    def begin_stage(self, stage_id):
-        self.opt = None
-        self.stage_id = stage_id
-
-    def boundary_records(self):
-        idx = [0, self.N - 1]
-        return torch.cat([self.p["global_rotation"][idx], self.p["joint_rotations"][idx].reshape(2, 102),
-                          self.p["trans"][idx]], 1).contiguous()
-
-    def shared_grad(self):
-        return self._shared
-
-    def evaluate(self, weights, w_temp, stage_id, want=None):
-        so = self.so
-        names = self.trainable(stage_id) if want is None else want
-        leaf = {k: v.detach().clone().requires_grad_(k in names) for k, v in self.p.items()}
-        total, _ = so.epoch_loss(self.prob, leaf, weights, w_temp)
-
-        def pair(a, b):       # temporal terms of one adjacent pair, a = (theta 105 | trans 3) records
-            return w_temp * (((a[:3] - b[:3]) ** 2).mean() + ((a[3:105] - b[3:105]) ** 2).mean()
-                             + ((a[105:] - b[105:]) ** 2).mean())
-
-        def rec(i):
-            return torch.cat([leaf["global_rotation"][i], leaf["joint_rotations"][i].reshape(102), leaf["trans"][i]])
-
-        if self.halo_next is not None:
-            total = total + pair(rec(self.N - 1), self.halo_next)
-        if self.halo_prev is not None:
-            total = total + pair(self.halo_prev, rec(0))
-        total.backward()
-        self.grads = {k: leaf[k].grad for k in names}
-        if "betas" in self.grads:
-            self._shared = torch.cat([self.grads["betas"], self.grads["log_beta_scales"]]).contiguous()
-        return self.losses
-
-    def apply_adam(self, names, lr, advance=True):   # the oracle's Adam counts steps per tensor
-        so = self.so
-        if self.opt is None:
-            self.opt = so.Adam(so.PARAM_ORDER, lr=lr)
-        if "betas" in names:
-            self.grads["betas"], self.grads["log_beta_scales"] = self._shared[:20].clone(), self._shared[20:].clone()
-        self.opt.step(self.p, {k: self.grads[k] for k in names})
+from tests.shard_cases import OracleLocalFitter  # noqa: E402  (the float64 oracle behind the local-fitter protocol; RankSim runs it too)
 
 
 def _problem(N=4, window=2):
