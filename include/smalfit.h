@@ -449,7 +449,13 @@ int smalfit_mesh_objective_counts(const smalfit_mesh_objective* objective, int* 
  * with weights[i] > 0 (weights: host, order w_chamfer, w_edge, w_normal, w_laplacian; trainer.py:31,203).
  * lbs_verts (N,V,3)  trans (N,3)  deform_verts (N,V,3)  points (N,S,3) (ignored when w_chamfer <= 0)
  * -> verts_out (N,V,3) or NULL, losses (5, device), dverts (N,V,3) = d total / d verts (also the gradient of
- * deform_verts), dtrans (N,3).  Chain dverts through smalfit_lbs_backward for the SMAL parameters. */
+ * deform_verts), dtrans (N,3).  Chain dverts through smalfit_lbs_backward for the SMAL parameters.
+ * Units and place: nothing is normalised.  The chamfer, edge and Laplacian terms and every gradient are built from differences
+ * of coordinates: a translation that is exact in float32 changes no bit of them, and at a unit of length 2^k times another they are
+ * the exact multiples (4^k, 4^k, 2^k) of their bits while no squared difference underflows and |n|^2 |n'|^2 of no face pair
+ * overflows (k of about -45 ... 35 on a mesh of extent 1).  The normal term is cos = <n, n'> / sqrt(max(|n|^2 |n'|^2, 1e-16)), torch's
+ * clamp on a length^8: it depends on the unit.  Between two units in which no pair is under the clamp it keeps its bits (its
+ * gradient times 2^-k); a pair with a zero normal reads 1 - cos = 1 exactly, a collapsed face included. */
 int smalfit_mesh_objective_eval(smalfit_mesh_objective* objective, void* stream, int num_meshes,
                                 const float* lbs_verts, const float* trans, const float* deform_verts,
                                 const float* points, int num_points, const float* weights /*host*/,
@@ -569,6 +575,9 @@ int smalfit_mesh_objective_eval_gated(smalfit_mesh_objective* objective, void* s
  *                    - the squared distance to the plane, when the normal n = (b - a) x (c - a) is not zero and p projects
  *                      inside: <(b - a) x (p - a), n>, <(c - b) x (p - b), n> and <(a - c) x (p - c), n> are all >= 0.
  *                  A degenerate triangle (collinear or coincident corners) is exactly its three segments.  float32 throughout.
+ *                  Every term is a difference of coordinates: an exact translation changes no bit, and at a unit of length 2^k
+ *                  times another the distances are the exact multiple 2^k of their bits while the plane product (distance x
+ *                  twice the face's area, squared: a length^6) and |n|^2 stay normal -- k of about -16 ... 22 at extent 1.
  *   vert_dist      [n][v] = the least distance from fitted vertex v of mesh n to the triangles of TARGET mesh n
  *   point_dist     [n][s] = the least distance from points[n][s] to the triangles of the FITTED mesh n (verts[n] with the
  *                  faces given to the objective's create call)

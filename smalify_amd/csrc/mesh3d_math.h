@@ -528,21 +528,22 @@ struct RingEval {
 
 SMALFIT_HD void vertex_ring(const float* verts /* [V][3] of one mesh */, int v, const int* nbr, int deg, RingEval& r) {
   const float x = verts[3 * v], y = verts[3 * v + 1], z = verts[3 * v + 2];
-  float sx = 0.f, sy = 0.f, sz = 0.f, es = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
+  float es = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
   for (int k = 0; k < deg; ++k) {
     const int u = nbr[k];
     const float ux = verts[3 * u], uy = verts[3 * u + 1], uz = verts[3 * u + 2];
     const float dx = x - ux, dy = y - uy, dz = z - uz;
     es += fmaf(dz, dz, fmaf(dy, dy, dx * dx));
     gx += dx; gy += dy; gz += dz;
-    sx += ux; sy += uy; sz += uz;
   }
   r.edge_sum = es;
   r.edge_grad[0] = gx; r.edge_grad[1] = gy; r.edge_grad[2] = gz;
+  // mean(ring) - v = -(sum over the ring of (v - u)) / deg: from the differences the edge term already sums, never from a sum
+  // of absolute coordinates -- that form lost the digits of |v| / |mean(ring) - v| on a mesh that stands far from the origin
   float lx = 0.f, ly = 0.f, lz = 0.f;
   if (deg > 0) {
     const float inv = 1.0f / (float)deg;
-    lx = sx * inv - x; ly = sy * inv - y; lz = sz * inv - z;
+    lx = -(gx * inv); ly = -(gy * inv); lz = -(gz * inv);
   }
   const float n2 = fmaf(lz, lz, fmaf(ly, ly, lx * lx));
   const float n = sqrtf(n2);
@@ -578,6 +579,19 @@ SMALFIT_HD void cross3(const float a[3], const float b[3], float o[3]) {
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// a x b with every product rounded on its own, never contracted to fma(a1, b2, -(a2 b1)): a x a is then the zero vector
+// exactly.  A face collapsed onto its edge (a == p1) has n0 = e x e; contracted, that is the rounding error of a product, ~6e-8 |e|^2,
+// and under the clamp r = 1e8 multiplies it back to |e|^2 |n1|: a cosine of order 1 on a mesh of extent 16 where torch gives 0
+SMALFIT_HD void cross3_rounded(const float a[3], const float b[3], float o[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float p0 = a[1] * b[2], q0 = a[2] * b[1], p1 = a[2] * b[0], q1 = a[0] * b[2], p2 = a[0] * b[1], q2 = a[1] * b[0];
+  o[0] = p0 - q0;
+  o[1] = p1 - q1;
+  o[2] = p2 - q2;
+}
+
 SMALFIT_HD float face_pair_eval(const float* p0, const float* p1, const float* pa, const float* pb, float grad[4][3]) {
   float e[3], ea[3], eb[3], n0[3], n1[3];
 #pragma unroll
@@ -586,8 +600,8 @@ SMALFIT_HD float face_pair_eval(const float* p0, const float* p1, const float* p
     ea[k] = pa[k] - p0[k];
     eb[k] = pb[k] - p0[k];
   }
-  cross3(e, ea, n0);
-  cross3(eb, e, n1);                     // -(e x eb)
+  cross3_rounded(e, ea, n0);
+  cross3_rounded(eb, e, n1);             // -(e x eb)
   const float w12 = n0[0] * n1[0] + n0[1] * n1[1] + n0[2] * n1[2];
   const float w1 = n0[0] * n0[0] + n0[1] * n0[1] + n0[2] * n0[2];
   const float w2 = n1[0] * n1[0] + n1[1] * n1[1] + n1[2] * n1[2];
