@@ -818,6 +818,85 @@ int smalfit_fit3d_step_robust(smalfit_engine* engine, smalfit_mesh_objective* ob
                               const smalfit_surface_gate_args* surface_gate, const smalfit_chamfer_gate_args* chamfer_gate,
                               const smalfit_robust_args* robust);
 
+/* ---- rigid pre-alignment: multi-start iterative closest point ----------------------------------------------------------------
+ * Every term above assumes that the fitted mesh already stands roughly where its target stands and faces the same way; the
+ * chamfer term is a local descent and settles back to front when it does not.  This call finds the rigid motion [R | t] that
+ * carries vertices x_v, v < V, onto points p_s, s < S, by ICP from K starting orientations at once, and says which start ended
+ * best.  THIS PROJECT'S definitions (the reference has none).  A handle of its own: no engine, no objective, no targets; any
+ * (N,V,3) vertices against any (N,S,3) points.  Everything is per mesh n and per start k, in float32.
+ *   transform      12 floats, three rows [R_i0 R_i1 R_i2 t_i].  z = R x + t is formed, per coordinate i, by the one chain
+ *                  fma(R_i2, x_2, fma(R_i1, x_1, fma(R_i0, x_0, t_i))).
+ *   means          c_X, c_P: the means of the vertices and of the points of mesh n.  Each coordinate is summed by 256 lanes, lane l
+ *                  taking the elements l, l + 256, ... in ascending order; the 64 lanes of a wave are added by a butterfly
+ *                  (xor 32, 16, ... 1), the four waves in wave order; one float32 divide by the count.
+ *   start          with `starts`: R = R_k, t_i = c_P_i - (R_k c_X)_i, the product by the chain fma(R_i2, c_2, fma(R_i1, c_1,
+ *                  R_i0 c_0)): z = R_k (x - c_X) + c_P.  With `start_transforms`: the given 12 floats as they are.
+ *   built-in starts   starts == NULL: the 24 rotations of the cube, the signed permutation matrices of determinant +1, in this
+ *                  order: the permutations (a, b, c) of (0, 1, 2) in lexicographic order (012, 021, 102, 120, 201, 210), within
+ *                  each the sign triples (s_0, s_1, s_2) in the order +++, ++-, +-+, +--, -++, -+-, --+, ---, keeping those for
+ *                  which the matrix with R[0][a] = s_0, R[1][b] = s_1, R[2][c] = s_2 (zero elsewhere) has determinant +1.  Start
+ *                  0 is the identity.
+ *   one iteration  1. z_v = R x_v + t.
+ *                  2. nn'(v) = the point nearest to z_v, nn(s) = the z nearest to p_s.  d^2 and the tie rule are the chamfer
+ *                     term's: fma(dz, dz, fma(dy, dy, dx dx)), the lowest index among equal d^2.
+ *                  3. the pairs (x_v, p_nn'(v)), each of weight w_vert / V, and (x_nn(s), p_s), each of weight w_point / S.  A
+ *                     direction of weight 0 is not scanned.
+ *                  4. R, t = argmin sum w |R x + t - p|^2 by Horn's closed form: on coordinates centred at c_X and c_P every
+ *                     block of 64 queries sums 1, x, p, x p^T, |x|^2, |p|^2 and d^2 over its pairs (a wave butterfly); the
+ *                     blocks are added in block order, then the two directions as fma(w_point / S, point sum, (w_vert / V)
+ *                     vertex sum).  With W the sum of the weights, the weighted means mx, mp and H = sum w x p^T - W mx mp^T, the
+ *                     unit quaternion of R is the eigenvector of Horn's symmetric 4x4 matrix of H with the largest eigenvalue,
+ *                     found by 8 cyclic Jacobi sweeps (6 rotations each, pivots (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)); the largest
+ *                     diagonal entry wins, the lowest index among equal ones.  The quaternion is normalised and R formed from
+ *                     it: det R = +1 always, a reflection is never returned.  t = (c_P + mp) - R (c_X + mx).
+ *                  5. rank test: with l1 >= l2 the two largest eigenvalues found, the rotation is DETERMINED when
+ *                       l1 - l2 > 1e-5 sqrt(sum w |x|^2  sum w |p|^2)
+ *                     in float32 (the centred sums of 4.; a NaN compares false).  Coincident or collinear points or vertices
+ *                     fail it: the previous R is kept, only t is updated by the line above, and kept_rotation counts the event.
+ *                     Every output stays finite for finite input.
+ *   cost, score    w_point / S sum_s d^2 + w_vert / V sum_v d^2 of a pair of scans, by the sums of 4.  `history` holds the cost
+ *                  before every solve and after the last; `scores` is the cost under the final transform: one more pair of
+ *                  scans after the last solve.  A skipped direction adds nothing.
+ *   best           the lowest score, the lowest k among equal bits; a NaN score never wins (all NaN: 0).
+ *   determinism    no atomics, every sum in a fixed order: the same call gives the same bits, and I iterations in one call give
+ *                  the bits of I one-iteration calls chained through transforms -> start_transforms.
+ * Everything is enqueued on `stream`; nothing synchronises.  A refused block launches nothing and leaves every output alone.  The
+ * call uses the handle's work buffers: it must not overlap another call on the same handle.  Non-finite coordinates stay in
+ * bounds, value unspecified.
+ * The handle holds the work buffers for up to max_meshes (at most 65535) meshes of up to max_verts vertices and max_points points
+ * and up to max_starts (at most 64) starts; a call may be smaller in every one of them and gives the same bits on a larger handle.
+ * The two weights reach the device as the float32 quotients w_vert / V and w_point / S, one divide each on the host.
+ * Not here: scale (similarity) estimation, trimming or robust weights, normals, the scan index. */
+typedef struct smalfit_rigid_aligner smalfit_rigid_aligner;
+#define SMALFIT_MAX_RIGID_STARTS 64
+#define SMALFIT_NUM_CUBE_ROTATIONS 24
+typedef struct smalfit_rigid_align_args {
+  unsigned struct_size;          /* sizeof(smalfit_rigid_align_args) of the caller's header; checked before any other field */
+  int num_meshes;                /* N in 1 .. the handle's max_meshes */
+  int num_verts;                 /* V in 1 .. the handle's max_verts */
+  int num_points;                /* S in 1 .. the handle's max_points */
+  const float* verts;            /* (N,V,3) device: x_v */
+  const float* points;           /* (N,S,3) device: p_s */
+  int num_starts;                /* K in 1 .. min(64, the handle's max_starts) */
+  int iterations;                /* I in 0 .. 1000; 0 scores the starts only */
+  const float* starts;           /* HOST (K,3,3) row-major proper rotations (finite, orthonormal with determinant +1 to within 1e-4),
+                                    or NULL: the 24 built-in ones, and K must be 24 (unless start_transforms is given) */
+  const float* start_transforms; /* optional, device (N,K,12): used as they are; `starts` must then be NULL */
+  float w_point;                 /* weight of the pairs (x_nn(s), p_s); >= 0 and finite */
+  float w_vert;                  /* weight of the pairs (x_v, p_nn'(v)); >= 0 and finite; not both 0 */
+  float* transforms;             /* (N,K,12): the transform of every start after I iterations */
+  float* scores;                 /* (N,K): the cost of every start under its final transform */
+  int* best;                     /* (N) */
+  float* best_transform;         /* (N,12): transforms[n][best[n]] */
+  int* kept_rotation;            /* (N,K): how many of a start's I solves kept the previous rotation */
+  float* history;                /* optional (N,K,I+1) */
+  int* vert_nn;                  /* optional (N,K,V): nn'(v) of the score's scans; left alone when w_vert == 0 */
+  int* point_nn;                 /* optional (N,K,S): nn(s) of the score's scans; left alone when w_point == 0 */
+} smalfit_rigid_align_args;
+int smalfit_rigid_aligner_create(int max_meshes, int max_verts, int max_points, int max_starts, smalfit_rigid_aligner** out);
+void smalfit_rigid_aligner_destroy(smalfit_rigid_aligner* aligner);
+int smalfit_rigid_align(smalfit_rigid_aligner* aligner, void* stream, const smalfit_rigid_align_args* args);
+
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137
  * t = 1-based step count; eps outside the bias-corrected sqrt, as torch does */

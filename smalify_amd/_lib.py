@@ -168,6 +168,23 @@ class ScanIndexStats(C.Structure):
         self.struct_size = C.sizeof(ScanIndexStats)
 
 
+MAX_RIGID_STARTS = 64             # SMALFIT_MAX_RIGID_STARTS
+NUM_CUBE_ROTATIONS = 24           # SMALFIT_NUM_CUBE_ROTATIONS
+
+
+class RigidAlignArgs(C.Structure):
+    """smalfit_rigid_align_args: multi-start ICP of (N,V,3) vertices onto (N,S,3) points (smalfit_rigid_align)"""
+    _fields_ = [("struct_size", C.c_uint), ("num_meshes", C.c_int), ("num_verts", C.c_int), ("num_points", C.c_int),
+                ("verts", C.c_void_p), ("points", C.c_void_p), ("num_starts", C.c_int), ("iterations", C.c_int),
+                ("starts", C.c_void_p), ("start_transforms", C.c_void_p), ("w_point", C.c_float), ("w_vert", C.c_float),
+                ("transforms", C.c_void_p), ("scores", C.c_void_p), ("best", C.c_void_p), ("best_transform", C.c_void_p),
+                ("kept_rotation", C.c_void_p), ("history", C.c_void_p), ("vert_nn", C.c_void_p), ("point_nn", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(RigidAlignArgs)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -287,6 +304,9 @@ SIGNATURES = {
                                        C.POINTER(ChamferGateArgs), C.POINTER(RobustArgs)]),
     "smalfit_mesh_targets_build_index": (_I, [_VP, C.POINTER(ScanIndexArgs)]),
     "smalfit_mesh_targets_index_stats": (_I, [_VP, _I, C.POINTER(ScanIndexStats)]),
+    "smalfit_rigid_aligner_create": (_I, [_I, _I, _I, _I, C.POINTER(_VP)]),
+    "smalfit_rigid_aligner_destroy": (None, [_VP]),
+    "smalfit_rigid_align": (_I, [_VP, _VP, C.POINTER(RigidAlignArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
@@ -296,7 +316,8 @@ LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "sm
                           "smalfit_mesh_targets_sample_normals", "smalfit_mesh_targets_sample_attrs",
                           "smalfit_mesh_objective_eval_gated", "smalfit_fit3d_step_partial", "smalfit_mesh_objective_eval_robust",
                           "smalfit_mesh_surface_eval_robust", "smalfit_fit3d_step_robust", "smalfit_mesh_targets_build_index",
-                          "smalfit_mesh_targets_index_stats"])
+                          "smalfit_mesh_targets_index_stats", "smalfit_rigid_aligner_create", "smalfit_rigid_aligner_destroy",
+                          "smalfit_rigid_align"])
 
 
 class SmalfitError(RuntimeError):

@@ -9,8 +9,8 @@
 //   with 35 entries per row, the code path is the same and the sums run in the same joint order.
 //
 // One translation unit: this file holds the shared device helpers and includes the kernels by subsystem
-// (kernels_lbs_forward.inc, kernels_raster.inc, kernels_color.inc, kernels_lbs_backward.inc, kernels_mesh3d.inc), then
-// the host side (smalfit_launch.inc, smalfit_mesh3d.inc: pointer plumbing, allocations, copies, launches, C entry points).  What
+// (kernels_lbs_forward.inc, kernels_raster.inc, kernels_color.inc, kernels_lbs_backward.inc, kernels_mesh3d.inc, kernels_rigid_align.inc), then
+// the host side (smalfit_launch.inc, smalfit_mesh3d.inc, smalfit_rigid_align.inc: pointer plumbing, allocations, copies, launches, C entry points).  What
 // the host DECIDES before it launches -- loop, fold, routes, the plan of an evaluation and of a fit3d step, kernel forms, grids,
 // refused arguments -- is smalfit_plan.h, and what it COMPUTES before it uploads -- a model's tables, a mesh's topology -- is
 // smal_model_pack.h and mesh3d_topology.h: plain C++ that the CPU tests compile and call (tests/host_plan_shim.cpp,
@@ -39,6 +39,7 @@
 #include "smalfit_internal.h"
 #include "mesh3d_math.h"
 #include "mesh3d_grid.h"
+#include "rigid_align_math.h"
 #include "smalfit_plan.h"
 
 namespace smalfit {
@@ -121,8 +122,10 @@ enum { PH_HEAD_POSE = 0, PH_HEAD_SHAPE, PH_SKIN, PH_VERTEX_BWD, PH_MID_PB, PH_MI
 #include "kernels_color.inc"
 #include "kernels_lbs_backward.inc"
 #include "kernels_mesh3d.inc"
+#include "kernels_rigid_align.inc"
 
 }  // namespace smalfit
 
 #include "smalfit_launch.inc"
 #include "smalfit_mesh3d.inc"
+#include "smalfit_rigid_align.inc"

@@ -430,6 +430,71 @@ inline const char* mesh_score_args_refusal(const smalfit_mesh_score_args* a, con
   return nullptr;
 }
 
+// ---- the rigid pre-alignment (smalfit_rigid_align; worded in include/smalfit.h) ---------------------------------------------
+// rigid_scan_kernel<DIR>: 64 queries a block like the chamfer kernels, x the K starts x the N meshes -- the starts are the
+// parallelism one mesh lacks (61 and 47 query blocks at the fitter's size, 24 starts make 2592 of them).  rigid_solve_kernel: one
+// wave per (start, mesh).  rigid_init_kernel (means, starts): one block per mesh.  rigid_pick_kernel: one mesh per thread.
+constexpr int kRigidMaxIterations = 1000;
+constexpr int kRigidMaxMeshes = 65535;          // a launch's largest y / z dimension
+constexpr double kRigidStartTolerance = 1e-4;   // how far a caller's float32 start may be from a proper rotation
+inline Grid3 rigid_scan_grid(int queries, int K, int N) { return Grid3{mesh_query_blocks(queries), K, N}; }
+inline Grid2 rigid_solve_grid(int K, int N) { return Grid2{K, N}; }
+constexpr int rigid_init_blocks(int N) { return N; }
+inline int rigid_pick_blocks(int N) { return (N + 63) / 64; }
+// launches of one call: the init, I + 1 rounds of (a scan per direction that is on, the solve), the pick
+inline int rigid_align_launches(int iterations, bool vert_dir, bool point_dir) {
+  return 1 + (iterations + 1) * ((vert_dir ? 1 : 0) + (point_dir ? 1 : 0) + 1) + 1;
+}
+inline const char* rigid_aligner_create_refusal(bool given, int max_meshes, int max_verts, int max_points, int max_starts) {
+  if (!given) return "null argument";
+  if (max_meshes <= 0 || max_verts <= 0 || max_points <= 0) return "max_meshes, max_verts and max_points must be positive";
+  if (max_meshes > kRigidMaxMeshes) return "max_meshes must be at most 65535";   // (the meshes are a grid's z and y dimension)
+  static_assert(SMALFIT_MAX_RIGID_STARTS == 64, "the message below names the limit");
+  return max_starts >= 1 && max_starts <= SMALFIT_MAX_RIGID_STARTS ? nullptr : "max_starts must be 1..64";
+}
+// -> why a (3,3) row-major start is no proper rotation (finite, R R^T = I and det R = +1 to within kRigidStartTolerance), or nullptr
+inline const char* rigid_start_refusal(const float* R) {
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(R[i])) return "every start must be finite";
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double d = i == j ? -1.0 : 0.0;
+      for (int k = 0; k < 3; ++k) d += (double)R[3 * i + k] * (double)R[3 * j + k];
+      if (!(std::fabs(d) <= kRigidStartTolerance)) return "every start must be orthonormal to within 1e-4";
+    }
+  const double det = (double)R[0] * ((double)R[4] * R[8] - (double)R[5] * R[7]) - (double)R[1] * ((double)R[3] * R[8] - (double)R[5] * R[6]) +
+                     (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
+  return std::fabs(det - 1.0) <= kRigidStartTolerance ? nullptr : "every start must have determinant +1 (a reflection is no start)";
+}
+// -> why smalfit_rigid_align refuses the block (the text behind "smalfit_rigid_align: "), or nullptr.  struct_size first; reads the
+// K host matrices of `starts` when they are given
+struct RigidAlignFacts { int max_meshes, max_verts, max_points, max_starts; };   // the handle's capacities
+inline const char* rigid_align_args_refusal(const smalfit_rigid_align_args* a, const RigidAlignFacts& f) {
+  if (a->struct_size != (unsigned)sizeof(smalfit_rigid_align_args))
+    return "smalfit_rigid_align_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (a->num_meshes < 1 || a->num_meshes > f.max_meshes) return "num_meshes must be 1 .. the aligner's max_meshes";
+  if (a->num_verts < 1 || a->num_verts > f.max_verts) return "num_verts must be 1 .. the aligner's max_verts";
+  if (a->num_points < 1 || a->num_points > f.max_points) return "num_points must be 1 .. the aligner's max_points";
+  if (a->num_starts < 1 || a->num_starts > SMALFIT_MAX_RIGID_STARTS || a->num_starts > f.max_starts)
+    return "num_starts must be 1 .. the aligner's max_starts (at most 64)";
+  static_assert(kRigidMaxIterations == 1000, "the message below names the limit");
+  if (a->iterations < 0 || a->iterations > kRigidMaxIterations) return "iterations must be 0..1000";
+  if (!(std::isfinite(a->w_point) && a->w_point >= 0.f && std::isfinite(a->w_vert) && a->w_vert >= 0.f))
+    return "w_point and w_vert must be finite and >= 0";
+  if (a->w_point == 0.f && a->w_vert == 0.f) return "w_point and w_vert are both 0";
+  if (!a->verts || !a->points) return "verts / points missing";
+  if (a->starts && a->start_transforms) return "starts and start_transforms are both given";
+  static_assert(SMALFIT_NUM_CUBE_ROTATIONS == 24, "the message below names the count");
+  if (!a->starts && !a->start_transforms && a->num_starts != SMALFIT_NUM_CUBE_ROTATIONS)
+    return "the built-in starts are 24: num_starts must be 24 without starts";
+  if (a->starts)
+    for (int k = 0; k < a->num_starts; ++k)
+      if (const char* msg = rigid_start_refusal(a->starts + 9 * (size_t)k)) return msg;
+  if (!a->transforms || !a->scores || !a->best || !a->best_transform || !a->kept_rotation)
+    return "transforms / scores / best / best_transform / kept_rotation missing";
+  return nullptr;
+}
+
 // -> why smalfit_mesh_surface_eval / smalfit_fit3d_step_surface refuse the surface block (the text behind "<entry point>: "), or
 // nullptr.  In a step the vertices and the points are the step's own: the block must carry neither, and what the points need is
 // asked of the step's block (step_points: its num_points; step_has_points: its `points` is given)

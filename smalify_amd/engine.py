@@ -812,6 +812,92 @@ _EVAL_ENTRY_POINTS = ("smalfit_mesh_objective_eval", "smalfit_mesh_objective_eva
 _SURFACE_ENTRY_POINTS = ("smalfit_mesh_surface_eval", "smalfit_mesh_surface_eval_gated", "smalfit_mesh_surface_eval_robust")
 
 
+class RigidAligner:
+    """Rigid pre-alignment of (N,V,3) vertices onto (N,S,3) points: iterative closest point from several starting orientations at
+    once (smalfit_rigid_aligner; the definition is this project's, include/smalfit.h).  A handle of its own: it needs no engine,
+    no objective and no targets."""
+
+    def __init__(self, max_meshes, max_verts, max_points, max_starts=_lib.MAX_RIGID_STARTS):
+        if not torch.cuda.is_available():
+            raise SmalfitError("no HIP device available: smalify_amd has no CPU fallback")
+        self.lib = _lib.load()
+        self.max_meshes, self.max_verts, self.max_points = int(max_meshes), int(max_verts), int(max_points)
+        self.max_starts = int(max_starts)
+        create = _lib.resolve(self.lib, "smalfit_rigid_aligner_create")
+        self._destroy = _lib.resolve(self.lib, "smalfit_rigid_aligner_destroy")
+        self._align = _lib.resolve(self.lib, "smalfit_rigid_align")
+        torch.cuda.init()
+        torch.cuda.current_device()
+        h = C.c_void_p()
+        check(create(self.max_meshes, self.max_verts, self.max_points, self.max_starts, C.byref(h)), "smalfit_rigid_aligner_create")
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self._destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def align(self, verts, points, starts=None, start_transforms=None, iterations=30, w_point=1.0, w_vert=1.0, history=False,
+              correspondences=False, out=None):
+        """verts (N,V,3), points (N,S,3): float32 device tensors.  starts: None (the library's 24 rotations of the cube) or host
+        (K,3,3) proper rotations; start_transforms: device (N,K,12) rows [R | t], used as they are (then starts must be None) -- the
+        `transforms` of an earlier call continue it.  -> dict of device tensors: transforms (N,K,12), scores (N,K), best (N) int32,
+        best_transform (N,12), kept_rotation (N,K) int32, with history=True history (N,K,iterations+1), with correspondences=True
+        vert_nn (N,K,V) / point_nn (N,K,S) int32 of the score's scans (a direction of weight 0 is not scanned: its tensor keeps what
+        it held).  `out` may carry preallocated tensors under the same keys.  Nothing synchronises."""
+        if not (isinstance(verts, torch.Tensor) and verts.dim() == 3 and int(verts.shape[2]) == 3):
+            raise SmalfitError("verts must be (num_meshes, V, 3)")
+        N, V = int(verts.shape[0]), int(verts.shape[1])
+        # the library cannot know the extent or the device of a pointer
+        if not (isinstance(points, torch.Tensor) and points.dim() == 3 and int(points.shape[0]) == N and int(points.shape[2]) == 3):
+            raise SmalfitError("points must be (num_meshes, S, 3)")
+        if points.device != verts.device:
+            raise SmalfitError("points must be on the device of verts (%s)" % verts.device)
+        S = int(points.shape[1])
+        dev = verts.device
+        a = _lib.RigidAlignArgs()
+        host_starts = None
+        if start_transforms is not None:
+            if not (isinstance(start_transforms, torch.Tensor) and start_transforms.dim() == 3 and int(start_transforms.shape[0]) == N
+                    and int(start_transforms.shape[2]) == 12):
+                raise SmalfitError("start_transforms must be (num_meshes, K, 12)")
+            if start_transforms.device != dev:
+                raise SmalfitError("start_transforms must be on the device of verts (%s)" % dev)
+            K = int(start_transforms.shape[1])
+            a.start_transforms = _ptr(start_transforms)
+            if starts is not None:       # the library words the refusal
+                host_starts = _host(starts, np.float32).reshape(-1, 3, 3)
+        elif starts is not None:
+            host_starts = _host(starts, np.float32).reshape(-1, 3, 3)
+            K = int(host_starts.shape[0])
+        else:
+            K = _lib.NUM_CUBE_ROTATIONS
+        if host_starts is not None:
+            a.starts = host_starts.ctypes.data
+        iterations = int(iterations)
+        a.num_meshes, a.num_verts, a.num_points, a.num_starts, a.iterations = N, V, S, K, iterations
+        a.verts, a.points = _ptr(verts), _ptr(points)
+        a.w_point, a.w_vert = float(w_point), float(w_vert)
+        o = out if out is not None else {}
+        fields = [("transforms", (N, K, 12), torch.float32), ("scores", (N, K), torch.float32), ("best", (N,), torch.int32),
+                  ("best_transform", (N, 12), torch.float32), ("kept_rotation", (N, K), torch.int32)]
+        if history:
+            fields.append(("history", (N, K, max(iterations, 0) + 1), torch.float32))
+        if correspondences:
+            fields += [("vert_nn", (N, K, V), torch.int32), ("point_nn", (N, K, S), torch.int32)]
+        for key, shape, dt in fields:
+            t = _out_tensor(o, key, shape, dt, dev, zero=True)
+            # a caller's tensor is written through its raw pointer: it must lie where and how the library expects it
+            if t.device != dev or not t.is_contiguous():
+                raise SmalfitError("out[%r] must be a contiguous tensor on the device of verts (%s)" % (key, dev))
+            setattr(a, key, C.c_void_p(t.data_ptr()))
+        check(self._align(self.handle, _stream(), C.byref(a)), "smalfit_rigid_align")
+        return o
+
+
 def _narrowest(names, *blocks):
     """-> (the narrowest entry point of `names` whose signature holds the last block that is not None, the blocks it takes: a
     library built before the later symbols still serves the calls it could serve)"""

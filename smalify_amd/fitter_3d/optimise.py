@@ -3,7 +3,8 @@
     python -m smalify_amd.fitter_3d.optimise --mesh_dir <dir> [--yaml_src cfg.yaml] [--scheme default --lr 1e-3 --nits 100]
 
 Same arguments and YAML layout (`stages: {name: {scheme, nits, lr, loss_weights, custom_lrs}}`, `args: {...}` overriding
-the command line) as fitter_3d/optimise.py:18-90 and fitter_3d/example_cfg.yaml."""
+the command line) as fitter_3d/optimise.py:18-90 and fitter_3d/example_cfg.yaml.  Beyond the reference, opt-in: --metrics,
+--scan_index, --prealign (YAML `args: {prealign: true}`)."""
 from __future__ import annotations
 
 import argparse
@@ -36,6 +37,10 @@ def build_parser():
     parser.add_argument("--scan_index", action="store_true",
                         help="build a grid over the target meshes for the vertex-to-surface scans (dense scan targets); the "
                              "results are bit for bit those without it")
+    parser.add_argument("--prealign", action="store_true",
+                        help="before the first stage, stand every SMAL mesh where its target stands: rigid multi-start ICP from the "
+                             "24 rotations of the cube, folded into global_rot and trans; its report goes to prealign.json in results_dir")
+    parser.add_argument("--prealign_iterations", type=int, default=30, help="ICP iterations of --prealign")
     return parser
 
 
@@ -59,6 +64,16 @@ def main(args, model_data=None, smal_data=None):
     manager = StageManager(out_dir=args.results_dir, labels=mesh_names)
     smal_model = SMAL3DFitter(batch_size=n_batch, shape_family=args.shape_family_id, model_data=model_data,
                               smal_data=smal_data)
+    if getattr(args, "prealign", False):
+        # once, before any stage is built (a stage reads the fitter's vertices when it is constructed)
+        import json
+        from .trainer import rigid_prealign
+        report = rigid_prealign(smal_model, target_meshes, iterations=int(getattr(args, "prealign_iterations", 30)),
+                                seed=getattr(args, "seed", 0))
+        names = [str(n) for n in mesh_names] if len(mesh_names) == len(report) else ["mesh_%d" % i for i in range(len(report))]
+        with open(os.path.join(args.results_dir, "prealign.json"), "w") as fh:
+            json.dump(dict(iterations=int(getattr(args, "prealign_iterations", 30)), starts=24,
+                           meshes=[dict(name=nm, **row) for nm, row in zip(names, report)]), fh, indent=1)
     stage_kwargs = dict(target_meshes=target_meshes, smal_3d_fitter=smal_model, out_dir=args.results_dir,
                         mesh_names=mesh_names, seed=getattr(args, "seed", 0))
     if stage_options is not None:

@@ -531,6 +531,91 @@ def _objective_for(fitter, max_points):
     return obj
 
 
+# rigid_prealign draws its target points with a key of its own, the way Stage.metrics does: never one of the fit's draws
+PREALIGN_SEED_OFFSET = 0x70726561        # added to the seed
+PREALIGN_ITERATION = 0xFFFFFFFE
+
+
+def _rotation_exp(r):
+    """Rodrigues in float64: axis-angle (3,) -> (3,3)"""
+    r = np.asarray(r, np.float64)
+    th = float(np.linalg.norm(r))
+    K = np.array([[0.0, -r[2], r[1]], [r[2], 0.0, -r[0]], [-r[1], r[0], 0.0]])
+    if th < 1e-8:
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
+
+
+def _rotation_log(R):
+    """(3,3) -> axis-angle (3,) in float64, angle in [0, pi].  R is first projected onto the rotations (a float32 matrix is not
+    exactly orthonormal); near pi the axis comes from the symmetric part, where the skew part vanishes"""
+    U, _, Vt = np.linalg.svd(np.asarray(R, np.float64))
+    R = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0]) @ Vt
+    w = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = float(np.linalg.norm(w)), 0.5 * (float(np.trace(R)) - 1.0)
+    th = float(np.arctan2(s, c))
+    if s > 1e-6:
+        return w * (th / s)
+    if c > 0:
+        return w                                   # angle ~ 0: theta / sin(theta) -> 1
+    B = 0.5 * (R + np.eye(3))                      # angle ~ pi: R = 2 a a^T - I up to O(pi - theta)
+    i = int(np.argmax(np.diag(B)))
+    a = B[:, i] / np.sqrt(B[i, i])
+    if float(a @ w) < 0:
+        a = -a
+    return a * th
+
+
+def rigid_prealign(fitter, target_meshes, starts=None, iterations=30, num_points=N_SAMPLE_POINTS, seed=0, w_point=1.0, w_vert=1.0):
+    """Stand the SMAL meshes where their targets stand before the first stage: multi-start ICP of fitter() onto points drawn on
+    the targets (engine.RigidAligner; smalfit_rigid_align, include/smalfit.h), then the winning [R | t] of every mesh folded into
+    the parameters: global_rot <- log(R exp(global_rot)) (the conversion on the host in float64) and trans such that the new
+    fitter() is R (old fitter()) + t -- the root rotation turns the mesh about its rest root joint, so trans is taken from a
+    second forward: the mean over the vertices of R (v_old + trans_old) + t - v_new.  betas, log_beta_scales and joint_rot are not
+    touched.  deform_verts is added after the pose and would not turn with it: any non-zero entry raises ValueError.
+    starts: None (the 24 rotations of the cube) or (K,3,3) proper rotations.  Opt-in: no stage calls this.
+    -> one dict per mesh: best (the winning start), score, angle (radians turned), angle_degrees, kept_rotation (of the winning
+    start), identity_score (the score of the identity start, None when it is not among the starts), transform (the winning
+    [R | t], 12 floats in rows).  Reading it synchronises."""
+    N = fitter.batch_size
+    if len(target_meshes) != N:
+        raise ValueError("%d target meshes for a fitter of batch size %d" % (len(target_meshes), N))
+    if bool(torch.any(fitter.deform_verts.detach() != 0)):
+        raise ValueError("rigid_prealign: deform_verts is not zero; it is added after the pose and would not turn with the mesh")
+    num_points, iterations = int(num_points), int(iterations)
+    key = (int(seed) + PREALIGN_SEED_OFFSET) & (2 ** 64 - 1)
+    points = target_meshes.sample(num_points, key, PREALIGN_ITERATION)
+    verts = fitter().contiguous()
+    V = int(verts.shape[1])
+    host_starts = None if starts is None else np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 3, 3))
+    K = _lib.NUM_CUBE_ROTATIONS if host_starts is None else int(host_starts.shape[0])
+    aligner = eng.RigidAligner(N, V, num_points, max(K, 1))
+    o = aligner.align(verts, points, starts=host_starts, iterations=iterations, w_point=w_point, w_vert=w_vert)
+    T = o["best_transform"].cpu().numpy().astype(np.float64).reshape(N, 3, 4)
+    best = o["best"].cpu().numpy()
+    scores = o["scores"].cpu().numpy()
+    kept = o["kept_rotation"].cpu().numpy()
+    # the identity among the starts: start 0 of the built-in ones, else the first caller's start that is exactly I
+    identity = 0 if host_starts is None else next((k for k in range(K) if np.array_equal(host_starts[k], np.eye(3, dtype=np.float32))), None)
+    v_old = fitter.lbs_verts().detach().cpu().numpy().astype(np.float64)
+    trans_old = fitter.trans.detach().cpu().numpy().astype(np.float64)
+    rot_old = fitter.global_rot.detach().cpu().numpy().astype(np.float64)
+    rot_new = np.stack([_rotation_log(T[n, :, :3] @ _rotation_exp(rot_old[n])) for n in range(N)])
+    fitter.global_rot.data.copy_(torch.from_numpy(rot_new.astype(np.float32)).to(fitter.global_rot.device))
+    v_new = fitter.lbs_verts().detach().cpu().numpy().astype(np.float64)
+    want = np.einsum("nij,nvj->nvi", T[:, :, :3], v_old + trans_old[:, None, :]) + T[:, None, :, 3]
+    trans_new = (want - v_new).mean(axis=1)
+    fitter.trans.data.copy_(torch.from_numpy(trans_new.astype(np.float32)).to(fitter.trans.device))
+    report = []
+    for n in range(N):
+        b = int(best[n])
+        angle = float(np.linalg.norm(_rotation_log(T[n, :, :3])))
+        report.append(dict(best=b, score=float(scores[n, b]), angle=angle, angle_degrees=float(np.degrees(angle)),
+                           kept_rotation=int(kept[n, b]), identity_score=None if identity is None else float(scores[n, identity]),
+                           transform=[float(v) for v in T[n].reshape(-1)]))
+    return report
+
+
 class StageManager:
     """Container for multiple stages of optimisation (trainer.py:282-323)."""
 
