@@ -866,7 +866,7 @@ int smalfit_fit3d_step_robust(smalfit_engine* engine, smalfit_mesh_objective* ob
  * The handle holds the work buffers for up to max_meshes (at most 65535) meshes of up to max_verts vertices and max_points points
  * and up to max_starts (at most 64) starts; a call may be smaller in every one of them and gives the same bits on a larger handle.
  * The two weights reach the device as the float32 quotients w_vert / V and w_point / S, one divide each on the host.
- * Not here: scale (similarity) estimation, trimming or robust weights, normals, the scan index. */
+ * Not here: scale (similarity) estimation, robust weights, normals, the scan index.  Trimming: smalfit_trimmed_rigid_align below. */
 typedef struct smalfit_rigid_aligner smalfit_rigid_aligner;
 #define SMALFIT_MAX_RIGID_STARTS 64
 #define SMALFIT_NUM_CUBE_ROTATIONS 24
@@ -896,6 +896,45 @@ typedef struct smalfit_rigid_align_args {
 int smalfit_rigid_aligner_create(int max_meshes, int max_verts, int max_points, int max_starts, smalfit_rigid_aligner** out);
 void smalfit_rigid_aligner_destroy(smalfit_rigid_aligner* aligner);
 int smalfit_rigid_align(smalfit_rigid_aligner* aligner, void* stream, const smalfit_rigid_align_args* args);
+
+/* ---- trimmed rigid pre-alignment: partial, cluttered scans -----------------------------------------------------------------------
+ * smalfit_rigid_align matches every vertex and every point and solves on all of the pairs: a scan that shows one side of the
+ * animal, or that holds a floor, pulls every start off.  Trimmed ICP (Chetverikov's TrICP) keeps, per iteration and per direction,
+ * only the pairs of smallest d^2.  THIS PROJECT'S definitions, per mesh n, start k and direction, in float32, on top of the ones
+ * above.
+ *   key            of query q: the pair (bits of its d^2 read as uint32, q).  d^2 is fma(dz, dz, fma(dy, dy, dx dx)) >= 0, so its
+ *                  bits order as the value does.  A query without a match (non-finite input) has no key and is never kept.
+ *   kept           the `keep` queries of the lowest keys, compared lexicographically: the lowest d^2, the lowest query index among
+ *                  bit-equal d^2.  keep_vert in 1..V counts vertices, keep_point in 1..S points: integers, no float rounding
+ *                  decides a count.  keep == the count: the direction is untrimmed.  Fewer keys than keep: all of them are kept.
+ *   threshold      the highest kept key: a query is kept iff its key <= the threshold.  The one fact the selection produces.
+ *   one iteration  the one above with step 3's pair set restricted to the kept pairs: a dropped query adds 0 in place of each of
+ *                  its 19 sums (d^2 among them: it is not in the cost either), in the same blocks of 64 queries, the same wave
+ *                  butterfly and the same block order.  The weights stay w_vert / V and w_point / S: denominators do not move
+ *                  with a count, so the combination, the solve, the rank test and kept_rotation are unchanged.
+ *   cost, score, history, best   as above, over the kept pairs.  keep is the same for every start: scores stay comparable.
+ *   determinism    as above: no float atomics, every float sum in a fixed order (the selection counts keys with integer counters in
+ *                  LDS, whose result does not depend on order).  The same call gives the same bits, I iterations give the bits of
+ *                  I chained one-iteration calls.
+ *   off            trim == NULL, or every direction of positive weight has keep == its count: exactly smalfit_rigid_align, launch
+ *                  for launch and bit for bit; vert_kept / point_kept, where given, are set to 1 (of the directions that are on)
+ *                  and trim_d2 to 0: nothing is computed for them.
+ * A keep given for a direction of weight 0 is accepted and ignored.  A refused block launches nothing and writes nothing.
+ * The FIRST trimmed call of a handle ALLOCATES (and so synchronises): 8 bytes per query of every (mesh, start) at the handle's
+ * capacities, (max_verts + max_points) 8 max_meshes max_starts bytes, freed with the handle.  Later calls only enqueue.
+ * Not here: estimating the overlap fraction (TrICP's search), scale, normal-compatible matching, translation starts (a scan cut
+ * along the body's long axis moves the centroid too far: give start_transforms), the scan index, a stage that re-aligns. */
+typedef struct smalfit_rigid_trim_args {
+  unsigned struct_size;          /* sizeof(smalfit_rigid_trim_args) of the caller's header; checked before any other field */
+  int keep_vert;                 /* vertices kept per iteration, 1 .. V (ignored when w_vert == 0) */
+  int keep_point;                /* points kept per iteration, 1 .. S (ignored when w_point == 0) */
+  unsigned char* vert_kept;      /* optional (N,K,V): 1 where vertex v was kept in the score's round, else 0; left alone when w_vert == 0 */
+  unsigned char* point_kept;     /* optional (N,K,S); left alone when w_point == 0 */
+  float* trim_d2;                /* optional (N,K,2): the d^2 of the threshold of the score's round, [0] vertices [1] points; 0 for a
+                                    skipped direction and for one that kept nothing */
+} smalfit_rigid_trim_args;
+int smalfit_trimmed_rigid_align(smalfit_rigid_aligner* aligner, void* stream, const smalfit_rigid_align_args* args,
+                                const smalfit_rigid_trim_args* trim);
 
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137

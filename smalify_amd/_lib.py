@@ -185,6 +185,16 @@ class RigidAlignArgs(C.Structure):
         self.struct_size = C.sizeof(RigidAlignArgs)
 
 
+class RigidTrimArgs(C.Structure):
+    """smalfit_rigid_trim_args: how many pairs of each direction an iteration keeps (smalfit_trimmed_rigid_align)"""
+    _fields_ = [("struct_size", C.c_uint), ("keep_vert", C.c_int), ("keep_point", C.c_int), ("vert_kept", C.c_void_p),
+                ("point_kept", C.c_void_p), ("trim_d2", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(RigidTrimArgs)
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -307,6 +317,7 @@ SIGNATURES = {
     "smalfit_rigid_aligner_create": (_I, [_I, _I, _I, _I, C.POINTER(_VP)]),
     "smalfit_rigid_aligner_destroy": (None, [_VP]),
     "smalfit_rigid_align": (_I, [_VP, _VP, C.POINTER(RigidAlignArgs)]),
+    "smalfit_trimmed_rigid_align": (_I, [_VP, _VP, C.POINTER(RigidAlignArgs), C.POINTER(RigidTrimArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
@@ -317,7 +328,7 @@ LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "sm
                           "smalfit_mesh_objective_eval_gated", "smalfit_fit3d_step_partial", "smalfit_mesh_objective_eval_robust",
                           "smalfit_mesh_surface_eval_robust", "smalfit_fit3d_step_robust", "smalfit_mesh_targets_build_index",
                           "smalfit_mesh_targets_index_stats", "smalfit_rigid_aligner_create", "smalfit_rigid_aligner_destroy",
-                          "smalfit_rigid_align"])
+                          "smalfit_rigid_align", "smalfit_trimmed_rigid_align"])
 
 
 class SmalfitError(RuntimeError):

@@ -6,7 +6,11 @@
 //                          transformed while they are staged); every block leaves the sums of its 64 pairs in a slot of its own
 //   rigid_solve_kernel     adds the slots in block order, records the cost, solves, writes the next transform
 //   rigid_pick_kernel      best, best_transform
-// No atomics; every sum has a fixed order.
+// Trimmed calls (smalfit_trimmed_rigid_align) run rigid_scan_kernel<DIR, true>, which leaves every query's d^2 and match and no
+// sums, then
+//   rigid_trim_kernel      per (direction, start, mesh): a radix select of the keep-th key, then the kept pairs' sums in the scan's
+//                          slots, so the solve reads what it always reads
+// No float atomics; every float sum has a fixed order.
 
 struct RigidArgs {
   int N, V, S, K;
@@ -19,6 +23,11 @@ struct RigidArgs {
   int bv, bp;            // query blocks over the vertices | over the points
   int* vert_nn;          // [N][K][V] or null: written by the scans of the score's round alone
   int* point_nn;         // [N][K][S] or null
+  // trimmed calls alone (null otherwise): every query's d^2 and match (-1: none) of the round, from the scan to the selection
+  float* qd2_v;          // [N][K][V]
+  int* qnn_v;            // [N][K][V]
+  float* qd2_p;          // [N][K][S]
+  int* qnn_p;            // [N][K][S]
 };
 
 struct RigidStarts {
@@ -71,7 +80,7 @@ __global__ __launch_bounds__(256) void rigid_init_kernel(RigidArgs a, RigidStart
   for (int i = 0; i < 12; ++i) T[i] = t[i];
 }
 
-template <int DIR>
+template <int DIR, bool TRIM = false>
 __global__ __launch_bounds__(256) void rigid_scan_kernel(RigidArgs a) {
   __shared__ float sd[4][kRigidQueries];
   __shared__ int si[4][kRigidQueries];
@@ -126,6 +135,16 @@ __global__ __launch_bounds__(256) void rigid_scan_kernel(RigidArgs a) {
   for (int s = 1; s < 4; ++s) nearest_merge(best, bidx, sd[s][lane], si[s][lane]);
   // the pair of this query: (x_v, p_nn'(v)) or (x_nn(s), p_s), centred; a query without a match (NaN input) adds its d^2 alone
   const bool valid = active && (unsigned)bidx < (unsigned)no;
+  if constexpr (TRIM) {
+    // the trimmed form: the round's keys for rigid_trim_kernel, which forms the sums of the pairs it keeps
+    if (active) {
+      (DIR == 0 ? a.qd2_v : a.qd2_p)[nk * nq + qi] = best;
+      (DIR == 0 ? a.qnn_v : a.qnn_p)[nk * nq + qi] = valid ? bidx : -1;
+      int* nn = DIR == 0 ? a.vert_nn : a.point_nn;
+      if (nn != nullptr) nn[nk * nq + qi] = valid ? bidx : -1;
+    }
+    return;
+  }
   const float* partner = o + 3 * (size_t)(valid ? bidx : 0);
   const float pr[3] = {partner[0], partner[1], partner[2]};
   const float* cen = a.cen + 6 * (size_t)n;
@@ -146,6 +165,133 @@ __global__ __launch_bounds__(256) void rigid_scan_kernel(RigidArgs a) {
     float* slot = (DIR == 0 ? a.part_v : a.part_p) + (nk * gridDim.x + blockIdx.x) * kRigidMoments;
 #pragma unroll
     for (int i = 0; i < kRigidMoments; ++i) slot[i] = m[i];
+  }
+}
+
+struct RigidTrimArgs {
+  int first_dir;              // the direction of block x = 0: 0 when the vertices ask, 1 when only the points do
+  int dirs;                   // directions that are on: gridDim.x
+  int keep_v, keep_p;
+  unsigned char* vert_kept;   // [N][K][V] or null: the score's round alone, like vert_nn
+  unsigned char* point_kept;  // [N][K][S] or null
+  float* trim_d2;             // [N][K][2] or null
+};
+
+// inclusive scan of one int per thread over the block's 256 threads in thread order (a wave's lanes by shuffles, the four waves
+// through `wtot`); *total: the sum over the block.  Two barriers; wtot is free again after it returns
+__device__ __forceinline__ int rigid_block_scan(int v, int* wtot, int* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(v, o, 64);
+    if (lane >= o) v += up;
+  }
+  __syncthreads();
+  if (lane == 63) wtot[w] = v;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int t = wtot[i];
+    before += i < w ? t : 0;
+    all += t;
+  }
+  *total = all;
+  return v + before;
+}
+
+__global__ __launch_bounds__(256) void rigid_trim_kernel(RigidArgs a, RigidTrimArgs t) {
+  __shared__ int hist[4][256];   // a histogram per wave: integer counters, their sums do not depend on the order of arrival
+  __shared__ int wtot[4];
+  __shared__ int sel[2];         // the chosen bucket and the rank left inside it
+  __shared__ int tie;            // the threshold's query index
+  const int n = blockIdx.z, k = blockIdx.y, lane = threadIdx.x & 63, tid = threadIdx.x;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int dir = t.first_dir + blockIdx.x;
+  const int nq = dir == 0 ? a.V : a.S, no = dir == 0 ? a.S : a.V;
+  const size_t nk = (size_t)n * a.K + k;
+  const float* qd2 = (dir == 0 ? a.qd2_v : a.qd2_p) + nk * nq;
+  const int* qnn = (dir == 0 ? a.qnn_v : a.qnn_p) + nk * nq;
+  // ---- the keep-th key: four passes over the bits of d^2, eight at a time from the top; the keys are read again from memory every
+  // pass (max_verts is not bounded by LDS)
+  unsigned prefix = 0, mask = 0;
+  int rank = dir == 0 ? t.keep_v : t.keep_p;   // 1-based, among the keys that share the prefix
+  for (int shift = 24; shift >= 0; shift -= 8) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) hist[i][tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < nq; i += 256) {
+      const unsigned bits = rigid_key_bits(qd2[i]);
+      if (qnn[i] >= 0 && (bits & mask) == prefix) atomicAdd(&hist[w][(bits >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    const int mine = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];
+    int keys;
+    const int incl = rigid_block_scan(mine, wtot, &keys);
+    if (shift == 24) rank = min(rank, keys);   // fewer keys than keep: all of them are kept
+    if (incl - mine < rank && rank <= incl) {  // one bucket holds the rank (none when there is no key at all)
+      sel[0] = tid;
+      sel[1] = rank - (incl - mine);
+    }
+    __syncthreads();
+    if (rank > 0) {
+      prefix |= (unsigned)sel[0] << shift;
+      rank = sel[1];
+    }
+    mask |= 255u << shift;
+  }
+  // ---- ties: of the keys whose d^2 is the threshold's, the `rank` of the lowest query index are kept: an in-order scan
+  const unsigned tbits = prefix;
+  if (tid == 0) tie = -1;
+  int seen = 0;
+  for (int base = 0; base < nq; base += 256) {
+    const int i = base + tid;
+    const int hit = i < nq && qnn[i] >= 0 && rigid_key_bits(qd2[i]) == tbits ? 1 : 0;
+    int total;
+    const int incl = rigid_block_scan(hit, wtot, &total);
+    if (hit && seen + incl == rank) tie = i;
+    seen += total;
+  }
+  __syncthreads();
+  const int tq = tie;
+  // ---- the kept pairs' sums: the waves take the blocks of 64 queries in turn, each block summed as the scan sums it
+  const float* x = a.verts + (size_t)n * a.V * 3;
+  const float* p = a.points + (size_t)n * a.S * 3;
+  const float* q = dir == 0 ? x : p;
+  const float* o = dir == 0 ? p : x;
+  const float* cen = a.cen + 6 * (size_t)n;
+  const int blocks = dir == 0 ? a.bv : a.bp;
+  unsigned char* kept_out = dir == 0 ? t.vert_kept : t.point_kept;
+  for (int b = w; b < blocks; b += 4) {
+    const int qi = b * kRigidQueries + lane;
+    const bool active = qi < nq;
+    const float d2 = active ? qd2[qi] : 0.f;
+    const int nn = active ? qnn[qi] : -1;
+    const bool kept = nn >= 0 && nn < no && rigid_key_kept(rigid_key_bits(d2), qi, tbits, tq);
+    const float* qs = q + 3 * (size_t)(active ? qi : 0);
+    const float* partner = o + 3 * (size_t)(kept ? nn : 0);
+    const float raw[3] = {qs[0], qs[1], qs[2]};
+    const float pr[3] = {partner[0], partner[1], partner[2]};
+    float xc[3], pc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      xc[c] = (dir == 0 ? raw[c] : pr[c]) - cen[c];
+      pc[c] = (dir == 0 ? pr[c] : raw[c]) - cen[3 + c];
+    }
+    float m[kRigidMoments];
+    rigid_pair_moments(xc, pc, d2, m);
+#pragma unroll
+    for (int i = 0; i < kRigidMoments; ++i) m[i] = wave_sum(kept ? m[i] : 0.f);
+    if (kept_out != nullptr && active) kept_out[nk * nq + qi] = kept ? 1 : 0;
+    if (lane == 0) {
+      float* slot = (dir == 0 ? a.part_v : a.part_p) + (nk * blocks + b) * kRigidMoments;
+#pragma unroll
+      for (int i = 0; i < kRigidMoments; ++i) slot[i] = m[i];
+    }
+  }
+  if (t.trim_d2 != nullptr && tid == 0) {
+    t.trim_d2[nk * 2 + dir] = tq >= 0 ? rigid_key_value(tbits) : 0.f;
+    if (t.dirs == 1) t.trim_d2[nk * 2 + (1 - dir)] = 0.f;
   }
 }
 

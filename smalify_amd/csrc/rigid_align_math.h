@@ -202,4 +202,16 @@ SMALFIT_HD int rigid_solve(const float M[kRigidMoments], const float cX[3], cons
   return determined ? 0 : 1;
 }
 
+// ---- trimming (smalfit_trimmed_rigid_align) -------------------------------------------------------------------------------------
+// the key of query q is (bits of its d^2, q): d^2 >= 0 is never -0, so its bits read as uint32 order as the value does
+SMALFIT_HD unsigned rigid_key_bits(float d2) { return __builtin_bit_cast(unsigned, d2); }
+SMALFIT_HD float rigid_key_value(unsigned bits) { return __builtin_bit_cast(float, bits); }
+// key (bits, q) <= the threshold key (tbits, tq), lexicographically: the query is kept.  tq = -1 keeps nothing (no key was there)
+SMALFIT_HD bool rigid_key_kept(unsigned bits, int q, unsigned tbits, int tq) { return bits < tbits || (bits == tbits && q <= tq); }
+// how many of `count` queries the fraction in (0, 1] keeps: min(count, max(1, ceil(fraction count))), in double, on the host
+inline int rigid_keep_count(double fraction, int count) {
+  const double c = ceil(fraction * (double)count);
+  return c >= (double)count ? count : c < 1.0 ? 1 : (int)c;
+}
+
 }  // namespace smalfit

@@ -494,6 +494,28 @@ inline const char* rigid_align_args_refusal(const smalfit_rigid_align_args* a, c
     return "transforms / scores / best / best_transform / kept_rotation missing";
   return nullptr;
 }
+// ---- trimming (smalfit_trimmed_rigid_align) ----
+// rigid_trim_kernel: one block of 256 per (direction that is on, start, mesh): selects the threshold key of the round, forms the
+// kept pairs' sums into the scan's own slots.  It runs between the scans and the solve of every round
+inline Grid3 rigid_trim_grid(bool vert_dir, bool point_dir, int K, int N) { return Grid3{(vert_dir ? 1 : 0) + (point_dir ? 1 : 0), K, N}; }
+// launches of one trimmed call: the init, I + 1 rounds of (a scan per direction that is on, the selection, the solve), the pick
+inline int rigid_trim_launches(int iterations, bool vert_dir, bool point_dir) {
+  return 1 + (iterations + 1) * ((vert_dir ? 1 : 0) + (point_dir ? 1 : 0) + 2) + 1;
+}
+// -> why smalfit_trimmed_rigid_align refuses the trim block, or nullptr; asked after rigid_align_args_refusal accepted the call's
+// own block.  struct_size first, then the range of each keep; a keep of a direction of weight 0 is not read
+struct RigidTrimFacts { int num_verts, num_points; bool vert_dir, point_dir; };
+inline const char* rigid_trim_args_refusal(const smalfit_rigid_trim_args* t, const RigidTrimFacts& f) {
+  if (t->struct_size != (unsigned)sizeof(smalfit_rigid_trim_args))
+    return "smalfit_rigid_trim_args.struct_size does not match this library (built against another smalfit.h?)";
+  if (f.vert_dir && (t->keep_vert < 1 || t->keep_vert > f.num_verts)) return "keep_vert must be 1 .. num_verts";
+  if (f.point_dir && (t->keep_point < 1 || t->keep_point > f.num_points)) return "keep_point must be 1 .. num_points";
+  return nullptr;
+}
+// an accepted block trims: some direction that is on keeps fewer than its count
+inline bool rigid_trim_on(const smalfit_rigid_trim_args* t, const RigidTrimFacts& f) {
+  return t && ((f.vert_dir && t->keep_vert != f.num_verts) || (f.point_dir && t->keep_point != f.num_points));
+}
 
 // -> why smalfit_mesh_surface_eval / smalfit_fit3d_step_surface refuse the surface block (the text behind "<entry point>: "), or
 // nullptr.  In a step the vertices and the points are the step's own: the block must carry neither, and what the points need is

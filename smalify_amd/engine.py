@@ -6,6 +6,7 @@ libsmalfit.so.  All tensors handed to these methods must be contiguous float32 C
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -841,13 +842,23 @@ class RigidAligner:
             pass
 
     def align(self, verts, points, starts=None, start_transforms=None, iterations=30, w_point=1.0, w_vert=1.0, history=False,
-              correspondences=False, out=None):
+              correspondences=False, out=None, trim_point=1.0, trim_vert=1.0, kept=False):
         """verts (N,V,3), points (N,S,3): float32 device tensors.  starts: None (the library's 24 rotations of the cube) or host
         (K,3,3) proper rotations; start_transforms: device (N,K,12) rows [R | t], used as they are (then starts must be None) -- the
         `transforms` of an earlier call continue it.  -> dict of device tensors: transforms (N,K,12), scores (N,K), best (N) int32,
         best_transform (N,12), kept_rotation (N,K) int32, with history=True history (N,K,iterations+1), with correspondences=True
         vert_nn (N,K,V) / point_nn (N,K,S) int32 of the score's scans (a direction of weight 0 is not scanned: its tensor keeps what
-        it held).  `out` may carry preallocated tensors under the same keys.  Nothing synchronises."""
+        it held).  `out` may carry preallocated tensors under the same keys.  Nothing synchronises.
+        trim_point / trim_vert: the fraction in (0, 1] of the points / vertices every iteration keeps, those of smallest d^2
+        (smalfit_trimmed_rigid_align; a partial or cluttered scan): keep = keep_count(fraction, count).  Both 1.0 and kept=False:
+        smalfit_rigid_align itself.  kept=True adds point_kept (N,K,S) / vert_kept (N,K,V) uint8 and trim_d2 (N,K,2) of the score's
+        round, and keep_point / keep_vert (ints).  The first trimmed call of an aligner allocates."""
+        keep = {}
+        for name, fraction in (("trim_point", trim_point), ("trim_vert", trim_vert)):
+            fraction = float(fraction)
+            if not (0.0 < fraction <= 1.0):
+                raise SmalfitError("%s must be in (0, 1], got %r" % (name, fraction))
+            keep[name] = fraction
         if not (isinstance(verts, torch.Tensor) and verts.dim() == 3 and int(verts.shape[2]) == 3):
             raise SmalfitError("verts must be (num_meshes, V, 3)")
         N, V = int(verts.shape[0]), int(verts.shape[1])
@@ -894,8 +905,28 @@ class RigidAligner:
             if t.device != dev or not t.is_contiguous():
                 raise SmalfitError("out[%r] must be a contiguous tensor on the device of verts (%s)" % (key, dev))
             setattr(a, key, C.c_void_p(t.data_ptr()))
-        check(self._align(self.handle, _stream(), C.byref(a)), "smalfit_rigid_align")
+        if not kept and keep["trim_point"] == 1.0 and keep["trim_vert"] == 1.0:
+            check(self._align(self.handle, _stream(), C.byref(a)), "smalfit_rigid_align")
+            return o
+        t = _lib.RigidTrimArgs()
+        t.keep_point, t.keep_vert = keep_count(keep["trim_point"], S), keep_count(keep["trim_vert"], V)
+        if kept:
+            for key, shape, dt in (("vert_kept", (N, K, V), torch.uint8), ("point_kept", (N, K, S), torch.uint8),
+                                   ("trim_d2", (N, K, 2), torch.float32)):
+                buf = _out_tensor(o, key, shape, dt, dev, zero=True)
+                if buf.device != dev or not buf.is_contiguous():
+                    raise SmalfitError("out[%r] must be a contiguous tensor on the device of verts (%s)" % (key, dev))
+                setattr(t, key, C.c_void_p(buf.data_ptr()))
+            o["keep_point"], o["keep_vert"] = int(t.keep_point), int(t.keep_vert)
+        check(_lib.resolve(self.lib, "smalfit_trimmed_rigid_align")(self.handle, _stream(), C.byref(a), C.byref(t)),
+              "smalfit_trimmed_rigid_align")
         return o
+
+
+def keep_count(fraction, count):
+    """how many of `count` queries a trim fraction in (0, 1] keeps: min(count, max(1, ceil(fraction count))) in double -- the rule
+    of rigid_keep_count (smalify_amd/csrc/rigid_align_math.h), restated for the binding"""
+    return int(min(int(count), max(1, math.ceil(float(fraction) * int(count)))))
 
 
 def _narrowest(names, *blocks):

@@ -4,7 +4,7 @@
 
 Same arguments and YAML layout (`stages: {name: {scheme, nits, lr, loss_weights, custom_lrs}}`, `args: {...}` overriding
 the command line) as fitter_3d/optimise.py:18-90 and fitter_3d/example_cfg.yaml.  Beyond the reference, opt-in: --metrics,
---scan_index, --prealign (YAML `args: {prealign: true}`)."""
+--scan_index, --prealign (YAML `args: {prealign: true}`) with --prealign_trim_point / --prealign_trim_vert."""
 from __future__ import annotations
 
 import argparse
@@ -41,6 +41,12 @@ def build_parser():
                         help="before the first stage, stand every SMAL mesh where its target stands: rigid multi-start ICP from the "
                              "24 rotations of the cube, folded into global_rot and trans; its report goes to prealign.json in results_dir")
     parser.add_argument("--prealign_iterations", type=int, default=30, help="ICP iterations of --prealign")
+    parser.add_argument("--prealign_trim_point", type=float, default=None, metavar="F",
+                        help="with --prealign: every ICP iteration keeps this fraction in (0, 1] of the drawn target points, those "
+                             "nearest to the mesh (trimmed ICP: a scan with a floor or a stand in it)")
+    parser.add_argument("--prealign_trim_vert", type=float, default=None, metavar="F",
+                        help="with --prealign: every ICP iteration keeps this fraction in (0, 1] of the SMAL vertices, those nearest "
+                             "to the target (trimmed ICP: a scan that shows part of the animal)")
     return parser
 
 
@@ -57,6 +63,10 @@ def main(args, model_data=None, smal_data=None):
         for arg, val in (yaml_cfg.get("args") or {}).items():       # YAML args overwrite the command line
             setattr(args, arg, val)
 
+    trims = {k: getattr(args, "prealign_" + k, None) for k in ("trim_point", "trim_vert")}
+    if any(v is not None for v in trims.values()) and not getattr(args, "prealign", False):
+        raise ValueError("--prealign_trim_point / --prealign_trim_vert trim the ICP of --prealign: give --prealign with them")
+    trims = {k: float(v) for k, v in trims.items() if v is not None}
     mesh_names, target_meshes = load_meshes(mesh_dir=args.mesh_dir, frame_step=args.frame_step,
                                             scan_index=bool(getattr(args, "scan_index", False)))
     n_batch = len(target_meshes)
@@ -69,7 +79,7 @@ def main(args, model_data=None, smal_data=None):
         import json
         from .trainer import rigid_prealign
         report = rigid_prealign(smal_model, target_meshes, iterations=int(getattr(args, "prealign_iterations", 30)),
-                                seed=getattr(args, "seed", 0))
+                                seed=getattr(args, "seed", 0), **trims)
         names = [str(n) for n in mesh_names] if len(mesh_names) == len(report) else ["mesh_%d" % i for i in range(len(report))]
         with open(os.path.join(args.results_dir, "prealign.json"), "w") as fh:
             json.dump(dict(iterations=int(getattr(args, "prealign_iterations", 30)), starts=24,

@@ -566,7 +566,8 @@ def _rotation_log(R):
     return a * th
 
 
-def rigid_prealign(fitter, target_meshes, starts=None, iterations=30, num_points=N_SAMPLE_POINTS, seed=0, w_point=1.0, w_vert=1.0):
+def rigid_prealign(fitter, target_meshes, starts=None, iterations=30, num_points=N_SAMPLE_POINTS, seed=0, w_point=1.0, w_vert=1.0,
+                   trim_point=1.0, trim_vert=1.0):
     """Stand the SMAL meshes where their targets stand before the first stage: multi-start ICP of fitter() onto points drawn on
     the targets (engine.RigidAligner; smalfit_rigid_align, include/smalfit.h), then the winning [R | t] of every mesh folded into
     the parameters: global_rot <- log(R exp(global_rot)) (the conversion on the host in float64) and trans such that the new
@@ -576,7 +577,11 @@ def rigid_prealign(fitter, target_meshes, starts=None, iterations=30, num_points
     starts: None (the 24 rotations of the cube) or (K,3,3) proper rotations.  Opt-in: no stage calls this.
     -> one dict per mesh: best (the winning start), score, angle (radians turned), angle_degrees, kept_rotation (of the winning
     start), identity_score (the score of the identity start, None when it is not among the starts), transform (the winning
-    [R | t], 12 floats in rows).  Reading it synchronises."""
+    [R | t], 12 floats in rows).  Reading it synchronises.
+    trim_point / trim_vert: fractions in (0, 1] of the drawn points / of the vertices that every iteration keeps, those of smallest
+    d^2 (trimmed ICP, smalfit_trimmed_rigid_align): for a scan that shows part of the animal, or a floor beside it.  Below 1 in
+    either, every row also holds trim_point, trim_vert, kept_points, kept_verts (the counts) and trim_dist_point, trim_dist_vert:
+    the distance of the farthest kept pair of the winning start, a direct hint for the stages' max_dist_* gates."""
     N = fitter.batch_size
     if len(target_meshes) != N:
         raise ValueError("%d target meshes for a fitter of batch size %d" % (len(target_meshes), N))
@@ -590,7 +595,10 @@ def rigid_prealign(fitter, target_meshes, starts=None, iterations=30, num_points
     host_starts = None if starts is None else np.ascontiguousarray(np.asarray(starts, np.float32).reshape(-1, 3, 3))
     K = _lib.NUM_CUBE_ROTATIONS if host_starts is None else int(host_starts.shape[0])
     aligner = eng.RigidAligner(N, V, num_points, max(K, 1))
-    o = aligner.align(verts, points, starts=host_starts, iterations=iterations, w_point=w_point, w_vert=w_vert)
+    trim_point, trim_vert = float(trim_point), float(trim_vert)
+    trimmed = trim_point != 1.0 or trim_vert != 1.0
+    o = aligner.align(verts, points, starts=host_starts, iterations=iterations, w_point=w_point, w_vert=w_vert,
+                      trim_point=trim_point, trim_vert=trim_vert, kept=trimmed)
     T = o["best_transform"].cpu().numpy().astype(np.float64).reshape(N, 3, 4)
     best = o["best"].cpu().numpy()
     scores = o["scores"].cpu().numpy()
@@ -613,6 +621,11 @@ def rigid_prealign(fitter, target_meshes, starts=None, iterations=30, num_points
         report.append(dict(best=b, score=float(scores[n, b]), angle=angle, angle_degrees=float(np.degrees(angle)),
                            kept_rotation=int(kept[n, b]), identity_score=None if identity is None else float(scores[n, identity]),
                            transform=[float(v) for v in T[n].reshape(-1)]))
+    if trimmed:
+        trim_d2 = o["trim_d2"].cpu().numpy().astype(np.float64)
+        for n, row in enumerate(report):
+            row.update(trim_point=trim_point, trim_vert=trim_vert, kept_points=int(o["keep_point"]), kept_verts=int(o["keep_vert"]),
+                       trim_dist_point=float(np.sqrt(trim_d2[n, row["best"], 1])), trim_dist_vert=float(np.sqrt(trim_d2[n, row["best"], 0])))
     return report
 
 

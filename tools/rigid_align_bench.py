@@ -3,7 +3,10 @@
 pick -- rigid_align_launches of smalfit_plan.h counts them --, no host synchronisation in between), warmed up, the median and
 the spread of the repeats.  Needs a GPU.
 
-    python tools/rigid_align_bench.py [--meshes 1 32] [--iterations 30] [--repeats 7] [--out FILE.json]
+    python tools/rigid_align_bench.py [--meshes 1 32] [--iterations 30] [--repeats 7] [--trim_point F] [--trim_vert F] [--out FILE.json]
+
+--trim_point / --trim_vert below 1 time smalfit_trimmed_rigid_align instead (a selection launch more per round;
+rigid_trim_launches); the handle's first trimmed call, which allocates, is one of the warm-ups.
 
 The points are a rigidly moved, sub-sampled copy of the vertices (a lopsided blob, seeded), so the call does what a user's does:
 most starts settle elsewhere, the right one converges."""
@@ -38,6 +41,8 @@ def main():
     ap.add_argument("--points", type=int, default=3000)
     ap.add_argument("--iterations", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--trim_point", type=float, default=1.0, help="fraction of the points every iteration keeps")
+    ap.add_argument("--trim_vert", type=float, default=1.0, help="fraction of the vertices every iteration keeps")
     ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -47,20 +52,21 @@ def main():
         x, p = problem(N, args.verts, args.points)
         al = eng.RigidAligner(N, args.verts, args.points, 24)
         out = {}
+        trim = dict(trim_point=args.trim_point, trim_vert=args.trim_vert) if (args.trim_point, args.trim_vert) != (1.0, 1.0) else {}
         for _ in range(2):
-            al.align(x, p, iterations=args.iterations, out=out)
+            al.align(x, p, iterations=args.iterations, out=out, **trim)
         torch.cuda.synchronize()
         ms = []
         for _ in range(args.repeats):
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
-            al.align(x, p, iterations=args.iterations, out=out)
+            al.align(x, p, iterations=args.iterations, out=out, **trim)
             t1.record()
             torch.cuda.synchronize()
             ms.append(t0.elapsed_time(t1))
         row = dict(meshes=N, verts=args.verts, points=args.points, starts=24, iterations=args.iterations,
                    call_ms_median=float(np.median(ms)), call_ms_min=float(min(ms)), call_ms_max=float(max(ms)),
-                   per_iteration_ms=float(np.median(ms)) / (args.iterations + 1),
+                   per_iteration_ms=float(np.median(ms)) / (args.iterations + 1), **trim,
                    best=[int(b) for b in out["best"].cpu()], best_score=[float(s) for s in out["scores"].min(1).values.cpu()])
         rows.append(row)
         print(json.dumps(row))
