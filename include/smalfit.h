@@ -936,6 +936,74 @@ typedef struct smalfit_rigid_trim_args {
 int smalfit_trimmed_rigid_align(smalfit_rigid_aligner* aligner, void* stream, const smalfit_rigid_align_args* args,
                                 const smalfit_rigid_trim_args* trim);
 
+/* ---- scan sequences: one shape per clip, temporal smoothness ---------------------------------------------------------------------
+ * A depth camera or a multi-view rig delivers a SEQUENCE of partial scans of ONE animal moving.  A single partial scan does not
+ * determine the shape; many of the same animal do, when the fitter knows that they are the same animal.  A sequence handle makes
+ * the N meshes of a batch a set of CLIPS: within a clip the shape is one shape and consecutive poses are tied by the temporal terms
+ * of the 2-D fitter (reference smal_fitter/smal_fitter.py:177-190, get_temporal).  THIS PROJECT'S definitions.
+ *   clips          clip_lengths holds G positive integers with sum N.  Clip c is the contiguous run of meshes start_c ..
+ *                  start_c + len_c - 1 in batch order, start_0 = 0, start_(c+1) = start_c + len_c.  Batch order within a clip is
+ *                  temporal order.  A clip of length 1 is an unrelated mesh: nothing below touches it.
+ *   shared shape   share_shape != 0: behind the step's betas gradient rows g_n (N x num_betas) every row of clip c is replaced by
+ *                  the float32 sum of the clip's rows, taken in ascending n: the first row, then one addition per further row.
+ *                  Adam then runs unchanged on all N rows.  Rows of betas and of their two Adam moments that are bit-equal within
+ *                  a clip before a step are bit-equal after it, so betas keeps its (N, num_betas) shape for every reader.  This is
+ *                  Adam on one shared parameter whose gradient is the sum over its users (the batch-mean chamfer term already
+ *                  puts 1/N on every row).  In a step it applies only while lr_betas > 0.
+ *   temporal terms three weights; a weight <= 0 skips its term.  x is joint_rot (L = 102 elements per mesh), global_rot (L = 3) or
+ *                  trans (L = 3).  For every pair (n, n+1) inside one clip the reference adds mse_loss(x[n], x[n+1]) w; no pair
+ *                  spans a clip boundary, and the sum over the pairs is NOT divided by N.  With S the float32 sum over all pairs
+ *                  and elements of d d, d = x[n+1][k] - x[n][k], accumulated by fused multiply-adds, a term's loss is
+ *                    w (S / L)         one divide by the float L, one multiply
+ *                  so a case whose sums are exact in float32 has one result whatever order the reduction runs in.  The device
+ *                  sums S by 256 lanes, lane l taking the elements l, l + 256, ... of the flat (N, L) array in ascending order
+ *                  (an element of the last mesh of a clip adds nothing), the 64 lanes of a wave by a butterfly (xor 32, 16, ...
+ *                  1), the four waves in wave order: the same bits every run.
+ *   gradient       with c = (2 w) / L formed once on the host in float32, element k of mesh n receives
+ *                    g <- fma(c, (x - prev) + (x - next), g)     prev = x[n-1][k], next = x[n+1][k], x = x[n][k]
+ *                  where the first mesh of a clip takes fma(c, x - next, g), the last fma(c, x - prev, g), and a mesh alone in
+ *                  its clip keeps g.  In a step the gradient of a term is added before Adam reads it and only where that
+ *                  parameter is trained (its lr > 0); the loss is reported either way.
+ *   losses         (4): the joint, global and trans terms as defined above (0 for a skipped term), then [3] = (joint + global) +
+ *                  trans.  args->losses of the step keeps its five entries WITHOUT these.
+ *   step_total     optional (1), a step only: (args->losses[4] + the surface block's weighted term, when that block is on) +
+ *                  losses[3]: what the step descends on.
+ *   off            a block that couples nothing -- every clip of length 1, or share_shape off (or betas not trained) and every
+ *                  weight <= 0 -- launches nothing: `losses` reads 0 and the step is the step without the block, launch for launch
+ *                  and bit for bit.
+ * One extra launch between the betas assembly and Adam, no atomics, one thread per output element; nothing synchronises.  A
+ * refused block launches nothing and leaves every output alone.  The handle owns the device clip tables; it is built for one N
+ * and one list of lengths, and may be used with any engine and objective.
+ * Not here: a temporal term on posed vertices, second-order (acceleration) terms, sharing deform_verts (it is added after
+ * posing), propagating a fitted frame to the next as its start, clips that are not contiguous in the batch, sequences sharded
+ * across GPUs. */
+typedef struct smalfit_scan_sequence smalfit_scan_sequence;
+typedef struct smalfit_sequence_args {
+  int share_shape;               /* != 0: one betas gradient per clip, see above */
+  float w_temp_joint;            /* weight of the term on joint_rot; <= 0: skipped; must be finite */
+  float w_temp_global;           /* ... on global_rot */
+  float w_temp_trans;            /* ... on trans */
+  float* losses;                 /* (4, device): joint, global, trans, their sum */
+  float* step_total;             /* optional (1, device), a step only */
+} smalfit_sequence_args;
+/* clip_lengths: HOST, num_clips positive integers with sum num_meshes */
+int smalfit_scan_sequence_create(int num_meshes, int num_clips, const int* clip_lengths, smalfit_scan_sequence** out);
+void smalfit_scan_sequence_destroy(smalfit_scan_sequence* sequence);
+/* the coupling alone, on the caller's gradients of the handle's N meshes (the unfused path).  global_rot (N,3), joint_rot (N,34,3)
+ * and trans (N,3) are read, each needed only while its weight is > 0.  g_betas (N,num_betas), g_theta (N,105: columns 0..2 global_rot,
+ * 3..104 joint_rot) and g_trans (N,3) are updated in place; any of them may be NULL, and its gradient is then not formed (share_shape
+ * applies when g_betas is given; num_betas is read only then).  step_total must be NULL. */
+int smalfit_scan_sequence_couple(smalfit_scan_sequence* sequence, void* stream, const smalfit_sequence_args* args, int num_betas,
+                                 const float* global_rot, const float* joint_rot, const float* trans, float* g_betas,
+                                 float* g_theta, float* g_trans);
+/* smalfit_fit3d_step_robust with the sequence block; any of the four opt-in blocks may be NULL as there.  args->num_meshes must be
+ * the handle's N. */
+int smalfit_scan_sequence_step(smalfit_scan_sequence* sequence, smalfit_engine* engine, smalfit_mesh_objective* objective,
+                               smalfit_mesh_targets* targets, void* stream, const smalfit_fit3d_args* args,
+                               const smalfit_surface_term_args* surface, const smalfit_surface_gate_args* surface_gate,
+                               const smalfit_chamfer_gate_args* chamfer_gate, const smalfit_robust_args* robust,
+                               const smalfit_sequence_args* sequence_args);
+
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137
  * t = 1-based step count; eps outside the bias-corrected sqrt, as torch does */

@@ -195,6 +195,13 @@ class RigidTrimArgs(C.Structure):
         self.struct_size = C.sizeof(RigidTrimArgs)
 
 
+class SequenceArgs(C.Structure):
+    """smalfit_sequence_args: one shape per clip and the temporal terms of a scan sequence (smalfit_scan_sequence_couple,
+    smalfit_scan_sequence_step); every weight 0 = off"""
+    _fields_ = [("share_shape", C.c_int), ("w_temp_joint", C.c_float), ("w_temp_global", C.c_float), ("w_temp_trans", C.c_float),
+                ("losses", C.c_void_p), ("step_total", C.c_void_p)]
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -318,6 +325,11 @@ SIGNATURES = {
     "smalfit_rigid_aligner_destroy": (None, [_VP]),
     "smalfit_rigid_align": (_I, [_VP, _VP, C.POINTER(RigidAlignArgs)]),
     "smalfit_trimmed_rigid_align": (_I, [_VP, _VP, C.POINTER(RigidAlignArgs), C.POINTER(RigidTrimArgs)]),
+    "smalfit_scan_sequence_create": (_I, [_I, _I, c_int_p, C.POINTER(_VP)]),
+    "smalfit_scan_sequence_destroy": (None, [_VP]),
+    "smalfit_scan_sequence_couple": (_I, [_VP, _VP, C.POINTER(SequenceArgs), _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "smalfit_scan_sequence_step": (_I, [_VP, _VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs),
+                                        C.POINTER(ChamferGateArgs), C.POINTER(RobustArgs), C.POINTER(SequenceArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
@@ -328,7 +340,8 @@ LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "sm
                           "smalfit_mesh_objective_eval_gated", "smalfit_fit3d_step_partial", "smalfit_mesh_objective_eval_robust",
                           "smalfit_mesh_surface_eval_robust", "smalfit_fit3d_step_robust", "smalfit_mesh_targets_build_index",
                           "smalfit_mesh_targets_index_stats", "smalfit_rigid_aligner_create", "smalfit_rigid_aligner_destroy",
-                          "smalfit_rigid_align", "smalfit_trimmed_rigid_align"])
+                          "smalfit_rigid_align", "smalfit_trimmed_rigid_align", "smalfit_scan_sequence_create",
+                          "smalfit_scan_sequence_destroy", "smalfit_scan_sequence_couple", "smalfit_scan_sequence_step"])
 
 
 class SmalfitError(RuntimeError):

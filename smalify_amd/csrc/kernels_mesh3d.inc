@@ -1058,6 +1058,102 @@ __global__ __launch_bounds__(64 * kScanGridQueries) void mesh3d_surface_dist_gri
   if (lane == 0) a.vert_dist[o] = sqrtf(h.d2);
 }
 
+// ---- the scan-sequence block: one shape per clip, temporal smoothness ---------------------------------------------------
+// One launch between the betas assembly and Adam (include/smalfit.h, "scan sequences"; the arithmetic is fit3d_sequence_math.h,
+// the grid sequence_blocks of smalfit_plan.h).  The sizes are tiny (N <= the engine's max_frames, 105 + 3 + num_betas columns): the
+// launch is latency, not bandwidth.  No atomics.  Block 0 sums the three losses in a fixed order; behind it one thread owns one
+// output element: thread (clip, column) of the shape sum reads all of its clip's rows before it writes any of them, thread
+// (mesh, element) of a temporal gradient reads parameters, which Adam has not touched yet, and its own gradient element.
+struct Fit3dSequenceArgs {
+  int N, G, nb;
+  const int* clip_start;    // [G]
+  const int* clip_len;      // [G]
+  const int* mesh_start;    // [N] first mesh of the clip of mesh n
+  const int* mesh_len;      // [N] length of that clip
+  const float* global_rot;  // [N][3]    read only while its term is on
+  const float* joint_rot;   // [N][102]
+  const float* trans;       // [N][3]
+  float* g_betas;           // [N][nb]; read only when nshape > 0
+  float* g_theta;           // [N][105]; read only with add_global | add_joint
+  float* g_trans;           // [N][3]; read only with add_trans
+  int nshape;               // G nb when the shape sum runs, else 0
+  bool joint, global, trans_on;              // the term is evaluated (its weight > 0)
+  bool add_joint, add_global, add_trans;     // ... and its gradient added
+  float w_joint, w_global, w_trans;
+  float c_joint, c_global, c_trans;          // temporal_grad_scale
+  float* losses;            // [4]
+  const float* base_total;     // the step's weighted total, or null
+  const float* surface_total;  // the surface term's, or null
+  float* step_total;           // [1] or null
+};
+
+// S of one term: lane l takes the elements l, l + 256, ... in ascending order, then the block's fixed-order sum
+__device__ __forceinline__ float sequence_term_sum(const float* x, int L, const Fit3dSequenceArgs& a, float* red) {
+  float s = 0.f;
+  const int count = a.N * L;
+  for (int i = threadIdx.x; i < count; i += kSeqBlock) {
+    const int n = i / L;
+    if (n + 1 < a.mesh_start[n] + a.mesh_len[n]) s = temporal_pair_sq(s, x[i], x[i + L]);
+  }
+  return block_sum(s, red);
+}
+
+__global__ __launch_bounds__(kSeqBlock) void fit3d_sequence_kernel(Fit3dSequenceArgs a) {
+  if (blockIdx.x == 0) {
+    __shared__ float red[16];
+    const float sj = a.joint ? sequence_term_sum(a.joint_rot, kSeqJointLen, a, red) : 0.f;
+    const float sg = a.global ? sequence_term_sum(a.global_rot, kSeqGlobalLen, a, red) : 0.f;
+    const float st = a.trans_on ? sequence_term_sum(a.trans, kSeqTransLen, a, red) : 0.f;
+    if (threadIdx.x == 0) {
+      const float lj = a.joint ? temporal_loss(a.w_joint, sj, kSeqJointLen) : 0.f;
+      const float lg = a.global ? temporal_loss(a.w_global, sg, kSeqGlobalLen) : 0.f;
+      const float lt = a.trans_on ? temporal_loss(a.w_trans, st, kSeqTransLen) : 0.f;
+      const float tot = temporal_total(lj, lg, lt);
+      a.losses[0] = lj;
+      a.losses[1] = lg;
+      a.losses[2] = lt;
+      a.losses[3] = tot;
+      if (a.step_total != nullptr) {
+        float base = a.base_total[0];
+        if (a.surface_total != nullptr) base += a.surface_total[0];
+        a.step_total[0] = base + tot;
+      }
+    }
+    return;
+  }
+  const int i = ((int)blockIdx.x - 1) * kSeqBlock + (int)threadIdx.x;
+  if (i < a.nshape) {
+    const int c = i / a.nb, col = i - c * a.nb;
+    const int start = a.clip_start[c], len = a.clip_len[c];
+    if (len < 2) return;
+    const float s = sequence_row_sum(a.g_betas, a.nb, col, start, len);
+    for (int r = 0; r < len; ++r) a.g_betas[(size_t)(start + r) * a.nb + col] = s;
+    return;
+  }
+  const int j = i - a.nshape;
+  if (j >= a.N * kSeqGradCols) return;
+  const int n = j / kSeqGradCols, k = j - n * kSeqGradCols;
+  const int start = a.mesh_start[n], len = a.mesh_len[n];
+  if (len < 2) return;
+  const bool has_prev = n > start, has_next = n + 1 < start + len;
+  float* g;
+  const float* x;
+  int L;
+  float c;
+  if (k < kSeqGlobalLen) {
+    if (!a.add_global) return;
+    g = a.g_theta + (size_t)n * kSeqThetaCols + k; x = a.global_rot + (size_t)n * kSeqGlobalLen + k; L = kSeqGlobalLen; c = a.c_global;
+  } else if (k < kSeqThetaCols) {
+    if (!a.add_joint) return;
+    g = a.g_theta + (size_t)n * kSeqThetaCols + k; x = a.joint_rot + (size_t)n * kSeqJointLen + (k - kSeqGlobalLen); L = kSeqJointLen; c = a.c_joint;
+  } else {
+    if (!a.add_trans) return;
+    g = a.g_trans + (size_t)n * kSeqTransLen + (k - kSeqThetaCols); x = a.trans + (size_t)n * kSeqTransLen + (k - kSeqThetaCols); L = kSeqTransLen; c = a.c_trans;
+  }
+  const float prev = has_prev ? x[-L] : 0.f, next = has_next ? x[L] : 0.f;
+  *g = temporal_grad(*g, c, *x, prev, next, has_prev, has_next);
+}
+
 // ---- Adam on all trained parameters of a Stage.step in one launch ----------------------------------------------------
 // torch.optim.Adam (adam_update) over the trained parameters, one launch (Fit3dAdamArgs: smalfit_plan.h, beside plan_fit3d, which
 // sizes its segments)

@@ -39,6 +39,7 @@
 #include "smalfit_internal.h"
 #include "mesh3d_math.h"
 #include "mesh3d_grid.h"
+#include "fit3d_sequence_math.h"
 #include "rigid_align_math.h"
 #include "smalfit_plan.h"
 

@@ -260,6 +260,12 @@ static int launch_mesh_sampler(const smalfit_mesh_targets* t, hipStream_t st, in
   return 0;
 }
 
+// the body of every smalfit_fit3d_step*, defined behind them with the scan-sequence block it optionally takes
+static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
+                          const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
+                          const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb, const smalfit_scan_sequence* seq,
+                          const smalfit_sequence_args* q);
+
 extern "C" {
 
 int smalfit_mesh_objective_create(int num_verts, int num_faces, const int* faces, int max_meshes, int max_points,
@@ -634,6 +640,56 @@ int smalfit_fit3d_step_robust(smalfit_engine* e, smalfit_mesh_objective* m, smal
                               const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
                               const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb) {
   const char* who = rb ? "smalfit_fit3d_step_robust" : cg ? "smalfit_fit3d_step_partial" : gate ? "smalfit_fit3d_step_gated" : sf ? "smalfit_fit3d_step_surface" : "smalfit_fit3d_step";
+  return fit3d_step_run(who, e, m, t, stream, a, sf, gate, cg, rb, nullptr, nullptr);
+}
+
+}  // extern "C"
+
+// ---- the scan-sequence block ---------------------------------------------------------------------------------------------
+struct smalfit_scan_sequence {
+  int N = 0, G = 0, lengths_sum = 0;
+  bool any_long = false;       // some clip is longer than 1
+  int* tables = nullptr;       // one device allocation: clip_start [G], clip_len [G], mesh_start [N], mesh_len [N]
+};
+
+// what fit3d_sequence_kernel is given beside the block: the parameters it reads, the gradients it updates (null: not formed), the
+// totals step_total is formed from
+struct SequenceRun {
+  int num_betas = 0;
+  const float *global_rot = nullptr, *joint_rot = nullptr, *trans = nullptr;
+  float *g_betas = nullptr, *g_theta = nullptr, *g_trans = nullptr;
+  bool add_global = false, add_joint = false;       // which column blocks of g_theta
+  const float *base_total = nullptr, *surface_total = nullptr;
+};
+static int launch_sequence(const smalfit_scan_sequence* s, hipStream_t st, const smalfit_sequence_args* q, const SequencePlan& p,
+                           const SequenceRun& r) {
+  Fit3dSequenceArgs k{};
+  k.N = s->N; k.G = s->G; k.nb = r.num_betas;
+  k.clip_start = s->tables; k.clip_len = s->tables + s->G; k.mesh_start = s->tables + 2 * s->G; k.mesh_len = s->tables + 2 * s->G + s->N;
+  k.global_rot = r.global_rot; k.joint_rot = r.joint_rot; k.trans = r.trans;
+  k.g_betas = r.g_betas; k.g_theta = r.g_theta; k.g_trans = r.g_trans;
+  k.nshape = p.share && r.g_betas ? sequence_shape_elements(p, s->G, r.num_betas) : 0;
+  k.joint = p.joint; k.global = p.global; k.trans_on = p.trans;
+  k.add_joint = p.joint && r.g_theta && r.add_joint;
+  k.add_global = p.global && r.g_theta && r.add_global;
+  k.add_trans = p.trans && r.g_trans;
+  k.w_joint = q->w_temp_joint; k.w_global = q->w_temp_global; k.w_trans = q->w_temp_trans;
+  k.c_joint = temporal_grad_scale(q->w_temp_joint, kSeqJointLen);
+  k.c_global = temporal_grad_scale(q->w_temp_global, kSeqGlobalLen);
+  k.c_trans = temporal_grad_scale(q->w_temp_trans, kSeqTransLen);
+  k.losses = q->losses;
+  k.base_total = r.base_total; k.surface_total = r.surface_total; k.step_total = r.base_total ? q->step_total : nullptr;
+  fit3d_sequence_kernel<<<sequence_blocks(p, s->N, s->G, r.num_betas), kSeqBlock, 0, st>>>(k);
+  LAUNCH_OK("fit3d_sequence_kernel");
+  return 0;
+}
+
+// the body of every smalfit_fit3d_step* and of smalfit_scan_sequence_step.  seq == nullptr (the five entry points of before): what
+// they launched and the bits they wrote
+static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
+                          const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
+                          const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb, const smalfit_scan_sequence* seq,
+                          const smalfit_sequence_args* q) {
   if (refused(who, null_argument_refusal(e && m && a))) return 1;
   const ModelDev& md = e->model->dev;
   if (refused(who, fit3d_args_refusal(a, Fit3dFacts{e->maxM, md.V, md.NBall, m->max_meshes, m->max_points, m->t.V,
@@ -649,9 +705,39 @@ int smalfit_fit3d_step_robust(smalfit_engine* e, smalfit_mesh_objective* m, smal
   if (rb && refused(who, robust_args_refusal(rb, RobustFacts{true, true, a->weights[0] > 0.f, surface && sf->w_point_surface > 0.f,
                                                              surface && sf->w_vert_surface > 0.f})))
     return 1;
+  if (seq && refused(who, sequence_args_refusal(q, SequenceFacts{seq->N, seq->lengths_sum, a->num_meshes, true, true, true, true}))) return 1;
   const Fit3dPlan plan = plan_fit3d(a, md.V, surface && sf->w_point_surface > 0.f);
   const int N = a->num_meshes, nb = a->num_betas, S = a->num_points;
   hipStream_t st = (hipStream_t)stream;
+  // the sequence block: a block that couples nothing launches nothing, its losses read 0 and its step_total is the step's own
+  // total (formed by the surface term where that is on: through a copy of its block when the caller asked it for none)
+  const SequencePlan sq = seq ? plan_sequence(q, seq->any_long, plan.need_beta) : SequencePlan{};
+  smalfit_surface_term_args sf_total;
+  if (seq && !sq.launch && q->step_total && surface && !sf->step_total) {
+    sf_total = *sf;
+    sf_total.step_total = q->step_total;
+    sf = &sf_total;
+  }
+  auto couple = [&]() -> int {
+    if (!seq) return 0;
+    if (!sq.launch) {
+      HIP_OK(hipMemsetAsync(q->losses, 0, 4 * sizeof(float), st));
+      const float* total = surface ? sf->step_total : a->losses + 4;
+      if (q->step_total && q->step_total != total) HIP_OK(hipMemcpyAsync(q->step_total, total, sizeof(float), hipMemcpyDeviceToDevice, st));
+      return 0;
+    }
+    SequenceRun r;
+    r.num_betas = nb;
+    r.global_rot = a->global_rot; r.joint_rot = a->joint_rot; r.trans = a->trans;
+    // a gradient joins only where its parameter is trained in this step
+    r.g_betas = plan.need_beta ? m->gbetas : nullptr;
+    r.add_global = a->lr_global_rot > 0.f; r.add_joint = a->lr_joint_rot > 0.f;
+    r.g_theta = r.add_global || r.add_joint ? e->dtheta : nullptr;
+    r.g_trans = a->lr_trans > 0.f ? m->dtrans : nullptr;
+    r.base_total = a->losses + 4;
+    r.surface_total = surface ? sf->losses + 2 : nullptr;
+    return launch_sequence(seq, st, q, sq, r);
+  };
 
   // SMAL3DFitter.forward: LBS on [global_rot | joint_rot] (theta is built inside the head kernel), untranslated
   HeadExtras ex;
@@ -697,13 +783,15 @@ int smalfit_fit3d_step_robust(smalfit_engine* e, smalfit_mesh_objective* m, smal
   }
   // (a step without the term skips both of its directions: their weight sums read 0)
   if (!surface && rb && rb->surface_weight_sums) HIP_OK(hipMemsetAsync(rb->surface_weight_sums, 0, (size_t)N * 2 * sizeof(float), st));
-  if (!plan.any_trained) return 0;
+  if (!plan.any_trained) return couple();   // (nothing is trained: the block only reports its losses)
 
   // back through the LBS (forward state is still in the engine)
   if (plan.need_pose || plan.need_beta) {
     if (run_lbs_backward(e, st, N, nb, 0, nullptr, nullptr, e->dext, true, plan.need_beta, false, nullptr, 105)) return 1;
     if (plan.need_beta && launch_frame_betas_assembly(e, st, N, nb, m->gbetas)) return 1;
   }
+  // one shape per clip and the temporal terms' gradients, on the gradients Adam is about to read
+  if (couple()) return 1;
 
   // torch.optim.Adam over the parameters of the scheme, one launch
   struct Tensor { float* p; const float* g; float* mm; float* vv; float lr; };
@@ -727,6 +815,78 @@ int smalfit_fit3d_step_robust(smalfit_engine* e, smalfit_mesh_objective* m, smal
   fit3d_adam_kernel<<<plan.adam_blocks, 256, 0, st>>>(ad);
   LAUNCH_OK("fit3d_adam_kernel");
   return 0;
+}
+
+extern "C" {
+
+int smalfit_scan_sequence_create(int num_meshes, int num_clips, const int* clip_lengths, smalfit_scan_sequence** out) {
+  const char* who = "smalfit_scan_sequence_create";
+  if (refused(who, sequence_create_refusal(out != nullptr, num_meshes, num_clips, clip_lengths))) return 1;
+  auto* s = new smalfit_scan_sequence();
+  s->N = num_meshes; s->G = num_clips;
+  std::vector<int> host((size_t)2 * num_clips + 2 * num_meshes);
+  int start = 0;
+  for (int c = 0; c < num_clips; ++c) {
+    const int len = clip_lengths[c];
+    host[c] = start;
+    host[num_clips + c] = len;
+    for (int n = start; n < start + len; ++n) {
+      host[2 * num_clips + n] = start;
+      host[2 * num_clips + num_meshes + n] = len;
+    }
+    s->any_long = s->any_long || len > 1;
+    start += len;
+  }
+  s->lengths_sum = start;
+  auto bail = [&](const char* what) {
+    smalfit_scan_sequence_destroy(s);
+    return refused(who, what);
+  };
+  if (hipMalloc((void**)&s->tables, host.size() * sizeof(int)) != hipSuccess) {
+    s->tables = nullptr;
+    return bail("hipMalloc of the clip tables failed (no HIP device?)");
+  }
+  if (hipMemcpy(s->tables, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy of the clip tables failed");
+  *out = s;
+  return 0;
+}
+
+void smalfit_scan_sequence_destroy(smalfit_scan_sequence* s) {
+  if (!s) return;
+  if (s->tables) (void)hipFree(s->tables);
+  delete s;
+}
+
+int smalfit_scan_sequence_couple(smalfit_scan_sequence* s, void* stream, const smalfit_sequence_args* q, int num_betas,
+                                 const float* global_rot, const float* joint_rot, const float* trans, float* g_betas, float* g_theta,
+                                 float* g_trans) {
+  const char* who = "smalfit_scan_sequence_couple";
+  if (refused(who, null_argument_refusal(s && q))) return 1;
+  if (refused(who, sequence_args_refusal(q, SequenceFacts{s->N, s->lengths_sum, s->N, false, global_rot != nullptr, joint_rot != nullptr,
+                                                          trans != nullptr})))
+    return 1;
+  if (g_betas && q->share_shape && (num_betas <= 0 || num_betas > 64)) return refused(who, "num_betas out of range");
+  hipStream_t st = (hipStream_t)stream;
+  const SequencePlan p = plan_sequence(q, s->any_long, g_betas != nullptr);
+  if (!p.launch) {
+    HIP_OK(hipMemsetAsync(q->losses, 0, 4 * sizeof(float), st));
+    return 0;
+  }
+  SequenceRun r;
+  r.num_betas = num_betas;
+  r.global_rot = global_rot; r.joint_rot = joint_rot; r.trans = trans;
+  r.g_betas = g_betas; r.g_theta = g_theta; r.g_trans = g_trans;
+  r.add_global = r.add_joint = g_theta != nullptr;
+  return launch_sequence(s, st, q, p, r);
+}
+
+int smalfit_scan_sequence_step(smalfit_scan_sequence* s, smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t,
+                               void* stream, const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf,
+                               const smalfit_surface_gate_args* gate, const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb,
+                               const smalfit_sequence_args* q) {
+  const char* who = "smalfit_scan_sequence_step";
+  if (refused(who, null_argument_refusal(s && q))) return 1;
+  return fit3d_step_run(who, e, m, t, stream, a, sf, gate, cg, rb, s, q);
 }
 
 }  // extern "C"

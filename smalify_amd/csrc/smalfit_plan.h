@@ -888,6 +888,72 @@ inline Fit3dRiders plan_fit3d_riders(const smalfit_surface_term_args* sf, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// the scan-sequence block (smalfit_scan_sequence_*): which lengths and blocks are refused, and whether anything is launched
+// ------------------------------------------------------------------------------------------------
+// -> why smalfit_scan_sequence_create refuses (the text behind its name), or nullptr.  clip_lengths is the host's
+inline const char* sequence_create_refusal(bool given, int num_meshes, int num_clips, const int* clip_lengths) {
+  if (!given || !clip_lengths) return "null argument";
+  if (num_meshes <= 0 || num_clips <= 0) return "num_meshes and num_clips must be positive";
+  long long sum = 0;
+  for (int c = 0; c < num_clips; ++c) {
+    if (clip_lengths[c] <= 0) return "every clip length must be positive";
+    sum += clip_lengths[c];
+  }
+  if (sum != num_meshes) return "clip_lengths do not sum to num_meshes";
+  return nullptr;
+}
+struct SequenceFacts {
+  int handle_meshes, lengths_sum;   // the N the handle was built for | the sum of its clip lengths
+  int num_meshes;                   // the N of this call
+  bool step;                        // the block rides on a smalfit_fit3d_args (else smalfit_scan_sequence_couple)
+  bool global_rot, joint_rot, trans;   // the parameters the call was given
+};
+// -> why the sequence entry points refuse the block (the text behind "<entry point>: "), or nullptr; asked after the call's other
+// blocks have been accepted.  The order: the handle's N, the lengths against N, the three weights (joint, global, trans), losses,
+// step_total outside a step, a term without its parameter
+inline const char* sequence_args_refusal(const smalfit_sequence_args* q, const SequenceFacts& f) {
+  if (f.handle_meshes != f.num_meshes) return "the sequence handle was built for another num_meshes";
+  if (f.lengths_sum != f.num_meshes) return "clip_lengths do not sum to num_meshes";
+  if (!std::isfinite(q->w_temp_joint)) return "w_temp_joint is not finite";
+  if (!std::isfinite(q->w_temp_global)) return "w_temp_global is not finite";
+  if (!std::isfinite(q->w_temp_trans)) return "w_temp_trans is not finite";
+  if (!q->losses) return "losses is NULL";
+  if (!f.step && q->step_total) return "step_total given outside a step";
+  if (q->w_temp_joint > 0.f && !f.joint_rot) return "w_temp_joint > 0 but joint_rot is missing";
+  if (q->w_temp_global > 0.f && !f.global_rot) return "w_temp_global > 0 but global_rot is missing";
+  if (q->w_temp_trans > 0.f && !f.trans) return "w_temp_trans > 0 but trans is missing";
+  return nullptr;
+}
+// what a block that sequence_args_refusal accepts couples.  any_long_clip: some clip is longer than 1; betas_given: there is a
+// betas gradient to share (a step: lr_betas > 0; couple: g_betas given).  launch: fit3d_sequence_kernel runs at all -- a block
+// that couples nothing launches nothing and its losses read 0
+struct SequencePlan {
+  bool launch;
+  bool share;                  // the shape sum runs
+  bool joint, global, trans;   // the term is evaluated
+};
+inline SequencePlan plan_sequence(const smalfit_sequence_args* q, bool any_long_clip, bool betas_given) {
+  SequencePlan p{};
+  if (!q || !any_long_clip) return p;
+  p.share = q->share_shape != 0 && betas_given;
+  p.joint = q->w_temp_joint > 0.f;
+  p.global = q->w_temp_global > 0.f;
+  p.trans = q->w_temp_trans > 0.f;
+  p.launch = p.share || p.joint || p.global || p.trans;
+  if (!p.launch) p = SequencePlan{};
+  return p;
+}
+// fit3d_sequence_kernel: block 0 sums the losses; behind it one thread per output element, the shape sums (clip, column) first,
+// then the temporal gradients (mesh, 105 columns of d theta | 3 of d trans)
+constexpr int kSeqBlock = 256;
+constexpr int kSeqGradCols = 105 + 3;
+inline int sequence_shape_elements(const SequencePlan& p, int num_clips, int num_betas) { return p.share ? num_clips * num_betas : 0; }
+inline int sequence_blocks(const SequencePlan& p, int num_meshes, int num_clips, int num_betas) {
+  const int elements = sequence_shape_elements(p, num_clips, num_betas) + (p.joint || p.global || p.trans ? num_meshes * kSeqGradCols : 0);
+  return 1 + (elements + kSeqBlock - 1) / kSeqBlock;
+}
+
+// ------------------------------------------------------------------------------------------------
 // smalfit_fit_args: which blocks are refused
 // ------------------------------------------------------------------------------------------------
 // struct_size first: with a block laid out by another version of smalfit.h no other field can be trusted (subject_frames sits

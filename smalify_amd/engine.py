@@ -929,6 +929,80 @@ def keep_count(fraction, count):
     return int(min(int(count), max(1, math.ceil(float(fraction) * int(count)))))
 
 
+TEMPORAL_KEYS = ("w_temp_joint", "w_temp_global", "w_temp_trans")
+
+
+def temporal_weights(weights=None):
+    """the three temporal weights of a scan sequence with every one 0 (off), overridden by `weights`; an unknown key raises"""
+    out = dict.fromkeys(TEMPORAL_KEYS, 0.0)
+    for k, v in (weights or {}).items():
+        if k not in out:
+            raise KeyError("unknown temporal weight %r (have %s)" % (k, list(TEMPORAL_KEYS)))
+        out[k] = float(v)
+    return out
+
+
+def check_clip_lengths(clip_lengths, num_meshes):
+    """-> the lengths as a list of ints; ValueError unless they are positive and sum to num_meshes"""
+    lengths = [int(c) for c in clip_lengths]
+    if not lengths or any(c <= 0 for c in lengths) or sum(lengths) != int(num_meshes):
+        raise ValueError("clip_lengths %r: positive integers with sum %d expected" % (lengths, int(num_meshes)))
+    return lengths
+
+
+class ScanSequence:
+    """The meshes of a batch as clips of one animal each (smalfit_scan_sequence; the definitions are this project's,
+    include/smalfit.h): within a clip one shape -- the betas gradient rows of a clip replaced by their sum -- and the 2-D fitter's
+    temporal terms between consecutive poses.  A handle of its own, for one N and one list of lengths."""
+
+    def __init__(self, clip_lengths, num_meshes=None):
+        if not torch.cuda.is_available():
+            raise SmalfitError("no HIP device available: smalify_amd has no CPU fallback")
+        lengths = [int(c) for c in clip_lengths]
+        self.num_meshes = int(sum(lengths) if num_meshes is None else num_meshes)
+        self.clip_lengths = tuple(lengths)
+        self.lib = _lib.load()
+        create = _lib.resolve(self.lib, "smalfit_scan_sequence_create")
+        self._destroy = _lib.resolve(self.lib, "smalfit_scan_sequence_destroy")
+        self._couple = _lib.resolve(self.lib, "smalfit_scan_sequence_couple")
+        torch.cuda.init()
+        torch.cuda.current_device()
+        h = C.c_void_p()
+        check(create(self.num_meshes, len(lengths), (C.c_int * max(len(lengths), 1))(*lengths), C.byref(h)), "smalfit_scan_sequence_create")
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self._destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def block(self, share_shape=True, temporal=None, losses=None, step_total=None):
+        """-> (smalfit_sequence_args, its losses tensor (4,)): the block of couple() and of smalfit_scan_sequence_step"""
+        w = temporal_weights(temporal)
+        if losses is None:
+            losses = torch.zeros(4, device="cuda")
+        q = _lib.SequenceArgs()
+        q.share_shape = int(bool(share_shape))
+        q.w_temp_joint, q.w_temp_global, q.w_temp_trans = (w[k] for k in TEMPORAL_KEYS)
+        q.losses = losses.data_ptr()
+        q.step_total = step_total.data_ptr() if step_total is not None else None
+        return q, losses
+
+    def couple(self, global_rot=None, joint_rot=None, trans=None, g_betas=None, g_theta=None, g_trans=None, share_shape=True,
+               temporal=None, losses=None):
+        """the coupling alone on the caller's gradients, in place (smalfit_scan_sequence_couple): g_betas (N,nb) rows of a clip
+        become their sum; g_theta (N,105) or (N,35,3) and g_trans (N,3) receive the temporal terms' gradients at global_rot (N,3),
+        joint_rot (N,34,3), trans (N,3).  Any gradient may be None.  -> losses (4,) device: joint, global, trans, their sum"""
+        q, losses = self.block(share_shape, temporal, losses)
+        nb = int(g_betas.shape[1]) if g_betas is not None else 0
+        check(self._couple(self.handle, _stream(), C.byref(q), nb, _ptr(global_rot), _ptr(joint_rot), _ptr(trans), _ptr(g_betas),
+                           _ptr(g_theta), _ptr(g_trans)), "smalfit_scan_sequence_couple")
+        return losses
+
+
 def _narrowest(names, *blocks):
     """-> (the narrowest entry point of `names` whose signature holds the last block that is not None, the blocks it takes: a
     library built before the later symbols still serves the calls it could serve)"""

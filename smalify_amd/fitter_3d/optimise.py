@@ -4,7 +4,13 @@
 
 Same arguments and YAML layout (`stages: {name: {scheme, nits, lr, loss_weights, custom_lrs}}`, `args: {...}` overriding
 the command line) as fitter_3d/optimise.py:18-90 and fitter_3d/example_cfg.yaml.  Beyond the reference, opt-in: --metrics,
---scan_index, --prealign (YAML `args: {prealign: true}`) with --prealign_trim_point / --prealign_trim_vert."""
+--scan_index, --prealign (YAML `args: {prealign: true}`) with --prealign_trim_point / --prealign_trim_vert, and scan sequences:
+--sequence (YAML `args: {sequence: true}`) or --clip_lengths L ... make the meshes clips of one animal each, with one shape per
+clip and, per stage, `share_shape:` and a `temporal: {w_temp_joint, w_temp_global, w_temp_trans}` block.
+
+The order of a sequence: with --sequence or --clip_lengths the .obj files are taken in ascending order of their file names (Python's
+`sorted`: zero-pad the frame numbers), then every --frame_step'th of them; that is the batch order, and batch order within a clip
+is temporal order.  Without either flag the files keep os.listdir's order, as in the reference, and the meshes stay unrelated."""
 from __future__ import annotations
 
 import argparse
@@ -47,7 +53,30 @@ def build_parser():
     parser.add_argument("--prealign_trim_vert", type=float, default=None, metavar="F",
                         help="with --prealign: every ICP iteration keeps this fraction in (0, 1] of the SMAL vertices, those nearest "
                              "to the target (trimmed ICP: a scan that shows part of the animal)")
+    parser.add_argument("--sequence", action="store_true",
+                        help="the meshes are ONE clip: scans of one animal moving, in ascending file-name order; one shape for all "
+                             "of them, and the stages' temporal weights tie consecutive poses")
+    parser.add_argument("--clip_lengths", type=int, nargs="+", default=None, metavar="L",
+                        help="the meshes are several clips, in ascending file-name order: positive lengths that sum to the number "
+                             "of meshes loaded (a length of 1 is an unrelated mesh)")
     return parser
+
+
+def sequence_clip_lengths(args, num_meshes=None):
+    """-> the clip lengths --sequence / --clip_lengths (or the YAML's args) ask for, None when neither is given.  num_meshes: the
+    number of meshes loaded, needed for --sequence and checked against --clip_lengths when given"""
+    lengths = getattr(args, "clip_lengths", None)
+    sequence = bool(getattr(args, "sequence", False))
+    if lengths is not None:
+        lengths = [int(c) for c in lengths]
+        if sequence and len(lengths) != 1:
+            raise ValueError("--sequence makes all meshes one clip: give it or --clip_lengths, not both")
+        if any(c <= 0 for c in lengths) or (num_meshes is not None and sum(lengths) != int(num_meshes)):
+            raise ValueError("--clip_lengths %r: positive lengths with sum %s expected" % (lengths, num_meshes))
+        return lengths
+    if not sequence:
+        return None
+    return None if num_meshes is None else [int(num_meshes)]
 
 
 def main(args, model_data=None, smal_data=None):
@@ -67,9 +96,12 @@ def main(args, model_data=None, smal_data=None):
     if any(v is not None for v in trims.values()) and not getattr(args, "prealign", False):
         raise ValueError("--prealign_trim_point / --prealign_trim_vert trim the ICP of --prealign: give --prealign with them")
     trims = {k: float(v) for k, v in trims.items() if v is not None}
+    is_sequence = bool(getattr(args, "sequence", False)) or getattr(args, "clip_lengths", None) is not None
+    sequence_order = dict(sorting=sorted) if is_sequence else {}       # a sequence needs a defined order: ascending file names
     mesh_names, target_meshes = load_meshes(mesh_dir=args.mesh_dir, frame_step=args.frame_step,
-                                            scan_index=bool(getattr(args, "scan_index", False)))
+                                            scan_index=bool(getattr(args, "scan_index", False)), **sequence_order)
     n_batch = len(target_meshes)
+    clip_lengths = sequence_clip_lengths(args, n_batch) if is_sequence else None
     os.makedirs(args.results_dir, exist_ok=True)
     manager = StageManager(out_dir=args.results_dir, labels=mesh_names)
     smal_model = SMAL3DFitter(batch_size=n_batch, shape_family=args.shape_family_id, model_data=model_data,
@@ -86,6 +118,11 @@ def main(args, model_data=None, smal_data=None):
                            meshes=[dict(name=nm, **row) for nm, row in zip(names, report)]), fh, indent=1)
     stage_kwargs = dict(target_meshes=target_meshes, smal_3d_fitter=smal_model, out_dir=args.results_dir,
                         mesh_names=mesh_names, seed=getattr(args, "seed", 0))
+    if clip_lengths is not None:
+        # one shape per clip from the first stage on (a stage that shares the shape refuses rows that differ within a clip)
+        from .trainer import tie_shapes
+        tie_shapes(smal_model, clip_lengths)
+        stage_kwargs["clip_lengths"] = clip_lengths
     if stage_options is not None:
         for stage_name, kwargs in stage_options.items():
             manager.add_stage(Stage(name=stage_name, **kwargs, **stage_kwargs))

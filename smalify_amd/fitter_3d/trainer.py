@@ -137,7 +137,8 @@ class Stage:
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes, mesh_names=[],
                  name="optimise", loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None,
-                 device="cuda", seed=0, iteration_offset=0, scan_index=False, surface_gates=None, chamfer_gates=None, robust=None):
+                 device="cuda", seed=0, iteration_offset=0, scan_index=False, clip_lengths=None, share_shape=True, temporal=None,
+                 surface_gates=None, chamfer_gates=None, robust=None):
         self.n_it = int(nits)
         self.name = name
         self.out_dir = out_dir
@@ -183,6 +184,18 @@ class Stage:
             if p.requires_grad:
                 self._adam[g["name"]] = dict(lr=float(g.get("lr", self.lr)), m=torch.zeros_like(p), v=torch.zeros_like(p))
         fit = smal_3d_fitter
+        # a scan sequence (include/smalfit.h): the batch as clips of one animal each, in batch order; within a clip one shape and the
+        # temporal terms between consecutive poses.  None: the meshes are unrelated, and nothing of this is constructed or called
+        self.clip_lengths = None if clip_lengths is None else tuple(eng.check_clip_lengths(clip_lengths, fit.batch_size))
+        self.share_shape = bool(share_shape)
+        self.temporal = eng.temporal_weights(temporal)
+        self._sequence = None
+        self._seq_args = None          # smalfit_sequence_args of step(), built on the first step
+        self._seq_losses = None
+        if self.clip_lengths is not None:
+            self._sequence = eng.ScanSequence(self.clip_lengths, fit.batch_size)
+            if self.share_shape and "betas" in self._adam:
+                _require_tied_shapes(fit, self.clip_lengths)     # one host read, here only
         V = int(fit.smal_model.v_template.shape[0])
         self.n_verts = V
         self.faces = fit.faces.detach()
@@ -284,6 +297,12 @@ class Stage:
         the most recent robust evaluation or step (a term without a scale on: None); None while no scale applies"""
         return self._robust_weights
 
+    @property
+    def last_temporal_losses(self):
+        """device tensor (4,): the temporal terms on joint_rot, global_rot and trans and their sum, of the most recent evaluation or
+        step; None without clip_lengths"""
+        return self._seq_losses
+
     def _chamfer_gated(self):
         return self.chamfer_gates_on and self.loss_weights["w_chamfer"] > 0
 
@@ -343,6 +362,15 @@ class Stage:
             self._surface_losses = sf["losses"]
             total = total + sf["losses"][2]
         dbeta, dtheta, dls = e.lbs_backward(betas, theta, ls, o["dverts"], None)
+        if self._sequence is not None:
+            # the coupling alone on the gradients of the trained parameters, where the fused step applies it: behind the LBS adjoint
+            pose = "global_rot" in self._adam or "joint_rot" in self._adam
+            self._seq_losses = self._sequence.couple(
+                fit.global_rot.detach().contiguous(), fit.joint_rot.detach().contiguous(), fit.trans.detach().contiguous(),
+                g_betas=dbeta if "betas" in self._adam else None, g_theta=dtheta if pose else None,
+                g_trans=o["dtrans"] if "trans" in self._adam else None, share_shape=self.share_shape, temporal=self.temporal,
+                losses=self._seq_losses)
+            total = total + self._seq_losses[3]
         grads = {"betas": dbeta, "global_rot": dtheta[:, 0].contiguous(), "joint_rot": dtheta[:, 1:].contiguous(),
                  "log_beta_scales": dls, "trans": o["dtrans"], "deform_verts": o["dverts"]}
         return total, grads
@@ -372,6 +400,14 @@ class Stage:
             gate = self._gate_block() if self.gates_on else None
         cgate = self._chamfer_gate_block() if self._chamfer_gated() else None
         rb = self._robust_block() if self._robust_applies() else None
+        if self._sequence is not None:
+            # a scan sequence: the widest step, with the sequence block behind the four others
+            q = self._sequence_block()
+            name = "smalfit_scan_sequence_step"
+            eng.check(_lib.resolve(e.lib, name)(self._sequence.handle, e.handle, self._objective.handle, dev_targets.handle, eng._stream(),
+                                                C.byref(a), *eng._refs((sf, gate, cgate, rb)), C.byref(q)), name)
+            self._last_points = self._points
+            return self._seq_total[0]
         # one call, through the narrowest entry point whose signature holds the last block that is on
         name, blocks = eng._narrowest(_STEP_ENTRY_POINTS, sf, gate, cgate, rb)
         eng.check(_lib.resolve(e.lib, name)(e.handle, self._objective.handle, dev_targets.handle, eng._stream(), C.byref(a),
@@ -470,6 +506,15 @@ class Stage:
         self._chamfer_kept = self._step_chamfer_kept
         return self._cgate_args
 
+    def _sequence_block(self):
+        """the smalfit_sequence_args of step(): the stage's switch and weights, the four temporal figures, the grand total"""
+        if self._seq_args is None:
+            self._seq_step_losses = torch.zeros(4, device=self.device)
+            self._seq_total = torch.zeros(1, device=self.device)
+            self._seq_args, _ = self._sequence.block(self.share_shape, self.temporal, self._seq_step_losses, self._seq_total)
+        self._seq_losses = self._seq_step_losses
+        return self._seq_args
+
     def _robust_block(self):
         """the smalfit_robust_args of step(): the stage's scales, the weight sums of both terms"""
         if self._robust_args is None:
@@ -518,6 +563,8 @@ class Stage:
         out["verts"] = self.smal_3d_fitter().cpu().detach().numpy()
         out["faces"] = self.faces.cpu().detach().numpy()
         out["labels"] = labels
+        if self.clip_lengths is not None:
+            out["clip_lengths"] = np.asarray(self.clip_lengths, np.int64)
         os.makedirs(self.out_dir, exist_ok=True)
         np.savez(os.path.join(self.out_dir, f"{self.name}.npz"), **out)
 
@@ -529,6 +576,45 @@ def _objective_for(fitter, max_points):
         obj = eng.MeshObjective(int(fitter.smal_model.v_template.shape[0]), fitter.smal_model.f, fitter.batch_size, max_points)
         fitter._mesh_objective = obj
     return obj
+
+
+def _clip_rows_tied(x, clip_lengths):
+    """every row of the host array x is bit-equal to the first row of its clip"""
+    x = np.ascontiguousarray(x)
+    bits = x.view(np.uint32) if x.dtype == np.float32 else x
+    start = 0
+    for length in clip_lengths:
+        if not (bits[start:start + length] == bits[start:start + 1]).all():
+            return False
+        start += length
+    return True
+
+
+def _require_tied_shapes(fitter, clip_lengths):
+    host = torch.cat([fitter.betas.detach(), fitter.log_beta_scales.detach()], dim=1).cpu().numpy()
+    if not _clip_rows_tied(host, clip_lengths):
+        raise ValueError("share_shape: the betas / log_beta_scales rows of a clip are not bit-equal; call "
+                         "smalify_amd.fitter_3d.trainer.tie_shapes(fitter, clip_lengths) before the stage is built")
+
+
+def tie_shapes(fitter, clip_lengths, how="first"):
+    """One shape per clip before a sequence stage: every betas row of a clip is overwritten with one row -- how="first": the
+    clip's first row; how="mean": the float32 mean of the clip's rows.  log_beta_scales is never trained and is not written: rows
+    of it that differ within a clip raise ValueError.  clip_lengths: positive integers with sum fitter.batch_size, clips in batch
+    order.  Reading the rows synchronises."""
+    lengths = eng.check_clip_lengths(clip_lengths, fitter.batch_size)
+    if how not in ("first", "mean"):
+        raise ValueError("tie_shapes: how must be 'first' or 'mean', got %r" % (how,))
+    if not _clip_rows_tied(fitter.log_beta_scales.detach().cpu().numpy(), lengths):
+        raise ValueError("tie_shapes: log_beta_scales rows differ within a clip; they are never trained, set them equal first")
+    betas = fitter.betas.detach()
+    start = 0
+    for length in lengths:
+        rows = betas[start:start + length]
+        row = rows[0].clone() if how == "first" else rows.mean(dim=0)
+        rows.copy_(row.unsqueeze(0).expand_as(rows))
+        start += length
+    return fitter
 
 
 # rigid_prealign draws its target points with a key of its own, the way Stage.metrics does: never one of the fit's draws
