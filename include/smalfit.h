@@ -850,10 +850,21 @@ int smalfit_fit3d_step_robust(smalfit_engine* engine, smalfit_mesh_objective* ob
  *                     diagonal entry wins, the lowest index among equal ones.  The quaternion is normalised and R formed from
  *                     it: det R = +1 always, a reflection is never returned.  t = (c_P + mp) - R (c_X + mx).
  *                  5. rank test: with l1 >= l2 the two largest eigenvalues found, the rotation is DETERMINED when
- *                       l1 - l2 > 1e-5 sqrt(sum w |x|^2  sum w |p|^2)
- *                     in float32 (the centred sums of 4.; a NaN compares false).  Coincident or collinear points or vertices
- *                     fail it: the previous R is kept, only t is updated by the line above, and kept_rotation counts the event.
- *                     Every output stays finite for finite input.
+ *                       l1 - l2 > 1e-5 sqrt(sum w |x|^2) sqrt(sum w |p|^2)
+ *                     in float32 (the centred sums of 4.; a NaN compares false).  The right-hand side is the product of the two
+ *                     roots, never the root of the product: every intermediate of the iteration is then of degree 2 at most
+ *                     in the lengths, and the test holds wherever the sums themselves are normal float32 numbers.  Coincident or
+ *                     collinear points or vertices fail it: the previous R is kept, only t is updated by the line above, and
+ *                     kept_rotation counts the event.
+ *                     Every output stays finite for finite input whose d^2 and unweighted sums of d^2 stay below float32's
+ *                     largest number: a set of unit extent times up to about 2^60.  Beyond that d^2 is +inf: no match, a +inf
+ *                     cost.  While, besides, the smallest d^2 that is not 0 stays a normal number (a unit extent times 2^-16
+ *                     or more where correspondences are exact and d^2 is rounding alone), a call on inputs times 2^k gives R,
+ *                     best, kept_rotation and the matches of the unscaled call, t times 2^k, scores and history times 2^2k,
+ *                     bit for bit; far below, every d^2 is 0, every match is index 0 and no rotation is determined.
+ *   place          a transform is about the origin, not about the centroid: t = c_P - R c_X is rounded at the size of the largest
+ *                  coordinate, so z is accurate to about one ulp of that coordinate, however small the mesh.  A scan that lies far
+ *                  from the origin should be re-centred first (the 3-D fitter's mesh loader does).
  *   cost, score    w_point / S sum_s d^2 + w_vert / V sum_v d^2 of a pair of scans, by the sums of 4.  `history` holds the cost
  *                  before every solve and after the last; `scores` is the cost under the final transform: one more pair of
  *                  scans after the last solve.  A skipped direction adds nothing.
@@ -904,6 +915,8 @@ int smalfit_rigid_align(smalfit_rigid_aligner* aligner, void* stream, const smal
  * above.
  *   key            of query q: the pair (bits of its d^2 read as uint32, q).  d^2 is fma(dz, dz, fma(dy, dy, dx dx)) >= 0, so its
  *                  bits order as the value does.  A query without a match (non-finite input) has no key and is never kept.
+ *                  A mesh with a non-finite coordinate has non-finite means, no query of it has a key, nothing is kept and every cost
+ *                  of it is 0, not +inf as in smalfit_rigid_align: its score, its best and its transforms mean nothing.
  *   kept           the `keep` queries of the lowest keys, compared lexicographically: the lowest d^2, the lowest query index among
  *                  bit-equal d^2.  keep_vert in 1..V counts vertices, keep_point in 1..S points: integers, no float rounding
  *                  decides a count.  keep == the count: the direction is untrimmed.  Fewer keys than keep: all of them are kept.

@@ -12,7 +12,7 @@ namespace smalfit {
 //   [0] 1   [1..3] x   [4..6] p   [7..15] x_a p_b (row a)   [16] |x|^2   [17] |p|^2   [18] d^2
 constexpr int kRigidMoments = 19;
 constexpr int kRigidSweeps = 8;           // cyclic Jacobi sweeps of the 4x4 solve, 6 rotations each
-constexpr float kRigidRankEps = 1e-5f;    // the rank test: l1 - l2 > kRigidRankEps sqrt(sum w |x|^2 sum w |p|^2)
+constexpr float kRigidRankEps = 1e-5f;    // the rank test: l1 - l2 > kRigidRankEps sqrt(sum w |x|^2) sqrt(sum w |p|^2)
 constexpr int kRigidCubeRotations = 24;
 
 // z = R x + t, T = three rows [R_i0 R_i1 R_i2 t_i]: one chain per coordinate
@@ -117,7 +117,7 @@ SMALFIT_HD void rigid_quat_rotation(const float q[4], float R[9]) {
 
 // The weighted least-squares rigid fit of the combined sums M (Horn 1987): -> T = [R | t]; returns 1 when the rank test failed and
 // the rotation of `prev` was kept (t is updated either way), 0 otherwise.  gap / scale (either may be null) receive l1 - l2 and
-// sqrt(sum w |x|^2 sum w |p|^2), the two sides of the test
+// sqrt(sum w |x|^2) sqrt(sum w |p|^2), the two sides of the test
 SMALFIT_HD int rigid_solve(const float M[kRigidMoments], const float cX[3], const float cP[3], const float prev[12], float T[12],
                            float* gap = nullptr, float* scale = nullptr) {
   const float W = M[0];
@@ -172,7 +172,9 @@ SMALFIT_HD int rigid_solve(const float M[kRigidMoments], const float cX[3], cons
 #pragma unroll
   for (int r = 0; r < 4; ++r) q[r] = i1 == 0 ? E[r][0] : i1 == 1 ? E[r][1] : i1 == 2 ? E[r][2] : E[r][3];
   const float n2 = fmaf(q[3], q[3], fmaf(q[2], q[2], fmaf(q[1], q[1], q[0] * q[0])));
-  const float sc = sqrtf(M[16] * M[17]);
+  // (a root of each sum, not of their product: the product is of degree 4 in the lengths and would leave float32's range long
+  // before any other intermediate of the solve, all of degree 2 at most, does)
+  const float sc = sqrtf(M[16]) * sqrtf(M[17]);
   const float gp = l1 - l2;
   if (gap != nullptr) *gap = gp;
   if (scale != nullptr) *scale = sc;

@@ -634,22 +634,34 @@ def _rotation_exp(r):
 
 def _rotation_log(R):
     """(3,3) -> axis-angle (3,) in float64, angle in [0, pi].  R is first projected onto the rotations (a float32 matrix is not
-    exactly orthonormal); near pi the axis comes from the symmetric part, where the skew part vanishes"""
+    exactly orthonormal).  Up to a quarter turn the axis is the skew part's; beyond it, where the skew part fades towards pi, it
+    comes from the unit quaternion, solved for its largest component first (Shepperd 1978): no entry is divided by a small one,
+    so a float64 rotation comes back to float64 accuracy at every angle, pi included"""
     U, _, Vt = np.linalg.svd(np.asarray(R, np.float64))
     R = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0]) @ Vt
     w = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     s, c = float(np.linalg.norm(w)), 0.5 * (float(np.trace(R)) - 1.0)
-    th = float(np.arctan2(s, c))
-    if s > 1e-6:
-        return w * (th / s)
-    if c > 0:
+    if c >= 0:
+        if s > 1e-6:
+            return w * (float(np.arctan2(s, c)) / s)
         return w                                   # angle ~ 0: theta / sin(theta) -> 1
-    B = 0.5 * (R + np.eye(3))                      # angle ~ pi: R = 2 a a^T - I up to O(pi - theta)
-    i = int(np.argmax(np.diag(B)))
-    a = B[:, i] / np.sqrt(B[i, i])
-    if float(a @ w) < 0:
-        a = -a
-    return a * th
+    q = _rotation_quaternion(R)
+    if q[0] < 0:
+        q = -q                                     # angle in [0, pi]; at pi itself (q[0] = 0) either axis is the rotation's
+    n = float(np.linalg.norm(q[1:]))
+    return q[1:] * (2.0 * float(np.arctan2(n, q[0])) / n)
+
+
+def _rotation_quaternion(R):
+    """the unit quaternion (w, x, y, z) of a rotation matrix, either sign: the component of largest square is taken from the
+    diagonal, the other three from the off-diagonal sums and differences divided by it (it is at least 1/2)"""
+    d = np.array([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2], R[2, 2] - R[0, 0] - R[1, 1]])
+    i = int(np.argmax(d))
+    h = 0.5 * np.sqrt(1.0 + d[i])
+    off = {(0, 1): R[2, 1] - R[1, 2], (0, 2): R[0, 2] - R[2, 0], (0, 3): R[1, 0] - R[0, 1],
+           (1, 2): R[0, 1] + R[1, 0], (1, 3): R[0, 2] + R[2, 0], (2, 3): R[1, 2] + R[2, 1]}
+    q = np.array([h if j == i else off[(min(i, j), max(i, j))] / (4.0 * h) for j in range(4)])
+    return q / np.linalg.norm(q)
 
 
 def rigid_prealign(fitter, target_meshes, starts=None, iterations=30, num_points=N_SAMPLE_POINTS, seed=0, w_point=1.0, w_vert=1.0,

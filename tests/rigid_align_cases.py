@@ -6,7 +6,7 @@ import itertools
 
 import numpy as np
 
-RANK_EPS = 1e-5           # the header's rank test: l1 - l2 > 1e-5 sqrt(sum w |x|^2 sum w |p|^2)
+RANK_EPS = 1e-5           # the header's rank test: l1 - l2 > 1e-5 sqrt(sum w |x|^2) sqrt(sum w |p|^2)
 RECOVERY_ITERATIONS = 30
 RECOVERY_ADMISSION = 1e-6   # rad: a recovery case counts only if this restatement alone recovers R* this well
 
