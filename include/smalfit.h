@@ -987,8 +987,39 @@ int smalfit_trimmed_rigid_align(smalfit_rigid_aligner* aligner, void* stream, co
  * One extra launch between the betas assembly and Adam, no atomics, one thread per output element; nothing synchronises.  A
  * refused block launches nothing and leaves every output alone.  The handle owns the device clip tables; it is built for one N
  * and one list of lengths, and may be used with any engine and objective.
- * Not here: a temporal term on posed vertices, second-order (acceleration) terms, sharing deform_verts (it is added after
- * posing), propagating a fitted frame to the next as its start, clips that are not contiguous in the batch, sequences sharded
+ * VERTEX TERMS  (velocity and acceleration on the posed vertices; the vertex block and the two vertex entry points below).  The
+ * terms above tie PARAMETERS: in axis-angle two poses a full turn apart look far apart, a change near the root of the kinematic
+ * tree looks as small as one at a paw, standing still is the only motion that costs nothing, and deform_verts is not tied at all.
+ * These tie the SURFACE.  x[n][v][k] is the float32 array (N, V, 3) the mesh objective composes -- LBS output + trans +
+ * deform_verts; in a step args->verts_out when given, else the objective's own buffer.  Clips are the handle's.
+ *   velocity       for every pair (n, n+1) inside one clip d = x[n+1] - x[n]; S_vel is the sum of d d over pairs, vertices and
+ *                  coordinates.  No pair spans a clip boundary.
+ *   acceleration   for every triple whose centre n lies strictly inside its clip a[n] = (x[n-1] - x[n]) + (x[n+1] - x[n]); S_acc
+ *                  is the sum of a a.  A clip shorter than 3 adds nothing.
+ *   loss           w (S / L) with L = 3 V as a float: the form of the terms above (a mean over the elements, summed over the pairs
+ *                  and NOT divided by N).  losses (3): velocity, acceleration, velocity + acceleration.
+ *   gradient       c = (2 w) / L per term, formed once on the host.  Element (n, v, k) has
+ *                    D = (x - prev) + (x - next)                  the one-neighbour forms at the ends of a clip
+ *                    A = (a[n-1] - a[n]) + (a[n+1] - a[n])        a = 0 where the mesh is no centre: five frames at most
+ *                    t = fma(c_acc, A, c_vel D)                   an absent part contributes nothing
+ *                  t is ADDED to the vertex gradient behind the objective's and the surface term's contributions, the bits are
+ *                  (objective + surface) + t, and the float32 sum of t over the vertices of mesh n is added to d trans [n].
+ *   destinations   in a step t joins a destination only where that destination feeds a trained parameter: the planar copy the
+ *                  LBS adjoint reads while pose or betas are trained, the interleaved gradient while deform_verts is, d trans
+ *                  while trans is.  The loss is reported either way.
+ *   reductions     no atomics.  One thread owns vertex (n, v) and its three coordinates; mesh n owns the pair (n, n+1), a centre
+ *                  owns its triple.  A block of 256 threads adds its lanes by the butterfly (xor 32 .. 1) and its four waves in
+ *                  wave order; the partials [N][blocks] of S_vel, S_acc and the three columns of d trans are added by one block
+ *                  in ascending mesh, then ascending block order: the same bits every run.
+ *   step_total     optional (1), a step only: ((args->losses[4] + the surface block's weighted term, when that block is on) +
+ *                  losses[3] of the parameter terms) + losses[2] of these.  The sequence block's own step_total keeps its meaning.
+ *   off            both weights <= 0, or no clip long enough for an enabled term (2 for velocity, 3 for acceleration): nothing is
+ *                  launched, `losses` is cleared by a 12-byte fill and the step is the sequence step, launch for launch and bit
+ *                  for bit (the stand-alone call then fills the gradients it was given with zeros).
+ * Two launches between the surface term and the LBS adjoint.  The handle owns the partials, allocated by the first call that needs
+ * them and regrown only when V grows.
+ * Not here: sharing deform_verts (it is added after posing), robust forms of the vertex terms, weights per vertex or per body
+ * part, propagating a fitted frame to the next as its start, clips that are not contiguous in the batch, sequences sharded
  * across GPUs. */
 typedef struct smalfit_scan_sequence smalfit_scan_sequence;
 typedef struct smalfit_sequence_args {
@@ -1016,6 +1047,25 @@ int smalfit_scan_sequence_step(smalfit_scan_sequence* sequence, smalfit_engine* 
                                const smalfit_surface_term_args* surface, const smalfit_surface_gate_args* surface_gate,
                                const smalfit_chamfer_gate_args* chamfer_gate, const smalfit_robust_args* robust,
                                const smalfit_sequence_args* sequence_args);
+
+typedef struct smalfit_sequence_vertex_args {
+  float w_temp_vert_vel;         /* weight of the velocity term on the posed vertices; <= 0: skipped; must be finite */
+  float w_temp_vert_acc;         /* ... of the acceleration term */
+  float* losses;                 /* (3, device): velocity, acceleration, their sum */
+  float* step_total;             /* optional (1, device), a step only */
+} smalfit_sequence_vertex_args;
+/* the vertex terms alone at the caller's vertices of the handle's N meshes (the unfused path).  verts (N,num_verts,3) is read;
+ * dverts (N,num_verts,3) and dtrans (N,3) are WRITTEN (t and its sum over a mesh's vertices), either may be NULL.  step_total must
+ * be NULL. */
+int smalfit_scan_sequence_vertex_term(smalfit_scan_sequence* sequence, void* stream, const smalfit_sequence_vertex_args* args,
+                                      int num_verts, const float* verts, float* dverts, float* dtrans);
+/* smalfit_scan_sequence_step with the vertex block behind the sequence block; both are required (a sequence block with share_shape
+ * 0 and every weight 0 couples nothing). */
+int smalfit_scan_sequence_vertex_step(smalfit_scan_sequence* sequence, smalfit_engine* engine, smalfit_mesh_objective* objective,
+                                      smalfit_mesh_targets* targets, void* stream, const smalfit_fit3d_args* args,
+                                      const smalfit_surface_term_args* surface, const smalfit_surface_gate_args* surface_gate,
+                                      const smalfit_chamfer_gate_args* chamfer_gate, const smalfit_robust_args* robust,
+                                      const smalfit_sequence_args* sequence_args, const smalfit_sequence_vertex_args* vertex_args);
 
 /* ---- torch.optim.Adam.step -----------------------------------------------------------------------
  * replaces: torch.optim.Adam(lr, betas=(0.5, 0.999)).step()  reference smal_fitter/optimize_to_joints.py:96,137

@@ -202,6 +202,12 @@ class SequenceArgs(C.Structure):
                 ("losses", C.c_void_p), ("step_total", C.c_void_p)]
 
 
+class SequenceVertexArgs(C.Structure):
+    """smalfit_sequence_vertex_args: the velocity and acceleration terms on the posed vertices of a scan sequence
+    (smalfit_scan_sequence_vertex_term, smalfit_scan_sequence_vertex_step); both weights 0 = off"""
+    _fields_ = [("w_temp_vert_vel", C.c_float), ("w_temp_vert_acc", C.c_float), ("losses", C.c_void_p), ("step_total", C.c_void_p)]
+
+
 class LbsArgs(C.Structure):
     _fields_ = [("num_frames", C.c_int), ("num_betas", C.c_int)] + [(n, C.c_void_p) for n in (
         "beta", "theta", "Rs", "logscale", "v_offset", "verts", "joints", "Rs_out", "v_shaped", "dverts", "djoints",
@@ -330,6 +336,10 @@ SIGNATURES = {
     "smalfit_scan_sequence_couple": (_I, [_VP, _VP, C.POINTER(SequenceArgs), _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "smalfit_scan_sequence_step": (_I, [_VP, _VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs), C.POINTER(SurfaceGateArgs),
                                         C.POINTER(ChamferGateArgs), C.POINTER(RobustArgs), C.POINTER(SequenceArgs)]),
+    "smalfit_scan_sequence_vertex_term": (_I, [_VP, _VP, C.POINTER(SequenceVertexArgs), _I, _VP, _VP, _VP]),
+    "smalfit_scan_sequence_vertex_step": (_I, [_VP, _VP, _VP, _VP, _VP, C.POINTER(Fit3dArgs), C.POINTER(SurfaceTermArgs),
+                                               C.POINTER(SurfaceGateArgs), C.POINTER(ChamferGateArgs), C.POINTER(RobustArgs),
+                                               C.POINTER(SequenceArgs), C.POINTER(SequenceVertexArgs)]),
 }
 
 # Entry points added without a new ABI version (no struct of version 6 changed its layout): a library of the same version
@@ -341,7 +351,8 @@ LAZY_SYMBOLS = frozenset(["smalfit_fit_eval_windows", "smalfit_fit_metrics", "sm
                           "smalfit_mesh_surface_eval_robust", "smalfit_fit3d_step_robust", "smalfit_mesh_targets_build_index",
                           "smalfit_mesh_targets_index_stats", "smalfit_rigid_aligner_create", "smalfit_rigid_aligner_destroy",
                           "smalfit_rigid_align", "smalfit_trimmed_rigid_align", "smalfit_scan_sequence_create",
-                          "smalfit_scan_sequence_destroy", "smalfit_scan_sequence_couple", "smalfit_scan_sequence_step"])
+                          "smalfit_scan_sequence_destroy", "smalfit_scan_sequence_couple", "smalfit_scan_sequence_step",
+                          "smalfit_scan_sequence_vertex_term", "smalfit_scan_sequence_vertex_step"])
 
 
 class SmalfitError(RuntimeError):

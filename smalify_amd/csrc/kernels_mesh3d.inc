@@ -1085,6 +1085,10 @@ struct Fit3dSequenceArgs {
   const float* base_total;     // the step's weighted total, or null
   const float* surface_total;  // the surface term's, or null
   float* step_total;           // [1] or null
+  // a step with the vertex terms on (smalfit_scan_sequence_vertex_step), else both null: their sum, which
+  // fit3d_sequence_vertex_finish_kernel has written, and where the vertex block's step_total goes
+  const float* vertex_total;
+  float* vertex_step_total;
 };
 
 // S of one term: lane l takes the elements l, l + 256, ... in ascending order, then the block's fixed-order sum
@@ -1117,6 +1121,11 @@ __global__ __launch_bounds__(kSeqBlock) void fit3d_sequence_kernel(Fit3dSequence
         float base = a.base_total[0];
         if (a.surface_total != nullptr) base += a.surface_total[0];
         a.step_total[0] = base + tot;
+      }
+      if (a.vertex_step_total != nullptr) {
+        float base = a.base_total[0];
+        if (a.surface_total != nullptr) base += a.surface_total[0];
+        a.vertex_step_total[0] = vertex_step_total(base, tot, a.vertex_total[0]);
       }
     }
     return;
@@ -1152,6 +1161,118 @@ __global__ __launch_bounds__(kSeqBlock) void fit3d_sequence_kernel(Fit3dSequence
   }
   const float prev = has_prev ? x[-L] : 0.f, next = has_next ? x[L] : 0.f;
   *g = temporal_grad(*g, c, *x, prev, next, has_prev, has_next);
+}
+
+// ---- the temporal terms on posed vertices: velocity and acceleration --------------------------------------------------------
+// Two launches between the surface term and the LBS adjoint (include/smalfit.h, "scan sequences", the vertex terms; the arithmetic
+// is fit3d_sequence_vertex_math.h, the grid sequence_vertex_grid of smalfit_plan.h).  No atomics.  Thread (n, v) owns vertex v of
+// mesh n and its three coordinates: it reads x of up to five meshes of its clip (N V 3 floats are 1.5 MB at 32 meshes: the
+// neighbours' reads hit L2), forms t and adds it where the gradient is read from; mesh n owns the velocity pair (n, n + 1), a
+// centre owns its acceleration triple.  block_sum leaves the block's five partials; the one-block finish kernel adds them in a
+// fixed order.
+struct Fit3dSequenceVertexArgs {
+  int N, V, Vp, blocks;     // blocks: of one mesh's row
+  const int* mesh_start;    // [N] first mesh of the clip of mesh n
+  const int* mesh_len;      // [N] length of that clip
+  const float* verts;       // [N][V][3]
+  bool vel, acc;            // the term is evaluated
+  float w_vel, w_acc;
+  float c_vel, c_acc;       // temporal_grad_scale; 0 for a term that is not evaluated
+  float* acc_dverts;        // [N][V][3] or null: t is added to it ...
+  float* acc_planar;        // [N][3][Vp] or null: ... and to the planar copy for the LBS adjoint (padding stays untouched)
+  float* dverts;            // [N][V][3] or null: t is written (the stand-alone call)
+  float* parts;             // [kSeqVertexSums][N][blocks]: S_vel, S_acc, the three columns of d trans
+  // the finish kernel only
+  float* acc_dtrans;        // [N][3] or null: the sum of t over a mesh is added to it
+  float* dtrans;            // [N][3] or null: ... is written
+  float* losses;            // [3]
+  const float* base_total;     // the step's weighted total, or null
+  const float* surface_total;  // the surface term's, or null
+  float* step_total;           // [1] or null: formed here when fit3d_sequence_kernel does not run behind this
+};
+
+__global__ __launch_bounds__(kSeqVertexBlock) void fit3d_sequence_vertex_kernel(Fit3dSequenceVertexArgs a) {
+  __shared__ float red[16];
+  const int n = blockIdx.y;
+  const int v = blockIdx.x * kSeqVertexBlock + (int)threadIdx.x;
+  const bool active = v < a.V;
+  const SeqVertexPlace p = sequence_vertex_place(n, a.mesh_start[n], a.mesh_len[n]);
+  const size_t stride = (size_t)a.V * 3;
+  const size_t o = ((size_t)n * a.V + (active ? v : 0)) * 3;
+  float t[3] = {0.f, 0.f, 0.f};
+  float sv = 0.f, sa = 0.f;
+  if (active) {
+    const float* x0 = a.verts + o;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float x = x0[k];
+      // (a frame is read only where the clip holds it; with only the velocity term on, only the two nearest)
+      const float xm1 = p.has_m1 ? x0[k - (ptrdiff_t)stride] : 0.f;
+      const float xp1 = p.has_p1 ? x0[k + stride] : 0.f;
+      float D = 0.f, A = 0.f;
+      if (a.vel) {
+        D = vertex_vel_stencil(x, xm1, xp1, p.has_m1, p.has_p1);
+        if (p.has_p1) sv = temporal_pair_sq(sv, x, xp1);
+      }
+      if (a.acc) {
+        const float xm2 = p.has_m2 ? x0[k - 2 * (ptrdiff_t)stride] : 0.f;
+        const float xp2 = p.has_p2 ? x0[k + 2 * stride] : 0.f;
+        A = vertex_acc_stencil5(p, xm2, xm1, x, xp1, xp2);
+        if (p.centre_0) sa = vertex_accel_sq(sa, vertex_accel(xm1, x, xp1));
+      }
+      t[k] = vertex_term_grad(a.c_acc, A, a.c_vel, D);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (a.acc_dverts != nullptr) a.acc_dverts[o + k] += t[k];     // (this thread alone writes the vertex)
+      if (a.acc_planar != nullptr) a.acc_planar[((size_t)n * 3 + k) * a.Vp + v] += t[k];
+      if (a.dverts != nullptr) a.dverts[o + k] = t[k];
+    }
+  }
+  const float sums[kSeqVertexSums] = {block_sum(sv, red), block_sum(sa, red), block_sum(t[0], red), block_sum(t[1], red),
+                                      block_sum(t[2], red)};
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < kSeqVertexSums; ++q) a.parts[((size_t)q * a.N + n) * a.blocks + blockIdx.x] = sums[q];
+  }
+}
+
+// sum q of the partials: ascending mesh order, then ascending block order (one mesh only for the columns of d trans)
+__device__ __forceinline__ float sequence_vertex_partial_sum(const Fit3dSequenceVertexArgs& a, int q, int n0, int n1) {
+  const float* part = a.parts + (size_t)q * a.N * a.blocks;
+  float s = 0.f;
+  for (int i = n0 * a.blocks; i < n1 * a.blocks; ++i) s += part[i];
+  return s;
+}
+
+// one block: lane 0 of wave 0 adds S_vel, lane 0 of wave 1 S_acc, the threads of waves 2 and 3 take the elements of d trans
+__global__ __launch_bounds__(kSeqVertexBlock) void fit3d_sequence_vertex_finish_kernel(Fit3dSequenceVertexArgs a) {
+  __shared__ float S[2];
+  const int tid = (int)threadIdx.x;
+  if (tid == 0) S[0] = a.vel ? sequence_vertex_partial_sum(a, 0, 0, a.N) : 0.f;
+  if (tid == 64) S[1] = a.acc ? sequence_vertex_partial_sum(a, 1, 0, a.N) : 0.f;
+  if (tid >= 128 && (a.dtrans != nullptr || a.acc_dtrans != nullptr)) {
+    for (int e = tid - 128; e < 3 * a.N; e += kSeqVertexBlock - 128) {
+      const int n = e / 3, k = e - 3 * n;
+      const float s = sequence_vertex_partial_sum(a, 2 + k, n, n + 1);
+      if (a.dtrans != nullptr) a.dtrans[e] = s;
+      if (a.acc_dtrans != nullptr) a.acc_dtrans[e] += s;
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const int L = sequence_vertex_len(a.V);
+  const float lv = a.vel ? temporal_loss(a.w_vel, S[0], L) : 0.f;
+  const float la = a.acc ? temporal_loss(a.w_acc, S[1], L) : 0.f;
+  const float tot = vertex_term_total(lv, la);
+  a.losses[0] = lv;
+  a.losses[1] = la;
+  a.losses[2] = tot;
+  if (a.step_total != nullptr) {
+    float base = a.base_total[0];
+    if (a.surface_total != nullptr) base += a.surface_total[0];
+    a.step_total[0] = vertex_step_total(base, 0.f, tot);       // (the parameter terms are off: their sum reads 0)
+  }
 }
 
 // ---- Adam on all trained parameters of a Stage.step in one launch ----------------------------------------------------

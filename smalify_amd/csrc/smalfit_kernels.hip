@@ -40,6 +40,7 @@
 #include "mesh3d_math.h"
 #include "mesh3d_grid.h"
 #include "fit3d_sequence_math.h"
+#include "fit3d_sequence_vertex_math.h"
 #include "rigid_align_math.h"
 #include "smalfit_plan.h"
 

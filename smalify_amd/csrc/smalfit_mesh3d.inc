@@ -260,11 +260,11 @@ static int launch_mesh_sampler(const smalfit_mesh_targets* t, hipStream_t st, in
   return 0;
 }
 
-// the body of every smalfit_fit3d_step*, defined behind them with the scan-sequence block it optionally takes
+// the body of every smalfit_fit3d_step*, defined behind them with the scan-sequence blocks it optionally takes
 static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
                           const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
-                          const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb, const smalfit_scan_sequence* seq,
-                          const smalfit_sequence_args* q);
+                          const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb, smalfit_scan_sequence* seq,
+                          const smalfit_sequence_args* q, const smalfit_sequence_vertex_args* vq = nullptr);
 
 extern "C" {
 
@@ -650,6 +650,10 @@ struct smalfit_scan_sequence {
   int N = 0, G = 0, lengths_sum = 0;
   bool any_long = false;       // some clip is longer than 1
   int* tables = nullptr;       // one device allocation: clip_start [G], clip_len [G], mesh_start [N], mesh_len [N]
+  // the vertex terms only: the longest clip, the per-block partials (sequence_vertex_partials floats for the largest V seen)
+  int longest = 0;
+  float* vertex_parts = nullptr;
+  size_t vertex_parts_count = 0;
 };
 
 // what fit3d_sequence_kernel is given beside the block: the parameters it reads, the gradients it updates (null: not formed), the
@@ -660,6 +664,8 @@ struct SequenceRun {
   float *g_betas = nullptr, *g_theta = nullptr, *g_trans = nullptr;
   bool add_global = false, add_joint = false;       // which column blocks of g_theta
   const float *base_total = nullptr, *surface_total = nullptr;
+  const float* vertex_total = nullptr;      // a step with the vertex terms on: their sum and where their step_total goes
+  float* vertex_step_total = nullptr;
 };
 static int launch_sequence(const smalfit_scan_sequence* s, hipStream_t st, const smalfit_sequence_args* q, const SequencePlan& p,
                            const SequenceRun& r) {
@@ -679,17 +685,60 @@ static int launch_sequence(const smalfit_scan_sequence* s, hipStream_t st, const
   k.c_trans = temporal_grad_scale(q->w_temp_trans, kSeqTransLen);
   k.losses = q->losses;
   k.base_total = r.base_total; k.surface_total = r.surface_total; k.step_total = r.base_total ? q->step_total : nullptr;
+  k.vertex_total = r.vertex_total; k.vertex_step_total = r.base_total && r.vertex_total ? r.vertex_step_total : nullptr;
   fit3d_sequence_kernel<<<sequence_blocks(p, s->N, s->G, r.num_betas), kSeqBlock, 0, st>>>(k);
   LAUNCH_OK("fit3d_sequence_kernel");
   return 0;
 }
 
-// the body of every smalfit_fit3d_step* and of smalfit_scan_sequence_step.  seq == nullptr (the five entry points of before): what
-// they launched and the bits they wrote
+// what the two vertex kernels are given beside the block: the vertices, where t is added or written (null: not formed), the totals
+// step_total is formed from
+struct SequenceVertexRun {
+  int num_verts = 0, Vp = 0;
+  const float* verts = nullptr;
+  float *acc_dverts = nullptr, *acc_planar = nullptr, *acc_dtrans = nullptr;    // a step: added to
+  float *dverts = nullptr, *dtrans = nullptr;                                   // the stand-alone call: written
+  const float *base_total = nullptr, *surface_total = nullptr;
+  float* step_total = nullptr;      // formed by the finish kernel: only when fit3d_sequence_kernel does not run behind it
+};
+static int launch_sequence_vertex(smalfit_scan_sequence* s, hipStream_t st, const smalfit_sequence_vertex_args* q,
+                                  const SequenceVertexPlan& p, const SequenceVertexRun& r) {
+  const int V = r.num_verts;
+  const size_t need = sequence_vertex_partials(V, s->N);
+  if (need > s->vertex_parts_count) {       // the first call for this V, or V grew
+    if (s->vertex_parts) (void)hipFree(s->vertex_parts);
+    s->vertex_parts = nullptr; s->vertex_parts_count = 0;
+    HIP_OK(hipMalloc((void**)&s->vertex_parts, need * sizeof(float)));
+    s->vertex_parts_count = need;
+  }
+  const Grid2 g = sequence_vertex_grid(V, s->N);
+  const int L = sequence_vertex_len(V);
+  Fit3dSequenceVertexArgs k{};
+  k.N = s->N; k.V = V; k.Vp = r.Vp; k.blocks = g.x;
+  k.mesh_start = s->tables + 2 * s->G; k.mesh_len = s->tables + 2 * s->G + s->N;
+  k.verts = r.verts;
+  k.vel = p.vel; k.acc = p.acc;
+  k.w_vel = q->w_temp_vert_vel; k.w_acc = q->w_temp_vert_acc;
+  k.c_vel = p.vel ? temporal_grad_scale(q->w_temp_vert_vel, L) : 0.f;
+  k.c_acc = p.acc ? temporal_grad_scale(q->w_temp_vert_acc, L) : 0.f;
+  k.acc_dverts = r.acc_dverts; k.acc_planar = r.acc_planar; k.dverts = r.dverts;
+  k.parts = s->vertex_parts;
+  k.acc_dtrans = r.acc_dtrans; k.dtrans = r.dtrans;
+  k.losses = q->losses;
+  k.base_total = r.base_total; k.surface_total = r.surface_total; k.step_total = r.base_total ? r.step_total : nullptr;
+  fit3d_sequence_vertex_kernel<<<dim3(g.x, g.y), kSeqVertexBlock, 0, st>>>(k);
+  LAUNCH_OK("fit3d_sequence_vertex_kernel");
+  fit3d_sequence_vertex_finish_kernel<<<1, kSeqVertexBlock, 0, st>>>(k);
+  LAUNCH_OK("fit3d_sequence_vertex_finish_kernel");
+  return 0;
+}
+
+// the body of every smalfit_fit3d_step*, of smalfit_scan_sequence_step and of smalfit_scan_sequence_vertex_step.  seq == nullptr
+// (the five entry points of before): what they launched and the bits they wrote; vq == nullptr: likewise the sequence step's
 static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t, void* stream,
                           const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf, const smalfit_surface_gate_args* gate,
-                          const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb, const smalfit_scan_sequence* seq,
-                          const smalfit_sequence_args* q) {
+                          const smalfit_chamfer_gate_args* cg, const smalfit_robust_args* rb, smalfit_scan_sequence* seq,
+                          const smalfit_sequence_args* q, const smalfit_sequence_vertex_args* vq) {
   if (refused(who, null_argument_refusal(e && m && a))) return 1;
   const ModelDev& md = e->model->dev;
   if (refused(who, fit3d_args_refusal(a, Fit3dFacts{e->maxM, md.V, md.NBall, m->max_meshes, m->max_points, m->t.V,
@@ -706,9 +755,21 @@ static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objec
                                                              surface && sf->w_vert_surface > 0.f})))
     return 1;
   if (seq && refused(who, sequence_args_refusal(q, SequenceFacts{seq->N, seq->lengths_sum, a->num_meshes, true, true, true, true}))) return 1;
+  if (vq && refused(who, sequence_vertex_args_refusal(vq, SequenceVertexFacts{true, md.V, true, seq->N, a->num_meshes}))) return 1;
   const Fit3dPlan plan = plan_fit3d(a, md.V, surface && sf->w_point_surface > 0.f);
   const int N = a->num_meshes, nb = a->num_betas, S = a->num_points;
   hipStream_t st = (hipStream_t)stream;
+  // the vertex block: with its terms off nothing of it is launched, its losses read 0 and its step_total is the sequence step's
+  // (formed where the sequence block's is: through a copy of that block when the caller asked it for none)
+  const SequenceVertexPlan vp = vq ? plan_sequence_vertex(vq, seq->longest) : SequenceVertexPlan{};
+  const bool vertex_off = vq && !vp.launch;
+  const smalfit_sequence_args* q_given = q;
+  smalfit_sequence_args q_total;
+  if (vertex_off && vq->step_total && !q->step_total) {
+    q_total = *q;
+    q_total.step_total = vq->step_total;
+    q = &q_total;
+  }
   // the sequence block: a block that couples nothing launches nothing, its losses read 0 and its step_total is the step's own
   // total (formed by the surface term where that is on: through a copy of its block when the caller asked it for none)
   const SequencePlan sq = seq ? plan_sequence(q, seq->any_long, plan.need_beta) : SequencePlan{};
@@ -718,7 +779,7 @@ static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objec
     sf_total.step_total = q->step_total;
     sf = &sf_total;
   }
-  auto couple = [&]() -> int {
+  auto couple_parameters = [&]() -> int {
     if (!seq) return 0;
     if (!sq.launch) {
       HIP_OK(hipMemsetAsync(q->losses, 0, 4 * sizeof(float), st));
@@ -736,7 +797,16 @@ static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objec
     r.g_trans = a->lr_trans > 0.f ? m->dtrans : nullptr;
     r.base_total = a->losses + 4;
     r.surface_total = surface ? sf->losses + 2 : nullptr;
+    // (the vertex terms ran before the LBS adjoint: this launch forms their step_total, as the last to know a term)
+    if (vp.launch) { r.vertex_total = vq->losses + 2; r.vertex_step_total = vq->step_total; }
     return launch_sequence(seq, st, q, sq, r);
+  };
+  auto couple = [&]() -> int {
+    if (couple_parameters()) return 1;
+    // the vertex block's terms are off and the caller asked both blocks for a total: the sequence block's, copied
+    if (vertex_off && vq->step_total && q_given->step_total && vq->step_total != q_given->step_total)
+      HIP_OK(hipMemcpyAsync(vq->step_total, q_given->step_total, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
   };
 
   // SMAL3DFitter.forward: LBS on [global_rot | joint_rot] (theta is built inside the head kernel), untranslated
@@ -783,7 +853,22 @@ static int fit3d_step_run(const char* who, smalfit_engine* e, smalfit_mesh_objec
   }
   // (a step without the term skips both of its directions: their weight sums read 0)
   if (!surface && rb && rb->surface_weight_sums) HIP_OK(hipMemsetAsync(rb->surface_weight_sums, 0, (size_t)N * 2 * sizeof(float), st));
-  if (!plan.any_trained) return couple();   // (nothing is trained: the block only reports its losses)
+  // the temporal terms on the vertices the objective composed, behind the surface term's contribution; t joins a destination
+  // only where that destination feeds a trained parameter
+  if (vertex_off) HIP_OK(hipMemsetAsync(vq->losses, 0, 3 * sizeof(float), st));
+  if (vp.launch) {
+    SequenceVertexRun vr;
+    vr.num_verts = md.V; vr.Vp = md.Vp;
+    vr.verts = a->verts_out ? a->verts_out : m->verts;
+    vr.acc_planar = ob.dverts_planar;
+    vr.acc_dverts = a->lr_deform_verts > 0.f ? m->dverts : nullptr;
+    vr.acc_dtrans = a->lr_trans > 0.f ? m->dtrans : nullptr;
+    vr.base_total = a->losses + 4;
+    vr.surface_total = surface ? sf->losses + 2 : nullptr;
+    vr.step_total = sq.launch ? nullptr : vq->step_total;
+    if (launch_sequence_vertex(seq, st, vq, vp, vr)) return 1;
+  }
+  if (!plan.any_trained) return couple();   // (nothing is trained: the blocks only report their losses)
 
   // back through the LBS (forward state is still in the engine)
   if (plan.need_pose || plan.need_beta) {
@@ -835,6 +920,7 @@ int smalfit_scan_sequence_create(int num_meshes, int num_clips, const int* clip_
       host[2 * num_clips + num_meshes + n] = len;
     }
     s->any_long = s->any_long || len > 1;
+    s->longest = len > s->longest ? len : s->longest;
     start += len;
   }
   s->lengths_sum = start;
@@ -854,6 +940,7 @@ int smalfit_scan_sequence_create(int num_meshes, int num_clips, const int* clip_
 void smalfit_scan_sequence_destroy(smalfit_scan_sequence* s) {
   if (!s) return;
   if (s->tables) (void)hipFree(s->tables);
+  if (s->vertex_parts) (void)hipFree(s->vertex_parts);
   delete s;
 }
 
@@ -887,6 +974,36 @@ int smalfit_scan_sequence_step(smalfit_scan_sequence* s, smalfit_engine* e, smal
   const char* who = "smalfit_scan_sequence_step";
   if (refused(who, null_argument_refusal(s && q))) return 1;
   return fit3d_step_run(who, e, m, t, stream, a, sf, gate, cg, rb, s, q);
+}
+
+int smalfit_scan_sequence_vertex_term(smalfit_scan_sequence* s, void* stream, const smalfit_sequence_vertex_args* q, int num_verts,
+                                      const float* verts, float* dverts, float* dtrans) {
+  const char* who = "smalfit_scan_sequence_vertex_term";
+  if (refused(who, null_argument_refusal(s != nullptr))) return 1;
+  if (refused(who, sequence_vertex_args_refusal(q, SequenceVertexFacts{false, num_verts, verts != nullptr, s->N, s->N}))) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  const SequenceVertexPlan p = plan_sequence_vertex(q, s->longest);
+  if (!p.launch) {     // nothing is launched: the losses and the gradients the caller gave read 0
+    HIP_OK(hipMemsetAsync(q->losses, 0, 3 * sizeof(float), st));
+    if (dverts) HIP_OK(hipMemsetAsync(dverts, 0, (size_t)s->N * num_verts * 3 * sizeof(float), st));
+    if (dtrans) HIP_OK(hipMemsetAsync(dtrans, 0, (size_t)s->N * 3 * sizeof(float), st));
+    return 0;
+  }
+  SequenceVertexRun r;
+  r.num_verts = num_verts;
+  r.verts = verts; r.dverts = dverts; r.dtrans = dtrans;
+  return launch_sequence_vertex(s, st, q, p, r);
+}
+
+int smalfit_scan_sequence_vertex_step(smalfit_scan_sequence* s, smalfit_engine* e, smalfit_mesh_objective* m, smalfit_mesh_targets* t,
+                                      void* stream, const smalfit_fit3d_args* a, const smalfit_surface_term_args* sf,
+                                      const smalfit_surface_gate_args* gate, const smalfit_chamfer_gate_args* cg,
+                                      const smalfit_robust_args* rb, const smalfit_sequence_args* q,
+                                      const smalfit_sequence_vertex_args* vq) {
+  const char* who = "smalfit_scan_sequence_vertex_step";
+  if (refused(who, null_argument_refusal(s && q))) return 1;
+  if (!vq && refused(who, sequence_vertex_args_refusal(nullptr, SequenceVertexFacts{}))) return 1;
+  return fit3d_step_run(who, e, m, t, stream, a, sf, gate, cg, rb, s, q, vq);
 }
 
 }  // extern "C"

@@ -953,6 +953,50 @@ inline int sequence_blocks(const SequencePlan& p, int num_meshes, int num_clips,
   return 1 + (elements + kSeqBlock - 1) / kSeqBlock;
 }
 
+// the temporal terms on posed vertices (smalfit_scan_sequence_vertex_term, smalfit_scan_sequence_vertex_step)
+struct SequenceVertexFacts {
+  bool step;                        // the block rides on a step (else smalfit_scan_sequence_vertex_term)
+  int num_verts;                    // V of the call
+  bool verts;                       // the vertices were given (a step composes its own)
+  int handle_meshes, num_meshes;    // the N the handle was built for | the N of this call
+};
+// -> why the vertex entry points refuse the block (the text behind "<entry point>: "), or nullptr; asked after the call's other
+// blocks have been accepted.  The order: the block, losses, the two weights (velocity, acceleration), step_total outside a step,
+// num_verts, verts, the handle's N
+inline const char* sequence_vertex_args_refusal(const smalfit_sequence_vertex_args* q, const SequenceVertexFacts& f) {
+  if (!q) return "the vertex block is NULL";
+  if (!q->losses) return "losses is NULL";
+  if (!std::isfinite(q->w_temp_vert_vel)) return "w_temp_vert_vel is not finite";
+  if (!std::isfinite(q->w_temp_vert_acc)) return "w_temp_vert_acc is not finite";
+  if (!f.step && q->step_total) return "step_total given outside a step";
+  if (f.num_verts < 1) return "num_verts must be positive";
+  if (!f.verts) return "verts is NULL";
+  if (f.handle_meshes != f.num_meshes) return "the sequence handle was built for another num_meshes";
+  return nullptr;
+}
+// what a block that sequence_vertex_args_refusal accepts evaluates.  longest_clip: the length of the handle's longest clip.  A
+// velocity pair needs a clip of 2, an acceleration triple one of 3.  launch: the two kernels run at all -- a block with both weights
+// <= 0, or with no clip long enough for an enabled term, launches nothing and its losses read 0
+struct SequenceVertexPlan {
+  bool launch;
+  bool vel, acc;   // the term is evaluated
+};
+inline SequenceVertexPlan plan_sequence_vertex(const smalfit_sequence_vertex_args* q, int longest_clip) {
+  SequenceVertexPlan p{};
+  if (!q) return p;
+  p.vel = q->w_temp_vert_vel > 0.f && longest_clip >= 2;
+  p.acc = q->w_temp_vert_acc > 0.f && longest_clip >= 3;
+  p.launch = p.vel || p.acc;
+  return p;
+}
+// fit3d_sequence_vertex_kernel: one thread per vertex (n, v), 256 a block, a row of blocks per mesh; every block leaves
+// kSeqVertexSums partials [sum][n][block] (S_vel, S_acc, the three columns of d trans), which the one-block
+// fit3d_sequence_vertex_finish_kernel adds in ascending mesh, then ascending block order
+constexpr int kSeqVertexBlock = 256;
+constexpr int kSeqVertexSums = 5;
+inline Grid2 sequence_vertex_grid(int V, int N) { return Grid2{(V + kSeqVertexBlock - 1) / kSeqVertexBlock, N}; }
+inline size_t sequence_vertex_partials(int V, int N) { return (size_t)kSeqVertexSums * (size_t)N * (size_t)sequence_vertex_grid(V, N).x; }
+
 // ------------------------------------------------------------------------------------------------
 // smalfit_fit_args: which blocks are refused
 // ------------------------------------------------------------------------------------------------

@@ -942,6 +942,25 @@ def temporal_weights(weights=None):
     return out
 
 
+TEMPORAL_VERTEX_KEYS = ("w_temp_vert_vel", "w_temp_vert_acc")
+
+
+def temporal_vertex_weights(weights=None):
+    """the two weights of the temporal terms on the posed vertices of a scan sequence (velocity, acceleration) with both 0 (off),
+    overridden by `weights`; an unknown key raises"""
+    out = dict.fromkeys(TEMPORAL_VERTEX_KEYS, 0.0)
+    for k, v in (weights or {}).items():
+        if k not in out:
+            raise KeyError("unknown temporal vertex weight %r (have %s)" % (k, list(TEMPORAL_VERTEX_KEYS)))
+        out[k] = float(v)
+    return out
+
+
+def temporal_vertex_on(weights):
+    """some weight of temporal_vertex_weights is positive (with none a stage calls what it called without the block)"""
+    return any(weights[k] > 0 for k in TEMPORAL_VERTEX_KEYS)
+
+
 def check_clip_lengths(clip_lengths, num_meshes):
     """-> the lengths as a list of ints; ValueError unless they are positive and sum to num_meshes"""
     lengths = [int(c) for c in clip_lengths]
@@ -953,7 +972,8 @@ def check_clip_lengths(clip_lengths, num_meshes):
 class ScanSequence:
     """The meshes of a batch as clips of one animal each (smalfit_scan_sequence; the definitions are this project's,
     include/smalfit.h): within a clip one shape -- the betas gradient rows of a clip replaced by their sum -- and the 2-D fitter's
-    temporal terms between consecutive poses.  A handle of its own, for one N and one list of lengths."""
+    temporal terms between consecutive poses; and, on the posed vertices, a velocity and an acceleration term (vertex_term).  A
+    handle of its own, for one N and one list of lengths."""
 
     def __init__(self, clip_lengths, num_meshes=None):
         if not torch.cuda.is_available():
@@ -1001,6 +1021,41 @@ class ScanSequence:
         check(self._couple(self.handle, _stream(), C.byref(q), nb, _ptr(global_rot), _ptr(joint_rot), _ptr(trans), _ptr(g_betas),
                            _ptr(g_theta), _ptr(g_trans)), "smalfit_scan_sequence_couple")
         return losses
+
+    def vertex_block(self, temporal_verts=None, losses=None, step_total=None):
+        """-> (smalfit_sequence_vertex_args, its losses tensor (3,)): the block of vertex_term() and of
+        smalfit_scan_sequence_vertex_step"""
+        w = temporal_vertex_weights(temporal_verts)
+        if losses is None:
+            losses = torch.zeros(3, device="cuda")
+        q = _lib.SequenceVertexArgs()
+        q.w_temp_vert_vel, q.w_temp_vert_acc = (w[k] for k in TEMPORAL_VERTEX_KEYS)
+        q.losses = losses.data_ptr()
+        q.step_total = step_total.data_ptr() if step_total is not None else None
+        return q, losses
+
+    def vertex_term(self, verts, temporal_verts=None, want_dverts=True, want_dtrans=True, losses=None, out=None):
+        """the velocity and acceleration terms alone at verts (N,V,3) (smalfit_scan_sequence_vertex_term) -> dict(losses (3,):
+        velocity, acceleration, their sum; dverts (N,V,3) and dtrans (N,3): the terms' gradient and its sum over every mesh's
+        vertices, None where not wanted).  `out`: a dict of an earlier call whose tensors are written again"""
+        N, V = int(verts.shape[0]), int(verts.shape[1])
+        if N != self.num_meshes or verts.dim() != 3 or int(verts.shape[2]) != 3:
+            raise ValueError("verts %r: (%d, V, 3) expected" % (tuple(verts.shape), self.num_meshes))
+        out = {} if out is None else out
+        q, losses = self.vertex_block(temporal_verts, losses if losses is not None else out.get("losses"))
+        dverts = dtrans = None
+        if want_dverts:
+            dverts = out.get("dverts")
+            if dverts is None or dverts.shape != verts.shape:
+                dverts = torch.empty_like(verts, dtype=torch.float32)
+        if want_dtrans:
+            dtrans = out.get("dtrans")
+            if dtrans is None:
+                dtrans = torch.empty(N, 3, device=verts.device)
+        check(_lib.resolve(self.lib, "smalfit_scan_sequence_vertex_term")(
+            self.handle, _stream(), C.byref(q), V, _ptr(verts), _ptr(dverts), _ptr(dtrans)), "smalfit_scan_sequence_vertex_term")
+        out.update(losses=losses, dverts=dverts, dtrans=dtrans)
+        return out
 
 
 def _narrowest(names, *blocks):

@@ -6,7 +6,8 @@ Same arguments and YAML layout (`stages: {name: {scheme, nits, lr, loss_weights,
 the command line) as fitter_3d/optimise.py:18-90 and fitter_3d/example_cfg.yaml.  Beyond the reference, opt-in: --metrics,
 --scan_index, --prealign (YAML `args: {prealign: true}`) with --prealign_trim_point / --prealign_trim_vert, and scan sequences:
 --sequence (YAML `args: {sequence: true}`) or --clip_lengths L ... make the meshes clips of one animal each, with one shape per
-clip and, per stage, `share_shape:` and a `temporal: {w_temp_joint, w_temp_global, w_temp_trans}` block.
+clip and, per stage, `share_shape:`, a `temporal: {w_temp_joint, w_temp_global, w_temp_trans}` block and a
+`temporal_verts: {w_temp_vert_vel, w_temp_vert_acc}` block (velocity and acceleration of the posed vertices).
 
 The order of a sequence: with --sequence or --clip_lengths the .obj files are taken in ascending order of their file names (Python's
 `sorted`: zero-pad the frame numbers), then every --frame_step'th of them; that is the batch order, and batch order within a clip

@@ -138,7 +138,7 @@ class Stage:
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes, mesh_names=[],
                  name="optimise", loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None,
                  device="cuda", seed=0, iteration_offset=0, scan_index=False, clip_lengths=None, share_shape=True, temporal=None,
-                 surface_gates=None, chamfer_gates=None, robust=None):
+                 temporal_verts=None, surface_gates=None, chamfer_gates=None, robust=None):
         self.n_it = int(nits)
         self.name = name
         self.out_dir = out_dir
@@ -192,6 +192,14 @@ class Stage:
         self._sequence = None
         self._seq_args = None          # smalfit_sequence_args of step(), built on the first step
         self._seq_losses = None
+        # ... and the velocity and acceleration terms on the posed vertices of a clip; both weights 0 unless given, and then
+        # evaluations and steps are the calls of before
+        self.temporal_verts = eng.temporal_vertex_weights(temporal_verts)
+        self._vert_args = None         # smalfit_sequence_vertex_args of step(), built on the first step while a weight is positive
+        self._vert_losses = None
+        self._vert_out = None
+        if temporal_verts is not None and self.clip_lengths is None:
+            raise ValueError("temporal_verts ties the posed vertices within a clip: give clip_lengths with it")
         if self.clip_lengths is not None:
             self._sequence = eng.ScanSequence(self.clip_lengths, fit.batch_size)
             if self.share_shape and "betas" in self._adam:
@@ -303,6 +311,15 @@ class Stage:
         step; None without clip_lengths"""
         return self._seq_losses
 
+    @property
+    def last_temporal_vertex_losses(self):
+        """device tensor (3,): the velocity and acceleration terms on the posed vertices and their sum, of the most recent
+        evaluation or step; None while both weights are off"""
+        return self._vert_losses
+
+    def _vertex_terms_on(self):
+        return self._sequence is not None and eng.temporal_vertex_on(self.temporal_verts)
+
     def _chamfer_gated(self):
         return self.chamfer_gates_on and self.loss_weights["w_chamfer"] > 0
 
@@ -361,6 +378,12 @@ class Stage:
             o["dtrans"] += sf["dtrans"]
             self._surface_losses = sf["losses"]
             total = total + sf["losses"][2]
+        if self._vertex_terms_on():
+            # the stand-alone call's gradient joins where the surface term's does, behind it
+            self._vert_out = self._sequence.vertex_term(o["verts"], self.temporal_verts, out=self._vert_out)
+            o["dverts"] += self._vert_out["dverts"]
+            o["dtrans"] += self._vert_out["dtrans"]
+            self._vert_losses = self._vert_out["losses"]
         dbeta, dtheta, dls = e.lbs_backward(betas, theta, ls, o["dverts"], None)
         if self._sequence is not None:
             # the coupling alone on the gradients of the trained parameters, where the fused step applies it: behind the LBS adjoint
@@ -371,6 +394,8 @@ class Stage:
                 g_trans=o["dtrans"] if "trans" in self._adam else None, share_shape=self.share_shape, temporal=self.temporal,
                 losses=self._seq_losses)
             total = total + self._seq_losses[3]
+            if self._vertex_terms_on():
+                total = total + self._vert_losses[2]
         grads = {"betas": dbeta, "global_rot": dtheta[:, 0].contiguous(), "joint_rot": dtheta[:, 1:].contiguous(),
                  "log_beta_scales": dls, "trans": o["dtrans"], "deform_verts": o["dverts"]}
         return total, grads
@@ -403,6 +428,15 @@ class Stage:
         if self._sequence is not None:
             # a scan sequence: the widest step, with the sequence block behind the four others
             q = self._sequence_block()
+            if self._vertex_terms_on():
+                # ... and the vertex block behind that
+                vq = self._vertex_block()
+                name = "smalfit_scan_sequence_vertex_step"
+                eng.check(_lib.resolve(e.lib, name)(self._sequence.handle, e.handle, self._objective.handle, dev_targets.handle,
+                                                    eng._stream(), C.byref(a), *eng._refs((sf, gate, cgate, rb)), C.byref(q),
+                                                    C.byref(vq)), name)
+                self._last_points = self._points
+                return self._vert_total[0]
             name = "smalfit_scan_sequence_step"
             eng.check(_lib.resolve(e.lib, name)(self._sequence.handle, e.handle, self._objective.handle, dev_targets.handle, eng._stream(),
                                                 C.byref(a), *eng._refs((sf, gate, cgate, rb)), C.byref(q)), name)
@@ -514,6 +548,15 @@ class Stage:
             self._seq_args, _ = self._sequence.block(self.share_shape, self.temporal, self._seq_step_losses, self._seq_total)
         self._seq_losses = self._seq_step_losses
         return self._seq_args
+
+    def _vertex_block(self):
+        """the smalfit_sequence_vertex_args of step(): the stage's two weights, the three figures, the grand total"""
+        if self._vert_args is None:
+            self._vert_step_losses = torch.zeros(3, device=self.device)
+            self._vert_total = torch.zeros(1, device=self.device)
+            self._vert_args, _ = self._sequence.vertex_block(self.temporal_verts, self._vert_step_losses, self._vert_total)
+        self._vert_losses = self._vert_step_losses
+        return self._vert_args
 
     def _robust_block(self):
         """the smalfit_robust_args of step(): the stage's scales, the weight sums of both terms"""
